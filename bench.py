@@ -40,6 +40,8 @@ LINE = 128                       # bytes the fabric MOVES for one gather: every 
 TB_STRIDE = 32                   # io::Cigar elements kept per read by the traceback stage
 SEED_KERNEL_TAG = "fm_seed_pipe_kernel<4>"            # the per-strand pass (--no-canonical)
 SEED_BOTH_KERNEL_TAG = "fm_seed_both_kernel<4, false, %s, %s>"   # the two-strand pass over the canonical table (default): % wide entries, deferred heavy searches
+DUMP_BYTES = 64 * 10 ** 6            # --dump-outputs: bound on the bytes written (arrays + .npy headers)
+DUMP_SAMPLE_SEED = 20261015          # --dump-outputs: seed of the read sample taken when the whole batch does not fit
 
 
 def log(msg):
@@ -384,6 +386,35 @@ def event_ms(pairs):
     return [a.elapsed_time(b) for a, b in pairs]
 
 
+def dump_outputs(torch, np, out_dir, R, per_read, scalars):
+    """--dump-outputs: write the timed step's results as out_dir/<name>.npy, float64 (exact for every value here: int32 scores, int64
+    positions < 2^53, small codes).  per_read: (name, tensor whose leading dimension is the read); scalars: name -> number.  When all R
+    reads do not fit in DUMP_BYTES, a fixed sample of them (seeded, sorted, the same for every run with the same arguments) is written,
+    its read ids in read_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                                        # bytes of a .npy header (version 1.0, these shapes)
+    per_read_elems = 1 + sum(t.numel() // max(R, 1) for _, t in per_read)          # + read_index
+    room = DUMP_BYTES - header * (1 + len(per_read) + len(scalars)) - 8 * len(scalars)
+    k = min(R, room // (8 * per_read_elems))
+    if k < R:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(R, k, replace=False))
+    else:
+        idx = np.arange(R)
+    idx_t = torch.from_numpy(idx).to(per_read[0][1].device)
+    arrays = {"read_index": idx.astype(np.float64)}
+    for name, t in per_read:
+        arrays[name] = t.index_select(0, idx_t).to(torch.float64).cpu().numpy()
+    for name, v in scalars.items():
+        arrays[name] = np.array([v], dtype=np.float64)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= DUMP_BYTES, "dump of %d bytes exceeds the bound of %d" % (total, DUMP_BYTES)
+    log("outputs of the last timed step: %d of %d reads, %d arrays, %.1f MB -> %s" % (k, R, len(arrays), total / 1e6, out_dir))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -437,7 +468,14 @@ def main():
     ap.add_argument("--robust-copies", type=int, default=10000, help="copies of the 300 bp element planted for the robust-input step")
     ap.add_argument("--repeat-family", type=int, default=0, metavar="COPIES",
                     help="plant COPIES copies of a random 300 bp element in the reference (and draw 5 %% of the reads from them): a repeat-rich workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's batch) as DIR/<name>.npy in float64; "
+                         "at most %d MB in all: a fixed, seeded sample of the reads when the batch is larger (DIR/read_index.npy)" % (DUMP_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import numpy as np
     import torch
@@ -578,6 +616,15 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # ---- what the last timed step returned to its caller (not timed) ----
+    if args.dump_outputs and rank == 0:
+        per_read = [("best_score", bs), ("best_pos", bp), ("best_rc", brc)]
+        if "mapq" in extras:
+            per_read += [("mapq", extras["mapq"]), ("second_score", extras["second_score"])]
+        if "traceback" in extras:
+            per_read += [("tb_" + k, v) for k, v in zip(("score", "align_pos", "source", "sink", "cigar", "cigar_len"), extras["traceback"])]
+        dump_outputs(torch, np, args.dump_outputs, R, per_read, {"n_candidates": int(nc)})
 
     # ---- quality of the result (not timed): reads aligned, and aligned where they came from ----
     aligned = bs >= min_score

@@ -23,6 +23,9 @@ Fixtures:
                   matrix) and by its full-matrix edit-distance aligner.
   tb_golden.npz   the same pairs traced back by the reference (banded_alignment_traceback, bands
                   3/7/15/31 x 3 types): score, source, sink and the run-length CIGAR.
+  ref_fuzz_golden.npz  what the reference returned to every call of tests/test_oracle_vs_reference.py, per
+                  test and function in call order, with a crc32 of each call's inputs: the fixture `ref`
+                  replays it where oracle/_ref is not built.  Rewrite it whenever those tests change.
 """
 import os
 import sys
@@ -644,6 +647,26 @@ def make_fswtb(R):
     print("fswtb_golden.npz: %d cases, %d traced, %d cigar elements" % (len(cases), int(out[:, 0].sum()), int(co[-1])))
 
 
+def make_ref_fuzz(R):
+    """run every test of tests/test_oracle_vs_reference.py against the live reference, recording what it returns"""
+    import importlib.util
+    sys.path.insert(0, os.path.dirname(HERE))
+    import util
+    spec = importlib.util.spec_from_file_location("test_oracle_vs_reference", os.path.join(os.path.dirname(HERE), "test_oracle_vs_reference.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    O = oracle.Oracle()
+    logs = {}
+    for name in sorted(n for n in dir(mod) if n.startswith("test_")):
+        rec = util.RecordingReference(R)
+        getattr(mod, name)(O, rec)
+        logs[name] = rec.log
+    path = os.path.join(HERE, util.REF_RECORDING)
+    util.save_recordings(path, logs)
+    print("%s: %d tests, %d calls, %d bytes" % (util.REF_RECORDING, len(logs), sum(len(c) for l in logs.values() for c in l.values()),
+                                              os.path.getsize(path)))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:                                            # python make_golden.py fswtb swtb ...: only these
         R = oracle.Reference()
@@ -667,3 +690,4 @@ if __name__ == "__main__":
     make_staged(R)
     make_swtb(R)
     make_fswtb(R)
+    make_ref_fuzz(R)

@@ -18,7 +18,9 @@ def _declared():
 
 def test_header_symbols_are_exported():
     amd = ge.load_package()
-    L = ctypes.CDLL(amd.LIB_PATH)
+    # through lib(), which loads torch's HIP runtime first: a bare CDLL as the first load binds the library to another runtime
+    # for the rest of the process, and on a GPU every later test in it then sees NVBIO_ERR_NO_DEVICE
+    L = amd.lib()
     names = _declared()
     assert len(names) >= 18
     missing = [n for n in names if not hasattr(L, n)]

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,3 +80,28 @@ def test_bench_json_contract(extra):
         assert rb["ms_per_step"] > 0 and rb["plain_operators"]["results_equal"] is True and rb["aligned_fraction"] > 0.97
     else:
         assert "robust" not in d
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's results; --steps sets the timed steps, and the inputs (hence the results) do not
+    depend on how many steps ran"""
+    lean = ["--no-cpu-baseline", "--no-sweep", "--no-configs", "--no-nvbowtie-mode", "--no-robust", "--no-plain-ab", "--no-traceback",
+            "--no-overlap-leg"]
+    dumps = []
+    for steps in (1, 3):
+        d = str(tmp_path / ("steps%d" % steps))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ref-len", "4e6", "--reads", "40000", "--steps", str(steps),
+                              "--warmup", "1", "--kmer", "15", "--dump-outputs", d] + lean, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert r["steps"] == steps and len(r["stage_ms"]) > 0
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 10 ** 6
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+        assert dumps[-1]["n_candidates"][0] == r["extend"]["candidates_per_step"]
+        got = dumps[-1]
+        assert got["best_score"].shape == (40000,) and got["best_score"].dtype == np.float64
+        assert np.array_equal(got["read_index"], np.arange(40000))
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["best_pos", "best_rc", "best_score", "mapq", "n_candidates", "read_index", "second_score"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)

@@ -1,5 +1,6 @@
-"""Live fuzz of the oracle against the reference's own host code (oracle/_ref, built from
-/root/reference by oracle/Makefile).  Skipped where the reference is not present (GPU box)."""
+"""Fuzz of the oracle against the reference's own host code: live where oracle/_ref is built (oracle/Makefile, from the
+reference sources), elsewhere against what that code returned for the same calls (tests/golden/ref_fuzz_golden.npz, the
+fixture `ref`).  Regenerate the recording with tests/golden/make_golden.py whenever these tests change."""
 import numpy as np
 
 import oracle
