@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <string.h>
+#include <vector>
 
 #include "../../include/nvbio_amd.h"
 
@@ -30,15 +31,96 @@ const char* get_error();
 #define NVB_REQUIRE(cond, msg)                                                                     \
     do { if (!(cond)) { nvbio_amd::set_error("invalid argument: %s", msg); return NVBIO_ERR_INVALID; } } while (0)
 
-// Scratch with stream-ordered semantics WITHOUT the runtime's stream-ordered pool: a block handed out by scratch_alloc may be used by work enqueued on
-// `s` after the call; scratch_free gives it back at once, for the next call on the SAME stream (whose work runs behind everything that used the block).
-// Blocks are plain hipMalloc allocations cached per (device, stream).  Why not hipMallocAsync / hipFreeAsync: on ROCm 7.2 a block RE-used from the
-// default pool did not hold what a kernel had just written into it -- the flags of the banded scorer's first pass read back as zeros in the second
-// call of a process (seen with hipMemcpy right behind the kernel; with hipMalloc / hipFree in its place: never), and once in a few fresh-box runs the
-// gap chance read zeros there in production (61,818 reads of 10 M scored -20 instead of -18).  core.hip.
-hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t s);
-void       scratch_free(void* p, hipStream_t s);
-void       scratch_release_idle();                        // hipFree every idle block (each behind a synchronisation of its stream)
+// Scratch with stream-ordered semantics WITHOUT the runtime's stream-ordered pool: a block taken by a ScratchBlock may be used by work enqueued on
+// `s` after the call; the ScratchBlock's destruction gives it back at once, for the next call on the SAME stream (whose work runs behind everything
+// that used the block).  Blocks are plain hipMalloc allocations cached per (device, stream).  Why not hipMallocAsync / hipFreeAsync: on ROCm 7.2 a
+// block RE-used from the default pool did not hold what a kernel had just written into it -- the flags of the banded scorer's first pass read back as
+// zeros in the second call of a process (seen with hipMemcpy right behind the kernel; with hipMalloc / hipFree in its place: never), and once in a few
+// fresh-box runs the gap chance read zeros there in production (61,818 reads of 10 M scored -20 instead of -18).  core.hip.
+void scratch_release_idle();                              // hipFree every idle block (each behind a synchronisation of its stream)
+
+// The sub-arrays of one scratch block in order, declared once per site by code that runs twice: over ScratchLayout() it only adds up their
+// sizes, over ScratchLayout( block ) it also hands out their pointers.  Every sub-array starts on a 256-byte boundary (hipcub temporaries need that).
+class ScratchLayout
+{
+public:
+    explicit ScratchLayout(uint8_t* base = nullptr) : base_( base ) {}
+    template <typename T> T* take(uint64_t count)
+    {
+        const uint64_t at = round( end_ );
+        end_ = at + count * sizeof(T);
+        return base_ ? (T*)(base_ + at) : nullptr;
+    }
+    uint64_t end() const   { return end_; }                      // the bytes a block must hold
+    uint64_t bytes() const { return round( end_ ) + 256u; }      // the bytes a caller's buffer must hold: room to align its start
+private:
+    static uint64_t round(uint64_t x) { return (x + 255u) & ~255ull; }
+    uint8_t* base_;
+    uint64_t end_ = 0;
+};
+
+// The scratch of one call: a block of the cache above for stream `s` (alloc), or the caller's temp_dev (adopt).  Only a block it took from the
+// cache is given back, when it goes out of scope -- so every exit of the call gives it back.
+class ScratchBlock
+{
+public:
+    ScratchBlock() = default;
+    ScratchBlock(ScratchBlock&& o) noexcept : p_( o.p_ ), s_( o.s_ ), own_( o.own_ ) { o.p_ = nullptr; o.own_ = false; }
+    ScratchBlock& operator=(ScratchBlock&& o) noexcept
+    {
+        if (this != &o) { release(); p_ = o.p_; s_ = o.s_; own_ = o.own_; o.p_ = nullptr; o.own_ = false; }
+        return *this;
+    }
+    ScratchBlock(const ScratchBlock&) = delete;
+    ScratchBlock& operator=(const ScratchBlock&) = delete;
+    ~ScratchBlock() { release(); }
+
+    // `bytes` of the cache for work on `s`; out of memory: the message printf( fmt, ... ) and NVBIO_ERR_NOMEM
+    nvbio_status alloc(uint64_t bytes, hipStream_t s, const char* fmt, ...);
+    // the block for the sub-arrays that layout( ScratchLayout& ) declares, run once to size it and once to set the site's pointers into it:
+    // alloc (msg: a format given the block's bytes as unsigned long long), or adopt when the caller passes its temp (sized by `query`)
+    template <typename Layout>
+    nvbio_status alloc_layout(hipStream_t s, const char* msg, Layout layout, void* temp = nullptr, uint64_t temp_bytes = 0, const char* query = nullptr)
+    {
+        ScratchLayout size; layout( size );
+        NVB_CHECK( temp ? adopt( temp, temp_bytes, size.end(), query ) : alloc( size.end(), s, msg, (unsigned long long)size.end() ) );
+        ScratchLayout c( p_ ); layout( c );
+        return NVBIO_OK;
+    }
+    uint8_t* get() const { return p_; }
+
+private:
+    // the caller's `temp_bytes` at `temp`, its start aligned up to 256, of which `bytes` must remain: else "temp_bytes too small (<query>)"
+    // and NVBIO_ERR_INVALID
+    nvbio_status adopt(void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query);
+    void release();
+    uint8_t*    p_   = nullptr;
+    hipStream_t s_   = nullptr;
+    bool        own_ = false;
+};
+
+// RAII for the hipMalloc temporaries of an index build (not the stream scratch above): every buffer it allocated and was not told to
+// forget (ownership handed over) is freed when it goes out of scope
+struct BuildBuffers
+{
+    std::vector<void*> ptrs;
+    ~BuildBuffers() { for (void* p : ptrs) (void)hipFree( p ); }
+    template <typename T> T* alloc(size_t count)            // nullptr when out of memory
+    {
+        void* p = nullptr;
+        if (hipMalloc( &p, (count ? count : 1) * sizeof(T) ) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        ptrs.push_back( p );
+        return (T*)p;
+    }
+    void release(void* p)
+    {
+        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { (void)hipFree( p ); ptrs.erase( ptrs.begin() + i ); return; }
+    }
+    void forget(void* p)
+    {
+        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase( ptrs.begin() + i ); return; }
+    }
+};
 
 // select the device and fail loudly if it is not a gfx950: there is no CPU fallback
 nvbio_status use_device(int device);

@@ -18,10 +18,30 @@ const char* get_error() { return g_error; }
 
 // ---- scratch blocks cached per (device, stream): see common.h ----
 namespace {
-struct ScratchBlock { void* p; size_t cap; bool busy; int device; hipStream_t stream; };
+struct CachedBlock { void* p; size_t cap; bool busy; int device; hipStream_t stream; };
 std::mutex                 g_scratch_mutex;
-std::vector<ScratchBlock>  g_scratch;
+std::vector<CachedBlock>   g_scratch;
 const size_t SCRATCH_KEEP_PER_STREAM = 32ull << 30;             // idle blocks beyond this are released (after the stream has drained)
+
+// hipFree the idle blocks `match` selects, each behind a synchronisation of its own stream (work behind which the block was given back may still
+// use it); the caller holds the mutex
+template <typename Match>
+void release_idle(Match match)
+{
+    int prev = -1; (void)hipGetDevice( &prev );
+    for (size_t i = 0; i < g_scratch.size(); )
+    {
+        const CachedBlock& b = g_scratch[i];
+        if (!b.busy && match( b ))
+        {
+            (void)hipSetDevice( b.device );
+            (void)hipStreamSynchronize( b.stream );
+            (void)hipFree( b.p );
+            g_scratch.erase( g_scratch.begin() + i );
+        }
+        else ++i;
+    }
+    if (prev >= 0) (void)hipSetDevice( prev );
 }
 
 hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t s)
@@ -37,7 +57,7 @@ hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t s)
     int best = -1;
     for (size_t i = 0; i < g_scratch.size(); ++i)
     {
-        const ScratchBlock& b = g_scratch[i];
+        const CachedBlock& b = g_scratch[i];
         if (!b.busy && b.device == dev && b.stream == s && b.cap >= want && (best < 0 || b.cap < g_scratch[best].cap)) best = (int)i;
     }
     if (best >= 0) { g_scratch[best].busy = true; *p = g_scratch[best].p; return hipSuccess; }
@@ -45,57 +65,69 @@ hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t s)
     e = hipMalloc( &q, want );
     if (e != hipSuccess)
     {
-        // out of memory: give this stream's idle blocks back (its work may still use them: drain it first) and try once more
+        // out of memory: give every idle block of the device back (of any stream, each once its stream has drained) and try once more
         (void)hipGetLastError();
-        (void)hipStreamSynchronize( s );
-        for (size_t i = 0; i < g_scratch.size(); )
-        {
-            if (!g_scratch[i].busy && g_scratch[i].device == dev) { (void)hipFree( g_scratch[i].p ); g_scratch.erase( g_scratch.begin() + i ); }
-            else ++i;
-        }
+        release_idle( [dev](const CachedBlock& b) { return b.device == dev; } );
         e = hipMalloc( &q, want );
         if (e != hipSuccess) return e;
     }
-    g_scratch.push_back( ScratchBlock{ q, want, true, dev, s } );
+    g_scratch.push_back( CachedBlock{ q, want, true, dev, s } );
     *p = q;
     return hipSuccess;
+}
+
+void scratch_free(void* p, hipStream_t s)
+{
+    std::lock_guard<std::mutex> lock( g_scratch_mutex );
+    size_t idle = 0; int dev = -1;
+    for (CachedBlock& b : g_scratch)
+        if (b.p == p) { b.busy = false; dev = b.device; }
+    for (const CachedBlock& b : g_scratch) if (!b.busy && b.device == dev && b.stream == s) idle += b.cap;
+    if (idle > SCRATCH_KEEP_PER_STREAM)
+        release_idle( [dev, s](const CachedBlock& b) { return b.device == dev && b.stream == s; } );
+}
 }
 
 void scratch_release_idle()
 {
     std::lock_guard<std::mutex> lock( g_scratch_mutex );
-    int prev = -1; (void)hipGetDevice( &prev );
-    for (size_t i = 0; i < g_scratch.size(); )
-    {
-        if (!g_scratch[i].busy)
-        {
-            (void)hipSetDevice( g_scratch[i].device );
-            (void)hipStreamSynchronize( g_scratch[i].stream );   // work behind which the block was given back may still use it
-            (void)hipFree( g_scratch[i].p );
-            g_scratch.erase( g_scratch.begin() + i );
-        }
-        else ++i;
-    }
-    if (prev >= 0) (void)hipSetDevice( prev );
+    release_idle( [](const CachedBlock&) { return true; } );
 }
 
-void scratch_free(void* p, hipStream_t s)
+nvbio_status ScratchBlock::alloc(uint64_t bytes, hipStream_t s, const char* fmt, ...)
 {
-    if (!p) return;
-    std::lock_guard<std::mutex> lock( g_scratch_mutex );
-    size_t idle = 0; int dev = -1;
-    for (ScratchBlock& b : g_scratch)
-        if (b.p == p) { b.busy = false; dev = b.device; }
-    for (const ScratchBlock& b : g_scratch) if (!b.busy && b.device == dev && b.stream == s) idle += b.cap;
-    if (idle > SCRATCH_KEEP_PER_STREAM)
+    release();
+    void* p = nullptr;
+    if (scratch_alloc( &p, bytes, s ) != hipSuccess)
     {
-        (void)hipStreamSynchronize( s );                          // work behind which the idle blocks were given back may still read them
-        for (size_t i = 0; i < g_scratch.size(); )
-        {
-            if (!g_scratch[i].busy && g_scratch[i].device == dev && g_scratch[i].stream == s) { (void)hipFree( g_scratch[i].p ); g_scratch.erase( g_scratch.begin() + i ); }
-            else ++i;
-        }
+        (void)hipGetLastError();
+        va_list ap;
+        va_start( ap, fmt );
+        vsnprintf( g_error, sizeof(g_error), fmt, ap );
+        va_end( ap );
+        return NVBIO_ERR_NOMEM;
     }
+    p_ = (uint8_t*)p; s_ = s; own_ = true;
+    return NVBIO_OK;
+}
+
+nvbio_status ScratchBlock::adopt(void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query)
+{
+    release();
+    const uint64_t skip = (256u - ((uintptr_t)temp & 255u)) & 255u;
+    if (temp == nullptr || temp_bytes < skip || temp_bytes - skip < bytes)
+    {
+        set_error( "invalid argument: temp_bytes too small (%s)", query );
+        return NVBIO_ERR_INVALID;
+    }
+    p_ = (uint8_t*)temp + skip;
+    return NVBIO_OK;
+}
+
+void ScratchBlock::release()
+{
+    if (own_) scratch_free( p_, s_ );
+    p_ = nullptr; own_ = false;
 }
 
 nvbio_status use_device(int device)
@@ -127,7 +159,7 @@ nvbio_status use_device(int device)
         set_error( "hipSetDevice(%d) failed", device );
         return NVBIO_ERR_HIP;
     }
-    // (scratch -- boundary columns, direction vectors, scan temporaries -- comes from scratch_alloc above, not from the runtime's stream-ordered pool)
+    // (scratch -- boundary columns, direction vectors, scan temporaries -- comes from the ScratchBlock cache above, not from the runtime's stream-ordered pool)
     return NVBIO_OK;
 }
 

@@ -241,34 +241,13 @@ ssa_kernel(const uint32_t* __restrict__ sa, const uint32_t sa_int, const uint64_
         ssa[j] = (j == 0) ? 0xFFFFFFFFu : sa[(size_t)sa_int * j - 1u];  // row sa_int*j of the full SA
 }
 
-// ---- small RAII for device scratch ----------------------------------------------------------
-struct Scratch
-{
-    std::vector<void*> ptrs;
-    ~Scratch() { for (void* p : ptrs) (void)hipFree( p ); }
-    template <typename T> T* alloc(size_t count)
-    {
-        void* p = nullptr;
-        if (hipMalloc( &p, (count ? count : 1) * sizeof(T) ) != hipSuccess) return nullptr;
-        ptrs.push_back( p );
-        return (T*)p;
-    }
-    void release(void* p)
-    {
-        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { (void)hipFree( p ); ptrs.erase( ptrs.begin() + i ); return; }
-    }
-    void forget(void* p)
-    {
-        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase( ptrs.begin() + i ); return; }
-    }
-};
-
+// ---- index-build temporaries (BuildBuffers, common.h) ------------------------------------------
 #define NVB_ALLOC(var, T, count)                                                                   \
-    T* var = scratch.alloc<T>( count );                                                            \
+    T* var = bufs.alloc<T>( count );                                                               \
     if (!var) { set_error( "index build: out of device memory (%s, %zu bytes)", #var, (size_t)(count) * sizeof(T) ); return NVBIO_ERR_NOMEM; }
 
 // inclusive max-scan in place, in chunks small enough for 32-bit-sized device primitives
-static nvbio_status scan_max_inplace(uint32_t* buf, uint64_t n, Scratch& scratch, hipStream_t s)
+static nvbio_status scan_max_inplace(uint32_t* buf, uint64_t n, BuildBuffers& bufs, hipStream_t s)
 {
     const uint64_t CHUNK = 1ull << 30;
     size_t temp_bytes = 0;
@@ -280,13 +259,13 @@ static nvbio_status scan_max_inplace(uint32_t* buf, uint64_t n, Scratch& scratch
         if (b) hipLaunchKernelGGL( patch_first_kernel, dim3(1), dim3(1), 0, s, buf + b, buf + b - 1 );
         NVB_HIP( rocprim::inclusive_scan( temp, temp_bytes, buf + b, buf + b, len, MaxU32(), s ) );
     }
-    scratch.release( temp );
+    bufs.release( temp );
     return NVBIO_OK;
 }
 
 // out[0..count) = { i in [0,n) : pred(i) } in increasing order, chunked; *count on the host
 template <typename Pred>
-static nvbio_status select_indices(const uint64_t n, Pred pred, uint32_t* out, uint64_t* count, Scratch& scratch, hipStream_t s)
+static nvbio_status select_indices(const uint64_t n, Pred pred, uint32_t* out, uint64_t* count, BuildBuffers& bufs, hipStream_t s)
 {
     const uint64_t CHUNK = 1ull << 30;
     NVB_ALLOC( d_cnt, size_t, 1 );
@@ -305,19 +284,19 @@ static nvbio_status select_indices(const uint64_t n, Pred pred, uint32_t* out, u
         total += c;
     }
     *count = total;
-    scratch.release( temp ); scratch.release( d_cnt );
+    bufs.release( temp ); bufs.release( d_cnt );
     return NVBIO_OK;
 }
 
 static nvbio_status sort_pairs(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n,
-                               unsigned begin_bit, unsigned end_bit, Scratch& scratch, hipStream_t s)
+                               unsigned begin_bit, unsigned end_bit, BuildBuffers& bufs, hipStream_t s)
 {
     size_t temp_bytes = 0;
     NVB_HIP( rocprim::radix_sort_pairs( nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, s ) );
     NVB_ALLOC( temp, uint8_t, temp_bytes );
     NVB_HIP( rocprim::radix_sort_pairs( temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, s ) );
     NVB_HIP( hipStreamSynchronize( s ) );
-    scratch.release( temp );
+    bufs.release( temp );
     return NVBIO_OK;
 }
 
@@ -325,7 +304,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
                                const uint32_t sa_int, uint32_t max_lcp, const bool verify, const uint32_t table_flags, const uint32_t bucket_symbols,
                                hipStream_t s, nvbio_fm_index_t* out)
 {
-    Scratch scratch;
+    BuildBuffers bufs;
     if (max_lcp == 0) max_lcp = 4096;
     if (max_lcp > (1u << 20)) max_lcp = 1u << 20;
     if (max_lcp > 0xFFFFFFFFu - n - 64u) max_lcp = 0xFFFFFFFFu - n - 64u;       // rank + h must not wrap
@@ -347,7 +326,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
         hipLaunchKernelGGL( bucket_histogram_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, t, bshift, d_hist );
         NVB_HIP( hipMemcpyAsync( hist.data(), d_hist, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s ) );
         NVB_HIP( hipStreamSynchronize( s ) );
-        scratch.release( d_hist );
+        bufs.release( d_hist );
     }
     else hist[0] = n;
     uint32_t max_bucket = 0;
@@ -373,11 +352,11 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
             {
                 uint64_t cnt = 0;
                 InBucket pred; pred.t = t; pred.shift = bshift; pred.bucket = b;
-                NVB_CHECK( select_indices( n, pred, b_idx, &cnt, scratch, s ) );
+                NVB_CHECK( select_indices( n, pred, b_idx, &cnt, bufs, s ) );
                 if (cnt != nb) { set_error( "index build: bucket %u size mismatch (%llu vs %u)", b, (unsigned long long)cnt, nb ); return NVBIO_ERR_HIP; }
                 KeyOf kf; kf.t = t;
                 NVB_HIP( rocprim::transform( b_idx, b_keys, (size_t)nb, kf, s ) );
-                NVB_CHECK( sort_pairs( b_keys, keys + offset, idx_in, sa + offset, nb, 0, bshift, scratch, s ) );
+                NVB_CHECK( sort_pairs( b_keys, keys + offset, idx_in, sa + offset, nb, 0, bshift, bufs, s ) );
             }
             else
             {
@@ -390,25 +369,25 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
                 NVB_ALLOC( temp, uint8_t, temp_bytes );
                 NVB_HIP( rocprim::radix_sort_pairs( temp, temp_bytes, keys_in, keys, vals_in, sa, (size_t)n, 0u, 64u, s ) );
                 NVB_HIP( hipStreamSynchronize( s ) );
-                scratch.release( temp );
+                bufs.release( temp );
             }
             offset += nb;
         }
-        scratch.release( b_idx ); scratch.release( b_keys );
+        bufs.release( b_idx ); bufs.release( b_keys );
     }
 
     // ---- 2. finish tied suffixes by prefix doubling on the unresolved set --------------------
     NVB_ALLOC( seg, uint32_t, n );           // head slot of the segment each slot belongs to
     hipLaunchKernelGGL( head_from_keys_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, (const uint64_t*)keys, (uint64_t)n, seg );
     NVB_HIP( hipGetLastError() );
-    scratch.release( keys );
-    NVB_CHECK( scan_max_inplace( seg, n, scratch, s ) );
+    bufs.release( keys );
+    NVB_CHECK( scan_max_inplace( seg, n, bufs, s ) );
 
     uint64_t m = 0;
     NVB_ALLOC( U, uint32_t, n );             // unresolved slots (upper bound n; usually tiny)
     {
         Unresolved pred; pred.seg = seg; pred.n = n;
-        NVB_CHECK( select_indices( n, pred, U, &m, scratch, s ) );
+        NVB_CHECK( select_indices( n, pred, U, &m, bufs, s ) );
     }
     if (m > 0)
     {
@@ -432,16 +411,16 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
             const uint32_t mm = (uint32_t)m;
             hipLaunchKernelGGL( doubling_keys_kernel, dim3( grid_for( mm ) ), dim3(256), 0, s,
                                 (const uint32_t*)U, mm, (const uint32_t*)sa, (const uint32_t*)seg, (const uint32_t*)rank, n, h, key2, val );
-            NVB_CHECK( sort_pairs( key2, key2s, val, vals, mm, 0, 64, scratch, s ) );
+            NVB_CHECK( sort_pairs( key2, key2s, val, vals, mm, 0, 64, bufs, s ) );
             hipLaunchKernelGGL( doubling_place_kernel, dim3( grid_for( mm ) ), dim3(256), 0, s,
                                 (const uint32_t*)U, mm, (const uint64_t*)key2s, (const uint32_t*)vals, sa, newseg );
-            NVB_CHECK( scan_max_inplace( newseg, mm, scratch, s ) );
+            NVB_CHECK( scan_max_inplace( newseg, mm, bufs, s ) );
             hipLaunchKernelGGL( doubling_update_kernel, dim3( grid_for( mm ) ), dim3(256), 0, s,
                                 (const uint32_t*)U, mm, (const uint32_t*)newseg, (const uint32_t*)vals, seg, rank );
             NVB_HIP( hipGetLastError() );
             uint64_t m2 = 0;
             StillUnresolvedU pred; pred.U = U; pred.newseg = newseg; pred.m = mm;
-            NVB_CHECK( select_indices( mm, pred, sel, &m2, scratch, s ) );
+            NVB_CHECK( select_indices( mm, pred, sel, &m2, bufs, s ) );
             if (m2)
             {
                 hipLaunchKernelGGL( gather_u_kernel, dim3( grid_for( m2 ) ), dim3(256), 0, s, (const uint32_t*)U, (const uint32_t*)sel, (uint32_t)m2, U2 );
@@ -451,10 +430,10 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
             if (h > (1u << 30)) break;
             h *= 2;
         }
-        scratch.release( rank ); scratch.release( key2 ); scratch.release( key2s ); scratch.release( val );
-        scratch.release( vals ); scratch.release( newseg ); scratch.release( sel ); scratch.release( U2 );
+        bufs.release( rank ); bufs.release( key2 ); bufs.release( key2s ); bufs.release( val );
+        bufs.release( vals ); bufs.release( newseg ); bufs.release( sel ); bufs.release( U2 );
     }
-    scratch.release( U ); scratch.release( seg );
+    bufs.release( U ); bufs.release( seg );
 
     // ---- 3. BWT, occ, L2, SSA ---------------------------------------------------------------
     const uint32_t words    = ((t.n_words + 3u) & ~3u);          // padded to whole 64-symbol blocks
@@ -485,7 +464,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
     }
     NVB_HIP( hipGetLastError() );
     NVB_HIP( hipStreamSynchronize( s ) );
-    scratch.release( sa );
+    bufs.release( sa );
 
     NVB_ALLOC( cnt, uint4, (size_t)n_blocks + 1u );
     NVB_ALLOC( occ, uint4, (size_t)n_blocks + 1u );
@@ -497,7 +476,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
         NVB_ALLOC( temp, uint8_t, temp_bytes );
         NVB_HIP( rocprim::exclusive_scan( temp, temp_bytes, cnt, occ, make_uint4( 0, 0, 0, 0 ), (size_t)n_blocks + 1u, AddU4(), s ) );
         NVB_HIP( hipStreamSynchronize( s ) );
-        scratch.release( temp );
+        bufs.release( temp );
     }
     hipLaunchKernelGGL( write_occ_kernel, dim3( grid_for( n_blocks ) ), dim3(256), 0, s, (const uint4*)occ, n_blocks, bwt_occ );
     uint4    totals;
@@ -517,9 +496,9 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
         set_error( "index build: inconsistent result (sum of counts %u, n %u, primary %u)", view.L2[4], n, primary );
         return NVBIO_ERR_HIP;
     }
-    scratch.forget( bwt_occ ); scratch.forget( ssa );           // ownership moves to the handle
-    if (isa) scratch.forget( isa );
-    if (text_copy) scratch.forget( text_copy );
+    bufs.forget( bwt_occ ); bufs.forget( ssa );           // ownership moves to the handle
+    if (isa) bufs.forget( isa );
+    if (text_copy) bufs.forget( text_copy );
     return fm_index_adopt( &view, device, kmer_len, true, s, out, isa, text_copy, table_flags );
 }
 
@@ -542,7 +521,7 @@ struct FileCloser { FILE* f; ~FileCloser() { if (f) fclose( f ); } };
 static nvbio_status load_impl(const char* bwt_path, const char* sa_path, const int device, const uint32_t kmer_len,
                               hipStream_t s, nvbio_fm_index_t* out)
 {
-    Scratch scratch;
+    BuildBuffers bufs;
     // ---- .bwt: primary, cumulative counts (the last is the length), packed words (fmindex_impl.cu:111-170) ----
     FileCloser bf = { fopen( bwt_path, "rb" ) };
     if (!bf.f) { set_error( "unable to open bwt \"%s\"", bwt_path ); return NVBIO_ERR_INVALID; }
@@ -576,7 +555,7 @@ static nvbio_status load_impl(const char* bwt_path, const char* sa_path, const i
         NVB_ALLOC( temp, uint8_t, temp_bytes );
         NVB_HIP( rocprim::exclusive_scan( temp, temp_bytes, cnt, occ, make_uint4( 0, 0, 0, 0 ), (size_t)n_blocks + 1u, AddU4(), s ) );
         NVB_HIP( hipStreamSynchronize( s ) );
-        scratch.release( temp );
+        bufs.release( temp );
     }
     hipLaunchKernelGGL( write_occ_kernel, dim3( grid_for( n_blocks ) ), dim3(256), 0, s, (const uint4*)occ, n_blocks, bwt_occ );
     uint4 totals;
@@ -611,13 +590,13 @@ static nvbio_status load_impl(const char* bwt_path, const char* sa_path, const i
         ssa = d_ssa;
         view.ssa_dev = ssa; view.ssa_words = sa_size; view.sa_int = K;
     }
-    scratch.forget( bwt_occ ); if (ssa) scratch.forget( ssa );
+    bufs.forget( bwt_occ ); if (ssa) bufs.forget( ssa );
     return fm_index_adopt( &view, device, kmer_len, true, s, out, nullptr, nullptr, 0u );
 }
 
 static nvbio_status save_impl(const nvbio_fm_index_view& v, const char* bwt_path, const char* sa_path, hipStream_t s)
 {
-    Scratch scratch;
+    BuildBuffers bufs;
     const uint32_t n = v.length, n_words = (n + 15u) / 16u;
     NVB_ALLOC( d_bwt, uint32_t, n_words );
     hipLaunchKernelGGL( deinterleave_bwt_kernel, dim3( grid_for( n_words ) ), dim3(256), 0, s, v.bwt_occ_dev, n_words, d_bwt );

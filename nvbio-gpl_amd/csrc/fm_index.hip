@@ -1175,18 +1175,21 @@ static nvbio_status build_direct_table(FMIndexImpl* idx, uint2* tab, const uint6
     }
     const uint32_t n_tiles = (uint32_t)((entries + DT_TILE - 1u) / DT_TILE);
     const dim3 grid( n_tiles < 256u * 64u ? n_tiles : 256u * 64u ), block( 256 );
-    uint32_t* cnt = nullptr; void* temp = nullptr; uint2* side = nullptr;
+    BuildBuffers bufs;
+    uint32_t* cnt = nullptr; uint2* side = nullptr;
     size_t temp_bytes = 0;
     uint32_t tot_small = 0, tot_large = 0;
     const bool want_groups = !(idx->table_flags & NVBIO_FM_TABLE_NO_GROUPS);
     nvbio_status st = NVBIO_OK;
     if (want_groups)
     {
-        if (hipMalloc( (void**)&cnt, 4ull * n_tiles * sizeof(uint32_t) ) != hipSuccess) { (void)hipGetLastError(); set_error( "direct table: out of device memory" ); return NVBIO_ERR_NOMEM; }
+        cnt = bufs.alloc<uint32_t>( 4ull * n_tiles );
+        if (!cnt) { set_error( "direct table: out of device memory" ); return NVBIO_ERR_NOMEM; }
         uint32_t *cs = cnt, *cl = cnt + n_tiles, *os = cnt + 2ull * n_tiles, *ol = cnt + 3ull * n_tiles;
         hipLaunchKernelGGL( fm_dtab_count_kernel, grid, block, 0, stream, (const uint2*)tab, entries, n_tiles, cs, cl );
         hipError_t e = hipcub::DeviceScan::ExclusiveSum( nullptr, temp_bytes, cs, os, (int)n_tiles, stream );
-        if (e == hipSuccess) e = hipMalloc( &temp, temp_bytes ? temp_bytes : 16 );
+        void* temp = nullptr;
+        if (e == hipSuccess && !(temp = bufs.alloc<uint8_t>( temp_bytes ))) e = hipErrorOutOfMemory;
         if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( temp, temp_bytes, cs, os, (int)n_tiles, stream );
         if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( temp, temp_bytes, cl, ol, (int)n_tiles, stream );
         uint32_t last[4] = { 0, 0, 0, 0 };
@@ -1199,9 +1202,7 @@ static nvbio_status build_direct_table(FMIndexImpl* idx, uint2* tab, const uint6
         tot_small = last[0] + last[1]; tot_large = last[2] + last[3];
         const uint64_t units = 2ull * tot_large + tot_small;                  // groups in units of 4 slots (32 bytes)
         if (st == NVBIO_OK && units > 0 && units < (1ull << 30))
-        {
-            if (hipMalloc( (void**)&side, units * 32ull ) != hipSuccess) { (void)hipGetLastError(); side = nullptr; }   // no memory: no groups
-        }
+            side = bufs.alloc<uint2>( units * 4u );                          // no memory: no groups
     }
     if (st == NVBIO_OK)
     {
@@ -1209,9 +1210,8 @@ static nvbio_status build_direct_table(FMIndexImpl* idx, uint2* tab, const uint6
                             cnt ? cnt + 3ull * n_tiles : nullptr, tot_large, idx->view.ssa_dev, (const uint32_t*)idx->text, length, side );
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize( stream ) != hipSuccess) { set_error( "direct table: fill pass failed" ); st = NVBIO_ERR_HIP; }
     }
-    if (cnt)  (void)hipFree( cnt );
-    if (temp) (void)hipFree( temp );
-    if (st != NVBIO_OK) { if (side) (void)hipFree( side ); return st; }
+    if (st != NVBIO_OK) return st;
+    bufs.forget( side );
     idx->side = side; idx->dmark = DTAB_MARK; idx->dctx = DTAB_CTX;
     if (side) idx->owned_bytes += (2ull * tot_large + tot_small) * 32ull;
     return NVBIO_OK;
@@ -1230,9 +1230,10 @@ static nvbio_status build_canonical_tables(FMIndexImpl* idx, uint32_t k, hipStre
 {
     const uint32_t kk = k - 1u;
     const uint64_t entries = 1ull << (2 * kk);
-    uint2 *a = nullptr, *b = nullptr;
-    if (hipMalloc( (void**)&a, entries * sizeof(uint2) ) != hipSuccess) { (void)hipGetLastError(); set_error( "k-mer table: out of device memory" ); return NVBIO_ERR_NOMEM; }
-    if (hipMalloc( (void**)&b, (entries / 4) * sizeof(uint2) ) != hipSuccess) { (void)hipGetLastError(); (void)hipFree( a ); set_error( "k-mer table: out of device memory" ); return NVBIO_ERR_NOMEM; }
+    BuildBuffers bufs;
+    uint2* a = bufs.alloc<uint2>( entries );
+    uint2* b = a ? bufs.alloc<uint2>( entries / 4 ) : nullptr;
+    if (!b) { set_error( "k-mer table: out of device memory" ); return NVBIO_ERR_NOMEM; }
     uint2* cur = (kk % 2 == 0) ? a : b;
     uint2* oth = (kk % 2 == 0) ? b : a;
     DevIndex f = idx->dev(); f.ktab = nullptr; f.kmer = 0; f.dtab = nullptr; f.dkmer = 0;
@@ -1244,13 +1245,14 @@ static nvbio_status build_canonical_tables(FMIndexImpl* idx, uint32_t k, hipStre
         uint2* t = cur; cur = oth; oth = t;
     }
     const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize( stream ) == hipSuccess;
-    (void)hipFree( b );                                          // level kk - 1
-    if (!ok) { (void)hipFree( a ); set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
+    bufs.release( b );                                           // level kk - 1
+    if (!ok) { set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
     idx->ktab = a; idx->kmer = kk;
     idx->owned_bytes += entries * sizeof(uint2);
     const nvbio_status st = build_canonical_table( idx, k, (idx->table_flags & NVBIO_FM_TABLE_CANONICAL_WIDE) != 0, stream );
-    if (st != NVBIO_OK) { (void)hipFree( a ); idx->ktab = nullptr; idx->kmer = 0; }
-    return st;
+    if (st != NVBIO_OK) { idx->ktab = nullptr; idx->kmer = 0; return st; }
+    bufs.forget( a );
+    return NVBIO_OK;
 }
 
 static nvbio_status build_kmer_table(FMIndexImpl* idx, uint32_t k, hipStream_t stream)
@@ -1269,9 +1271,10 @@ static nvbio_status build_kmer_table(FMIndexImpl* idx, uint32_t k, hipStream_t s
         return build_canonical_tables( idx, k, stream );
     }
     const uint64_t entries = 1ull << (2 * k);
-    uint2 *a = nullptr, *b = nullptr;
-    if (hipMalloc( (void**)&a, entries * sizeof(uint2) ) != hipSuccess) { (void)hipGetLastError(); set_error( "k-mer table: out of device memory" ); return NVBIO_ERR_NOMEM; }
-    if (hipMalloc( (void**)&b, (entries / 4) * sizeof(uint2) ) != hipSuccess) { (void)hipGetLastError(); (void)hipFree( a ); set_error( "k-mer table: out of device memory" ); return NVBIO_ERR_NOMEM; }
+    BuildBuffers bufs;
+    uint2* a = bufs.alloc<uint2>( entries );
+    uint2* b = a ? bufs.alloc<uint2>( entries / 4 ) : nullptr;
+    if (!b) { set_error( "k-mer table: out of device memory" ); return NVBIO_ERR_NOMEM; }
     // levels alternate between the two buffers so that level k lands in `a` (the large one) and level k-1 in `b`
     uint2* cur = (k % 2 == 0) ? a : b;
     uint2* oth = (k % 2 == 0) ? b : a;
@@ -1284,23 +1287,18 @@ static nvbio_status build_kmer_table(FMIndexImpl* idx, uint32_t k, hipStream_t s
         uint2* t = cur; cur = oth; oth = t;
     }
     // cur == a (level k), oth == b (level k-1) by construction
-    nvbio_status st = NVBIO_OK;
-    if (hipGetLastError() != hipSuccess) { set_error( "k-mer table build failed" ); st = NVBIO_ERR_HIP; }
-    if (st == NVBIO_OK && direct) st = build_direct_table( idx, a, entries, stream );
-    if (st == NVBIO_OK && hipStreamSynchronize( stream ) != hipSuccess) { set_error( "k-mer table build failed" ); st = NVBIO_ERR_HIP; }
-    if (st != NVBIO_OK)
-    {
-        (void)hipFree( a ); (void)hipFree( b );
-        return st;
-    }
+    if (hipGetLastError() != hipSuccess) { set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
+    if (direct) NVB_CHECK( build_direct_table( idx, a, entries, stream ) );
+    if (hipStreamSynchronize( stream ) != hipSuccess) { set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
+    bufs.forget( a );
     if (direct)
     {
+        bufs.forget( b );
         idx->ktab = b; idx->kmer = k - 1u; idx->dtab = a; idx->dkmer = k;
         idx->owned_bytes += (entries + entries / 4) * sizeof(uint2);
     }
     else
     {
-        (void)hipFree( b );
         idx->ktab = a; idx->kmer = k;
         idx->owned_bytes += entries * sizeof(uint2);
     }
@@ -1518,10 +1516,9 @@ nvbio_status nvbio_fm_filter_scan(nvbio_fm_index_t index, const nvbio_uint2* ran
     hipcub::TransformInputIterator<uint64_t, RangeSize, const uint2*> sizes( (const uint2*)ranges_dev, RangeSize() );
     size_t temp_bytes = 0;
     NVB_HIP( hipcub::DeviceScan::InclusiveSum( nullptr, temp_bytes, sizes, slots_dev, (int)n_queries, s ) );
-    void* temp = nullptr;
-    if (scratch_alloc( &temp, temp_bytes ? temp_bytes : 16, s ) != hipSuccess) { set_error( "filter_scan: out of device memory" ); return NVBIO_ERR_NOMEM; }
-    const hipError_t e = hipcub::DeviceScan::InclusiveSum( temp, temp_bytes, sizes, slots_dev, (int)n_queries, s );
-    scratch_free( temp, s );
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc( temp_bytes, s, "filter_scan: out of device memory" ) );
+    const hipError_t e = hipcub::DeviceScan::InclusiveSum( temp.get(), temp_bytes, sizes, slots_dev, (int)n_queries, s );
     if (e != hipSuccess) { set_error( "filter_scan: scan failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     NVB_HIP( hipMemcpyAsync( n_hits, slots_dev + (n_queries - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, s ) );
     NVB_HIP( hipStreamSynchronize( s ) );
@@ -1605,8 +1602,9 @@ nvbio_status nvbio_fm_hamming_backtrack(nvbio_fm_index_t index, const nvbio_stri
     NVB_REQUIRE( ranges_dev == nullptr || max_ranges > 0, "ranges_dev without max_ranges" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    uint32_t* overflow = nullptr;
-    NVB_HIP( scratch_alloc( (void**)&overflow, sizeof(uint32_t), s ) );
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc( sizeof(uint32_t), s, "hamming_backtrack: out of device memory" ) );
+    uint32_t* overflow = (uint32_t*)temp.get();
     NVB_HIP( hipMemsetAsync( overflow, 0, sizeof(uint32_t), s ) );
     const DevIndex f = idx->dev();
     const dim3 grid( grid_for( q.n, 128 ) ), block( 128 );
@@ -1623,40 +1621,58 @@ nvbio_status nvbio_fm_hamming_backtrack(nvbio_fm_index_t index, const nvbio_stri
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync( &h_over, overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s );
     if (e == hipSuccess) e = hipStreamSynchronize( s );
-    scratch_free( overflow, s );
     if (e != hipSuccess) { set_error( "hamming_backtrack failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     if (h_over) { set_error( "hamming_backtrack: the 128-entry stack of the reference's benchmark overflowed for %u branches", h_over ); return NVBIO_ERR_UNSUPPORTED; }
     return NVBIO_OK;
 }
 
-// scratch layout of nvbio_fm_match_seed_diagonals: tile keys | tile counts | tile offsets | scan temp
-struct SeedScratch { SeedTiles tl; uint32_t slots; uint64_t keys_bytes, counts_bytes, scan_bytes, total; };
+// the tiles of a seed pass and its scratch: tile keys | tile counts | tile offsets | scan temp, and in the two-strand pass (128 key slots per tile)
+// what NVBIO_FM_DEFER_HEAVY uses: 128 deferred slots per tile | their counts | their offsets | the dense list of deferred searches | its length
+struct SeedScratch
+{
+    SeedTiles tl; uint32_t slots; size_t scan_bytes; bool both;
+    uint64_t* tile_keys; uint32_t *tile_counts, *tile_offsets; void* scan_temp;
+    uint32_t *tile_defer, *defer_counts, *defer_offsets, *defer_list, *defer_n;
+    void carve(ScratchLayout& c)
+    {
+        tile_keys    = c.take<uint64_t>( (uint64_t)tl.n_tiles * slots );
+        tile_counts  = c.take<uint32_t>( tl.n_tiles + 1u );
+        tile_offsets = c.take<uint32_t>( tl.n_tiles + 1u );
+        scan_temp    = c.take<uint8_t>( scan_bytes );
+        if (both)
+        {
+            tile_defer    = c.take<uint32_t>( (uint64_t)tl.n_tiles * 128u );
+            defer_counts  = c.take<uint32_t>( tl.n_tiles + 1u );
+            defer_offsets = c.take<uint32_t>( tl.n_tiles + 1u );
+            defer_list    = c.take<uint32_t>( (uint64_t)tl.n_tiles * 128u );
+            defer_n       = c.take<uint32_t>( 1 );
+        }
+    }
+};
 
-static nvbio_status seed_scratch_layout(const nvbio_string_set* seeds, SeedScratch* L)
+static nvbio_status seed_scratch_layout(const nvbio_string_set* seeds, bool both, SeedScratch* L)
 {
     NVB_REQUIRE( seeds != nullptr, "seeds is NULL" );
     const uint32_t spr = seeds->seeds_per_string;
     NVB_REQUIRE( spr > 0, "the string set must enumerate seeds (seeds_per_string > 0)" );
     NVB_REQUIRE( seeds->n % spr == 0, "n must be a multiple of seeds_per_string" );
+    NVB_REQUIRE( !both || spr <= 64u, "the two-strand seed pass takes at most 64 seeds per read" );
+    L->both       = both;
     L->tl.reads   = seeds->n / spr;
     L->tl.rpt     = spr <= 64u ? 64u / spr : 1u;
     L->tl.n_tiles = (L->tl.reads + L->tl.rpt - 1u) / L->tl.rpt;
-    L->slots      = 64u * ((spr + 63u) / 64u);
-    L->keys_bytes   = ((uint64_t)L->tl.n_tiles * L->slots * sizeof(uint64_t) + 255u) & ~255ull;
-    L->counts_bytes = ((uint64_t)(L->tl.n_tiles + 1u) * sizeof(uint32_t) + 255u) & ~255ull;
-    size_t scan = 0;
+    L->slots      = both ? 128u : 64u * ((spr + 63u) / 64u);
+    L->scan_bytes = 0;
     if (L->tl.n_tiles)
-        NVB_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)L->tl.n_tiles, (hipStream_t)0 ) );
-    L->scan_bytes = ((uint64_t)scan + 255u) & ~255ull;
-    L->total = L->keys_bytes + 2u * L->counts_bytes + L->scan_bytes + 256u;
+        NVB_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, L->scan_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)L->tl.n_tiles, (hipStream_t)0 ) );
     return NVBIO_OK;
 }
 
 nvbio_status nvbio_fm_match_seed_diagonals_temp_bytes(const nvbio_string_set* seeds, uint64_t* bytes)
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
-    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, &L ) );
-    *bytes = L.total;
+    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, false, &L ) );
+    ScratchLayout c; L.carve( c ); *bytes = c.bytes();
     return NVBIO_OK;
 }
 
@@ -1684,20 +1700,11 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
     NVB_HIP( hipMemsetAsync( counts_dev, 0, (count ? 4 : 2) * sizeof(uint32_t), s ) );
     if (q.n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && residual_ranges_dev && residual_ids_dev, "NULL device pointer" );
-    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, &L ) );
-    uint8_t* temp = (uint8_t*)temp_dev;
-    bool own_temp = false;
-    if (temp == nullptr)
-    {
-        if (scratch_alloc( (void**)&temp, L.total, s ) != hipSuccess) { (void)hipGetLastError(); set_error( "seed pass: out of device memory for %llu bytes of scratch", (unsigned long long)L.total ); return NVBIO_ERR_NOMEM; }
-        own_temp = true;
-    }
-    else NVB_REQUIRE( temp_bytes >= L.total, "temp_bytes too small (nvbio_fm_match_seed_diagonals_temp_bytes)" );
-    uint8_t* base = (uint8_t*)(((uintptr_t)temp + 255u) & ~(uintptr_t)255u);
-    uint64_t* tile_keys    = (uint64_t*)base;
-    uint32_t* tile_counts  = (uint32_t*)(base + L.keys_bytes);
-    uint32_t* tile_offsets = (uint32_t*)(base + L.keys_bytes + L.counts_bytes);
-    void*     scan_temp    = base + L.keys_bytes + 2u * L.counts_bytes;
+    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, false, &L ) );
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc_layout( s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
+                                  temp_dev, temp_bytes, "nvbio_fm_match_seed_diagonals_temp_bytes" ) );
+    uint64_t* tile_keys = L.tile_keys; uint32_t* tile_counts = L.tile_counts;
     const DevIndex f = idx->dev();
     // one wave per tile of whole reads; the grid keeps every wave slot of the chip busy a few times over (flags bits 16..31:
     // workgroups in units of 64, a tuning/testing knob -- results do not depend on it)
@@ -1724,14 +1731,13 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
 #undef NVB_LAUNCH_SD
     hipError_t e = hipGetLastError();
     size_t scan_bytes = L.scan_bytes;
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( scan_temp, scan_bytes, (const uint32_t*)tile_counts, tile_offsets, (int)L.tl.n_tiles, s );
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
     if (e == hipSuccess)
     {
         hipLaunchKernelGGL( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, 0, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
-                            (const uint32_t*)tile_offsets, L.tl.n_tiles, L.slots, keys_dev, (unsigned int*)counts_dev );
+                            (const uint32_t*)L.tile_offsets, L.tl.n_tiles, L.slots, keys_dev, (unsigned int*)counts_dev );
         e = hipGetLastError();
     }
-    if (own_temp) scratch_free( temp, s );
     if (e != hipSuccess) { set_error( "seed pass failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVBIO_OK;
 }
@@ -1741,40 +1747,18 @@ int nvbio_fm_index_is_canonical(nvbio_fm_index_t index)
     return index != nullptr && ((FMIndexImpl*)index)->ctab != nullptr ? (int)((FMIndexImpl*)index)->ckmer : 0;
 }
 
-// scratch of the two-strand pass: 128 key slots and 2 counts per tile; with NVBIO_FM_DEFER_HEAVY also 128 deferred slots (uint32) and 2 counts per
-// tile, the dense list of deferred searches and its length
-struct SeedBothScratch { SeedScratch L; uint64_t defer_bytes, list_bytes; };
-static nvbio_status seed_both_layout(const nvbio_string_set* seeds, SeedScratch* L, SeedBothScratch* B = nullptr)
-{
-    NVB_CHECK( seed_scratch_layout( seeds, L ) );
-    NVB_REQUIRE( seeds->seeds_per_string <= 64u, "the two-strand seed pass takes at most 64 seeds per read" );
-    L->slots        = 128u;
-    L->keys_bytes   = ((uint64_t)L->tl.n_tiles * 128u * sizeof(uint64_t) + 255u) & ~255ull;
-    L->counts_bytes = ((uint64_t)(L->tl.n_tiles + 1u) * sizeof(uint32_t) + 255u) & ~255ull;
-    size_t scan = 0;
-    if (L->tl.n_tiles)
-        NVB_HIP( hipcub::DeviceScan::ExclusiveSum( nullptr, scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)L->tl.n_tiles, (hipStream_t)0 ) );
-    L->scan_bytes = ((uint64_t)scan + 255u) & ~255ull;
-    const uint64_t defer_bytes = ((uint64_t)L->tl.n_tiles * 128u * sizeof(uint32_t) + 255u) & ~255ull;
-    const uint64_t list_bytes  = ((uint64_t)L->tl.n_tiles * 128u * sizeof(uint32_t) + 255u) & ~255ull;
-    // keys | counts | offsets | scan temp | deferred slots | deferred counts | deferred offsets | dense deferred list | its length
-    L->total = L->keys_bytes + 2u * L->counts_bytes + L->scan_bytes + defer_bytes + 2u * L->counts_bytes + list_bytes + 256u + 256u;
-    if (B) { B->L = *L; B->defer_bytes = defer_bytes; B->list_bytes = list_bytes; }
-    return NVBIO_OK;
-}
-
 nvbio_status nvbio_fm_match_seed_diagonals_both_temp_bytes(const nvbio_string_set* seeds, uint64_t* bytes)
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
-    SeedScratch L; NVB_CHECK( seed_both_layout( seeds, &L ) );
-    *bytes = L.total;
+    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
+    ScratchLayout c; L.carve( c ); *bytes = c.bytes();
     return NVBIO_OK;
 }
 
 nvbio_status nvbio_fm_match_seed_diagonals_both_keys_capacity(const nvbio_string_set* seeds, uint64_t* n_keys)
 {
     NVB_REQUIRE( n_keys != nullptr, "n_keys is NULL" );
-    SeedScratch L; NVB_CHECK( seed_both_layout( seeds, &L ) );
+    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
     // a tile of 64 / seeds_per_string reads can leave up to 64 keys per strand, and (NVBIO_FM_DEFER_HEAVY) one more per deferred search
     *n_keys = 256ull * L.tl.n_tiles;
     return NVBIO_OK;
@@ -1808,26 +1792,11 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
     NVB_HIP( hipMemsetAsync( counts_dev, 0, (count ? 6 : 4) * sizeof(uint32_t), s ) );
     if (q.n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && residual_ranges_dev && residual_ids_dev, "NULL device pointer" );
-    SeedScratch L; SeedBothScratch B; NVB_CHECK( seed_both_layout( seeds, &L, &B ) );
-    uint8_t* temp = (uint8_t*)temp_dev;
-    bool own_temp = false;
-    if (temp == nullptr)
-    {
-        if (scratch_alloc( (void**)&temp, L.total, s ) != hipSuccess) { (void)hipGetLastError(); set_error( "seed pass: out of device memory for %llu bytes of scratch", (unsigned long long)L.total ); return NVBIO_ERR_NOMEM; }
-        own_temp = true;
-    }
-    else NVB_REQUIRE( temp_bytes >= L.total, "temp_bytes too small (nvbio_fm_match_seed_diagonals_both_temp_bytes)" );
-    uint8_t* base = (uint8_t*)(((uintptr_t)temp + 255u) & ~(uintptr_t)255u);
-    uint64_t* tile_keys    = (uint64_t*)base;
-    uint32_t* tile_counts  = (uint32_t*)(base + L.keys_bytes);
-    uint32_t* tile_offsets = (uint32_t*)(base + L.keys_bytes + L.counts_bytes);
-    void*     scan_temp    = base + L.keys_bytes + 2u * L.counts_bytes;
-    uint8_t*  dbase        = base + L.keys_bytes + 2u * L.counts_bytes + L.scan_bytes;
-    uint32_t* tile_defer    = (uint32_t*)dbase;
-    uint32_t* defer_counts  = (uint32_t*)(dbase + B.defer_bytes);
-    uint32_t* defer_offsets = (uint32_t*)(dbase + B.defer_bytes + L.counts_bytes);
-    uint32_t* defer_list    = (uint32_t*)(dbase + B.defer_bytes + 2u * L.counts_bytes);
-    uint32_t* defer_n       = (uint32_t*)(dbase + B.defer_bytes + 2u * L.counts_bytes + B.list_bytes);
+    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc_layout( s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
+                                  temp_dev, temp_bytes, "nvbio_fm_match_seed_diagonals_both_temp_bytes" ) );
+    uint64_t* tile_keys = L.tile_keys; uint32_t* tile_counts = L.tile_counts; uint32_t* tile_defer = L.tile_defer; uint32_t* defer_counts = L.defer_counts;
     const DevIndex f = idx->dev();
     unsigned blocks = (L.tl.n_tiles + 3u) / 4u;
     const unsigned cap = (flags >> 16) ? (flags >> 16) * 64u : 256u * 64u;
@@ -1848,34 +1817,33 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
 #undef NVB_LAUNCH_SBD
     hipError_t e = hipGetLastError();
     size_t scan_bytes = L.scan_bytes;
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( scan_temp, scan_bytes, (const uint32_t*)tile_counts, tile_offsets, (int)L.tl.n_tiles, s );
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
     if (e == hipSuccess)
     {
         hipLaunchKernelGGL( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, 0, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
-                            (const uint32_t*)tile_offsets, L.tl.n_tiles, 128u, keys_dev, (unsigned int*)counts_dev );
+                            (const uint32_t*)L.tile_offsets, L.tl.n_tiles, 128u, keys_dev, (unsigned int*)counts_dev );
         e = hipGetLastError();
     }
     if (e == hipSuccess && defer)
     {
         // the deferred searches: their slots made dense, then a launch of their own that appends to the keys and the residual lists
         scan_bytes = L.scan_bytes;
-        e = hipcub::DeviceScan::ExclusiveSum( scan_temp, scan_bytes, (const uint32_t*)defer_counts, defer_offsets, (int)L.tl.n_tiles, s );
+        e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)defer_counts, L.defer_offsets, (int)L.tl.n_tiles, s );
         if (e == hipSuccess)
         {
             hipLaunchKernelGGL( fm_seed_defer_compact_kernel, dim3( grid_for( L.tl.n_tiles ) ), block, 0, s, (const uint32_t*)tile_defer, (const uint32_t*)defer_counts,
-                                (const uint32_t*)defer_offsets, L.tl.n_tiles, defer_list, defer_n );
+                                (const uint32_t*)L.defer_offsets, L.tl.n_tiles, L.defer_list, L.defer_n );
             const uint64_t max_chunks = (128ull * L.tl.n_tiles + 256u * HEAVY_PER_LANE - 1u) / (256u * HEAVY_PER_LANE);
             const dim3 hgrid( (unsigned)(max_chunks < 4096u ? (max_chunks ? max_chunks : 1u) : 4096u) );
             if (seeds->symbol_bits == 2)
-                hipLaunchKernelGGL( (fm_seed_heavy_kernel<2>), hgrid, block, 0, s, f, q, read_len, (const uint32_t*)defer_list, (const uint32_t*)defer_n, keys_dev,
+                hipLaunchKernelGGL( (fm_seed_heavy_kernel<2>), hgrid, block, 0, s, f, q, read_len, (const uint32_t*)L.defer_list, (const uint32_t*)L.defer_n, keys_dev,
                                     (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev );
             else
-                hipLaunchKernelGGL( (fm_seed_heavy_kernel<4>), hgrid, block, 0, s, f, q, read_len, (const uint32_t*)defer_list, (const uint32_t*)defer_n, keys_dev,
+                hipLaunchKernelGGL( (fm_seed_heavy_kernel<4>), hgrid, block, 0, s, f, q, read_len, (const uint32_t*)L.defer_list, (const uint32_t*)L.defer_n, keys_dev,
                                     (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev );
             e = hipGetLastError();
         }
     }
-    if (own_temp) scratch_free( temp, s );
     if (e != hipSuccess) { set_error( "seed pass failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVBIO_OK;
 }
@@ -1961,20 +1929,13 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
         set_error( "nvbio_fm_residual_diagonals needs the full suffix array: build the index with sa_int = 1" );
         return NVBIO_ERR_UNSUPPORTED;
     }
-    // scratch: sorted ids | sorted ranges | sort temp
-    const uint64_t ids_bytes = ((uint64_t)n * 4u + 255u) & ~255ull, rng_bytes = ((uint64_t)n * 8u + 255u) & ~255ull;
     size_t sort_bytes = 0;
     NVB_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n, 0, 32, s ) );
-    uint8_t* aux = nullptr;
-    if (scratch_alloc( (void**)&aux, ids_bytes + rng_bytes + sort_bytes + 256u, s ) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        set_error( "residual diagonals: out of device memory" );
-        return NVBIO_ERR_NOMEM;
-    }
-    uint32_t* ids_s = (uint32_t*)aux;
-    uint64_t* rng_s = (uint64_t*)(aux + ids_bytes);
-    void*     tmp   = aux + ids_bytes + rng_bytes;
+    // scratch: sorted ids | sorted ranges | sort temp
+    uint32_t* ids_s; uint64_t* rng_s; void* tmp;
+    ScratchBlock aux;
+    NVB_CHECK( aux.alloc_layout( s, "residual diagonals: out of device memory", [&](ScratchLayout& c)
+                                 { ids_s = c.take<uint32_t>( n ); rng_s = c.take<uint64_t>( n ); tmp = c.take<uint8_t>( sort_bytes ); } ) );
     hipError_t e = hipcub::DeviceRadixSort::SortPairs( tmp, sort_bytes, ids_dev, ids_s, (const uint64_t*)ranges_dev, rng_s, (int)n, 0, 32, s );
     if (e == hipSuccess)
     {
@@ -1983,7 +1944,6 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
                             keys_dev, (unsigned int*)n_keys_dev );
         e = hipGetLastError();
     }
-    scratch_free( aux, s );
     if (e != hipSuccess) { set_error( "residual diagonals failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVBIO_OK;
 }

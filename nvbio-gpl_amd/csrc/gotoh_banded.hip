@@ -1411,31 +1411,27 @@ job_length_keys_kernel(const BatchDev b, const uint32_t* __restrict__ jobs, cons
     }
 }
 
-// sorted list and its length (device) in *list_out / *count_out; the scratch is freed stream-ordered by the caller through *aux_out
+// sorted list and its length (device) in *list_out / *count_out, both in *aux: the caller keeps it until the work that reads them is enqueued
 static nvbio_status sort_jobs_by_length(const BatchDev& b, const uint32_t* job_list, const uint32_t* job_count, const uint32_t** list_out,
-                                        const uint32_t** count_out, void** aux_out, hipStream_t s)
+                                        const uint32_t** count_out, ScratchBlock* aux, hipStream_t s)
 {
-    const uint64_t kb = ((uint64_t)b.n * 2u + 255u) & ~255ull, lb = ((uint64_t)b.n * 4u + 255u) & ~255ull;
     size_t sort_bytes = 0;
     int bits = 1; while ((1u << bits) <= (b.max_read_len ? b.max_read_len : 0xFFFEu) && bits < 16) ++bits;
     bits = 16;                                   // (the 0xFFFF keys behind the list's end must sort last: all 16 bits)
     NVB_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, sort_bytes, (const uint16_t*)nullptr, (uint16_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                  (int)b.n, 0, bits, s ) );
-    uint8_t* aux = nullptr;
-    if (scratch_alloc( (void**)&aux, 2u * kb + 2u * lb + 256u + sort_bytes, s ) != hipSuccess)
+    uint16_t *k_in, *k_out; uint32_t *l_all, *l_out, *c_all; void* tmp;
+    NVB_CHECK( aux->alloc_layout( s, "banded score: out of device memory for the length-sorted job list", [&](ScratchLayout& c)
     {
-        (void)hipGetLastError();
-        set_error( "banded score: out of device memory for the length-sorted job list" );
-        return NVBIO_ERR_NOMEM;
-    }
-    uint16_t* k_in = (uint16_t*)aux; uint16_t* k_out = (uint16_t*)(aux + kb);
-    uint32_t* l_all = (uint32_t*)(aux + 2u * kb); uint32_t* l_out = (uint32_t*)(aux + 2u * kb + lb);
-    uint32_t* c_all = (uint32_t*)(aux + 2u * kb + 2u * lb);
-    void* tmp = aux + 2u * kb + 2u * lb + 256u;
+        k_in  = c.take<uint16_t>( b.n ); k_out = c.take<uint16_t>( b.n );
+        l_all = c.take<uint32_t>( b.n ); l_out = c.take<uint32_t>( b.n );
+        c_all = c.take<uint32_t>( 1 );
+        tmp   = c.take<uint8_t>( sort_bytes );
+    } ) );
     hipLaunchKernelGGL( job_length_keys_kernel, dim3( (b.n + 255u) / 256u < 65536u ? (b.n + 255u) / 256u : 65536u ), dim3( 256 ), 0, s, b, job_list, job_count, k_in, l_all, c_all );
     const hipError_t e = hipcub::DeviceRadixSort::SortPairs( tmp, sort_bytes, (const uint16_t*)k_in, k_out, job_list ? job_list : (const uint32_t*)l_all, l_out, (int)b.n, 0, bits, s );
-    if (e != hipSuccess) { scratch_free( aux, s ); set_error( "job sort failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
-    *list_out = l_out; *count_out = job_list ? job_count : c_all; *aux_out = aux;
+    if (e != hipSuccess) { set_error( "job sort failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+    *list_out = l_out; *count_out = job_list ? job_count : c_all;
     return NVBIO_OK;
 }
 
@@ -1488,29 +1484,26 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         size_t sel_bytes = 0;
         hipcub::CountingInputIterator<uint32_t> ids( 0u );
         NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
-        const uint64_t flags_bytes = ((uint64_t)b.n + 255u) & ~255ull;
-        const uint64_t list_bytes  = ((uint64_t)b.n * 4u + 255u) & ~255ull;
         const bool third = !(b.algo & NVBIO_ALN_NO_THIRD_CHANCE);
-        void* aux = nullptr;
         // three-way partition of the job ids by flag (3: second chance, 2: third chance), the rest discarded
         size_t part_bytes = 0;
         hipcub::DiscardOutputIterator<uint32_t> nowhere;
         const FlagIs is3 = { nullptr, 3 }; const FlagIn is2 = { nullptr, 0u };
         NVB_HIP( hipcub::DevicePartition::If( nullptr, part_bytes, ids, (uint32_t*)nullptr, (uint32_t*)nullptr, nowhere, (uint32_t*)nullptr, (int)b.n, is3, is2, s ) );
         if (part_bytes > sel_bytes) sel_bytes = part_bytes;
-        if (scratch_alloc( &aux, flags_bytes + 3u * list_bytes + 256u + sel_bytes, s ) != hipSuccess)
+        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *counts; void* sel_temp;
+        ScratchBlock aux;
+        NVB_CHECK( aux.alloc_layout( s, "banded score: out of device memory for the job list", [&](ScratchLayout& c)
         {
-            (void)hipGetLastError();
-            set_error( "banded score: out of device memory for the job list" );
-            return NVBIO_ERR_NOMEM;
-        }
-        uint8_t*  need_dp   = (uint8_t*)aux;
-        uint32_t* job_list  = (uint32_t*)((uint8_t*)aux + flags_bytes);
-        uint32_t* list_s    = (uint32_t*)((uint8_t*)aux + flags_bytes + list_bytes);          // second-chance jobs
-        uint32_t* list_t    = (uint32_t*)((uint8_t*)aux + flags_bytes + 2u * list_bytes);     // third-chance jobs
-        uint32_t* job_count = (uint32_t*)((uint8_t*)aux + flags_bytes + 3u * list_bytes);
-        uint32_t* count_st  = job_count + 2;                                                  // [2]: second, third
-        void*     sel_temp  = (uint8_t*)aux + flags_bytes + 3u * list_bytes + 256u;
+            need_dp  = c.take<uint8_t>( b.n );
+            job_list = c.take<uint32_t>( b.n );
+            list_s   = c.take<uint32_t>( b.n );                                              // second-chance jobs
+            list_t   = c.take<uint32_t>( b.n );                                              // third-chance jobs
+            counts   = c.take<uint32_t>( 4 );                                                // [0]: job_list's length, [2..3]: list_s's, list_t's
+            sel_temp = c.take<uint8_t>( sel_bytes );
+        } ) );
+        uint32_t* job_count = counts;
+        uint32_t* count_st  = counts + 2;                                                   // (DevicePartition writes both lengths)
         if (by_quality)
             hipLaunchKernelGGL( (ungapped_e2e31_kernel<RB,0,true>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                 (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc );
@@ -1544,26 +1537,20 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, need_dp, job_list, job_count, (int)b.n, s );
         if (e == hipSuccess)
         {
-            const uint32_t* jl = job_list; const uint32_t* jc = job_count; void* aux2 = nullptr;
+            const uint32_t* jl = job_list; const uint32_t* jc = job_count; ScratchBlock sorted;
             if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT))
-            {
-                const nvbio_status st = sort_jobs_by_length( b, job_list, job_count, &jl, &jc, &aux2, s );
-                if (st != NVBIO_OK) { scratch_free( aux, s ); return st; }
-            }
+                NVB_CHECK( sort_jobs_by_length( b, job_list, job_count, &jl, &jc, &sorted, s ) );
             launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s );
-            if (aux2) scratch_free( aux2, s );
         }
-        scratch_free( aux, s );
         if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
         NVB_HIP( hipGetLastError() );
         return NVBIO_OK;
     }
     if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT) && b.n > 1u)
     {
-        const uint32_t* jl = nullptr; const uint32_t* jc = nullptr; void* aux2 = nullptr;
-        NVB_CHECK( sort_jobs_by_length( b, nullptr, nullptr, &jl, &jc, &aux2, s ) );
+        const uint32_t* jl = nullptr; const uint32_t* jc = nullptr; ScratchBlock sorted;
+        NVB_CHECK( sort_jobs_by_length( b, nullptr, nullptr, &jl, &jc, &sorted, s ) );
         launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s );
-        scratch_free( aux2, s );
         NVB_HIP( hipGetLastError() );
         return NVBIO_OK;
     }

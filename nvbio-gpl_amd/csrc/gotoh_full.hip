@@ -1335,7 +1335,7 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
     //     N = max_text_len) go to the 16-bit packed kernel two per lane (list A), the others to the int32 kernel (list B);
     //     otherwise every flagged job goes to the int32 kernel (list B).
     //  The lists and their lengths stay on the device.
-    uint32_t *list_a = nullptr, *count_a = nullptr, *job_list = nullptr, *job_count = nullptr; void* aux = nullptr;
+    uint32_t *list_a = nullptr, *count_a = nullptr, *job_list = nullptr, *job_count = nullptr; ScratchBlock aux;
     int32_t P = 0;
     const bool packable_bits = batch->text_bits == 2 && (batch->read_bits == 4 || batch->read_bits == 2);
     const bool shortcut = type == NVBIO_SEMI_GLOBAL && packable_bits && plain_gotoh( sc ) && full_ungapped_ok( sc, b, &P ) && !(b.algo & NVBIO_ALN_NO_UNGAPPED_SCORE);
@@ -1347,30 +1347,26 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         size_t sel_bytes = 0;
         hipcub::CountingInputIterator<uint32_t> ids( 0u );
         NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
-        const uint64_t flags_bytes = ((uint64_t)b.n + 255u) & ~255ull;
-        const uint64_t list_bytes  = ((uint64_t)b.n * 4u + 255u) & ~255ull;
         // (the narrow route: one more flag array, its job list, the band windows; see narrow_jobs_kernel)
         const bool narrow = shortcut && !text_blocking && !(b.algo & (NVBIO_ALN_NO_NARROW_SCORE | NVBIO_ALN_NO_PACKED_DP)) && max_pattern_len <= 161u &&
                             banded31_packed_ok( sc, max_pattern_len ) && sc.pat_ge < 0;
-        if (scratch_alloc( &aux, 4u * flags_bytes + 5u * list_bytes + 512u + sel_bytes, s ) != hipSuccess)
+        uint8_t *need_dp, *to_packed, *to_plain, *route; uint32_t *counts, *list_n, *wb2, *we2; void* sel_temp;
+        NVB_CHECK( aux.alloc_layout( s, "full Gotoh: out of device memory for the job lists", [&](ScratchLayout& c)
         {
-            (void)hipGetLastError();
-            set_error( "full Gotoh: out of device memory for the job lists" );
-            return NVBIO_ERR_NOMEM;
-        }
-        uint8_t* need_dp   = (uint8_t*)aux;
-        uint8_t* to_packed = need_dp + flags_bytes;
-        uint8_t* to_plain  = to_packed + flags_bytes;
-        list_a    = (uint32_t*)(to_plain + flags_bytes);
-        job_list  = (uint32_t*)((uint8_t*)list_a + list_bytes);
-        count_a   = (uint32_t*)((uint8_t*)job_list + list_bytes);
-        job_count = count_a + 1;
-        uint32_t* count_n  = count_a + 2;
-        uint8_t*  route    = (uint8_t*)count_a + 256u;
-        uint32_t* list_n   = (uint32_t*)(route + flags_bytes);
-        uint32_t* wb2      = (uint32_t*)((uint8_t*)list_n + list_bytes);
-        uint32_t* we2      = (uint32_t*)((uint8_t*)wb2 + list_bytes);
-        void* sel_temp = (uint8_t*)we2 + list_bytes + 256u;
+            need_dp   = c.take<uint8_t>( b.n );
+            to_packed = c.take<uint8_t>( b.n );
+            to_plain  = c.take<uint8_t>( b.n );
+            list_a    = c.take<uint32_t>( b.n );
+            job_list  = c.take<uint32_t>( b.n );
+            counts    = c.take<uint32_t>( 4 );            // the lengths of list_a, job_list, list_n and the second chance's list
+            route     = c.take<uint8_t>( b.n );
+            list_n    = c.take<uint32_t>( b.n );
+            wb2       = c.take<uint32_t>( b.n );
+            we2       = c.take<uint32_t>( b.n );
+            sel_temp  = c.take<uint8_t>( sel_bytes );
+        } ) );
+        count_a = counts; job_count = counts + 1;
+        uint32_t* count_n = counts + 2;
         const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
         if (shortcut)
         {
@@ -1383,10 +1379,10 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
             if (second_chance)
             {
                 // the jobs the second chance can still settle (need_dp == 3), compacted, through their own launch: every job ends as 0 or 1
-                uint32_t* list_s = list_n; uint32_t* count_s = count_n + 1;                    // (the narrow route's list is built after this)
+                uint32_t* list_s = list_n; uint32_t* count_s = counts + 3;                     // (the narrow route's list is built after this)
                 hipcub::TransformInputIterator<uint8_t, FlagIs3, const uint8_t*> is3( need_dp, FlagIs3() );
                 const hipError_t e3 = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is3, list_s, count_s, (int)b.n, s );
-                if (e3 != hipSuccess) { scratch_free( aux, s ); set_error( "DeviceSelect failed: %s", hipGetErrorString( e3 ) ); return NVBIO_ERR_HIP; }
+                if (e3 != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e3 ) ); return NVBIO_ERR_HIP; }
                 if (batch->read_bits == 4) hipLaunchKernelGGL( (ungapped_full_e2e_kernel<4,1>), grid, block, 0, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
                                                                (const uint32_t*)list_s, (const uint32_t*)count_s );
                 else                       hipLaunchKernelGGL( (ungapped_full_e2e_kernel<2,1>), grid, block, 0, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
@@ -1419,23 +1415,18 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
             list_a = nullptr; count_a = nullptr;
             e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, need_dp, job_list, job_count, (int)b.n, s );
         }
-        if (e != hipSuccess) { scratch_free( aux, s ); set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+        if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     }
 
     // boundary columns: caller scratch if given, else stream-ordered scratch; jobs are processed in
     // as many launches as the scratch allows (at least one wave of jobs per launch)
-    void*    owned = nullptr;
+    ScratchBlock owned;
     uint32_t* column = (uint32_t*)temp_dev;
     uint64_t  cap_jobs;
     if (column)
     {
         cap_jobs = temp_bytes / (rows * sizeof(uint32_t));
-        if (!(cap_jobs >= 64 || cap_jobs >= b.n))
-        {
-            if (aux) scratch_free( aux, s );
-            set_error( "invalid argument: temp_bytes too small (see nvbio_full_gotoh_temp_bytes)" );
-            return NVBIO_ERR_INVALID;
-        }
+        NVB_REQUIRE( cap_jobs >= 64 || cap_jobs >= b.n, "temp_bytes too small (see nvbio_full_gotoh_temp_bytes)" );
     }
     else
     {
@@ -1443,14 +1434,8 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         const uint64_t budget = 8ull << 30;                      // at most 8 GiB of scratch per launch
         if (cap_jobs * rows * sizeof(uint32_t) > budget) cap_jobs = budget / (rows * sizeof(uint32_t));
         if (cap_jobs < 64) cap_jobs = 64;
-        if (scratch_alloc( &owned, cap_jobs * rows * sizeof(uint32_t), s ) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            if (aux) scratch_free( aux, s );
-            set_error( "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs );
-            return NVBIO_ERR_NOMEM;
-        }
-        column = (uint32_t*)owned;
+        NVB_CHECK( owned.alloc( cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
+        column = (uint32_t*)owned.get();
     }
     nvbio_status st = NVBIO_OK;
     if (list_a)
@@ -1489,8 +1474,6 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
             launch_type<true> ( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count ) :
             launch_type<false>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count );
     }
-    if (owned) scratch_free( owned, s );
-    if (aux)   scratch_free( aux, s );
     return st;
 }
 
@@ -1543,23 +1526,18 @@ extern "C" nvbio_status nvbio_full_gotoh_score_best2(int device, nvbio_alignment
     const uint64_t budget = 8ull << 30;
     if (cap_jobs * rows * sizeof(uint32_t) > budget) cap_jobs = budget / (rows * sizeof(uint32_t));
     if (cap_jobs < 64) cap_jobs = 64;
-    void* column = nullptr;
-    if (scratch_alloc( &column, cap_jobs * rows * sizeof(uint32_t), s ) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        set_error( "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs );
-        return NVBIO_ERR_NOMEM;
-    }
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc( cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
+    uint32_t* column = (uint32_t*)temp.get();
     nvbio_status st = NVBIO_OK;
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
     {
         const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
-#define NVB_B2(TYPE_) (text_blocking ? launch_best2<TYPE_,true> ( b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, (uint32_t*)column, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s ) \
-                                     : launch_best2<TYPE_,false>( b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, (uint32_t*)column, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s ))
+#define NVB_B2(TYPE_) (text_blocking ? launch_best2<TYPE_,true> ( b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s ) \
+                                     : launch_best2<TYPE_,false>( b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s ))
         st = type == NVBIO_GLOBAL ? NVB_B2( NVBIO_GLOBAL ) : type == NVBIO_LOCAL ? NVB_B2( NVBIO_LOCAL ) : NVB_B2( NVBIO_SEMI_GLOBAL );
 #undef NVB_B2
     }
-    scratch_free( column, s );
     return st;
 }
 

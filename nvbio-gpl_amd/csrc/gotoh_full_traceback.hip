@@ -555,7 +555,7 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         NVB_CHECK( nvbio_full_sw_score( device, type, 0, sw, batch, max_pattern_len, max_text_len, min_scores_dev, scores_dev, sinks_dev,
                                         nullptr, 0, stream ) );
     const bool shortcut = !(b.algo & NVBIO_ALN_NO_UNGAPPED_TRACEBACK) && !sw;
-    uint32_t *job_list = nullptr, *job_count = nullptr; void* aux = nullptr; uint8_t* need_dp = nullptr;
+    uint32_t *job_list = nullptr, *job_count = nullptr; ScratchBlock aux; uint8_t* need_dp = nullptr;
     uint32_t *band_list = nullptr, *band_count = nullptr, *band_wb = nullptr, *band_we = nullptr; uint8_t* band_route = nullptr;
     // the row-restricted DP applies to nvBowtie's end-to-end mode (see full_gotoh_traceback_kernel)
     const int32_t go_min = -(sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go), ge_min = -(sc.pat_ge > sc.txt_ge ? sc.pat_ge : sc.txt_ge);
@@ -570,23 +570,19 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         size_t sel_bytes = 0;
         hipcub::CountingInputIterator<uint32_t> ids( 0u );
         NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
-        const uint64_t flags_bytes = ((uint64_t)b.n + 255u) & ~255ull;
-        const uint64_t list_bytes  = ((uint64_t)b.n * 4u + 255u) & ~255ull;
-        if (scratch_alloc( &aux, 2u * flags_bytes + 4u * list_bytes + 256u + sel_bytes, s ) != hipSuccess)
+        void* sel_temp;
+        NVB_CHECK( aux.alloc_layout( s, "full traceback: out of device memory for the job list", [&](ScratchLayout& c)
         {
-            (void)hipGetLastError();
-            set_error( "full traceback: out of device memory for the job list" );
-            return NVBIO_ERR_NOMEM;
-        }
-        need_dp   = (uint8_t*)aux;
-        job_list  = (uint32_t*)((uint8_t*)aux + flags_bytes);
-        job_count = (uint32_t*)((uint8_t*)aux + flags_bytes + list_bytes);
+            need_dp    = c.take<uint8_t>( b.n );
+            job_list   = c.take<uint32_t>( b.n );
+            job_count  = c.take<uint32_t>( 2 );           // [1]: band_list's length
+            band_route = c.take<uint8_t>( b.n );
+            band_list  = c.take<uint32_t>( b.n );
+            band_wb    = c.take<uint32_t>( b.n );
+            band_we    = c.take<uint32_t>( b.n );
+            sel_temp   = c.take<uint8_t>( sel_bytes );
+        } ) );
         band_count = job_count + 1;
-        band_route = (uint8_t*)job_count + 256u;
-        band_list  = (uint32_t*)(band_route + flags_bytes);
-        band_wb    = (uint32_t*)((uint8_t*)band_list + list_bytes);
-        band_we    = (uint32_t*)((uint8_t*)band_wb + list_bytes);
-        void* sel_temp = (uint8_t*)band_we + list_bytes;
         const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
 #define NVB_UNG(TYPE_, RB, TB) hipLaunchKernelGGL( (ungapped_full_traceback_kernel<TYPE_,RB,TB>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, \
                                                    (const int32_t*)scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp, \
@@ -606,21 +602,16 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
             e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, band_route, band_list, band_count, (int)b.n, s );
         }
         if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, need_dp, job_list, job_count, (int)b.n, s );
-        if (e != hipSuccess) { scratch_free( aux, s ); set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+        if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     }
 
     // ---- 4. the DP with direction vectors + walk, over the job list (or every job) ----
     const uint64_t per_job = full_tb_bytes_per_job( max_pattern_len, max_text_len );
-    void* owned = nullptr; uint8_t* scratch = (uint8_t*)temp_dev; uint64_t cap_jobs;
+    ScratchBlock owned; uint8_t* scratch = (uint8_t*)temp_dev; uint64_t cap_jobs;
     if (scratch)
     {
         cap_jobs = (temp_bytes / per_job) & ~63ull;                  // whole waves of 64 jobs
-        if (cap_jobs < 64)
-        {
-            if (aux) scratch_free( aux, s );
-            set_error( "invalid argument: temp_bytes too small (see nvbio_full_gotoh_traceback_temp_bytes)" );
-            return NVBIO_ERR_INVALID;
-        }
+        NVB_REQUIRE( cap_jobs >= 64, "temp_bytes too small (see nvbio_full_gotoh_traceback_temp_bytes)" );
     }
     else
     {
@@ -629,14 +620,8 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         const uint64_t budget = 8ull << 30;
         if (cap_jobs * per_job > budget) cap_jobs = budget / per_job;
         cap_jobs = (cap_jobs + 63u) & ~63ull;
-        if (scratch_alloc( &owned, cap_jobs * per_job, s ) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            if (aux) scratch_free( aux, s );
-            set_error( "full traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs );
-            return NVBIO_ERR_NOMEM;
-        }
-        scratch = (uint8_t*)owned;
+        NVB_CHECK( owned.alloc( cap_jobs * per_job, s, "full traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
+        scratch = owned.get();
     }
     nvbio_status st = NVBIO_OK;
     if (band_ok)
@@ -667,8 +652,6 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
 #undef NVB_TB
         if (hipGetLastError() != hipSuccess) { set_error( "full traceback launch failed" ); st = NVBIO_ERR_HIP; }
     }
-    if (owned) scratch_free( owned, s );
-    if (aux)   scratch_free( aux, s );
     return st;
 }
 

@@ -580,8 +580,7 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
     const int32_t go_min = -(sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go), ge_min = -(sc.pat_ge > sc.txt_ge ? sc.pat_ge : sc.txt_ge);
     const bool narrow = band == 31 && type == NVBIO_SEMI_GLOBAL && sc.match == 0 && sc.mm_min >= 0 && sc.mm_max >= 0 && plain_gotoh( sc ) &&
                         ge_min > 0 && go_min >= ge_min && !(b.algo & NVBIO_ALN_NO_NARROW_TRACEBACK);
-    void*     sel_temp  = nullptr;
-    void*     aux       = nullptr;
+    ScratchBlock aux;
     if (shortcut)
     {
         if (!(flags & NVBIO_TRACEBACK_SINKS_GIVEN))
@@ -590,23 +589,19 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         size_t sel_bytes = 0;
         hipcub::CountingInputIterator<uint32_t> ids( 0u );
         NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
-        const uint64_t flags_bytes = ((uint64_t)b.n + 255u) & ~255ull;
-        const uint64_t list_bytes  = ((uint64_t)b.n * 4u + 255u) & ~255ull;
-        if (scratch_alloc( &aux, 2u * (flags_bytes + list_bytes + 256u) + list_bytes + 256u + sel_bytes, s ) != hipSuccess)
+        void* sel_temp;
+        NVB_CHECK( aux.alloc_layout( s, "banded traceback: out of device memory for the job list", [&](ScratchLayout& c)
         {
-            (void)hipGetLastError();
-            set_error( "banded traceback: out of device memory for the job list" );
-            return NVBIO_ERR_NOMEM;
-        }
-        need_dp   = (uint8_t*)aux;
-        job_list  = (uint32_t*)((uint8_t*)aux + flags_bytes);
-        job_count = (uint32_t*)((uint8_t*)aux + flags_bytes + list_bytes);
-        band_off   = (uint8_t*)aux + flags_bytes + list_bytes + 256u;
-        job_list2  = (uint32_t*)(band_off + flags_bytes);
-        job_count2 = (uint32_t*)(band_off + flags_bytes + list_bytes);
-        job_list3  = (uint32_t*)((uint8_t*)aux + 2u * (flags_bytes + list_bytes + 256u));
-        job_count3 = (uint32_t*)((uint8_t*)job_list3 + list_bytes);
-        sel_temp   = (uint8_t*)aux + 2u * (flags_bytes + list_bytes + 256u) + list_bytes + 256u;
+            need_dp    = c.take<uint8_t>( b.n );
+            job_list   = c.take<uint32_t>( b.n );
+            job_count  = c.take<uint32_t>( 1 );
+            band_off   = c.take<uint8_t>( b.n );
+            job_list2  = c.take<uint32_t>( b.n );
+            job_count2 = c.take<uint32_t>( 1 );
+            job_list3  = c.take<uint32_t>( b.n );
+            job_count3 = c.take<uint32_t>( 1 );
+            sel_temp   = c.take<uint8_t>( sel_bytes );
+        } ) );
         nvbio_status st1;
 #define NVB_BAND(B) st1 = launch_ungapped_type<B>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (const uint2*)sinks_dev, \
                                                    (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp,             \
@@ -619,7 +614,7 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         default: NVB_BAND(31); break;
         }
 #undef NVB_BAND
-        if (st1 != NVBIO_OK) { scratch_free( aux, s ); return st1; }
+        NVB_CHECK( st1 );
         // ---- 3. the jobs that do need the DP, compacted (their number stays on the device) ----
         hipcub::TransformInputIterator<uint8_t, IsCode<1>, const uint8_t*> is_full( need_dp, IsCode<1>() );
         hipcub::TransformInputIterator<uint8_t, IsCode<2>, const uint8_t*> is_narrow( need_dp, IsCode<2>() );
@@ -627,23 +622,18 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         if (e == hipSuccess && narrow) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is_narrow, job_list2, job_count2, (int)b.n, s );
         hipcub::TransformInputIterator<uint8_t, IsCode<3>, const uint8_t*> is_narrow7( need_dp, IsCode<3>() );
         if (e == hipSuccess && narrow) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is_narrow7, job_list3, job_count3, (int)b.n, s );
-        if (e != hipSuccess) { scratch_free( aux, s ); set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+        if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     }
 
     // ---- 4. the DP with direction vectors + walk back, over the job list (or every job) ----
     const uint64_t per_job = (uint64_t)b.max_read_len * row_bytes( band );
-    void*     owned = nullptr;
+    ScratchBlock owned;
     uint32_t* dirs  = (uint32_t*)temp_dev;
     uint64_t  cap_jobs;
     if (dirs)
     {
         cap_jobs = temp_bytes / per_job;
-        if (!(cap_jobs >= 64 || cap_jobs >= b.n))
-        {
-            if (aux) scratch_free( aux, s );
-            set_error( "invalid argument: temp_bytes too small (see nvbio_banded_gotoh_traceback_temp_bytes)" );
-            return NVBIO_ERR_INVALID;
-        }
+        NVB_REQUIRE( cap_jobs >= 64 || cap_jobs >= b.n, "temp_bytes too small (see nvbio_banded_gotoh_traceback_temp_bytes)" );
     }
     else
     {
@@ -654,14 +644,8 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         const uint64_t budget = 16ull << 30;                     // at most 16 GiB of scratch per launch
         if (cap_jobs * per_job > budget) cap_jobs = budget / per_job;
         if (cap_jobs < 64) cap_jobs = 64;
-        if (scratch_alloc( &owned, cap_jobs * per_job, s ) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            if (aux) scratch_free( aux, s );
-            set_error( "banded traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs );
-            return NVBIO_ERR_NOMEM;
-        }
-        dirs = (uint32_t*)owned;
+        NVB_CHECK( owned.alloc( cap_jobs * per_job, s, "banded traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
+        dirs = (uint32_t*)owned.get();
     }
     nvbio_status st = NVBIO_OK;
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
@@ -696,8 +680,6 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
                                  (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s, band_off );
         }
     }
-    if (owned) scratch_free( owned, s );
-    if (aux)   scratch_free( aux, s );
     return st;
 }
 

@@ -464,14 +464,14 @@ nvbio_status nvbio_read_queue_filter(int device, const uint32_t* queue_dev, uint
     NVB_REQUIRE( read_flags_dev && queue_out_dev, "NULL device pointer" );
     NVB_REQUIRE( n < (1u << 31), "n too large" );
     const ReadFlagSet pred = { read_flags_dev };
-    size_t bytes = 0; void* tmp = nullptr;
+    size_t bytes = 0;
     hipcub::CountingInputIterator<uint32_t> ids( 0u );
     if (queue_dev) NVB_HIP( hipcub::DeviceSelect::If( nullptr, bytes, queue_dev, queue_out_dev, count_dev, (int)n, pred, s ) );
     else           NVB_HIP( hipcub::DeviceSelect::If( nullptr, bytes, ids, queue_out_dev, count_dev, (int)n, pred, s ) );
-    if (scratch_alloc( &tmp, bytes ? bytes : 16, s ) != hipSuccess) { (void)hipGetLastError(); set_error( "read_queue_filter: out of device memory" ); return NVBIO_ERR_NOMEM; }
-    const hipError_t e = queue_dev ? hipcub::DeviceSelect::If( tmp, bytes, queue_dev, queue_out_dev, count_dev, (int)n, pred, s )
-                                   : hipcub::DeviceSelect::If( tmp, bytes, ids, queue_out_dev, count_dev, (int)n, pred, s );
-    scratch_free( tmp, s );
+    ScratchBlock tmp;
+    NVB_CHECK( tmp.alloc( bytes, s, "read_queue_filter: out of device memory" ) );
+    const hipError_t e = queue_dev ? hipcub::DeviceSelect::If( tmp.get(), bytes, queue_dev, queue_out_dev, count_dev, (int)n, pred, s )
+                                   : hipcub::DeviceSelect::If( tmp.get(), bytes, ids, queue_out_dev, count_dev, (int)n, pred, s );
     if (e != hipSuccess) { set_error( "read_queue_filter failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVBIO_OK;
 }
@@ -485,12 +485,12 @@ nvbio_status nvbio_select_flagged_indices(int device, const uint8_t* flags_dev, 
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( flags_dev && queue_out_dev, "NULL device pointer" );
     NVB_REQUIRE( n < (1u << 31), "n too large" );
-    size_t bytes = 0; void* tmp = nullptr;
+    size_t bytes = 0;
     hipcub::CountingInputIterator<uint32_t> ids( 0u );
     NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, bytes, ids, flags_dev, queue_out_dev, count_dev, (int)n, s ) );
-    if (scratch_alloc( &tmp, bytes ? bytes : 16, s ) != hipSuccess) { (void)hipGetLastError(); set_error( "select_flagged_indices: out of device memory" ); return NVBIO_ERR_NOMEM; }
-    const hipError_t e = hipcub::DeviceSelect::Flagged( tmp, bytes, ids, flags_dev, queue_out_dev, count_dev, (int)n, s );
-    scratch_free( tmp, s );
+    ScratchBlock tmp;
+    NVB_CHECK( tmp.alloc( bytes, s, "select_flagged_indices: out of device memory" ) );
+    const hipError_t e = hipcub::DeviceSelect::Flagged( tmp.get(), bytes, ids, flags_dev, queue_out_dev, count_dev, (int)n, s );
     if (e != hipSuccess) { set_error( "select_flagged_indices failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVBIO_OK;
 }
