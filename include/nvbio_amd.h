@@ -52,6 +52,14 @@ nvbio_status nvbio_amd_device_arch(int device, char* name, uint32_t name_len);
 nvbio_status nvbio_amd_stream_synchronize(int device, void* stream);
 /* hipFree every scratch block that no call is using (see "Conventions"); each behind a synchronisation of the stream it served */
 nvbio_status nvbio_amd_release_scratch(void);
+/* check mode: every scratch block exact-size, guard-banded, filled with `fill`; set only between calls */
+nvbio_status nvbio_amd_set_scratch_check(int enable, uint32_t fill_byte);
+/* one text line per site seen since the last enable: "<tag> <blocks checked> <blocks damaged> <first bad sub-array> <first bad offset>"
+ * (a test tool: with check mode on, each scratch block is a fresh hipMalloc with a 4 KiB guard band at each end, a layout leaves 256 bytes before
+ * each sub-array and after the last, a caller's temp_dev is filled whole, so the *_temp_bytes queries grow: query after enabling.  When the block
+ * goes out of use its bands and gaps are read back.  The first bad sub-array is the one that precedes the first damaged byte, -1 before the
+ * first; the offset is in bytes from the block's first sub-array.  A clean site prints "- -" for both.) */
+nvbio_status nvbio_amd_scratch_check_report(char* buf, uint64_t buf_len);
 
 /* -------------------------------------------------------------------------------------------
  * pair of uint32, layout-compatible with the reference's uint2 (SA ranges, hits, sinks)

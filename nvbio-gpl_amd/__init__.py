@@ -128,6 +128,25 @@ def release_scratch():
     _check(lib().nvbio_amd_release_scratch())
 
 
+def set_scratch_check(enable, fill_byte=0):
+    """nvbio_amd_set_scratch_check: a test tool.  Enabled, every scratch block is a fresh exact-size allocation between two guard
+    bands, its layout leaves a gap around each sub-array, and all of it (a caller's temp included) is filled with `fill_byte` before
+    any work; enabling clears the report.  Switch it only between calls; query *_temp_bytes after switching."""
+    _check(lib().nvbio_amd_set_scratch_check(ctypes.c_int(1 if enable else 0), ctypes.c_uint32(fill_byte)))
+
+
+def scratch_check_report():
+    """nvbio_amd_scratch_check_report, parsed: {tag: (blocks checked, blocks damaged, first bad sub-array, first bad offset)}, the
+    last two None for a clean site"""
+    buf = ctypes.create_string_buffer(1 << 16)
+    _check(lib().nvbio_amd_scratch_check_report(buf, ctypes.c_uint64(len(buf))))
+    out = {}
+    for line in buf.value.decode().splitlines():
+        tag, checked, damaged, sub, off = line.split()
+        out[tag] = (int(checked), int(damaged), None if sub == "-" else int(sub), None if off == "-" else int(off))
+    return out
+
+
 def _check(status):
     if status != 0:
         raise NvbioError(status, lib().nvbio_amd_last_error().decode())

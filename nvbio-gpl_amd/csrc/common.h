@@ -35,40 +35,58 @@ const char* get_error();
 // `s` after the call; the ScratchBlock's destruction gives it back at once, for the next call on the SAME stream (whose work runs behind everything
 // that used the block).  Blocks are plain hipMalloc allocations cached per (device, stream).  Why not hipMallocAsync / hipFreeAsync: on ROCm 7.2 a
 // block RE-used from the default pool did not hold what a kernel had just written into it -- the flags of the banded scorer's first pass read back as
-// zeros in the second call of a process (seen with hipMemcpy right behind the kernel; with hipMalloc / hipFree in its place: never), and once in a few
-// fresh-box runs the gap chance read zeros there in production (61,818 reads of 10 M scored -20 instead of -18).  core.hip.
+// zeros in the second call of a process (seen with hipMemcpy right behind the kernel; with hipMalloc / hipFree in its place: never).  A few fresh-box
+// runs also scored 61,818 reads of 10 M -20 instead of -18 in production; that those read zeros from a pool block is inferred, not observed.  What
+// is established: under the scratch check mode below (exact-size guard-banded blocks filled with 0x00, 0xFF or 0x02) every site's parity cases
+// equal the oracle and no band or gap is touched (tests/test_gpu_scratch_check.py), so no library kernel overruns its scratch or reads scratch it
+// did not write at the tested shapes; and a cached block that still holds the previous batch's flags gives the oracle's results.  core.hip.
 void scratch_release_idle();                              // hipFree every idle block (each behind a synchronisation of its stream)
+
+// Scratch check mode (nvbio_amd_set_scratch_check, a test tool, off by default): every ScratchBlock takes a fresh exact-size hipMalloc with a
+// guard band at each end, the layouts leave a gap before each sub-array and after the last, blocks (a caller's temp included) and BuildBuffers are
+// filled with one byte before any work, and each block's bands and gaps are read back when it is given back.  core.hip.
+bool    scratch_check_enabled();
+uint8_t scratch_check_fill();
 
 // The sub-arrays of one scratch block in order, declared once per site by code that runs twice: over ScratchLayout() it only adds up their
 // sizes, over ScratchLayout( block ) it also hands out their pointers.  Every sub-array starts on a 256-byte boundary (hipcub temporaries need that).
+// With `check` (check mode, read once per block) every sub-array is preceded by a gap of 256 bytes and the last one followed by one; `extents`,
+// when given, receives each sub-array's [begin, end) in the block.
 class ScratchLayout
 {
 public:
-    explicit ScratchLayout(uint8_t* base = nullptr) : base_( base ) {}
+    static const uint64_t GAP = 256u;
+    explicit ScratchLayout(uint8_t* base = nullptr, bool check = false, std::vector<uint64_t>* extents = nullptr)
+        : base_( base ), check_( check ), extents_( extents ) {}
     template <typename T> T* take(uint64_t count)
     {
-        const uint64_t at = round( end_ );
+        const uint64_t at = round( end_ ) + (check_ ? GAP : 0u);
         end_ = at + count * sizeof(T);
+        if (extents_) { extents_->push_back( at ); extents_->push_back( end_ ); }
         return base_ ? (T*)(base_ + at) : nullptr;
     }
-    uint64_t end() const   { return end_; }                      // the bytes a block must hold
-    uint64_t bytes() const { return round( end_ ) + 256u; }      // the bytes a caller's buffer must hold: room to align its start
+    uint64_t end() const   { return check_ ? round( end_ ) + GAP : end_; }   // the bytes a block must hold
+    uint64_t bytes() const { return round( end() ) + 256u; }               // the bytes a caller's buffer must hold: room to align its start
 private:
     static uint64_t round(uint64_t x) { return (x + 255u) & ~255ull; }
     uint8_t* base_;
+    bool     check_;
+    std::vector<uint64_t>* extents_;
     uint64_t end_ = 0;
 };
 
+struct ScratchCheckState;                                  // the check-mode bookkeeping of one block (core.hip)
+
 // The scratch of one call: a block of the cache above for stream `s` (alloc), or the caller's temp_dev (adopt).  Only a block it took from the
-// cache is given back, when it goes out of scope -- so every exit of the call gives it back.
+// cache is given back, when it goes out of scope -- so every exit of the call gives it back.  `tag` names the site in the check-mode report.
 class ScratchBlock
 {
 public:
     ScratchBlock() = default;
-    ScratchBlock(ScratchBlock&& o) noexcept : p_( o.p_ ), s_( o.s_ ), own_( o.own_ ) { o.p_ = nullptr; o.own_ = false; }
+    ScratchBlock(ScratchBlock&& o) noexcept : p_( o.p_ ), s_( o.s_ ), own_( o.own_ ), chk_( o.chk_ ) { o.p_ = nullptr; o.own_ = false; o.chk_ = nullptr; }
     ScratchBlock& operator=(ScratchBlock&& o) noexcept
     {
-        if (this != &o) { release(); p_ = o.p_; s_ = o.s_; own_ = o.own_; o.p_ = nullptr; o.own_ = false; }
+        if (this != &o) { release(); p_ = o.p_; s_ = o.s_; own_ = o.own_; chk_ = o.chk_; o.p_ = nullptr; o.own_ = false; o.chk_ = nullptr; }
         return *this;
     }
     ScratchBlock(const ScratchBlock&) = delete;
@@ -76,31 +94,38 @@ public:
     ~ScratchBlock() { release(); }
 
     // `bytes` of the cache for work on `s`; out of memory: the message printf( fmt, ... ) and NVBIO_ERR_NOMEM
-    nvbio_status alloc(uint64_t bytes, hipStream_t s, const char* fmt, ...);
+    nvbio_status alloc(const char* tag, uint64_t bytes, hipStream_t s, const char* fmt, ...);
     // the block for the sub-arrays that layout( ScratchLayout& ) declares, run once to size it and once to set the site's pointers into it:
     // alloc (msg: a format given the block's bytes as unsigned long long), or adopt when the caller passes its temp (sized by `query`)
     template <typename Layout>
-    nvbio_status alloc_layout(hipStream_t s, const char* msg, Layout layout, void* temp = nullptr, uint64_t temp_bytes = 0, const char* query = nullptr)
+    nvbio_status alloc_layout(const char* tag, hipStream_t s, const char* msg, Layout layout, void* temp = nullptr, uint64_t temp_bytes = 0,
+                              const char* query = nullptr)
     {
-        ScratchLayout size; layout( size );
-        NVB_CHECK( temp ? adopt( temp, temp_bytes, size.end(), query ) : alloc( size.end(), s, msg, (unsigned long long)size.end() ) );
-        ScratchLayout c( p_ ); layout( c );
+        const bool check = scratch_check_enabled();
+        ScratchLayout size( nullptr, check ); layout( size );
+        NVB_CHECK( temp ? adopt( tag, temp, temp_bytes, size.end(), query, s, check )
+                        : alloc_impl( tag, size.end(), s, check, msg, (unsigned long long)size.end() ) );
+        ScratchLayout c( p_, check, check ? extents() : nullptr ); layout( c );
         return NVBIO_OK;
     }
     uint8_t* get() const { return p_; }
 
 private:
+    nvbio_status alloc_impl(const char* tag, uint64_t bytes, hipStream_t s, bool check, const char* fmt, ...);
+    nvbio_status alloc_v(const char* tag, uint64_t bytes, hipStream_t s, bool check, const char* fmt, va_list ap);
     // the caller's `temp_bytes` at `temp`, its start aligned up to 256, of which `bytes` must remain: else "temp_bytes too small (<query>)"
     // and NVBIO_ERR_INVALID
-    nvbio_status adopt(void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query);
+    nvbio_status adopt(const char* tag, void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query, hipStream_t s, bool check);
+    std::vector<uint64_t>* extents();                      // check mode: the sub-array extents the pointer pass records
     void release();
     uint8_t*    p_   = nullptr;
     hipStream_t s_   = nullptr;
     bool        own_ = false;
+    ScratchCheckState* chk_ = nullptr;                     // check mode only
 };
 
 // RAII for the hipMalloc temporaries of an index build (not the stream scratch above): every buffer it allocated and was not told to
-// forget (ownership handed over) is freed when it goes out of scope
+// forget (ownership handed over) is freed when it goes out of scope.  In check mode each buffer is filled (no guard bands) before it is handed out.
 struct BuildBuffers
 {
     std::vector<void*> ptrs;
@@ -108,8 +133,13 @@ struct BuildBuffers
     template <typename T> T* alloc(size_t count)            // nullptr when out of memory
     {
         void* p = nullptr;
-        if (hipMalloc( &p, (count ? count : 1) * sizeof(T) ) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        const size_t bytes = (count ? count : 1) * sizeof(T);
+        if (hipMalloc( &p, bytes ) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         ptrs.push_back( p );
+        if (scratch_check_enabled() && (hipMemset( p, scratch_check_fill(), bytes ) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+        {
+            (void)hipGetLastError(); return nullptr;
+        }
         return (T*)p;
     }
     void release(void* p)

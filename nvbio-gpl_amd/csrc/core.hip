@@ -1,6 +1,8 @@
 // core.hip -- status/error plumbing and device selection of the C ABI.
 #include "common.h"
+#include <atomic>
 #include <mutex>
+#include <string>
 #include <vector>
 
 namespace nvbio_amd {
@@ -94,24 +96,82 @@ void scratch_release_idle()
     release_idle( [](const CachedBlock&) { return true; } );
 }
 
-nvbio_status ScratchBlock::alloc(uint64_t bytes, hipStream_t s, const char* fmt, ...)
+// ---- scratch check mode: see common.h ----
+struct ScratchCheckState
+{
+    const char*           tag;
+    uint8_t*              base;         // what check mode hipMalloc'ed (nullptr: the caller's temp)
+    int64_t               lo, hi;       // the checked span around p_: [p_ + lo, p_ + hi)
+    std::vector<uint64_t> extents;      // the sub-arrays' [begin, end) pairs
+};
+
+namespace {
+struct CheckRecord { uint64_t checked = 0, damaged = 0; int64_t first_sub = -1, first_off = 0; };
+std::atomic<bool>                  g_check_on{ false };
+uint8_t                            g_check_fill = 0;
+std::mutex                         g_check_mutex;
+std::vector<std::pair<std::string, CheckRecord>> g_check_report;    // in the order the sites were first seen
+const int64_t CHECK_BAND = 4096;                                     // guard band at each end of a block check mode allocates
+
+CheckRecord& check_record(const char* tag)
+{
+    for (auto& r : g_check_report) if (r.first == tag) return r.second;
+    g_check_report.emplace_back( tag, CheckRecord() );
+    return g_check_report.back().second;
+}
+}
+
+bool    scratch_check_enabled() { return g_check_on.load( std::memory_order_relaxed ); }
+uint8_t scratch_check_fill()    { return g_check_fill; }
+
+nvbio_status ScratchBlock::alloc(const char* tag, uint64_t bytes, hipStream_t s, const char* fmt, ...)
+{
+    va_list ap;
+    va_start( ap, fmt );
+    const nvbio_status st = alloc_v( tag, bytes, s, scratch_check_enabled(), fmt, ap );
+    va_end( ap );
+    return st;
+}
+
+nvbio_status ScratchBlock::alloc_impl(const char* tag, uint64_t bytes, hipStream_t s, bool check, const char* fmt, ...)
+{
+    va_list ap;
+    va_start( ap, fmt );
+    const nvbio_status st = alloc_v( tag, bytes, s, check, fmt, ap );
+    va_end( ap );
+    return st;
+}
+
+nvbio_status ScratchBlock::alloc_v(const char* tag, uint64_t bytes, hipStream_t s, bool check, const char* fmt, va_list ap)
 {
     release();
+    if (check)
+    {
+        // a fresh exact-size block between two guard bands, all of it filled before any work of the call
+        void* p = nullptr;
+        if (hipMalloc( &p, bytes + 2 * CHECK_BAND ) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            vsnprintf( g_error, sizeof(g_error), fmt, ap );
+            return NVBIO_ERR_NOMEM;
+        }
+        chk_ = new ScratchCheckState{ tag, (uint8_t*)p, -CHECK_BAND, (int64_t)bytes + CHECK_BAND, { 0, bytes } };
+        p_ = (uint8_t*)p + CHECK_BAND; s_ = s; own_ = false;
+        NVB_HIP( hipMemsetAsync( p, g_check_fill, bytes + 2 * CHECK_BAND, s ) );
+        return NVBIO_OK;
+    }
     void* p = nullptr;
     if (scratch_alloc( &p, bytes, s ) != hipSuccess)
     {
         (void)hipGetLastError();
-        va_list ap;
-        va_start( ap, fmt );
         vsnprintf( g_error, sizeof(g_error), fmt, ap );
-        va_end( ap );
         return NVBIO_ERR_NOMEM;
     }
     p_ = (uint8_t*)p; s_ = s; own_ = true;
     return NVBIO_OK;
 }
 
-nvbio_status ScratchBlock::adopt(void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query)
+nvbio_status ScratchBlock::adopt(const char* tag, void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query, hipStream_t s, bool check)
 {
     release();
     const uint64_t skip = (256u - ((uintptr_t)temp & 255u)) & 255u;
@@ -121,12 +181,58 @@ nvbio_status ScratchBlock::adopt(void* temp, uint64_t temp_bytes, uint64_t bytes
         return NVBIO_ERR_INVALID;
     }
     p_ = (uint8_t*)temp + skip;
+    if (check)
+    {
+        // the caller's whole buffer is filled; checked: the alignment skip, the gaps and at most a band's worth behind the layout
+        const uint64_t tail = temp_bytes - skip - bytes;
+        chk_ = new ScratchCheckState{ tag, nullptr, -(int64_t)skip, (int64_t)(bytes + (tail < (uint64_t)CHECK_BAND ? tail : (uint64_t)CHECK_BAND)), { 0, bytes } };
+        s_ = s;
+        NVB_HIP( hipMemsetAsync( temp, g_check_fill, temp_bytes, s ) );
+    }
     return NVBIO_OK;
+}
+
+std::vector<uint64_t>* ScratchBlock::extents()
+{
+    if (!chk_) return nullptr;
+    chk_->extents.clear();                                  // the layout's sub-arrays replace the whole-block extent
+    return &chk_->extents;
 }
 
 void ScratchBlock::release()
 {
     if (own_) scratch_free( p_, s_ );
+    if (chk_)
+    {
+        // check mode: once the call's work has drained, every byte of the bands and gaps must still hold the fill
+        ScratchCheckState& c = *chk_;
+        if (hipStreamSynchronize( s_ ) == hipSuccess)
+        {
+            bool bad = false; int64_t bad_sub = -1, bad_off = 0;
+            std::vector<uint8_t> h;
+            int64_t from = c.lo;
+            const size_t n = c.extents.size() / 2;
+            for (size_t i = 0; i <= n && !bad; ++i)
+            {
+                const int64_t to = i < n ? (int64_t)c.extents[2 * i] : c.hi;            // the gap behind sub-array i - 1
+                if (to > from)
+                {
+                    h.resize( (size_t)(to - from) );
+                    if (hipMemcpy( h.data(), p_ + from, h.size(), hipMemcpyDeviceToHost ) != hipSuccess) { (void)hipGetLastError(); break; }
+                    for (size_t k = 0; k < h.size(); ++k)
+                        if (h[k] != g_check_fill) { bad = true; bad_sub = (int64_t)i - 1; bad_off = from + (int64_t)k; break; }
+                }
+                if (i < n) from = (int64_t)c.extents[2 * i + 1];
+            }
+            std::lock_guard<std::mutex> lock( g_check_mutex );
+            CheckRecord& r = check_record( c.tag );
+            ++r.checked;
+            if (bad && r.damaged++ == 0) { r.first_sub = bad_sub; r.first_off = bad_off; }
+        }
+        else (void)hipGetLastError();
+        if (c.base) (void)hipFree( c.base );
+        delete chk_; chk_ = nullptr;
+    }
     p_ = nullptr; own_ = false;
 }
 
@@ -172,6 +278,33 @@ extern "C" {
 int         nvbio_amd_version(void)    { return NVBIO_AMD_VERSION; }
 nvbio_status nvbio_amd_release_scratch(void) { scratch_release_idle(); return NVBIO_OK; }
 const char* nvbio_amd_last_error(void) { return get_error(); }
+
+nvbio_status nvbio_amd_set_scratch_check(int enable, uint32_t fill_byte)
+{
+    NVB_REQUIRE( fill_byte <= 0xFFu, "fill_byte must be a byte" );
+    std::lock_guard<std::mutex> lock( g_check_mutex );
+    if (enable) { g_check_report.clear(); g_check_fill = (uint8_t)fill_byte; }
+    g_check_on.store( enable != 0 );
+    return NVBIO_OK;
+}
+
+nvbio_status nvbio_amd_scratch_check_report(char* buf, uint64_t buf_len)
+{
+    NVB_REQUIRE( buf != nullptr && buf_len > 0, "buf is NULL" );
+    std::lock_guard<std::mutex> lock( g_check_mutex );
+    std::string out;
+    char line[256];
+    for (const auto& r : g_check_report)
+    {
+        if (r.second.damaged) snprintf( line, sizeof(line), "%s %llu %llu %lld %lld\n", r.first.c_str(), (unsigned long long)r.second.checked,
+                                        (unsigned long long)r.second.damaged, (long long)r.second.first_sub, (long long)r.second.first_off );
+        else                  snprintf( line, sizeof(line), "%s %llu 0 - -\n", r.first.c_str(), (unsigned long long)r.second.checked );
+        out += line;
+    }
+    NVB_REQUIRE( out.size() < buf_len, "buf_len too small for the report" );
+    memcpy( buf, out.c_str(), out.size() + 1 );
+    return NVBIO_OK;
+}
 
 nvbio_status nvbio_amd_device_count(int* count)
 {

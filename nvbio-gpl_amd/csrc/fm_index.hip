@@ -1517,7 +1517,7 @@ nvbio_status nvbio_fm_filter_scan(nvbio_fm_index_t index, const nvbio_uint2* ran
     size_t temp_bytes = 0;
     NVB_HIP( hipcub::DeviceScan::InclusiveSum( nullptr, temp_bytes, sizes, slots_dev, (int)n_queries, s ) );
     ScratchBlock temp;
-    NVB_CHECK( temp.alloc( temp_bytes, s, "filter_scan: out of device memory" ) );
+    NVB_CHECK( temp.alloc( "fm_filter_scan", temp_bytes, s, "filter_scan: out of device memory" ) );
     const hipError_t e = hipcub::DeviceScan::InclusiveSum( temp.get(), temp_bytes, sizes, slots_dev, (int)n_queries, s );
     if (e != hipSuccess) { set_error( "filter_scan: scan failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     NVB_HIP( hipMemcpyAsync( n_hits, slots_dev + (n_queries - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, s ) );
@@ -1603,7 +1603,7 @@ nvbio_status nvbio_fm_hamming_backtrack(nvbio_fm_index_t index, const nvbio_stri
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     ScratchBlock temp;
-    NVB_CHECK( temp.alloc( sizeof(uint32_t), s, "hamming_backtrack: out of device memory" ) );
+    NVB_CHECK( temp.alloc( "fm_hamming_backtrack", sizeof(uint32_t), s, "hamming_backtrack: out of device memory" ) );
     uint32_t* overflow = (uint32_t*)temp.get();
     NVB_HIP( hipMemsetAsync( overflow, 0, sizeof(uint32_t), s ) );
     const DevIndex f = idx->dev();
@@ -1672,7 +1672,7 @@ nvbio_status nvbio_fm_match_seed_diagonals_temp_bytes(const nvbio_string_set* se
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
     SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, false, &L ) );
-    ScratchLayout c; L.carve( c ); *bytes = c.bytes();
+    ScratchLayout c( nullptr, scratch_check_enabled() ); L.carve( c ); *bytes = c.bytes();
     return NVBIO_OK;
 }
 
@@ -1702,7 +1702,7 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
     NVB_REQUIRE( keys_dev && residual_ranges_dev && residual_ids_dev, "NULL device pointer" );
     SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, false, &L ) );
     ScratchBlock temp;
-    NVB_CHECK( temp.alloc_layout( s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
+    NVB_CHECK( temp.alloc_layout( "fm_seed_pass", s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
                                   temp_dev, temp_bytes, "nvbio_fm_match_seed_diagonals_temp_bytes" ) );
     uint64_t* tile_keys = L.tile_keys; uint32_t* tile_counts = L.tile_counts;
     const DevIndex f = idx->dev();
@@ -1751,7 +1751,7 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_temp_bytes(const nvbio_string_se
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
     SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
-    ScratchLayout c; L.carve( c ); *bytes = c.bytes();
+    ScratchLayout c( nullptr, scratch_check_enabled() ); L.carve( c ); *bytes = c.bytes();
     return NVBIO_OK;
 }
 
@@ -1794,7 +1794,7 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
     NVB_REQUIRE( keys_dev && residual_ranges_dev && residual_ids_dev, "NULL device pointer" );
     SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
     ScratchBlock temp;
-    NVB_CHECK( temp.alloc_layout( s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
+    NVB_CHECK( temp.alloc_layout( "fm_seed_pass_both", s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
                                   temp_dev, temp_bytes, "nvbio_fm_match_seed_diagonals_both_temp_bytes" ) );
     uint64_t* tile_keys = L.tile_keys; uint32_t* tile_counts = L.tile_counts; uint32_t* tile_defer = L.tile_defer; uint32_t* defer_counts = L.defer_counts;
     const DevIndex f = idx->dev();
@@ -1934,7 +1934,7 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
     // scratch: sorted ids | sorted ranges | sort temp
     uint32_t* ids_s; uint64_t* rng_s; void* tmp;
     ScratchBlock aux;
-    NVB_CHECK( aux.alloc_layout( s, "residual diagonals: out of device memory", [&](ScratchLayout& c)
+    NVB_CHECK( aux.alloc_layout( "fm_residual_diagonals", s, "residual diagonals: out of device memory", [&](ScratchLayout& c)
                                  { ids_s = c.take<uint32_t>( n ); rng_s = c.take<uint64_t>( n ); tmp = c.take<uint8_t>( sort_bytes ); } ) );
     hipError_t e = hipcub::DeviceRadixSort::SortPairs( tmp, sort_bytes, ids_dev, ids_s, (const uint64_t*)ranges_dev, rng_s, (int)n, 0, 32, s );
     if (e == hipSuccess)

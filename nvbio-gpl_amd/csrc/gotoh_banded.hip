@@ -1421,7 +1421,7 @@ static nvbio_status sort_jobs_by_length(const BatchDev& b, const uint32_t* job_l
     NVB_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, sort_bytes, (const uint16_t*)nullptr, (uint16_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                  (int)b.n, 0, bits, s ) );
     uint16_t *k_in, *k_out; uint32_t *l_all, *l_out, *c_all; void* tmp;
-    NVB_CHECK( aux->alloc_layout( s, "banded score: out of device memory for the length-sorted job list", [&](ScratchLayout& c)
+    NVB_CHECK( aux->alloc_layout( "banded_length_sort", s, "banded score: out of device memory for the length-sorted job list", [&](ScratchLayout& c)
     {
         k_in  = c.take<uint16_t>( b.n ); k_out = c.take<uint16_t>( b.n );
         l_all = c.take<uint32_t>( b.n ); l_out = c.take<uint32_t>( b.n );
@@ -1493,7 +1493,7 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         if (part_bytes > sel_bytes) sel_bytes = part_bytes;
         uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *counts; void* sel_temp;
         ScratchBlock aux;
-        NVB_CHECK( aux.alloc_layout( s, "banded score: out of device memory for the job list", [&](ScratchLayout& c)
+        NVB_CHECK( aux.alloc_layout( "banded_job_list", s, "banded score: out of device memory for the job list", [&](ScratchLayout& c)
         {
             need_dp  = c.take<uint8_t>( b.n );
             job_list = c.take<uint32_t>( b.n );

@@ -1351,7 +1351,7 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         const bool narrow = shortcut && !text_blocking && !(b.algo & (NVBIO_ALN_NO_NARROW_SCORE | NVBIO_ALN_NO_PACKED_DP)) && max_pattern_len <= 161u &&
                             banded31_packed_ok( sc, max_pattern_len ) && sc.pat_ge < 0;
         uint8_t *need_dp, *to_packed, *to_plain, *route; uint32_t *counts, *list_n, *wb2, *we2; void* sel_temp;
-        NVB_CHECK( aux.alloc_layout( s, "full Gotoh: out of device memory for the job lists", [&](ScratchLayout& c)
+        NVB_CHECK( aux.alloc_layout( "full_job_lists", s, "full Gotoh: out of device memory for the job lists", [&](ScratchLayout& c)
         {
             need_dp   = c.take<uint8_t>( b.n );
             to_packed = c.take<uint8_t>( b.n );
@@ -1434,7 +1434,7 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         const uint64_t budget = 8ull << 30;                      // at most 8 GiB of scratch per launch
         if (cap_jobs * rows * sizeof(uint32_t) > budget) cap_jobs = budget / (rows * sizeof(uint32_t));
         if (cap_jobs < 64) cap_jobs = 64;
-        NVB_CHECK( owned.alloc( cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
+        NVB_CHECK( owned.alloc( "full_columns", cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
         column = (uint32_t*)owned.get();
     }
     nvbio_status st = NVBIO_OK;
@@ -1527,7 +1527,7 @@ extern "C" nvbio_status nvbio_full_gotoh_score_best2(int device, nvbio_alignment
     if (cap_jobs * rows * sizeof(uint32_t) > budget) cap_jobs = budget / (rows * sizeof(uint32_t));
     if (cap_jobs < 64) cap_jobs = 64;
     ScratchBlock temp;
-    NVB_CHECK( temp.alloc( cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
+    NVB_CHECK( temp.alloc( "full_best2_columns", cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
     uint32_t* column = (uint32_t*)temp.get();
     nvbio_status st = NVBIO_OK;
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)

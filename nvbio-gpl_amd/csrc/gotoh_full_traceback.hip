@@ -571,7 +571,7 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         hipcub::CountingInputIterator<uint32_t> ids( 0u );
         NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
         void* sel_temp;
-        NVB_CHECK( aux.alloc_layout( s, "full traceback: out of device memory for the job list", [&](ScratchLayout& c)
+        NVB_CHECK( aux.alloc_layout( "full_tb_job_list", s, "full traceback: out of device memory for the job list", [&](ScratchLayout& c)
         {
             need_dp    = c.take<uint8_t>( b.n );
             job_list   = c.take<uint32_t>( b.n );
@@ -620,7 +620,7 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         const uint64_t budget = 8ull << 30;
         if (cap_jobs * per_job > budget) cap_jobs = budget / per_job;
         cap_jobs = (cap_jobs + 63u) & ~63ull;
-        NVB_CHECK( owned.alloc( cap_jobs * per_job, s, "full traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
+        NVB_CHECK( owned.alloc( "full_tb_dirs", cap_jobs * per_job, s, "full traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
         scratch = owned.get();
     }
     nvbio_status st = NVBIO_OK;

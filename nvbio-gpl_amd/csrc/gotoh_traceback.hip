@@ -590,7 +590,7 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         hipcub::CountingInputIterator<uint32_t> ids( 0u );
         NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
         void* sel_temp;
-        NVB_CHECK( aux.alloc_layout( s, "banded traceback: out of device memory for the job list", [&](ScratchLayout& c)
+        NVB_CHECK( aux.alloc_layout( "banded_tb_job_list", s, "banded traceback: out of device memory for the job list", [&](ScratchLayout& c)
         {
             need_dp    = c.take<uint8_t>( b.n );
             job_list   = c.take<uint32_t>( b.n );
@@ -644,7 +644,7 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         const uint64_t budget = 16ull << 30;                     // at most 16 GiB of scratch per launch
         if (cap_jobs * per_job > budget) cap_jobs = budget / per_job;
         if (cap_jobs < 64) cap_jobs = 64;
-        NVB_CHECK( owned.alloc( cap_jobs * per_job, s, "banded traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
+        NVB_CHECK( owned.alloc( "banded_tb_dirs", cap_jobs * per_job, s, "banded traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
         dirs = (uint32_t*)owned.get();
     }
     nvbio_status st = NVBIO_OK;

@@ -132,7 +132,7 @@ nvbio_status nvbio_rank_dictionary_build(int device, const nvbio_rank_dictionary
     // scratch: per-block symbol counts | their exclusive sums (4 x nb each) | scan temp
     uint32_t* cnt; uint64_t* sums; void* temp;
     ScratchBlock aux;
-    NVB_CHECK( aux.alloc_layout( s, "rank_dictionary_build: out of device memory", [&](ScratchLayout& c)
+    NVB_CHECK( aux.alloc_layout( "rank_dictionary_build", s, "rank_dictionary_build: out of device memory", [&](ScratchLayout& c)
                                  { cnt = c.take<uint32_t>( 4ull * nb ); sums = c.take<uint64_t>( 4ull * nb ); temp = c.take<uint8_t>( temp_bytes ); } ) );
     if (dict->word_bits == 32) hipLaunchKernelGGL( block_symbol_counts_kernel<uint32_t>, dim3( grid_for( nb ) ), dim3(256), 0, s, (const uint32_t*)dict->text_dev, dict->length, dict->K, nb, cnt );
     else                       hipLaunchKernelGGL( block_symbol_counts_kernel<uint64_t>, dim3( grid_for( nb ) ), dim3(256), 0, s, (const uint64_t*)dict->text_dev, dict->length, dict->K, nb, cnt );

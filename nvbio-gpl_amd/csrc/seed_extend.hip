@@ -678,6 +678,7 @@ extern "C" nvbio_status nvbio_sort_unique_keys_temp_bytes(uint64_t n, uint64_t* 
     size_t work_bytes = 0; NVB_CHECK( sort_unique_work_bytes( n, &work_bytes ) );
     // (up to 256 bytes more than the layout of nvbio_sort_unique_keys needs: the number callers have always sized their buffers by, kept)
     *bytes = ((work_bytes + 255u) & ~255ull) + n * sizeof(uint64_t) + 512u;
+    if (scratch_check_enabled()) *bytes += 3u * ScratchLayout::GAP;        // check mode: the gaps before both sub-arrays and after the last
     return NVBIO_OK;
 }
 
@@ -692,7 +693,7 @@ extern "C" nvbio_status nvbio_sort_unique_keys(int device, uint64_t* keys_dev, u
     // scratch: sorted keys | the sort's and the unique's temporaries
     uint64_t* sorted; void* work;
     ScratchBlock temp;
-    NVB_CHECK( temp.alloc_layout( s, "sort_unique_keys: out of device memory", [&](ScratchLayout& c) { sorted = c.take<uint64_t>( n ); work = c.take<uint8_t>( work_bytes ); },
+    NVB_CHECK( temp.alloc_layout( "sort_unique_keys", s, "sort_unique_keys: out of device memory", [&](ScratchLayout& c) { sorted = c.take<uint64_t>( n ); work = c.take<uint8_t>( work_bytes ); },
                                   temp_dev, temp_bytes, "nvbio_sort_unique_keys_temp_bytes" ) );
     hipError_t e = hipcub::DeviceRadixSort::SortKeys( work, work_bytes, (const uint64_t*)keys_dev, sorted, (int)n, 0, 64, s );
     if (e == hipSuccess) e = hipcub::DeviceSelect::Unique( work, work_bytes, (const uint64_t*)sorted, keys_dev, n_out_dev, (int)n, s );

@@ -469,7 +469,7 @@ nvbio_status nvbio_read_queue_filter(int device, const uint32_t* queue_dev, uint
     if (queue_dev) NVB_HIP( hipcub::DeviceSelect::If( nullptr, bytes, queue_dev, queue_out_dev, count_dev, (int)n, pred, s ) );
     else           NVB_HIP( hipcub::DeviceSelect::If( nullptr, bytes, ids, queue_out_dev, count_dev, (int)n, pred, s ) );
     ScratchBlock tmp;
-    NVB_CHECK( tmp.alloc( bytes, s, "read_queue_filter: out of device memory" ) );
+    NVB_CHECK( tmp.alloc( "read_queue_filter", bytes, s, "read_queue_filter: out of device memory" ) );
     const hipError_t e = queue_dev ? hipcub::DeviceSelect::If( tmp.get(), bytes, queue_dev, queue_out_dev, count_dev, (int)n, pred, s )
                                    : hipcub::DeviceSelect::If( tmp.get(), bytes, ids, queue_out_dev, count_dev, (int)n, pred, s );
     if (e != hipSuccess) { set_error( "read_queue_filter failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
@@ -489,7 +489,7 @@ nvbio_status nvbio_select_flagged_indices(int device, const uint8_t* flags_dev, 
     hipcub::CountingInputIterator<uint32_t> ids( 0u );
     NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, bytes, ids, flags_dev, queue_out_dev, count_dev, (int)n, s ) );
     ScratchBlock tmp;
-    NVB_CHECK( tmp.alloc( bytes, s, "select_flagged_indices: out of device memory" ) );
+    NVB_CHECK( tmp.alloc( "select_flagged_indices", bytes, s, "select_flagged_indices: out of device memory" ) );
     const hipError_t e = hipcub::DeviceSelect::Flagged( tmp.get(), bytes, ids, flags_dev, queue_out_dev, count_dev, (int)n, s );
     if (e != hipSuccess) { set_error( "select_flagged_indices failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVBIO_OK;
