@@ -393,6 +393,54 @@ nvbio_status nvbio_fm_filter_locate(nvbio_fm_index_t index, const nvbio_uint2* r
                                     nvbio_uint2* hits_dev, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * SMEM seeding: MEMFilter<device_tag, fm_index> (nvbio/fmindex/mem.h, mem_inl.h:1303-1528) over a forward index and the
+ * index of the reversed text (csrc/mem.hip).
+ *
+ * rank finds, for every read, its maximal exact matches in the reference's passes: right (forward extension with the reverse
+ * index from x = 0, x = max(end, x + 1)), left (backward extension with the forward index), discard (per group, in entry order:
+ * keep iff span begin < the left-most begin kept so far, span length >= min_span and occurrences <= max_intv; the device
+ * filter's rule -- the marker moves only for kept MEMs), and, when split_len < 0xFFFFFFFF, split (a kept MEM with span >=
+ * split_len and occurrences <= split_width is replaced by the forward extension from its midpoint with min_intv = occurrences
+ * + 1, then left and discard again).  Reads are plain string sets (2-, 4- or 8-bit, symbols > 3 are N) of at most 65535 symbols.
+ *
+ * Departures from the reference (its defects):
+ *   - ranges are exact SA intervals of their spans: the reference's extend_forward leaves out the suffix P$, which puts its
+ *     forward ranges one row low;
+ *   - span begins are not masked to 8 bits (the reference's MEMRange::span() is wrong from 256 symbols on);
+ *   - inside a read the ranges are in ascending (span begin, span end) order (the reference leaves each read's last group
+ *     unreversed);
+ *   - nothing is dropped for capacity: a short buffer fails with NVBIO_ERR_INVALID and a message naming the size needed.
+ * Working storage is the caller's temp only; the scratch check mode (nvbio_amd_set_scratch_check) does not cover these calls.
+ * ------------------------------------------------------------------------------------------- */
+
+/* MEMRange<uint32>: SA range [x, y], string id | 0x80000000 on the first kept MEM of a group, span begin | span end << 16 */
+typedef struct { uint32_t x, y, string_id, span; } nvbio_mem_range;
+/* MEMHit<uint32>: text position, string id, span [begin, end) */
+typedef struct { uint32_t pos, string_id, span_begin, span_end; } nvbio_mem_hit;
+/* the reference's defaults (mem.h:306-314): min_intv 1, max_intv 0xFFFFFFFF, min_span 1, split_len 0xFFFFFFFF (no split),
+ * split_width 0xFFFFFFFF */
+typedef struct { uint32_t min_intv, max_intv, min_span, split_len, split_width; } nvbio_mem_params;
+
+/* the temp bytes nvbio_mem_filter_rank needs for these reads (a ragged set's offsets are read from the device: synchronizes) */
+nvbio_status nvbio_mem_filter_temp_bytes(const nvbio_string_set* reads, const nvbio_mem_params* params, uint64_t* bytes, void* stream);
+/* MEMFilter::rank.  ranges_dev / slots_dev: max_ranges entries; first_range_dev: reads->n + 1 entries, first_range[i] = index of
+ * string i's first range (first_hit(i) = slots[first_range[i] - 1], 0 for the first).  slots = inclusive scan (uint64) of the range
+ * sizes.  *n_ranges, *n_mems (host) = ranges and MEM occurrences; *records (optional, host) = the 32-byte bwt_occ records the
+ * passes gathered.  f_index and r_index must have the same length and L2 (NVBIO_ERR_INVALID otherwise); seed-enumerated sets are
+ * rejected.  max_ranges too small: NVBIO_ERR_INVALID, *n_ranges = the number needed.  temp too small (the split pass may need more
+ * than nvbio_mem_filter_temp_bytes): NVBIO_ERR_INVALID, the message names the bytes needed.  Either failure is found only after
+ * the passes before it have run, and a rerun repeats every pass: without split, max_ranges = the reads' symbol total (a read has at
+ * most one range per symbol) and the temp of nvbio_mem_filter_temp_bytes always suffice; with split, keep the sizes a call needed
+ * for the next batch (the mirrors do).  Synchronizes. */
+nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_index, const nvbio_string_set* reads,
+                                   const nvbio_mem_params* params, nvbio_mem_range* ranges_dev, uint32_t max_ranges,
+                                   uint32_t* first_range_dev, uint64_t* slots_dev, void* temp_dev, uint64_t temp_bytes,
+                                   uint32_t* n_ranges, uint64_t* n_mems, uint64_t* records, void* stream);
+/* MEMFilter::locate: hits_dev[h - begin] for the MEM occurrences h in [begin, end), end <= *n_mems (checked: reads slots, synchronizes) */
+nvbio_status nvbio_mem_filter_locate(nvbio_fm_index_t f_index, const nvbio_mem_range* ranges_dev, const uint64_t* slots_dev,
+                                     uint32_t n_ranges, uint64_t begin, uint64_t end, nvbio_mem_hit* hits_dev, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * seed hits -> candidate windows: the two index-arithmetic functors between FMIndexFilter::locate
  * and the banded aligner in the reference's smallest seed-and-extend caller (examples/fmmap/fmmap.cu)
  * ------------------------------------------------------------------------------------------- */

@@ -7,6 +7,7 @@ argument meaning as the reference's C++ templates --
 
     FMIndex                      nvbio::fm_index / io::FMIndexDataDevice   (nvbio/fmindex/fmindex.h:320-557)
     FMIndexFilter                nvbio::FMIndexFilter<device_tag,...>      (nvbio/fmindex/filter.h:52-231)
+    MEMFilter                    nvbio::MEMFilter<device_tag,...>          (nvbio/fmindex/mem.h, mem_inl.h:1303-1528)
     SimpleGotohScheme, GotohAligner, BestSink semantics                    (nvbio/alignment/utils.h:103-123, alignment.h:437-449)
     BatchedBandedAlignmentScore, batch_banded_alignment_score              (nvbio/alignment/batched.h:104-298)
 
@@ -585,6 +586,125 @@ class FMIndexFilter:
 
     def slots(self):
         return self._slots
+
+
+class _MemParams(ctypes.Structure):
+    _fields_ = [("min_intv", ctypes.c_uint32), ("max_intv", ctypes.c_uint32), ("min_span", ctypes.c_uint32),
+                ("split_len", ctypes.c_uint32), ("split_width", ctypes.c_uint32)]
+
+
+MEM_GROUP_FLAG = 1 << 31
+MEM_UNLIMITED = 0xFFFFFFFF
+
+
+class MEMFilter:
+    """nvbio::MEMFilter<device_tag, fm_index_type> (nvbio/fmindex/mem.h:270-360): the maximal exact matches of every read over a
+    forward index and the index of the reversed text (nvbio_mem_filter_*; the departures from the reference are listed in
+    include/nvbio_amd.h)."""
+
+    def __init__(self):
+        self._index = None
+        self._ranges = self._slots = self._first = self._temp = None
+        self._n_ranges = self._n_mems = self._n_queries = 0
+        self.records = 0                             # bwt_occ records the last rank() gathered
+        self.attempts = 0                            # library calls the last rank() made (1 unless a buffer had to grow)
+
+    @staticmethod
+    def _symbols(string_set):
+        """the symbols of a plain string set: a bound on its MEM ranges without split (a read has at most one range per symbol)"""
+        n = string_set.n
+        if n and string_set.offsets is not None and string_set.ranges:
+            ends = string_set.offsets[[0, n]].cpu().numpy().astype(np.uint32).astype(np.int64)
+            return int(ends[1] - ends[0])
+        return n * string_set.fixed_len
+
+    def rank(self, f_index, r_index, string_set, min_intv=1, max_intv=MEM_UNLIMITED, min_span=1, split_len=MEM_UNLIMITED,
+             split_width=MEM_UNLIMITED, max_ranges=None):
+        """enact the filter; returns the total number of MEM occurrences (mem_inl.h:1303-1445).
+        max_ranges None: the range buffers hold the reads' symbol total (a bound without split) or what an earlier call needed,
+        whichever is larger, and grow when a split call needs more -- a call that has to grow repeats every pass, so a filter
+        reused over batches pays that at most once.  An explicit max_ranges that is too small raises NvbioError naming the
+        number needed (so does a temp that is too small)."""
+        torch = _torch()
+        dev = f_index.device
+        params = _MemParams(min_intv, max_intv, min_span, split_len, split_width)
+        qs = string_set.c_struct()
+        tb = ctypes.c_uint64(0)
+        _check(lib().nvbio_mem_filter_temp_bytes(ctypes.byref(qs), ctypes.byref(params), ctypes.byref(tb), _stream_ptr(dev)))
+        n = string_set.n
+        self._index, self._n_queries = f_index, n
+        self._first = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        if max_ranges is None:
+            held = 0 if self._ranges is None or self._ranges.device != torch.device(dev) else self._ranges.shape[0]
+            cap = max(1, held, self._symbols(string_set))
+        else:
+            cap = max(1, int(max_ranges))
+        if self._ranges is None or self._ranges.shape[0] != cap or self._ranges.device != torch.device(dev):
+            self._ranges = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            self._slots = torch.empty(cap, dtype=torch.int64, device=dev)
+        if self._temp is None or self._temp.numel() < tb.value or self._temp.device != torch.device(dev):
+            self._temp = torch.empty(max(int(tb.value), 1), dtype=torch.uint8, device=dev)
+        self.attempts = 0
+        while True:
+            nr, nm, rec = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+            self.attempts += 1
+            st = lib().nvbio_mem_filter_rank(f_index._h, r_index._h, ctypes.byref(qs), ctypes.byref(params), _ptr(self._ranges),
+                                             ctypes.c_uint32(cap), _ptr(self._first), _ptr(self._slots), _ptr(self._temp),
+                                             ctypes.c_uint64(self._temp.numel()), ctypes.byref(nr), ctypes.byref(nm), ctypes.byref(rec),
+                                             _stream_ptr(dev))
+            if st == 1 and max_ranges is None:
+                msg = lib().nvbio_amd_last_error().decode()
+                if "max_ranges" in msg and nr.value > cap:
+                    cap = nr.value
+                    self._ranges = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+                    self._slots = torch.empty(cap, dtype=torch.int64, device=dev)
+                    continue
+                if "temp_bytes" in msg:
+                    import re
+                    need = int(re.search(r"needs (\d+)", msg).group(1))
+                    if need > self._temp.numel():
+                        self._temp = None
+                        self._temp = torch.empty(need, dtype=torch.uint8, device=dev)
+                        continue
+            _check(st)
+            break
+        self._n_ranges, self._n_mems, self.records = nr.value, nm.value, rec.value
+        return self._n_mems
+
+    @property
+    def n_ranges(self):
+        return self._n_ranges
+
+    def n_mems(self):
+        return self._n_mems
+
+    def ranges(self):
+        """[n_ranges, 4] int32 (uint32 bits): SA x, SA y, string id | MEM_GROUP_FLAG, span begin | span end << 16"""
+        return self._ranges[:self._n_ranges]
+
+    def slots(self):
+        return self._slots[:self._n_ranges]
+
+    def first_ranges(self):
+        """[n_strings + 1]: the index of every string's first range"""
+        return self._first
+
+    def first_hit(self, string_id):
+        """index of the first MEM occurrence of string_id (mem_inl.h:1449-1461); n_mems past the last string"""
+        if string_id >= self._n_queries:
+            return self._n_mems
+        r = int(self._first[string_id].item())
+        return int(self._slots[r - 1].item()) if r else 0
+
+    def locate(self, begin, end, hits=None):
+        """hits[h - begin] = (text position, string id, span begin, span end) for MEM occurrences [begin, end) (mem_inl.h:1463-1505)"""
+        torch = _torch()
+        if hits is None:
+            hits = torch.empty((max(end - begin, 0), 4), dtype=torch.int32, device=self._index.device)
+        if end > begin:
+            _check(lib().nvbio_mem_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), ctypes.c_uint32(self._n_ranges),
+                                                 ctypes.c_uint64(begin), ctypes.c_uint64(end), _ptr(hits), _stream_ptr(self._index.device)))
+        return hits
 
 
 # ---- alignment ---------------------------------------------------------------------------------

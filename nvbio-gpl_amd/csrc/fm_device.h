@@ -125,6 +125,20 @@ __device__ __forceinline__ void search_step(const DevIndex& f, uint32_t& x, uint
     y = base + vh;
 }
 
+// the device view of a handle and the device it lives on (fm_index.hip)
+nvbio_status fm_handle_dev(nvbio_fm_index_t index, DevIndex* d, int* device);
+
+// first i in [lo, hi) with a[i] > v (hi if none): the slot of a global hit index in an inclusive scan of range sizes
+__device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__ a, uint32_t lo, uint32_t hi, const uint64_t v)
+{
+    while (lo < hi)
+    {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] <= v) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+
 // one LF step of locate(): j -> L2[c] + rank(fmi,j,c) with c = bwt[j] (or 0 at the primary row)
 __device__ __forceinline__ uint32_t lf_step(const DevIndex& f, const uint32_t j)
 {

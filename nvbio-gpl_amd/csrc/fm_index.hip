@@ -893,16 +893,6 @@ struct RangeSize
 // upper_bound runs over a few cached entries instead of log2(n_queries) HBM round trips.
 constexpr uint32_t FILTER_TILE = 256u * 8u;
 
-__device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__ a, uint32_t lo, uint32_t hi, const uint64_t v)
-{
-    while (lo < hi)
-    {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-
 // seed enumeration of a hit's query id -> its diagonal key (hit_to_diagonal, examples/fmmap/fmmap.cu:92-117; see
 // nvbio_hits_to_diagonals): with KEYS the expansion writes the 8-byte key instead of the (position, query) pair
 // qid: optional seed id of every query; read_offsets / intervals: ragged reads (every read's length and seed interval)
@@ -1334,6 +1324,14 @@ nvbio_status fm_index_adopt(const nvbio_fm_index_view* view, int device, uint32_
 } // namespace nvbio_amd
 
 using namespace nvbio_amd;
+
+nvbio_status nvbio_amd::fm_handle_dev(nvbio_fm_index_t index, DevIndex* d, int* device)
+{
+    NVB_REQUIRE( index != nullptr, "index is NULL" );
+    const FMIndexImpl* idx = (const FMIndexImpl*)index;
+    *d = idx->dev(); *device = idx->device;
+    return NVBIO_OK;
+}
 
 extern "C" {
 

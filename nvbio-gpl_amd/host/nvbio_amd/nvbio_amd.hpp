@@ -8,6 +8,8 @@
 //   match / locate                 ~ the free functions of nvbio/fmindex/fmindex.h:370-557, batched over a set
 //   FMIndexFilter<amd_device_tag>  ~ nvbio::FMIndexFilter<device_tag,fm_index> (nvbio/fmindex/filter.h:136-231):
 //                                    rank(index, string_set) -> n_hits ; locate(begin, end, hits) ; owns ranges/slots
+//   MEMFilter<amd_device_tag>      ~ nvbio::MEMFilter<device_tag,fm_index> (nvbio/fmindex/mem.h:270-360):
+//                                    rank(f_index, r_index, string_set, min_intv, ...) -> n_mems ; first_hit ; locate(begin, end, mems)
 //   aln::SimpleGotohScheme, aln::GotohAligner<TYPE,scheme>, aln::make_gotoh_aligner<TYPE>()
 //                                  ~ nvbio/alignment/utils.h:103-123, alignment.h:437-462
 //   aln::BatchedBandedAlignmentScore<BAND, stream, AmdDeviceScheduler>
@@ -296,6 +298,104 @@ private:
     device_vector<uint64_t>    m_slots;
     device_vector<uint8_t>     m_direct;
     bool                       m_is_direct = false;
+};
+
+template <typename system_tag> class MEMFilter;
+
+// the maximal exact matches of every string over a forward index and the index of the reversed text (nvbio_mem_filter_*; the
+// reference's semantics and this library's departures from them are listed in nvbio_amd.h).  Owns its ranges, slots and temp,
+// grown to what a call needs: nothing is dropped.
+template <>
+class MEMFilter<amd_device_tag>
+{
+public:
+    typedef fm_index        fm_index_type;
+    typedef nvbio_mem_range rank_type;      // MEMRange<uint32>
+    typedef nvbio_mem_hit   mem_type;       // MEMHit<uint32>
+    typedef mem_type        hit_type;
+
+    MEMFilter() : m_f_index( nullptr ), m_n_queries( 0 ), m_n_ranges( 0 ), m_n_occurrences( 0 ), m_records( 0 ) {}
+
+    // enact the filter (mem_inl.h:1303-1445); returns the total number of MEM occurrences
+    uint64_t rank(const fm_index& f_index, const fm_index& r_index, const string_set& set,
+                  uint32_t min_intv = 1u, uint32_t max_intv = 0xFFFFFFFFu, uint32_t min_span = 1u,
+                  uint32_t split_len = 0xFFFFFFFFu, uint32_t split_width = 0xFFFFFFFFu, hipStream_t stream = 0)
+    {
+        m_f_index = &f_index; m_n_queries = set.size();
+        const nvbio_mem_params p = { min_intv, max_intv, min_span, split_len, split_width };
+        uint64_t temp_bytes = 0;
+        check( nvbio_mem_filter_temp_bytes( &set.c, &p, &temp_bytes, stream ) );
+        m_first.resize( m_n_queries + 1u );
+        // the reads' symbol total bounds the ranges without split; the buffers keep what earlier calls needed, so only a split
+        // call that needs more than both repeats its passes (once: the grown buffers stay)
+        const uint64_t bound = symbols( set );
+        if (m_mem_ranges.size() < bound) { m_mem_ranges.resize( bound ); m_slots.resize( bound ); }
+        for (;;)
+        {
+            if (m_temp.size() < temp_bytes) m_temp.resize( temp_bytes );
+            uint32_t n_ranges = 0;
+            const nvbio_status st = nvbio_mem_filter_rank( f_index.handle(), r_index.handle(), &set.c, &p, m_mem_ranges.data(),
+                                                           (uint32_t)m_mem_ranges.size(), m_first.data(), m_slots.data(), m_temp.data(),
+                                                           m_temp.size(), &n_ranges, &m_n_occurrences, &m_records, stream );
+            if (st == NVBIO_ERR_INVALID && n_ranges > m_mem_ranges.size())          // max_ranges too small: grow to the count it names
+            {
+                m_mem_ranges.resize( n_ranges ); m_slots.resize( n_ranges );
+                continue;
+            }
+            const std::string msg = st == NVBIO_OK ? std::string() : std::string( nvbio_amd_last_error() );
+            const size_t at = msg.find( "needs " );
+            if (st == NVBIO_ERR_INVALID && msg.find( "temp_bytes" ) != std::string::npos && at != std::string::npos)
+            {
+                const uint64_t need = std::stoull( msg.substr( at + 6 ) );             // the split pass needs more temp
+                if (need > m_temp.size()) { temp_bytes = need; continue; }
+            }
+            check( st );
+            m_n_ranges = n_ranges;
+            return m_n_occurrences;
+        }
+    }
+    // index of the first MEM occurrence of string_id (mem_inl.h:1449-1461); reads two words from the device
+    uint64_t first_hit(uint32_t string_id) const
+    {
+        if (string_id >= m_n_queries) return m_n_occurrences;
+        uint32_t r = 0; uint64_t h = 0;
+        check_hip( hipMemcpy( &r, m_first.data() + string_id, 4, hipMemcpyDeviceToHost ), "MEMFilter::first_hit" );
+        if (r) check_hip( hipMemcpy( &h, m_slots.data() + (r - 1u), 8, hipMemcpyDeviceToHost ), "MEMFilter::first_hit" );
+        return h;
+    }
+    // the MEM occurrences [begin, end) into caller-owned device memory (mem_inl.h:1463-1505)
+    void locate(uint64_t begin, uint64_t end, mem_type* mems_dev, hipStream_t stream = 0) const
+    {
+        if (end > begin) check( nvbio_mem_filter_locate( m_f_index->handle(), m_mem_ranges.data(), m_slots.data(), m_n_ranges, begin, end, mems_dev, stream ) );
+    }
+    // the symbols of a plain string set (a ragged set's two end offsets are read from the device)
+    static uint64_t symbols(const string_set& set)
+    {
+        if (set.c.n == 0) return 1u;
+        if (set.c.offsets_dev && set.c.offsets_are_ranges)
+        {
+            uint32_t a = 0, b = 0;
+            check_hip( hipMemcpy( &a, set.c.offsets_dev, 4, hipMemcpyDeviceToHost ), "MEMFilter::rank" );
+            check_hip( hipMemcpy( &b, set.c.offsets_dev + set.c.n, 4, hipMemcpyDeviceToHost ), "MEMFilter::rank" );
+            return b > a ? b - a : 1u;
+        }
+        return set.c.n * (uint64_t)set.c.fixed_len + 1u;
+    }
+    uint32_t n_queries() const { return m_n_queries; }
+    uint32_t n_ranges()  const { return m_n_ranges; }
+    uint64_t n_mems()    const { return m_n_occurrences; }
+    uint64_t records()   const { return m_records; }                  // bwt_occ records the last rank() gathered
+    const rank_type* mem_ranges()   const { return m_mem_ranges.data(); }
+    const uint64_t*  slots()        const { return m_slots.data(); }
+    const uint32_t*  first_ranges() const { return m_first.data(); }  // n_queries + 1 entries
+private:
+    const fm_index*          m_f_index;
+    uint32_t                 m_n_queries, m_n_ranges;
+    uint64_t                 m_n_occurrences, m_records;
+    device_vector<rank_type> m_mem_ranges;
+    device_vector<uint64_t>  m_slots;
+    device_vector<uint32_t>  m_first;
+    device_vector<uint8_t>   m_temp;
 };
 
 namespace aln {
