@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nvbio_amd.h"
@@ -151,6 +152,28 @@ struct BuildBuffers
         for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase( ptrs.begin() + i ); return; }
     }
 };
+
+// ---- runtime value -> template argument ------------------------------------------------------
+// Values<...> lists the values a template is instantiated for, BitsList<Bits<r, t>, ...> the (read_bits, text_bits) pairs.
+// with_value( list, v, f, miss ) returns f( std::integral_constant<int, V>() ) for the listed V equal to v, with_bits( list, rbits,
+// tbits, f, miss ) returns f( Bits<r, t>() ) for the listed pair equal to (rbits, tbits); either returns miss() when the list holds no
+// such entry, so that each call site keeps its own status and message.  Every entry instantiates f; the choice is a chain of compares.
+template <int... Vs> struct Values {};
+template <int R, int T> struct Bits { static constexpr int r = R, t = T; };
+template <typename... Ps> struct BitsList {};
+
+template <int... Vs, typename F, typename Miss>
+inline auto with_value(Values<Vs...>, const int v, F&& f, Miss&& miss) -> decltype(miss())
+{
+    decltype(miss()) r{};
+    return ((v == Vs && ((r = f( std::integral_constant<int, Vs>() )), true)) || ...) ? r : miss();
+}
+template <typename... Ps, typename F, typename Miss>
+inline auto with_bits(BitsList<Ps...>, const uint32_t rbits, const uint32_t tbits, F&& f, Miss&& miss) -> decltype(miss())
+{
+    decltype(miss()) r{};
+    return ((rbits == (uint32_t)Ps::r && tbits == (uint32_t)Ps::t && ((r = f( Ps() )), true)) || ...) ? r : miss();
+}
 
 // select the device and fail loudly if it is not a gfx950: there is no CPU fallback
 nvbio_status use_device(int device);

@@ -1024,6 +1024,8 @@ residual_locate_kernel(const DevIndex f, const uint2* __restrict__ ranges, const
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+using SymbolBits = Values<2, 4, 8>;                       // what make_set admits: every seed / match kernel is instantiated for each (common.h: with_value)
+
 static nvbio_status make_set(const nvbio_string_set* s, StringSetDev* d)
 {
     NVB_REQUIRE( s != nullptr, "queries is NULL" );
@@ -1411,17 +1413,13 @@ nvbio_status nvbio_fm_match(nvbio_fm_index_t index, const nvbio_string_set* quer
     const dim3 grid( grid_for( q.n ) ), block( 256 );
     hipStream_t s = (hipStream_t)stream;
     const bool use_table = (f.ktab != nullptr) && !(flags & NVBIO_FM_NO_KMER_TABLE);
-#define NVB_LAUNCH_MATCH(BITS)                                                                                              \
-    if (blocks_dev)    hipLaunchKernelGGL( (fm_match_kernel<BITS,true,false>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev ); \
-    else if (use_table) hipLaunchKernelGGL( (fm_match_kernel<BITS,false,true>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev ); \
-    else                hipLaunchKernelGGL( (fm_match_kernel<BITS,false,false>), grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev )
-    switch (queries->symbol_bits)
+    (void)with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
     {
-    case 2: NVB_LAUNCH_MATCH(2); break;
-    case 4: NVB_LAUNCH_MATCH(4); break;
-    default: NVB_LAUNCH_MATCH(8); break;
-    }
-#undef NVB_LAUNCH_MATCH
+        if (blocks_dev)     hipLaunchKernelGGL( (fm_match_kernel<BITS,true,false>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev );
+        else if (use_table) hipLaunchKernelGGL( (fm_match_kernel<BITS,false,true>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev );
+        else                hipLaunchKernelGGL( (fm_match_kernel<BITS,false,false>), grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev );
+        return true;
+    }, [] { return false; } );
     NVB_HIP( hipGetLastError() );
     return NVBIO_OK;
 }
@@ -1575,16 +1573,12 @@ nvbio_status nvbio_fm_match_direct(nvbio_fm_index_t index, const nvbio_string_se
     const dim3 grid( grid_for( q.n ) ), block( 256 );
     hipStream_t s = (hipStream_t)stream;
     const bool use_table = (f.ktab != nullptr) && !(flags & NVBIO_FM_NO_KMER_TABLE);
-#define NVB_LAUNCH_DIRECT(BITS)                                                                                              \
-    if (use_table) hipLaunchKernelGGL( (fm_match_kernel<BITS,false,true,true>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev ); \
-    else           hipLaunchKernelGGL( (fm_match_kernel<BITS,false,false,true>), grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev )
-    switch (queries->symbol_bits)
+    (void)with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
     {
-    case 2: NVB_LAUNCH_DIRECT(2); break;
-    case 4: NVB_LAUNCH_DIRECT(4); break;
-    default: NVB_LAUNCH_DIRECT(8); break;
-    }
-#undef NVB_LAUNCH_DIRECT
+        if (use_table) hipLaunchKernelGGL( (fm_match_kernel<BITS,false,true,true>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev );
+        else           hipLaunchKernelGGL( (fm_match_kernel<BITS,false,false,true>), grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev );
+        return true;
+    }, [] { return false; } );
     NVB_HIP( hipGetLastError() );
     return NVBIO_OK;
 }
@@ -1606,15 +1600,12 @@ nvbio_status nvbio_fm_hamming_backtrack(nvbio_fm_index_t index, const nvbio_stri
     NVB_HIP( hipMemsetAsync( overflow, 0, sizeof(uint32_t), s ) );
     const DevIndex f = idx->dev();
     const dim3 grid( grid_for( q.n, 128 ) ), block( 128 );
-#define NVB_LAUNCH_BT(BITS) hipLaunchKernelGGL( (fm_hamming_backtrack_kernel<BITS>), grid, block, 0, s, f, q, seed_len, mismatches, (flags & NVBIO_BACKTRACK_REFERENCE_QUIRKS) != 0, counts_dev, n_ranges_dev, \
-                                                (uint2*)ranges_dev, max_ranges, overflow )
-    switch (queries->symbol_bits)
+    (void)with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
     {
-    case 2: NVB_LAUNCH_BT(2); break;
-    case 4: NVB_LAUNCH_BT(4); break;
-    default: NVB_LAUNCH_BT(8); break;
-    }
-#undef NVB_LAUNCH_BT
+        hipLaunchKernelGGL( (fm_hamming_backtrack_kernel<BITS>), grid, block, 0, s, f, q, seed_len, mismatches, (flags & NVBIO_BACKTRACK_REFERENCE_QUIRKS) != 0,
+                            counts_dev, n_ranges_dev, (uint2*)ranges_dev, max_ranges, overflow );
+        return true;
+    }, [] { return false; } );
     uint32_t h_over = 0;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync( &h_over, overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s );
@@ -1713,20 +1704,16 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
     // the pipelined kernel serves the production shape: packed seeds of up to 32 symbols resolved by the direct table's contexts
     const bool pipe = !count && !(flags & NVBIO_FM_NO_PIPELINE) && seeds->symbol_bits != 8 && q.spr <= 64u && q.fixed_len <= 32u && f.dtab != nullptr &&
                       f.ktab != nullptr && !(flags & NVBIO_FM_NO_KMER_TABLE) && f.dctx != 0u && q.fixed_len >= f.dkmer && q.fixed_len - f.dkmer <= f.dctx;
-#define NVB_LAUNCH_SD(BITS) \
-    if (pipe)  hipLaunchKernelGGL( (fm_seed_pipe_kernel<(BITS == 8 ? 4 : BITS)>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts, \
-                                   (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev );                                              \
-    else if (count) hipLaunchKernelGGL( (fm_seed_tiles_kernel<BITS,true>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts, \
-                                   (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)(counts_dev + 2) );       \
-    else       hipLaunchKernelGGL( (fm_seed_tiles_kernel<BITS,false>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts, \
-                                   (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)nullptr )
-    switch (seeds->symbol_bits)
+    (void)with_value( SymbolBits(), seeds->symbol_bits, [&](auto BITS)
     {
-    case 2: NVB_LAUNCH_SD(2); break;
-    case 4: NVB_LAUNCH_SD(4); break;
-    default: NVB_LAUNCH_SD(8); break;
-    }
-#undef NVB_LAUNCH_SD
+        if (pipe)  hipLaunchKernelGGL( (fm_seed_pipe_kernel<(BITS == 8 ? 4 : BITS)>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
+                                       (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev );
+        else if (count) hipLaunchKernelGGL( (fm_seed_tiles_kernel<BITS,true>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
+                                       (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)(counts_dev + 2) );
+        else       hipLaunchKernelGGL( (fm_seed_tiles_kernel<BITS,false>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
+                                       (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)nullptr );
+        return true;
+    }, [] { return false; } );
     hipError_t e = hipGetLastError();
     size_t scan_bytes = L.scan_bytes;
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
@@ -1803,16 +1790,23 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
     // flags bits 8..11: a seed with up to that many hits on a strand leaves them all as keys (0/1: only one-hit seeds do)
     uint32_t inline_max = (flags >> 8) & 15u;
     inline_max = inline_max < 1u ? 1u : (inline_max > CTAB_INLINE ? CTAB_INLINE : inline_max);
-#define NVB_LAUNCH_SBD(BITS, CNT, W, D) hipLaunchKernelGGL( (fm_seed_both_kernel<BITS,CNT,W,D>), grid, block, 0, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts, \
-                                    (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,                         \
-                                    CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts )
-#define NVB_LAUNCH_SBW(BITS, W) do { if (count) NVB_LAUNCH_SBD( BITS, true, W, false ); else if (defer) NVB_LAUNCH_SBD( BITS, false, W, true ); \
-                                     else NVB_LAUNCH_SBD( BITS, false, W, false ); } while (0)
-#define NVB_LAUNCH_SB(BITS) do { if (idx->cwide) NVB_LAUNCH_SBW( BITS, true ); else NVB_LAUNCH_SBW( BITS, false ); } while (0)
-    if (seeds->symbol_bits == 2) NVB_LAUNCH_SB( 2 ); else NVB_LAUNCH_SB( 4 );
-#undef NVB_LAUNCH_SB
-#undef NVB_LAUNCH_SBW
-#undef NVB_LAUNCH_SBD
+    (void)with_value( Values<2, 4>(), seeds->symbol_bits, [&](auto BITS)
+    {
+        const auto launch = [&](auto CNT, auto W, auto D)
+        {
+            hipLaunchKernelGGL( (fm_seed_both_kernel<BITS,CNT,W,D>), grid, block, 0, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
+                                (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
+                                CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts );
+        };
+        const auto wide = [&](auto W)
+        {
+            if (count)      launch( std::true_type(),  W, std::false_type() );
+            else if (defer) launch( std::false_type(), W, std::true_type() );
+            else            launch( std::false_type(), W, std::false_type() );
+        };
+        if (idx->cwide) wide( std::true_type() ); else wide( std::false_type() );
+        return true;
+    }, [] { return false; } );
     hipError_t e = hipGetLastError();
     size_t scan_bytes = L.scan_bytes;
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
@@ -1965,11 +1959,13 @@ nvbio_status nvbio_seed_hits_map_approx(nvbio_fm_index_t index, nvbio_fm_index_t
     DeviceGuard g( fi->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     DevIndex f = fi->dev(), rf = ri->dev();
     const dim3 grid( grid_for( n_reads, 128 ) ), block( 128 );
-#define NVB_LAUNCH_MA(BITS) hipLaunchKernelGGL( (fm_map_approx_kernel<BITS>), grid, block, 0, (hipStream_t)stream, f, rf, reads_dev, read_queue_dev, n_reads, \
-                                                p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,   \
-                                                (uint2*)deques_dev, sizes_dev, reseed_dev )
-    switch (read_bits) { case 2: NVB_LAUNCH_MA(2); break; case 4: NVB_LAUNCH_MA(4); break; default: NVB_LAUNCH_MA(8); break; }
-#undef NVB_LAUNCH_MA
+    (void)with_value( SymbolBits(), read_bits, [&](auto BITS)
+    {
+        hipLaunchKernelGGL( (fm_map_approx_kernel<BITS>), grid, block, 0, (hipStream_t)stream, f, rf, reads_dev, read_queue_dev, n_reads,
+                            p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,
+                            (uint2*)deques_dev, sizes_dev, reseed_dev );
+        return true;
+    }, [] { return false; } );
     NVB_HIP( hipGetLastError() );
     return NVBIO_OK;
 }

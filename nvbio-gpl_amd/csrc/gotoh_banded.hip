@@ -1559,70 +1559,40 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
     return NVBIO_OK;
 }
 
-template <int BAND, int TYPE>
-static nvbio_status launch_bits(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
-                                int32_t* scores, uint2* sinks, hipStream_t s)
-{
-    if (BAND == 31 && plain_gotoh( sc ) && packed_ok( TYPE, sc, b.max_read_len ) && !(b.algo & NVBIO_ALN_NO_PACKED_DP))
-    {
-        if      (rbits == 4 && tbits == 2) return launch_pk<TYPE,4>( b, sc, scores, sinks, s );
-        else if (rbits == 2 && tbits == 2) return launch_pk<TYPE,2>( b, sc, scores, sinks, s );
-    }
-    const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
-#define NVB_GO(RB, TB) hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,RB,TB>), grid, block, 0, s, b, sc, scores, sinks )
-    if      (rbits == 4 && tbits == 2) NVB_GO(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO(2, 2);
-    else if (rbits == 8 && tbits == 2) NVB_GO(8, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO(8, 8);
-    else if (rbits == 4 && tbits == 8) NVB_GO(4, 8);
-    else if (rbits == 2 && tbits == 8) NVB_GO(2, 8);
-    else { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; }
-#undef NVB_GO
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
-}
-
-template <int BAND, int TYPE>
-static nvbio_status launch_staged_bits(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
-                                       const int32_t* min_scores, int32_t min_score, int32_t* scores, uint2* sinks, hipStream_t s)
-{
-    const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
-#define NVB_GO(RB, TB) hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,RB,TB,false,true>), grid, block, 0, s, b, sc, scores, sinks, \
-                                           0u, (int32_t*)nullptr, (uint2*)nullptr, min_scores, min_score )
-    if      (rbits == 4 && tbits == 2) NVB_GO(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO(2, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO(8, 8);
-    else { set_error( "staged scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; }
-#undef NVB_GO
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
-}
 template <int BAND>
-static nvbio_status launch_staged_type(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
-                                       const int32_t* min_scores, int32_t min_score, int32_t* scores, uint2* sinks, hipStream_t s)
+static nvbio_status launch_score(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
+                                 int32_t* scores, uint2* sinks, hipStream_t s)
 {
-    switch (type)
+    return with_value( AlnTypes(), type, [&](auto TYPE)
     {
-    case NVBIO_GLOBAL:      return launch_staged_bits<BAND,NVBIO_GLOBAL>     ( b, sc, rbits, tbits, min_scores, min_score, scores, sinks, s );
-    case NVBIO_LOCAL:       return launch_staged_bits<BAND,NVBIO_LOCAL>      ( b, sc, rbits, tbits, min_scores, min_score, scores, sinks, s );
-    case NVBIO_SEMI_GLOBAL: return launch_staged_bits<BAND,NVBIO_SEMI_GLOBAL>( b, sc, rbits, tbits, min_scores, min_score, scores, sinks, s );
-    }
-    set_error( "invalid alignment type %d", type );
-    return NVBIO_ERR_INVALID;
+        if (BAND == 31 && plain_gotoh( sc ) && packed_ok( TYPE, sc, b.max_read_len ) && !(b.algo & NVBIO_ALN_NO_PACKED_DP) &&
+            tbits == 2 && (rbits == 4 || rbits == 2))
+            return rbits == 4 ? launch_pk<TYPE,4>( b, sc, scores, sinks, s ) : launch_pk<TYPE,2>( b, sc, scores, sinks, s );
+        const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
+        return with_bits( BitsAll(), rbits, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t>), grid, block, 0, s, b, sc, scores, sinks );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+    }, [&] { return invalid_type( type ); } );
 }
 
 template <int BAND>
-static nvbio_status launch_type(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
-                                int32_t* scores, uint2* sinks, hipStream_t s)
+static nvbio_status launch_staged(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
+                                  const int32_t* min_scores, int32_t min_score, int32_t* scores, uint2* sinks, hipStream_t s)
 {
-    switch (type)
+    const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
+    return with_value( AlnTypes(), type, [&](auto TYPE)
     {
-    case NVBIO_GLOBAL:      return launch_bits<BAND,NVBIO_GLOBAL>     ( b, sc, rbits, tbits, scores, sinks, s );
-    case NVBIO_LOCAL:       return launch_bits<BAND,NVBIO_LOCAL>      ( b, sc, rbits, tbits, scores, sinks, s );
-    case NVBIO_SEMI_GLOBAL: return launch_bits<BAND,NVBIO_SEMI_GLOBAL>( b, sc, rbits, tbits, scores, sinks, s );
-    }
-    set_error( "invalid alignment type %d", type );
-    return NVBIO_ERR_INVALID;
+        return with_bits( BitsStaged(), rbits, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t,false,true>), grid, block, 0, s, b, sc, scores, sinks,
+                                0u, (int32_t*)nullptr, (uint2*)nullptr, min_scores, min_score );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "staged scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
+    }, [&] { return invalid_type( type ); } );
 }
 
 // the packed band-31 end-to-end kernel over a job list, for the full-matrix scorer's narrow route (gotoh_full.hip): 4- or 2-bit reads in a
@@ -1660,33 +1630,20 @@ nvbio_status make_batch(const nvbio_alignment_batch* in, BatchDev* b)
 
 using namespace nvbio_amd;
 
-template <int BAND, int TYPE>
-static nvbio_status launch_best2_bits(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t dist,
-                                      int32_t* scores, uint2* sinks, int32_t* scores2, uint2* sinks2, hipStream_t s)
+template <int BAND>
+static nvbio_status launch_best2(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t dist,
+                                 int32_t* scores, uint2* sinks, int32_t* scores2, uint2* sinks2, hipStream_t s)
 {
     const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
-#define NVB_GO2(RB, TB) hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,RB,TB,true>), grid, block, 0, s, b, sc, scores, sinks, dist, scores2, sinks2 )
-    if      (rbits == 4 && tbits == 2) NVB_GO2(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO2(2, 2);
-    else if (rbits == 8 && tbits == 2) NVB_GO2(8, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO2(8, 8);
-    else { set_error( "Best2Sink scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; }
-#undef NVB_GO2
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
-}
-template <int BAND>
-static nvbio_status launch_best2_type(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t dist,
-                                      int32_t* scores, uint2* sinks, int32_t* scores2, uint2* sinks2, hipStream_t s)
-{
-    switch (type)
+    return with_value( AlnTypes(), type, [&](auto TYPE)
     {
-    case NVBIO_GLOBAL:      return launch_best2_bits<BAND,NVBIO_GLOBAL>     ( b, sc, rbits, tbits, dist, scores, sinks, scores2, sinks2, s );
-    case NVBIO_LOCAL:       return launch_best2_bits<BAND,NVBIO_LOCAL>      ( b, sc, rbits, tbits, dist, scores, sinks, scores2, sinks2, s );
-    case NVBIO_SEMI_GLOBAL: return launch_best2_bits<BAND,NVBIO_SEMI_GLOBAL>( b, sc, rbits, tbits, dist, scores, sinks, scores2, sinks2, s );
-    }
-    set_error( "invalid alignment type %d", type );
-    return NVBIO_ERR_INVALID;
+        return with_bits( BitsBest2(), rbits, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t,true>), grid, block, 0, s, b, sc, scores, sinks, dist, scores2, sinks2 );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "Best2Sink scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
+    }, [&] { return invalid_type( type ); } );
 }
 
 extern "C" nvbio_status nvbio_banded_gotoh_score_best2(int device, uint32_t band, nvbio_alignment_type type,
@@ -1696,23 +1653,17 @@ extern "C" nvbio_status nvbio_banded_gotoh_score_best2(int device, uint32_t band
 {
     NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
-    if (band != 3 && band != 7 && band != 15 && band != 31)
-    {
-        set_error( "band %u is not instantiated (3, 7, 15, 31)", band );
-        return NVBIO_ERR_UNSUPPORTED;
-    }
+    NVB_CHECK( check_band( band, NVBIO_ERR_UNSUPPORTED ) );
     if (b.n == 0) return NVBIO_OK;
     NVB_REQUIRE( scores_dev && sinks_dev && scores2_dev && sinks2_dev, "NULL output pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     const SchemeDev sc = scheme_dev( scheme );
     hipStream_t s = (hipStream_t)stream;
-    switch (band)
+    return with_value( Bands(), band, [&](auto BAND)
     {
-    case 3:  return launch_best2_type<3> ( type, b, sc, batch->read_bits, batch->text_bits, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
-    case 7:  return launch_best2_type<7> ( type, b, sc, batch->read_bits, batch->text_bits, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
-    case 15: return launch_best2_type<15>( type, b, sc, batch->read_bits, batch->text_bits, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
-    default: return launch_best2_type<31>( type, b, sc, batch->read_bits, batch->text_bits, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
-    }
+        return launch_best2<BAND>( type, b, sc, batch->read_bits, batch->text_bits, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev,
+                                   (uint2*)sinks2_dev, s );
+    }, [] { return NVBIO_ERR_UNSUPPORTED; } );                             // (the band was checked)
 }
 
 static nvbio_status banded_score(int device, uint32_t band, int type, const SchemeDev sc, const BatchDev& b, const nvbio_alignment_batch* batch,
@@ -1720,13 +1671,10 @@ static nvbio_status banded_score(int device, uint32_t band, int type, const Sche
 {
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    switch (band)
+    return with_value( Bands(), band, [&](auto BAND)
     {
-    case 3:  return launch_type<3> ( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s );
-    case 7:  return launch_type<7> ( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s );
-    case 15: return launch_type<15>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s );
-    default: return launch_type<31>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s );
-    }
+        return launch_score<BAND>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s );
+    }, [] { return NVBIO_ERR_UNSUPPORTED; } );                             // (the band was checked)
 }
 
 extern "C" nvbio_status nvbio_banded_gotoh_score(int device, uint32_t band, nvbio_alignment_type type,
@@ -1735,11 +1683,7 @@ extern "C" nvbio_status nvbio_banded_gotoh_score(int device, uint32_t band, nvbi
 {
     NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
-    if (band != 3 && band != 7 && band != 15 && band != 31)
-    {
-        set_error( "band %u is not instantiated (3, 7, 15, 31)", band );
-        return NVBIO_ERR_UNSUPPORTED;
-    }
+    NVB_CHECK( check_band( band, NVBIO_ERR_UNSUPPORTED ) );
     if (b.n == 0) return NVBIO_OK;
     NVB_REQUIRE( scores_dev && sinks_dev, "NULL output pointer" );
     return banded_score( device, band, type, scheme_dev( scheme ), b, batch, scores_dev, sinks_dev, stream );
@@ -1752,23 +1696,16 @@ extern "C" nvbio_status nvbio_banded_gotoh_score_staged(int device, uint32_t ban
 {
     NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
-    if (band != 3 && band != 7 && band != 15 && band != 31)
-    {
-        set_error( "band %u is not instantiated (3, 7, 15, 31)", band );
-        return NVBIO_ERR_UNSUPPORTED;
-    }
+    NVB_CHECK( check_band( band, NVBIO_ERR_UNSUPPORTED ) );
     if (b.n == 0) return NVBIO_OK;
     NVB_REQUIRE( scores_dev && sinks_dev, "NULL output pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const SchemeDev sc = scheme_dev( scheme );
-    switch (band)
+    return with_value( Bands(), band, [&](auto BAND)
     {
-    case 3:  return launch_staged_type<3> ( type, b, sc, batch->read_bits, batch->text_bits, min_scores_dev, min_score, scores_dev, (uint2*)sinks_dev, s );
-    case 7:  return launch_staged_type<7> ( type, b, sc, batch->read_bits, batch->text_bits, min_scores_dev, min_score, scores_dev, (uint2*)sinks_dev, s );
-    case 15: return launch_staged_type<15>( type, b, sc, batch->read_bits, batch->text_bits, min_scores_dev, min_score, scores_dev, (uint2*)sinks_dev, s );
-    default: return launch_staged_type<31>( type, b, sc, batch->read_bits, batch->text_bits, min_scores_dev, min_score, scores_dev, (uint2*)sinks_dev, s );
-    }
+        return launch_staged<BAND>( type, b, sc, batch->read_bits, batch->text_bits, min_scores_dev, min_score, scores_dev, (uint2*)sinks_dev, s );
+    }, [] { return NVBIO_ERR_UNSUPPORTED; } );                             // (the band was checked)
 }
 
 extern "C" nvbio_status nvbio_banded_sw_score(int device, uint32_t band, nvbio_alignment_type type,
@@ -1777,11 +1714,7 @@ extern "C" nvbio_status nvbio_banded_sw_score(int device, uint32_t band, nvbio_a
 {
     NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
-    if (band != 3 && band != 7 && band != 15 && band != 31)
-    {
-        set_error( "band %u is not instantiated (3, 7, 15, 31)", band );
-        return NVBIO_ERR_UNSUPPORTED;
-    }
+    NVB_CHECK( check_band( band, NVBIO_ERR_UNSUPPORTED ) );
     if (b.n == 0) return NVBIO_OK;
     NVB_REQUIRE( scores_dev && sinks_dev, "NULL output pointer" );
     // in the band the boundary row runs over the text; with deletion == insertion this is Gotoh(open = extension) and takes

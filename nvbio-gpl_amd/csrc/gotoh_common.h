@@ -54,6 +54,30 @@ inline bool plain_gotoh(const SchemeDev& sc)
     return !sc.wide && sc.ins_go == sc.pat_go && sc.ins_ge == sc.pat_ge && sc.top_go == sc.pat_go && sc.top_ge == sc.pat_ge;
 }
 
+// What the alignment kernels are instantiated for (common.h: with_value, with_bits)
+using AlnTypes   = Values<NVBIO_GLOBAL, NVBIO_LOCAL, NVBIO_SEMI_GLOBAL>;
+using Bands      = Values<3, 7, 15, 31>;
+using BitsAll    = BitsList<Bits<4,2>, Bits<2,2>, Bits<8,2>, Bits<8,8>, Bits<4,8>, Bits<2,8>>;     // every pair make_batch accepts
+using BitsBest2  = BitsList<Bits<4,2>, Bits<2,2>, Bits<8,2>, Bits<8,8>>;                           // Best2Sink scorers, Myers
+using BitsStaged = BitsList<Bits<4,2>, Bits<2,2>, Bits<8,8>>;                                      // the staged scorer
+
+// the band check of the banded entry points: `bad` is what a band outside Bands gets -- UNSUPPORTED from the scorers, INVALID from the
+// tracebacks
+inline nvbio_status check_band(const uint32_t band, const nvbio_status bad)
+{
+    if (with_value( Bands(), (int)band, [](auto) { return true; }, [] { return false; } )) return NVBIO_OK;
+    if (bad == NVBIO_ERR_UNSUPPORTED) set_error( "band %u is not instantiated (3, 7, 15, 31)", band );
+    else                              set_error( "invalid argument: band must be 3, 7, 15 or 31" );
+    return bad;
+}
+
+// what an alignment type outside AlnTypes gets
+inline nvbio_status invalid_type(const int type)
+{
+    set_error( "invalid alignment type %d", type );
+    return NVBIO_ERR_INVALID;
+}
+
 nvbio_status make_batch(const nvbio_alignment_batch* in, BatchDev* b);      // gotoh_banded.hip
 nvbio_status banded15_full_ties_traceback(const BatchDev& b, const SchemeDev& sc, const uint32_t rbits, const uint32_t tbits, const uint32_t max_jobs,
                                           const uint32_t* job_list, const uint32_t* job_count, uint32_t* dirs, const uint64_t dirs_bytes,

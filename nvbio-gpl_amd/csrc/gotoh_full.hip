@@ -1232,39 +1232,22 @@ static bool full_ungapped_ok(const SchemeDev& sc, const BatchDev& b, int32_t* P)
     return true;
 }
 
-template <int TYPE, bool TB>
-nvbio_status launch_bits(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
-                         const int32_t* min_scores, uint32_t* column, int32_t* scores, uint2* sinks, hipStream_t s,
-                         const uint32_t* job_list, const uint32_t* job_count)
+template <bool TB>
+nvbio_status launch_dp(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
+                       const int32_t* min_scores, uint32_t* column, int32_t* scores, uint2* sinks, hipStream_t s,
+                       const uint32_t* job_list, const uint32_t* job_count)
 {
     const dim3 grid( (jobs + 127u) / 128u ), block( 128 );
-#define NVB_GO(RB, TBITS) do { if (sc.wide) hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,RB,TBITS,false,true>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count ); \
-                               else         hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,RB,TBITS>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count ); } while (0)
-    if      (rbits == 4 && tbits == 2) NVB_GO(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO(2, 2);
-    else if (rbits == 8 && tbits == 2) NVB_GO(8, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO(8, 8);
-    else if (rbits == 4 && tbits == 8) NVB_GO(4, 8);
-    else if (rbits == 2 && tbits == 8) NVB_GO(2, 8);
-    else { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; }
-#undef NVB_GO
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
-}
-
-template <bool TB>
-nvbio_status launch_type(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
-                         const int32_t* min_scores, uint32_t* column, int32_t* scores, uint2* sinks, hipStream_t s,
-                         const uint32_t* job_list, const uint32_t* job_count)
-{
-    switch (type)
+    return with_value( AlnTypes(), type, [&](auto TYPE)
     {
-    case NVBIO_GLOBAL:      return launch_bits<NVBIO_GLOBAL,TB>     ( b, sc, rbits, tbits, job_begin, jobs, min_scores, column, scores, sinks, s, job_list, job_count );
-    case NVBIO_LOCAL:       return launch_bits<NVBIO_LOCAL,TB>      ( b, sc, rbits, tbits, job_begin, jobs, min_scores, column, scores, sinks, s, job_list, job_count );
-    case NVBIO_SEMI_GLOBAL: return launch_bits<NVBIO_SEMI_GLOBAL,TB>( b, sc, rbits, tbits, job_begin, jobs, min_scores, column, scores, sinks, s, job_list, job_count );
-    }
-    set_error( "invalid alignment type %d", type );
-    return NVBIO_ERR_INVALID;
+        return with_bits( BitsAll(), rbits, tbits, [&](auto P)
+        {
+            if (sc.wide) hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,P.r,P.t,false,true>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count );
+            else         hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,P.r,P.t>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+    }, [&] { return invalid_type( type ); } );
 }
 
 } // anonymous namespace
@@ -1471,8 +1454,8 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
     {
         const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
         st = text_blocking ?
-            launch_type<true> ( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count ) :
-            launch_type<false>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count );
+            launch_dp<true> ( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count ) :
+            launch_dp<false>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count );
     }
     return st;
 }
@@ -1489,21 +1472,21 @@ extern "C" nvbio_status nvbio_full_gotoh_score(int device, nvbio_alignment_type 
 }
 
 // Best2Sink scoring: the int32 kernel reporting cell by cell (no shortcut, no packed kernel: both rely on BestSink's rule)
-template <int TYPE, bool TB>
-static nvbio_status launch_best2(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
+template <bool TB>
+static nvbio_status launch_best2(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
                                  const int32_t* min_scores, uint32_t* column, uint32_t dist, int32_t* scores, uint2* sinks, int32_t* scores2, uint2* sinks2, hipStream_t s)
 {
     const dim3 grid( (jobs + 127u) / 128u ), block( 128 );
-#define NVB_GO2(RB, TBITS) hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,RB,TBITS,true>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, \
-                                               (const uint32_t*)nullptr, (const uint32_t*)nullptr, dist, scores2, sinks2 )
-    if      (rbits == 4 && tbits == 2) NVB_GO2(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO2(2, 2);
-    else if (rbits == 8 && tbits == 2) NVB_GO2(8, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO2(8, 8);
-    else { set_error( "Best2Sink scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; }
-#undef NVB_GO2
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return with_value( AlnTypes(), type, [&](auto TYPE)
+    {
+        return with_bits( BitsBest2(), rbits, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,P.r,P.t,true>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks,
+                                (const uint32_t*)nullptr, (const uint32_t*)nullptr, dist, scores2, sinks2 );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "Best2Sink scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
+    }, [&] { return invalid_type( type ); } );                              // (the entry point checked the type)
 }
 
 extern "C" nvbio_status nvbio_full_gotoh_score_best2(int device, nvbio_alignment_type type, int text_blocking,
@@ -1533,10 +1516,10 @@ extern "C" nvbio_status nvbio_full_gotoh_score_best2(int device, nvbio_alignment
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
     {
         const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
-#define NVB_B2(TYPE_) (text_blocking ? launch_best2<TYPE_,true> ( b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s ) \
-                                     : launch_best2<TYPE_,false>( b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist, scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s ))
-        st = type == NVBIO_GLOBAL ? NVB_B2( NVBIO_GLOBAL ) : type == NVBIO_LOCAL ? NVB_B2( NVBIO_LOCAL ) : NVB_B2( NVBIO_SEMI_GLOBAL );
-#undef NVB_B2
+        st = text_blocking ? launch_best2<true> ( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist,
+                                                  scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s )
+                           : launch_best2<false>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist,
+                                                  scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
     }
     return st;
 }

@@ -490,12 +490,12 @@ extern "C" nvbio_status nvbio_finish_alignment(int device, const nvbio_alignment
     const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
     const uint32_t rb = batch->read_bits, tbits = batch->text_bits;
     hipStream_t s = (hipStream_t)stream;
-#define NVB_FIN(RB, TB) hipLaunchKernelGGL( (finish_alignment_kernel<RB,TB>), grid, block, 0, s, b, (const uint2*)sources_dev, cigars_dev, cigar_stride, \
-                                            cigar_lens_dev, ed_dev, mds_dev, mds_stride, mds_lens_dev )
-    if      (rb == 4 && tbits == 2) NVB_FIN( 4, 2 ); else if (rb == 2 && tbits == 2) NVB_FIN( 2, 2 );
-    else if (rb == 8 && tbits == 2) NVB_FIN( 8, 2 ); else if (rb == 8 && tbits == 8) NVB_FIN( 8, 8 );
-    else if (rb == 4 && tbits == 8) NVB_FIN( 4, 8 ); else NVB_FIN( 2, 8 );
-#undef NVB_FIN
+    (void)with_bits( BitsAll(), rb, tbits, [&](auto P)                     // (make_batch admits no other pair)
+    {
+        hipLaunchKernelGGL( (finish_alignment_kernel<P.r,P.t>), grid, block, 0, s, b, (const uint2*)sources_dev, cigars_dev, cigar_stride,
+                            cigar_lens_dev, ed_dev, mds_dev, mds_stride, mds_lens_dev );
+        return true;
+    }, [] { return false; } );
     NVB_HIP( hipGetLastError() );
     return NVBIO_OK;
 }
@@ -584,16 +584,13 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         } ) );
         band_count = job_count + 1;
         const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
-#define NVB_UNG(TYPE_, RB, TB) hipLaunchKernelGGL( (ungapped_full_traceback_kernel<TYPE_,RB,TB>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, \
-                                                   (const int32_t*)scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp, \
-                                                   go_min, narrow ? ge_min : 0 )
-#define NVB_UNG_BITS(TYPE_) \
-        if      (rb == 4 && tbits == 2) NVB_UNG( TYPE_, 4, 2 ); else if (rb == 2 && tbits == 2) NVB_UNG( TYPE_, 2, 2 ); \
-        else if (rb == 8 && tbits == 2) NVB_UNG( TYPE_, 8, 2 ); else if (rb == 8 && tbits == 8) NVB_UNG( TYPE_, 8, 8 ); \
-        else if (rb == 4 && tbits == 8) NVB_UNG( TYPE_, 4, 8 ); else NVB_UNG( TYPE_, 2, 8 )
-        if (type == NVBIO_GLOBAL) { NVB_UNG_BITS( NVBIO_GLOBAL ); } else if (type == NVBIO_LOCAL) { NVB_UNG_BITS( NVBIO_LOCAL ); } else { NVB_UNG_BITS( NVBIO_SEMI_GLOBAL ); }
-#undef NVB_UNG_BITS
-#undef NVB_UNG
+        (void)with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (ungapped_full_traceback_kernel<TYPE,P.r,P.t>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len,
+                                (const int32_t*)scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp,
+                                go_min, narrow ? ge_min : 0 );
+            return true;
+        }, [] { return false; } ); }, [] { return false; } );              // (the type and the pair were checked)
         hipError_t e = hipSuccess;
         if (band_ok)
         {
@@ -640,16 +637,13 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         const uint64_t jobs64 = ((uint64_t)jobs + 63u) & ~63ull;                  // whole waves own scratch
         uint32_t* dirs   = column + (size_t)jobs64 * max_text_len;
         const dim3 grid( (jobs + 127u) / 128u ), block( 128 );
-#define NVB_TB(TYPE_, RB, TB) hipLaunchKernelGGL( (full_gotoh_traceback_kernel<TYPE_,RB,TB>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, (uint32_t)begin, jobs, \
-                                                  (const uint32_t*)job_list, (const uint32_t*)job_count, min_scores_dev, column, dirs, scores_dev, (uint2*)sources_dev, \
-                                                  (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, (const uint8_t*)(narrow ? need_dp : nullptr), sw ? 1u : 0u )
-#define NVB_TB_BITS(TYPE_) \
-        if      (rb == 4 && tbits == 2) NVB_TB( TYPE_, 4, 2 ); else if (rb == 2 && tbits == 2) NVB_TB( TYPE_, 2, 2 ); \
-        else if (rb == 8 && tbits == 2) NVB_TB( TYPE_, 8, 2 ); else if (rb == 8 && tbits == 8) NVB_TB( TYPE_, 8, 8 ); \
-        else if (rb == 4 && tbits == 8) NVB_TB( TYPE_, 4, 8 ); else NVB_TB( TYPE_, 2, 8 )
-        if (type == NVBIO_GLOBAL) { NVB_TB_BITS( NVBIO_GLOBAL ); } else if (type == NVBIO_LOCAL) { NVB_TB_BITS( NVBIO_LOCAL ); } else { NVB_TB_BITS( NVBIO_SEMI_GLOBAL ); }
-#undef NVB_TB_BITS
-#undef NVB_TB
+        (void)with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (full_gotoh_traceback_kernel<TYPE,P.r,P.t>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, (uint32_t)begin, jobs,
+                                (const uint32_t*)job_list, (const uint32_t*)job_count, min_scores_dev, column, dirs, scores_dev, (uint2*)sources_dev,
+                                (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, (const uint8_t*)(narrow ? need_dp : nullptr), sw ? 1u : 0u );
+            return true;
+        }, [] { return false; } ); }, [] { return false; } );              // (the type and the pair were checked)
         if (hipGetLastError() != hipSuccess) { set_error( "full traceback launch failed" ); st = NVBIO_ERR_HIP; }
     }
     return st;

@@ -424,72 +424,40 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
     cigar_lens[job] = clen;
 }
 
-template <int BAND, int TYPE>
-nvbio_status launch_ungapped(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, const int32_t* scores, const uint2* sinks,
-                             uint2* sources, uint16_t* cigars, uint32_t stride, uint32_t* lens, uint8_t* need_dp, uint8_t* band_off, int32_t go_min, int32_t ge_min,
-                             hipStream_t s)
+template <int BAND>
+nvbio_status launch_ungapped(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, const int32_t* scores,
+                             const uint2* sinks, uint2* sources, uint16_t* cigars, uint32_t stride, uint32_t* lens, uint8_t* need_dp,
+                             uint8_t* band_off, int32_t go_min, int32_t ge_min, hipStream_t s)
 {
     const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
-#define NVB_GO(RB, TB) hipLaunchKernelGGL( (ungapped_traceback_kernel<BAND,TYPE,RB,TB>), grid, block, 0, s, b, sc, scores, sinks, sources, cigars, stride, lens, need_dp, band_off, go_min, ge_min )
-    if      (rbits == 4 && tbits == 2) NVB_GO(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO(2, 2);
-    else if (rbits == 8 && tbits == 2) NVB_GO(8, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO(8, 8);
-    else if (rbits == 4 && tbits == 8) NVB_GO(4, 8);
-    else if (rbits == 2 && tbits == 8) NVB_GO(2, 8);
-    else { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; }
-#undef NVB_GO
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return with_value( AlnTypes(), type, [&](auto TYPE)
+    {
+        return with_bits( BitsAll(), rbits, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (ungapped_traceback_kernel<BAND,TYPE,P.r,P.t>), grid, block, 0, s, b, sc, scores, sinks, sources, cigars, stride, lens,
+                                need_dp, band_off, go_min, ge_min );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+    }, [&] { return invalid_type( type ); } );
 }
 
 template <int BAND>
-nvbio_status launch_ungapped_type(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, const int32_t* scores,
-                                  const uint2* sinks, uint2* sources, uint16_t* cigars, uint32_t stride, uint32_t* lens, uint8_t* need_dp,
-                                  uint8_t* band_off, int32_t go_min, int32_t ge_min, hipStream_t s)
-{
-    switch (type)
-    {
-    case NVBIO_GLOBAL:      return launch_ungapped<BAND,NVBIO_GLOBAL>     ( b, sc, rbits, tbits, scores, sinks, sources, cigars, stride, lens, need_dp, band_off, go_min, ge_min, s );
-    case NVBIO_LOCAL:       return launch_ungapped<BAND,NVBIO_LOCAL>      ( b, sc, rbits, tbits, scores, sinks, sources, cigars, stride, lens, need_dp, band_off, go_min, ge_min, s );
-    case NVBIO_SEMI_GLOBAL: return launch_ungapped<BAND,NVBIO_SEMI_GLOBAL>( b, sc, rbits, tbits, scores, sinks, sources, cigars, stride, lens, need_dp, band_off, go_min, ge_min, s );
-    }
-    set_error( "invalid alignment type %d", type );
-    return NVBIO_ERR_INVALID;
-}
-
-template <int BAND, int TYPE>
-nvbio_status launch_bits(const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
-                         const uint32_t* job_list, const uint32_t* job_count, uint32_t* dirs, int32_t* scores, uint2* sources, uint2* sinks, uint16_t* cigars, uint32_t stride,
-                         uint32_t* lens, hipStream_t s, const uint8_t* band_off = nullptr, const uint32_t full_ties = 0u)
+nvbio_status launch_dp(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
+                       const uint32_t* job_list, const uint32_t* job_count, uint32_t* dirs, int32_t* scores, uint2* sources, uint2* sinks, uint16_t* cigars, uint32_t stride,
+                       uint32_t* lens, hipStream_t s, const uint8_t* band_off = nullptr, const uint32_t full_ties = 0u)
 {
     const dim3 grid( (jobs + 127u) / 128u ), block( 128 );
-#define NVB_GO(RB, TB) hipLaunchKernelGGL( (banded_gotoh_traceback_kernel<BAND,TYPE,RB,TB>), grid, block, 0, s, b, sc, job_begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, band_off, full_ties )
-    if      (rbits == 4 && tbits == 2) NVB_GO(4, 2);
-    else if (rbits == 2 && tbits == 2) NVB_GO(2, 2);
-    else if (rbits == 8 && tbits == 2) NVB_GO(8, 2);
-    else if (rbits == 8 && tbits == 8) NVB_GO(8, 8);
-    else if (rbits == 4 && tbits == 8) NVB_GO(4, 8);
-    else if (rbits == 2 && tbits == 8) NVB_GO(2, 8);
-    else { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; }
-#undef NVB_GO
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
-}
-
-template <int BAND>
-nvbio_status launch_type(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits, uint32_t job_begin, uint32_t jobs,
-                         const uint32_t* job_list, const uint32_t* job_count, uint32_t* dirs, int32_t* scores, uint2* sources, uint2* sinks, uint16_t* cigars, uint32_t stride,
-                         uint32_t* lens, hipStream_t s, const uint8_t* band_off = nullptr, const uint32_t full_ties = 0u)
-{
-    switch (type)
+    return with_value( AlnTypes(), type, [&](auto TYPE)
     {
-    case NVBIO_GLOBAL:      return launch_bits<BAND,NVBIO_GLOBAL>     ( b, sc, rbits, tbits, job_begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s, band_off, full_ties );
-    case NVBIO_LOCAL:       return launch_bits<BAND,NVBIO_LOCAL>      ( b, sc, rbits, tbits, job_begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s, band_off, full_ties );
-    case NVBIO_SEMI_GLOBAL: return launch_bits<BAND,NVBIO_SEMI_GLOBAL>( b, sc, rbits, tbits, job_begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s, band_off, full_ties );
-    }
-    set_error( "invalid alignment type %d", type );
-    return NVBIO_ERR_INVALID;
+        return with_bits( BitsAll(), rbits, tbits, [&](auto P)
+        {
+            hipLaunchKernelGGL( (banded_gotoh_traceback_kernel<BAND,TYPE,P.r,P.t>), grid, block, 0, s, b, sc, job_begin, jobs, job_list, job_count, dirs,
+                                scores, sources, sinks, cigars, stride, lens, band_off, full_ties );
+            NVB_HIP( hipGetLastError() );
+            return NVBIO_OK;
+        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+    }, [&] { return invalid_type( type ); } );
 }
 
 inline uint64_t row_bytes(const uint32_t band) { return (uint64_t)((band + 7u) / 8u) * sizeof(uint32_t); }
@@ -511,8 +479,8 @@ nvbio_status banded15_full_ties_traceback(const BatchDev& b, const SchemeDev& sc
     for (uint64_t begin = 0; begin < max_jobs && st == NVBIO_OK; begin += cap)
     {
         const uint32_t jobs = (uint32_t)((max_jobs - begin) < cap ? (max_jobs - begin) : cap);
-        st = launch_type<15>( NVBIO_SEMI_GLOBAL, b, sc, rbits, tbits, (uint32_t)begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s,
-                              nullptr, 1u );
+        st = launch_dp<15>( NVBIO_SEMI_GLOBAL, b, sc, rbits, tbits, (uint32_t)begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s,
+                            nullptr, 1u );
     }
     return st;
 }
@@ -523,7 +491,7 @@ using namespace nvbio_amd;
 extern "C" nvbio_status nvbio_banded_gotoh_traceback_temp_bytes(const nvbio_alignment_batch* batch, uint32_t band, uint64_t* bytes)
 {
     NVB_REQUIRE( batch && bytes, "batch/bytes is NULL" );
-    NVB_REQUIRE( band == 3 || band == 7 || band == 15 || band == 31, "band must be 3, 7, 15 or 31" );
+    NVB_CHECK( check_band( band, NVBIO_ERR_INVALID ) );
     NVB_REQUIRE( batch->n == 0 || batch->max_read_len > 0, "batch.max_read_len must bound the pattern lengths" );
     *bytes = (uint64_t)batch->n * batch->max_read_len * row_bytes( band );
     return NVBIO_OK;
@@ -542,7 +510,7 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
     const nvbio_gotoh_scheme* scheme = gotoh ? gotoh : &as_gotoh;
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
     if (b.n == 0) return NVBIO_OK;
-    NVB_REQUIRE( band == 3 || band == 7 || band == 15 || band == 31, "band must be 3, 7, 15 or 31" );
+    NVB_CHECK( check_band( band, NVBIO_ERR_INVALID ) );
     NVB_REQUIRE( scores_dev && sources_dev && sinks_dev && cigar_lens_dev, "NULL output pointer" );
     NVB_REQUIRE( cigars_dev != nullptr || cigar_stride == 0, "cigars_dev is NULL" );
     NVB_REQUIRE( b.max_read_len > 0, "batch.max_read_len must bound the pattern lengths (it sizes the direction-vector scratch)" );
@@ -602,18 +570,11 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
             job_count3 = c.take<uint32_t>( 1 );
             sel_temp   = c.take<uint8_t>( sel_bytes );
         } ) );
-        nvbio_status st1;
-#define NVB_BAND(B) st1 = launch_ungapped_type<B>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (const uint2*)sinks_dev, \
-                                                   (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp,             \
-                                                   narrow ? band_off : nullptr, go_min, ge_min, s )
-        switch (band)
+        const nvbio_status st1 = with_value( Bands(), band, [&](auto BAND)
         {
-        case 3:  NVB_BAND(3);  break;
-        case 7:  NVB_BAND(7);  break;
-        case 15: NVB_BAND(15); break;
-        default: NVB_BAND(31); break;
-        }
-#undef NVB_BAND
+            return launch_ungapped<BAND>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev,
+                                          cigars_dev, cigar_stride, cigar_lens_dev, need_dp, narrow ? band_off : nullptr, go_min, ge_min, s );
+        }, [] { return NVBIO_ERR_INVALID; } );                                // (the band was checked)
         NVB_CHECK( st1 );
         // ---- 3. the jobs that do need the DP, compacted (their number stays on the device) ----
         hipcub::TransformInputIterator<uint8_t, IsCode<1>, const uint8_t*> is_full( need_dp, IsCode<1>() );
@@ -651,16 +612,11 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
     {
         const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
-#define NVB_BAND(B) st = launch_type<B>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list, job_count, dirs, scores_dev, \
-                                         (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s )
-        switch (band)
+        st = with_value( Bands(), band, [&](auto BAND)
         {
-        case 3:  NVB_BAND(3);  break;
-        case 7:  NVB_BAND(7);  break;
-        case 15: NVB_BAND(15); break;
-        default: NVB_BAND(31); break;
-        }
-#undef NVB_BAND
+            return launch_dp<BAND>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list, job_count, dirs, scores_dev,
+                                    (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s );
+        }, [] { return NVBIO_ERR_INVALID; } );                                // (the band was checked)
     }
     if (narrow && shortcut)
     {
@@ -669,14 +625,14 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap2)
         {
             const uint32_t jobs = (uint32_t)((b.n - begin) < cap2 ? (b.n - begin) : cap2);
-            st = launch_type<15>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list2, job_count2, dirs, scores_dev,
+            st = launch_dp<15>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list2, job_count2, dirs, scores_dev,
                                   (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s, band_off );
         }
         const uint64_t cap3 = cap_jobs * per_job / ((uint64_t)b.max_read_len * row_bytes( 7 ));
         for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap3)
         {
             const uint32_t jobs = (uint32_t)((b.n - begin) < cap3 ? (b.n - begin) : cap3);
-            st = launch_type<7>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list3, job_count3, dirs, scores_dev,
+            st = launch_dp<7>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list3, job_count3, dirs, scores_dev,
                                  (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s, band_off );
         }
     }

@@ -96,14 +96,11 @@ extern "C" nvbio_status nvbio_banded_myers_score(int device, uint32_t band, nvbi
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
     hipStream_t s = (hipStream_t)stream;
-#define NVB_MY(RB, TB) hipLaunchKernelGGL( (banded_myers_kernel<RB,TB>), grid, block, 0, s, b, band, (int)type, min_score, scores_dev, (uint2*)sinks_dev )
     const uint32_t rb = batch->read_bits, tbits = batch->text_bits;
-    if      (rb == 4 && tbits == 2) NVB_MY( 4, 2 );
-    else if (rb == 2 && tbits == 2) NVB_MY( 2, 2 );
-    else if (rb == 8 && tbits == 2) NVB_MY( 8, 2 );
-    else if (rb == 8 && tbits == 8) NVB_MY( 8, 8 );
-    else { set_error( "unsupported read_bits / text_bits combination %u / %u", rb, tbits ); return NVBIO_ERR_UNSUPPORTED; }
-#undef NVB_MY
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return with_bits( BitsBest2(), rb, tbits, [&](auto P)
+    {
+        hipLaunchKernelGGL( (banded_myers_kernel<P.r,P.t>), grid, block, 0, s, b, band, (int)type, min_score, scores_dev, (uint2*)sinks_dev );
+        NVB_HIP( hipGetLastError() );
+        return NVBIO_OK;
+    }, [&] { set_error( "unsupported read_bits / text_bits combination %u / %u", rb, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
 }
