@@ -441,6 +441,93 @@ nvbio_status nvbio_mem_filter_locate(nvbio_fm_index_t f_index, const nvbio_mem_r
                                      uint32_t n_ranges, uint64_t begin, uint64_t end, nvbio_mem_hit* hits_dev, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * q-gram seeding: QGramIndexDevice, QGramSetIndexDevice and QGramFilter<device_tag> (nvbio/qgram/qgram.h, qgram_inl.h,
+ * filter.h, filter_inl.h; csrc/qgram.hip), the pieces of examples/qmap/qmap.cu.  No BWT and no suffix array: a q-gram index is
+ * the sorted unique q-grams of a text (or of the seeds of a string set), their slots and their occurrences.
+ *
+ *   packing  g = sum_j (s[i+j] & mask) << (j * symbol_size), mask = (1 << symbol_size) - 1: the FIRST symbol in the LEAST
+ *            significant bits (numeric order is not lexicographic order), positions past the end of the string give 0 symbols, and
+ *            a 4-bit N (4) read with symbol_size 2 becomes A (qmap relies on it).
+ *   string   all `length` positions are indexed, the last q - 1 padded with 0 symbols (n_qgrams = length); the occurrences of a
+ *            q-gram are uint32 text positions in ascending order (a stable radix sort over bits [0, q * symbol_size)).
+ *   set      seeds at pos = k * seed_interval for every k with pos + q <= the string's length (no padding), string-major then by
+ *            position; coordinates (string_id, string_pos), uint32 each, in that order inside a q-gram.
+ *   view     qgrams[n_unique] sorted unique q-grams; slots[n_unique + 1] exclusive scan of their counts; index[n_qgrams] the
+ *            occurrences; lut[A^qlut + 1] (qlut > 0, A = 1 << symbol_size): lut[k] = lower_bound( qgrams, k << (q - qlut) *
+ *            symbol_size ), lut[A^qlut] = n_unique -- it keys on a q-gram's top bits, its LAST qlut symbols.
+ *   range    the HALF-OPEN occurrence range [slots[i], slots[i+1]) of g, (0, 0) on a miss (the FM ranges above are inclusive).
+ *   rank     ranges[i] = range( qgrams[i] ); slots = INCLUSIVE uint64 scan of the range sizes; *n_hits = slots[n - 1].
+ *   locate   output o belongs to query i = upper_bound( o, slots ).  String index: hits are uint2 (index[ranges[i].x + o -
+ *            slots[i-1]], indices[i]) = (text position of the occurrence, the caller's coordinate of query i); set index: uint4
+ *            (string_id, string_pos, indices[i], 0).
+ *   merge    diagonal = text_pos - index_pos (string hits: hit.y - hit.x) or text_pos - string_pos (set hits: hit.z - hit.y), uint32
+ *            (it wraps), snapped to the closest multiple of interval (ties down, mod 2^32), sorted and run-length encoded: string
+ *            hits give uint32 diagonals, set hits uint2 (diagonal, string_id) ordered by string id, then diagonal; counts uint32.
+ *
+ * Departures from the reference (its defects): util::round returns r + 1 instead of the closest multiple r + interval; rank over
+ * no queries returns 0 hits (the reference reads slots[-1]); the set-index locate keeps the hit index 64-bit (the reference
+ * truncates it to 32 bits); merged counts are uint32 (qmap's uint16 can overflow on a repeat).
+ * Limits (NVBIO_ERR_INVALID otherwise): 1 <= symbol_size <= 8, q >= 1, q * symbol_size <= 64, qlut <= q, qlut * symbol_size <=
+ * 28; text lengths and n_qgrams below 2^32 - 1; text / symbol bits 2, 4 or 8 (the nvbio_string_set packing).
+ * Working storage: the builds allocate their own (the arrays stay with the handle); generate (sorted), rank and merge use the
+ * caller's temp only, which the scratch check mode (nvbio_amd_set_scratch_check) does not fill.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nvbio_qgram_index_s* nvbio_qgram_index_t;     /* opaque handle */
+
+typedef struct
+{
+    uint32_t        q, symbol_size, qlut;
+    uint32_t        is_set;            /* 0: string index (index = uint32 positions); 1: set index (index = uint2 coordinates) */
+    uint32_t        n_qgrams, n_unique;
+    uint64_t        lut_size;          /* A^qlut (lut_dev holds lut_size + 1 entries), 0 without a LUT */
+    int             device;
+    const uint64_t* qgrams_dev;
+    const uint32_t* slots_dev;
+    const void*     index_dev;
+    const uint32_t* lut_dev;           /* NULL without a LUT */
+} nvbio_qgram_index_view;
+
+/* QGramIndexDevice::build( q, symbol_size, length, text, qlut ): text_dev packed as nvbio_string_set symbols (big-endian words of
+ * 2 or 4 bits, or bytes).  Synchronizes. */
+nvbio_status nvbio_qgram_index_build(int device, const void* text_dev, uint32_t text_bits, uint32_t length, uint32_t q, uint32_t symbol_size,
+                                     uint32_t qlut, nvbio_qgram_index_t* out, void* stream);
+/* QGramSetIndexDevice::build( q, symbol_size, set, uniform_seeds_functor( q, seed_interval ), qlut ) over a plain string set (fixed,
+ * ragged, or offsets not starting at 0); seed-enumerated sets are rejected.  Synchronizes. */
+nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set, uint32_t q, uint32_t symbol_size, uint32_t seed_interval,
+                                         uint32_t qlut, nvbio_qgram_index_t* out, void* stream);
+nvbio_status nvbio_qgram_index_destroy(nvbio_qgram_index_t index);
+nvbio_status nvbio_qgram_index_get_view(nvbio_qgram_index_t index, nvbio_qgram_index_view* view);
+nvbio_status nvbio_qgram_index_device_bytes(nvbio_qgram_index_t index, uint64_t* bytes);
+/* copy the index arrays into caller buffers in HBM (any may be NULL; sizes from get_view: n_unique, n_unique + 1, n_qgrams entries of
+ * uint32 or uint2, lut_size + 1) */
+nvbio_status nvbio_qgram_index_export(nvbio_qgram_index_t index, uint64_t* qgrams_out_dev, uint32_t* slots_out_dev, void* index_out_dev,
+                                      uint32_t* lut_out_dev, void* stream);
+
+/* qmap's build_qgrams (examples/qmap/qmap.cu:75-99): qgrams_dev[i] = the q-gram at text position first_pos + i for i < n (padded
+ * past text_len), indices_dev[i] = first_pos + i (indices_dev may be NULL when !sort).  sort != 0: the (q-gram, position) pairs
+ * stably sorted by q-gram, in the caller's temp (nvbio_generate_qgrams_temp_bytes; none without sort). */
+nvbio_status nvbio_generate_qgrams_temp_bytes(uint32_t n, int sort, uint64_t* bytes);
+nvbio_status nvbio_generate_qgrams(int device, uint32_t q, uint32_t symbol_size, const void* text_dev, uint32_t text_bits, uint32_t text_len,
+                                   uint32_t first_pos, uint32_t n, uint64_t* qgrams_dev, uint32_t* indices_dev, int sort,
+                                   void* temp_dev, uint64_t temp_bytes, void* stream);
+/* the index as a search functor: ranges_dev[i] = range( qgrams_dev[i] ) */
+nvbio_status nvbio_qgram_ranges(nvbio_qgram_index_t index, const uint64_t* qgrams_dev, uint32_t n, nvbio_uint2* ranges_dev, void* stream);
+
+/* QGramFilter::rank: ranges_dev / slots_dev hold n entries; temp: nvbio_qgram_filter_temp_bytes( n ).  Synchronizes. */
+nvbio_status nvbio_qgram_filter_temp_bytes(uint32_t n_queries, uint64_t* bytes);
+nvbio_status nvbio_qgram_filter_rank(nvbio_qgram_index_t index, const uint64_t* qgrams_dev, uint32_t n, nvbio_uint2* ranges_dev, uint64_t* slots_dev,
+                                     void* temp_dev, uint64_t temp_bytes, uint64_t* n_hits, void* stream);
+/* QGramFilter::locate: hits_dev[o - begin] for the outputs o in [begin, end), end <= slots[n - 1] (checked: reads it, synchronizes);
+ * uint2 hits for a string index, uint4 for a set index.  indices_dev: the query coordinates rank's queries came with (n entries). */
+nvbio_status nvbio_qgram_filter_locate(nvbio_qgram_index_t index, const nvbio_uint2* ranges_dev, const uint64_t* slots_dev, const uint32_t* indices_dev,
+                                       uint32_t n, uint64_t begin, uint64_t end, void* hits_dev, void* stream);
+/* QGramFilter::merge: merged_dev (n_hits uint32, or uint2 when is_set) and counts_dev (n_hits uint32) receive *n_merged entries;
+ * temp: nvbio_qgram_filter_merge_temp_bytes( is_set, n_hits ).  interval >= 1.  Synchronizes. */
+nvbio_status nvbio_qgram_filter_merge_temp_bytes(int is_set, uint32_t n_hits, uint64_t* bytes);
+nvbio_status nvbio_qgram_filter_merge(int device, int is_set, uint32_t interval, const void* hits_dev, uint32_t n_hits, void* merged_dev,
+                                      uint32_t* counts_dev, uint32_t* n_merged, void* temp_dev, uint64_t temp_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * seed hits -> candidate windows: the two index-arithmetic functors between FMIndexFilter::locate
  * and the banded aligner in the reference's smallest seed-and-extend caller (examples/fmmap/fmmap.cu)
  * ------------------------------------------------------------------------------------------- */

@@ -8,6 +8,8 @@ argument meaning as the reference's C++ templates --
     FMIndex                      nvbio::fm_index / io::FMIndexDataDevice   (nvbio/fmindex/fmindex.h:320-557)
     FMIndexFilter                nvbio::FMIndexFilter<device_tag,...>      (nvbio/fmindex/filter.h:52-231)
     MEMFilter                    nvbio::MEMFilter<device_tag,...>          (nvbio/fmindex/mem.h, mem_inl.h:1303-1528)
+    QGramIndex, QGramSetIndex    nvbio::QGramIndexDevice / QGramSetIndexDevice (nvbio/qgram/qgram.h, qgram_inl.h)
+    QGramFilter, generate_qgrams nvbio::QGramFilter<device_tag,...>        (nvbio/qgram/filter.h, filter_inl.h)
     SimpleGotohScheme, GotohAligner, BestSink semantics                    (nvbio/alignment/utils.h:103-123, alignment.h:437-449)
     BatchedBandedAlignmentScore, batch_banded_alignment_score              (nvbio/alignment/batched.h:104-298)
 
@@ -705,6 +707,215 @@ class MEMFilter:
             _check(lib().nvbio_mem_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), ctypes.c_uint32(self._n_ranges),
                                                  ctypes.c_uint64(begin), ctypes.c_uint64(end), _ptr(hits), _stream_ptr(self._index.device)))
         return hits
+
+
+# ---- q-gram seeding -----------------------------------------------------------------------------
+class _QGramView(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_uint32), ("symbol_size", ctypes.c_uint32), ("qlut", ctypes.c_uint32), ("is_set", ctypes.c_uint32),
+                ("n_qgrams", ctypes.c_uint32), ("n_unique", ctypes.c_uint32), ("lut_size", ctypes.c_uint64), ("device", ctypes.c_int),
+                ("qgrams_dev", ctypes.c_void_p), ("slots_dev", ctypes.c_void_p), ("index_dev", ctypes.c_void_p), ("lut_dev", ctypes.c_void_p)]
+
+
+def _qgram_text(text, bits, device):
+    torch = _torch()
+    return _dev_tensor(text, torch.uint8 if bits == 8 else torch.int32, device)
+
+
+class QGramIndex:
+    """nvbio::QGramIndexDevice (nvbio/qgram/qgram.h, qgram_inl.h:30-140): the q-grams of every position of a text (nvbio_qgram_*; the
+    packing, ordering and departures are listed in include/nvbio_amd.h).  The arrays are views of the handle's device memory."""
+    IS_SET = False
+
+    def __init__(self, handle, device, keep=()):
+        self._h, self.device, self._keep = handle, device, keep
+
+    @classmethod
+    def build(cls, text, text_bits, length, q, symbol_size=2, qlut=0, device="cuda:0"):
+        """QGramIndexDevice::build( q, symbol_size, length, text, qlut ); text: packed words (bits 2, 4) or bytes (8)"""
+        t = _qgram_text(text, text_bits, device)
+        h = ctypes.c_void_p()
+        _check(lib().nvbio_qgram_index_build(FMIndex._dev_index(device), _ptr(t), ctypes.c_uint32(text_bits), ctypes.c_uint32(length),
+                                             ctypes.c_uint32(q), ctypes.c_uint32(symbol_size), ctypes.c_uint32(qlut), ctypes.byref(h),
+                                             _stream_ptr(device)))
+        return cls(h, device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().nvbio_qgram_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def view(self):
+        v = _QGramView()
+        _check(lib().nvbio_qgram_index_get_view(self._h, ctypes.byref(v)))
+        return v
+
+    def device_bytes(self):
+        b = ctypes.c_uint64(0)
+        _check(lib().nvbio_qgram_index_device_bytes(self._h, ctypes.byref(b)))
+        return b.value
+
+    def arrays(self):
+        """copies of the index arrays as device tensors (nvbio_qgram_index_export): qgrams int64 [n_unique], slots int32
+        [n_unique + 1], index int32 [n_qgrams] (or [n_qgrams, 2] (string_id, string_pos) for a set index), lut int32
+        [lut_size + 1] or None (uint bit patterns)"""
+        torch = _torch()
+        v = self.view()
+        qg = torch.empty(max(v.n_unique, 1), dtype=torch.int64, device=self.device)
+        sl = torch.empty(v.n_unique + 1, dtype=torch.int32, device=self.device)
+        ix = torch.empty((max(v.n_qgrams, 1), 2) if v.is_set else max(v.n_qgrams, 1), dtype=torch.int32, device=self.device)
+        lut = torch.empty(v.lut_size + 1, dtype=torch.int32, device=self.device) if v.lut_dev else None
+        _check(lib().nvbio_qgram_index_export(self._h, _ptr(qg), _ptr(sl), _ptr(ix), _ptr(lut), _stream_ptr(self.device)))
+        return dict(qgrams=qg[:v.n_unique], slots=sl, index=ix[:v.n_qgrams], lut=lut)
+
+    @property
+    def q(self):
+        return self.view().q
+
+    @property
+    def n_qgrams(self):
+        return self.view().n_qgrams
+
+    @property
+    def n_unique(self):
+        return self.view().n_unique
+
+    def ranges(self, qgrams):
+        """the index as a search functor: int32 [n, 2] half-open (begin, end) slots of each q-gram, (0, 0) on a miss"""
+        torch = _torch()
+        g = _dev_tensor(qgrams, torch.int64, self.device)
+        out = torch.empty((g.numel(), 2), dtype=torch.int32, device=self.device)
+        _check(lib().nvbio_qgram_ranges(self._h, _ptr(g), ctypes.c_uint32(g.numel()), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+
+class QGramSetIndex(QGramIndex):
+    """nvbio::QGramSetIndexDevice (qgram_inl.h:186-300): the q-grams of the seeds k * seed_interval of every string of a plain set"""
+    IS_SET = True
+
+    @classmethod
+    def build(cls, string_set, q, symbol_size=2, seed_interval=1, qlut=0):
+        """QGramSetIndexDevice::build( q, symbol_size, string_set, uniform_seeds_functor( q, seed_interval ), qlut )"""
+        h = ctypes.c_void_p()
+        ss = string_set.c_struct()
+        dev = string_set.device
+        _check(lib().nvbio_qgram_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size),
+                                                 ctypes.c_uint32(seed_interval), ctypes.c_uint32(qlut), ctypes.byref(h), _stream_ptr(dev)))
+        return cls(h, dev, keep=(string_set,))
+
+
+_GENERATE_TEMP = {}
+
+
+def generate_qgrams(q, symbol_size, text, text_bits, text_len, first_pos, n, sort=False, device="cuda:0"):
+    """qmap's build_qgrams (examples/qmap/qmap.cu:75-99, nvbio_generate_qgrams): (qgrams int64 [n], positions int32 [n]) of text
+    positions [first_pos, first_pos + n), padded past text_len; sort: the pairs stably sorted by q-gram"""
+    torch = _torch()
+    t = _qgram_text(text, text_bits, device)
+    qg = torch.empty(n, dtype=torch.int64, device=device)
+    ix = torch.empty(n, dtype=torch.int32, device=device)
+    tb = ctypes.c_uint64(0)
+    _check(lib().nvbio_generate_qgrams_temp_bytes(ctypes.c_uint32(n), ctypes.c_int(1 if sort else 0), ctypes.byref(tb)))
+    key = str(device)
+    temp = _GENERATE_TEMP.get(key)
+    if tb.value and (temp is None or temp.numel() < tb.value):
+        _GENERATE_TEMP[key] = None
+        temp = _GENERATE_TEMP[key] = torch.empty(int(tb.value), dtype=torch.uint8, device=device)
+    _check(lib().nvbio_generate_qgrams(FMIndex._dev_index(device), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size), _ptr(t),
+                                       ctypes.c_uint32(text_bits), ctypes.c_uint32(text_len), ctypes.c_uint32(first_pos), ctypes.c_uint32(n),
+                                       _ptr(qg), _ptr(ix), ctypes.c_int(1 if sort else 0), _ptr(temp) if tb.value else None,
+                                       ctypes.c_uint64(temp.numel() if tb.value else 0), _stream_ptr(device)))
+    return qg, ix
+
+
+class QGramFilter:
+    """nvbio::QGramFilter<device_tag, qgram_index_type, ...> (nvbio/qgram/filter.h, filter_inl.h:336-483).  Owns its ranges, slots,
+    hits, merge outputs and temp, and keeps their sizes across batches."""
+
+    def __init__(self):
+        self._index = None
+        self._ranges = self._slots = self._indices = self._temp = None
+        self._merged = self._counts = None
+        self._n_queries = self._n_hits = 0
+
+    def _grow_temp(self, nbytes, dev):
+        torch = _torch()
+        if self._temp is None or self._temp.numel() < nbytes or self._temp.device != torch.device(dev):
+            self._temp = None
+            self._temp = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+    def rank(self, index, qgrams, indices):
+        """enact the filter over the query q-grams (int64) and their coordinates (int32, e.g. text positions); returns the number of
+        hits (filter_inl.h:336-380)"""
+        torch = _torch()
+        dev = index.device
+        g = _dev_tensor(qgrams, torch.int64, dev)
+        ix = _dev_tensor(indices, torch.int32, dev)
+        n = g.numel()
+        self._index, self._n_queries, self._indices = index, n, ix
+        if self._ranges is None or self._ranges.shape[0] < n or self._ranges.device != torch.device(dev):
+            self._ranges = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+            self._slots = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        tb = ctypes.c_uint64(0)
+        _check(lib().nvbio_qgram_filter_temp_bytes(ctypes.c_uint32(n), ctypes.byref(tb)))
+        self._grow_temp(tb.value, dev)
+        nh = ctypes.c_uint64(0)
+        _check(lib().nvbio_qgram_filter_rank(index._h, _ptr(g), ctypes.c_uint32(n), _ptr(self._ranges), _ptr(self._slots), _ptr(self._temp),
+                                             ctypes.c_uint64(self._temp.numel()), ctypes.byref(nh), _stream_ptr(dev)))
+        self._n_hits = nh.value
+        return self._n_hits
+
+    def n_hits(self):
+        return self._n_hits
+
+    def ranges(self):
+        """int32 [n_queries, 2]: the half-open slots of every query q-gram"""
+        return self._ranges[:self._n_queries]
+
+    def slots(self):
+        """int64 [n_queries]: the inclusive scan of the range sizes"""
+        return self._slots[:self._n_queries]
+
+    def locate(self, begin, end, hits=None):
+        """hits of outputs [begin, end): int32 [end - begin, 2] (index position, query coordinate) for a string index,
+        [end - begin, 4] (string_id, string_pos, query coordinate, 0) for a set index (filter_inl.h:386-410)"""
+        torch = _torch()
+        cols = 4 if self._index.IS_SET else 2
+        if hits is None:
+            hits = torch.empty((max(end - begin, 0), cols), dtype=torch.int32, device=self._index.device)
+        if end > begin:
+            _check(lib().nvbio_qgram_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._indices),
+                                                   ctypes.c_uint32(self._n_queries), ctypes.c_uint64(begin), ctypes.c_uint64(end), _ptr(hits),
+                                                   _stream_ptr(self._index.device)))
+        return hits
+
+    def merge(self, interval, hits, is_set=None):
+        """merge hits by snapped diagonal (filter_inl.h:446-483): (merged, counts) -- int32 [n_merged] diagonals for string hits or
+        [n_merged, 2] (diagonal, string_id) for set hits, and int32 [n_merged] counts (uint32 bit patterns)"""
+        torch = _torch()
+        if is_set is None:
+            is_set = hits.dim() == 2 and hits.shape[1] == 4
+        dev = hits.device
+        n = hits.shape[0]
+        tb = ctypes.c_uint64(0)
+        _check(lib().nvbio_qgram_filter_merge_temp_bytes(ctypes.c_int(1 if is_set else 0), ctypes.c_uint32(n), ctypes.byref(tb)))
+        self._grow_temp(tb.value, dev)
+        if self._merged is None or self._merged.shape[0] < max(n, 1) or self._merged.device != dev:
+            self._merged = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+            self._counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        nm = ctypes.c_uint32(0)
+        hits = hits.contiguous()
+        _check(lib().nvbio_qgram_filter_merge(FMIndex._dev_index(dev), ctypes.c_int(1 if is_set else 0), ctypes.c_uint32(interval), _ptr(hits),
+                                              ctypes.c_uint32(n), _ptr(self._merged), _ptr(self._counts), ctypes.byref(nm), _ptr(self._temp),
+                                              ctypes.c_uint64(self._temp.numel()), _stream_ptr(dev)))
+        m = nm.value
+        merged = self._merged.view(-1)[:2 * m].view(m, 2) if is_set else self._merged.view(-1)[:m]
+        return merged.clone(), self._counts[:m].clone()
 
 
 # ---- alignment ---------------------------------------------------------------------------------

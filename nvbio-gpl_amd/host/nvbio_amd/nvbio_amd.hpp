@@ -10,6 +10,12 @@
 //                                    rank(index, string_set) -> n_hits ; locate(begin, end, hits) ; owns ranges/slots
 //   MEMFilter<amd_device_tag>      ~ nvbio::MEMFilter<device_tag,fm_index> (nvbio/fmindex/mem.h:270-360):
 //                                    rank(f_index, r_index, string_set, min_intv, ...) -> n_mems ; first_hit ; locate(begin, end, mems)
+//   QGramIndexDevice, QGramSetIndexDevice
+//                                  ~ nvbio::QGramIndexDevice / QGramSetIndexDevice (nvbio/qgram/qgram.h, qgram_inl.h:30-300):
+//                                    build(q, symbol_size, ..., qlut) ; Q, n_qgrams, n_unique_qgrams ; qgrams / slots / index / lut
+//   QGramFilterDevice<index_type>  ~ nvbio::QGramFilter<device_tag,index,...> (nvbio/qgram/filter.h, filter_inl.h:336-483):
+//                                    rank(index, n_queries, queries, indices) -> n_hits ; locate(begin, end, hits) ;
+//                                    merge(interval, n_hits, hits, merged_hits, merged_counts) -> n_merged
 //   aln::SimpleGotohScheme, aln::GotohAligner<TYPE,scheme>, aln::make_gotoh_aligner<TYPE>()
 //                                  ~ nvbio/alignment/utils.h:103-123, alignment.h:437-462
 //   aln::BatchedBandedAlignmentScore<BAND, stream, AmdDeviceScheduler>
@@ -396,6 +402,140 @@ private:
     device_vector<uint64_t>  m_slots;
     device_vector<uint32_t>  m_first;
     device_vector<uint8_t>   m_temp;
+};
+
+// ---- q-gram seeding (nvbio_qgram_*; the packing, ordering and departures are listed in nvbio_amd.h) ----
+// qmap's build_qgrams: the q-grams of text positions [first_pos, first_pos + n) (padded past text_len), stably sorted by q-gram
+// with their positions when `sort`
+inline void generate_qgrams(int device, uint32_t q, uint32_t symbol_size, const void* text, uint32_t text_bits, uint32_t text_len,
+                            uint32_t first_pos, uint32_t n, uint64_t* qgrams, uint32_t* indices, bool sort, hipStream_t stream = 0)
+{
+    uint64_t bytes = 0;
+    check( nvbio_generate_qgrams_temp_bytes( n, sort ? 1 : 0, &bytes ) );
+    device_vector<uint8_t> temp( bytes );
+    check( nvbio_generate_qgrams( device, q, symbol_size, text, text_bits, text_len, first_pos, n, qgrams, indices, sort ? 1 : 0,
+                                  bytes ? temp.data() : nullptr, bytes, stream ) );
+    if (bytes) check_hip( hipStreamSynchronize( stream ), "generate_qgrams" );      // the temp goes out of scope
+}
+
+// the owner of a q-gram index handle; the arrays are views of the handle's device memory
+class QGramIndexBase
+{
+public:
+    QGramIndexBase() : m_h( nullptr ) { m_view = nvbio_qgram_index_view(); }
+    QGramIndexBase(const QGramIndexBase&) = delete;
+    QGramIndexBase& operator=(const QGramIndexBase&) = delete;
+    ~QGramIndexBase() { reset(); }
+    nvbio_qgram_index_t handle() const { return m_h; }
+    const nvbio_qgram_index_view& view() const { return m_view; }
+    uint32_t Q() const               { return m_view.q; }
+    uint32_t symbol_size() const     { return m_view.symbol_size; }
+    uint32_t QL() const              { return m_view.qlut; }
+    uint32_t n_qgrams() const        { return m_view.n_qgrams; }
+    uint32_t n_unique_qgrams() const { return m_view.n_unique; }
+    int      device() const          { return m_view.device; }
+    const uint64_t* qgrams() const   { return m_view.qgrams_dev; }
+    const uint32_t* slots() const    { return m_view.slots_dev; }
+    const uint32_t* lut() const      { return m_view.lut_dev; }
+    uint64_t used_device_memory() const { uint64_t b = 0; check( nvbio_qgram_index_device_bytes( m_h, &b ) ); return b; }
+protected:
+    void reset() { if (m_h) (void)nvbio_qgram_index_destroy( m_h ); m_h = nullptr; m_view = nvbio_qgram_index_view(); }
+    void adopt(nvbio_qgram_index_t h) { reset(); m_h = h; check( nvbio_qgram_index_get_view( m_h, &m_view ) ); }
+    nvbio_qgram_index_t    m_h;
+    nvbio_qgram_index_view m_view;
+};
+
+// QGramIndexDevice: the q-grams of every position of a string (coordinate: uint32 position)
+class QGramIndexDevice : public QGramIndexBase
+{
+public:
+    typedef uint32_t    coord_type;
+    typedef nvbio_uint2 hit_type;        // (index position, query coordinate)
+    typedef uint32_t    diagonal_type;
+    static const bool   is_set = false;
+    // build( q, symbol_size, string_len, string, qlut ): string packed as nvbio_string_set symbols of `string_bits` (2, 4 or 8)
+    void build(uint32_t q, uint32_t symbol_size, uint32_t string_len, const void* string, uint32_t string_bits, uint32_t qlut = 0u,
+               int device = 0, hipStream_t stream = 0)
+    {
+        nvbio_qgram_index_t h = nullptr;
+        check( nvbio_qgram_index_build( device, string, string_bits, string_len, q, symbol_size, qlut, &h, stream ) );
+        adopt( h );
+    }
+    const uint32_t* index() const { return (const uint32_t*)m_view.index_dev; }
+};
+
+// QGramSetIndexDevice: the q-grams of the seeds k * seed_interval of every string of a plain set (coordinate: (string_id, string_pos))
+class QGramSetIndexDevice : public QGramIndexBase
+{
+public:
+    typedef nvbio_uint2 coord_type;
+    struct hit_type { uint32_t string_id, string_pos, text_pos, pad; };
+    typedef nvbio_uint2 diagonal_type;   // (diagonal, string_id)
+    static const bool   is_set = true;
+    // build( q, symbol_size, string_set, uniform_seeds_functor( q, seed_interval ), qlut )
+    void build(uint32_t q, uint32_t symbol_size, const string_set& set, uint32_t seed_interval, uint32_t qlut = 0u, int device = 0,
+               hipStream_t stream = 0)
+    {
+        nvbio_qgram_index_t h = nullptr;
+        check( nvbio_qgram_set_index_build( device, &set.c, q, symbol_size, seed_interval, qlut, &h, stream ) );
+        adopt( h );
+    }
+    const nvbio_uint2* index() const { return (const nvbio_uint2*)m_view.index_dev; }
+};
+
+// QGramFilter<device_tag, qgram_index_type, const uint64*, const uint32*>: owns its ranges, slots and temp, grown to what a call needs
+template <typename qgram_index_type>
+class QGramFilterDevice
+{
+public:
+    typedef typename qgram_index_type::hit_type      hit_type;
+    typedef typename qgram_index_type::diagonal_type diagonal_type;
+    typedef nvbio_uint2                              rank_type;
+
+    QGramFilterDevice() : m_index( nullptr ), m_indices( nullptr ), m_n_queries( 0 ), m_n_occurrences( 0 ) {}
+
+    // enact the filter over n_queries q-grams and their coordinates (device pointers); returns the number of hits
+    uint64_t rank(const qgram_index_type& index, uint32_t n_queries, const uint64_t* queries, const uint32_t* indices, hipStream_t stream = 0)
+    {
+        m_index = &index; m_n_queries = n_queries; m_indices = indices;
+        if (m_ranges.size() < n_queries) { m_ranges.resize( n_queries ); m_slots.resize( n_queries ); }
+        uint64_t bytes = 0;
+        check( nvbio_qgram_filter_temp_bytes( n_queries, &bytes ) );
+        if (m_temp.size() < bytes) m_temp.resize( bytes );
+        check( nvbio_qgram_filter_rank( index.handle(), queries, n_queries, m_ranges.data(), m_slots.data(), m_temp.data(), m_temp.size(),
+                                        &m_n_occurrences, stream ) );
+        return m_n_occurrences;
+    }
+    // the hits [begin, end) into caller-owned device memory
+    void locate(uint64_t begin, uint64_t end, hit_type* hits, hipStream_t stream = 0) const
+    {
+        if (end > begin) check( nvbio_qgram_filter_locate( m_index->handle(), m_ranges.data(), m_slots.data(), m_indices, m_n_queries, begin,
+                                                           end, hits, stream ) );
+    }
+    // merge n_hits hits by snapped diagonal into caller-owned merged_hits / merged_counts (n_hits entries each); returns n_merged
+    uint32_t merge(uint32_t interval, uint32_t n_hits, const hit_type* hits, diagonal_type* merged_hits, uint32_t* merged_counts,
+                   hipStream_t stream = 0)
+    {
+        uint64_t bytes = 0;
+        check( nvbio_qgram_filter_merge_temp_bytes( qgram_index_type::is_set ? 1 : 0, n_hits, &bytes ) );
+        if (m_temp.size() < bytes) m_temp.resize( bytes );
+        uint32_t n_merged = 0;
+        check( nvbio_qgram_filter_merge( m_index ? m_index->device() : 0, qgram_index_type::is_set ? 1 : 0, interval, hits, n_hits, merged_hits,
+                                         merged_counts, &n_merged, m_temp.data(), m_temp.size(), stream ) );
+        return n_merged;
+    }
+    uint32_t n_queries() const     { return m_n_queries; }
+    uint64_t n_hits() const        { return m_n_occurrences; }
+    const rank_type* ranges() const { return m_ranges.data(); }
+    const uint64_t*  slots() const  { return m_slots.data(); }
+private:
+    const qgram_index_type*   m_index;
+    const uint32_t*           m_indices;
+    uint32_t                  m_n_queries;
+    uint64_t                  m_n_occurrences;
+    device_vector<rank_type>  m_ranges;
+    device_vector<uint64_t>   m_slots;
+    device_vector<uint8_t>    m_temp;
 };
 
 namespace aln {
