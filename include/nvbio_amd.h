@@ -410,7 +410,7 @@ nvbio_status nvbio_fm_filter_locate(nvbio_fm_index_t index, const nvbio_uint2* r
  *   - inside a read the ranges are in ascending (span begin, span end) order (the reference leaves each read's last group
  *     unreversed);
  *   - nothing is dropped for capacity: a short buffer fails with NVBIO_ERR_INVALID and a message naming the size needed.
- * Working storage is the caller's temp only; the scratch check mode (nvbio_amd_set_scratch_check) does not cover these calls.
+ * Working storage is the caller's temp only.
  * ------------------------------------------------------------------------------------------- */
 
 /* MEMRange<uint32>: SA range [x, y], string id | 0x80000000 on the first kept MEM of a group, span begin | span end << 16 */
@@ -470,7 +470,7 @@ nvbio_status nvbio_mem_filter_locate(nvbio_fm_index_t f_index, const nvbio_mem_r
  * Limits (NVBIO_ERR_INVALID otherwise): 1 <= symbol_size <= 8, q >= 1, q * symbol_size <= 64, qlut <= q, qlut * symbol_size <=
  * 28; text lengths and n_qgrams below 2^32 - 1; text / symbol bits 2, 4 or 8 (the nvbio_string_set packing).
  * Working storage: the builds allocate their own (the arrays stay with the handle); generate (sorted), rank and merge use the
- * caller's temp only, which the scratch check mode (nvbio_amd_set_scratch_check) does not fill.
+ * caller's temp only.
  * ------------------------------------------------------------------------------------------- */
 typedef struct nvbio_qgram_index_s* nvbio_qgram_index_t;     /* opaque handle */
 

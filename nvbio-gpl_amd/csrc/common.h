@@ -68,8 +68,8 @@ public:
     }
     uint64_t end() const   { return check_ ? round( end_ ) + GAP : end_; }   // the bytes a block must hold
     uint64_t bytes() const { return round( end() ) + 256u; }               // the bytes a caller's buffer must hold: room to align its start
-private:
     static uint64_t round(uint64_t x) { return (x + 255u) & ~255ull; }
+private:
     uint8_t* base_;
     bool     check_;
     std::vector<uint64_t>* extents_;
@@ -97,14 +97,15 @@ public:
     // `bytes` of the cache for work on `s`; out of memory: the message printf( fmt, ... ) and NVBIO_ERR_NOMEM
     nvbio_status alloc(const char* tag, uint64_t bytes, hipStream_t s, const char* fmt, ...);
     // the block for the sub-arrays that layout( ScratchLayout& ) declares, run once to size it and once to set the site's pointers into it:
-    // alloc (msg: a format given the block's bytes as unsigned long long), or adopt when the caller passes its temp (sized by `query`)
+    // alloc (msg: a format given the block's bytes as unsigned long long), or adopt when the caller passes its temp (sized by `query`);
+    // `at`: the block starts that many bytes, rounded up to 256, into the caller's temp (behind another block of the same call)
     template <typename Layout>
     nvbio_status alloc_layout(const char* tag, hipStream_t s, const char* msg, Layout layout, void* temp = nullptr, uint64_t temp_bytes = 0,
-                              const char* query = nullptr)
+                              const char* query = nullptr, uint64_t at = 0)
     {
         const bool check = scratch_check_enabled();
         ScratchLayout size( nullptr, check ); layout( size );
-        NVB_CHECK( temp ? adopt( tag, temp, temp_bytes, size.end(), query, s, check )
+        NVB_CHECK( temp ? adopt( tag, temp, temp_bytes, at, size.end(), query, s, check )
                         : alloc_impl( tag, size.end(), s, check, msg, (unsigned long long)size.end() ) );
         ScratchLayout c( p_, check, check ? extents() : nullptr ); layout( c );
         return NVBIO_OK;
@@ -114,9 +115,9 @@ public:
 private:
     nvbio_status alloc_impl(const char* tag, uint64_t bytes, hipStream_t s, bool check, const char* fmt, ...);
     nvbio_status alloc_v(const char* tag, uint64_t bytes, hipStream_t s, bool check, const char* fmt, va_list ap);
-    // the caller's `temp_bytes` at `temp`, its start aligned up to 256, of which `bytes` must remain: else "temp_bytes too small (<query>)"
-    // and NVBIO_ERR_INVALID
-    nvbio_status adopt(const char* tag, void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query, hipStream_t s, bool check);
+    // `bytes` of the caller's `temp_bytes` at `temp`, from round( at ) on behind its start aligned up to 256: else NVBIO_ERR_INVALID and
+    // "temp_bytes <temp_bytes> too small: this call needs <n> (<query>)", n = ScratchLayout::bytes() of a buffer that ends with this block
+    nvbio_status adopt(const char* tag, void* temp, uint64_t temp_bytes, uint64_t at, uint64_t bytes, const char* query, hipStream_t s, bool check);
     std::vector<uint64_t>* extents();                      // check mode: the sub-array extents the pointer pass records
     void release();
     uint8_t*    p_   = nullptr;
@@ -127,9 +128,12 @@ private:
 
 // RAII for the hipMalloc temporaries of an index build (not the stream scratch above): every buffer it allocated and was not told to
 // forget (ownership handed over) is freed when it goes out of scope.  In check mode each buffer is filled (no guard bands) before it is handed out.
+// `what` names the build in NVB_ALLOC's out-of-memory message.
 struct BuildBuffers
 {
     std::vector<void*> ptrs;
+    const char*        what;
+    explicit BuildBuffers(const char* what = "index build") : what( what ) {}
     ~BuildBuffers() { for (void* p : ptrs) (void)hipFree( p ); }
     template <typename T> T* alloc(size_t count)            // nullptr when out of memory
     {
@@ -153,12 +157,19 @@ struct BuildBuffers
     }
 };
 
+// T* var = `count` T's of the BuildBuffers `bufs` in scope; out of memory: "<bufs.what>: out of device memory (var, <bytes> bytes)" and
+// NVBIO_ERR_NOMEM
+#define NVB_ALLOC(var, T, count)                                                                   \
+    T* var = bufs.alloc<T>( count );                                                               \
+    if (!var) { nvbio_amd::set_error( "%s: out of device memory (%s, %zu bytes)", bufs.what, #var, (size_t)(count) * sizeof(T) ); return NVBIO_ERR_NOMEM; }
+
 // ---- runtime value -> template argument ------------------------------------------------------
 // Values<...> lists the values a template is instantiated for, BitsList<Bits<r, t>, ...> the (read_bits, text_bits) pairs.
 // with_value( list, v, f, miss ) returns f( std::integral_constant<int, V>() ) for the listed V equal to v, with_bits( list, rbits,
 // tbits, f, miss ) returns f( Bits<r, t>() ) for the listed pair equal to (rbits, tbits); either returns miss() when the list holds no
 // such entry, so that each call site keeps its own status and message.  Every entry instantiates f; the choice is a chain of compares.
 template <int... Vs> struct Values {};
+using SymbolBits = Values<2, 4, 8>;                       // the symbol widths of an nvbio_string_set: kernels over strings are instantiated for each
 template <int R, int T> struct Bits { static constexpr int r = R, t = T; };
 template <typename... Ps> struct BitsList {};
 

@@ -171,23 +171,26 @@ nvbio_status ScratchBlock::alloc_v(const char* tag, uint64_t bytes, hipStream_t 
     return NVBIO_OK;
 }
 
-nvbio_status ScratchBlock::adopt(const char* tag, void* temp, uint64_t temp_bytes, uint64_t bytes, const char* query, hipStream_t s, bool check)
+nvbio_status ScratchBlock::adopt(const char* tag, void* temp, uint64_t temp_bytes, uint64_t at, uint64_t bytes, const char* query, hipStream_t s, bool check)
 {
     release();
     const uint64_t skip = (256u - ((uintptr_t)temp & 255u)) & 255u;
-    if (temp == nullptr || temp_bytes < skip || temp_bytes - skip < bytes)
+    at = ScratchLayout::round( at );
+    if (temp == nullptr || temp_bytes < skip || temp_bytes - skip < at + bytes)
     {
-        set_error( "invalid argument: temp_bytes too small (%s)", query );
+        set_error( "invalid argument: temp_bytes %llu too small: this call needs %llu (%s)", (unsigned long long)temp_bytes,
+                   (unsigned long long)(ScratchLayout::round( at + bytes ) + 256u), query );
         return NVBIO_ERR_INVALID;
     }
-    p_ = (uint8_t*)temp + skip;
+    p_ = (uint8_t*)temp + skip + at;
     if (check)
     {
-        // the caller's whole buffer is filled; checked: the alignment skip, the gaps and at most a band's worth behind the layout
-        const uint64_t tail = temp_bytes - skip - bytes;
-        chk_ = new ScratchCheckState{ tag, nullptr, -(int64_t)skip, (int64_t)(bytes + (tail < (uint64_t)CHECK_BAND ? tail : (uint64_t)CHECK_BAND)), { 0, bytes } };
+        // the caller's buffer from the block's start on is filled (the first block's from the buffer's start); checked: the alignment skip
+        // (the first block's), the gaps and at most a band's worth behind the layout
+        const uint64_t lead = at ? 0u : skip, tail = temp_bytes - skip - at - bytes;
+        chk_ = new ScratchCheckState{ tag, nullptr, -(int64_t)lead, (int64_t)(bytes + (tail < (uint64_t)CHECK_BAND ? tail : (uint64_t)CHECK_BAND)), { 0, bytes } };
         s_ = s;
-        NVB_HIP( hipMemsetAsync( temp, g_check_fill, temp_bytes, s ) );
+        NVB_HIP( hipMemsetAsync( p_ - lead, g_check_fill, lead + bytes + tail, s ) );
     }
     return NVBIO_OK;
 }

@@ -241,10 +241,7 @@ ssa_kernel(const uint32_t* __restrict__ sa, const uint32_t sa_int, const uint64_
         ssa[j] = (j == 0) ? 0xFFFFFFFFu : sa[(size_t)sa_int * j - 1u];  // row sa_int*j of the full SA
 }
 
-// ---- index-build temporaries (BuildBuffers, common.h) ------------------------------------------
-#define NVB_ALLOC(var, T, count)                                                                   \
-    T* var = bufs.alloc<T>( count );                                                               \
-    if (!var) { set_error( "index build: out of device memory (%s, %zu bytes)", #var, (size_t)(count) * sizeof(T) ); return NVBIO_ERR_NOMEM; }
+// ---- index-build temporaries (BuildBuffers and NVB_ALLOC, common.h) ------------------------------
 
 // inclusive max-scan in place, in chunks small enough for 32-bit-sized device primitives
 static nvbio_status scan_max_inplace(uint32_t* buf, uint64_t n, BuildBuffers& bufs, hipStream_t s)

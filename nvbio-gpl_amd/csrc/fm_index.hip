@@ -1024,8 +1024,6 @@ residual_locate_kernel(const DevIndex f, const uint2* __restrict__ ranges, const
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-using SymbolBits = Values<2, 4, 8>;                       // what make_set admits: every seed / match kernel is instantiated for each (common.h: with_value)
-
 static nvbio_status make_set(const nvbio_string_set* s, StringSetDev* d)
 {
     NVB_REQUIRE( s != nullptr, "queries is NULL" );

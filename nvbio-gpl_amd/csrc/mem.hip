@@ -35,8 +35,7 @@
 // output) or per entry (left, split); no per-lane arrays (a runtime-indexed private array would live in scratch): each lane keeps its
 // current (f_range, r_range, prev_range) in registers and writes every pushed range straight to global memory.  One forward step of
 // the reverse index is one rank4 at two rows -- one record, or two when the rows fall in different 64-symbol blocks.
-// Working storage is the caller's temp (nvbio_mem_filter_temp_bytes), carved with a plain ScratchLayout: the scratch check mode
-// does not cover these calls.
+// Working storage is the caller's temp (nvbio_mem_filter_temp_bytes), two ScratchBlocks: see MemTemp.
 #include "fm_device.h"
 #include <hipcub/hipcub.hpp>
 
@@ -407,8 +406,9 @@ static nvbio_status mem_total(const MemReads& q, hipStream_t s, uint64_t* total)
     return NVBIO_OK;
 }
 
-// the caller's temp: per-read counters, the dense candidates, the candidate regions (reused as the split arena, of `cap` >= total
-// entries), and the scans' hipcub temporaries last
+// the caller's temp, two blocks: the head -- per-read counters, per-candidate scan arrays, the dense candidates -- and, from the
+// head's rounded end, the arena -- the candidate regions (reused as the split arena, of `cap` >= total entries) and the scans'
+// hipcub temporaries.  A larger split arena lays out the arena again and leaves the head alone: the head is live by then, the arena is not.
 struct MemTemp
 {
     uint32_t* cnt;   uint32_t* off;  uint32_t* kept; uint32_t* first_tmp;
@@ -424,23 +424,26 @@ struct MemTemp
         (void)hipcub::DeviceScan::InclusiveSum( nullptr, b, sizes, (uint64_t*)nullptr, n );
         return a > b ? a : b;
     }
-    void carve(ScratchLayout& c, uint32_t n, uint64_t total, uint64_t cap)
+    void head(ScratchLayout& c, uint32_t n, uint64_t total)
     {
         cnt  = c.take<uint32_t>( n + 1u ); off = c.take<uint32_t>( n + 1u ); kept = c.take<uint32_t>( n + 1u );
         first_tmp = c.take<uint32_t>( n + 1u );
         scnt = c.take<uint32_t>( total + 1u ); soff = c.take<uint32_t>( total + 1u );
         misc = c.take<uint32_t>( 8 );
-        dense = c.take<uint4>( total ); cand = c.take<uint4>( cap );
+        dense = c.take<uint4>( total );
+    }
+    void arena(ScratchLayout& c, uint32_t n, uint64_t cap)
+    {
+        cand = c.take<uint4>( cap );
         cub_bytes = cub_need( (cap > n ? cap : n) + 1u );
         cub = c.take<uint8_t>( cub_bytes );
     }
+    static uint64_t head_end(uint32_t n, uint64_t total)     // where the arena starts, before rounding
+    {
+        MemTemp t; ScratchLayout c( nullptr, scratch_check_enabled() ); t.head( c, n, total );
+        return c.end();
+    }
 };
-
-static uint64_t mem_temp_bytes(uint32_t n, uint64_t total, uint64_t cap)
-{
-    MemTemp t; ScratchLayout size; t.carve( size, n, total, cap );
-    return size.bytes();
-}
 
 // exclusive scan of in[0, n) into out[0, n] (out[n] = the total)
 static nvbio_status scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, MemTemp& T, hipStream_t s)
@@ -470,7 +473,9 @@ nvbio_status nvbio_mem_filter_temp_bytes(const nvbio_string_set* reads, const nv
     NVB_REQUIRE( reads && params && bytes, "NULL argument" );
     MemReads q; NVB_CHECK( mem_reads( reads, &q ) );
     uint64_t total = 0; NVB_CHECK( mem_total( q, (hipStream_t)stream, &total ) );
-    *bytes = mem_temp_bytes( q.n, total, total );
+    MemTemp t; ScratchLayout arena( nullptr, scratch_check_enabled() ); t.arena( arena, q.n, total );
+    ScratchLayout both; both.take<uint8_t>( MemTemp::head_end( q.n, total ) ); both.take<uint8_t>( arena.end() );   // as nvbio_mem_filter_rank adopts them
+    *bytes = both.bytes();
     return NVBIO_OK;
 }
 
@@ -499,15 +504,16 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
     }
     NVB_REQUIRE( first_range_dev && temp_dev, "NULL device pointer" );
     uint64_t total = 0; NVB_CHECK( mem_total( q, s, &total ) );
-    const uint64_t need = mem_temp_bytes( q.n, total, total );
-    if (temp_bytes < need)
-    {
-        set_error( "invalid argument: temp_bytes %llu too small: this call needs %llu (nvbio_mem_filter_temp_bytes)",
-                   (unsigned long long)temp_bytes, (unsigned long long)need );
-        return NVBIO_ERR_INVALID;
-    }
-    uint8_t* base = (uint8_t*)(((uintptr_t)temp_dev + 255u) & ~(uintptr_t)255u);
-    MemTemp T; { ScratchLayout c( base ); T.carve( c, q.n, total, total ); }
+    // the arena first: its size check covers the whole temp, and its message names what the call needs; the head then ends where it begins
+    MemTemp T;
+    ScratchBlock arena, head;
+    auto take_arena = [&](uint64_t cap) {
+        return arena.alloc_layout( "mem_filter_arena", s, "MEM filter: out of device memory", [&](ScratchLayout& c) { T.arena( c, q.n, cap ); },
+                                   temp_dev, temp_bytes, "nvbio_mem_filter_temp_bytes", MemTemp::head_end( q.n, total ) );
+    };
+    NVB_CHECK( take_arena( total ) );
+    NVB_CHECK( head.alloc_layout( "mem_filter_head", s, "MEM filter: out of device memory", [&](ScratchLayout& c) { T.head( c, q.n, total ); },
+                                  temp_dev, (uint64_t)(arena.get() - (uint8_t*)temp_dev), "nvbio_mem_filter_temp_bytes" ) );
 
     NVB_HIP( hipMemsetAsync( T.misc, 0, 32, s ) );
     uint64_t* rec = (uint64_t*)(T.misc + 2);
@@ -515,13 +521,13 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
     const bool do_split = params->split_len < 0xFFFFFFFFu;
 
     // right pass -> candidates per read
+    (void)with_value( SymbolBits(), bits, [&](auto BITS)
     {
-        const dim3 grid( grid_for( q.n ) ), block( 256 );
-        if (bits == 2)      hipLaunchKernelGGL( mem_right_kernel<2>, grid, block, 0, s, f, r, q, (uint32_t)total, params->min_intv, T.cand, T.cnt, T.misc, rec );
-        else if (bits == 4) hipLaunchKernelGGL( mem_right_kernel<4>, grid, block, 0, s, f, r, q, (uint32_t)total, params->min_intv, T.cand, T.cnt, T.misc, rec );
-        else                hipLaunchKernelGGL( mem_right_kernel<8>, grid, block, 0, s, f, r, q, (uint32_t)total, params->min_intv, T.cand, T.cnt, T.misc, rec );
-        NVB_HIP( hipGetLastError() );
-    }
+        hipLaunchKernelGGL( mem_right_kernel<BITS>, dim3( grid_for( q.n ) ), dim3(256), 0, s, f, r, q, (uint32_t)total, params->min_intv, T.cand, T.cnt,
+                            T.misc, rec );
+        return true;
+    }, [] { return false; } );
+    NVB_HIP( hipGetLastError() );
     NVB_CHECK( scan_u32( T.cnt, T.off, q.n, T, s ) );
     uint32_t n_cand = 0, err = 0;
     NVB_CHECK( read_u32( T.off + q.n, &n_cand, s ) );
@@ -531,10 +537,11 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
 
     auto left = [&](uint4* mems, uint32_t n) -> nvbio_status {
         if (n == 0) return NVBIO_OK;
-        const dim3 grid( grid_for( n ) ), block( 256 );
-        if (bits == 2)      hipLaunchKernelGGL( mem_left_kernel<2>, grid, block, 0, s, f, q, mems, n, params->min_intv, rec );
-        else if (bits == 4) hipLaunchKernelGGL( mem_left_kernel<4>, grid, block, 0, s, f, q, mems, n, params->min_intv, rec );
-        else                hipLaunchKernelGGL( mem_left_kernel<8>, grid, block, 0, s, f, q, mems, n, params->min_intv, rec );
+        (void)with_value( SymbolBits(), bits, [&](auto BITS)
+        {
+            hipLaunchKernelGGL( mem_left_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), 0, s, f, q, mems, n, params->min_intv, rec );
+            return true;
+        }, [] { return false; } );
         NVB_HIP( hipGetLastError() );
         return NVBIO_OK;
     };
@@ -549,34 +556,23 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
     const uint32_t* final_soff = nullptr;
     if (do_split && n_cand)
     {
-        const dim3 grid( grid_for( n_cand ) ), block( 256 );
-        uint32_t arena_cap = 0;
-#define NVB_SPLIT(BITS, COUNT, ARENA, SOFF) hipLaunchKernelGGL( (mem_split_kernel<BITS, COUNT>), grid, block, 0, s, f, r, q, (const uint4*)T.dense, n_cand, \
-            (const uint32_t*)T.off, (const uint32_t*)T.kept, params->split_len, params->split_width, T.scnt, SOFF, ARENA, arena_cap, T.misc, rec )
-        if (bits == 2)      NVB_SPLIT(2, true, (uint4*)nullptr, (const uint32_t*)nullptr);
-        else if (bits == 4) NVB_SPLIT(4, true, (uint4*)nullptr, (const uint32_t*)nullptr);
-        else                NVB_SPLIT(8, true, (uint4*)nullptr, (const uint32_t*)nullptr);
+        // count (COUNT = true: no arena, no soff), then write into the arena of arena_cap entries
+        auto split = [&](auto COUNT, uint4* arena_p, const uint32_t* soff, uint32_t arena_cap) {
+            (void)with_value( SymbolBits(), bits, [&](auto BITS)
+            {
+                hipLaunchKernelGGL( (mem_split_kernel<BITS, COUNT>), dim3( grid_for( n_cand ) ), dim3(256), 0, s, f, r, q, (const uint4*)T.dense, n_cand,
+                                    (const uint32_t*)T.off, (const uint32_t*)T.kept, params->split_len, params->split_width, T.scnt, soff, arena_p,
+                                    arena_cap, T.misc, rec );
+                return true;
+            }, [] { return false; } );
+        };
+        split( std::true_type(), (uint4*)nullptr, (const uint32_t*)nullptr, 0u );
         NVB_HIP( hipGetLastError() );
         NVB_CHECK( scan_u32( T.scnt, T.soff, n_cand, T, s ) );
         uint32_t n_split = 0;
         NVB_CHECK( read_u32( T.soff + n_cand, &n_split, s ) );
-        if (n_split > total)
-        {
-            // the split arena is the candidate region: a larger one moves only the hipcub temporaries behind it
-            const uint64_t need2 = mem_temp_bytes( q.n, total, n_split );
-            if (temp_bytes < need2)
-            {
-                set_error( "invalid argument: temp_bytes %llu too small: the split pass of this call needs %llu", (unsigned long long)temp_bytes,
-                           (unsigned long long)need2 );
-                return NVBIO_ERR_INVALID;
-            }
-            ScratchLayout c( base ); T.carve( c, q.n, total, n_split );
-        }
-        arena_cap = n_split > total ? n_split : (uint32_t)total;
-        if (bits == 2)      NVB_SPLIT(2, false, T.cand, (const uint32_t*)T.soff);
-        else if (bits == 4) NVB_SPLIT(4, false, T.cand, (const uint32_t*)T.soff);
-        else                NVB_SPLIT(8, false, T.cand, (const uint32_t*)T.soff);
-#undef NVB_SPLIT
+        if (n_split > total) NVB_CHECK( take_arena( n_split ) );     // the split arena is the candidate region: a larger one moves the hipcub temporaries
+        split( std::false_type(), T.cand, (const uint32_t*)T.soff, n_split > total ? n_split : (uint32_t)total );
         NVB_HIP( hipGetLastError() );
         NVB_CHECK( left( T.cand, n_split ) );
         hipLaunchKernelGGL( mem_discard_kernel, dim3( grid_for( q.n ) ), dim3(256), 0, s, q.n, (const uint32_t*)T.off, (const uint32_t*)T.soff,

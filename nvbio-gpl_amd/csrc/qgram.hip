@@ -50,8 +50,7 @@
 // (two upper_bounds), so each output's own upper_bound runs over a few cached entries; a 10^4-copy repeat is spread over 10^4 lanes.
 // Extraction, seed enumeration, LUT build and the diagonal snap are one lane per item.  No private arrays; sorting, scans and
 // run-length encoding are rocPRIM.  Working storage: the index builds take BuildBuffers (their arrays are handed to the handle),
-// generate_qgrams (sorted), rank and merge take the caller's temp carved with a plain ScratchLayout: the scratch check mode fills
-// the build buffers but does not cover the caller's temp of these calls.
+// generate_qgrams (sorted), rank and merge a ScratchBlock on the caller's temp.
 // Registers (gfx950 code object, -Rpass-analysis=kernel-resource-usage): VGPRs extract 14-16, seed count 8, seed enumerate 22-24,
 // LUT 11, range 11, locate 20, diagonal 9-10; private_segment_fixed_size = 0 (no scratch) for every one.
 #include "common.h"
@@ -286,10 +285,6 @@ qgram_diagonal_kernel(const void* __restrict__ hits, const uint32_t n, const uin
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-#define NVB_QALLOC(var, T, count)                                                                  \
-    T* var = bufs.alloc<T>( count );                                                               \
-    if (!var) { set_error( "q-gram index build: out of device memory (%s, %zu bytes)", #var, (size_t)(count) * sizeof(T) ); return NVBIO_ERR_NOMEM; }
-
 static nvbio_status check_qgram_params(const uint32_t q, const uint32_t ss, const uint32_t qlut)
 {
     NVB_REQUIRE( ss >= 1 && ss <= 8, "symbol_size must be in [1, 8]" );
@@ -305,32 +300,24 @@ static nvbio_status check_text_bits(const uint32_t bits)
     return NVBIO_OK;
 }
 
-template <typename F>
-static void with_text_bits(const uint32_t bits, F&& f)
-{
-    if (bits == 2)      f( std::integral_constant<int, 2>() );
-    else if (bits == 4) f( std::integral_constant<int, 4>() );
-    else                f( std::integral_constant<int, 8>() );
-}
-
 // sort (q-gram, coordinate) pairs stably over [0, q * ss), run-length encode them and build slots and the LUT; hands qgrams, slots,
 // index and lut to a new handle.  keys / vals hold n entries (the unsorted pairs); V is uint32 or uint64 (a uint2 coordinate).
 template <typename V>
 static nvbio_status finish_index(BuildBuffers& bufs, const int device, const uint32_t q, const uint32_t ss, const uint32_t qlut, const uint32_t is_set,
                                  const uint32_t n, uint64_t* keys, V* vals, hipStream_t s, nvbio_qgram_index_t* out)
 {
-    NVB_QALLOC( skeys, uint64_t, n );
-    NVB_QALLOC( index, V, n );
-    NVB_QALLOC( qgrams, uint64_t, n );
-    NVB_QALLOC( counts, uint32_t, n );
-    NVB_QALLOC( d_runs, uint64_t, 1 );
+    NVB_ALLOC( skeys, uint64_t, n );
+    NVB_ALLOC( index, V, n );
+    NVB_ALLOC( qgrams, uint64_t, n );
+    NVB_ALLOC( counts, uint32_t, n );
+    NVB_ALLOC( d_runs, uint64_t, 1 );
     uint64_t n_unique = 0;
     if (n)
     {
         size_t a = 0, b = 0;
         NVB_HIP( rocprim::radix_sort_pairs( nullptr, a, keys, skeys, vals, index, (size_t)n, 0u, q * ss, s ) );
         NVB_HIP( rocprim::run_length_encode( nullptr, b, skeys, (size_t)n, qgrams, counts, d_runs, s ) );
-        NVB_QALLOC( temp, uint8_t, a > b ? a : b );
+        NVB_ALLOC( temp, uint8_t, a > b ? a : b );
         NVB_HIP( rocprim::radix_sort_pairs( temp, a, keys, skeys, vals, index, (size_t)n, 0u, q * ss, s ) );
         NVB_HIP( rocprim::run_length_encode( temp, b, skeys, (size_t)n, qgrams, counts, d_runs, s ) );
         NVB_HIP( hipMemcpyAsync( &n_unique, d_runs, 8, hipMemcpyDeviceToHost, s ) );
@@ -339,13 +326,13 @@ static nvbio_status finish_index(BuildBuffers& bufs, const int device, const uin
     }
     bufs.release( keys ); bufs.release( vals ); bufs.release( skeys );
     // slots = exclusive scan of the counts (n_unique + 1 entries)
-    NVB_QALLOC( slots, uint32_t, n_unique + 1u );
+    NVB_ALLOC( slots, uint32_t, n_unique + 1u );
     NVB_HIP( hipMemsetAsync( slots, 0, 4, s ) );
     if (n_unique)
     {
         size_t a = 0;
         NVB_HIP( rocprim::inclusive_scan( nullptr, a, counts, slots + 1, (size_t)n_unique, rocprim::plus<uint32_t>(), s ) );
-        NVB_QALLOC( temp, uint8_t, a );
+        NVB_ALLOC( temp, uint8_t, a );
         NVB_HIP( rocprim::inclusive_scan( temp, a, counts, slots + 1, (size_t)n_unique, rocprim::plus<uint32_t>(), s ) );
         NVB_HIP( hipStreamSynchronize( s ) );
         bufs.release( temp );
@@ -429,19 +416,6 @@ struct GenerateTemp
     }
 };
 
-static nvbio_status temp_check(const uint64_t temp_bytes, const uint64_t need, const char* query)
-{
-    if (temp_bytes < need)
-    {
-        set_error( "invalid argument: temp_bytes %llu too small: this call needs %llu (%s)", (unsigned long long)temp_bytes,
-                   (unsigned long long)need, query );
-        return NVBIO_ERR_INVALID;
-    }
-    return NVBIO_OK;
-}
-
-static uint8_t* align_temp(void* p) { return (uint8_t*)(((uintptr_t)p + 255u) & ~(uintptr_t)255u); }
-
 } // namespace nvbio_amd
 
 using namespace nvbio_amd;
@@ -459,15 +433,17 @@ nvbio_status nvbio_qgram_index_build(int device, const void* text_dev, uint32_t 
     NVB_REQUIRE( length < 0xFFFFFFFFu, "length must be below 2^32 - 1" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    BuildBuffers bufs;
-    NVB_QALLOC( keys, uint64_t, length );
-    NVB_QALLOC( pos, uint32_t, length );
+    BuildBuffers bufs( "q-gram index build" );
+    NVB_ALLOC( keys, uint64_t, length );
+    NVB_ALLOC( pos, uint32_t, length );
     if (length)
     {
-        with_text_bits( text_bits, [&](auto B) {
-            hipLaunchKernelGGL( qgram_extract_kernel<decltype(B)::value>, dim3( grid_for( length ) ), dim3(256), 0, s, text_dev, length, q,
-                                symbol_size, 0u, length, keys, pos );
-        } );
+        (void)with_value( SymbolBits(), text_bits, [&](auto BITS)
+        {
+            hipLaunchKernelGGL( qgram_extract_kernel<BITS>, dim3( grid_for( length ) ), dim3(256), 0, s, text_dev, length, q, symbol_size, 0u,
+                                length, keys, pos );
+            return true;
+        }, [] { return false; } );
         NVB_HIP( hipGetLastError() );
     }
     return finish_index<uint32_t>( bufs, device, q, symbol_size, qlut, 0u, length, keys, pos, s, out );
@@ -488,9 +464,9 @@ nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     QGramSet qs{ set->symbols_dev, set->offsets_dev, set->offsets_are_ranges, set->fixed_len, set->stride, set->n };
-    BuildBuffers bufs;
-    NVB_QALLOC( cnt, uint64_t, set->n + 1u );
-    NVB_QALLOC( first, uint64_t, set->n + 1u );
+    BuildBuffers bufs( "q-gram index build" );
+    NVB_ALLOC( cnt, uint64_t, set->n + 1u );
+    NVB_ALLOC( first, uint64_t, set->n + 1u );
     uint64_t total = 0;
     NVB_HIP( hipMemsetAsync( first, 0, 8, s ) );
     if (set->n)
@@ -499,7 +475,7 @@ nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set
         NVB_HIP( hipGetLastError() );
         size_t a = 0;
         NVB_HIP( rocprim::inclusive_scan( nullptr, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
-        NVB_QALLOC( temp, uint8_t, a );
+        NVB_ALLOC( temp, uint8_t, a );
         NVB_HIP( rocprim::inclusive_scan( temp, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
         NVB_HIP( hipMemcpyAsync( &total, first + set->n, 8, hipMemcpyDeviceToHost, s ) );
         NVB_HIP( hipStreamSynchronize( s ) );
@@ -508,14 +484,16 @@ nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set
     bufs.release( cnt );
     NVB_REQUIRE( total < 0xFFFFFFFFull, "the set has 2^32 - 1 seeds or more" );
     const uint32_t n = (uint32_t)total;
-    NVB_QALLOC( keys, uint64_t, n );
-    NVB_QALLOC( coords, uint64_t, n );
+    NVB_ALLOC( keys, uint64_t, n );
+    NVB_ALLOC( coords, uint64_t, n );
     if (n)
     {
-        with_text_bits( set->symbol_bits, [&](auto B) {
-            hipLaunchKernelGGL( qgram_seed_enumerate_kernel<decltype(B)::value>, dim3( grid_for( n ) ), dim3(256), 0, s, qs, q, symbol_size,
-                                seed_interval, (const uint64_t*)first, n, keys, (uint2*)coords );
-        } );
+        (void)with_value( SymbolBits(), set->symbol_bits, [&](auto BITS)
+        {
+            hipLaunchKernelGGL( qgram_seed_enumerate_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), 0, s, qs, q, symbol_size, seed_interval,
+                                (const uint64_t*)first, n, keys, (uint2*)coords );
+            return true;
+        }, [] { return false; } );
         NVB_HIP( hipGetLastError() );
     }
     NVB_HIP( hipStreamSynchronize( s ) );
@@ -570,8 +548,8 @@ nvbio_status nvbio_generate_qgrams_temp_bytes(uint32_t n, int sort, uint64_t* by
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
     if (!sort) { *bytes = 0; return NVBIO_OK; }
-    GenerateTemp t; ScratchLayout size; t.carve( size, n );
-    *bytes = size.bytes();
+    GenerateTemp t; ScratchLayout c( nullptr, scratch_check_enabled() ); t.carve( c, n );
+    *bytes = c.bytes();
     return NVBIO_OK;
 }
 
@@ -590,17 +568,19 @@ nvbio_status nvbio_generate_qgrams(int device, uint32_t q, uint32_t symbol_size,
     hipStream_t s = (hipStream_t)stream;
     uint64_t* keys = qgrams_dev; uint32_t* pos = indices_dev;
     GenerateTemp T;
+    ScratchBlock temp;
     if (sort)
     {
-        ScratchLayout size; T.carve( size, n );
-        NVB_CHECK( temp_check( temp_bytes, size.bytes(), "nvbio_generate_qgrams_temp_bytes" ) );
-        ScratchLayout c( align_temp( temp_dev ) ); T.carve( c, n );
+        NVB_CHECK( temp.alloc_layout( "qgram_generate", s, "generate_qgrams: out of device memory", [&](ScratchLayout& c) { T.carve( c, n ); },
+                                      temp_dev, temp_bytes, "nvbio_generate_qgrams_temp_bytes" ) );
         keys = T.keys; pos = T.pos;
     }
-    with_text_bits( text_bits, [&](auto B) {
-        hipLaunchKernelGGL( qgram_extract_kernel<decltype(B)::value>, dim3( grid_for( n ) ), dim3(256), 0, s, text_dev, text_len, q, symbol_size,
-                            first_pos, n, keys, pos );
-    } );
+    (void)with_value( SymbolBits(), text_bits, [&](auto BITS)
+    {
+        hipLaunchKernelGGL( qgram_extract_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), 0, s, text_dev, text_len, q, symbol_size, first_pos, n,
+                            keys, pos );
+        return true;
+    }, [] { return false; } );
     NVB_HIP( hipGetLastError() );
     if (sort)
     {
@@ -625,7 +605,8 @@ nvbio_status nvbio_qgram_ranges(nvbio_qgram_index_t index, const uint64_t* qgram
 nvbio_status nvbio_qgram_filter_temp_bytes(uint32_t n_queries, uint64_t* bytes)
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
-    *bytes = rank_cub_bytes( n_queries ) + 256u;
+    ScratchLayout c( nullptr, scratch_check_enabled() ); c.take<uint8_t>( rank_cub_bytes( n_queries ) );
+    *bytes = c.bytes();
     return NVBIO_OK;
 }
 
@@ -636,15 +617,18 @@ nvbio_status nvbio_qgram_filter_rank(nvbio_qgram_index_t index, const uint64_t* 
     *n_hits = 0;
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( qgrams_dev && ranges_dev && slots_dev && temp_dev, "NULL device pointer" );
-    const uint64_t cub_bytes = rank_cub_bytes( n );
-    NVB_CHECK( temp_check( temp_bytes, cub_bytes + 256u, "nvbio_qgram_filter_temp_bytes" ) );
     DeviceGuard g( index->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
+    const uint64_t cub_bytes = rank_cub_bytes( n );
+    uint8_t* cub = nullptr;
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc_layout( "qgram_filter_rank", s, "q-gram filter rank: out of device memory", [&](ScratchLayout& c) { cub = c.take<uint8_t>( cub_bytes ); },
+                                  temp_dev, temp_bytes, "nvbio_qgram_filter_temp_bytes" ) );
     hipLaunchKernelGGL( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, view_of( index ), qgrams_dev, n, (uint2*)ranges_dev );
     NVB_HIP( hipGetLastError() );
     rocprim::transform_iterator<const uint2*, QGramRangeSize, uint64_t> sizes( (const uint2*)ranges_dev, QGramRangeSize() );
     size_t bytes = cub_bytes;
-    NVB_HIP( rocprim::inclusive_scan( align_temp( temp_dev ), bytes, sizes, slots_dev, (size_t)n, rocprim::plus<uint64_t>(), s ) );
+    NVB_HIP( rocprim::inclusive_scan( cub, bytes, sizes, slots_dev, (size_t)n, rocprim::plus<uint64_t>(), s ) );
     NVB_HIP( hipMemcpyAsync( n_hits, slots_dev + (n - 1u), 8, hipMemcpyDeviceToHost, s ) );
     NVB_HIP( hipStreamSynchronize( s ) );
     return NVBIO_OK;
@@ -675,8 +659,8 @@ nvbio_status nvbio_qgram_filter_locate(nvbio_qgram_index_t index, const nvbio_ui
 nvbio_status nvbio_qgram_filter_merge_temp_bytes(int is_set, uint32_t n_hits, uint64_t* bytes)
 {
     NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
-    MergeTemp t; ScratchLayout size; t.carve( size, is_set != 0, n_hits );
-    *bytes = size.bytes();
+    MergeTemp t; ScratchLayout c( nullptr, scratch_check_enabled() ); t.carve( c, is_set != 0, n_hits );
+    *bytes = c.bytes();
     return NVBIO_OK;
 }
 
@@ -689,11 +673,12 @@ nvbio_status nvbio_qgram_filter_merge(int device, int is_set, uint32_t interval,
     if (n_hits == 0) return NVBIO_OK;
     NVB_REQUIRE( hits_dev && merged_dev && counts_dev && temp_dev, "NULL device pointer" );
     const bool set = is_set != 0;
-    MergeTemp T;
-    { ScratchLayout size; T.carve( size, set, n_hits ); NVB_CHECK( temp_check( temp_bytes, size.bytes(), "nvbio_qgram_filter_merge_temp_bytes" ) ); }
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    { ScratchLayout c( align_temp( temp_dev ) ); T.carve( c, set, n_hits ); }
+    MergeTemp T;
+    ScratchBlock temp;
+    NVB_CHECK( temp.alloc_layout( "qgram_filter_merge", s, "q-gram filter merge: out of device memory", [&](ScratchLayout& c) { T.carve( c, set, n_hits ); },
+                                  temp_dev, temp_bytes, "nvbio_qgram_filter_merge_temp_bytes" ) );
     const dim3 grid( grid_for( n_hits ) ), block( 256 );
     size_t a = T.cub_bytes, b = T.cub_bytes;
     if (set)

@@ -5,7 +5,8 @@ sub-array and after the last, and all of it (a caller's temp included) holds the
 that writes past a sub-array damages a band or gap (the report says where); one that reads scratch it never wrote reads the fill instead of
 the previous call's right answer, and its results stop equalling the oracle.  The fills: 0x00 (a fresh block), 0xFF (every flag "needs work",
 every count huge), 0x02 (every unwritten need_dp flag a third-chance job).  Every case runs with the library's own scratch (temp=None) and,
-where the entry point takes one, with a caller temp.  The cases are the other modules' tests, called through their modules."""
+where the entry point takes one, with a caller temp (the MEM and q-gram filters take only a caller temp).  The cases are the other
+modules' tests, called through their modules."""
 import ctypes
 
 import numpy as np
@@ -15,11 +16,14 @@ import oracle
 import test_gpu_fm as fm
 import test_gpu_gotoh as g
 import test_gpu_gotoh_full as gf
+import test_gpu_mem as mem
 import test_gpu_pipeline as pl
+import test_gpu_qgram as qg
 import test_gpu_rank_dictionary as rd
 import test_gpu_seed_hits as sh
 import test_gpu_seed_pass as sp
 import test_gpu_traceback as tb
+from test_mem_oracle import NaiveIndex, make_reads, make_text
 from test_scratch_sites import SCRATCH_TAGS
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +156,46 @@ def test_sort_unique_keys(amd, fill, checked):
             m = int(n_out.item())
             assert m == len(want)
             assert np.array_equal(d[:m].cpu().numpy().view(np.uint64), want)
+
+
+# ---- MEM filter and q-gram filter: the caller's temp only -----------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mem_texts(amd, orc):
+    """test_gpu_mem's 60 kbp workload, and a 4 kbp text over two symbols whose split entries outnumber the reads' symbols several times"""
+    out = []
+    rng = np.random.default_rng(2)
+    text = make_text(rng, 60_000)
+    text[30_000:31_200] = np.tile(text[500:560], 20)
+    reads = make_reads(rng, text, 150, [1, 30, 100, 150, 300])
+    out.append((NaiveIndex(text), *mem._indices(amd, orc, text), reads))
+    rng = np.random.default_rng(7)
+    text = rng.integers(0, 2, 4000, dtype=np.uint8)
+    reads = [text[p:p + 150].copy() for p in rng.integers(0, 4000 - 150, 40)] + [rng.integers(0, 2, 150, dtype=np.uint8) for _ in range(10)]
+    out.append((NaiveIndex(text), *mem._indices(amd, orc, text), reads))
+    yield out
+    for _, f, r, _ in out:
+        f.close(); r.close()
+
+
+@fills
+def test_mem_filter(amd, orc, fill, checked, mem_texts):
+    """ragged and fixed-length sets, with and without split.  The binary text's split arena outgrows the candidate regions: the first
+    attempt fails naming the temp it needs, the second moves the arena within the grown caller temp and fails on max_ranges, the third
+    succeeds"""
+    (idx, f, r, reads), (bidx, bf, br, breads) = mem_texts
+    for params in (dict(min_intv=1), dict(min_intv=2, max_intv=20, split_len=28, split_width=10)):
+        mem._check(amd, orc, idx, f, r, reads, 4, **params)
+        mem._check(amd, orc, idx, f, r, [x for x in reads if len(x) == 150], 8, fixed=True, **params)
+    mf, _, _ = mem._check(amd, orc, bidx, bf, br, breads, 2, min_intv=2, split_len=8, split_width=1000)
+    assert mf.attempts == 3
+
+
+@fills
+def test_qgram_filter(amd, orc, fill, checked):
+    qg.test_string_index_and_filter(amd, orc, 4, 2, True, 12, 8)
+    qg.test_set_index_and_filter(amd, orc, "ragged", 3, 4, 2, 5, 1)
+    qg.test_generate_qgrams(amd, orc, 4, 2, 12)
+    qg.test_merge_wrapped_diagonals(amd)
 
 
 # ---- whole pipeline (read_queue_filter and select_flagged_indices are the C++ host loop's) -------------------------------------------

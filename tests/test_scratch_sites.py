@@ -14,6 +14,8 @@ SCRATCH_TAGS = (
     "banded_tb_job_list", "banded_tb_dirs",
     "full_tb_job_list", "full_tb_dirs",
     "rank_dictionary_build", "sort_unique_keys", "read_queue_filter", "select_flagged_indices",
+    "mem_filter_head", "mem_filter_arena",
+    "qgram_generate", "qgram_filter_rank", "qgram_filter_merge",
 )
 
 _CALL = re.compile(r"(?:\.|->)alloc(?:_layout)?\(\s*(\"[a-z0-9_]*\")?")
@@ -31,11 +33,11 @@ def site_tags():
     return out
 
 
-def test_every_scratch_site_has_an_expected_tag():
+def test_scratch_site_tags_equal_the_expected_set():
     sites = site_tags()
     untagged = [f for t, f in sites if t is None]
     assert not untagged, "ScratchBlock alloc without a tag in %s" % untagged
     tags = [t for t, _ in sites]
     assert len(tags) == len(set(tags)), "tags must be unique: %s" % sorted(tags)
     assert sorted(tags) == sorted(SCRATCH_TAGS)
-    assert len(tags) == 18
+    assert len(tags) == 23
