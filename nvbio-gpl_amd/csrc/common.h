@@ -170,6 +170,7 @@ struct BuildBuffers
 // such entry, so that each call site keeps its own status and message.  Every entry instantiates f; the choice is a chain of compares.
 template <int... Vs> struct Values {};
 using SymbolBits = Values<2, 4, 8>;                       // the symbol widths of an nvbio_string_set: kernels over strings are instantiated for each
+nvbio_status bad_symbol_bits();                           // the miss of a dispatch over SymbolBits: "symbol_bits must be 2, 4 or 8", NVBIO_ERR_INVALID
 template <int R, int T> struct Bits { static constexpr int r = R, t = T; };
 template <typename... Ps> struct BitsList {};
 
@@ -211,6 +212,22 @@ static inline unsigned grid_for(uint64_t n, unsigned block = 256, unsigned cap_b
     if (b > cap_blocks) b = cap_blocks;
     return (unsigned)b;
 }
+
+// ---- kernel launch ---------------------------------------------------------------------------
+// Every kernel of the library is launched here, and every launch is checked: NVB_LAUNCH( kernel, grid, block, stream, args... )
+// enqueues the kernel (none takes dynamic LDS) and returns NVBIO_OK, or NVBIO_ERR_HIP and the message "<kernel> launch failed:
+// <the runtime's reason>" when the runtime rejects the launch -- so a bad launch is reported by its own site, under its own name.
+// A call site wraps it in NVB_CHECK, or keeps the status where it carries one through a loop.  A kernel whose template arguments
+// hold a comma goes in parentheses.  The arguments convert to the kernel's parameter types as in a plain call.
+template <typename... P, typename... A>
+inline nvbio_status launch_kernel(const char* what, void (*kernel)(P...), const dim3 grid, const dim3 block, hipStream_t s, A&&... args)
+{
+    hipLaunchKernelGGL( kernel, grid, block, 0, s, args... );
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error( "%s launch failed: %s", what, hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+    return NVBIO_OK;
+}
+#define NVB_LAUNCH(kernel, ...) nvbio_amd::launch_kernel( #kernel, kernel, __VA_ARGS__ )
 
 // ---- device-side symbol access --------------------------------------------------------------
 // Big-endian packed streams (PackedStream<..,BITS,true>): symbol i of a 2-bit stream sits at bits

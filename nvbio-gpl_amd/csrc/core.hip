@@ -18,6 +18,8 @@ void set_error(const char* fmt, ...)
 }
 const char* get_error() { return g_error; }
 
+nvbio_status bad_symbol_bits() { set_error( "invalid argument: symbol_bits must be 2, 4 or 8" ); return NVBIO_ERR_INVALID; }
+
 // ---- scratch blocks cached per (device, stream): see common.h ----
 namespace {
 struct CachedBlock { void* p; size_t cap; bool busy; int device; hipStream_t stream; };

@@ -253,7 +253,7 @@ static nvbio_status scan_max_inplace(uint32_t* buf, uint64_t n, BuildBuffers& bu
     for (uint64_t b = 0; b < n; b += CHUNK)
     {
         const size_t len = (size_t)((n - b) < CHUNK ? (n - b) : CHUNK);
-        if (b) hipLaunchKernelGGL( patch_first_kernel, dim3(1), dim3(1), 0, s, buf + b, buf + b - 1 );
+        if (b) NVB_CHECK( NVB_LAUNCH( patch_first_kernel, dim3(1), dim3(1), s, buf + b, buf + b - 1 ) );
         NVB_HIP( rocprim::inclusive_scan( temp, temp_bytes, buf + b, buf + b, len, MaxU32(), s ) );
     }
     bufs.release( temp );
@@ -320,7 +320,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
     {
         NVB_ALLOC( d_hist, uint32_t, 256 );
         NVB_HIP( hipMemsetAsync( d_hist, 0, 256 * sizeof(uint32_t), s ) );
-        hipLaunchKernelGGL( bucket_histogram_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, t, bshift, d_hist );
+        NVB_CHECK( NVB_LAUNCH( bucket_histogram_kernel, dim3( grid_for( n ) ), dim3(256), s, t, bshift, d_hist ) );
         NVB_HIP( hipMemcpyAsync( hist.data(), d_hist, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, s ) );
         NVB_HIP( hipStreamSynchronize( s ) );
         bufs.release( d_hist );
@@ -375,8 +375,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
 
     // ---- 2. finish tied suffixes by prefix doubling on the unresolved set --------------------
     NVB_ALLOC( seg, uint32_t, n );           // head slot of the segment each slot belongs to
-    hipLaunchKernelGGL( head_from_keys_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, (const uint64_t*)keys, (uint64_t)n, seg );
-    NVB_HIP( hipGetLastError() );
+    NVB_CHECK( NVB_LAUNCH( head_from_keys_kernel, dim3( grid_for( n ) ), dim3(256), s, (const uint64_t*)keys, (uint64_t)n, seg ) );
     bufs.release( keys );
     NVB_CHECK( scan_max_inplace( seg, n, bufs, s ) );
 
@@ -389,7 +388,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
     if (m > 0)
     {
         NVB_ALLOC( rank, uint32_t, n );
-        hipLaunchKernelGGL( scatter_rank_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, (const uint32_t*)sa, (const uint32_t*)seg, (uint64_t)n, rank );
+        NVB_CHECK( NVB_LAUNCH( scatter_rank_kernel, dim3( grid_for( n ) ), dim3(256), s, (const uint32_t*)sa, (const uint32_t*)seg, (uint64_t)n, rank ) );
         NVB_ALLOC( key2,   uint64_t, m );
         NVB_ALLOC( key2s,  uint64_t, m );
         NVB_ALLOC( val,    uint32_t, m );
@@ -406,21 +405,20 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
                 return NVBIO_ERR_UNSUPPORTED;
             }
             const uint32_t mm = (uint32_t)m;
-            hipLaunchKernelGGL( doubling_keys_kernel, dim3( grid_for( mm ) ), dim3(256), 0, s,
-                                (const uint32_t*)U, mm, (const uint32_t*)sa, (const uint32_t*)seg, (const uint32_t*)rank, n, h, key2, val );
+            NVB_CHECK( NVB_LAUNCH( doubling_keys_kernel, dim3( grid_for( mm ) ), dim3(256), s,
+                                   (const uint32_t*)U, mm, (const uint32_t*)sa, (const uint32_t*)seg, (const uint32_t*)rank, n, h, key2, val ) );
             NVB_CHECK( sort_pairs( key2, key2s, val, vals, mm, 0, 64, bufs, s ) );
-            hipLaunchKernelGGL( doubling_place_kernel, dim3( grid_for( mm ) ), dim3(256), 0, s,
-                                (const uint32_t*)U, mm, (const uint64_t*)key2s, (const uint32_t*)vals, sa, newseg );
+            NVB_CHECK( NVB_LAUNCH( doubling_place_kernel, dim3( grid_for( mm ) ), dim3(256), s,
+                                   (const uint32_t*)U, mm, (const uint64_t*)key2s, (const uint32_t*)vals, sa, newseg ) );
             NVB_CHECK( scan_max_inplace( newseg, mm, bufs, s ) );
-            hipLaunchKernelGGL( doubling_update_kernel, dim3( grid_for( mm ) ), dim3(256), 0, s,
-                                (const uint32_t*)U, mm, (const uint32_t*)newseg, (const uint32_t*)vals, seg, rank );
-            NVB_HIP( hipGetLastError() );
+            NVB_CHECK( NVB_LAUNCH( doubling_update_kernel, dim3( grid_for( mm ) ), dim3(256), s,
+                                   (const uint32_t*)U, mm, (const uint32_t*)newseg, (const uint32_t*)vals, seg, rank ) );
             uint64_t m2 = 0;
             StillUnresolvedU pred; pred.U = U; pred.newseg = newseg; pred.m = mm;
             NVB_CHECK( select_indices( mm, pred, sel, &m2, bufs, s ) );
             if (m2)
             {
-                hipLaunchKernelGGL( gather_u_kernel, dim3( grid_for( m2 ) ), dim3(256), 0, s, (const uint32_t*)U, (const uint32_t*)sel, (uint32_t)m2, U2 );
+                NVB_CHECK( NVB_LAUNCH( gather_u_kernel, dim3( grid_for( m2 ) ), dim3(256), s, (const uint32_t*)U, (const uint32_t*)sel, (uint32_t)m2, U2 ) );
                 NVB_HIP( hipMemcpyAsync( U, U2, m2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s ) );
             }
             m = m2;
@@ -439,12 +437,12 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
 
     NVB_ALLOC( d_primary, uint32_t, 1 );
     NVB_HIP( hipMemsetAsync( d_primary, 0, sizeof(uint32_t), s ) );
-    hipLaunchKernelGGL( find_primary_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, (const uint32_t*)sa, (uint64_t)n, d_primary );
+    NVB_CHECK( NVB_LAUNCH( find_primary_kernel, dim3( grid_for( n ) ), dim3(256), s, (const uint32_t*)sa, (uint64_t)n, d_primary ) );
 
     NVB_ALLOC( bwt_occ, uint32_t, (size_t)words * 2u );
     NVB_ALLOC( ssa,     uint32_t, n_ssa );
-    hipLaunchKernelGGL( bwt_words_kernel, dim3( grid_for( words ) ), dim3(256), 0, s, t, (const uint32_t*)sa, (const uint32_t*)d_primary, words, bwt_occ, (uint4*)nullptr );
-    hipLaunchKernelGGL( ssa_kernel, dim3( grid_for( n_ssa ) ), dim3(256), 0, s, (const uint32_t*)sa, sa_int, n_ssa, ssa );
+    NVB_CHECK( NVB_LAUNCH( bwt_words_kernel, dim3( grid_for( words ) ), dim3(256), s, t, (const uint32_t*)sa, (const uint32_t*)d_primary, words, bwt_occ, (uint4*)nullptr ) );
+    NVB_CHECK( NVB_LAUNCH( ssa_kernel, dim3( grid_for( n_ssa ) ), dim3(256), s, (const uint32_t*)sa, sa_int, n_ssa, ssa ) );
     uint32_t* isa = nullptr; uint32_t* text_copy = nullptr;
     if (sa_int == 1)                                             // the full SA + the text: nvbio_fm_match_direct can finish on the text
     {
@@ -456,16 +454,15 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
     if (verify)
     {
         NVB_ALLOC( isa_, uint32_t, (size_t)n + 1u );
-        hipLaunchKernelGGL( isa_kernel, dim3( grid_for( (uint64_t)n + 1u ) ), dim3(256), 0, s, (const uint32_t*)sa, (uint64_t)n, isa_ );
+        NVB_CHECK( NVB_LAUNCH( isa_kernel, dim3( grid_for( (uint64_t)n + 1u ) ), dim3(256), s, (const uint32_t*)sa, (uint64_t)n, isa_ ) );
         isa = isa_;
     }
-    NVB_HIP( hipGetLastError() );
     NVB_HIP( hipStreamSynchronize( s ) );
     bufs.release( sa );
 
     NVB_ALLOC( cnt, uint4, (size_t)n_blocks + 1u );
     NVB_ALLOC( occ, uint4, (size_t)n_blocks + 1u );
-    hipLaunchKernelGGL( block_counts_kernel, dim3( grid_for( n_blocks ) ), dim3(256), 0, s, (const uint32_t*)bwt_occ, n, n_blocks, cnt );
+    NVB_CHECK( NVB_LAUNCH( block_counts_kernel, dim3( grid_for( n_blocks ) ), dim3(256), s, (const uint32_t*)bwt_occ, n, n_blocks, cnt ) );
     NVB_HIP( hipMemsetAsync( cnt + n_blocks, 0, sizeof(uint4), s ) );                  // extra entry: its scan value is the total
     {
         size_t temp_bytes = 0;
@@ -475,7 +472,7 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
         NVB_HIP( hipStreamSynchronize( s ) );
         bufs.release( temp );
     }
-    hipLaunchKernelGGL( write_occ_kernel, dim3( grid_for( n_blocks ) ), dim3(256), 0, s, (const uint4*)occ, n_blocks, bwt_occ );
+    NVB_CHECK( NVB_LAUNCH( write_occ_kernel, dim3( grid_for( n_blocks ) ), dim3(256), s, (const uint4*)occ, n_blocks, bwt_occ ) );
     uint4    totals;
     uint32_t primary = 0;
     NVB_HIP( hipMemcpyAsync( &totals, occ + n_blocks, sizeof(uint4), hipMemcpyDeviceToHost, s ) );
@@ -539,12 +536,12 @@ static nvbio_status load_impl(const char* bwt_path, const char* sa_path, const i
     NVB_ALLOC( d_bwt, uint32_t, words );
     NVB_ALLOC( bwt_occ, uint32_t, (size_t)words * 2u );
     NVB_HIP( hipMemcpyAsync( d_bwt, h_bwt.data(), (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, s ) );
-    hipLaunchKernelGGL( interleave_bwt_kernel, dim3( grid_for( words ) ), dim3(256), 0, s, (const uint32_t*)d_bwt, n_words, words, bwt_occ );
+    NVB_CHECK( NVB_LAUNCH( interleave_bwt_kernel, dim3( grid_for( words ) ), dim3(256), s, (const uint32_t*)d_bwt, n_words, words, bwt_occ ) );
 
     // ---- occurrence table (K = 64) on the GPU: per-record counts, exclusive scan, interleave (fmindex_impl.cu:254-331) ----
     NVB_ALLOC( cnt, uint4, (size_t)n_blocks + 1u );
     NVB_ALLOC( occ, uint4, (size_t)n_blocks + 1u );
-    hipLaunchKernelGGL( block_counts_kernel, dim3( grid_for( n_blocks ) ), dim3(256), 0, s, (const uint32_t*)bwt_occ, n, n_blocks, cnt );
+    NVB_CHECK( NVB_LAUNCH( block_counts_kernel, dim3( grid_for( n_blocks ) ), dim3(256), s, (const uint32_t*)bwt_occ, n, n_blocks, cnt ) );
     NVB_HIP( hipMemsetAsync( cnt + n_blocks, 0, sizeof(uint4), s ) );
     {
         size_t temp_bytes = 0;
@@ -554,7 +551,7 @@ static nvbio_status load_impl(const char* bwt_path, const char* sa_path, const i
         NVB_HIP( hipStreamSynchronize( s ) );
         bufs.release( temp );
     }
-    hipLaunchKernelGGL( write_occ_kernel, dim3( grid_for( n_blocks ) ), dim3(256), 0, s, (const uint4*)occ, n_blocks, bwt_occ );
+    NVB_CHECK( NVB_LAUNCH( write_occ_kernel, dim3( grid_for( n_blocks ) ), dim3(256), s, (const uint4*)occ, n_blocks, bwt_occ ) );
     uint4 totals;
     NVB_HIP( hipMemcpyAsync( &totals, occ + n_blocks, sizeof(uint4), hipMemcpyDeviceToHost, s ) );
     NVB_HIP( hipStreamSynchronize( s ) );
@@ -596,7 +593,7 @@ static nvbio_status save_impl(const nvbio_fm_index_view& v, const char* bwt_path
     BuildBuffers bufs;
     const uint32_t n = v.length, n_words = (n + 15u) / 16u;
     NVB_ALLOC( d_bwt, uint32_t, n_words );
-    hipLaunchKernelGGL( deinterleave_bwt_kernel, dim3( grid_for( n_words ) ), dim3(256), 0, s, v.bwt_occ_dev, n_words, d_bwt );
+    NVB_CHECK( NVB_LAUNCH( deinterleave_bwt_kernel, dim3( grid_for( n_words ) ), dim3(256), s, v.bwt_occ_dev, n_words, d_bwt ) );
     std::vector<uint32_t> h_bwt( n_words );
     NVB_HIP( hipMemcpyAsync( h_bwt.data(), d_bwt, (size_t)n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, s ) );
     NVB_HIP( hipStreamSynchronize( s ) );

@@ -192,9 +192,9 @@ static nvbio_status build_canonical_table(FMIndexImpl* idx, const uint32_t k, co
     if (hipMalloc( (void**)&cnt, 4ull * n_tiles * sizeof(uint32_t) ) != hipSuccess) { (void)hipGetLastError(); (void)hipFree( tab ); set_error( "canonical table: out of device memory" ); return NVBIO_ERR_NOMEM; }
     uint32_t *cs = cnt, *cl = cnt + n_tiles, *os = cnt + 2ull * n_tiles, *ol = cnt + 3ull * n_tiles;
     const DevIndex f = idx->dev();
-    hipLaunchKernelGGL( fm_ctab_count_kernel, grid, block, 0, stream, f, k, wide ? 1u : 0u, tab, entries, n_tiles, cs, cl );
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( nullptr, temp_bytes, cs, os, (int)n_tiles, stream );
+    nvbio_status st = NVB_LAUNCH( fm_ctab_count_kernel, grid, block, stream, f, k, wide ? 1u : 0u, tab, entries, n_tiles, cs, cl );
+    if (st != NVBIO_OK) { (void)hipFree( cnt ); (void)hipFree( tab ); return st; }
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum( nullptr, temp_bytes, cs, os, (int)n_tiles, stream );
     if (e == hipSuccess) e = hipMalloc( &temp, temp_bytes ? temp_bytes : 16 );
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( temp, temp_bytes, cs, os, (int)n_tiles, stream );
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( temp, temp_bytes, cl, ol, (int)n_tiles, stream );
@@ -204,7 +204,6 @@ static nvbio_status build_canonical_table(FMIndexImpl* idx, const uint32_t k, co
     if (e == hipSuccess) e = hipMemcpyAsync( &last[2], cl + n_tiles - 1u, 4, hipMemcpyDeviceToHost, stream );
     if (e == hipSuccess) e = hipMemcpyAsync( &last[3], ol + n_tiles - 1u, 4, hipMemcpyDeviceToHost, stream );
     if (e == hipSuccess) e = hipStreamSynchronize( stream );
-    nvbio_status st = NVBIO_OK;
     if (e != hipSuccess) { (void)hipGetLastError(); set_error( "canonical table: counting pass failed: %s", hipGetErrorString( e ) ); st = NVBIO_ERR_HIP; }
     const uint32_t tot_small = last[0] + last[1], tot_large = last[2] + last[3];
     const uint64_t units = 2ull * tot_large + tot_small;                      // groups in units of 4 slots (32 bytes)
@@ -212,8 +211,8 @@ static nvbio_status build_canonical_table(FMIndexImpl* idx, const uint32_t k, co
     if (st == NVBIO_OK && hipMalloc( (void**)&side, (units ? units : 1u) * 32ull ) != hipSuccess) { (void)hipGetLastError(); set_error( "canonical table: out of device memory" ); st = NVBIO_ERR_NOMEM; }
     if (st == NVBIO_OK)
     {
-        hipLaunchKernelGGL( fm_ctab_fill_kernel, grid, block, 0, stream, f, k, wide ? 1u : 0u, tab, entries, n_tiles, (const uint32_t*)os, (const uint32_t*)ol, tot_large, side );
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize( stream ) != hipSuccess) { set_error( "canonical table: fill pass failed" ); st = NVBIO_ERR_HIP; }
+        st = NVB_LAUNCH( fm_ctab_fill_kernel, grid, block, stream, f, k, wide ? 1u : 0u, tab, entries, n_tiles, (const uint32_t*)os, (const uint32_t*)ol, tot_large, side );
+        if (st == NVBIO_OK && hipStreamSynchronize( stream ) != hipSuccess) { set_error( "canonical table: fill pass failed" ); st = NVBIO_ERR_HIP; }
     }
     (void)hipFree( cnt );
     if (temp) (void)hipFree( temp );

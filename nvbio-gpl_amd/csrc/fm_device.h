@@ -13,6 +13,7 @@
 // to both ends, sharing the 32-byte record when both ends fall in one block.
 #pragma once
 #include "common.h"
+#include "range_expand.h"
 
 namespace nvbio_amd {
 
@@ -128,17 +129,6 @@ __device__ __forceinline__ void search_step(const DevIndex& f, uint32_t& x, uint
 // the device view of a handle and the device it lives on (fm_index.hip)
 nvbio_status fm_handle_dev(nvbio_fm_index_t index, DevIndex* d, int* device);
 
-// first i in [lo, hi) with a[i] > v (hi if none): the slot of a global hit index in an inclusive scan of range sizes
-__device__ __forceinline__ uint32_t upper_bound_u64(const uint64_t* __restrict__ a, uint32_t lo, uint32_t hi, const uint64_t v)
-{
-    while (lo < hi)
-    {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-
 // one LF step of locate(): j -> L2[c] + rank(fmi,j,c) with c = bwt[j] (or 0 at the primary row)
 __device__ __forceinline__ uint32_t lf_step(const DevIndex& f, const uint32_t j)
 {
@@ -148,6 +138,45 @@ __device__ __forceinline__ uint32_t lf_step(const DevIndex& f, const uint32_t j)
     const uint4 b = f.rec[2u * blk], o = f.rec[2u * blk + 1u];
     const uint32_t c = bwt_symbol( b, kt & 63u );
     return L2_of( f, c ) + pick4( o.x, o.y, o.z, o.w, c ) + count_in_block( b, kt & 63u, c );
+}
+
+// The range expansion (range_expand.h) of the filters whose ranges hold SA rows: the outputs [begin, end) located by LF walks.
+// start( h, i, base, row ) sets the SA row of output h -- element h - base of range i -- and keeps what the caller needs to write it;
+// emit( h, pos ) writes it once the walk has reached a sampled row.  An output that needs no walk is written by start itself, which
+// then returns false.  Lanes are refilled as in fm_locate_kernel: a lane that reaches a sampled row takes the next of its outputs in
+// the tile while its neighbours keep walking, so every iteration of the wave-uniform loop issues (nearly) 64 gathers.
+template <typename Start, typename Emit>
+__device__ __forceinline__ void locate_ranges(const DevIndex& f, const uint64_t* __restrict__ slots, const uint32_t n, const uint64_t begin,
+                                              const uint64_t end, Start start, Emit emit)
+{
+    const uint32_t mask = (1u << f.sa_log) - 1u;
+    for_each_tile( slots, n, begin, end, [&](const uint64_t t_first, const uint64_t t_end, const TileSlots ts)
+    {
+        uint64_t h = t_first + threadIdx.x;
+        uint32_t j = 0, t = 0;
+        auto refill = [&]() -> bool {                            // the lane's next output that needs a walk, from h on
+            for (; h < t_end; h += 256u)
+            {
+                uint64_t base;
+                const uint32_t i = ts.find( h, base );
+                if (start( h, i, base, j )) { t = 0; return true; }
+            }
+            return false;
+        };
+        bool have = refill();
+        while (__any( have ))
+        {
+            if (have)
+            {
+                if ((j & mask) == 0)                             // SSA_index_multiple_context<K>::has (ssa_inl.h:491-495)
+                {
+                    emit( h, f.ssa[j >> f.sa_log] + t );
+                    h += 256u; have = refill();
+                }
+                else { j = lf_step( f, j ); ++t; }
+            }
+        }
+    } );
 }
 
 } // namespace nvbio_amd

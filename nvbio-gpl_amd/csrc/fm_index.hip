@@ -317,7 +317,7 @@ __device__ __forceinline__ void match_one(const DevIndex& f, const StringSetDev&
 template <int BITS, bool COUNT, bool TABLE, bool DIRECT = false>
 __global__ void __launch_bounds__(256)
 fm_match_kernel(const DevIndex f, const StringSetDev q, const uint32_t flags, uint2* __restrict__ ranges, uint32_t* __restrict__ blocks,
-                uint8_t* __restrict__ direct = nullptr)
+                uint8_t* __restrict__ direct)
 {
     const bool tab    = TABLE && (f.ktab != nullptr) && !(flags & NVBIO_FM_NO_KMER_TABLE) && !COUNT;
     const bool verify = (f.isa != nullptr) && (f.sa_log == 0) && !(flags & NVBIO_FM_NO_VERIFY) && !COUNT;
@@ -410,7 +410,7 @@ template <int BITS, bool COUNT = false>
 __global__ void __launch_bounds__(256)
 fm_seed_tiles_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, const uint32_t flags, const uint32_t read_len, const uint32_t strand,
                      uint64_t* __restrict__ tile_keys, uint32_t* __restrict__ tile_counts, uint2* __restrict__ res_ranges,
-                     uint32_t* __restrict__ res_ids, unsigned int* __restrict__ counts, unsigned long long* __restrict__ sectors_out = nullptr)
+                     uint32_t* __restrict__ res_ids, unsigned int* __restrict__ counts, unsigned long long* __restrict__ sectors_out)
 {
     const bool fwd  = (flags & NVBIO_FM_SCAN_FORWARD) != 0;
     const bool comp = (flags & NVBIO_FM_COMPLEMENT) != 0;
@@ -882,78 +882,42 @@ fm_lookup_kernel(const DevIndex f, const uint2* __restrict__ jt, const uint32_t 
 // ---------------------------------------------------------------------------------------------
 // filter
 // ---------------------------------------------------------------------------------------------
-struct RangeSize
-{
-    __host__ __device__ __forceinline__ uint64_t operator()(const uint2 r) const { return (uint64_t)(uint32_t)(1u + r.y - r.x); }
-};
-
-// hits[h-begin] = (locate(range.x + local), query) for the global hit index h (filter_inl.h:66-118,359-392).
-// A workgroup owns a tile of consecutive hit indices; their queries form a contiguous slice of
-// `slots`, found once per tile (two binary searches by two lanes), so that each hit's own
-// upper_bound runs over a few cached entries instead of log2(n_queries) HBM round trips.
-constexpr uint32_t FILTER_TILE = 256u * 8u;
-
 // seed enumeration of a hit's query id -> its diagonal key (hit_to_diagonal, examples/fmmap/fmmap.cu:92-117; see
 // nvbio_hits_to_diagonals): with KEYS the expansion writes the 8-byte key instead of the (position, query) pair
 // qid: optional seed id of every query; read_offsets / intervals: ragged reads (every read's length and seed interval)
 struct DiagSpec { uint32_t spr, interval, seed_len, read_len, strand; const uint32_t* qid; const uint32_t* read_offsets; const uint32_t* intervals; };
 
+// hits[h-begin] = (locate(range.x + local), query) for the global hit index h (filter_inl.h:66-118,359-392), over the shared
+// expansion (locate_ranges, fm_device.h).  A query whose range already holds a text position (direct) needs no walk.
 template <bool KEYS>
 __global__ void __launch_bounds__(256)
 fm_filter_locate_kernel(const DevIndex f, const uint2* __restrict__ ranges, const uint64_t* __restrict__ slots, const uint32_t n_queries,
                         const uint64_t begin, const uint64_t end, uint2* __restrict__ hits, const uint8_t* __restrict__ direct,
                         const DiagSpec ds, uint64_t* __restrict__ keys)
 {
-    __shared__ uint32_t s_q[2];
-    const uint32_t mask    = (1u << f.sa_log) - 1u;
-    const uint64_t n_tiles = (end - begin + FILTER_TILE - 1u) / FILTER_TILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
-    {
-        const uint64_t t_first = begin + tile * FILTER_TILE;
-        const uint64_t t_end   = (t_first + FILTER_TILE < end) ? t_first + FILTER_TILE : end;
-        __syncthreads();
-        if (threadIdx.x < 2)
-            s_q[threadIdx.x] = upper_bound_u64( slots, 0u, n_queries, threadIdx.x ? t_end - 1u : t_first );
-        __syncthreads();
-        const uint32_t q_lo = s_q[0], q_hi = s_q[1] + 1u < n_queries ? s_q[1] + 1u : n_queries;
-
-        uint64_t h    = t_first + threadIdx.x;
-        bool     have = h < t_end;
-        uint32_t slot = 0, j = 0, t = 0;
-        bool     is_pos = false;                                 // the range of this query already holds a text position
-        auto start = [&]() {
-            slot = upper_bound_u64( slots, q_lo, q_hi, h );
-            const uint64_t base = slot ? slots[slot - 1u] : 0ull;
-            j = ranges[slot].x + (uint32_t)(h - base); t = 0;
-            is_pos = direct && direct[slot];
-        };
-        if (have) start();
-        while (__any( have ))
+    auto write = [&](const uint64_t h, const uint32_t slot, const uint32_t pos) {
+        if (KEYS)
         {
-            if (have)
-            {
-                if (is_pos || (j & mask) == 0)
-                {
-                    const uint32_t pos = is_pos ? j : f.ssa[j >> f.sa_log] + t;
-                    if (KEYS)
-                    {
-                        // bit 31 of a query id flips the strand: the two residual lists of the two-strand seed pass go through one call
-                        const uint32_t qv  = ds.qid ? ds.qid[slot] : slot;
-                        const uint32_t sid = ds.qid ? (qv & 0x7FFFFFFFu) : qv;
-                        const uint32_t str = (ds.strand ^ (ds.qid ? qv >> 31 : 0u)) & 1u;
-                        const uint32_t rid = sid / ds.spr;
-                        uint32_t       p   = (sid - rid * ds.spr) * (ds.intervals ? ds.intervals[rid] : ds.interval);
-                        if (str) p = (ds.read_offsets ? ds.read_offsets[rid + 1] - ds.read_offsets[rid] : ds.read_len) - p - ds.seed_len;
-                        keys[h - begin] = ((uint64_t)rid << 34) | ((uint64_t)str << 33) | ((uint64_t)pos + 1024u - p);
-                    }
-                    else hits[h - begin] = make_uint2( pos, slot );
-                    h += 256u; have = h < t_end;
-                    if (have) start();
-                }
-                else { j = lf_step( f, j ); ++t; }
-            }
+            // bit 31 of a query id flips the strand: the two residual lists of the two-strand seed pass go through one call
+            const uint32_t qv  = ds.qid ? ds.qid[slot] : slot;
+            const uint32_t sid = ds.qid ? (qv & 0x7FFFFFFFu) : qv;
+            const uint32_t str = (ds.strand ^ (ds.qid ? qv >> 31 : 0u)) & 1u;
+            const uint32_t rid = sid / ds.spr;
+            uint32_t       p   = (sid - rid * ds.spr) * (ds.intervals ? ds.intervals[rid] : ds.interval);
+            if (str) p = (ds.read_offsets ? ds.read_offsets[rid + 1] - ds.read_offsets[rid] : ds.read_len) - p - ds.seed_len;
+            keys[h - begin] = ((uint64_t)rid << 34) | ((uint64_t)str << 33) | ((uint64_t)pos + 1024u - p);
         }
-    }
+        else hits[h - begin] = make_uint2( pos, slot );
+    };
+    uint32_t slot = 0;                                           // the query of the hit this lane is walking to
+    locate_ranges( f, slots, n_queries, begin, end,
+        [&](const uint64_t h, const uint32_t i, const uint64_t base, uint32_t& row) {
+            row = ranges[i].x + (uint32_t)(h - base);
+            if (direct && direct[i]) { write( h, i, row ); return false; }
+            slot = i;
+            return true;
+        },
+        [&](const uint64_t h, const uint32_t pos) { write( h, slot, pos ); } );
 }
 
 
@@ -1159,9 +1123,7 @@ static nvbio_status build_direct_table(FMIndexImpl* idx, uint2* tab, const uint6
     idx->side = nullptr; idx->dmark = 0xFFFFFFFFu; idx->dctx = 0;
     if ((uint64_t)length + 2u > DTAB_MARK || (idx->table_flags & NVBIO_FM_TABLE_NO_CONTEXT))
     {
-        hipLaunchKernelGGL( fm_dtab_kernel, dim3( grid_for( entries ) ), dim3(256), 0, stream, tab, idx->view.ssa_dev, length, entries );
-        NVB_HIP( hipGetLastError() );
-        return NVBIO_OK;
+        return NVB_LAUNCH( fm_dtab_kernel, dim3( grid_for( entries ) ), dim3(256), stream, tab, idx->view.ssa_dev, length, entries );
     }
     const uint32_t n_tiles = (uint32_t)((entries + DT_TILE - 1u) / DT_TILE);
     const dim3 grid( n_tiles < 256u * 64u ? n_tiles : 256u * 64u ), block( 256 );
@@ -1176,7 +1138,7 @@ static nvbio_status build_direct_table(FMIndexImpl* idx, uint2* tab, const uint6
         cnt = bufs.alloc<uint32_t>( 4ull * n_tiles );
         if (!cnt) { set_error( "direct table: out of device memory" ); return NVBIO_ERR_NOMEM; }
         uint32_t *cs = cnt, *cl = cnt + n_tiles, *os = cnt + 2ull * n_tiles, *ol = cnt + 3ull * n_tiles;
-        hipLaunchKernelGGL( fm_dtab_count_kernel, grid, block, 0, stream, (const uint2*)tab, entries, n_tiles, cs, cl );
+        NVB_CHECK( NVB_LAUNCH( fm_dtab_count_kernel, grid, block, stream, (const uint2*)tab, entries, n_tiles, cs, cl ) );
         hipError_t e = hipcub::DeviceScan::ExclusiveSum( nullptr, temp_bytes, cs, os, (int)n_tiles, stream );
         void* temp = nullptr;
         if (e == hipSuccess && !(temp = bufs.alloc<uint8_t>( temp_bytes ))) e = hipErrorOutOfMemory;
@@ -1196,9 +1158,9 @@ static nvbio_status build_direct_table(FMIndexImpl* idx, uint2* tab, const uint6
     }
     if (st == NVBIO_OK)
     {
-        hipLaunchKernelGGL( fm_dtab_fill_kernel, grid, block, 0, stream, tab, entries, n_tiles, cnt ? cnt + 2ull * n_tiles : nullptr,
-                            cnt ? cnt + 3ull * n_tiles : nullptr, tot_large, idx->view.ssa_dev, (const uint32_t*)idx->text, length, side );
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize( stream ) != hipSuccess) { set_error( "direct table: fill pass failed" ); st = NVBIO_ERR_HIP; }
+        NVB_CHECK( NVB_LAUNCH( fm_dtab_fill_kernel, grid, block, stream, tab, entries, n_tiles, cnt ? cnt + 2ull * n_tiles : nullptr,
+                               cnt ? cnt + 3ull * n_tiles : nullptr, tot_large, idx->view.ssa_dev, (const uint32_t*)idx->text, length, side ) );
+        if (hipStreamSynchronize( stream ) != hipSuccess) { set_error( "direct table: fill pass failed" ); st = NVBIO_ERR_HIP; }
     }
     if (st != NVBIO_OK) return st;
     bufs.forget( side );
@@ -1227,14 +1189,14 @@ static nvbio_status build_canonical_tables(FMIndexImpl* idx, uint32_t k, hipStre
     uint2* cur = (kk % 2 == 0) ? a : b;
     uint2* oth = (kk % 2 == 0) ? b : a;
     DevIndex f = idx->dev(); f.ktab = nullptr; f.kmer = 0; f.dtab = nullptr; f.dkmer = 0;
-    hipLaunchKernelGGL( fm_ktab_root_kernel, dim3(1), dim3(1), 0, stream, cur, idx->view.length );
+    NVB_CHECK( NVB_LAUNCH( fm_ktab_root_kernel, dim3(1), dim3(1), stream, cur, idx->view.length ) );
     for (uint32_t j = 1; j <= kk; ++j)
     {
         const uint64_t n_next = 1ull << (2 * j);
-        hipLaunchKernelGGL( fm_ktab_level_kernel, dim3( grid_for( n_next ) ), dim3(256), 0, stream, f, (const uint2*)cur, oth, n_next );
+        NVB_CHECK( NVB_LAUNCH( fm_ktab_level_kernel, dim3( grid_for( n_next ) ), dim3(256), stream, f, (const uint2*)cur, oth, n_next ) );
         uint2* t = cur; cur = oth; oth = t;
     }
-    const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize( stream ) == hipSuccess;
+    const bool ok = hipStreamSynchronize( stream ) == hipSuccess;
     bufs.release( b );                                           // level kk - 1
     if (!ok) { set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
     idx->ktab = a; idx->kmer = kk;
@@ -1269,15 +1231,14 @@ static nvbio_status build_kmer_table(FMIndexImpl* idx, uint32_t k, hipStream_t s
     uint2* cur = (k % 2 == 0) ? a : b;
     uint2* oth = (k % 2 == 0) ? b : a;
     DevIndex f = idx->dev(); f.ktab = nullptr; f.kmer = 0; f.dtab = nullptr; f.dkmer = 0;
-    hipLaunchKernelGGL( fm_ktab_root_kernel, dim3(1), dim3(1), 0, stream, cur, idx->view.length );
+    NVB_CHECK( NVB_LAUNCH( fm_ktab_root_kernel, dim3(1), dim3(1), stream, cur, idx->view.length ) );
     for (uint32_t j = 1; j <= k; ++j)
     {
         const uint64_t n_next = 1ull << (2 * j);
-        hipLaunchKernelGGL( fm_ktab_level_kernel, dim3( grid_for( n_next ) ), dim3(256), 0, stream, f, (const uint2*)cur, oth, n_next );
+        NVB_CHECK( NVB_LAUNCH( fm_ktab_level_kernel, dim3( grid_for( n_next ) ), dim3(256), stream, f, (const uint2*)cur, oth, n_next ) );
         uint2* t = cur; cur = oth; oth = t;
     }
     // cur == a (level k), oth == b (level k-1) by construction
-    if (hipGetLastError() != hipSuccess) { set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
     if (direct) NVB_CHECK( build_direct_table( idx, a, entries, stream ) );
     if (hipStreamSynchronize( stream ) != hipSuccess) { set_error( "k-mer table build failed" ); return NVBIO_ERR_HIP; }
     bufs.forget( a );
@@ -1411,15 +1372,12 @@ nvbio_status nvbio_fm_match(nvbio_fm_index_t index, const nvbio_string_set* quer
     const dim3 grid( grid_for( q.n ) ), block( 256 );
     hipStream_t s = (hipStream_t)stream;
     const bool use_table = (f.ktab != nullptr) && !(flags & NVBIO_FM_NO_KMER_TABLE);
-    (void)with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
+    return with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
     {
-        if (blocks_dev)     hipLaunchKernelGGL( (fm_match_kernel<BITS,true,false>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev );
-        else if (use_table) hipLaunchKernelGGL( (fm_match_kernel<BITS,false,true>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev );
-        else                hipLaunchKernelGGL( (fm_match_kernel<BITS,false,false>), grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, blocks_dev );
-        return true;
-    }, [] { return false; } );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+        if (blocks_dev) return NVB_LAUNCH( (fm_match_kernel<BITS,true,false>),  grid, block, s, f, q, flags, (uint2*)ranges_dev, blocks_dev, nullptr );
+        if (use_table)  return NVB_LAUNCH( (fm_match_kernel<BITS,false,true>),  grid, block, s, f, q, flags, (uint2*)ranges_dev, blocks_dev, nullptr );
+        return                 NVB_LAUNCH( (fm_match_kernel<BITS,false,false>), grid, block, s, f, q, flags, (uint2*)ranges_dev, blocks_dev, nullptr );
+    }, bad_symbol_bits );                                        // (make_set checked the width)
 }
 
 nvbio_status nvbio_fm_rank(nvbio_fm_index_t index, const uint32_t* rows_dev, const uint8_t* syms_dev, uint32_t n, uint32_t* out_dev, void* stream)
@@ -1429,9 +1387,7 @@ nvbio_status nvbio_fm_rank(nvbio_fm_index_t index, const uint32_t* rows_dev, con
     NVB_REQUIRE( rows_dev && syms_dev && out_dev, "NULL device pointer" );
     FMIndexImpl* idx = (FMIndexImpl*)index;
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( fm_rank_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, idx->dev(), rows_dev, syms_dev, n, out_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_rank_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, idx->dev(), rows_dev, syms_dev, n, out_dev );
 }
 
 nvbio_status nvbio_fm_rank4(nvbio_fm_index_t index, const uint32_t* rows_dev, uint32_t n, uint32_t* out_dev, void* stream)
@@ -1442,9 +1398,7 @@ nvbio_status nvbio_fm_rank4(nvbio_fm_index_t index, const uint32_t* rows_dev, ui
     NVB_REQUIRE( ((uintptr_t)out_dev & 15u) == 0, "out_dev must be 16-byte aligned" );
     FMIndexImpl* idx = (FMIndexImpl*)index;
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( fm_rank4_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, idx->dev(), rows_dev, n, (uint4*)out_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_rank4_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, idx->dev(), rows_dev, n, (uint4*)out_dev );
 }
 
 static nvbio_status locate_common(nvbio_fm_index_t index, const uint32_t* rows_dev, uint32_t n, uint32_t* pos_dev, nvbio_uint2* jt_dev, void* stream)
@@ -1455,9 +1409,8 @@ static nvbio_status locate_common(nvbio_fm_index_t index, const uint32_t* rows_d
     FMIndexImpl* idx = (FMIndexImpl*)index;
     NVB_REQUIRE( jt_dev || idx->view.ssa_dev, "index has no sampled suffix array" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    if (pos_dev) hipLaunchKernelGGL( fm_locate_kernel<0>, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, idx->dev(), rows_dev, n, pos_dev, (uint2*)nullptr );
-    else         hipLaunchKernelGGL( fm_locate_kernel<1>, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, idx->dev(), rows_dev, n, (uint32_t*)nullptr, (uint2*)jt_dev );
-    NVB_HIP( hipGetLastError() );
+    if (pos_dev) NVB_CHECK( NVB_LAUNCH( fm_locate_kernel<0>, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, idx->dev(), rows_dev, n, pos_dev, (uint2*)nullptr ) );
+    else         NVB_CHECK( NVB_LAUNCH( fm_locate_kernel<1>, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, idx->dev(), rows_dev, n, (uint32_t*)nullptr, (uint2*)jt_dev ) );
     return NVBIO_OK;
 }
 
@@ -1468,9 +1421,7 @@ nvbio_status nvbio_fm_basic_inv_psi(nvbio_fm_index_t index, const uint32_t* rows
     NVB_REQUIRE( rows_dev && out_dev, "NULL device pointer" );
     FMIndexImpl* idx = (FMIndexImpl*)index;
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( fm_inv_psi_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, idx->dev(), rows_dev, n, out_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_inv_psi_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, idx->dev(), rows_dev, n, out_dev );
 }
 
 nvbio_status nvbio_fm_locate(nvbio_fm_index_t index, const uint32_t* rows_dev, uint32_t n, uint32_t* pos_dev, void* stream)
@@ -1491,9 +1442,7 @@ nvbio_status nvbio_fm_locate_lookup(nvbio_fm_index_t index, const nvbio_uint2* j
     FMIndexImpl* idx = (FMIndexImpl*)index;
     NVB_REQUIRE( idx->view.ssa_dev, "index has no sampled suffix array" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( fm_lookup_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, idx->dev(), (const uint2*)jt_dev, n, pos_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_lookup_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, idx->dev(), (const uint2*)jt_dev, n, pos_dev );
 }
 
 nvbio_status nvbio_fm_filter_scan(nvbio_fm_index_t index, const nvbio_uint2* ranges_dev, uint32_t n_queries,
@@ -1539,10 +1488,8 @@ nvbio_status nvbio_fm_filter_locate(nvbio_fm_index_t index, const nvbio_uint2* r
     FMIndexImpl* idx = (FMIndexImpl*)index;
     NVB_REQUIRE( idx->view.ssa_dev, "index has no sampled suffix array" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( fm_filter_locate_kernel<false>, dim3( grid_for( (end - begin + FILTER_TILE - 1u) / FILTER_TILE * 256u ) ), dim3(256), 0, (hipStream_t)stream,
-                        idx->dev(), (const uint2*)ranges_dev, slots_dev, n_queries, begin, end, (uint2*)hits_dev, (const uint8_t*)nullptr, DiagSpec{}, (uint64_t*)nullptr );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_filter_locate_kernel<false>, dim3( expand_grid( begin, end ) ), dim3(256), (hipStream_t)stream,
+                       idx->dev(), (const uint2*)ranges_dev, slots_dev, n_queries, begin, end, (uint2*)hits_dev, (const uint8_t*)nullptr, DiagSpec{}, (uint64_t*)nullptr );
 }
 
 nvbio_status nvbio_fm_index_supports_direct(nvbio_fm_index_t index, int* yes)
@@ -1571,14 +1518,11 @@ nvbio_status nvbio_fm_match_direct(nvbio_fm_index_t index, const nvbio_string_se
     const dim3 grid( grid_for( q.n ) ), block( 256 );
     hipStream_t s = (hipStream_t)stream;
     const bool use_table = (f.ktab != nullptr) && !(flags & NVBIO_FM_NO_KMER_TABLE);
-    (void)with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
+    return with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
     {
-        if (use_table) hipLaunchKernelGGL( (fm_match_kernel<BITS,false,true,true>),  grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev );
-        else           hipLaunchKernelGGL( (fm_match_kernel<BITS,false,false,true>), grid, block, 0, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev );
-        return true;
-    }, [] { return false; } );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+        if (use_table) return NVB_LAUNCH( (fm_match_kernel<BITS,false,true,true>),  grid, block, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev );
+        return                NVB_LAUNCH( (fm_match_kernel<BITS,false,false,true>), grid, block, s, f, q, flags, (uint2*)ranges_dev, (uint32_t*)nullptr, direct_dev );
+    }, bad_symbol_bits );                                        // (make_set checked the width)
 }
 
 nvbio_status nvbio_fm_hamming_backtrack(nvbio_fm_index_t index, const nvbio_string_set* queries, uint32_t seed_len, uint32_t mismatches, uint32_t flags,
@@ -1598,15 +1542,13 @@ nvbio_status nvbio_fm_hamming_backtrack(nvbio_fm_index_t index, const nvbio_stri
     NVB_HIP( hipMemsetAsync( overflow, 0, sizeof(uint32_t), s ) );
     const DevIndex f = idx->dev();
     const dim3 grid( grid_for( q.n, 128 ) ), block( 128 );
-    (void)with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
+    NVB_CHECK( with_value( SymbolBits(), queries->symbol_bits, [&](auto BITS)
     {
-        hipLaunchKernelGGL( (fm_hamming_backtrack_kernel<BITS>), grid, block, 0, s, f, q, seed_len, mismatches, (flags & NVBIO_BACKTRACK_REFERENCE_QUIRKS) != 0,
-                            counts_dev, n_ranges_dev, (uint2*)ranges_dev, max_ranges, overflow );
-        return true;
-    }, [] { return false; } );
+        return NVB_LAUNCH( (fm_hamming_backtrack_kernel<BITS>), grid, block, s, f, q, seed_len, mismatches, (flags & NVBIO_BACKTRACK_REFERENCE_QUIRKS) != 0,
+                           counts_dev, n_ranges_dev, (uint2*)ranges_dev, max_ranges, overflow );
+    }, bad_symbol_bits ) );                                      // (make_set checked the width)
     uint32_t h_over = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync( &h_over, overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s );
+    hipError_t e = hipMemcpyAsync( &h_over, overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s );
     if (e == hipSuccess) e = hipStreamSynchronize( s );
     if (e != hipSuccess) { set_error( "hamming_backtrack failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     if (h_over) { set_error( "hamming_backtrack: the 128-entry stack of the reference's benchmark overflowed for %u branches", h_over ); return NVBIO_ERR_UNSUPPORTED; }
@@ -1702,27 +1644,20 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
     // the pipelined kernel serves the production shape: packed seeds of up to 32 symbols resolved by the direct table's contexts
     const bool pipe = !count && !(flags & NVBIO_FM_NO_PIPELINE) && seeds->symbol_bits != 8 && q.spr <= 64u && q.fixed_len <= 32u && f.dtab != nullptr &&
                       f.ktab != nullptr && !(flags & NVBIO_FM_NO_KMER_TABLE) && f.dctx != 0u && q.fixed_len >= f.dkmer && q.fixed_len - f.dkmer <= f.dctx;
-    (void)with_value( SymbolBits(), seeds->symbol_bits, [&](auto BITS)
+    NVB_CHECK( with_value( SymbolBits(), seeds->symbol_bits, [&](auto BITS)
     {
-        if (pipe)  hipLaunchKernelGGL( (fm_seed_pipe_kernel<(BITS == 8 ? 4 : BITS)>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
-                                       (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev );
-        else if (count) hipLaunchKernelGGL( (fm_seed_tiles_kernel<BITS,true>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
-                                       (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)(counts_dev + 2) );
-        else       hipLaunchKernelGGL( (fm_seed_tiles_kernel<BITS,false>), grid, block, 0, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
-                                       (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)nullptr );
-        return true;
-    }, [] { return false; } );
-    hipError_t e = hipGetLastError();
+        if (pipe)  return NVB_LAUNCH( (fm_seed_pipe_kernel<(BITS == 8 ? 4 : BITS)>), grid, block, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
+                                      (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev );
+        if (count) return NVB_LAUNCH( (fm_seed_tiles_kernel<BITS,true>), grid, block, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
+                                      (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)(counts_dev + 2) );
+        return            NVB_LAUNCH( (fm_seed_tiles_kernel<BITS,false>), grid, block, s, f, q, L.tl, flags & 0xFFFFu, read_len, strand, tile_keys, tile_counts,
+                                      (uint2*)residual_ranges_dev, residual_ids_dev, (unsigned int*)counts_dev, (unsigned long long*)nullptr );
+    }, bad_symbol_bits ) );                                      // (make_set checked the width)
     size_t scan_bytes = L.scan_bytes;
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
-    if (e == hipSuccess)
-    {
-        hipLaunchKernelGGL( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, 0, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
-                            (const uint32_t*)L.tile_offsets, L.tl.n_tiles, L.slots, keys_dev, (unsigned int*)counts_dev );
-        e = hipGetLastError();
-    }
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
     if (e != hipSuccess) { set_error( "seed pass failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
+                       (const uint32_t*)L.tile_offsets, L.tl.n_tiles, L.slots, keys_dev, (unsigned int*)counts_dev );
 }
 
 int nvbio_fm_index_is_canonical(nvbio_fm_index_t index)
@@ -1788,32 +1723,27 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
     // flags bits 8..11: a seed with up to that many hits on a strand leaves them all as keys (0/1: only one-hit seeds do)
     uint32_t inline_max = (flags >> 8) & 15u;
     inline_max = inline_max < 1u ? 1u : (inline_max > CTAB_INLINE ? CTAB_INLINE : inline_max);
-    (void)with_value( Values<2, 4>(), seeds->symbol_bits, [&](auto BITS)
+    NVB_CHECK( with_value( Values<2, 4>(), seeds->symbol_bits, [&](auto BITS)
     {
         const auto launch = [&](auto CNT, auto W, auto D)
         {
-            hipLaunchKernelGGL( (fm_seed_both_kernel<BITS,CNT,W,D>), grid, block, 0, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
-                                (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
-                                CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts );
+            return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D>), grid, block, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
+                               (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
+                               CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts );
         };
         const auto wide = [&](auto W)
         {
-            if (count)      launch( std::true_type(),  W, std::false_type() );
-            else if (defer) launch( std::false_type(), W, std::true_type() );
-            else            launch( std::false_type(), W, std::false_type() );
+            if (count) return launch( std::true_type(),  W, std::false_type() );
+            if (defer) return launch( std::false_type(), W, std::true_type() );
+            return            launch( std::false_type(), W, std::false_type() );
         };
-        if (idx->cwide) wide( std::true_type() ); else wide( std::false_type() );
-        return true;
-    }, [] { return false; } );
-    hipError_t e = hipGetLastError();
+        return idx->cwide ? wide( std::true_type() ) : wide( std::false_type() );
+    }, bad_symbol_bits ) );                                      // (packed seeds were required above)
     size_t scan_bytes = L.scan_bytes;
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
     if (e == hipSuccess)
-    {
-        hipLaunchKernelGGL( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, 0, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
-                            (const uint32_t*)L.tile_offsets, L.tl.n_tiles, 128u, keys_dev, (unsigned int*)counts_dev );
-        e = hipGetLastError();
-    }
+        NVB_CHECK( NVB_LAUNCH( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
+                               (const uint32_t*)L.tile_offsets, L.tl.n_tiles, 128u, keys_dev, (unsigned int*)counts_dev ) );
     if (e == hipSuccess && defer)
     {
         // the deferred searches: their slots made dense, then a launch of their own that appends to the keys and the residual lists
@@ -1821,17 +1751,16 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
         e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)defer_counts, L.defer_offsets, (int)L.tl.n_tiles, s );
         if (e == hipSuccess)
         {
-            hipLaunchKernelGGL( fm_seed_defer_compact_kernel, dim3( grid_for( L.tl.n_tiles ) ), block, 0, s, (const uint32_t*)tile_defer, (const uint32_t*)defer_counts,
-                                (const uint32_t*)L.defer_offsets, L.tl.n_tiles, L.defer_list, L.defer_n );
+            NVB_CHECK( NVB_LAUNCH( fm_seed_defer_compact_kernel, dim3( grid_for( L.tl.n_tiles ) ), block, s, (const uint32_t*)tile_defer, (const uint32_t*)defer_counts,
+                                   (const uint32_t*)L.defer_offsets, L.tl.n_tiles, L.defer_list, L.defer_n ) );
             const uint64_t max_chunks = (128ull * L.tl.n_tiles + 256u * HEAVY_PER_LANE - 1u) / (256u * HEAVY_PER_LANE);
             const dim3 hgrid( (unsigned)(max_chunks < 4096u ? (max_chunks ? max_chunks : 1u) : 4096u) );
             if (seeds->symbol_bits == 2)
-                hipLaunchKernelGGL( (fm_seed_heavy_kernel<2>), hgrid, block, 0, s, f, q, read_len, (const uint32_t*)L.defer_list, (const uint32_t*)L.defer_n, keys_dev,
-                                    (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev );
+                NVB_CHECK( NVB_LAUNCH( (fm_seed_heavy_kernel<2>), hgrid, block, s, f, q, read_len, (const uint32_t*)L.defer_list, (const uint32_t*)L.defer_n, keys_dev,
+                                       (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev ) );
             else
-                hipLaunchKernelGGL( (fm_seed_heavy_kernel<4>), hgrid, block, 0, s, f, q, read_len, (const uint32_t*)L.defer_list, (const uint32_t*)L.defer_n, keys_dev,
-                                    (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev );
-            e = hipGetLastError();
+                NVB_CHECK( NVB_LAUNCH( (fm_seed_heavy_kernel<4>), hgrid, block, s, f, q, read_len, (const uint32_t*)L.defer_list, (const uint32_t*)L.defer_n, keys_dev,
+                                       (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev ) );
         }
     }
     if (e != hipSuccess) { set_error( "seed pass failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
@@ -1848,10 +1777,8 @@ nvbio_status nvbio_fm_filter_locate_direct(nvbio_fm_index_t index, const nvbio_u
     FMIndexImpl* idx = (FMIndexImpl*)index;
     NVB_REQUIRE( idx->view.ssa_dev, "index has no sampled suffix array" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( fm_filter_locate_kernel<false>, dim3( grid_for( (end - begin + FILTER_TILE - 1u) / FILTER_TILE * 256u ) ), dim3(256), 0, (hipStream_t)stream,
-                        idx->dev(), (const uint2*)ranges_dev, slots_dev, n_queries, begin, end, (uint2*)hits_dev, direct_dev, DiagSpec{}, (uint64_t*)nullptr );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_filter_locate_kernel<false>, dim3( expand_grid( begin, end ) ), dim3(256), (hipStream_t)stream,
+                       idx->dev(), (const uint2*)ranges_dev, slots_dev, n_queries, begin, end, (uint2*)hits_dev, direct_dev, DiagSpec{}, (uint64_t*)nullptr );
 }
 
 static nvbio_status filter_locate_diagonals(nvbio_fm_index_t index, const nvbio_uint2* ranges_dev, const uint64_t* slots_dev,
@@ -1870,10 +1797,8 @@ static nvbio_status filter_locate_diagonals(nvbio_fm_index_t index, const nvbio_
     NVB_REQUIRE( idx->view.ssa_dev, "index has no sampled suffix array" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     const DiagSpec ds = { seeds_per_read, seed_interval, seed_len, read_len, strand, query_ids_dev, read_offsets_dev, seed_intervals_dev };
-    hipLaunchKernelGGL( fm_filter_locate_kernel<true>, dim3( grid_for( (end - begin + FILTER_TILE - 1u) / FILTER_TILE * 256u ) ), dim3(256), 0, (hipStream_t)stream,
-                        idx->dev(), (const uint2*)ranges_dev, slots_dev, n_queries, begin, end, (uint2*)nullptr, direct_dev, ds, keys_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( fm_filter_locate_kernel<true>, dim3( expand_grid( begin, end ) ), dim3(256), (hipStream_t)stream,
+                       idx->dev(), (const uint2*)ranges_dev, slots_dev, n_queries, begin, end, (uint2*)nullptr, direct_dev, ds, keys_dev );
 }
 
 nvbio_status nvbio_fm_filter_locate_diagonals(nvbio_fm_index_t index, const nvbio_uint2* ranges_dev, const uint64_t* slots_dev,
@@ -1926,16 +1851,11 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
     ScratchBlock aux;
     NVB_CHECK( aux.alloc_layout( "fm_residual_diagonals", s, "residual diagonals: out of device memory", [&](ScratchLayout& c)
                                  { ids_s = c.take<uint32_t>( n ); rng_s = c.take<uint64_t>( n ); tmp = c.take<uint8_t>( sort_bytes ); } ) );
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs( tmp, sort_bytes, ids_dev, ids_s, (const uint64_t*)ranges_dev, rng_s, (int)n, 0, 32, s );
-    if (e == hipSuccess)
-    {
-        const DiagSpec ds = { seeds_per_read, seed_interval, seed_len, read_len, 0u, nullptr, read_offsets_dev, seed_intervals_dev };
-        hipLaunchKernelGGL( residual_locate_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, idx->dev(), (const uint2*)rng_s, (const uint32_t*)ids_s, n, cap, ds,
-                            keys_dev, (unsigned int*)n_keys_dev );
-        e = hipGetLastError();
-    }
+    const hipError_t e = hipcub::DeviceRadixSort::SortPairs( tmp, sort_bytes, ids_dev, ids_s, (const uint64_t*)ranges_dev, rng_s, (int)n, 0, 32, s );
     if (e != hipSuccess) { set_error( "residual diagonals failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
-    return NVBIO_OK;
+    const DiagSpec ds = { seeds_per_read, seed_interval, seed_len, read_len, 0u, nullptr, read_offsets_dev, seed_intervals_dev };
+    return NVB_LAUNCH( residual_locate_kernel, dim3( grid_for( n ) ), dim3(256), s, idx->dev(), (const uint2*)rng_s, (const uint32_t*)ids_s, n, cap, ds,
+                       keys_dev, (unsigned int*)n_keys_dev );
 }
 
 nvbio_status nvbio_seed_hits_map_approx(nvbio_fm_index_t index, nvbio_fm_index_t reverse_index, const void* reads_dev, uint32_t read_bits,
@@ -1957,15 +1877,12 @@ nvbio_status nvbio_seed_hits_map_approx(nvbio_fm_index_t index, nvbio_fm_index_t
     DeviceGuard g( fi->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     DevIndex f = fi->dev(), rf = ri->dev();
     const dim3 grid( grid_for( n_reads, 128 ) ), block( 128 );
-    (void)with_value( SymbolBits(), read_bits, [&](auto BITS)
+    return with_value( SymbolBits(), read_bits, [&](auto BITS)
     {
-        hipLaunchKernelGGL( (fm_map_approx_kernel<BITS>), grid, block, 0, (hipStream_t)stream, f, rf, reads_dev, read_queue_dev, n_reads,
-                            p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,
-                            (uint2*)deques_dev, sizes_dev, reseed_dev );
-        return true;
-    }, [] { return false; } );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+        return NVB_LAUNCH( (fm_map_approx_kernel<BITS>), grid, block, (hipStream_t)stream, f, rf, reads_dev, read_queue_dev, n_reads,
+                           p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,
+                           (uint2*)deques_dev, sizes_dev, reseed_dev );
+    }, bad_symbol_bits );                                        // (read_bits was checked above)
 }
 
 nvbio_status nvbio_seed_hits_approx_capacity(uint32_t seeds_per_read, uint32_t seed_len, uint32_t max_hits, uint32_t* capacity)

@@ -36,8 +36,8 @@ namespace nvbio_amd {
 template <int BAND, int TYPE, int RBITS, int TBITS, bool BEST2 = false, bool STAGED = false>
 __global__ void __launch_bounds__(128)
 banded_gotoh_kernel(const BatchDev b, const SchemeDev sc, int32_t* __restrict__ scores, uint2* __restrict__ sinks,
-                    const uint32_t distinct_dist = 0, int32_t* __restrict__ scores2 = nullptr, uint2* __restrict__ sinks2 = nullptr,
-                    const int32_t* __restrict__ min_scores = nullptr, const int32_t min_score_all = 0)
+                    const uint32_t distinct_dist, int32_t* __restrict__ scores2, uint2* __restrict__ sinks2,
+                    const int32_t* __restrict__ min_scores, const int32_t min_score_all)
 {
     // mismatch score per quality value, computed once per workgroup
     __shared__ int32_t s_mm[64];
@@ -695,8 +695,8 @@ template <int RBITS, int MODE, bool QUAL = false>
 __global__ void __launch_bounds__(256)
 ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
                       int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
-                      const uint32_t* __restrict__ job_list = nullptr, const uint32_t* __restrict__ job_count = nullptr,
-                      const SchemeDev sc = SchemeDev{})
+                      const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
+                      const SchemeDev sc)
 {
     __shared__ int32_t s_pen[QUAL ? 64 : 1];
     if (QUAL)
@@ -1428,7 +1428,7 @@ static nvbio_status sort_jobs_by_length(const BatchDev& b, const uint32_t* job_l
         c_all = c.take<uint32_t>( 1 );
         tmp   = c.take<uint8_t>( sort_bytes );
     } ) );
-    hipLaunchKernelGGL( job_length_keys_kernel, dim3( (b.n + 255u) / 256u < 65536u ? (b.n + 255u) / 256u : 65536u ), dim3( 256 ), 0, s, b, job_list, job_count, k_in, l_all, c_all );
+    NVB_CHECK( NVB_LAUNCH( job_length_keys_kernel, dim3( (b.n + 255u) / 256u < 65536u ? (b.n + 255u) / 256u : 65536u ), dim3( 256 ), s, b, job_list, job_count, k_in, l_all, c_all ) );
     const hipError_t e = hipcub::DeviceRadixSort::SortPairs( tmp, sort_bytes, (const uint16_t*)k_in, k_out, job_list ? job_list : (const uint32_t*)l_all, l_out, (int)b.n, 0, bits, s );
     if (e != hipSuccess) { set_error( "job sort failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     *list_out = l_out; *count_out = job_list ? job_count : c_all;
@@ -1437,8 +1437,8 @@ static nvbio_status sort_jobs_by_length(const BatchDev& b, const uint32_t* job_l
 
 // the packed kernel's instantiation for this scheme: match = 0 (every end-to-end scheme of nvBowtie) drops one operation per cell
 template <int TYPE, int RB>
-static void launch_pk_kernel(const BatchDev& b, const SchemeDev& sc, const uint32_t pairs, int32_t* scores, uint2* sinks,
-                             const uint32_t* job_list, const uint32_t* job_count, hipStream_t s)
+static nvbio_status launch_pk_kernel(const BatchDev& b, const SchemeDev& sc, const uint32_t pairs, int32_t* scores, uint2* sinks,
+                                     const uint32_t* job_list, const uint32_t* job_count, hipStream_t s)
 {
     const dim3 grid( (pairs + 127u) / 128u ), block( 128 );
     const bool two = (b.algo & NVBIO_ALN_PK_THREE_WAVES) == 0;
@@ -1450,23 +1450,19 @@ static void launch_pk_kernel(const BatchDev& b, const SchemeDev& sc, const uint3
     {
         // reads of different lengths (the caller says so): both alignments of a lane in one pass
         constexpr int T = (TYPE == NVBIO_SEMI_GLOBAL) ? TYPE : NVBIO_SEMI_GLOBAL;
-        if (fp) hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true,true>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
-        else    hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
-        return;
+        if (fp) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+        return         NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
     }
     if (TYPE != NVBIO_LOCAL && sc.match == 0)
     {
         constexpr int T = (TYPE == NVBIO_LOCAL) ? NVBIO_SEMI_GLOBAL : TYPE;      // (never LOCAL here: keeps that instantiation out)
         // (the binary16 build of the GLOBAL kernel spills: SEMI_GLOBAL only)
-        if (fp)  hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<NVBIO_SEMI_GLOBAL,RB,2,true,false,true>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
-        else if (two) hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<T,RB,2,true>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
-        else     hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<T,RB,3,true>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
+        if (fp)  return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<NVBIO_SEMI_GLOBAL,RB,2,true,false,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+        if (two) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+        return          NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,3,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
     }
-    else
-    {
-        if (two) hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<TYPE,RB,2,false>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
-        else     hipLaunchKernelGGL( (banded_gotoh_band31_pk_kernel<TYPE,RB,3,false>), grid, block, 0, s, b, sc, scores, sinks, job_list, job_count );
-    }
+    if (two) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<TYPE,RB,2,false>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+    return          NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<TYPE,RB,3,false>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
 }
 
 template <int TYPE, int RB>
@@ -1505,11 +1501,11 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         uint32_t* job_count = counts;
         uint32_t* count_st  = counts + 2;                                                   // (DevicePartition writes both lengths)
         if (by_quality)
-            hipLaunchKernelGGL( (ungapped_e2e31_kernel<RB,0,true>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc );
+            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0,true>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc ) );
         else
-            hipLaunchKernelGGL( (ungapped_e2e31_kernel<RB,0>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc );
+            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc ) );
         hipError_t e = hipSuccess;
         {
             // the jobs a chance can still settle, compacted by ONE three-way partition, each list through its own launch; every job ends as 0 or 1.
@@ -1525,14 +1521,14 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
             size_t pb = sel_bytes;
             e = hipcub::DevicePartition::If( sel_temp, pb, ids, list_s, list_t, nowhere, count_st, (int)b.n, f3, f2, s );
             if (e == hipSuccess)
-                hipLaunchKernelGGL( (ungapped_e2e31_kernel<RB,1>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                    (const uint32_t*)list_s, (const uint32_t*)count_st );
+                NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                       (const uint32_t*)list_s, (const uint32_t*)count_st, SchemeDev{} ) );
             if (e == hipSuccess && gapc)
-                hipLaunchKernelGGL( (gap_chance_e2e31_kernel<RB>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                    (const uint32_t*)list_t, (const uint32_t*)(count_st + 1) );
+                NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                       (const uint32_t*)list_t, (const uint32_t*)(count_st + 1) ) );
             else if (e == hipSuccess && third)
-                hipLaunchKernelGGL( (ungapped_e2e31_kernel<RB,2>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                    (const uint32_t*)list_t, (const uint32_t*)(count_st + 1) );
+                NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,2>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                       (const uint32_t*)list_t, (const uint32_t*)(count_st + 1), SchemeDev{} ) );
         }
         if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, need_dp, job_list, job_count, (int)b.n, s );
         if (e == hipSuccess)
@@ -1540,23 +1536,18 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
             const uint32_t* jl = job_list; const uint32_t* jc = job_count; ScratchBlock sorted;
             if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT))
                 NVB_CHECK( sort_jobs_by_length( b, job_list, job_count, &jl, &jc, &sorted, s ) );
-            launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s );
+            NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s )) );
         }
         if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
-        NVB_HIP( hipGetLastError() );
         return NVBIO_OK;
     }
     if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT) && b.n > 1u)
     {
         const uint32_t* jl = nullptr; const uint32_t* jc = nullptr; ScratchBlock sorted;
         NVB_CHECK( sort_jobs_by_length( b, nullptr, nullptr, &jl, &jc, &sorted, s ) );
-        launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s );
-        NVB_HIP( hipGetLastError() );
-        return NVBIO_OK;
+        return launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s );
     }
-    launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, nullptr, nullptr, s );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, nullptr, nullptr, s );
 }
 
 template <int BAND>
@@ -1571,10 +1562,8 @@ static nvbio_status launch_score(int type, const BatchDev& b, const SchemeDev& s
         const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
         return with_bits( BitsAll(), rbits, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t>), grid, block, 0, s, b, sc, scores, sinks );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
-        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+            return NVB_LAUNCH( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t>), grid, block, s, b, sc, scores, sinks, 0u, nullptr, nullptr, nullptr, 0 );
+        }, [&] { return invalid_bits( rbits, tbits ); } );
     }, [&] { return invalid_type( type ); } );
 }
 
@@ -1587,10 +1576,8 @@ static nvbio_status launch_staged(int type, const BatchDev& b, const SchemeDev& 
     {
         return with_bits( BitsStaged(), rbits, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t,false,true>), grid, block, 0, s, b, sc, scores, sinks,
-                                0u, (int32_t*)nullptr, (uint2*)nullptr, min_scores, min_score );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
+            return NVB_LAUNCH( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t,false,true>), grid, block, s, b, sc, scores, sinks,
+                               0u, (int32_t*)nullptr, (uint2*)nullptr, min_scores, min_score );
         }, [&] { set_error( "staged scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
     }, [&] { return invalid_type( type ); } );
 }
@@ -1601,12 +1588,12 @@ bool banded31_packed_ok(const SchemeDev& sc, const uint32_t max_read_len)
 {
     return plain_gotoh( sc ) && packed_ok( NVBIO_SEMI_GLOBAL, sc, max_read_len );
 }
-void banded31_packed_launch(const BatchDev& b, const SchemeDev& sc, const uint32_t read_bits, const uint32_t max_jobs, int32_t* scores, uint2* sinks,
-                            const uint32_t* job_list, const uint32_t* job_count, hipStream_t s)
+nvbio_status banded31_packed_launch(const BatchDev& b, const SchemeDev& sc, const uint32_t read_bits, const uint32_t max_jobs, int32_t* scores, uint2* sinks,
+                                    const uint32_t* job_list, const uint32_t* job_count, hipStream_t s)
 {
     const uint32_t pairs = (max_jobs + 1u) / 2u;
-    if (read_bits == 4) launch_pk_kernel<NVBIO_SEMI_GLOBAL,4>( b, sc, pairs, scores, sinks, job_list, job_count, s );
-    else                launch_pk_kernel<NVBIO_SEMI_GLOBAL,2>( b, sc, pairs, scores, sinks, job_list, job_count, s );
+    if (read_bits == 4) return launch_pk_kernel<NVBIO_SEMI_GLOBAL,4>( b, sc, pairs, scores, sinks, job_list, job_count, s );
+    return                     launch_pk_kernel<NVBIO_SEMI_GLOBAL,2>( b, sc, pairs, scores, sinks, job_list, job_count, s );
 }
 
 nvbio_status make_batch(const nvbio_alignment_batch* in, BatchDev* b)
@@ -1639,9 +1626,7 @@ static nvbio_status launch_best2(int type, const BatchDev& b, const SchemeDev& s
     {
         return with_bits( BitsBest2(), rbits, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t,true>), grid, block, 0, s, b, sc, scores, sinks, dist, scores2, sinks2 );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
+            return NVB_LAUNCH( (banded_gotoh_kernel<BAND,TYPE,P.r,P.t,true>), grid, block, s, b, sc, scores, sinks, dist, scores2, sinks2, nullptr, 0 );
         }, [&] { set_error( "Best2Sink scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
     }, [&] { return invalid_type( type ); } );
 }

@@ -77,6 +77,12 @@ inline nvbio_status invalid_type(const int type)
     set_error( "invalid alignment type %d", type );
     return NVBIO_ERR_INVALID;
 }
+// what a (read_bits, text_bits) pair outside BitsAll gets
+inline nvbio_status invalid_bits(const uint32_t rbits, const uint32_t tbits)
+{
+    set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits );
+    return NVBIO_ERR_INVALID;
+}
 
 nvbio_status make_batch(const nvbio_alignment_batch* in, BatchDev* b);      // gotoh_banded.hip
 nvbio_status banded15_full_ties_traceback(const BatchDev& b, const SchemeDev& sc, const uint32_t rbits, const uint32_t tbits, const uint32_t max_jobs,
@@ -84,8 +90,8 @@ nvbio_status banded15_full_ties_traceback(const BatchDev& b, const SchemeDev& sc
                                           int32_t* scores, uint2* sources, uint2* sinks, uint16_t* cigars, const uint32_t stride, uint32_t* lens,
                                           hipStream_t s);                   // gotoh_traceback.hip
 bool banded31_packed_ok(const SchemeDev& sc, const uint32_t max_read_len);  // gotoh_banded.hip
-void banded31_packed_launch(const BatchDev& b, const SchemeDev& sc, const uint32_t read_bits, const uint32_t max_jobs, int32_t* scores, uint2* sinks,
-                            const uint32_t* job_list, const uint32_t* job_count, hipStream_t s);
+nvbio_status banded31_packed_launch(const BatchDev& b, const SchemeDev& sc, const uint32_t read_bits, const uint32_t max_jobs, int32_t* scores, uint2* sinks,
+                                    const uint32_t* job_list, const uint32_t* job_count, hipStream_t s);
 
 // QualCost (nvBowtie/bowtie2/cuda/scoring.h:84-88) negated (:280-281); IEEE float ops, no contraction
 __device__ __forceinline__ int32_t mismatch_score(const SchemeDev& sc, const uint32_t q)

@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(128)
 full_gotoh_kernel(const BatchDev b, const SchemeDev sc, const uint32_t job_begin, const uint32_t jobs, const int32_t* __restrict__ min_scores,
                   uint32_t* __restrict__ column, int32_t* __restrict__ scores, uint2* __restrict__ sinks,
                   const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
-                  const uint32_t distinct_dist = 0, int32_t* __restrict__ scores2 = nullptr, uint2* __restrict__ sinks2 = nullptr)
+                  const uint32_t distinct_dist, int32_t* __restrict__ scores2, uint2* __restrict__ sinks2)
 {
     __shared__ int32_t s_mm[64];
     if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
@@ -464,8 +464,8 @@ template <int RBITS, int MODE = 0>
 __global__ void __launch_bounds__(256)
 ungapped_full_e2e_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext, const bool second_chance,
                          const int32_t* __restrict__ min_scores, const bool text_blocking,
-                         int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp, const bool stash = false,
-                         const uint32_t* __restrict__ job_list = nullptr, const uint32_t* __restrict__ job_count = nullptr)
+                         int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp, const bool stash,
+                         const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count)
 {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (MODE == 0 ? slot >= b.n : slot >= *job_count) return;
@@ -1242,11 +1242,9 @@ nvbio_status launch_dp(int type, const BatchDev& b, const SchemeDev& sc, uint32_
     {
         return with_bits( BitsAll(), rbits, tbits, [&](auto P)
         {
-            if (sc.wide) hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,P.r,P.t,false,true>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count );
-            else         hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,P.r,P.t>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
-        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+            if (sc.wide) return NVB_LAUNCH( (full_gotoh_kernel<TYPE,TB,P.r,P.t,false,true>), grid, block, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count, 0u, nullptr, nullptr );
+            return              NVB_LAUNCH( (full_gotoh_kernel<TYPE,TB,P.r,P.t>), grid, block, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks, job_list, job_count, 0u, nullptr, nullptr );
+        }, [&] { return invalid_bits( rbits, tbits ); } );
     }, [&] { return invalid_type( type ); } );
 }
 
@@ -1293,8 +1291,8 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         if (coop)
         {
 #define NVB_COOP(TYPE_, L_, W_) do { const uint64_t lanes = (uint64_t)b.n * L_; const dim3 grid( (uint32_t)((lanes + 255u) / 256u) ), block( 256 ); \
-            if (batch->read_bits == 4) hipLaunchKernelGGL( (full_gotoh_coop_kernel<TYPE_,L_,W_,4>), grid, block, 0, s, b, sc, text_blocking != 0, scores_dev, (uint2*)sinks_dev ); \
-            else                       hipLaunchKernelGGL( (full_gotoh_coop_kernel<TYPE_,L_,W_,2>), grid, block, 0, s, b, sc, text_blocking != 0, scores_dev, (uint2*)sinks_dev ); } while (0)
+            if (batch->read_bits == 4) NVB_CHECK( NVB_LAUNCH( (full_gotoh_coop_kernel<TYPE_,L_,W_,4>), grid, block, s, b, sc, text_blocking != 0, scores_dev, (uint2*)sinks_dev ) ); \
+            else                       NVB_CHECK( NVB_LAUNCH( (full_gotoh_coop_kernel<TYPE_,L_,W_,2>), grid, block, s, b, sc, text_blocking != 0, scores_dev, (uint2*)sinks_dev ) ); } while (0)
 #define NVB_COOP_SHAPE(TYPE_) do { const uint32_t mp = max_pattern_len; \
             if      (mp <=  32u) NVB_COOP( TYPE_, 4, 8 );  \
             else if (mp <=  64u) NVB_COOP( TYPE_, 4, 16 ); \
@@ -1306,7 +1304,6 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
             if (type == NVBIO_GLOBAL) NVB_COOP_SHAPE( NVBIO_GLOBAL ); else NVB_COOP_SHAPE( NVBIO_SEMI_GLOBAL );
 #undef NVB_COOP_SHAPE
 #undef NVB_COOP
-            NVB_HIP( hipGetLastError() );
             return NVBIO_OK;
         }
     }
@@ -1355,10 +1352,10 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         {
             const int32_t G = sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go;
             const bool second_chance = (sc.pat_go == sc.txt_go && sc.pat_ge == sc.txt_ge);
-            if (batch->read_bits == 4) hipLaunchKernelGGL( (ungapped_full_e2e_kernel<4,0>), grid, block, 0, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
-                                                           (const uint32_t*)nullptr, (const uint32_t*)nullptr );
-            else                       hipLaunchKernelGGL( (ungapped_full_e2e_kernel<2,0>), grid, block, 0, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
-                                                           (const uint32_t*)nullptr, (const uint32_t*)nullptr );
+            if (batch->read_bits == 4) NVB_CHECK( NVB_LAUNCH( (ungapped_full_e2e_kernel<4,0>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
+                                                              (const uint32_t*)nullptr, (const uint32_t*)nullptr ) );
+            else                       NVB_CHECK( NVB_LAUNCH( (ungapped_full_e2e_kernel<2,0>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
+                                                              (const uint32_t*)nullptr, (const uint32_t*)nullptr ) );
             if (second_chance)
             {
                 // the jobs the second chance can still settle (need_dp == 3), compacted, through their own launch: every job ends as 0 or 1
@@ -1366,30 +1363,30 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
                 hipcub::TransformInputIterator<uint8_t, FlagIs3, const uint8_t*> is3( need_dp, FlagIs3() );
                 const hipError_t e3 = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is3, list_s, count_s, (int)b.n, s );
                 if (e3 != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e3 ) ); return NVBIO_ERR_HIP; }
-                if (batch->read_bits == 4) hipLaunchKernelGGL( (ungapped_full_e2e_kernel<4,1>), grid, block, 0, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
-                                                               (const uint32_t*)list_s, (const uint32_t*)count_s );
-                else                       hipLaunchKernelGGL( (ungapped_full_e2e_kernel<2,1>), grid, block, 0, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
-                                                               (const uint32_t*)list_s, (const uint32_t*)count_s );
+                if (batch->read_bits == 4) NVB_CHECK( NVB_LAUNCH( (ungapped_full_e2e_kernel<4,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
+                                                                  (const uint32_t*)list_s, (const uint32_t*)count_s ) );
+                else                       NVB_CHECK( NVB_LAUNCH( (ungapped_full_e2e_kernel<2,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, second_chance, min_scores_dev, text_blocking != 0, scores_dev, (uint2*)sinks_dev, need_dp, narrow,
+                                                                  (const uint32_t*)list_s, (const uint32_t*)count_s ) );
             }
         }
         hipError_t e = hipSuccess;
         if (narrow)
         {
             // the unsettled jobs with room for a band around their best diagonal: band-31 score, then the run test (narrow_check_kernel)
-            hipLaunchKernelGGL( narrow_jobs_kernel, grid, block, 0, s, b, (const uint8_t*)need_dp, (const uint2*)sinks_dev, wb2, we2, route );
+            NVB_CHECK( NVB_LAUNCH( narrow_jobs_kernel, grid, block, s, b, (const uint8_t*)need_dp, (const uint2*)sinks_dev, wb2, we2, route ) );
             e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, route, list_n, count_n, (int)b.n, s );
             if (e == hipSuccess)
             {
                 BatchDev b2 = b; b2.win_begin = wb2; b2.win_end = we2; b2.max_read_len = max_pattern_len;
-                banded31_packed_launch( b2, sc, batch->read_bits, b.n, scores_dev, (uint2*)sinks_dev, list_n, count_n, s );
-                if (batch->read_bits == 4) hipLaunchKernelGGL( (narrow_check_kernel<4>), grid, block, 0, s, b, P, sc.pat_go, sc.pat_ge, min_scores_dev, (const uint32_t*)wb2, (const int32_t*)scores_dev, (uint2*)sinks_dev, need_dp, (const uint32_t*)list_n, (const uint32_t*)count_n );
-                else                       hipLaunchKernelGGL( (narrow_check_kernel<2>), grid, block, 0, s, b, P, sc.pat_go, sc.pat_ge, min_scores_dev, (const uint32_t*)wb2, (const int32_t*)scores_dev, (uint2*)sinks_dev, need_dp, (const uint32_t*)list_n, (const uint32_t*)count_n );
+                NVB_CHECK( banded31_packed_launch( b2, sc, batch->read_bits, b.n, scores_dev, (uint2*)sinks_dev, list_n, count_n, s ) );
+                if (batch->read_bits == 4) NVB_CHECK( NVB_LAUNCH( (narrow_check_kernel<4>), grid, block, s, b, P, sc.pat_go, sc.pat_ge, min_scores_dev, (const uint32_t*)wb2, (const int32_t*)scores_dev, (uint2*)sinks_dev, need_dp, (const uint32_t*)list_n, (const uint32_t*)count_n ) );
+                else                       NVB_CHECK( NVB_LAUNCH( (narrow_check_kernel<2>), grid, block, s, b, P, sc.pat_go, sc.pat_ge, min_scores_dev, (const uint32_t*)wb2, (const int32_t*)scores_dev, (uint2*)sinks_dev, need_dp, (const uint32_t*)list_n, (const uint32_t*)count_n ) );
             }
         }
         if (packed)
         {
-            hipLaunchKernelGGL( classify_shape_kernel, grid, block, 0, s, b, max_pattern_len, max_text_len, shortcut ? (const uint8_t*)need_dp : (const uint8_t*)nullptr,
-                                to_packed, to_plain );
+            NVB_CHECK( NVB_LAUNCH( classify_shape_kernel, grid, block, s, b, max_pattern_len, max_text_len, shortcut ? (const uint8_t*)need_dp : (const uint8_t*)nullptr,
+                                   to_packed, to_plain ) );
             e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, to_packed, list_a, count_a, (int)b.n, s );
             if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, to_plain, job_list, job_count, (int)b.n, s );
         }
@@ -1430,10 +1427,10 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
         {
             const uint32_t pairs = (uint32_t)((all_pairs - pb) < cap_pairs ? (all_pairs - pb) : cap_pairs);
             const dim3 grid( (pairs + 127u) / 128u ), block( 128 );
-#define NVB_PK(TYPE_, RB) hipLaunchKernelGGL( (full_gotoh_pb_pk_kernel<TYPE_,RB>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, (uint32_t)pb, pairs, \
-                                              min_scores_dev, (uint2*)column, scores_dev, (uint2*)sinks_dev, (const uint32_t*)list_a, (const uint32_t*)count_a )
-#define NVB_PK16(RB) hipLaunchKernelGGL( (full_gotoh_pb_pk16_kernel<RB>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, (uint32_t)pb, pairs, \
-                                         min_scores_dev, (uint2*)column, scores_dev, (uint2*)sinks_dev, (const uint32_t*)list_a, (const uint32_t*)count_a )
+#define NVB_PK(TYPE_, RB) st = NVB_LAUNCH( (full_gotoh_pb_pk_kernel<TYPE_,RB>), grid, block, s, b, sc, max_pattern_len, max_text_len, (uint32_t)pb, pairs, \
+                                           min_scores_dev, (uint2*)column, scores_dev, (uint2*)sinks_dev, (const uint32_t*)list_a, (const uint32_t*)count_a )
+#define NVB_PK16(RB) st = NVB_LAUNCH( (full_gotoh_pb_pk16_kernel<RB>), grid, block, s, b, sc, max_pattern_len, max_text_len, (uint32_t)pb, pairs, \
+                                      min_scores_dev, (uint2*)column, scores_dev, (uint2*)sinks_dev, (const uint32_t*)list_a, (const uint32_t*)count_a )
             const bool wide16 = type == NVBIO_SEMI_GLOBAL && sc.match == 0 && !(b.algo & NVBIO_ALN_PK_STRIPE8);      // the end-to-end kernel, 16 columns per stripe
             if (batch->read_bits == 4)
             {
@@ -1447,7 +1444,6 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
             }
 #undef NVB_PK16
 #undef NVB_PK
-            if (hipGetLastError() != hipSuccess) { set_error( "packed full Gotoh launch failed" ); st = NVBIO_ERR_HIP; }
         }
     }
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
@@ -1481,10 +1477,8 @@ static nvbio_status launch_best2(int type, const BatchDev& b, const SchemeDev& s
     {
         return with_bits( BitsBest2(), rbits, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (full_gotoh_kernel<TYPE,TB,P.r,P.t,true>), grid, block, 0, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks,
-                                (const uint32_t*)nullptr, (const uint32_t*)nullptr, dist, scores2, sinks2 );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
+            return NVB_LAUNCH( (full_gotoh_kernel<TYPE,TB,P.r,P.t,true>), grid, block, s, b, sc, job_begin, jobs, min_scores, column, scores, sinks,
+                               (const uint32_t*)nullptr, (const uint32_t*)nullptr, dist, scores2, sinks2 );
         }, [&] { set_error( "Best2Sink scoring: read_bits/text_bits %u/%u not instantiated (4/2, 2/2, 8/2, 8/8)", rbits, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
     }, [&] { return invalid_type( type ); } );                              // (the entry point checked the type)
 }

@@ -64,7 +64,7 @@ full_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32_t
                             const int32_t* __restrict__ min_scores, uint32_t* __restrict__ column, uint32_t* __restrict__ dirs,
                             int32_t* __restrict__ scores, uint2* __restrict__ sources, uint2* __restrict__ sinks,
                             uint16_t* __restrict__ cigars, const uint32_t cigar_stride, uint32_t* __restrict__ cigar_lens,
-                            const uint8_t* __restrict__ band_code = nullptr, const uint32_t given_sinks = 0u)
+                            const uint8_t* __restrict__ band_code, const uint32_t given_sinks)
 {
     __shared__ int32_t s_mm[64];
     if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
@@ -310,7 +310,7 @@ ungapped_full_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint3
                                const int32_t* __restrict__ scores, const uint2* __restrict__ sinks,
                                uint2* __restrict__ sources, uint16_t* __restrict__ cigars, const uint32_t cigar_stride,
                                uint32_t* __restrict__ cigar_lens, uint8_t* __restrict__ need_dp,
-                               const int32_t gap_open_min = 0, const int32_t gap_ext_min = 0)
+                               const int32_t gap_open_min, const int32_t gap_ext_min)
 {
     __shared__ int32_t s_mm[64];
     if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
@@ -490,14 +490,11 @@ extern "C" nvbio_status nvbio_finish_alignment(int device, const nvbio_alignment
     const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
     const uint32_t rb = batch->read_bits, tbits = batch->text_bits;
     hipStream_t s = (hipStream_t)stream;
-    (void)with_bits( BitsAll(), rb, tbits, [&](auto P)                     // (make_batch admits no other pair)
+    return with_bits( BitsAll(), rb, tbits, [&](auto P)
     {
-        hipLaunchKernelGGL( (finish_alignment_kernel<P.r,P.t>), grid, block, 0, s, b, (const uint2*)sources_dev, cigars_dev, cigar_stride,
-                            cigar_lens_dev, ed_dev, mds_dev, mds_stride, mds_lens_dev );
-        return true;
-    }, [] { return false; } );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+        return NVB_LAUNCH( (finish_alignment_kernel<P.r,P.t>), grid, block, s, b, (const uint2*)sources_dev, cigars_dev, cigar_stride,
+                           cigar_lens_dev, ed_dev, mds_dev, mds_stride, mds_lens_dev );
+    }, [&] { return invalid_bits( rb, tbits ); } );                        // (make_batch admits no other pair)
 }
 
 static inline uint64_t full_tb_bytes_per_job(const uint32_t max_M, const uint32_t max_N)
@@ -584,18 +581,17 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         } ) );
         band_count = job_count + 1;
         const dim3 grid( (b.n + 255u) / 256u ), block( 256 );
-        (void)with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
+        NVB_CHECK( with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (ungapped_full_traceback_kernel<TYPE,P.r,P.t>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len,
-                                (const int32_t*)scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp,
-                                go_min, narrow ? ge_min : 0 );
-            return true;
-        }, [] { return false; } ); }, [] { return false; } );              // (the type and the pair were checked)
+            return NVB_LAUNCH( (ungapped_full_traceback_kernel<TYPE,P.r,P.t>), grid, block, s, b, sc, max_pattern_len, max_text_len,
+                               (const int32_t*)scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp,
+                               go_min, narrow ? ge_min : 0 );
+        }, [&] { return invalid_bits( rb, tbits ); } ); }, [&] { return invalid_type( type ); } ) );      // (the type and the pair were checked)
         hipError_t e = hipSuccess;
         if (band_ok)
         {
             // the restricted jobs that fit a band of 15 leave the full-matrix list (see tb_band_route_kernel); launched below
-            hipLaunchKernelGGL( tb_band_route_kernel, grid, block, 0, s, b, need_dp, (const uint2*)sinks_dev, band_wb, band_we, band_route );
+            NVB_CHECK( NVB_LAUNCH( tb_band_route_kernel, grid, block, s, b, need_dp, (const uint2*)sinks_dev, band_wb, band_we, band_route ) );
             e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, band_route, band_list, band_count, (int)b.n, s );
         }
         if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, need_dp, job_list, job_count, (int)b.n, s );
@@ -627,8 +623,8 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         st = banded15_full_ties_traceback( b2, sc, rb, tbits, b.n, band_list, band_count, (uint32_t*)scratch, cap_jobs * per_job,
                                            scores_dev, (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s );
         if (st == NVBIO_OK)
-            hipLaunchKernelGGL( tb_band_fixup_kernel, dim3( (b.n + 255u) / 256u ), dim3( 256 ), 0, s, b, (const uint32_t*)band_wb, (const uint32_t*)band_list,
-                                (const uint32_t*)band_count, (uint2*)sources_dev, (uint2*)sinks_dev );
+            st = NVB_LAUNCH( tb_band_fixup_kernel, dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, (const uint32_t*)band_wb, (const uint32_t*)band_list,
+                             (const uint32_t*)band_count, (uint2*)sources_dev, (uint2*)sinks_dev );
     }
     for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
     {
@@ -637,14 +633,12 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
         const uint64_t jobs64 = ((uint64_t)jobs + 63u) & ~63ull;                  // whole waves own scratch
         uint32_t* dirs   = column + (size_t)jobs64 * max_text_len;
         const dim3 grid( (jobs + 127u) / 128u ), block( 128 );
-        (void)with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
+        st = with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (full_gotoh_traceback_kernel<TYPE,P.r,P.t>), grid, block, 0, s, b, sc, max_pattern_len, max_text_len, (uint32_t)begin, jobs,
-                                (const uint32_t*)job_list, (const uint32_t*)job_count, min_scores_dev, column, dirs, scores_dev, (uint2*)sources_dev,
-                                (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, (const uint8_t*)(narrow ? need_dp : nullptr), sw ? 1u : 0u );
-            return true;
-        }, [] { return false; } ); }, [] { return false; } );              // (the type and the pair were checked)
-        if (hipGetLastError() != hipSuccess) { set_error( "full traceback launch failed" ); st = NVBIO_ERR_HIP; }
+            return NVB_LAUNCH( (full_gotoh_traceback_kernel<TYPE,P.r,P.t>), grid, block, s, b, sc, max_pattern_len, max_text_len, (uint32_t)begin, jobs,
+                               (const uint32_t*)job_list, (const uint32_t*)job_count, min_scores_dev, column, dirs, scores_dev, (uint2*)sources_dev,
+                               (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, (const uint8_t*)(narrow ? need_dp : nullptr), sw ? 1u : 0u );
+        }, [&] { return invalid_bits( rb, tbits ); } ); }, [&] { return invalid_type( type ); } );          // (the type and the pair were checked)
     }
     return st;
 }

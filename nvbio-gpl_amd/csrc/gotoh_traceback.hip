@@ -36,7 +36,7 @@ banded_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32
                               uint32_t* __restrict__ dirs,
                               int32_t* __restrict__ scores, uint2* __restrict__ sources, uint2* __restrict__ sinks,
                               uint16_t* __restrict__ cigars, const uint32_t cigar_stride, uint32_t* __restrict__ cigar_lens,
-                              const uint8_t* __restrict__ band_off = nullptr, const uint32_t full_ties = 0u)
+                              const uint8_t* __restrict__ band_off, const uint32_t full_ties)
 {
     constexpr int WORDS = (BAND + 7) / 8;                        // 32-bit words of direction nibbles per row
 
@@ -300,7 +300,7 @@ __global__ void __launch_bounds__(256)
 ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* __restrict__ scores, const uint2* __restrict__ sinks,
                           uint2* __restrict__ sources, uint16_t* __restrict__ cigars, const uint32_t cigar_stride,
                           uint32_t* __restrict__ cigar_lens, uint8_t* __restrict__ need_dp,
-                          uint8_t* __restrict__ band_off = nullptr, const int32_t gap_open_min = 0, const int32_t gap_ext_min = 0)
+                          uint8_t* __restrict__ band_off, const int32_t gap_open_min, const int32_t gap_ext_min)
 {
     __shared__ int32_t s_mm[64];
     if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
@@ -434,11 +434,9 @@ nvbio_status launch_ungapped(int type, const BatchDev& b, const SchemeDev& sc, u
     {
         return with_bits( BitsAll(), rbits, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (ungapped_traceback_kernel<BAND,TYPE,P.r,P.t>), grid, block, 0, s, b, sc, scores, sinks, sources, cigars, stride, lens,
-                                need_dp, band_off, go_min, ge_min );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
-        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+            return NVB_LAUNCH( (ungapped_traceback_kernel<BAND,TYPE,P.r,P.t>), grid, block, s, b, sc, scores, sinks, sources, cigars, stride, lens,
+                               need_dp, band_off, go_min, ge_min );
+        }, [&] { return invalid_bits( rbits, tbits ); } );
     }, [&] { return invalid_type( type ); } );
 }
 
@@ -452,11 +450,9 @@ nvbio_status launch_dp(int type, const BatchDev& b, const SchemeDev& sc, uint32_
     {
         return with_bits( BitsAll(), rbits, tbits, [&](auto P)
         {
-            hipLaunchKernelGGL( (banded_gotoh_traceback_kernel<BAND,TYPE,P.r,P.t>), grid, block, 0, s, b, sc, job_begin, jobs, job_list, job_count, dirs,
-                                scores, sources, sinks, cigars, stride, lens, band_off, full_ties );
-            NVB_HIP( hipGetLastError() );
-            return NVBIO_OK;
-        }, [&] { set_error( "unsupported read_bits/text_bits %u/%u", rbits, tbits ); return NVBIO_ERR_INVALID; } );
+            return NVB_LAUNCH( (banded_gotoh_traceback_kernel<BAND,TYPE,P.r,P.t>), grid, block, s, b, sc, job_begin, jobs, job_list, job_count, dirs,
+                               scores, sources, sinks, cigars, stride, lens, band_off, full_ties );
+        }, [&] { return invalid_bits( rbits, tbits ); } );
     }, [&] { return invalid_type( type ); } );
 }
 

@@ -317,58 +317,20 @@ mem_output_kernel(const uint32_t n_reads, const uint32_t* __restrict__ off, cons
     }
 }
 
-struct MemRangeSize
-{
-    __host__ __device__ __forceinline__ uint64_t operator()(const uint4 r) const { return (uint64_t)(uint32_t)(1u + r.y - r.x); }
-};
-
-// locate (MEMFilter::locate, mem_inl.h:1463-1505, over fm_filter_locate_kernel's tiling): hits[h - begin] = (text position, string id,
-// span begin, span end) of the global MEM index h.  A workgroup owns FILTER_TILE consecutive indices; their ranges form a contiguous
-// slice of `slots`, found once per tile, so that each index's own upper_bound runs over a few cached entries.
-constexpr uint32_t MEM_LOCATE_TILE = 256u * 8u;
-
+// locate (MEMFilter::locate, mem_inl.h:1463-1505): hits[h - begin] = (text position, string id, span begin, span end) of the global
+// MEM index h, over the shared expansion (locate_ranges, fm_device.h)
 __global__ void __launch_bounds__(256)
 mem_locate_kernel(const DevIndex f, const uint4* __restrict__ ranges, const uint64_t* __restrict__ slots, const uint32_t n_ranges,
                   const uint64_t begin, const uint64_t end, uint4* __restrict__ hits)
 {
-    __shared__ uint32_t s_q[2];
-    const uint32_t mask    = (1u << f.sa_log) - 1u;
-    const uint64_t n_tiles = (end - begin + MEM_LOCATE_TILE - 1u) / MEM_LOCATE_TILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
-    {
-        const uint64_t t_first = begin + tile * MEM_LOCATE_TILE;
-        const uint64_t t_end   = (t_first + MEM_LOCATE_TILE < end) ? t_first + MEM_LOCATE_TILE : end;
-        __syncthreads();
-        if (threadIdx.x < 2)
-            s_q[threadIdx.x] = upper_bound_u64( slots, 0u, n_ranges, threadIdx.x ? t_end - 1u : t_first );
-        __syncthreads();
-        const uint32_t q_lo = s_q[0], q_hi = s_q[1] + 1u < n_ranges ? s_q[1] + 1u : n_ranges;
-
-        uint64_t h    = t_first + threadIdx.x;
-        bool     have = h < t_end;
-        uint32_t j = 0, t = 0;
-        uint4    m = make_uint4( 0, 0, 0, 0 );
-        auto start = [&]() {
-            const uint32_t slot = upper_bound_u64( slots, q_lo, q_hi, h );
-            const uint64_t base = slot ? slots[slot - 1u] : 0ull;
-            m = ranges[slot];
-            j = m.x + (uint32_t)(h - base); t = 0;
-        };
-        if (have) start();
-        while (__any( have ))
-        {
-            if (have)
-            {
-                if ((j & mask) == 0)
-                {
-                    hits[h - begin] = make_uint4( f.ssa[j >> f.sa_log] + t, m.z & ~MEM_FLAG, span_begin( m ), span_end( m ) );
-                    h += 256u; have = h < t_end;
-                    if (have) start();
-                }
-                else { j = lf_step( f, j ); ++t; }
-            }
-        }
-    }
+    uint4 m = make_uint4( 0, 0, 0, 0 );                          // the MEM of the index this lane is walking to
+    locate_ranges( f, slots, n_ranges, begin, end,
+        [&](const uint64_t h, const uint32_t i, const uint64_t base, uint32_t& row) {
+            m = ranges[i];
+            row = m.x + (uint32_t)(h - base);
+            return true;
+        },
+        [&](const uint64_t h, const uint32_t pos) { hits[h - begin] = make_uint4( pos, m.z & ~MEM_FLAG, span_begin( m ), span_end( m ) ); } );
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -420,7 +382,7 @@ struct MemTemp
         size_t a = 0, b = 0;
         const int n = (int)(n_items ? n_items : 1);
         (void)hipcub::DeviceScan::InclusiveSum( nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, n );
-        hipcub::TransformInputIterator<uint64_t, MemRangeSize, const uint4*> sizes( (const uint4*)nullptr, MemRangeSize() );
+        hipcub::TransformInputIterator<uint64_t, RangeSize, const uint4*> sizes( (const uint4*)nullptr, RangeSize() );
         (void)hipcub::DeviceScan::InclusiveSum( nullptr, b, sizes, (uint64_t*)nullptr, n );
         return a > b ? a : b;
     }
@@ -520,14 +482,12 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
     const uint32_t bits = reads->symbol_bits;
     const bool do_split = params->split_len < 0xFFFFFFFFu;
 
-    // right pass -> candidates per read
-    (void)with_value( SymbolBits(), bits, [&](auto BITS)
+    // right pass -> candidates per read (mem_reads checked the symbol width: no dispatch below misses)
+    NVB_CHECK( with_value( SymbolBits(), bits, [&](auto BITS)
     {
-        hipLaunchKernelGGL( mem_right_kernel<BITS>, dim3( grid_for( q.n ) ), dim3(256), 0, s, f, r, q, (uint32_t)total, params->min_intv, T.cand, T.cnt,
-                            T.misc, rec );
-        return true;
-    }, [] { return false; } );
-    NVB_HIP( hipGetLastError() );
+        return NVB_LAUNCH( mem_right_kernel<BITS>, dim3( grid_for( q.n ) ), dim3(256), s, f, r, q, (uint32_t)total, params->min_intv, T.cand, T.cnt,
+                           T.misc, rec );
+    }, bad_symbol_bits ) );
     NVB_CHECK( scan_u32( T.cnt, T.off, q.n, T, s ) );
     uint32_t n_cand = 0, err = 0;
     NVB_CHECK( read_u32( T.off + q.n, &n_cand, s ) );
@@ -537,20 +497,15 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
 
     auto left = [&](uint4* mems, uint32_t n) -> nvbio_status {
         if (n == 0) return NVBIO_OK;
-        (void)with_value( SymbolBits(), bits, [&](auto BITS)
+        return with_value( SymbolBits(), bits, [&](auto BITS)
         {
-            hipLaunchKernelGGL( mem_left_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), 0, s, f, q, mems, n, params->min_intv, rec );
-            return true;
-        }, [] { return false; } );
-        NVB_HIP( hipGetLastError() );
-        return NVBIO_OK;
+            return NVB_LAUNCH( mem_left_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), s, f, q, mems, n, params->min_intv, rec );
+        }, bad_symbol_bits );
     };
-    hipLaunchKernelGGL( mem_gather_kernel, dim3( grid_for( q.n ) ), dim3(256), 0, s, q, (const uint4*)T.cand, T.cnt, T.off, T.dense );
-    NVB_HIP( hipGetLastError() );
+    NVB_CHECK( NVB_LAUNCH( mem_gather_kernel, dim3( grid_for( q.n ) ), dim3(256), s, q, (const uint4*)T.cand, T.cnt, T.off, T.dense ) );
     NVB_CHECK( left( T.dense, n_cand ) );
-    hipLaunchKernelGGL( mem_discard_kernel, dim3( grid_for( q.n ) ), dim3(256), 0, s, q.n, (const uint32_t*)T.off, (const uint32_t*)nullptr,
-                        T.dense, params->max_intv, params->min_span, T.kept );
-    NVB_HIP( hipGetLastError() );
+    NVB_CHECK( NVB_LAUNCH( mem_discard_kernel, dim3( grid_for( q.n ) ), dim3(256), s, q.n, (const uint32_t*)T.off, (const uint32_t*)nullptr,
+                           T.dense, params->max_intv, params->min_span, T.kept ) );
 
     const uint4* final_mems = T.dense;
     const uint32_t* final_soff = nullptr;
@@ -558,26 +513,22 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
     {
         // count (COUNT = true: no arena, no soff), then write into the arena of arena_cap entries
         auto split = [&](auto COUNT, uint4* arena_p, const uint32_t* soff, uint32_t arena_cap) {
-            (void)with_value( SymbolBits(), bits, [&](auto BITS)
+            return with_value( SymbolBits(), bits, [&](auto BITS)
             {
-                hipLaunchKernelGGL( (mem_split_kernel<BITS, COUNT>), dim3( grid_for( n_cand ) ), dim3(256), 0, s, f, r, q, (const uint4*)T.dense, n_cand,
-                                    (const uint32_t*)T.off, (const uint32_t*)T.kept, params->split_len, params->split_width, T.scnt, soff, arena_p,
-                                    arena_cap, T.misc, rec );
-                return true;
-            }, [] { return false; } );
+                return NVB_LAUNCH( (mem_split_kernel<BITS, COUNT>), dim3( grid_for( n_cand ) ), dim3(256), s, f, r, q, (const uint4*)T.dense, n_cand,
+                                   (const uint32_t*)T.off, (const uint32_t*)T.kept, params->split_len, params->split_width, T.scnt, soff, arena_p,
+                                   arena_cap, T.misc, rec );
+            }, bad_symbol_bits );
         };
-        split( std::true_type(), (uint4*)nullptr, (const uint32_t*)nullptr, 0u );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( split( std::true_type(), (uint4*)nullptr, (const uint32_t*)nullptr, 0u ) );
         NVB_CHECK( scan_u32( T.scnt, T.soff, n_cand, T, s ) );
         uint32_t n_split = 0;
         NVB_CHECK( read_u32( T.soff + n_cand, &n_split, s ) );
         if (n_split > total) NVB_CHECK( take_arena( n_split ) );     // the split arena is the candidate region: a larger one moves the hipcub temporaries
-        split( std::false_type(), T.cand, (const uint32_t*)T.soff, n_split > total ? n_split : (uint32_t)total );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( split( std::false_type(), T.cand, (const uint32_t*)T.soff, n_split > total ? n_split : (uint32_t)total ) );
         NVB_CHECK( left( T.cand, n_split ) );
-        hipLaunchKernelGGL( mem_discard_kernel, dim3( grid_for( q.n ) ), dim3(256), 0, s, q.n, (const uint32_t*)T.off, (const uint32_t*)T.soff,
-                            T.cand, params->max_intv, params->min_span, T.kept );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( NVB_LAUNCH( mem_discard_kernel, dim3( grid_for( q.n ) ), dim3(256), s, q.n, (const uint32_t*)T.off, (const uint32_t*)T.soff,
+                               T.cand, params->max_intv, params->min_span, T.kept ) );
         NVB_CHECK( read_u32( T.misc, &err, s ) );
         if (err & MEM_ERR_BOUND) { set_error( "MEM filter: internal bound violated in the split pass" ); return NVBIO_ERR_HIP; }
         final_mems = T.cand; final_soff = T.soff;
@@ -598,10 +549,9 @@ nvbio_status nvbio_mem_filter_rank(nvbio_fm_index_t f_index, nvbio_fm_index_t r_
     if (nr)
     {
         NVB_REQUIRE( ranges_dev && slots_dev, "NULL device pointer" );
-        hipLaunchKernelGGL( mem_output_kernel, dim3( grid_for( q.n ) ), dim3(256), 0, s, q.n, (const uint32_t*)T.off, final_soff, final_mems,
-                            (const uint32_t*)T.first_tmp, (uint4*)ranges_dev );
-        NVB_HIP( hipGetLastError() );
-        hipcub::TransformInputIterator<uint64_t, MemRangeSize, const uint4*> sizes( (const uint4*)ranges_dev, MemRangeSize() );
+        NVB_CHECK( NVB_LAUNCH( mem_output_kernel, dim3( grid_for( q.n ) ), dim3(256), s, q.n, (const uint32_t*)T.off, final_soff, final_mems,
+                               (const uint32_t*)T.first_tmp, (uint4*)ranges_dev ) );
+        hipcub::TransformInputIterator<uint64_t, RangeSize, const uint4*> sizes( (const uint4*)ranges_dev, RangeSize() );
         size_t bytes = T.cub_bytes;
         NVB_HIP( hipcub::DeviceScan::InclusiveSum( T.cub, bytes, sizes, slots_dev, (int)nr, s ) );
         NVB_HIP( hipMemcpyAsync( n_mems, slots_dev + (nr - 1u), 8, hipMemcpyDeviceToHost, s ) );
@@ -627,10 +577,8 @@ nvbio_status nvbio_mem_filter_locate(nvbio_fm_index_t f_index, const nvbio_mem_r
     NVB_HIP( hipMemcpyAsync( &n_mems, slots_dev + (n_ranges - 1u), 8, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
     NVB_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
     NVB_REQUIRE( end <= n_mems, "end is past the last MEM (slots[n_ranges - 1])" );
-    hipLaunchKernelGGL( mem_locate_kernel, dim3( grid_for( (end - begin + MEM_LOCATE_TILE - 1u) / MEM_LOCATE_TILE * 256u ) ), dim3(256), 0,
-                        (hipStream_t)stream, f, (const uint4*)ranges_dev, slots_dev, n_ranges, begin, end, (uint4*)hits_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( mem_locate_kernel, dim3( expand_grid( begin, end ) ), dim3(256),
+                       (hipStream_t)stream, f, (const uint4*)ranges_dev, slots_dev, n_ranges, begin, end, (uint4*)hits_dev );
 }
 
 } // extern "C"

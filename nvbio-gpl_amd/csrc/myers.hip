@@ -99,8 +99,6 @@ extern "C" nvbio_status nvbio_banded_myers_score(int device, uint32_t band, nvbi
     const uint32_t rb = batch->read_bits, tbits = batch->text_bits;
     return with_bits( BitsBest2(), rb, tbits, [&](auto P)
     {
-        hipLaunchKernelGGL( (banded_myers_kernel<P.r,P.t>), grid, block, 0, s, b, band, (int)type, min_score, scores_dev, (uint2*)sinks_dev );
-        NVB_HIP( hipGetLastError() );
-        return NVBIO_OK;
+        return NVB_LAUNCH( (banded_myers_kernel<P.r,P.t>), grid, block, s, b, band, (int)type, min_score, scores_dev, (uint2*)sinks_dev );
     }, [&] { set_error( "unsupported read_bits / text_bits combination %u / %u", rb, tbits ); return NVBIO_ERR_UNSUPPORTED; } );
 }

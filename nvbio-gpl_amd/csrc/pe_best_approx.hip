@@ -320,10 +320,8 @@ nvbio_status nvbio_pe_init(int device, uint32_t n_reads, int32_t worst_score_mat
     if (n_reads == 0) return NVBIO_OK;
     NVB_REQUIRE( best_a_dev && best_o_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( pe_init_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream, n_reads, worst_score_mate1, worst_score_mate2,
-                        (PeAln*)best_a_dev, (PeAln*)best_o_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( pe_init_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, n_reads, worst_score_mate1, worst_score_mate2,
+                       (PeAln*)best_a_dev, (PeAln*)best_o_dev );
 }
 
 nvbio_status nvbio_pe_anchor_flatten(int device, const nvbio_pe_params* params, const nvbio_hit_queues* hits, const int32_t* best_a_dev, const int32_t* best_o_dev,
@@ -335,11 +333,9 @@ nvbio_status nvbio_pe_anchor_flatten(int device, const nvbio_pe_params* params, 
     NVB_REQUIRE( hits->hit_read_id_dev && hits->hit_seed_dev && hits->hit_loc_dev && best_a_dev && best_o_dev && read_id_dev && flags_dev && win_begin_dev &&
                  win_end_dev && min_scores_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( pe_anchor_flatten_kernel, dim3( grid_for( hits->n ) ), dim3(256), 0, (hipStream_t)stream, pe_params( params ), hits->n, hits->hit_read_id_dev,
-                        hits->hit_seed_dev, hits->hit_loc_dev, (const PeAln*)best_a_dev, (const PeAln*)best_o_dev, read_id_dev, flags_dev, win_begin_dev,
-                        win_end_dev, min_scores_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( pe_anchor_flatten_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, pe_params( params ), hits->n, hits->hit_read_id_dev,
+                       hits->hit_seed_dev, hits->hit_loc_dev, (const PeAln*)best_a_dev, (const PeAln*)best_o_dev, read_id_dev, flags_dev, win_begin_dev,
+                       win_end_dev, min_scores_dev );
 }
 
 nvbio_status nvbio_pe_anchor_output(int device, const nvbio_pe_params* params, const nvbio_hit_queues* hits, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
@@ -351,10 +347,8 @@ nvbio_status nvbio_pe_anchor_output(int device, const nvbio_pe_params* params, c
     NVB_REQUIRE( hits->hit_score_dev && hits->hit_sink_dev && scores_dev && sinks_dev && win_begin_dev && min_scores_dev && hit_opposite_score_dev && valid_dev,
                  "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( pe_anchor_output_kernel, dim3( grid_for( hits->n ) ), dim3(256), 0, (hipStream_t)stream, hits->n, scores_dev, (const uint2*)sinks_dev,
-                        win_begin_dev, min_scores_dev, params->worst_score, hits->hit_score_dev, hits->hit_sink_dev, hit_opposite_score_dev, valid_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( pe_anchor_output_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, hits->n, scores_dev, (const uint2*)sinks_dev,
+                       win_begin_dev, min_scores_dev, params->worst_score, hits->hit_score_dev, hits->hit_sink_dev, hit_opposite_score_dev, valid_dev );
 }
 
 nvbio_status nvbio_pe_opposite_flatten(int device, const nvbio_pe_params* params, const uint32_t* queue_dev, uint32_t n, const nvbio_hit_queues* hits,
@@ -366,11 +360,9 @@ nvbio_status nvbio_pe_opposite_flatten(int device, const nvbio_pe_params* params
     NVB_REQUIRE( queue_dev && hits->hit_read_id_dev && hits->hit_seed_dev && hits->hit_loc_dev && hits->hit_score_dev && best_a_dev && best_o_dev && read_id_dev &&
                  flags_dev && win_begin_dev && win_end_dev && min_scores_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( pe_opposite_flatten_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, pe_params( params ), queue_dev, n, hits->hit_read_id_dev,
-                        hits->hit_seed_dev, hits->hit_loc_dev, hits->hit_score_dev, (const PeAln*)best_a_dev, (const PeAln*)best_o_dev, read_id_dev, flags_dev,
-                        win_begin_dev, win_end_dev, min_scores_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( pe_opposite_flatten_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, pe_params( params ), queue_dev, n, hits->hit_read_id_dev,
+                       hits->hit_seed_dev, hits->hit_loc_dev, hits->hit_score_dev, (const PeAln*)best_a_dev, (const PeAln*)best_o_dev, read_id_dev, flags_dev,
+                       win_begin_dev, win_end_dev, min_scores_dev );
 }
 
 nvbio_status nvbio_pe_opposite_output(int device, const nvbio_pe_params* params, const uint32_t* queue_dev, uint32_t n, const int32_t* scores_dev,
@@ -382,10 +374,8 @@ nvbio_status nvbio_pe_opposite_output(int device, const nvbio_pe_params* params,
     NVB_REQUIRE( queue_dev && scores_dev && sinks_dev && win_begin_dev && win_end_dev && min_scores_dev && hit_opposite_score_dev && hit_opposite_loc_dev &&
                  hit_opposite_sink_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( pe_opposite_output_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, queue_dev, n, scores_dev, (const uint2*)sinks_dev,
-                        win_begin_dev, win_end_dev, min_scores_dev, params->worst_score, hit_opposite_score_dev, hit_opposite_loc_dev, hit_opposite_sink_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( pe_opposite_output_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, queue_dev, n, scores_dev, (const uint2*)sinks_dev,
+                       win_begin_dev, win_end_dev, min_scores_dev, params->worst_score, hit_opposite_score_dev, hit_opposite_loc_dev, hit_opposite_sink_dev );
 }
 
 nvbio_status nvbio_pe_score_reduce(int device, const nvbio_pe_params* params, const uint32_t* active_dev, uint32_t n_active, const uint32_t* hits_first_dev,
@@ -398,11 +388,9 @@ nvbio_status nvbio_pe_score_reduce(int device, const nvbio_pe_params* params, co
     NVB_REQUIRE( active_dev && hits_first_dev && hits_count_dev && hits->hit_seed_dev && hits->hit_loc_dev && hits->hit_sink_dev && hits->hit_score_dev &&
                  hit_opposite_score_dev && hit_opposite_loc_dev && hit_opposite_sink_dev && best_a_dev && best_o_dev && trys_dev && sizes_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( pe_reduce_kernel, dim3( grid_for( n_active ) ), dim3(256), 0, (hipStream_t)stream, pe_params( params ), active_dev, n_active, hits_first_dev,
-                        hits_count_dev, hits->hit_seed_dev, hits->hit_loc_dev, hits->hit_sink_dev, hits->hit_score_dev, hit_opposite_score_dev,
-                        hit_opposite_loc_dev, hit_opposite_sink_dev, n_ext, (PeAln*)best_a_dev, (PeAln*)best_o_dev, trys_dev, sizes_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( pe_reduce_kernel, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, pe_params( params ), active_dev, n_active, hits_first_dev,
+                       hits_count_dev, hits->hit_seed_dev, hits->hit_loc_dev, hits->hit_sink_dev, hits->hit_score_dev, hit_opposite_score_dev,
+                       hit_opposite_loc_dev, hit_opposite_sink_dev, n_ext, (PeAln*)best_a_dev, (PeAln*)best_o_dev, trys_dev, sizes_dev );
 }
 
 } // extern "C"

@@ -46,14 +46,14 @@
 // and at a 100 Mbp string index about six, so the search is one to three steps and a wave-cooperative 64-ary search would spend 64
 // lanes on what one lane finishes in as many dependent loads; one lane per query it is.  qmap feeds its queries sorted, so
 // neighbouring lanes hit neighbouring buckets.  (At 3 Gbp, ~180 entries per bucket, the lane does ~8 steps; not measured.)
-// Locate: one lane per output, as the reference, but a workgroup first bounds the queries its 2,048 consecutive outputs belong to
-// (two upper_bounds), so each output's own upper_bound runs over a few cached entries; a 10^4-copy repeat is spread over 10^4 lanes.
+// Locate: one lane per output, as the reference, through the expansion the three filters share (range_expand.h): a workgroup first
+// bounds the queries its 2,048 consecutive outputs belong to, so each output's own upper_bound runs over a few cached entries.
 // Extraction, seed enumeration, LUT build and the diagonal snap are one lane per item.  No private arrays; sorting, scans and
 // run-length encoding are rocPRIM.  Working storage: the index builds take BuildBuffers (their arrays are handed to the handle),
 // generate_qgrams (sorted), rank and merge a ScratchBlock on the caller's temp.
-// Registers (gfx950 code object, -Rpass-analysis=kernel-resource-usage): VGPRs extract 14-16, seed count 8, seed enumerate 22-24,
+// Registers (gfx950 code object, -Rpass-analysis=kernel-resource-usage): VGPRs extract 14-16, seed count 8, seed enumerate 26-28,
 // LUT 11, range 11, locate 20, diagonal 9-10; private_segment_fixed_size = 0 (no scratch) for every one.
-#include "common.h"
+#include "range_expand.h"
 #include <rocprim/rocprim.hpp>
 
 struct nvbio_qgram_index_s
@@ -110,27 +110,6 @@ __device__ __forceinline__ uint64_t qgram_at(SymbolReader<BITS>& rd, const uint6
     return g;
 }
 
-// first i in [lo, hi) with a[i] > v (hi if none)
-__device__ __forceinline__ uint32_t qg_upper_bound(const uint64_t* __restrict__ a, uint32_t lo, uint32_t hi, const uint64_t v)
-{
-    while (lo < hi)
-    {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-// first i in [lo, hi) with a[i] >= v (hi if none)
-__device__ __forceinline__ uint32_t qg_lower_bound(const uint64_t* __restrict__ a, uint32_t lo, uint32_t hi, const uint64_t v)
-{
-    while (lo < hi)
-    {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-
 // qgrams[i] = the q-gram at text position first + i (padded past len), pos[i] = first + i (pos may be NULL)
 template <int BITS>
 __global__ void __launch_bounds__(256)
@@ -158,30 +137,24 @@ qgram_seed_count_kernel(const QGramSet s, const uint32_t q, const uint32_t inter
     }
 }
 
-// seed k of the set (first[i] = exclusive scan of the seed counts, n + 1 entries): its coordinate and q-gram.  A workgroup bounds
-// the strings of its 256 consecutive seeds once, so that each seed's own search runs over a few cached entries.
+// seed k of the set (first[i] = exclusive scan of the seed counts, n + 1 entries): its coordinate and q-gram.  The shared expansion
+// (range_expand.h) over tiles of 256 seeds: read as an inclusive scan, `first` has the empty range 0 in front of the strings' seeds,
+// so seed k falls into range sid + 1 and `base` is first[sid].
 template <int BITS>
 __global__ void __launch_bounds__(256)
 qgram_seed_enumerate_kernel(const QGramSet s, const uint32_t q, const uint32_t ss, const uint32_t interval, const uint64_t* __restrict__ first,
                             const uint32_t n_seeds, uint64_t* __restrict__ qgrams, uint2* __restrict__ coords)
 {
-    __shared__ uint32_t s_b[2];
-    for (uint32_t base = blockIdx.x * blockDim.x; base < n_seeds; base += gridDim.x * blockDim.x)
+    expand_ranges<256u>( first, s.n + 1u, 0u, n_seeds, [&](const uint64_t k, const uint32_t i, const uint64_t base)
     {
-        const uint32_t last = base + blockDim.x - 1u < n_seeds ? base + blockDim.x - 1u : n_seeds - 1u;
-        __syncthreads();
-        if (threadIdx.x < 2) s_b[threadIdx.x] = qg_upper_bound( first, 0u, s.n + 1u, threadIdx.x ? last : base );
-        __syncthreads();
-        const uint32_t k = base + threadIdx.x;
-        if (k > last) continue;
-        const uint32_t sid = qg_upper_bound( first, s_b[0], s_b[1] + 1u < s.n + 1u ? s_b[1] + 1u : s.n + 1u, k ) - 1u;
-        const uint32_t pos = (uint32_t)(k - first[sid]) * interval;
+        const uint32_t sid = i - 1u;
+        const uint32_t pos = (uint32_t)(k - base) * interval;
         uint32_t begin, len;
         s.bounds( sid, begin, len );
         SymbolReader<BITS> rd( s.symbols );
         qgrams[k] = qgram_at<BITS>( rd, begin, len, pos, q, ss );
         coords[k] = make_uint2( sid, pos );
-    }
+    } );
 }
 
 // lut[k] = lower_bound( qgrams, k << qls ) for k < lut_size, lut[lut_size] = n_unique
@@ -189,7 +162,7 @@ __global__ void __launch_bounds__(256)
 qgram_lut_kernel(const uint64_t* __restrict__ qgrams, const uint32_t n_unique, const uint32_t qls, const uint64_t lut_size, uint32_t* __restrict__ lut)
 {
     for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k <= lut_size; k += (uint64_t)gridDim.x * blockDim.x)
-        lut[k] = k < lut_size ? qg_lower_bound( qgrams, 0u, n_unique, k << qls ) : n_unique;
+        lut[k] = k < lut_size ? lower_bound_u64( qgrams, 0u, n_unique, k << qls ) : n_unique;
 }
 
 // range( g ) (qgram.h:451-475): half-open slots of g, (0, 0) on a miss
@@ -202,7 +175,7 @@ __device__ __forceinline__ uint2 qgram_range(const QGramView& v, const uint64_t 
         if (k >= v.lut_size) return make_uint2( 0u, 0u );
         lo = v.lut[k]; hi = v.lut[k + 1u];
     }
-    const uint32_t i = qg_lower_bound( v.qgrams, lo, hi, g );
+    const uint32_t i = lower_bound_u64( v.qgrams, lo, hi, g );
     if (i >= v.n_unique || v.qgrams[i] != g) return make_uint2( 0u, 0u );
     return make_uint2( v.slots[i], v.slots[i + 1u] );
 }
@@ -219,38 +192,23 @@ struct QGramRangeSize
     __host__ __device__ __forceinline__ uint64_t operator()(const uint2 r) const { return (uint64_t)(r.y - r.x); }
 };
 
-// locate (filter_results, filter_inl.h:88-190): hits[o - begin] for the outputs o in [begin, end).  A workgroup owns QGRAM_LOCATE_TILE
-// consecutive outputs and bounds their queries once.
-constexpr uint32_t QGRAM_LOCATE_TILE = 256u * 8u;
-
+// locate (filter_results, filter_inl.h:88-190): hits[o - begin] for the outputs o in [begin, end), over the shared expansion
+// (expand_ranges, range_expand.h)
 template <bool SET>
 __global__ void __launch_bounds__(256)
 qgram_locate_kernel(const void* __restrict__ index, const uint2* __restrict__ ranges, const uint64_t* __restrict__ slots,
                     const uint32_t* __restrict__ indices, const uint32_t n, const uint64_t begin, const uint64_t end, void* __restrict__ hits)
 {
-    __shared__ uint32_t s_q[2];
-    const uint64_t n_tiles = (end - begin + QGRAM_LOCATE_TILE - 1u) / QGRAM_LOCATE_TILE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+    expand_ranges( slots, n, begin, end, [&](const uint64_t o, const uint32_t i, const uint64_t base)
     {
-        const uint64_t t_first = begin + tile * QGRAM_LOCATE_TILE;
-        const uint64_t t_end   = (t_first + QGRAM_LOCATE_TILE < end) ? t_first + QGRAM_LOCATE_TILE : end;
-        __syncthreads();
-        if (threadIdx.x < 2) s_q[threadIdx.x] = qg_upper_bound( slots, 0u, n, threadIdx.x ? t_end - 1u : t_first );
-        __syncthreads();
-        const uint32_t q_lo = s_q[0], q_hi = s_q[1] + 1u < n ? s_q[1] + 1u : n;
-        for (uint64_t o = t_first + threadIdx.x; o < t_end; o += blockDim.x)
+        const uint64_t at = (uint64_t)ranges[i].x + (o - base);
+        if (SET)
         {
-            const uint32_t i = qg_upper_bound( slots, q_lo, q_hi, o );
-            const uint64_t base = i ? slots[i - 1u] : 0ull;
-            const uint64_t at = (uint64_t)ranges[i].x + (o - base);
-            if (SET)
-            {
-                const uint2 c = ((const uint2*)index)[at];
-                ((uint4*)hits)[o - begin] = make_uint4( c.x, c.y, indices[i], 0u );
-            }
-            else ((uint2*)hits)[o - begin] = make_uint2( ((const uint32_t*)index)[at], indices[i] );
+            const uint2 c = ((const uint2*)index)[at];
+            ((uint4*)hits)[o - begin] = make_uint4( c.x, c.y, indices[i], 0u );
         }
-    }
+        else ((uint2*)hits)[o - begin] = make_uint2( ((const uint32_t*)index)[at], indices[i] );
+    } );
 }
 
 // the closest multiple of `interval` to d, ties down, mod 2^32 (see "Departures": rounding)
@@ -346,9 +304,8 @@ static nvbio_status finish_index(BuildBuffers& bufs, const int device, const uin
         lut_size = 1ull << (qlut * ss);
         lut = bufs.alloc<uint32_t>( lut_size + 1u );
         if (!lut) { set_error( "q-gram index build: out of device memory (lut, %llu bytes)", (unsigned long long)(4u * (lut_size + 1u)) ); return NVBIO_ERR_NOMEM; }
-        hipLaunchKernelGGL( qgram_lut_kernel, dim3( grid_for( lut_size + 1u ) ), dim3(256), 0, s, (const uint64_t*)qgrams, (uint32_t)n_unique, qls,
-                            lut_size, lut );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( NVB_LAUNCH( qgram_lut_kernel, dim3( grid_for( lut_size + 1u ) ), dim3(256), s, (const uint64_t*)qgrams, (uint32_t)n_unique, qls,
+                               lut_size, lut ) );
     }
     NVB_HIP( hipStreamSynchronize( s ) );
     nvbio_qgram_index_s* h = new (std::nothrow) nvbio_qgram_index_s();
@@ -438,13 +395,11 @@ nvbio_status nvbio_qgram_index_build(int device, const void* text_dev, uint32_t 
     NVB_ALLOC( pos, uint32_t, length );
     if (length)
     {
-        (void)with_value( SymbolBits(), text_bits, [&](auto BITS)
+        NVB_CHECK( with_value( SymbolBits(), text_bits, [&](auto BITS)
         {
-            hipLaunchKernelGGL( qgram_extract_kernel<BITS>, dim3( grid_for( length ) ), dim3(256), 0, s, text_dev, length, q, symbol_size, 0u,
-                                length, keys, pos );
-            return true;
-        }, [] { return false; } );
-        NVB_HIP( hipGetLastError() );
+            return NVB_LAUNCH( qgram_extract_kernel<BITS>, dim3( grid_for( length ) ), dim3(256), s, text_dev, length, q, symbol_size, 0u,
+                               length, keys, pos );
+        }, bad_symbol_bits ) );
     }
     return finish_index<uint32_t>( bufs, device, q, symbol_size, qlut, 0u, length, keys, pos, s, out );
 }
@@ -471,8 +426,7 @@ nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set
     NVB_HIP( hipMemsetAsync( first, 0, 8, s ) );
     if (set->n)
     {
-        hipLaunchKernelGGL( qgram_seed_count_kernel, dim3( grid_for( set->n ) ), dim3(256), 0, s, qs, q, seed_interval, cnt );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( NVB_LAUNCH( qgram_seed_count_kernel, dim3( grid_for( set->n ) ), dim3(256), s, qs, q, seed_interval, cnt ) );
         size_t a = 0;
         NVB_HIP( rocprim::inclusive_scan( nullptr, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
         NVB_ALLOC( temp, uint8_t, a );
@@ -488,13 +442,11 @@ nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set
     NVB_ALLOC( coords, uint64_t, n );
     if (n)
     {
-        (void)with_value( SymbolBits(), set->symbol_bits, [&](auto BITS)
+        NVB_CHECK( with_value( SymbolBits(), set->symbol_bits, [&](auto BITS)
         {
-            hipLaunchKernelGGL( qgram_seed_enumerate_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), 0, s, qs, q, symbol_size, seed_interval,
-                                (const uint64_t*)first, n, keys, (uint2*)coords );
-            return true;
-        }, [] { return false; } );
-        NVB_HIP( hipGetLastError() );
+            return NVB_LAUNCH( qgram_seed_enumerate_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), s, qs, q, symbol_size, seed_interval,
+                               (const uint64_t*)first, n, keys, (uint2*)coords );
+        }, bad_symbol_bits ) );
     }
     NVB_HIP( hipStreamSynchronize( s ) );
     bufs.release( first );
@@ -575,13 +527,11 @@ nvbio_status nvbio_generate_qgrams(int device, uint32_t q, uint32_t symbol_size,
                                       temp_dev, temp_bytes, "nvbio_generate_qgrams_temp_bytes" ) );
         keys = T.keys; pos = T.pos;
     }
-    (void)with_value( SymbolBits(), text_bits, [&](auto BITS)
+    NVB_CHECK( with_value( SymbolBits(), text_bits, [&](auto BITS)
     {
-        hipLaunchKernelGGL( qgram_extract_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), 0, s, text_dev, text_len, q, symbol_size, first_pos, n,
-                            keys, pos );
-        return true;
-    }, [] { return false; } );
-    NVB_HIP( hipGetLastError() );
+        return NVB_LAUNCH( qgram_extract_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), s, text_dev, text_len, q, symbol_size, first_pos, n,
+                           keys, pos );
+    }, bad_symbol_bits ) );
     if (sort)
     {
         size_t bytes = T.cub_bytes;
@@ -596,10 +546,8 @@ nvbio_status nvbio_qgram_ranges(nvbio_qgram_index_t index, const uint64_t* qgram
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( qgrams_dev && ranges_dev, "NULL device pointer" );
     DeviceGuard g( index->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, view_of( index ), qgrams_dev, n,
-                        (uint2*)ranges_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, view_of( index ), qgrams_dev, n,
+                       (uint2*)ranges_dev );
 }
 
 nvbio_status nvbio_qgram_filter_temp_bytes(uint32_t n_queries, uint64_t* bytes)
@@ -624,8 +572,7 @@ nvbio_status nvbio_qgram_filter_rank(nvbio_qgram_index_t index, const uint64_t* 
     ScratchBlock temp;
     NVB_CHECK( temp.alloc_layout( "qgram_filter_rank", s, "q-gram filter rank: out of device memory", [&](ScratchLayout& c) { cub = c.take<uint8_t>( cub_bytes ); },
                                   temp_dev, temp_bytes, "nvbio_qgram_filter_temp_bytes" ) );
-    hipLaunchKernelGGL( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), 0, s, view_of( index ), qgrams_dev, n, (uint2*)ranges_dev );
-    NVB_HIP( hipGetLastError() );
+    NVB_CHECK( NVB_LAUNCH( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), s, view_of( index ), qgrams_dev, n, (uint2*)ranges_dev ) );
     rocprim::transform_iterator<const uint2*, QGramRangeSize, uint64_t> sizes( (const uint2*)ranges_dev, QGramRangeSize() );
     size_t bytes = cub_bytes;
     NVB_HIP( rocprim::inclusive_scan( cub, bytes, sizes, slots_dev, (size_t)n, rocprim::plus<uint64_t>(), s ) );
@@ -647,12 +594,11 @@ nvbio_status nvbio_qgram_filter_locate(nvbio_qgram_index_t index, const nvbio_ui
     NVB_HIP( hipMemcpyAsync( &n_hits, slots_dev + (n - 1u), 8, hipMemcpyDeviceToHost, s ) );
     NVB_HIP( hipStreamSynchronize( s ) );
     NVB_REQUIRE( end <= n_hits, "end is past the last hit (slots[n - 1])" );
-    const dim3 grid( grid_for( (end - begin + QGRAM_LOCATE_TILE - 1u) / QGRAM_LOCATE_TILE * 256u ) ), block( 256 );
-    if (index->is_set) hipLaunchKernelGGL( qgram_locate_kernel<true>, grid, block, 0, s, (const void*)index->index, (const uint2*)ranges_dev,
-                                           slots_dev, indices_dev, n, begin, end, hits_dev );
-    else               hipLaunchKernelGGL( qgram_locate_kernel<false>, grid, block, 0, s, (const void*)index->index, (const uint2*)ranges_dev,
-                                           slots_dev, indices_dev, n, begin, end, hits_dev );
-    NVB_HIP( hipGetLastError() );
+    const dim3 grid( expand_grid( begin, end ) ), block( 256 );
+    if (index->is_set) NVB_CHECK( NVB_LAUNCH( qgram_locate_kernel<true>, grid, block, s, (const void*)index->index, (const uint2*)ranges_dev,
+                                              slots_dev, indices_dev, n, begin, end, hits_dev ) );
+    else               NVB_CHECK( NVB_LAUNCH( qgram_locate_kernel<false>, grid, block, s, (const void*)index->index, (const uint2*)ranges_dev,
+                                              slots_dev, indices_dev, n, begin, end, hits_dev ) );
     return NVBIO_OK;
 }
 
@@ -683,15 +629,13 @@ nvbio_status nvbio_qgram_filter_merge(int device, int is_set, uint32_t interval,
     size_t a = T.cub_bytes, b = T.cub_bytes;
     if (set)
     {
-        hipLaunchKernelGGL( qgram_diagonal_kernel<true>, grid, block, 0, s, hits_dev, n_hits, interval, T.keys );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( NVB_LAUNCH( qgram_diagonal_kernel<true>, grid, block, s, hits_dev, n_hits, interval, T.keys ) );
         NVB_HIP( rocprim::radix_sort_keys( T.cub, a, (const uint64_t*)T.keys, (uint64_t*)T.sorted, (size_t)n_hits, 0u, 64u, s ) );
         NVB_HIP( rocprim::run_length_encode( T.cub, b, (const uint64_t*)T.sorted, (size_t)n_hits, (uint64_t*)merged_dev, counts_dev, T.runs, s ) );
     }
     else
     {
-        hipLaunchKernelGGL( qgram_diagonal_kernel<false>, grid, block, 0, s, hits_dev, n_hits, interval, T.keys );
-        NVB_HIP( hipGetLastError() );
+        NVB_CHECK( NVB_LAUNCH( qgram_diagonal_kernel<false>, grid, block, s, hits_dev, n_hits, interval, T.keys ) );
         NVB_HIP( rocprim::radix_sort_keys( T.cub, a, (const uint32_t*)T.keys, (uint32_t*)T.sorted, (size_t)n_hits, 0u, 32u, s ) );
         NVB_HIP( rocprim::run_length_encode( T.cub, b, (const uint32_t*)T.sorted, (size_t)n_hits, (uint32_t*)merged_dev, counts_dev, T.runs, s ) );
     }

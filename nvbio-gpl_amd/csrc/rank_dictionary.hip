@@ -134,9 +134,9 @@ nvbio_status nvbio_rank_dictionary_build(int device, const nvbio_rank_dictionary
     ScratchBlock aux;
     NVB_CHECK( aux.alloc_layout( "rank_dictionary_build", s, "rank_dictionary_build: out of device memory", [&](ScratchLayout& c)
                                  { cnt = c.take<uint32_t>( 4ull * nb ); sums = c.take<uint64_t>( 4ull * nb ); temp = c.take<uint8_t>( temp_bytes ); } ) );
-    if (dict->word_bits == 32) hipLaunchKernelGGL( block_symbol_counts_kernel<uint32_t>, dim3( grid_for( nb ) ), dim3(256), 0, s, (const uint32_t*)dict->text_dev, dict->length, dict->K, nb, cnt );
-    else                       hipLaunchKernelGGL( block_symbol_counts_kernel<uint64_t>, dim3( grid_for( nb ) ), dim3(256), 0, s, (const uint64_t*)dict->text_dev, dict->length, dict->K, nb, cnt );
-    hipError_t e = hipGetLastError();
+    if (dict->word_bits == 32) NVB_CHECK( NVB_LAUNCH( block_symbol_counts_kernel<uint32_t>, dim3( grid_for( nb ) ), dim3(256), s, (const uint32_t*)dict->text_dev, dict->length, dict->K, nb, cnt ) );
+    else                       NVB_CHECK( NVB_LAUNCH( block_symbol_counts_kernel<uint64_t>, dim3( grid_for( nb ) ), dim3(256), s, (const uint64_t*)dict->text_dev, dict->length, dict->K, nb, cnt ) );
+    hipError_t e = hipSuccess;
     for (uint32_t c = 0; c < 4u && e == hipSuccess; ++c)
     {
         hipcub::TransformInputIterator<uint64_t, U32toU64, const uint32_t*> in( (const uint32_t*)cnt + c * nb, U32toU64() );
@@ -144,9 +144,8 @@ nvbio_status nvbio_rank_dictionary_build(int device, const nvbio_rank_dictionary
     }
     if (e == hipSuccess)
     {
-        if (dict->index_bits == 32) hipLaunchKernelGGL( interleave_occ_kernel<uint32_t>, dim3( grid_for( nb ) ), dim3(256), 0, s, (const uint64_t*)sums, nb, (uint32_t*)occ_out_dev );
-        else                        hipLaunchKernelGGL( interleave_occ_kernel<uint64_t>, dim3( grid_for( nb ) ), dim3(256), 0, s, (const uint64_t*)sums, nb, (uint64_t*)occ_out_dev );
-        e = hipGetLastError();
+        if (dict->index_bits == 32) NVB_CHECK( NVB_LAUNCH( interleave_occ_kernel<uint32_t>, dim3( grid_for( nb ) ), dim3(256), s, (const uint64_t*)sums, nb, (uint32_t*)occ_out_dev ) );
+        else                        NVB_CHECK( NVB_LAUNCH( interleave_occ_kernel<uint64_t>, dim3( grid_for( nb ) ), dim3(256), s, (const uint64_t*)sums, nb, (uint64_t*)occ_out_dev ) );
     }
     // totals = the last block's exclusive sum + its own counts
     uint64_t last_sum[4] = { 0, 0, 0, 0 }; uint32_t last_cnt[4] = { 0, 0, 0, 0 };
@@ -169,14 +168,13 @@ static nvbio_status rank_common(int device, const nvbio_rank_dictionary* d, cons
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     const dim3 grid( grid_for( n ) ), block( 256 );
     hipStream_t s = (hipStream_t)stream;
-#define NVB_RK(W, I) do { if (all4) hipLaunchKernelGGL( (rank_generic_kernel<W,I,true>),  grid, block, 0, s, (const W*)d->text_dev, (const I*)d->occ_dev, d->K, (const I*)idx, sym, n, (I*)out ); \
-                          else      hipLaunchKernelGGL( (rank_generic_kernel<W,I,false>), grid, block, 0, s, (const W*)d->text_dev, (const I*)d->occ_dev, d->K, (const I*)idx, sym, n, (I*)out ); } while (0)
+#define NVB_RK(W, I) do { if (all4) NVB_CHECK( NVB_LAUNCH( (rank_generic_kernel<W,I,true>),  grid, block, s, (const W*)d->text_dev, (const I*)d->occ_dev, d->K, (const I*)idx, sym, n, (I*)out ) ); \
+                          else      NVB_CHECK( NVB_LAUNCH( (rank_generic_kernel<W,I,false>), grid, block, s, (const W*)d->text_dev, (const I*)d->occ_dev, d->K, (const I*)idx, sym, n, (I*)out ) ); } while (0)
     if      (d->word_bits == 32 && d->index_bits == 32) NVB_RK( uint32_t, uint32_t );
     else if (d->word_bits == 32)                        NVB_RK( uint32_t, uint64_t );
     else if (d->index_bits == 32)                       NVB_RK( uint64_t, uint32_t );
     else                                                NVB_RK( uint64_t, uint64_t );
 #undef NVB_RK
-    NVB_HIP( hipGetLastError() );
     return NVBIO_OK;
 }
 

@@ -29,7 +29,7 @@ hits_to_diagonals_kernel(const uint2* __restrict__ hits, const uint64_t n, const
 __global__ void __launch_bounds__(256)
 diagonals_to_windows_kernel(const uint64_t* __restrict__ keys, const uint64_t n, const uint32_t band, const uint32_t read_len_all,
                             const uint32_t genome_len, uint32_t* __restrict__ read_id, uint8_t* __restrict__ flags,
-                            uint32_t* __restrict__ wb, uint32_t* __restrict__ we, const uint32_t* __restrict__ read_offsets = nullptr)
+                            uint32_t* __restrict__ wb, uint32_t* __restrict__ we, const uint32_t* __restrict__ read_offsets)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
     {
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256)
 traceback_best_batch_kernel(const unsigned long long* __restrict__ best, const long long* __restrict__ best_wb, const uint32_t n,
                             const uint32_t read_len_all, const uint32_t band, const uint32_t genome_len, const int32_t min_score_all,
                             uint8_t* __restrict__ flags, uint32_t* __restrict__ wb, uint32_t* __restrict__ we, int32_t* __restrict__ scores,
-                            uint2* __restrict__ sinks, const uint32_t* __restrict__ read_offsets = nullptr, const int32_t* __restrict__ min_scores = nullptr)
+                            uint2* __restrict__ sinks, const uint32_t* __restrict__ read_offsets, const int32_t* __restrict__ min_scores)
 {
     for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x)
     {
@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(256)
 second_candidate_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ scores, const uint2* __restrict__ sinks,
                         const uint32_t* __restrict__ wb, const uint64_t n, const unsigned long long* __restrict__ best,
                         const uint32_t dist_all, const int32_t worst_score_all, unsigned long long* __restrict__ second,
-                        const uint32_t* __restrict__ read_offsets = nullptr, const int32_t* __restrict__ min_scores = nullptr)
+                        const uint32_t* __restrict__ read_offsets, const int32_t* __restrict__ min_scores)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride)       // wave-uniform bound
@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(256)
 mapq_kernel(const unsigned long long* __restrict__ best, const unsigned long long* __restrict__ second, const uint32_t n,
             const int version, const bool monotone, const float max_score_all, const float min_score_all,
             int32_t* __restrict__ second_score, uint8_t* __restrict__ mapq,
-            const uint32_t* __restrict__ read_offsets = nullptr, const int32_t* __restrict__ min_scores = nullptr, const int32_t match = 0)
+            const uint32_t* __restrict__ read_offsets, const int32_t* __restrict__ min_scores, const int32_t match)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
@@ -432,9 +432,7 @@ extern "C" nvbio_status nvbio_text_2bit_le_to_be(int device, const uint32_t* in_
     if (n_words == 0) return NVBIO_OK;
     NVB_REQUIRE( in_dev && out_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( text_le_to_be_kernel, dim3( grid_for( n_words ) ), dim3(256), 0, (hipStream_t)stream, in_dev, n_words, out_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( text_le_to_be_kernel, dim3( grid_for( n_words ) ), dim3(256), (hipStream_t)stream, in_dev, n_words, out_dev );
 }
 
 extern "C" nvbio_status nvbio_scores_to_int16(int device, const int32_t* scores_dev, uint32_t n, int16_t* out_dev, void* stream)
@@ -442,9 +440,7 @@ extern "C" nvbio_status nvbio_scores_to_int16(int device, const int32_t* scores_
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( scores_dev && out_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( scores_to_int16_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, scores_dev, n, out_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( scores_to_int16_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, scores_dev, n, out_dev );
 }
 
 extern "C" nvbio_status nvbio_score_stream_flatten(int device, const nvbio_hit_queues* hits, const uint32_t* read_index_dev, uint32_t band_len,
@@ -456,11 +452,9 @@ extern "C" nvbio_status nvbio_score_stream_flatten(int device, const nvbio_hit_q
     NVB_REQUIRE( hits->hit_read_id_dev && hits->hit_seed_dev && hits->hit_loc_dev && read_index_dev, "NULL device pointer in the hit queues" );
     NVB_REQUIRE( read_id_dev && flags_dev && win_begin_dev && win_end_dev, "NULL output pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( score_stream_flatten_kernel, dim3( grid_for( hits->n ) ), dim3(256), 0, (hipStream_t)stream, hits->idx_queue_dev, hits->n,
-                        hits->hit_read_id_dev, hits->hit_seed_dev, hits->hit_loc_dev, read_index_dev, band_len, genome_len, reads_reversed,
-                        read_id_dev, flags_dev, win_begin_dev, win_end_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( score_stream_flatten_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, hits->idx_queue_dev, hits->n,
+                       hits->hit_read_id_dev, hits->hit_seed_dev, hits->hit_loc_dev, read_index_dev, band_len, genome_len, reads_reversed,
+                       read_id_dev, flags_dev, win_begin_dev, win_end_dev );
 }
 
 extern "C" nvbio_status nvbio_score_stream_output(int device, const nvbio_hit_queues* hits, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
@@ -470,10 +464,8 @@ extern "C" nvbio_status nvbio_score_stream_output(int device, const nvbio_hit_qu
     if (hits->n == 0) return NVBIO_OK;
     NVB_REQUIRE( hits->hit_score_dev && hits->hit_sink_dev && scores_dev && sinks_dev && win_begin_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( score_stream_output_kernel, dim3( grid_for( hits->n ) ), dim3(256), 0, (hipStream_t)stream, hits->idx_queue_dev, hits->n,
-                        scores_dev, (const uint2*)sinks_dev, win_begin_dev, worst_score, hits->hit_score_dev, hits->hit_sink_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( score_stream_output_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, hits->idx_queue_dev, hits->n,
+                       scores_dev, (const uint2*)sinks_dev, win_begin_dev, worst_score, hits->hit_score_dev, hits->hit_sink_dev );
 }
 
 extern "C" nvbio_status nvbio_opposite_mate_windows(int device, const uint32_t* g_pos_dev, const uint8_t* anchor_rc_dev, uint32_t n,
@@ -487,11 +479,9 @@ extern "C" nvbio_status nvbio_opposite_mate_windows(int device, const uint32_t* 
     NVB_REQUIRE( policy <= NVBIO_PE_POLICY_RR, "invalid paired-end policy" );
     NVB_REQUIRE( anchor <= 1u, "anchor must be 0 or 1" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( opposite_mate_windows_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream,
-                        g_pos_dev, anchor_rc_dev, n, anchor_len, opposite_gapped_len, anchor, policy, min_frag_len, max_frag_len, overlap,
-                        genome_len, win_begin_dev, win_end_dev, flags_dev, valid_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( opposite_mate_windows_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream,
+                       g_pos_dev, anchor_rc_dev, n, anchor_len, opposite_gapped_len, anchor, policy, min_frag_len, max_frag_len, overlap,
+                       genome_len, win_begin_dev, win_end_dev, flags_dev, valid_dev );
 }
 
 extern "C" nvbio_status nvbio_hits_to_diagonals(int device, const nvbio_uint2* hits_dev, uint64_t n_hits, uint32_t seeds_per_read,
@@ -503,10 +493,8 @@ extern "C" nvbio_status nvbio_hits_to_diagonals(int device, const nvbio_uint2* h
     NVB_REQUIRE( seeds_per_read > 0, "seeds_per_read must be positive" );
     NVB_REQUIRE( (uint64_t)(seeds_per_read - 1u) * seed_interval + seed_len <= read_len, "seeds do not fit the read" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( hits_to_diagonals_kernel, dim3( grid_for( n_hits ) ), dim3(256), 0, (hipStream_t)stream,
-                        (const uint2*)hits_dev, n_hits, seeds_per_read, seed_interval, seed_len, read_len, strand, keys_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( hits_to_diagonals_kernel, dim3( grid_for( n_hits ) ), dim3(256), (hipStream_t)stream,
+                       (const uint2*)hits_dev, n_hits, seeds_per_read, seed_interval, seed_len, read_len, strand, keys_dev );
 }
 
 extern "C" nvbio_status nvbio_diagonals_to_windows(int device, const uint64_t* keys_dev, uint64_t n, uint32_t band, uint32_t read_len,
@@ -516,10 +504,8 @@ extern "C" nvbio_status nvbio_diagonals_to_windows(int device, const uint64_t* k
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && read_id_dev && flags_dev && win_begin_dev && win_end_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( diagonals_to_windows_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream,
-                        keys_dev, n, band, read_len, genome_len, read_id_dev, flags_dev, win_begin_dev, win_end_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( diagonals_to_windows_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream,
+                       keys_dev, n, band, read_len, genome_len, read_id_dev, flags_dev, win_begin_dev, win_end_dev, nullptr );
 }
 
 extern "C" nvbio_status nvbio_diagonals_to_windows_ragged(int device, const uint64_t* keys_dev, uint64_t n, uint32_t band, const uint32_t* read_offsets_dev,
@@ -529,10 +515,8 @@ extern "C" nvbio_status nvbio_diagonals_to_windows_ragged(int device, const uint
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && read_offsets_dev && read_id_dev && flags_dev && win_begin_dev && win_end_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( diagonals_to_windows_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream,
-                        keys_dev, n, band, 0u, genome_len, read_id_dev, flags_dev, win_begin_dev, win_end_dev, read_offsets_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( diagonals_to_windows_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream,
+                       keys_dev, n, band, 0u, genome_len, read_id_dev, flags_dev, win_begin_dev, win_end_dev, read_offsets_dev );
 }
 
 extern "C" nvbio_status nvbio_best_candidate_reduce(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
@@ -541,10 +525,8 @@ extern "C" nvbio_status nvbio_best_candidate_reduce(int device, const uint64_t* 
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && scores_dev && sinks_dev && win_begin_dev && best_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( best_candidate_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream,
-                        keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n, (unsigned long long*)best_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( best_candidate_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream,
+                       keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n, (unsigned long long*)best_dev );
 }
 
 extern "C" nvbio_status nvbio_best_candidate_windows(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
@@ -554,10 +536,8 @@ extern "C" nvbio_status nvbio_best_candidate_windows(int device, const uint64_t*
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && scores_dev && sinks_dev && win_begin_dev && best_dev && best_wb_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( best_window_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, keys_dev, scores_dev, (const uint2*)sinks_dev,
-                        win_begin_dev, n, (const unsigned long long*)best_dev, (long long*)best_wb_dev, (long long*)best_locus_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( best_window_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, keys_dev, scores_dev, (const uint2*)sinks_dev,
+                       win_begin_dev, n, (const unsigned long long*)best_dev, (long long*)best_wb_dev, (long long*)best_locus_dev );
 }
 
 extern "C" nvbio_status nvbio_traceback_best_batch(int device, const uint64_t* best_dev, const int64_t* best_wb_dev, uint32_t n_reads, uint32_t read_len,
@@ -567,11 +547,9 @@ extern "C" nvbio_status nvbio_traceback_best_batch(int device, const uint64_t* b
     if (n_reads == 0) return NVBIO_OK;
     NVB_REQUIRE( best_dev && best_wb_dev && flags_dev && win_begin_dev && win_end_dev && scores_dev && sinks_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( traceback_best_batch_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)best_dev,
-                        (const long long*)best_wb_dev, n_reads, read_len, band, genome_len, min_score, flags_dev, win_begin_dev, win_end_dev,
-                        scores_dev, (uint2*)sinks_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( traceback_best_batch_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, (const unsigned long long*)best_dev,
+                       (const long long*)best_wb_dev, n_reads, read_len, band, genome_len, min_score, flags_dev, win_begin_dev, win_end_dev,
+                       scores_dev, (uint2*)sinks_dev, nullptr, nullptr );
 }
 
 extern "C" nvbio_status nvbio_traceback_best_batch_ragged(int device, const uint64_t* best_dev, const int64_t* best_wb_dev, uint32_t n_reads,
@@ -582,11 +560,9 @@ extern "C" nvbio_status nvbio_traceback_best_batch_ragged(int device, const uint
     if (n_reads == 0) return NVBIO_OK;
     NVB_REQUIRE( best_dev && best_wb_dev && read_offsets_dev && min_scores_dev && flags_dev && win_begin_dev && win_end_dev && scores_dev && sinks_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( traceback_best_batch_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)best_dev,
-                        (const long long*)best_wb_dev, n_reads, 0u, band, genome_len, 0, flags_dev, win_begin_dev, win_end_dev,
-                        scores_dev, (uint2*)sinks_dev, read_offsets_dev, min_scores_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( traceback_best_batch_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, (const unsigned long long*)best_dev,
+                       (const long long*)best_wb_dev, n_reads, 0u, band, genome_len, 0, flags_dev, win_begin_dev, win_end_dev,
+                       scores_dev, (uint2*)sinks_dev, read_offsets_dev, min_scores_dev );
 }
 
 extern "C" nvbio_status nvbio_best_candidate_unpack(int device, const uint64_t* best_dev, uint32_t n_reads, int32_t* scores_dev,
@@ -595,10 +571,8 @@ extern "C" nvbio_status nvbio_best_candidate_unpack(int device, const uint64_t* 
     if (n_reads == 0) return NVBIO_OK;
     NVB_REQUIRE( best_dev && scores_dev && end_pos_dev && rc_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( best_unpack_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream,
-                        (const unsigned long long*)best_dev, n_reads, scores_dev, end_pos_dev, rc_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( best_unpack_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream,
+                       (const unsigned long long*)best_dev, n_reads, scores_dev, end_pos_dev, rc_dev );
 }
 
 extern "C" nvbio_status nvbio_second_candidate_reduce(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
@@ -608,11 +582,9 @@ extern "C" nvbio_status nvbio_second_candidate_reduce(int device, const uint64_t
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && scores_dev && sinks_dev && win_begin_dev && best_dev && second_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( second_candidate_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream,
-                        keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n, (const unsigned long long*)best_dev,
-                        distinct_dist, worst_score, (unsigned long long*)second_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( second_candidate_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream,
+                       keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n, (const unsigned long long*)best_dev,
+                       distinct_dist, worst_score, (unsigned long long*)second_dev, nullptr, nullptr );
 }
 
 extern "C" nvbio_status nvbio_second_candidate_reduce_ragged(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
@@ -622,11 +594,9 @@ extern "C" nvbio_status nvbio_second_candidate_reduce_ragged(int device, const u
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && scores_dev && sinks_dev && win_begin_dev && best_dev && second_dev && read_offsets_dev && min_scores_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( second_candidate_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream,
-                        keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n, (const unsigned long long*)best_dev,
-                        0u, 0, (unsigned long long*)second_dev, read_offsets_dev, min_scores_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( second_candidate_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream,
+                       keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n, (const unsigned long long*)best_dev,
+                       0u, 0, (unsigned long long*)second_dev, read_offsets_dev, min_scores_dev );
 }
 
 extern "C" nvbio_status nvbio_mapq_ragged(int device, const uint64_t* best_dev, const uint64_t* second_dev, uint32_t n_reads, int32_t version, int32_t match,
@@ -637,11 +607,9 @@ extern "C" nvbio_status nvbio_mapq_ragged(int device, const uint64_t* best_dev, 
     NVB_REQUIRE( best_dev && mapq_dev && read_offsets_dev && min_scores_dev, "NULL pointer" );
     NVB_REQUIRE( version == 2 || version == 3, "mapq version must be 2 or 3" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( mapq_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream,
-                        (const unsigned long long*)best_dev, (const unsigned long long*)second_dev, n_reads, (int)version,
-                        match == 0, 0.0f, 0.0f, second_scores_dev, mapq_dev, read_offsets_dev, min_scores_dev, match );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( mapq_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream,
+                       (const unsigned long long*)best_dev, (const unsigned long long*)second_dev, n_reads, (int)version,
+                       match == 0, 0.0f, 0.0f, second_scores_dev, mapq_dev, read_offsets_dev, min_scores_dev, match );
 }
 
 extern "C" nvbio_status nvbio_mapq(int device, const uint64_t* best_dev, const uint64_t* second_dev, uint32_t n_reads,
@@ -652,11 +620,9 @@ extern "C" nvbio_status nvbio_mapq(int device, const uint64_t* best_dev, const u
     NVB_REQUIRE( params->version == 2 || params->version == 3, "mapq version must be 2 or 3" );
     NVB_REQUIRE( params->perfect_score > params->min_score, "perfect_score must exceed min_score" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( mapq_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream,
-                        (const unsigned long long*)best_dev, (const unsigned long long*)second_dev, n_reads, (int)params->version,
-                        params->monotone != 0, (float)params->perfect_score, (float)params->min_score, second_scores_dev, mapq_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( mapq_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream,
+                       (const unsigned long long*)best_dev, (const unsigned long long*)second_dev, n_reads, (int)params->version,
+                       params->monotone != 0, (float)params->perfect_score, (float)params->min_score, second_scores_dev, mapq_dev, nullptr, nullptr, 0 );
 }
 
 // sort + unique of candidate keys: what fmmap does with its diagonals before extending them (examples/fmmap/fmmap.cu:320-344:

@@ -345,11 +345,9 @@ nvbio_status nvbio_seed_hits_map(int device, const nvbio_uint2* fw_ranges_dev, c
     NVB_REQUIRE( p->read_len < 1024u, "SeedHit keeps the seed position in 10 bits (seed_hit.h:217)" );
     uint32_t cap = 0; NVB_CHECK( nvbio_seed_hits_capacity( p->seeds_per_read, p->max_hits, &cap ) );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( seed_hits_map_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream, (const uint2*)fw_ranges_dev, (const uint2*)rc_ranges_dev,
-                        read_queue_dev, n_reads, p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,
-                        (uint2*)deques_dev, sizes_dev, reseed_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( seed_hits_map_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, (const uint2*)fw_ranges_dev, (const uint2*)rc_ranges_dev,
+                       read_queue_dev, n_reads, p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,
+                       (uint2*)deques_dev, sizes_dev, reseed_dev );
 }
 
 nvbio_status nvbio_seed_hits_select(int device, const uint32_t* active_in_dev, uint32_t n_active, const uint32_t* trys_dev, uint32_t capacity,
@@ -361,11 +359,9 @@ nvbio_status nvbio_seed_hits_select(int device, const uint32_t* active_in_dev, u
     NVB_HIP( hipMemsetAsync( count_dev, 0, sizeof(uint32_t), (hipStream_t)stream ) );
     if (n_active == 0) return NVBIO_OK;
     NVB_REQUIRE( active_in_dev && deques_dev && sizes_dev && active_out_dev && hits->hit_read_id_dev && hits->hit_loc_dev && hits->hit_seed_dev, "NULL device pointer" );
-    hipLaunchKernelGGL( seed_hits_select_kernel, dim3( grid_for( n_active ) ), dim3(256), 0, (hipStream_t)stream, active_in_dev, n_active, trys_dev, capacity,
-                        (uint2*)deques_dev, sizes_dev, active_out_dev, (uint32_t*)hits->hit_read_id_dev, (uint32_t*)hits->hit_loc_dev, (uint32_t*)hits->hit_seed_dev,
-                        (unsigned int*)count_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( seed_hits_select_kernel, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, active_in_dev, n_active, trys_dev, capacity,
+                       (uint2*)deques_dev, sizes_dev, active_out_dev, (uint32_t*)hits->hit_read_id_dev, (uint32_t*)hits->hit_loc_dev, (uint32_t*)hits->hit_seed_dev,
+                       (unsigned int*)count_dev );
 }
 
 nvbio_status nvbio_seed_hits_loc(int device, const uint32_t* positions_dev, const nvbio_hit_queues* hits, void* stream)
@@ -374,9 +370,7 @@ nvbio_status nvbio_seed_hits_loc(int device, const uint32_t* positions_dev, cons
     if (hits->n == 0) return NVBIO_OK;
     NVB_REQUIRE( positions_dev && hits->hit_seed_dev && hits->hit_loc_dev, "NULL device pointer" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( seed_hits_loc_kernel, dim3( grid_for( hits->n ) ), dim3(256), 0, (hipStream_t)stream, positions_dev, hits->hit_seed_dev, hits->n, (uint32_t*)hits->hit_loc_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( seed_hits_loc_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, positions_dev, hits->hit_seed_dev, hits->n, (uint32_t*)hits->hit_loc_dev );
 }
 
 nvbio_status nvbio_score_reduce_effort(int device, const uint32_t* active_dev, const nvbio_hit_queues* hits, uint32_t read_len, uint32_t n_ext,
@@ -388,10 +382,8 @@ nvbio_status nvbio_score_reduce_effort(int device, const uint32_t* active_dev, c
     NVB_REQUIRE( active_dev && hits->hit_score_dev && hits->hit_loc_dev && hits->hit_seed_dev && best_dev && best_rc_dev && trys_dev && sizes_dev, "NULL device pointer" );
     NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( score_reduce_effort_kernel, dim3( grid_for( hits->n ) ), dim3(256), 0, (hipStream_t)stream, active_dev, hits->n, hits->hit_score_dev,
-                        hits->hit_loc_dev, hits->hit_seed_dev, read_len, n_ext, p->max_effort, p->min_ext, p->max_ext, (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( score_reduce_effort_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, active_dev, hits->n, hits->hit_score_dev,
+                       hits->hit_loc_dev, hits->hit_seed_dev, read_len, n_ext, p->max_effort, p->min_ext, p->max_ext, (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
 }
 
 nvbio_status nvbio_seed_hits_select_multi(int device, const uint32_t* active_in_dev, uint32_t n_active, const uint32_t* trys_dev, uint32_t capacity,
@@ -406,11 +398,9 @@ nvbio_status nvbio_seed_hits_select_multi(int device, const uint32_t* active_in_
     if (n_active == 0) return NVBIO_OK;
     NVB_REQUIRE( active_in_dev && deques_dev && sizes_dev && active_out_dev && hits_first_dev && hits_count_dev && hits->hit_read_id_dev && hits->hit_loc_dev &&
                  hits->hit_seed_dev, "NULL device pointer" );
-    hipLaunchKernelGGL( seed_hits_select_multi_kernel, dim3( grid_for( n_active ) ), dim3(256), 0, (hipStream_t)stream, active_in_dev, n_active, trys_dev, capacity,
-                        n_multi, (uint2*)deques_dev, sizes_dev, active_out_dev, hits_first_dev, hits_count_dev, (uint32_t*)hits->hit_read_id_dev,
-                        (uint32_t*)hits->hit_loc_dev, (uint32_t*)hits->hit_seed_dev, (unsigned int*)counts_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( seed_hits_select_multi_kernel, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, active_in_dev, n_active, trys_dev, capacity,
+                       n_multi, (uint2*)deques_dev, sizes_dev, active_out_dev, hits_first_dev, hits_count_dev, (uint32_t*)hits->hit_read_id_dev,
+                       (uint32_t*)hits->hit_loc_dev, (uint32_t*)hits->hit_seed_dev, (unsigned int*)counts_dev );
 }
 
 nvbio_status nvbio_score_reduce_effort_multi(int device, const uint32_t* active_dev, uint32_t n_active, const uint32_t* hits_first_dev,
@@ -424,11 +414,9 @@ nvbio_status nvbio_score_reduce_effort_multi(int device, const uint32_t* active_
                  trys_dev && sizes_dev, "NULL device pointer" );
     NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( score_reduce_effort_multi_kernel, dim3( grid_for( n_active ) ), dim3(256), 0, (hipStream_t)stream, active_dev, n_active, hits_first_dev,
-                        hits_count_dev, hits->hit_score_dev, hits->hit_loc_dev, hits->hit_seed_dev, read_len, n_ext, p->max_effort, p->min_ext, p->max_ext,
-                        (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( score_reduce_effort_multi_kernel, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, active_dev, n_active, hits_first_dev,
+                       hits_count_dev, hits->hit_score_dev, hits->hit_loc_dev, hits->hit_seed_dev, read_len, n_ext, p->max_effort, p->min_ext, p->max_ext,
+                       (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
 }
 
 nvbio_status nvbio_best_approx_init(int device, uint32_t n_reads, int32_t worst_score, int32_t* best_dev, uint8_t* best_rc_dev, void* stream)
@@ -437,9 +425,7 @@ nvbio_status nvbio_best_approx_init(int device, uint32_t n_reads, int32_t worst_
     NVB_REQUIRE( best_dev && best_rc_dev, "NULL device pointer" );
     NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( best_approx_init_kernel, dim3( grid_for( n_reads ) ), dim3(256), 0, (hipStream_t)stream, n_reads, worst_score, (int4*)best_dev, best_rc_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( best_approx_init_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, n_reads, worst_score, (int4*)best_dev, best_rc_dev );
 }
 
 nvbio_status nvbio_read_queue_begin(int device, const uint32_t* queue_dev, uint32_t n, uint32_t read_len, uint32_t first_offset, uint32_t top_seed,
@@ -447,10 +433,8 @@ nvbio_status nvbio_read_queue_begin(int device, const uint32_t* queue_dev, uint3
 {
     if (n == 0) return NVBIO_OK;
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    hipLaunchKernelGGL( read_queue_begin_kernel, dim3( grid_for( n ) ), dim3(256), 0, (hipStream_t)stream, queue_dev, n, read_len, first_offset, top_seed & 1u,
-                        max_effort_init, seed_offsets_dev, active_dev, trys_dev );
-    NVB_HIP( hipGetLastError() );
-    return NVBIO_OK;
+    return NVB_LAUNCH( read_queue_begin_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, queue_dev, n, read_len, first_offset, top_seed & 1u,
+                       max_effort_init, seed_offsets_dev, active_dev, trys_dev );
 }
 
 nvbio_status nvbio_read_queue_filter(int device, const uint32_t* queue_dev, uint32_t n, const uint8_t* read_flags_dev, uint32_t* queue_out_dev,
