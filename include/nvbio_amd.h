@@ -866,7 +866,10 @@ enum
                                               end-to-end kernel -- two alignments per lane -- then runs a build that takes a lane's two alignments
                                               in one pass whatever their lengths (the shorter one starts late); without the hint such a lane takes
                                               two passes.  Results are identical either way.                                        */
-    NVBIO_ALN_NO_LENGTH_SORT        = 8192, /* with NVBIO_ALN_RAGGED_READS: the DP's job list in batch order instead of ascending read length (A/B)   */
+    NVBIO_ALN_NO_LENGTH_SORT        = 8192, /* with NVBIO_ALN_RAGGED_READS: the DP's job list as it was built instead of in ascending read length (A/B).
+                                              Band-31 end-to-end scoring runs first pass -> second chance -> gap (or third) chance -> DP; each kernel appends
+                                              the jobs it leaves to the list of the launch that takes them next, so the lists are dense but in no
+                                              particular order; no result depends on it.                                              */
     NVBIO_ALN_NO_QUALITY_SHORTCUT   = 2048, /* band-31 end-to-end scoring of reads WITH base qualities under a quality-dependent mismatch penalty
                                               (nvBowtie's default ramp): every job through the DP, as before round 3 (A/B)          */
     NVBIO_ALN_NO_GAP_CHANCE         = 65536, /* band-31 end-to-end scoring: jobs without a near-clean diagonal (reads with an indel) go to the DP instead of the

@@ -691,23 +691,74 @@ __device__ __forceinline__ int32_t gap_chance_unknown_cost(const int32_t P, cons
     return c;
 }
 
-template <int RBITS, int MODE, bool QUAL = false>
-__global__ void __launch_bounds__(256)
-ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
-                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
-                      const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
-                      const SchemeDev sc)
+// ---- the stage's job lists, appended to by the kernels that decide a job's route ----
+// Each kernel in front of the DP holds a job's flag in a register when it stores need_dp[job]; it puts the job id on the list of the launch
+// that takes the job next itself.  Per workgroup and list: the waves count their jobs with a ballot, ONE lane reserves the workgroup's range
+// with a returning atomicAdd on the list's counter (none when the workgroup has no job for the list), every lane stores its id at the
+// range's start + the jobs of the waves before it + its rank in the ballot.  A workgroup walks JOB_LIST_CHUNKS chunks of 256 jobs and
+// reserves once for all of them.  The lists are dense but NOT in ascending job order (workgroups reserve in the order they finish).
+// Counters: `counts` of the "banded_job_list" layout, one 128-byte line each, zeroed on the stream before the first pass.
+constexpr uint32_t JOB_COUNT_STRIDE = 32u;                        // in uint32: counts[0] the DP's list, [32] the second chance's, [64] the third / gap chance's
+#ifndef NVB_JOB_LIST_CHUNKS
+#define NVB_JOB_LIST_CHUNKS 1
+#endif
+constexpr int JOB_LIST_CHUNKS = NVB_JOB_LIST_CHUNKS;              // at most 4 (JobAppend::mine holds a byte per chunk)
+static inline uint32_t job_list_grid(const uint32_t n) { return (n + 256u * JOB_LIST_CHUNKS - 1u) / (256u * JOB_LIST_CHUNKS); }
+
+struct JobLists { uint32_t *dp, *second, *third; uint32_t* counts; };      // list 0, 1, 2 and their counters
+
+template <int NL>
+struct JobAppend
 {
-    __shared__ int32_t s_pen[QUAL ? 64 : 1];
-    if (QUAL)
+    static_assert( NL >= 1 && NL <= 3 && JOB_LIST_CHUNKS >= 1 && JOB_LIST_CHUNKS <= 4, "JobAppend: up to 3 lists, up to 4 chunks" );
+    struct Lds { uint32_t cnt[NL][4 * JOB_LIST_CHUNKS]; uint32_t base[NL]; };
+    uint32_t mine = 0;                                            // chunk k in bits 8k .. 8k+7: (list + 1) << 6 | rank among the wave's jobs for that list
+    // chunk k's job of this lane goes on list `which` (-1: on none).  Called by EVERY lane of the workgroup (256 threads), converged.
+    __device__ __forceinline__ void note(Lds& lds, const int k, const int which)
     {
-        if (threadIdx.x < 64) s_pen[threadIdx.x] = -mismatch_score( sc, threadIdx.x );     // the DP kernels' table, negated
-        __syncthreads();
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        #pragma unroll
+        for (int l = 0; l < NL; ++l)
+        {
+            const uint64_t m = __ballot( which == l );
+            if (lane == 0) lds.cnt[l][4 * k + wave] = (uint32_t)__popcll( m );
+            if (which == l) mine |= (((uint32_t)(l + 1) << 6) | (uint32_t)__popcll( m & ((1ull << lane) - 1ull) )) << (8 * k);
+        }
     }
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    // reserve and store; job_of( k ) = the id of this lane's job of chunk k.  Called once by every lane of the workgroup, after the last note().
+    template <typename JobOf>
+    __device__ __forceinline__ void flush(Lds& lds, const JobLists& out, JobOf job_of)
+    {
+        __syncthreads();
+        if (threadIdx.x < (uint32_t)NL)
+        {
+            uint32_t tot = 0;
+            for (int i = 0; i < 4 * JOB_LIST_CHUNKS; ++i) { const uint32_t c = lds.cnt[threadIdx.x][i]; lds.cnt[threadIdx.x][i] = tot; tot += c; }
+            lds.base[threadIdx.x] = tot ? atomicAdd( out.counts + JOB_COUNT_STRIDE * threadIdx.x, (unsigned int)tot ) : 0u;
+        }
+        __syncthreads();
+        const uint32_t wave = threadIdx.x >> 6;
+        #pragma unroll
+        for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
+        {
+            const uint32_t e = (mine >> (8 * k)) & 255u;
+            if (e)
+            {
+                const uint32_t l = (e >> 6) - 1u;
+                uint32_t* const list = l == 0u ? out.dp : (l == 1u ? out.second : out.third);
+                list[lds.base[l] + lds.cnt[l][4 * k + wave] + (e & 63u)] = job_of( k );
+            }
+        }
+    }
+};
+
+// one job of the pass below: scores / sinks as its MODE says, returns the job's flag (what the kernel stores in need_dp[job])
+template <int RBITS, int MODE, bool QUAL>
+__device__ __forceinline__ uint32_t
+ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
+                   int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const int32_t* s_pen)
+{
     constexpr bool LIST = MODE != 0;
-    if (LIST ? slot >= *job_count : slot >= b.n) return;
-    const uint32_t job = LIST ? job_list[slot] : slot;
     const uint32_t rid   = b.read_id ? b.read_id[job] : job;
     const uint32_t first = b.read_offsets[rid];
     const uint32_t M     = b.read_offsets[rid + 1] - first;
@@ -719,10 +770,10 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
 
     if (N < M)                                                   // nothing reported (gotoh_banded_inl.h:422-423)
     {
-        scores[job] = NVBIO_SCORE_MIN; sinks[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); need_dp[job] = 0;
-        return;
+        scores[job] = NVBIO_SCORE_MIN; sinks[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu );
+        return 0u;
     }
-    if (M == 0u || M > 161u) { need_dp[job] = 1; return; }      // planes below hold 192 text symbols
+    if (M == 0u || M > 161u) return 1u;                          // planes below hold 192 text symbols
 
     // bit planes of the read and of the window (bitplanes.h); all loads first, then the bit work
     uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
@@ -813,15 +864,14 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
             // list pass) evaluates the one-gap alignments of such a job exactly; it needs every diagonal inside the text and plain gap terms
             // (not under a quality ramp: see the kernel's header)
             const bool gap_chance = !QUAL && P > 0 && N >= M + 30u && gap_ext < 0 && gap_open <= gap_ext && !(b.algo & NVBIO_ALN_NO_GAP_CHANCE);
-            need_dp[job] = gap_chance ? 4 : 1;
-            return;
+            return gap_chance ? 4u : 1u;
         }
         U = -(int64_t)P * (int64_t)best_cnt;
         if (QUAL)
         {
             // no class of alignments the three chances know can be settled below 3 G - P (the third chance's `beyond`): such a job
             // needs the DP whatever its exact U*, so its qualities are not even read
-            if (U <= 3 * (int64_t)G - P) { need_dp[job] = 1; return; }
+            if (U <= 3 * (int64_t)G - P) return 1u;
             const uint32_t pmax  = (uint32_t)s_pen[63];
             const uint64_t bound = (uint64_t)pmax * best_cnt;                    // a diagonal with P c_d > pmax c_min cannot hold the maximum
             uint32_t cand = 0;
@@ -860,7 +910,7 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
     {
         int32_t gmax = 0;
         while (gmax < 5 && (int64_t)gap_open + (int64_t)gmax * gap_ext >= U) ++gmax;
-        if (gmax >= 1 && gmax <= 4) { need_dp[job] = 3; stash(); return; }      // for the second-chance launch
+        if (gmax >= 1 && gmax <= 4) { stash(); return 3u; }                     // for the second-chance launch
     }
     if (MODE == 1 && second_applies)
     {
@@ -936,8 +986,8 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
     const bool third_applies = !settled && N >= M + 30u && !beyond && gmax0 >= 1 && (gmax1 >= 1 || two11);
     if (MODE == 0 && third_applies)
     {
-        need_dp[job] = 2; stash();                               // for the third-chance launch
-        return;
+        stash();                                                 // for the third-chance launch
+        return 2u;
     }
     if (MODE != 0 && third_applies)                              // (MODE 1: a job the second chance did not settle)
     {
@@ -1072,9 +1122,52 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
     }
     if (settled)
     {
-        scores[job] = (int32_t)U; sinks[job] = make_uint2( M + best_d, M ); need_dp[job] = 0;
+        scores[job] = (int32_t)U; sinks[job] = make_uint2( M + best_d, M );
+        return 0u;
     }
-    else need_dp[job] = 1;
+    return 1u;
+}
+
+// MODE 0: every job of the batch; its flag goes to need_dp (the gap chance tells 2 from 4 by it) and its id on the list of the launch that
+//   takes it next: flag 3 on out.second, a flag in `third_mask` (bit f set: flag f is taken by the launch over out.third -- the host passes
+//   the flags of the launch that really follows, none when none does) on out.third, any other non-zero flag on out.dp.
+// MODE 1 / 2: the jobs of job_list; one that ends as 1 goes on out.dp.  (Launched over the whole batch's workgroups: those behind the
+//   list's end leave before they touch anything.)
+template <int RBITS, int MODE, bool QUAL = false>
+__global__ void __launch_bounds__(256)
+ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
+                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
+                      const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
+                      const SchemeDev sc, const JobLists out, const uint32_t third_mask)
+{
+    constexpr bool LIST = MODE != 0;
+    constexpr int  NL   = LIST ? 1 : 3;
+    __shared__ int32_t s_pen[QUAL ? 64 : 1];
+    __shared__ typename JobAppend<NL>::Lds s_lists;
+    const uint32_t n    = LIST ? *job_count : b.n;
+    const uint32_t slot0 = blockIdx.x * (256u * JOB_LIST_CHUNKS);
+    if (slot0 >= n) return;                                          // (the whole workgroup)
+    if (QUAL)
+    {
+        if (threadIdx.x < 64) s_pen[threadIdx.x] = -mismatch_score( sc, threadIdx.x );     // the DP kernels' table, negated
+        __syncthreads();
+    }
+    JobAppend<NL> app;
+    auto job_of = [&](const int k) -> uint32_t { const uint32_t slot = slot0 + 256u * k + threadIdx.x; return LIST ? job_list[slot] : slot; };
+    #pragma unroll 1
+    for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
+    {
+        int which = -1;
+        if (slot0 + 256u * k + threadIdx.x < n)
+        {
+            const uint32_t job  = job_of( k );
+            const uint32_t flag = ungapped_e2e31_job<RBITS,MODE,QUAL>( b, P, G, gap_open, gap_ext, scores, sinks, job, s_pen );
+            need_dp[job] = (uint8_t)flag;
+            if (flag) which = LIST ? 0 : (flag == 3u ? 1 : (((third_mask >> flag) & 1u) ? 2 : 0));
+        }
+        app.note( s_lists, k, which );
+    }
+    app.flush( s_lists, out, job_of );
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1102,15 +1195,12 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
 // penalty -- costs 14, so a job settles only while its optimum costs 13 or less; the third chance already takes U* >= -11 there, and on the robust
 // batch the pass cost 1.1-1.7 ms for 0.5-1.0 ms of DP saved.  With the ladder taken to four priced mismatches per member (bound 18: two gaps and a
 // mismatch; also built, also green) the DP went 3.9 -> 2.7 ms and the pass cost 2.1: a job costs the pass half a DP and only half of them settle.
+// one job of the gap chance: returns its flag, 0 (settled: scores / sinks written) or 1 (the DP's); has_u: a third-chance job (need_dp = 2)
 template <int RBITS>
-__global__ void __launch_bounds__(256)
-gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
-                        int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
-                        const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count)
+__device__ __forceinline__ uint32_t
+gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
+                     int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const bool has_u)
 {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= *job_count) return;
-    const uint32_t job = job_list[slot];
     const uint32_t rid   = b.read_id ? b.read_id[job] : job;
     const uint32_t first = b.read_offsets[rid];
     const uint32_t M     = b.read_offsets[rid + 1] - first;
@@ -1121,8 +1211,7 @@ gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, cons
     const uint32_t N     = b.win_end[job] - tb;
     // (flagged by the first pass: 1 <= M <= 161, N >= M + 30, P > 0, open <= ext < 0)
     // need_dp = 2: a third-chance job -- its best diagonal (2 or 3 mismatches) is in scores / sinks; that ungapped class joins the evaluated ones
-    const bool     has_u = need_dp[job] == 2;
-    const int32_t  cu    = has_u ? -scores[job] : 0x7FFFFFFF;
+    const int32_t  cu   = has_u ? -scores[job] : 0x7FFFFFFF;
     const uint32_t cu_end = has_u ? sinks[job].x - M : 0u;
 
     uint32_t pl[6], ph[6], pn[6], pm[6], ql[7], qh[7];
@@ -1345,8 +1434,38 @@ gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, cons
     }
     if (cu < best_cost || (cu == best_cost && cu_end > best_end)) { best_cost = cu; best_end = cu_end; }
     const bool settled = best_cost < c_unk && !(ex11 && cost11 <= best_cost) && !(ex12 && cost12 <= best_cost);
-    if (settled) { scores[job] = -best_cost; sinks[job] = make_uint2( M + best_end, M ); need_dp[job] = 0; }
-    else need_dp[job] = 1;
+    if (settled) { scores[job] = -best_cost; sinks[job] = make_uint2( M + best_end, M ); return 0u; }
+    return 1u;
+}
+
+// the jobs of job_list (launched over the whole batch's workgroups: those behind the list's end leave before they touch anything); one that
+// ends as 1 goes on out.dp
+template <int RBITS>
+__global__ void __launch_bounds__(256)
+gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
+                        int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
+                        const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count, const JobLists out)
+{
+    __shared__ JobAppend<1>::Lds s_lists;
+    const uint32_t n     = *job_count;
+    const uint32_t slot0 = blockIdx.x * (256u * JOB_LIST_CHUNKS);
+    if (slot0 >= n) return;                                          // (the whole workgroup)
+    JobAppend<1> app;
+    auto job_of = [&](const int k) -> uint32_t { return job_list[slot0 + 256u * k + threadIdx.x]; };
+    #pragma unroll 1
+    for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
+    {
+        int which = -1;
+        if (slot0 + 256u * k + threadIdx.x < n)
+        {
+            const uint32_t job  = job_of( k );
+            const uint32_t flag = gap_chance_e2e31_job<RBITS>( b, P, G, gap_open, gap_ext, scores, sinks, job, need_dp[job] == 2 );
+            need_dp[job] = (uint8_t)flag;
+            if (flag) which = 0;
+        }
+        app.note( s_lists, k, which );
+    }
+    app.flush( s_lists, out, job_of );
 }
 
 // host-side conditions of the shortcut: SEMI_GLOBAL, match = 0, one mismatch penalty for every quality,
@@ -1383,8 +1502,6 @@ static bool packed_ok(const int type, const SchemeDev& sc, const uint32_t max_re
 }
 
 struct IsTwo { __host__ __device__ __forceinline__ uint8_t operator()(const uint8_t v) const { return v == 2u ? 1u : 0u; } };
-struct FlagIs { const uint8_t* flags; uint8_t code; __host__ __device__ __forceinline__ bool operator()(const uint32_t i) const { return flags[i] == code; } };
-struct FlagIn { const uint8_t* flags; uint32_t mask; __host__ __device__ __forceinline__ bool operator()(const uint32_t i) const { return ((mask >> flags[i]) & 1u) != 0u; } };
 
 
 // RAGGED batches: the DP's job list in ascending order of read length, so that the two alignments of a lane -- and the lanes of a wave --
@@ -1475,70 +1592,53 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
     // the two must disable the shortcut, as gotoh_full.hip does with `second_chance`.)
     if (TYPE == NVBIO_SEMI_GLOBAL && ungapped_ok( sc, b, &P, &by_quality ) && !(b.algo & NVBIO_ALN_NO_UNGAPPED_SCORE))
     {
-        // 1. settle the jobs whose best diagonal beats every gapped alignment; 2. compact the rest; 3. DP over the list
+        // 1. settle the jobs whose best diagonal beats every gapped alignment, 2. give the ones a chance can still settle to that chance,
+        // 3. DP over the rest.  Every kernel puts the jobs it does not settle on the list of the launch that takes them next (JobAppend).
         const int32_t G = sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go;
-        size_t sel_bytes = 0;
-        hipcub::CountingInputIterator<uint32_t> ids( 0u );
-        NVB_HIP( hipcub::DeviceSelect::Flagged( nullptr, sel_bytes, ids, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)b.n, s ) );
         const bool third = !(b.algo & NVBIO_ALN_NO_THIRD_CHANCE);
-        // three-way partition of the job ids by flag (3: second chance, 2: third chance), the rest discarded
-        size_t part_bytes = 0;
-        hipcub::DiscardOutputIterator<uint32_t> nowhere;
-        const FlagIs is3 = { nullptr, 3 }; const FlagIn is2 = { nullptr, 0u };
-        NVB_HIP( hipcub::DevicePartition::If( nullptr, part_bytes, ids, (uint32_t*)nullptr, (uint32_t*)nullptr, nowhere, (uint32_t*)nullptr, (int)b.n, is3, is2, s ) );
-        if (part_bytes > sel_bytes) sel_bytes = part_bytes;
-        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *counts; void* sel_temp;
+        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *counts;
         ScratchBlock aux;
         NVB_CHECK( aux.alloc_layout( "banded_job_list", s, "banded score: out of device memory for the job list", [&](ScratchLayout& c)
         {
             need_dp  = c.take<uint8_t>( b.n );
-            job_list = c.take<uint32_t>( b.n );
+            job_list = c.take<uint32_t>( b.n );                                              // the DP's jobs
             list_s   = c.take<uint32_t>( b.n );                                              // second-chance jobs
-            list_t   = c.take<uint32_t>( b.n );                                              // third-chance jobs
-            counts   = c.take<uint32_t>( 4 );                                                // [0]: job_list's length, [2..3]: list_s's, list_t's
-            sel_temp = c.take<uint8_t>( sel_bytes );
+            list_t   = c.take<uint32_t>( b.n );                                              // third-chance / gap-chance jobs
+            counts   = c.take<uint32_t>( 3 * JOB_COUNT_STRIDE );                             // the three lists' lengths, a 128-byte line each
         } ) );
-        uint32_t* job_count = counts;
-        uint32_t* count_st  = counts + 2;                                                   // (DevicePartition writes both lengths)
+        const JobLists out = { job_list, list_s, list_t, counts };
+        const uint32_t* job_count = counts;
+        const uint32_t* count_s   = counts + JOB_COUNT_STRIDE;
+        const uint32_t* count_t   = counts + 2u * JOB_COUNT_STRIDE;
+        // the jobs a chance can still settle, each list through its own launch; every job ends as 0 or 1.
+        //   out.second: need_dp == 3, the second chance.
+        //   out.third:  the gap chance's jobs -- need_dp == 4 (no diagonal in reach of the other chances: reads with an indel, mostly) and
+        //               need_dp == 2 (third-chance jobs: the gap chance evaluates what the third chance only rules out, with the job's best diagonal as
+        //               one more class) -- or, without the gap chance (qualities, NVBIO_ALN_NO_GAP_CHANCE), need_dp == 2 for the third chance.
+        // A flag whose launch does not follow (NVBIO_ALN_NO_THIRD_CHANCE: 2; neither launch: none at all) is not in the mask: the first pass hands
+        // those jobs to the DP.  (NVBIO_ALN_NO_SECOND_CHANCE keeps the first pass from flagging any 3.)
+        const bool gapc = !by_quality && !(b.algo & NVBIO_ALN_NO_GAP_CHANCE);
+        const uint32_t third_mask = gapc ? ((third ? 1u << 2 : 0u) | 1u << 4) : (third ? 1u << 2 : 0u);
+        const dim3 grid( job_list_grid( b.n ) ), block( 256 );
+        NVB_HIP( hipMemsetAsync( counts, 0, 3 * JOB_COUNT_STRIDE * sizeof(uint32_t), s ) );
         if (by_quality)
-            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0,true>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc ) );
+            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0,true>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
         else
-            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc ) );
-        hipError_t e = hipSuccess;
-        {
-            // the jobs a chance can still settle, compacted by ONE three-way partition, each list through its own launch; every job ends as 0 or 1.
-            //   list 1: need_dp == 3, the second chance.
-            //   list 2: the gap chance's jobs -- need_dp == 4 (no diagonal in reach of the other chances: reads with an indel, mostly) and
-            //           need_dp == 2 (third-chance jobs: the gap chance evaluates what the third chance only rules out, with the job's best diagonal as
-            //           one more class) -- or, without the gap chance (qualities, NVBIO_ALN_NO_GAP_CHANCE), need_dp == 2 for the third chance.
-            // (With NVBIO_ALN_NO_THIRD_CHANCE the third-chance jobs are simply handed to the DP: a non-zero flag selects;
-            // NVBIO_ALN_NO_SECOND_CHANCE keeps the first pass from flagging any.)
-            const bool gapc = !by_quality && !(b.algo & NVBIO_ALN_NO_GAP_CHANCE);
-            const FlagIs f3 = { need_dp, 3 };
-            const FlagIn f2 = { need_dp, gapc ? ((third ? 4u : 0u) | 16u) : 4u };
-            size_t pb = sel_bytes;
-            e = hipcub::DevicePartition::If( sel_temp, pb, ids, list_s, list_t, nowhere, count_st, (int)b.n, f3, f2, s );
-            if (e == hipSuccess)
-                NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                       (const uint32_t*)list_s, (const uint32_t*)count_st, SchemeDev{} ) );
-            if (e == hipSuccess && gapc)
-                NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                       (const uint32_t*)list_t, (const uint32_t*)(count_st + 1) ) );
-            else if (e == hipSuccess && third)
-                NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,2>), dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                       (const uint32_t*)list_t, (const uint32_t*)(count_st + 1), SchemeDev{} ) );
-        }
-        if (e == hipSuccess) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, need_dp, job_list, job_count, (int)b.n, s );
-        if (e == hipSuccess)
-        {
-            const uint32_t* jl = job_list; const uint32_t* jc = job_count; ScratchBlock sorted;
-            if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT))
-                NVB_CHECK( sort_jobs_by_length( b, job_list, job_count, &jl, &jc, &sorted, s ) );
-            NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s )) );
-        }
-        if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
+        NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                               (const uint32_t*)list_s, count_s, SchemeDev{}, out, 0u ) );
+        if (gapc)
+            NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)list_t, count_t, out ) );
+        else if (third)
+            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,2>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)list_t, count_t, SchemeDev{}, out, 0u ) );
+        const uint32_t* jl = job_list; const uint32_t* jc = job_count; ScratchBlock sorted;
+        if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT))
+            NVB_CHECK( sort_jobs_by_length( b, job_list, job_count, &jl, &jc, &sorted, s ) );
+        NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s )) );
         return NVBIO_OK;
     }
     if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT) && b.n > 1u)
