@@ -528,6 +528,67 @@ nvbio_status nvbio_qgram_filter_merge(int device, int is_set, uint32_t interval,
                                       uint32_t* counts_dev, uint32_t* n_merged, void* temp_dev, uint64_t temp_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * the q-group index: QGroupIndexDevice (the PEANUT structure; nvbio/qgram/qgroup.h:60-290, qgroup_inl.h:28-277;
+ * csrc/qgroup_inl.h), the O(1)-lookup alternative to the sorted q-gram index above (nvbio/qgram/qgram.h:76-88), in a string and
+ * a set form.  A bit table addressed by the q-gram itself replaces the search, so a range lookup is two dependent loads whatever
+ * the text size.  The handle is an nvbio_qgram_index_t: nvbio_qgram_index_destroy, nvbio_qgram_index_device_bytes,
+ * nvbio_qgram_ranges, nvbio_qgram_filter_rank and nvbio_qgram_filter_locate take it unchanged in signature and meaning.
+ *
+ * With A = 1 << symbol_size and W = A^q / 32 (integer division):
+ *   I        W + 1 words; bit (g & 31) of word g / 32 is set iff q-gram g occurs.
+ *   S        W + 1 words; the exclusive scan of popc( I[i] ).
+ *   SS       n_unique + 1 words; the exclusive scan of the occurrence counts of the unique q-grams in ascending numeric order;
+ *            SS[n_unique] = n_qgrams.
+ *   P        n_qgrams coordinates: uint32 positions (string index), uint2 (string_id, string_pos) (set index).
+ *   range    (0, 0) if the bit of g is clear; else the HALF-OPEN (SS[S[i] + j'], SS[S[i] + j' + 1]) with i = g / 32, j = g & 31,
+ *            j' = popc( I[i] & ((1 << j) - 1) ) (qgroup.h:112-130).
+ *   table    I[i] and S[i] are kept interleaved as uint2 (I[i], S[i]), so the first step of a lookup is one 8-byte load; export
+ *            hands them out as the reference's two arrays.
+ * Packing, padding (string: every position, the tail padded; set: uniform_seeds_functor( q, seed_interval ), no padding) and
+ * N -> A are exactly those of the q-gram index.
+ *
+ * Departures from the reference:
+ *   order    the reference's fill takes slots with a returning atomic, so the order of a q-gram's occurrences in P is whatever the
+ *            scheduler made it.  Here it is defined: ascending position (string index); string-major, then position (set index).
+ *            For the same input SS equals the q-gram index's slots, P its index, the set bits of I its qgrams, and two builds
+ *            give identical bytes.
+ *   range    range( g ) for g >= A^q is a miss (the reference reads I out of bounds).
+ *   n_unique S[W] + popc( I[W] ); the reference takes S[W], which is 0 when q * symbol_size < 5 (W = 0: the one word holds every
+ *            bit).  For q * symbol_size >= 5 word W holds no bit and S[W] = n_unique.
+ *   empty    an empty text or set builds (n_unique = 0, SS = {0}); the reference has no set form.
+ * Limits (NVBIO_ERR_INVALID otherwise): 1 <= symbol_size <= 8, q >= 1, q * symbol_size <= 36 (the word index still fits uint32; the
+ * table is then 16 GiB -- qmap's Q = 20 at two bits would need 2^40 bits and is outside); n_qgrams below 2^32 - 1; text / symbol
+ * bits 2, 4 or 8.  A table that does not fit in HBM gives NVBIO_ERR_NOMEM.
+ * Working storage: the builds allocate their own (the table, SS and P stay with the handle).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct
+{
+    uint32_t           q, symbol_size;
+    uint32_t           is_set;         /* 0: string index (P = uint32 positions); 1: set index (P = uint2 coordinates) */
+    uint32_t           n_qgrams, n_unique;
+    uint64_t           n_words;        /* W + 1: the entries of table_dev */
+    int                device;
+    const nvbio_uint2* table_dev;      /* (I[i], S[i]) */
+    const uint32_t*    ss_dev;         /* n_unique + 1 */
+    const void*        p_dev;          /* n_qgrams */
+} nvbio_qgroup_index_view;
+
+/* QGroupIndexDevice::build( q, symbol_size, length, text ) (qgroup_inl.h:162-277): text_dev packed as nvbio_string_set symbols.
+ * Synchronizes. */
+nvbio_status nvbio_qgroup_index_build(int device, const void* text_dev, uint32_t text_bits, uint32_t length, uint32_t q, uint32_t symbol_size,
+                                      nvbio_qgram_index_t* out, void* stream);
+/* the set form over a plain string set, seeded as nvbio_qgram_set_index_build.  Synchronizes. */
+nvbio_status nvbio_qgroup_set_index_build(int device, const nvbio_string_set* set, uint32_t q, uint32_t symbol_size, uint32_t seed_interval,
+                                          nvbio_qgram_index_t* out, void* stream);
+/* NVBIO_ERR_INVALID on a sorted q-gram index.  (nvbio_qgram_index_get_view on a q-group handle fills the common fields with
+ * slots_dev = SS, index_dev = P, qgrams_dev = lut_dev = NULL and qlut = 0; nvbio_qgram_index_export on one is NVBIO_ERR_INVALID.) */
+nvbio_status nvbio_qgroup_index_get_view(nvbio_qgram_index_t index, nvbio_qgroup_index_view* view);
+/* copy I and S (n_words uint32 each, the reference's layout), SS (n_unique + 1) and P (n_qgrams uint32 or uint2) into caller buffers
+ * in HBM; any may be NULL */
+nvbio_status nvbio_qgroup_index_export(nvbio_qgram_index_t index, uint32_t* I_out_dev, uint32_t* S_out_dev, uint32_t* SS_out_dev, void* P_out_dev,
+                                       void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * seed hits -> candidate windows: the two index-arithmetic functors between FMIndexFilter::locate
  * and the banded aligner in the reference's smallest seed-and-extend caller (examples/fmmap/fmmap.cu)
  * ------------------------------------------------------------------------------------------- */

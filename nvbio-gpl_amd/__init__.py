@@ -9,6 +9,7 @@ argument meaning as the reference's C++ templates --
     FMIndexFilter                nvbio::FMIndexFilter<device_tag,...>      (nvbio/fmindex/filter.h:52-231)
     MEMFilter                    nvbio::MEMFilter<device_tag,...>          (nvbio/fmindex/mem.h, mem_inl.h:1303-1528)
     QGramIndex, QGramSetIndex    nvbio::QGramIndexDevice / QGramSetIndexDevice (nvbio/qgram/qgram.h, qgram_inl.h)
+    QGroupIndex, QGroupSetIndex  nvbio::QGroupIndexDevice (nvbio/qgram/qgroup.h, qgroup_inl.h) and its set form
     QGramFilter, generate_qgrams nvbio::QGramFilter<device_tag,...>        (nvbio/qgram/filter.h, filter_inl.h)
     SimpleGotohScheme, GotohAligner, BestSink semantics                    (nvbio/alignment/utils.h:103-123, alignment.h:437-449)
     BatchedBandedAlignmentScore, batch_banded_alignment_score              (nvbio/alignment/batched.h:104-298)
@@ -806,6 +807,60 @@ class QGramSetIndex(QGramIndex):
         dev = string_set.device
         _check(lib().nvbio_qgram_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size),
                                                  ctypes.c_uint32(seed_interval), ctypes.c_uint32(qlut), ctypes.byref(h), _stream_ptr(dev)))
+        return cls(h, dev, keep=(string_set,))
+
+
+class _QGroupView(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_uint32), ("symbol_size", ctypes.c_uint32), ("is_set", ctypes.c_uint32), ("n_qgrams", ctypes.c_uint32),
+                ("n_unique", ctypes.c_uint32), ("n_words", ctypes.c_uint64), ("device", ctypes.c_int), ("table_dev", ctypes.c_void_p),
+                ("ss_dev", ctypes.c_void_p), ("p_dev", ctypes.c_void_p)]
+
+
+class QGroupIndex(QGramIndex):
+    """nvbio::QGroupIndexDevice (nvbio/qgram/qgroup.h, qgroup_inl.h:162-277): the q-group index of every position of a text, the
+    O(1)-lookup alternative to QGramIndex (nvbio_qgroup_*; the structure, layout and departures are listed in include/nvbio_amd.h).
+    Usable wherever QGramFilter.rank takes an index; ranges(), q, n_qgrams, n_unique, device_bytes() and close() are inherited."""
+
+    @classmethod
+    def build(cls, text, text_bits, length, q, symbol_size=2, device="cuda:0"):
+        """QGroupIndexDevice::build( q, symbol_size, length, text ); text: packed words (bits 2, 4) or bytes (8)"""
+        t = _qgram_text(text, text_bits, device)
+        h = ctypes.c_void_p()
+        _check(lib().nvbio_qgroup_index_build(FMIndex._dev_index(device), _ptr(t), ctypes.c_uint32(text_bits), ctypes.c_uint32(length),
+                                              ctypes.c_uint32(q), ctypes.c_uint32(symbol_size), ctypes.byref(h), _stream_ptr(device)))
+        return cls(h, device)
+
+    def view(self):
+        v = _QGroupView()
+        _check(lib().nvbio_qgroup_index_get_view(self._h, ctypes.byref(v)))
+        return v
+
+    def arrays(self):
+        """copies of the index arrays as device tensors (nvbio_qgroup_index_export), in the reference's layout: I int32 [n_words],
+        S int32 [n_words], SS int32 [n_unique + 1], P int32 [n_qgrams] (or [n_qgrams, 2] (string_id, string_pos) for a set index)
+        (uint bit patterns)"""
+        torch = _torch()
+        v = self.view()
+        I = torch.empty(v.n_words, dtype=torch.int32, device=self.device)
+        S = torch.empty(v.n_words, dtype=torch.int32, device=self.device)
+        SS = torch.empty(v.n_unique + 1, dtype=torch.int32, device=self.device)
+        P = torch.empty((max(v.n_qgrams, 1), 2) if v.is_set else max(v.n_qgrams, 1), dtype=torch.int32, device=self.device)
+        _check(lib().nvbio_qgroup_index_export(self._h, _ptr(I), _ptr(S), _ptr(SS), _ptr(P), _stream_ptr(self.device)))
+        return dict(I=I, S=S, SS=SS, P=P[:v.n_qgrams])
+
+
+class QGroupSetIndex(QGroupIndex):
+    """the q-group index of the seeds k * seed_interval of every string of a plain set, seeded as QGramSetIndex (the reference has
+    no set form; PEANUT indexes the reads)"""
+    IS_SET = True
+
+    @classmethod
+    def build(cls, string_set, q, symbol_size=2, seed_interval=1):
+        h = ctypes.c_void_p()
+        ss = string_set.c_struct()
+        dev = string_set.device
+        _check(lib().nvbio_qgroup_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size),
+                                                  ctypes.c_uint32(seed_interval), ctypes.byref(h), _stream_ptr(dev)))
         return cls(h, dev, keep=(string_set,))
 
 

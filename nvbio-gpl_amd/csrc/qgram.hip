@@ -1,5 +1,5 @@
 // qgram.hip -- q-gram seeding for gfx950: the q-gram string index, the q-gram string-set index and the q-gram filter (rank / locate /
-// merge) behind the C ABI.
+// merge) behind the C ABI.  The q-group index, the O(1)-lookup alternative behind the same handle, is qgroup_inl.h, included below.
 //
 // Reference behaviour reproduced (file:line relative to the reference tree):
 //   string_qgram_functor / string_set_qgram_functor   nvbio/qgram/qgram.h:793-886
@@ -67,6 +67,10 @@ struct nvbio_qgram_index_s
     uint32_t* lut;         // lut_size + 1, or NULL
     uint64_t  lut_size;    // A^QL (0 without a LUT)
     uint64_t  bytes;
+    // a q-group index (qgroup_inl.h): slots = SS, index = P, qgrams = lut = NULL, qlut = 0
+    uint32_t  is_group;
+    uint2*    table;       // n_words interleaved (I[i], S[i]) pairs
+    uint64_t  n_words;     // A^q / 32 + 1
 };
 
 namespace nvbio_amd {
@@ -320,6 +324,57 @@ static nvbio_status finish_index(BuildBuffers& bufs, const int device, const uin
     return NVBIO_OK;
 }
 
+// the argument checks both set builds share: a plain string set and a seed interval
+static nvbio_status check_plain_set(const nvbio_string_set* set, const uint32_t seed_interval)
+{
+    NVB_REQUIRE( seed_interval >= 1, "seed_interval must be >= 1" );
+    NVB_REQUIRE( set->seeds_per_string == 0 && set->seed_intervals_dev == nullptr, "the q-gram set index takes plain string sets, not seed enumerations" );
+    NVB_REQUIRE( set->n == 0 || set->symbols_dev != nullptr, "symbols_dev is NULL" );
+    NVB_REQUIRE( !(set->offsets_are_ranges && set->offsets_dev == nullptr), "offsets_are_ranges without offsets_dev" );
+    NVB_REQUIRE( set->n < 0xFFFFFFFFu, "more than 2^32 - 2 strings" );
+    return NVBIO_OK;
+}
+
+// the seeds of a plain set in string-major order: n of them, their q-grams in keys and their (string_id, string_pos) in coords,
+// both buffers of `bufs`
+static nvbio_status enumerate_set_seeds(BuildBuffers& bufs, const nvbio_string_set* set, const uint32_t q, const uint32_t symbol_size,
+                                        const uint32_t seed_interval, hipStream_t s, uint32_t& n_out, uint64_t*& keys_out, uint64_t*& coords_out)
+{
+    QGramSet qs{ set->symbols_dev, set->offsets_dev, set->offsets_are_ranges, set->fixed_len, set->stride, set->n };
+    NVB_ALLOC( cnt, uint64_t, set->n + 1u );
+    NVB_ALLOC( first, uint64_t, set->n + 1u );
+    uint64_t total = 0;
+    NVB_HIP( hipMemsetAsync( first, 0, 8, s ) );
+    if (set->n)
+    {
+        NVB_CHECK( NVB_LAUNCH( qgram_seed_count_kernel, dim3( grid_for( set->n ) ), dim3(256), s, qs, q, seed_interval, cnt ) );
+        size_t a = 0;
+        NVB_HIP( rocprim::inclusive_scan( nullptr, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
+        NVB_ALLOC( temp, uint8_t, a );
+        NVB_HIP( rocprim::inclusive_scan( temp, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
+        NVB_HIP( hipMemcpyAsync( &total, first + set->n, 8, hipMemcpyDeviceToHost, s ) );
+        NVB_HIP( hipStreamSynchronize( s ) );
+        bufs.release( temp );
+    }
+    bufs.release( cnt );
+    NVB_REQUIRE( total < 0xFFFFFFFFull, "the set has 2^32 - 1 seeds or more" );
+    const uint32_t n = (uint32_t)total;
+    NVB_ALLOC( keys, uint64_t, n );
+    NVB_ALLOC( coords, uint64_t, n );
+    if (n)
+    {
+        NVB_CHECK( with_value( SymbolBits(), set->symbol_bits, [&](auto BITS)
+        {
+            return NVB_LAUNCH( qgram_seed_enumerate_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), s, qs, q, symbol_size, seed_interval,
+                               (const uint64_t*)first, n, keys, (uint2*)coords );
+        }, bad_symbol_bits ) );
+    }
+    NVB_HIP( hipStreamSynchronize( s ) );
+    bufs.release( first );
+    n_out = n; keys_out = keys; coords_out = coords;
+    return NVBIO_OK;
+}
+
 static QGramView view_of(const nvbio_qgram_index_s* h)
 {
     QGramView v;
@@ -375,6 +430,8 @@ struct GenerateTemp
 
 } // namespace nvbio_amd
 
+#include "qgroup_inl.h"                                   // the q-group index: its build, lookup and entry points
+
 using namespace nvbio_amd;
 
 extern "C" {
@@ -411,45 +468,12 @@ nvbio_status nvbio_qgram_set_index_build(int device, const nvbio_string_set* set
     *out = nullptr;
     NVB_CHECK( check_text_bits( set->symbol_bits ) );
     NVB_CHECK( check_qgram_params( q, symbol_size, qlut ) );
-    NVB_REQUIRE( seed_interval >= 1, "seed_interval must be >= 1" );
-    NVB_REQUIRE( set->seeds_per_string == 0 && set->seed_intervals_dev == nullptr, "the q-gram set index takes plain string sets, not seed enumerations" );
-    NVB_REQUIRE( set->n == 0 || set->symbols_dev != nullptr, "symbols_dev is NULL" );
-    NVB_REQUIRE( !(set->offsets_are_ranges && set->offsets_dev == nullptr), "offsets_are_ranges without offsets_dev" );
-    NVB_REQUIRE( set->n < 0xFFFFFFFFu, "more than 2^32 - 2 strings" );
+    NVB_CHECK( check_plain_set( set, seed_interval ) );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    QGramSet qs{ set->symbols_dev, set->offsets_dev, set->offsets_are_ranges, set->fixed_len, set->stride, set->n };
     BuildBuffers bufs( "q-gram index build" );
-    NVB_ALLOC( cnt, uint64_t, set->n + 1u );
-    NVB_ALLOC( first, uint64_t, set->n + 1u );
-    uint64_t total = 0;
-    NVB_HIP( hipMemsetAsync( first, 0, 8, s ) );
-    if (set->n)
-    {
-        NVB_CHECK( NVB_LAUNCH( qgram_seed_count_kernel, dim3( grid_for( set->n ) ), dim3(256), s, qs, q, seed_interval, cnt ) );
-        size_t a = 0;
-        NVB_HIP( rocprim::inclusive_scan( nullptr, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
-        NVB_ALLOC( temp, uint8_t, a );
-        NVB_HIP( rocprim::inclusive_scan( temp, a, cnt, first + 1, (size_t)set->n, rocprim::plus<uint64_t>(), s ) );
-        NVB_HIP( hipMemcpyAsync( &total, first + set->n, 8, hipMemcpyDeviceToHost, s ) );
-        NVB_HIP( hipStreamSynchronize( s ) );
-        bufs.release( temp );
-    }
-    bufs.release( cnt );
-    NVB_REQUIRE( total < 0xFFFFFFFFull, "the set has 2^32 - 1 seeds or more" );
-    const uint32_t n = (uint32_t)total;
-    NVB_ALLOC( keys, uint64_t, n );
-    NVB_ALLOC( coords, uint64_t, n );
-    if (n)
-    {
-        NVB_CHECK( with_value( SymbolBits(), set->symbol_bits, [&](auto BITS)
-        {
-            return NVB_LAUNCH( qgram_seed_enumerate_kernel<BITS>, dim3( grid_for( n ) ), dim3(256), s, qs, q, symbol_size, seed_interval,
-                               (const uint64_t*)first, n, keys, (uint2*)coords );
-        }, bad_symbol_bits ) );
-    }
-    NVB_HIP( hipStreamSynchronize( s ) );
-    bufs.release( first );
+    uint32_t n = 0; uint64_t* keys = nullptr; uint64_t* coords = nullptr;
+    NVB_CHECK( enumerate_set_seeds( bufs, set, q, symbol_size, seed_interval, s, n, keys, coords ) );
     return finish_index<uint64_t>( bufs, device, q, symbol_size, qlut, 1u, n, keys, coords, s, out );
 }
 
@@ -461,6 +485,7 @@ nvbio_status nvbio_qgram_index_destroy(nvbio_qgram_index_t index)
     (void)hipSetDevice( index->device );
     (void)hipFree( index->qgrams ); (void)hipFree( index->slots ); (void)hipFree( index->index );
     if (index->lut) (void)hipFree( index->lut );
+    if (index->table) (void)hipFree( index->table );
     if (prev >= 0) (void)hipSetDevice( prev );
     delete index;
     return NVBIO_OK;
@@ -486,6 +511,7 @@ nvbio_status nvbio_qgram_index_export(nvbio_qgram_index_t index, uint64_t* qgram
                                       uint32_t* lut_out_dev, void* stream)
 {
     NVB_REQUIRE( index != nullptr, "index is NULL" );
+    NVB_REQUIRE( !index->is_group, "a q-group index is exported by nvbio_qgroup_index_export" );
     DeviceGuard g( index->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const uint64_t w = index->is_set ? 8u : 4u;
@@ -546,8 +572,7 @@ nvbio_status nvbio_qgram_ranges(nvbio_qgram_index_t index, const uint64_t* qgram
     if (n == 0) return NVBIO_OK;
     NVB_REQUIRE( qgrams_dev && ranges_dev, "NULL device pointer" );
     DeviceGuard g( index->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    return NVB_LAUNCH( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, view_of( index ), qgrams_dev, n,
-                       (uint2*)ranges_dev );
+    return launch_ranges( index, qgrams_dev, n, (uint2*)ranges_dev, (hipStream_t)stream );
 }
 
 nvbio_status nvbio_qgram_filter_temp_bytes(uint32_t n_queries, uint64_t* bytes)
@@ -572,7 +597,7 @@ nvbio_status nvbio_qgram_filter_rank(nvbio_qgram_index_t index, const uint64_t* 
     ScratchBlock temp;
     NVB_CHECK( temp.alloc_layout( "qgram_filter_rank", s, "q-gram filter rank: out of device memory", [&](ScratchLayout& c) { cub = c.take<uint8_t>( cub_bytes ); },
                                   temp_dev, temp_bytes, "nvbio_qgram_filter_temp_bytes" ) );
-    NVB_CHECK( NVB_LAUNCH( qgram_range_kernel, dim3( grid_for( n ) ), dim3(256), s, view_of( index ), qgrams_dev, n, (uint2*)ranges_dev ) );
+    NVB_CHECK( launch_ranges( index, qgrams_dev, n, (uint2*)ranges_dev, s ) );
     rocprim::transform_iterator<const uint2*, QGramRangeSize, uint64_t> sizes( (const uint2*)ranges_dev, QGramRangeSize() );
     size_t bytes = cub_bytes;
     NVB_HIP( rocprim::inclusive_scan( cub, bytes, sizes, slots_dev, (size_t)n, rocprim::plus<uint64_t>(), s ) );

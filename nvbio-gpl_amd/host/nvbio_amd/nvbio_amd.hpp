@@ -13,6 +13,10 @@
 //   QGramIndexDevice, QGramSetIndexDevice
 //                                  ~ nvbio::QGramIndexDevice / QGramSetIndexDevice (nvbio/qgram/qgram.h, qgram_inl.h:30-300):
 //                                    build(q, symbol_size, ..., qlut) ; Q, n_qgrams, n_unique_qgrams ; qgrams / slots / index / lut
+//   QGroupIndexDevice, QGroupSetIndexDevice
+//                                  ~ nvbio::QGroupIndexDevice (nvbio/qgram/qgroup.h, qgroup_inl.h:162-277) and its set form:
+//                                    build(q, symbol_size, ...) ; Q, n_qgrams, n_unique_qgrams ; table / SS / P ; a QGramFilterDevice
+//                                    takes either as its index_type
 //   QGramFilterDevice<index_type>  ~ nvbio::QGramFilter<device_tag,index,...> (nvbio/qgram/filter.h, filter_inl.h:336-483):
 //                                    rank(index, n_queries, queries, indices) -> n_hits ; locate(begin, end, hits) ;
 //                                    merge(interval, n_hits, hits, merged_hits, merged_counts) -> n_merged
@@ -481,6 +485,62 @@ public:
         adopt( h );
     }
     const nvbio_uint2* index() const { return (const nvbio_uint2*)m_view.index_dev; }
+};
+
+// QGroupIndexDevice: the q-group index of every position of a string, the O(1)-lookup alternative to QGramIndexDevice (the structure,
+// layout and departures are listed in nvbio_amd.h).  The inherited slots() is SS; qgrams() and lut() are NULL and QL() is 0.
+class QGroupIndexDevice : public QGramIndexBase
+{
+public:
+    typedef uint32_t    coord_type;
+    typedef nvbio_uint2 hit_type;        // (index position, query coordinate)
+    typedef uint32_t    diagonal_type;
+    static const bool   is_set = false;
+    QGroupIndexDevice() { m_group = nvbio_qgroup_index_view(); }
+    // build( q, symbol_size, string_len, string ): string packed as nvbio_string_set symbols of `string_bits` (2, 4 or 8)
+    void build(uint32_t q, uint32_t symbol_size, uint32_t string_len, const void* string, uint32_t string_bits, int device = 0,
+               hipStream_t stream = 0)
+    {
+        nvbio_qgram_index_t h = nullptr;
+        check( nvbio_qgroup_index_build( device, string, string_bits, string_len, q, symbol_size, &h, stream ) );
+        adopt( h );
+        check( nvbio_qgroup_index_get_view( m_h, &m_group ) );
+    }
+    const nvbio_qgroup_index_view& group_view() const { return m_group; }
+    uint64_t           n_words() const { return m_group.n_words; }
+    const nvbio_uint2* table() const   { return m_group.table_dev; }      // (I[i], S[i])
+    const uint32_t*    SS() const      { return m_group.ss_dev; }
+    const uint32_t*    P() const       { return (const uint32_t*)m_group.p_dev; }
+    const uint32_t*    index() const   { return P(); }
+private:
+    nvbio_qgroup_index_view m_group;
+};
+
+// QGroupSetIndexDevice: the q-group index of the seeds k * seed_interval of every string of a plain set (coordinate: (string_id, string_pos))
+class QGroupSetIndexDevice : public QGramIndexBase
+{
+public:
+    typedef nvbio_uint2 coord_type;
+    typedef QGramSetIndexDevice::hit_type hit_type;
+    typedef nvbio_uint2 diagonal_type;   // (diagonal, string_id)
+    static const bool   is_set = true;
+    QGroupSetIndexDevice() { m_group = nvbio_qgroup_index_view(); }
+    // build( q, symbol_size, string_set, uniform_seeds_functor( q, seed_interval ) )
+    void build(uint32_t q, uint32_t symbol_size, const string_set& set, uint32_t seed_interval, int device = 0, hipStream_t stream = 0)
+    {
+        nvbio_qgram_index_t h = nullptr;
+        check( nvbio_qgroup_set_index_build( device, &set.c, q, symbol_size, seed_interval, &h, stream ) );
+        adopt( h );
+        check( nvbio_qgroup_index_get_view( m_h, &m_group ) );
+    }
+    const nvbio_qgroup_index_view& group_view() const { return m_group; }
+    uint64_t           n_words() const { return m_group.n_words; }
+    const nvbio_uint2* table() const   { return m_group.table_dev; }
+    const uint32_t*    SS() const      { return m_group.ss_dev; }
+    const nvbio_uint2* P() const       { return (const nvbio_uint2*)m_group.p_dev; }
+    const nvbio_uint2* index() const   { return P(); }
+private:
+    nvbio_qgroup_index_view m_group;
 };
 
 // QGramFilter<device_tag, qgram_index_type, const uint64*, const uint32*>: owns its ranges, slots and temp, grown to what a call needs
