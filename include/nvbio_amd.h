@@ -589,6 +589,70 @@ nvbio_status nvbio_qgroup_index_export(nvbio_qgram_index_t index, uint32_t* I_ou
                                        void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * sufsort: the suffix sort and the BWT of a string set and of a string (nvbio/sufsort/sufsort.h: cuda::suffix_sort( string_set ),
+ * cuda::bwt( string_set ), the engine of nvSetBWT; cuda::suffix_sort( string ), cuda::bwt( string ), find_primary).
+ * csrc/sufsort.hip (sets), csrc/fm_build.hip (strings).
+ *
+ * String sets (plain sets of N strings of lengths len_i, in any form of nvbio_string_set; seed enumerations are rejected):
+ *   suffix   (pos, string_id) with 0 <= pos <= len_i; pos == len_i is the empty suffix.
+ *   order    by raw symbol value (the whole symbol_bits-wide symbol); a suffix that is a proper prefix of another sorts first (the
+ *            implicit '$', below every symbol); suffixes equal up to and including their ends sort by ascending string_id.  Hence
+ *            the N empty suffixes come first, in string order (sufsort_inl.h:70-135: a stable LSD sort from string-major order with
+ *            SetSuffixFlattener's empty suffixes; sufsort_inl.h:535-560: the "dollar" block first).
+ *   bwt      bwt[r] = the symbol in front of the r-th sorted suffix, 255 when pos == 0 (string_set_bwt_functor,
+ *            sufsort_priv.h:881-904); one byte per suffix, sum( len_i + 1 ) of them.
+ *   flag     NVBIO_SUFSORT_NO_EMPTY_SUFFIXES drops the N empty suffixes from every output: sum( len_i ) entries.
+ *   global   the reference's global suffix index (what its SuffixHandler consumes): pos + the exclusive sum of (len_j + 1), or of
+ *            len_j under the flag, over the strings j before string_id.
+ * Departures from the reference: the method.  The reference sorts all suffixes once per 14-symbol word, least significant word
+ * first; this library sorts the first word once and refines only the suffixes that still tie (csrc/sufsort.hip).  The order is the
+ * one stated above in every case, and two calls give equal bytes.
+ * Limits (NVBIO_ERR_INVALID otherwise): symbol_bits 2, 4 or 8; sum( len_i + 1 ) < 2^32 - 1, with or without the flag; N = 0 and
+ * strings of length 0 are valid.  Out of scope: the reference's host-memory-bounded large_bwt, its BWT file writers, and an
+ * FM-index over a read set.
+ * Working storage: each call allocates its own and frees it before it returns; each call synchronizes.  An output capacity (in
+ * suffixes) below the count fails with the needed size in nvbio_amd_last_error, before any sort work.
+ *
+ * Strings (2-bit big-endian packed texts, as nvbio_fm_index_build takes them): the sorter of the index build, with repeats of up to
+ * 2^20 symbols.
+ * ------------------------------------------------------------------------------------------- */
+enum { NVBIO_SUFSORT_NO_EMPTY_SUFFIXES = 1 };
+
+/* the work a set sort did, so that tests and benchmarks can see it without timing it */
+typedef struct
+{
+    uint32_t n_suffixes;
+    uint32_t rounds;                /* sorts run: round 0 over every suffix, round k > 0 over the suffixes still tied after k words */
+    uint32_t sorted_per_round[16];  /* the suffixes that entered round k's sort (the first 16 rounds) */
+    uint32_t symbols_per_word;      /* 29 (2-bit), 15 (4-bit) or 7 (8-bit) symbols per 64-bit key word */
+    uint64_t peak_bytes;            /* the most device memory the call held at once, outputs excluded */
+} nvbio_sufsort_stats;
+
+/* the number of suffixes the two calls below write */
+nvbio_status nvbio_set_suffix_count(int device, const nvbio_string_set* set, uint32_t flags, uint32_t* n_suffixes, void* stream);
+/* suffixes_dev[r] = (pos, string_id) of the r-th suffix, global_dev[r] (may be NULL) its global index; both hold `capacity` entries.
+ * stats may be NULL. */
+nvbio_status nvbio_set_suffix_sort(int device, const nvbio_string_set* set, uint32_t flags, nvbio_uint2* suffixes_dev, uint32_t* global_dev,
+                                   uint64_t capacity, uint32_t* n_suffixes, nvbio_sufsort_stats* stats, void* stream);
+/* the same sort in the form the reference's suffix handler takes (process( n_suffixes, suffix_array, string_ids, cum_lengths )), all in
+ * device memory: suffix_array_dev[r] = the global index of the r-th suffix, string_ids_dev[r] (may be NULL) its string, both of `capacity`
+ * entries; cum_lengths_dev[i] (may be NULL, set->n entries) = the suffixes of the strings up to and including i. */
+nvbio_status nvbio_set_suffix_sort_flat(int device, const nvbio_string_set* set, uint32_t flags, uint32_t* suffix_array_dev, uint32_t* string_ids_dev,
+                                        uint32_t* cum_lengths_dev, uint64_t capacity, uint32_t* n_suffixes, nvbio_sufsort_stats* stats, void* stream);
+/* bwt_dev[r] = the symbol in front of the r-th suffix (255 in front of a string), suffixes_dev (may be NULL) as above */
+nvbio_status nvbio_set_bwt(int device, const nvbio_string_set* set, uint32_t flags, uint8_t* bwt_dev, nvbio_uint2* suffixes_dev,
+                           uint64_t capacity, uint32_t* n_suffixes, nvbio_sufsort_stats* stats, void* stream);
+
+/* cuda::suffix_sort( string ): sa_dev[length + 1], the suffix array in the convention of nvbio/fmindex/bwt.h:28-37 (row 0 = the empty
+ * suffix, sa_dev[0] = length).  length > 0.  Repeats of up to 2^20 symbols are sorted (the most the sorter's doubling rounds take; the
+ * index build's default of 4096 does not apply here); a text with a longer one is NVBIO_ERR_UNSUPPORTED.  Synchronizes. */
+nvbio_status nvbio_suffix_sort(const uint32_t* text2_dev, uint32_t length, int device, uint32_t* sa_dev, void* stream);
+/* cuda::bwt( string ) and find_primary: bwt_words_dev[ceil( length / 16 )], the BWT 2-bit big-endian packed with the primary row
+ * squeezed out (bwt.h:41-53) -- exactly the words nvbio_fm_index_build interleaves with its occurrence counts -- and *primary, the
+ * row of '$'.  Synchronizes. */
+nvbio_status nvbio_bwt(const uint32_t* text2_dev, uint32_t length, int device, uint32_t* bwt_words_dev, uint32_t* primary, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * seed hits -> candidate windows: the two index-arithmetic functors between FMIndexFilter::locate
  * and the banded aligner in the reference's smallest seed-and-extend caller (examples/fmmap/fmmap.cu)
  * ------------------------------------------------------------------------------------------- */

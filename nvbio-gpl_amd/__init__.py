@@ -11,6 +11,7 @@ argument meaning as the reference's C++ templates --
     QGramIndex, QGramSetIndex    nvbio::QGramIndexDevice / QGramSetIndexDevice (nvbio/qgram/qgram.h, qgram_inl.h)
     QGroupIndex, QGroupSetIndex  nvbio::QGroupIndexDevice (nvbio/qgram/qgroup.h, qgroup_inl.h) and its set form
     QGramFilter, generate_qgrams nvbio::QGramFilter<device_tag,...>        (nvbio/qgram/filter.h, filter_inl.h)
+    set_suffix_sort, set_bwt, suffix_sort, bwt  cuda::suffix_sort / cuda::bwt of string sets and strings (nvbio/sufsort/sufsort.h)
     SimpleGotohScheme, GotohAligner, BestSink semantics                    (nvbio/alignment/utils.h:103-123, alignment.h:437-449)
     BatchedBandedAlignmentScore, batch_banded_alignment_score              (nvbio/alignment/batched.h:104-298)
 
@@ -862,6 +863,98 @@ class QGroupSetIndex(QGroupIndex):
         _check(lib().nvbio_qgroup_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size),
                                                   ctypes.c_uint32(seed_interval), ctypes.byref(h), _stream_ptr(dev)))
         return cls(h, dev, keep=(string_set,))
+
+
+# ---- sufsort -------------------------------------------------------------------------------------
+SUFSORT_NO_EMPTY_SUFFIXES = 1
+
+
+class _SufsortStats(ctypes.Structure):
+    _fields_ = [("n_suffixes", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("sorted_per_round", ctypes.c_uint32 * 16),
+                ("symbols_per_word", ctypes.c_uint32), ("peak_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return dict(n_suffixes=self.n_suffixes, rounds=self.rounds, sorted_per_round=list(self.sorted_per_round),
+                    symbols_per_word=self.symbols_per_word, peak_bytes=self.peak_bytes)
+
+
+def set_suffix_count(string_set, flags=0):
+    """nvbio_set_suffix_count: the suffixes set_suffix_sort / set_bwt write: sum( len + 1 ), or sum( len ) with
+    SUFSORT_NO_EMPTY_SUFFIXES"""
+    n = ctypes.c_uint32(0)
+    ss = string_set.c_struct()
+    dev = string_set.device
+    _check(lib().nvbio_set_suffix_count(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), ctypes.byref(n), _stream_ptr(dev)))
+    return n.value
+
+
+def set_suffix_sort(string_set, flags=0, want_global=True, capacity=None):
+    """cuda::suffix_sort( string_set ) (nvbio/sufsort/sufsort.h; nvbio_set_suffix_sort): (suffixes int32 [n, 2] = (pos, string_id) in
+    sorted order, global int32 [n] = the reference's global suffix indices or None, stats dict); uint bit patterns.  The order is
+    stated in include/nvbio_amd.h.  capacity: the entries to allocate (default: the count)"""
+    torch = _torch()
+    dev = string_set.device
+    cap = set_suffix_count(string_set, flags) if capacity is None else int(capacity)
+    suf = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)
+    glb = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_global else None
+    n, st = ctypes.c_uint32(0), _SufsortStats()
+    ss = string_set.c_struct()
+    _check(lib().nvbio_set_suffix_sort(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), _ptr(suf), _ptr(glb),
+                                       ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(st), _stream_ptr(dev)))
+    return suf[:n.value], (glb[:n.value] if want_global else None), st.as_dict()
+
+
+def set_suffix_sort_flat(string_set, flags=0):
+    """the sort in the form the reference's suffix handler takes (nvbio_set_suffix_sort_flat): (suffix_array int32 [n] = global suffix
+    indices in sorted order, string_ids int32 [n], cum_lengths int32 [N] = the inclusive scan of the strings' suffix counts, stats)"""
+    torch = _torch()
+    dev = string_set.device
+    cap = set_suffix_count(string_set, flags)
+    sa = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    ids = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    cum = torch.empty(max(string_set.n, 1), dtype=torch.int32, device=dev)
+    n, st = ctypes.c_uint32(0), _SufsortStats()
+    ss = string_set.c_struct()
+    _check(lib().nvbio_set_suffix_sort_flat(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), _ptr(sa), _ptr(ids), _ptr(cum),
+                                            ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(st), _stream_ptr(dev)))
+    return sa[:n.value], ids[:n.value], cum[:string_set.n], st.as_dict()
+
+
+def set_bwt(string_set, flags=0, want_suffixes=True, capacity=None):
+    """cuda::bwt( string_set ) (the engine of nvSetBWT; nvbio_set_bwt): (bwt uint8 [n], the symbol in front of each sorted suffix, 255
+    in front of a string; suffixes int32 [n, 2] or None; stats dict)"""
+    torch = _torch()
+    dev = string_set.device
+    cap = set_suffix_count(string_set, flags) if capacity is None else int(capacity)
+    bwt = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    suf = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev) if want_suffixes else None
+    n, st = ctypes.c_uint32(0), _SufsortStats()
+    ss = string_set.c_struct()
+    _check(lib().nvbio_set_bwt(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), _ptr(bwt), _ptr(suf),
+                               ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(st), _stream_ptr(dev)))
+    return bwt[:n.value], (suf[:n.value] if want_suffixes else None), st.as_dict()
+
+
+def suffix_sort(text2, length, device="cuda:0"):
+    """cuda::suffix_sort( string ) (nvbio_suffix_sort): the suffix array int32 [length + 1] of a 2-bit packed text, row 0 = the empty
+    suffix (nvbio/fmindex/bwt.h:28-37); uint bit patterns"""
+    torch = _torch()
+    t = _dev_tensor(text2, torch.int32, device)
+    sa = torch.empty(int(length) + 1, dtype=torch.int32, device=device)
+    _check(lib().nvbio_suffix_sort(_ptr(t), ctypes.c_uint32(length), FMIndex._dev_index(device), _ptr(sa), _stream_ptr(device)))
+    return sa
+
+
+def bwt(text2, length, device="cuda:0"):
+    """cuda::bwt( string ) with find_primary (nvbio_bwt): (bwt words int32 [ceil( length / 16 )], 2-bit big-endian packed with the
+    primary row squeezed out, as nvbio_fm_index_build interleaves them; primary)"""
+    torch = _torch()
+    t = _dev_tensor(text2, torch.int32, device)
+    words = torch.empty((int(length) + 15) // 16, dtype=torch.int32, device=device)
+    primary = ctypes.c_uint32(0)
+    _check(lib().nvbio_bwt(_ptr(t), ctypes.c_uint32(length), FMIndex._dev_index(device), _ptr(words), ctypes.byref(primary),
+                           _stream_ptr(device)))
+    return words, primary.value
 
 
 _GENERATE_TEMP = {}

@@ -128,11 +128,13 @@ private:
 
 // RAII for the hipMalloc temporaries of an index build (not the stream scratch above): every buffer it allocated and was not told to
 // forget (ownership handed over) is freed when it goes out of scope.  In check mode each buffer is filled (no guard bands) before it is handed out.
-// `what` names the build in NVB_ALLOC's out-of-memory message.
+// `what` names the build in NVB_ALLOC's out-of-memory message.  It counts the bytes it holds (`live`) and the most it ever held (`peak`).
 struct BuildBuffers
 {
-    std::vector<void*> ptrs;
-    const char*        what;
+    std::vector<void*>  ptrs;
+    std::vector<size_t> sizes;                                // of ptrs, in order
+    uint64_t            live = 0, peak = 0;
+    const char*         what;
     explicit BuildBuffers(const char* what = "index build") : what( what ) {}
     ~BuildBuffers() { for (void* p : ptrs) (void)hipFree( p ); }
     template <typename T> T* alloc(size_t count)            // nullptr when out of memory
@@ -140,20 +142,22 @@ struct BuildBuffers
         void* p = nullptr;
         const size_t bytes = (count ? count : 1) * sizeof(T);
         if (hipMalloc( &p, bytes ) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        ptrs.push_back( p );
+        ptrs.push_back( p ); sizes.push_back( bytes );
+        live += bytes; if (live > peak) peak = live;
         if (scratch_check_enabled() && (hipMemset( p, scratch_check_fill(), bytes ) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
         {
             (void)hipGetLastError(); return nullptr;
         }
         return (T*)p;
     }
-    void release(void* p)
+    void release(void* p) { if (drop( p )) (void)hipFree( p ); }
+    void forget(void* p)  { (void)drop( p ); }
+private:
+    bool drop(void* p)
     {
-        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { (void)hipFree( p ); ptrs.erase( ptrs.begin() + i ); return; }
-    }
-    void forget(void* p)
-    {
-        for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase( ptrs.begin() + i ); return; }
+        for (size_t i = 0; i < ptrs.size(); ++i)
+            if (ptrs[i] == p) { live -= sizes[i]; ptrs.erase( ptrs.begin() + i ); sizes.erase( sizes.begin() + i ); return true; }
+        return false;
     }
 };
 

@@ -20,7 +20,7 @@
 //   3. BWT words, per-block symbol counts, their exclusive scan (occ), L2 and the SSA are one
 //      pass each over the sorted positions.
 #include "fm_device.h"
-#include <rocprim/rocprim.hpp>
+#include "build_prims.h"
 #include <vector>
 #include <stdlib.h>
 #include <stdio.h>
@@ -86,7 +86,6 @@ head_from_keys_kernel(const uint64_t* __restrict__ keys, const uint64_t n, uint3
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (uint64_t)gridDim.x * blockDim.x)
         head[s] = (s == 0 || keys[s] != keys[s - 1]) ? (uint32_t)s : 0u;
 }
-__global__ void patch_first_kernel(uint32_t* p, const uint32_t* carry) { if (*carry > *p) *p = *carry; }
 
 // unresolved[s] = 1 iff the segment of slot s has more than one element (seg = head slot of s)
 struct Unresolved
@@ -224,10 +223,6 @@ struct AddU4
     __device__ __host__ __forceinline__ uint4 operator()(const uint4 a, const uint4 b) const
     { return make_uint4( a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w ); }
 };
-struct MaxU32
-{
-    __device__ __host__ __forceinline__ uint32_t operator()(const uint32_t a, const uint32_t b) const { return a > b ? a : b; }
-};
 __global__ void __launch_bounds__(256)
 write_occ_kernel(const uint4* __restrict__ occ, const uint32_t n_blocks, uint32_t* __restrict__ bwt_occ)
 {
@@ -243,70 +238,15 @@ ssa_kernel(const uint32_t* __restrict__ sa, const uint32_t sa_int, const uint64_
 
 // ---- index-build temporaries (BuildBuffers and NVB_ALLOC, common.h) ------------------------------
 
-// inclusive max-scan in place, in chunks small enough for 32-bit-sized device primitives
-static nvbio_status scan_max_inplace(uint32_t* buf, uint64_t n, BuildBuffers& bufs, hipStream_t s)
+// The suffixes of the text in sorted order: sa[n] = rows 1..n of the full suffix array (row 0 is the empty suffix), a buffer of
+// `bufs`.  Steps 1 and 2 of the header comment; max_lcp and bucket_symbols as in nvbio_fm_build_options.
+static nvbio_status sort_text_suffixes(BuildBuffers& bufs, const TextView t, uint32_t max_lcp, const uint32_t bucket_symbols, hipStream_t s,
+                                       uint32_t*& sa_out)
 {
-    const uint64_t CHUNK = 1ull << 30;
-    size_t temp_bytes = 0;
-    NVB_HIP( rocprim::inclusive_scan( nullptr, temp_bytes, buf, buf, (size_t)(n < CHUNK ? n : CHUNK), MaxU32(), s ) );
-    NVB_ALLOC( temp, uint8_t, temp_bytes );
-    for (uint64_t b = 0; b < n; b += CHUNK)
-    {
-        const size_t len = (size_t)((n - b) < CHUNK ? (n - b) : CHUNK);
-        if (b) NVB_CHECK( NVB_LAUNCH( patch_first_kernel, dim3(1), dim3(1), s, buf + b, buf + b - 1 ) );
-        NVB_HIP( rocprim::inclusive_scan( temp, temp_bytes, buf + b, buf + b, len, MaxU32(), s ) );
-    }
-    bufs.release( temp );
-    return NVBIO_OK;
-}
-
-// out[0..count) = { i in [0,n) : pred(i) } in increasing order, chunked; *count on the host
-template <typename Pred>
-static nvbio_status select_indices(const uint64_t n, Pred pred, uint32_t* out, uint64_t* count, BuildBuffers& bufs, hipStream_t s)
-{
-    const uint64_t CHUNK = 1ull << 30;
-    NVB_ALLOC( d_cnt, size_t, 1 );
-    size_t temp_bytes = 0;
-    NVB_HIP( rocprim::select( nullptr, temp_bytes, rocprim::counting_iterator<uint32_t>( 0 ), out, d_cnt,
-                              (size_t)(n < CHUNK ? n : CHUNK), pred, s ) );
-    NVB_ALLOC( temp, uint8_t, temp_bytes );
-    uint64_t total = 0;
-    for (uint64_t b = 0; b < n; b += CHUNK)
-    {
-        const size_t len = (size_t)((n - b) < CHUNK ? (n - b) : CHUNK);
-        NVB_HIP( rocprim::select( temp, temp_bytes, rocprim::counting_iterator<uint32_t>( (uint32_t)b ), out + total, d_cnt, len, pred, s ) );
-        size_t c = 0;
-        NVB_HIP( hipMemcpyAsync( &c, d_cnt, sizeof(size_t), hipMemcpyDeviceToHost, s ) );
-        NVB_HIP( hipStreamSynchronize( s ) );
-        total += c;
-    }
-    *count = total;
-    bufs.release( temp ); bufs.release( d_cnt );
-    return NVBIO_OK;
-}
-
-static nvbio_status sort_pairs(uint64_t* keys_in, uint64_t* keys_out, uint32_t* vals_in, uint32_t* vals_out, size_t n,
-                               unsigned begin_bit, unsigned end_bit, BuildBuffers& bufs, hipStream_t s)
-{
-    size_t temp_bytes = 0;
-    NVB_HIP( rocprim::radix_sort_pairs( nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, s ) );
-    NVB_ALLOC( temp, uint8_t, temp_bytes );
-    NVB_HIP( rocprim::radix_sort_pairs( temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, s ) );
-    NVB_HIP( hipStreamSynchronize( s ) );
-    bufs.release( temp );
-    return NVBIO_OK;
-}
-
-static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, const int device, const uint32_t kmer_len,
-                               const uint32_t sa_int, uint32_t max_lcp, const bool verify, const uint32_t table_flags, const uint32_t bucket_symbols,
-                               hipStream_t s, nvbio_fm_index_t* out)
-{
-    BuildBuffers bufs;
+    const uint32_t n = t.n;
     if (max_lcp == 0) max_lcp = 4096;
     if (max_lcp > (1u << 20)) max_lcp = 1u << 20;
     if (max_lcp > 0xFFFFFFFFu - n - 64u) max_lcp = 0xFFFFFFFFu - n - 64u;       // rank + h must not wrap
-
-    TextView t; t.words = text2_dev; t.n = n; t.n_words = (n + 15u) / 16u;
 
     // ---- 1. bucketed sort of (32-mer key, position) ------------------------------------------
     uint32_t bsym = 0;                                          // symbols used for bucketing (<= 4 -> <= 256 buckets)
@@ -429,6 +369,18 @@ static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, cons
         bufs.release( vals ); bufs.release( newseg ); bufs.release( sel ); bufs.release( U2 );
     }
     bufs.release( U ); bufs.release( seg );
+    sa_out = sa;
+    return NVBIO_OK;
+}
+
+static nvbio_status build_impl(const uint32_t* text2_dev, const uint32_t n, const int device, const uint32_t kmer_len,
+                               const uint32_t sa_int, const uint32_t max_lcp, const bool verify, const uint32_t table_flags, const uint32_t bucket_symbols,
+                               hipStream_t s, nvbio_fm_index_t* out)
+{
+    BuildBuffers bufs;
+    TextView t; t.words = text2_dev; t.n = n; t.n_words = (n + 15u) / 16u;
+    uint32_t* sa = nullptr;
+    NVB_CHECK( sort_text_suffixes( bufs, t, max_lcp, bucket_symbols, s, sa ) );
 
     // ---- 3. BWT, occ, L2, SSA ---------------------------------------------------------------
     const uint32_t words    = ((t.n_words + 3u) & ~3u);          // padded to whole 64-symbol blocks
@@ -620,6 +572,42 @@ static nvbio_status save_impl(const nvbio_fm_index_view& v, const char* bwt_path
     return NVBIO_OK;
 }
 
+// A plain suffix sort takes the longest repeats the doubling rounds support (the build's own default, 4096, is a guard for an index
+// build that would rather fail fast): sort_text_suffixes clamps max_lcp to 2^20.
+static const uint32_t SORT_MAX_LCP = 1u << 20;
+
+// the single-string entries of the sufsort module (nvbio/sufsort/sufsort.h: cuda::suffix_sort( string ), cuda::bwt( string )) over
+// the sorter above
+static nvbio_status suffix_sort_impl(const uint32_t* text2_dev, const uint32_t n, uint32_t* sa_dev, hipStream_t s)
+{
+    BuildBuffers bufs( "suffix sort" );
+    TextView t; t.words = text2_dev; t.n = n; t.n_words = (n + 15u) / 16u;
+    uint32_t* sa = nullptr;
+    NVB_CHECK( sort_text_suffixes( bufs, t, SORT_MAX_LCP, 0u, s, sa ) );
+    NVB_HIP( hipMemcpyAsync( sa_dev, &n, sizeof(uint32_t), hipMemcpyHostToDevice, s ) );          // row 0: the empty suffix
+    NVB_HIP( hipMemcpyAsync( sa_dev + 1, sa, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s ) );
+    NVB_HIP( hipStreamSynchronize( s ) );
+    return NVBIO_OK;
+}
+
+static nvbio_status bwt_impl(const uint32_t* text2_dev, const uint32_t n, uint32_t* bwt_words_dev, uint32_t* primary, hipStream_t s)
+{
+    BuildBuffers bufs( "bwt" );
+    TextView t; t.words = text2_dev; t.n = n; t.n_words = (n + 15u) / 16u;
+    uint32_t* sa = nullptr;
+    NVB_CHECK( sort_text_suffixes( bufs, t, SORT_MAX_LCP, 0u, s, sa ) );
+    const uint32_t words = ((t.n_words + 3u) & ~3u);
+    NVB_ALLOC( d_primary, uint32_t, 1 );
+    NVB_HIP( hipMemsetAsync( d_primary, 0, sizeof(uint32_t), s ) );
+    NVB_CHECK( NVB_LAUNCH( find_primary_kernel, dim3( grid_for( n ) ), dim3(256), s, (const uint32_t*)sa, (uint64_t)n, d_primary ) );
+    NVB_ALLOC( bwt_occ, uint32_t, (size_t)words * 2u );
+    NVB_CHECK( NVB_LAUNCH( bwt_words_kernel, dim3( grid_for( words ) ), dim3(256), s, t, (const uint32_t*)sa, (const uint32_t*)d_primary, words, bwt_occ, (uint4*)nullptr ) );
+    NVB_CHECK( NVB_LAUNCH( deinterleave_bwt_kernel, dim3( grid_for( t.n_words ) ), dim3(256), s, (const uint32_t*)bwt_occ, t.n_words, bwt_words_dev ) );
+    NVB_HIP( hipMemcpyAsync( primary, d_primary, sizeof(uint32_t), hipMemcpyDeviceToHost, s ) );
+    NVB_HIP( hipStreamSynchronize( s ) );
+    return NVBIO_OK;
+}
+
 } // anonymous namespace
 } // namespace nvbio_amd
 
@@ -663,4 +651,22 @@ extern "C" nvbio_status nvbio_fm_index_build(const uint32_t* text2_dev, uint32_t
     NVB_REQUIRE( !options || options->bucket_symbols <= 5u, "bucket_symbols must be 0 (automatic) or 1 + a value in 0..4" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     return build_impl( text2_dev, length, device, kmer_len, sa_int, max_lcp, verify, options ? options->table_flags : 0u, options ? options->bucket_symbols : 0u, (hipStream_t)stream, out );
+}
+
+extern "C" nvbio_status nvbio_suffix_sort(const uint32_t* text2_dev, uint32_t length, int device, uint32_t* sa_dev, void* stream)
+{
+    NVB_REQUIRE( text2_dev && sa_dev, "text2_dev/sa_dev is NULL" );
+    NVB_REQUIRE( length > 0, "empty text" );
+    NVB_REQUIRE( length <= 0xFFFFFFFFu - 8192u, "text too long for 32-bit coordinates" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return suffix_sort_impl( text2_dev, length, sa_dev, (hipStream_t)stream );
+}
+
+extern "C" nvbio_status nvbio_bwt(const uint32_t* text2_dev, uint32_t length, int device, uint32_t* bwt_words_dev, uint32_t* primary, void* stream)
+{
+    NVB_REQUIRE( text2_dev && bwt_words_dev && primary, "text2_dev/bwt_words_dev/primary is NULL" );
+    NVB_REQUIRE( length > 0, "empty text" );
+    NVB_REQUIRE( length <= 0xFFFFFFFFu - 8192u, "text too long for 32-bit coordinates" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return bwt_impl( text2_dev, length, bwt_words_dev, primary, (hipStream_t)stream );
 }

@@ -20,6 +20,8 @@
 //   QGramFilterDevice<index_type>  ~ nvbio::QGramFilter<device_tag,index,...> (nvbio/qgram/filter.h, filter_inl.h:336-483):
 //                                    rank(index, n_queries, queries, indices) -> n_hits ; locate(begin, end, hits) ;
 //                                    merge(interval, n_hits, hits, merged_hits, merged_counts) -> n_merged
+//   cuda::suffix_sort, cuda::bwt, cuda::find_primary
+//                                  ~ nvbio/sufsort/sufsort.h: of a string set through the reference's output handlers, and of a string
 //   aln::SimpleGotohScheme, aln::GotohAligner<TYPE,scheme>, aln::make_gotoh_aligner<TYPE>()
 //                                  ~ nvbio/alignment/utils.h:103-123, alignment.h:437-462
 //   aln::BatchedBandedAlignmentScore<BAND, stream, AmdDeviceScheduler>
@@ -597,6 +599,62 @@ private:
     device_vector<uint64_t>   m_slots;
     device_vector<uint8_t>    m_temp;
 };
+
+// ---- sufsort (nvbio/sufsort/sufsort.h) -------------------------------------------------------------
+// The reference's entry points live in nvbio::cuda; so do these.  The order, the BWT bytes and the flag are those of
+// include/nvbio_amd.h ("sufsort"); the handlers are the reference's concepts, called once with the whole result.
+namespace cuda {
+
+// cuda::suffix_sort( string_set, output ): output.process( n_suffixes, suffix_array, string_ids, cum_lengths ) with device pointers:
+// suffix_array[r] = the global index of the r-th suffix, string_ids[r] = its string, cum_lengths[i] = the suffixes of the strings up to
+// and including i (SetSuffixFlattener's inclusive scan).  The library writes all three on the device; nothing crosses to the host.
+template <typename output_handler>
+inline void suffix_sort(const string_set& set, output_handler& output, uint32_t flags = 0u, int device = 0, hipStream_t stream = 0,
+                        nvbio_sufsort_stats* stats = nullptr)
+{
+    uint32_t n = 0;
+    check( nvbio_set_suffix_count( device, &set.c, flags, &n, stream ) );
+    device_vector<uint32_t> suffix_array( n ), string_ids( n ), cum_lengths( set.c.n );
+    check( nvbio_set_suffix_sort_flat( device, &set.c, flags, suffix_array.data(), string_ids.data(), cum_lengths.data(), n, &n, stats, stream ) );
+    output.process( n, (const uint32_t*)suffix_array.data(), (const uint32_t*)string_ids.data(), (const uint32_t*)cum_lengths.data() );
+}
+
+// cuda::bwt( string_set, output ): output.process( n_suffixes, h_bwt, d_bwt, h_suffixes, d_suffixes, d_indices ): the BWT bytes and the
+// (pos, string_id) pairs on the host and on the device; d_indices is NULL (the reference passes the slots of its blockwise sorter)
+template <typename output_handler>
+inline void bwt(const string_set& set, output_handler& output, uint32_t flags = 0u, int device = 0, hipStream_t stream = 0,
+                nvbio_sufsort_stats* stats = nullptr)
+{
+    uint32_t n = 0;
+    check( nvbio_set_suffix_count( device, &set.c, flags, &n, stream ) );
+    device_vector<uint8_t>     d_bwt( n );
+    device_vector<nvbio_uint2> d_suf( n );
+    check( nvbio_set_bwt( device, &set.c, flags, d_bwt.data(), d_suf.data(), n, &n, stats, stream ) );
+    const std::vector<uint8_t>     h_bwt = d_bwt.to_host();
+    const std::vector<nvbio_uint2> h_suf = d_suf.to_host();
+    output.process( n, h_bwt.data(), (const uint8_t*)d_bwt.data(), h_suf.data(), (const nvbio_uint2*)d_suf.data(), (const uint32_t*)nullptr );
+}
+
+// cuda::suffix_sort( string_len, string, output ): sa_dev[string_len + 1], row 0 = the empty suffix (nvbio/fmindex/bwt.h:28-37)
+inline void suffix_sort(uint32_t string_len, const uint32_t* text2_dev, uint32_t* sa_dev, int device = 0, hipStream_t stream = 0)
+{ check( nvbio_suffix_sort( text2_dev, string_len, device, sa_dev, stream ) ); }
+
+// cuda::bwt( string_len, string, output ): bwt_words_dev[ceil( string_len / 16 )], the primary row squeezed out; returns primary
+inline uint32_t bwt(uint32_t string_len, const uint32_t* text2_dev, uint32_t* bwt_words_dev, int device = 0, hipStream_t stream = 0)
+{
+    uint32_t primary = 0;
+    check( nvbio_bwt( text2_dev, string_len, device, bwt_words_dev, &primary, stream ) );
+    return primary;
+}
+
+// cuda::find_primary( string_len, string ): the row of the whole string among the sorted suffixes
+inline uint32_t find_primary(uint32_t string_len, const uint32_t* text2_dev, int device = 0, hipStream_t stream = 0)
+{
+    device_vector<uint32_t> words( ((size_t)string_len + 15u) / 16u );
+    return bwt( string_len, text2_dev, words.data(), device, stream );
+}
+
+} // namespace cuda
 
 namespace aln {
 
