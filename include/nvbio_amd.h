@@ -1003,6 +1003,8 @@ enum
                                                several-lanes-per-job kernel (boundary in registers, no scratch) applies (A/B)                           */
     NVBIO_ALN_NO_F16_DP             = 16384, /* packed band-31 DP with 16-bit INTEGER lanes even where the binary16 lanes (exact while every score is an integer of
                                                magnitude <= 2040; one operation less per cell) would do (A/B)                                           */
+    NVBIO_ALN_SPLIT_CHANCES         = 131072, /* band-31 end-to-end scoring: the second chance and the gap chance as two launches, one after the other,
+                                                instead of one launch with the two roles interleaved (chances_e2e31_kernel) (A/B)                      */
     NVBIO_ALN_NO_NARROW_TRACEBACK   = 64   /* band-31 end-to-end traceback: every DP over the whole band (no band-15 route for the jobs
                                               whose optimal paths provably stay within 7 diagonals of the sink)                  */
 };

@@ -681,7 +681,7 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
 // the gap chance's cost ladder (gap_chance_e2e31_kernel): the cheapest class of gapped alignments it neither evaluates nor rules out, with P the
 // least a mismatch can cost and gaps of up to GAP_CHANCE_GA symbols evaluated
 constexpr int GAP_CHANCE_GA = 5;
-__device__ __forceinline__ int32_t gap_chance_unknown_cost(const int32_t P, const int32_t go, const int32_t ge)
+__host__ __device__ __forceinline__ int32_t gap_chance_unknown_cost(const int32_t P, const int32_t go, const int32_t ge)
 {
     auto cg = [&](const int g) -> int32_t { return -(go + (g - 1) * ge); };
     int32_t c = cg( 1 ) + 3 * P;                                  // one gap and three mismatches
@@ -689,6 +689,19 @@ __device__ __forceinline__ int32_t gap_chance_unknown_cost(const int32_t P, cons
     #pragma unroll
     for (int k = 0; k < 5; ++k) c = others[k] < c ? others[k] : c;
     return c;
+}
+// what the gap chance needs of the ladder beyond the kernel's own arguments, computed ONCE on the host (it depends on the scheme only, and
+// `cap` is a 64-bit division that every wave used to expand: two v_rcp_f32 and some 160 scalar instructions): c_unk for a job that brings its best diagonal (need_dp = 2)
+// and for one that does not (need_dp = 4: every diagonal has more than `cap` mismatches, so the ungapped class costs >= (cap + 1) P)
+struct GapLadder { int32_t c_unk_u, c_unk_n; };
+static GapLadder gap_ladder(const int32_t P, const int32_t G, const int32_t go, const int32_t ge)
+{
+    const int64_t floor_u = 3 * (int64_t)(G < go ? G : go) - P;
+    const int32_t cap = P > 0 ? (int32_t)((-floor_u - 1) / (int64_t)P) : 0;      // (P <= 0: the first pass sends no job to the gap chance)
+    GapLadder l;
+    l.c_unk_u = gap_chance_unknown_cost( P, go, ge );
+    l.c_unk_n = (cap + 1) * P < l.c_unk_u ? (cap + 1) * P : l.c_unk_u;
+    return l;
 }
 
 // ---- the stage's job lists, appended to by the kernels that decide a job's route ----
@@ -1198,7 +1211,7 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
 // one job of the gap chance: returns its flag, 0 (settled: scores / sinks written) or 1 (the DP's); has_u: a third-chance job (need_dp = 2)
 template <int RBITS>
 __device__ __forceinline__ uint32_t
-gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
+gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const bool has_u)
 {
     const uint32_t rid   = b.read_id ? b.read_id[job] : job;
@@ -1246,10 +1259,7 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
     #pragma unroll
     for (int g = 1; g <= GA + 1; ++g) cg[g] = -(go + (g - 1) * ge);
     cg[0] = 0;
-    const int64_t floor_u = 3 * (int64_t)(G < gap_open ? G : gap_open) - P;
-    const int32_t cap = (int32_t)((-floor_u - 1) / (int64_t)P);
-    int32_t c_unk = gap_chance_unknown_cost( P, go, ge );
-    if (!has_u && (cap + 1) * P < c_unk) c_unk = (cap + 1) * P;  // (every OTHER diagonal of a job that brings its best one costs at least that much)
+    const int32_t c_unk = has_u ? lad.c_unk_u : lad.c_unk_n;     // (every OTHER diagonal of a job that brings its best one costs at least c_unk_u)
     const int32_t cost11 = 2 * cg[1], cost12 = cg[1] + cg[2];
 
     // mismatch word k (rows 32 k .. 32 k + 31) of diagonal x: the text planes x symbols on (x is wave-uniform: one funnel shift per plane word)
@@ -1286,6 +1296,7 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
     uint32_t hot = 0;                                            // bit k: slot k's diagonal could be half of a one-gap alignment
     int32_t best_cost = 0x7FFFFFFF; uint32_t best_end = 0;
     bool ex11 = false, ex12 = false;
+    uint32_t lng = 0, nmid = 0;                                  // the two-gap gate's history: bit k = diagonal d - 1 - k is `long` / has NO `mid` (below)
     const int32_t Mi = (int32_t)M;
     // lead_i(a) + tail_j(c) + g >= M with g <= GA needs one of the two at least (M - GA) / 2: only such diagonals are looked at pair by pair
     const int32_t hot_thr = (Mi - GA) / 2;
@@ -1317,6 +1328,7 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
         // indel) holds three mismatches in its first 32 and in its last 32 rows: those two words decide, branch-free; only where some lane of
         // the wave found fewer are the words walked from both ends, as far as some lane still needs
         uint32_t f0 = M, f1 = M, f2 = M, l0 = 0xFFFFFFFFu, l1 = 0xFFFFFFFFu, l2 = 0xFFFFFFFFu;
+        bool mid_d = false;
         if (have)
         {
             uint32_t w = mmw( 0, d );
@@ -1328,6 +1340,7 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
             if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = base + t; w &= ~(1u << t); }
             if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = base + t; w &= ~(1u << t); }
             if (w) l2 = base + 31u - (uint32_t)__builtin_clz( w );
+            mid_d = M >= 96u && mmw( 1, d ) != 0u;               // a mismatch in rows 32 .. 63, all of them rows of the read and below its last 32
         }
         if (have && __any( M > 32u && (f2 == M || l2 == 0xFFFFFFFFu) ))
         {
@@ -1356,6 +1369,7 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
         const int32_t T1 = l1 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l1;
         const int32_t T2 = l2 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l2;
         const bool hot_d = have && (L2 >= hot_thr || T2 >= hot_thr);
+        const bool long_d = have && (L0 >= 30 || T0 >= 30);
 
         if (have && __any( hot_d || (hot & 31u) != 0u ))
         {
@@ -1405,8 +1419,15 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
                 }
         }
         // two gaps around the middle diagonal bm = d - 2 (history slot 1): neighbours bm - 2 (slot 3), bm - 1 (slot 2), bm + 1 (slot 0),
-        // bm + 2 (this diagonal)
-        if (d >= 2u)
+        // bm + 2 (this diagonal).
+        // THE GATE.  Each test below asks whether bm is clean on [lo, hi) with lo <= lead0(a) + 2 and hi >= M - tail0(c) - 2 for neighbours a, c
+        // of bm.  If no neighbour is `long` (lead0 >= 30 or tail0 >= 30) then lo <= 31 and hi >= M - 31; if besides bm has a `mid` (M >= 96 and a
+        // mismatch in rows 32 .. 63) then M - 31 >= 65, so lo < hi, rows 32 .. 63 lie inside [lo, hi) and bm is NOT clean there: all three tests
+        // are false and ex11 / ex12 stay as they are.  The block is skipped for a diagonal where that holds for EVERY lane of the wave: an
+        // unrelated diagonal has its first and last mismatch within a few rows of the ends and one in any 32 rows, so only the diagonals
+        // around some lane's own ones (and those of the few lanes with M < 96) still run it.  Nothing is approximated: a skipped test is a
+        // test whose outcome is known to be "no member".
+        if (d >= 2u && __any( long_d || (lng & 0xDu) != 0u || (nmid & 2u) != 0u ))
         {
             const uint32_t bm = d - 2u;                            // <= 30
             const int32_t NEG = -(1 << 20), POS = 1 << 20;
@@ -1431,6 +1452,8 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
         Lp[0] = (uint32_t)L0 | ((uint32_t)L1 << 8) | ((uint32_t)L2 << 16);
         Tp[0] = (uint32_t)T0 | ((uint32_t)T1 << 8) | ((uint32_t)T2 << 16);
         hot = (hot << 1) | (hot_d ? 1u : 0u);
+        lng = (lng << 1) | (long_d ? 1u : 0u);
+        nmid = (nmid << 1) | (mid_d ? 0u : 1u);
     }
     if (cu < best_cost || (cu == best_cost && cu_end > best_end)) { best_cost = cu; best_end = cu_end; }
     const bool settled = best_cost < c_unk && !(ex11 && cost11 <= best_cost) && !(ex12 && cost12 <= best_cost);
@@ -1442,7 +1465,7 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const 
 // ends as 1 goes on out.dp
 template <int RBITS>
 __global__ void __launch_bounds__(256)
-gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
+gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
                         int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
                         const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count, const JobLists out)
 {
@@ -1459,7 +1482,50 @@ gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, cons
         if (slot0 + 256u * k + threadIdx.x < n)
         {
             const uint32_t job  = job_of( k );
-            const uint32_t flag = gap_chance_e2e31_job<RBITS>( b, P, G, gap_open, gap_ext, scores, sinks, job, need_dp[job] == 2 );
+            const uint32_t flag = gap_chance_e2e31_job<RBITS>( b, P, lad, gap_open, gap_ext, scores, sinks, job, need_dp[job] == 2 );
+            need_dp[job] = (uint8_t)flag;
+            if (flag) which = 0;
+        }
+        app.note( s_lists, k, which );
+    }
+    app.flush( s_lists, out, job_of );
+}
+
+// BOTH chances in one launch: the second chance (list_s) waits for lines in scans of divergent depth, the gap chance (list_t) is bound by VALU
+// issue, neither reads what the other writes (each job is on one list; both only append to out.dp), so the wave slots and issue cycles one
+// leaves idle are the other's.  A workgroup has ONE role, taken from blockIdx.x: with nb2 / nb3 workgroups' worth of jobs on the two lists,
+// workgroup i is the second chance's iff floor( (i + 1) nb2 / (nb2 + nb3) ) > floor( i nb2 / (nb2 + nb3) ) -- an even interleave, nb2 such
+// workgroups among the first nb2 + nb3, spread over the gap chance's whole duration -- and walks chunk floor( i nb2 / (nb2 + nb3) ) of its
+// list (the gap chance's: i minus that).  The jobs run the device functions of the two separate launches, so every job ends as it does there.
+// (Launched over job_list_grid( b.n ) + 1 workgroups -- the lists are disjoint, so nb2 + nb3 <= that --; those past nb2 + nb3 leave at once.)
+template <int RBITS>
+__global__ void __launch_bounds__(256)
+chances_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
+                     int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
+                     const uint32_t* __restrict__ list_s, const uint32_t* __restrict__ count_s,
+                     const uint32_t* __restrict__ list_t, const uint32_t* __restrict__ count_t, const JobLists out)
+{
+    __shared__ JobAppend<1>::Lds s_lists;
+    constexpr uint32_t W = 256u * JOB_LIST_CHUNKS;
+    const uint32_t n2 = *count_s, n3 = *count_t;
+    const uint32_t nb2 = (n2 + W - 1u) / W, nb3 = (n3 + W - 1u) / W, nb = nb2 + nb3;     // (n2, n3 < 2^31: no overflow)
+    if (blockIdx.x >= nb) return;                                    // (the whole workgroup)
+    const uint32_t before = (uint32_t)((uint64_t)blockIdx.x * nb2 / nb);                 // second-chance workgroups in front of this one
+    const bool     second = (uint32_t)((uint64_t)(blockIdx.x + 1u) * nb2 / nb) > before;
+    const uint32_t n      = second ? n2 : n3;
+    const uint32_t* __restrict__ job_list = second ? list_s : list_t;
+    const uint32_t slot0  = (second ? before : blockIdx.x - before) * W;                 // < n: this role has a chunk left (see above)
+    JobAppend<1> app;
+    auto job_of = [&](const int k) -> uint32_t { return job_list[slot0 + 256u * k + threadIdx.x]; };
+    #pragma unroll 1
+    for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
+    {
+        int which = -1;
+        if (slot0 + 256u * k + threadIdx.x < n)
+        {
+            const uint32_t job  = job_of( k );
+            const uint32_t flag = second ? ungapped_e2e31_job<RBITS,1,false>( b, P, G, gap_open, gap_ext, scores, sinks, job, nullptr )
+                                         : gap_chance_e2e31_job<RBITS>( b, P, lad, gap_open, gap_ext, scores, sinks, job, need_dp[job] == 2 );
             need_dp[job] = (uint8_t)flag;
             if (flag) which = 0;
         }
@@ -1619,6 +1685,9 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         // those jobs to the DP.  (NVBIO_ALN_NO_SECOND_CHANCE keeps the first pass from flagging any 3.)
         const bool gapc = !by_quality && !(b.algo & NVBIO_ALN_NO_GAP_CHANCE);
         const uint32_t third_mask = gapc ? ((third ? 1u << 2 : 0u) | 1u << 4) : (third ? 1u << 2 : 0u);
+        // both chances on: ONE launch with the two roles interleaved (chances_e2e31_kernel); NVBIO_ALN_SPLIT_CHANCES keeps them apart (A/B)
+        const bool fused = gapc && third && !(b.algo & (NVBIO_ALN_NO_SECOND_CHANCE | NVBIO_ALN_SPLIT_CHANCES));
+        const GapLadder lad = gap_ladder( P, G, sc.pat_go, sc.pat_ge );
         const dim3 grid( job_list_grid( b.n ) ), block( 256 );
         NVB_HIP( hipMemsetAsync( counts, 0, 3 * JOB_COUNT_STRIDE * sizeof(uint32_t), s ) );
         if (by_quality)
@@ -1627,10 +1696,16 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         else
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                    (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
-        NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                               (const uint32_t*)list_s, count_s, SchemeDev{}, out, 0u ) );
-        if (gapc)
-            NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+        if (fused)
+            NVB_CHECK( NVB_LAUNCH( (chances_e2e31_kernel<RB>), dim3( job_list_grid( b.n ) + 1u ), block, s, b, P, G, lad, sc.pat_go, sc.pat_ge, scores, sinks,
+                                   need_dp, (const uint32_t*)list_s, count_s, (const uint32_t*)list_t, count_t, out ) );
+        else
+            NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
+                                   (const uint32_t*)list_s, count_s, SchemeDev{}, out, 0u ) );
+        if (fused)
+            ;                                                        // (list_t went through the launch above)
+        else if (gapc)
+            NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), grid, block, s, b, P, lad, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                    (const uint32_t*)list_t, count_t, out ) );
         else if (third)
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,2>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
