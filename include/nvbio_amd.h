@@ -365,6 +365,17 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
                                                 uint64_t* keys_dev, nvbio_uint2* residual_ranges_dev, uint32_t* residual_ids_dev,
                                                 uint32_t residual_capacity, uint32_t* counts_dev, void* temp_dev, uint64_t temp_bytes,
                                                 void* stream);
+/* The same pass with the tiles' spans kept: tile t (nvbio_fm_seed_tiles: reads_per_tile = 64 / seeds_per_string consecutive reads,
+ * n_tiles = ceil( reads / reads_per_tile )) owns keys_dev[tile_offsets_dev[t] .. tile_offsets_dev[t + 1]): its forward-strand keys, then its
+ * reverse-strand keys, every one of a read in [t * reads_per_tile, (t + 1) * reads_per_tile).  tile_offsets_dev: n_tiles + 1 uint32 (the
+ * exclusive scan of the per-tile key counts the compaction runs anyway, NULL: not kept); counts_dev[3] = tile_offsets_dev[n_tiles], the
+ * number of keys in tile order.  The keys NVBIO_FM_DEFER_HEAVY appends, [counts_dev[3], counts_dev[0]), belong to no tile's span: a
+ * consumer that relies on the tile order (nvbio_finish_reads) needs counts_dev[3] == counts_dev[0]. */
+nvbio_status nvbio_fm_seed_tiles(const nvbio_string_set* seeds, uint32_t* reads_per_tile, uint32_t* n_tiles);
+nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, const nvbio_string_set* seeds, uint32_t flags, uint32_t read_len,
+                                                      uint64_t* keys_dev, nvbio_uint2* residual_ranges_dev, uint32_t* residual_ids_dev,
+                                                      uint32_t residual_capacity, uint32_t* counts_dev, uint32_t* tile_offsets_dev,
+                                                      void* temp_dev, uint64_t temp_bytes, void* stream);
 /* the k of the canonical two-strand table the handle holds (built with NVBIO_FM_TABLE_CANONICAL: it serves seeds of k .. k + 7 symbols),
  * 0 if it holds none */
 int nvbio_fm_index_is_canonical(nvbio_fm_index_t index);
@@ -1071,6 +1082,36 @@ typedef struct
 } nvbio_mapq_params;
 nvbio_status nvbio_mapq(int device, const uint64_t* best_dev, const uint64_t* second_dev, uint32_t n_reads,
                         const nvbio_mapq_params* params, int32_t* second_scores_dev, uint8_t* mapq_dev, void* stream);
+
+/* nvbio_best_candidate_reduce + nvbio_best_candidate_unpack + nvbio_second_candidate_reduce + nvbio_mapq in ONE pass over a candidate
+ * list that is in TILE ORDER (the per-read score reduction of examples/fmmap/fmmap.cu:367-376 with a total order; nvBowtie's
+ * score_reduce, nvBowtie/bowtie2/cuda/reduce_inl.h:65-140, and io::distinct_alignments, nvbio/io/alignments_inl.h:26-38; BowtieMapq2 /
+ * BowtieMapq3, nvBowtie/bowtie2/cuda/mapq.h:32-297): the same outputs, bit for bit, with no atomic on device memory, no array
+ * the caller has to fill first and every candidate read once.
+ * Tile order: candidate i belongs to read keys_dev[i] >> 34; tile t = the reads [t * reads_per_tile, (t + 1) * reads_per_tile), and ALL
+ * of their candidates are the entries [tile_offsets_dev[t], tile_offsets_dev[t + 1]) of the list, in any order within the tile
+ * (tile_offsets_dev: n_tiles + 1 ascending uint32, [0] = 0, [n_tiles] = n; n_tiles = ceil( n_reads / reads_per_tile ), reads_per_tile
+ * <= 192).  That is the order nvbio_fm_match_seed_diagonals_both_tiled leaves its keys in -- tile t's forward keys, then its reverse
+ * keys -- as long as nothing was appended behind them (counts_dev[3] == counts_dev[0], no residual keys), and the windows / the extension
+ * keep the order of the keys.  A workgroup owns nvbio_finish_reads_tiles_per_group( reads_per_tile ) = 192 / reads_per_tile consecutive
+ * tiles and reduces their candidates in LDS.
+ * Outputs, every entry of every array written (reads without candidates: key 0 and what the separate calls derive from it):
+ *   best_dev / second_dev [n_reads]    the selection keys of nvbio_best_candidate_reduce / nvbio_second_candidate_reduce
+ *   scores_out_dev, end_pos_dev, rc_dev  of nvbio_best_candidate_unpack;  mapq_dev, second_scores_dev  of nvbio_mapq
+ * distinct_dist, worst_score: as nvbio_second_candidate_reduce; params: as nvbio_mapq.  Ragged reads (read_offsets_dev and
+ * min_scores_dev both given): the per-read forms of nvbio_second_candidate_reduce_ragged and nvbio_mapq_ragged( version =
+ * params->version, match ); distinct_dist, worst_score and the other fields of params are ignored then.
+ * The precondition is checked on the device: offsets that do not ascend from 0 to n, or a candidate whose read is not one of its
+ * tile group's, OR 1 into *status_dev (a device word the caller zeroed; it is never cleared here) and that candidate is left out --
+ * the caller reads the word once the stream got there and must discard the outputs when it is set.  n = 0 (pointers to the
+ * candidates may be NULL) writes every read's no-candidate outputs; n_reads = 0 returns at once. */
+nvbio_status nvbio_finish_reads_tiles_per_group(uint32_t reads_per_tile, uint32_t* tiles_per_group);
+nvbio_status nvbio_finish_reads(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
+                                const uint32_t* win_begin_dev, uint64_t n, const uint32_t* tile_offsets_dev, uint32_t n_tiles,
+                                uint32_t reads_per_tile, uint32_t n_reads, uint32_t distinct_dist, int32_t worst_score,
+                                const nvbio_mapq_params* params, int32_t match, const uint32_t* read_offsets_dev, const int32_t* min_scores_dev,
+                                uint64_t* best_dev, uint64_t* second_dev, int32_t* scores_out_dev, int64_t* end_pos_dev, uint8_t* rc_dev,
+                                uint8_t* mapq_dev, int32_t* second_scores_dev, uint32_t* status_dev, void* stream);
 
 /* Paired-end: the genome window in which the opposite mate of an anchored mate is aligned (full-matrix DP),
  * BestOppositeScoreStream::init_context (nvBowtie/bowtie2/cuda/score_inl.h:389-425) with frame_opposite_mate

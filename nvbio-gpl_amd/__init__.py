@@ -427,7 +427,9 @@ class FMIndex:
         """the seed pass of BOTH strands in one launch over the canonical table (nvbio_fm_match_seed_diagonals_both) -> the buffers dict:
         "keys" int64 (the first counts[0]: both strands, tile by tile), "ranges" int32 [2 n, 2] / "ids" int32 [2 n]: residual seeds on
         several rows, forward strand in [0, counts[1]), reverse strand in [n, n + counts[2]); "counts" int32 [6] on the device.
-        inline_hits (2..4): a search that ends on up to that many rows leaves all their keys in "keys" instead of a residual entry."""
+        inline_hits (2..4): a search that ends on up to that many rows leaves all their keys in "keys" instead of a residual entry.
+        "tile_offsets" int32 [n_tiles + 1]: tile t (the reads [t * reads_per_tile, (t + 1) * reads_per_tile)) owns keys[tile_offsets[t] :
+        tile_offsets[t + 1]]; counts[3] = tile_offsets[n_tiles], the keys in tile order (deferred searches append theirs behind them)."""
         torch = _torch()
         n = seeds.n
         if buffers is None:
@@ -444,12 +446,16 @@ class FMIndex:
             nb = ctypes.c_uint64(0)
             _check(lib().nvbio_fm_match_seed_diagonals_both_temp_bytes(ctypes.byref(qs), ctypes.byref(nb)))
             buffers["temp"] = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+            rpt, nt = ctypes.c_uint32(0), ctypes.c_uint32(0)
+            _check(lib().nvbio_fm_seed_tiles(ctypes.byref(qs), ctypes.byref(rpt), ctypes.byref(nt)))
+            buffers["reads_per_tile"], buffers["n_tiles"] = int(rpt.value), int(nt.value)
+            buffers["tile_offsets"] = torch.zeros(int(nt.value) + 1, dtype=torch.int32, device=self.device)
         assert grid_blocks % 64 == 0 and grid_blocks < (1 << 22)
-        _check(lib().nvbio_fm_match_seed_diagonals_both(
+        _check(lib().nvbio_fm_match_seed_diagonals_both_tiled(
             self._h, ctypes.byref(qs), ctypes.c_uint32(flags | (FM_DEFER_HEAVY if defer_heavy else 0) | ((int(inline_hits) & 15) << 8) | ((grid_blocks // 64) << 16)),
             ctypes.c_uint32(read_len),
             _ptr(buffers["keys"]), _ptr(buffers["ranges"]), _ptr(buffers["ids"]), ctypes.c_uint32(n), _ptr(buffers["counts"]),
-            _ptr(buffers["temp"]), ctypes.c_uint64(buffers["temp"].numel()), _stream_ptr(self.device)))
+            _ptr(buffers["tile_offsets"]), _ptr(buffers["temp"]), ctypes.c_uint64(buffers["temp"].numel()), _stream_ptr(self.device)))
         return buffers
 
     def residual_diagonals(self, ranges, ids, cap, seeds_per_read, seed_interval, seed_len, read_len, read_offsets=None, seed_intervals=None):
@@ -1475,6 +1481,81 @@ def mapq(best, second, perfect_score, min_score, monotone, version=2, read_offse
     _check(lib().nvbio_mapq(FMIndex._dev_index(best.device), _ptr(best), _ptr(second) if second is not None else None,
                             ctypes.c_uint32(R), ctypes.byref(prm), _ptr(ss), _ptr(q), _stream_ptr(best.device)))
     return q, ss
+
+
+class FinishStatus:
+    """the device status word of finish_reads calls on one device and its way to the host: the kernel ORs 1 into the word when the candidate
+    list is not in tile order; every call copies the word to pinned memory behind its kernel.  check() raises if a call that has finished
+    reported it (wait = True: after waiting for all of them) -- a pipelined caller looks where it synchronises anyway."""
+    _per_device = {}
+
+    @classmethod
+    def of(cls, device):
+        st = cls._per_device.get(str(device))
+        if st is None:
+            st = cls._per_device[str(device)] = cls(device)
+        return st
+
+    def __init__(self, device):
+        torch = _torch()
+        self.word = torch.zeros(1, dtype=torch.int32, device=device)
+        self.host = torch.zeros(8, dtype=torch.int32, pin_memory=True)
+        self.pending, self.slot = [], 0
+
+    def record(self):
+        torch = _torch()
+        if len(self.pending) == self.host.numel():                   # every slot in flight: the oldest has to land first
+            self.check(wait=True)
+        i = self.slot
+        self.slot = (i + 1) % self.host.numel()
+        self.host[i:i + 1].copy_(self.word, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending.append((ev, i))
+
+    def check(self, wait=False):
+        bad = False
+        while self.pending and (wait or self.pending[0][0].query()):
+            ev, i = self.pending.pop(0)
+            ev.synchronize()
+            bad = bad or int(self.host[i]) != 0
+        if bad:
+            self.pending = []
+            _torch().cuda.synchronize(self.word.device)
+            self.word.zero_()
+            raise RuntimeError("finish_reads: the candidate list is not in tile order (a candidate outside its tile's span, or offsets that "
+                               "do not cover the list): its outputs are invalid")
+
+
+def finish_reads(keys, scores, sinks, wb, tile_offsets, reads_per_tile, n_reads, distinct_dist, worst_score, perfect_score, min_score, monotone,
+                 version=2, read_offsets=None, min_scores=None, match=0, check=True):
+    """nvbio_finish_reads: best_candidate_reduce + best_candidate_unpack + second_candidate_reduce + mapq of a candidate list in tile order (tile t
+    = the reads [t * reads_per_tile, (t + 1) * reads_per_tile), its candidates = entries [tile_offsets[t], tile_offsets[t + 1]) of the list) in
+    one launch -> dict(best, second, best_score, best_pos, best_rc, mapq, second_score).  A list that is not in tile order is reported by the
+    device: check = True waits for the call and raises; check = False leaves that to FinishStatus.of( device ).check()."""
+    torch = _torch()
+    dev, R = tile_offsets.device, int(n_reads)
+    n_tiles = int(tile_offsets.numel()) - 1
+    out = dict(best=torch.empty(R, dtype=torch.int64, device=dev), second=torch.empty(R, dtype=torch.int64, device=dev),
+               best_score=torch.empty(R, dtype=torch.int32, device=dev), best_pos=torch.empty(R, dtype=torch.int64, device=dev),
+               best_rc=torch.empty(R, dtype=torch.uint8, device=dev), mapq=torch.empty(R, dtype=torch.uint8, device=dev),
+               second_score=torch.empty(R, dtype=torch.int32, device=dev))
+    if R == 0:
+        return out
+    st = FinishStatus.of(dev)
+    prm = _MapqParams(int(version), 1 if monotone else 0, int(perfect_score), int(min_score))
+    n = int(keys.numel())
+    _check(lib().nvbio_finish_reads(
+        FMIndex._dev_index(dev), _ptr(keys) if n else None, _ptr(scores) if n else None, _ptr(sinks) if n else None, _ptr(wb) if n else None,
+        ctypes.c_uint64(n), _ptr(tile_offsets), ctypes.c_uint32(n_tiles), ctypes.c_uint32(int(reads_per_tile)), ctypes.c_uint32(R),
+        ctypes.c_uint32(int(distinct_dist)), ctypes.c_int32(int(worst_score)), ctypes.byref(prm), ctypes.c_int32(int(match)),
+        _ptr(read_offsets) if read_offsets is not None else None, _ptr(min_scores) if min_scores is not None else None,
+        _ptr(out["best"]), _ptr(out["second"]), _ptr(out["best_score"]), _ptr(out["best_pos"]), _ptr(out["best_rc"]), _ptr(out["mapq"]),
+        _ptr(out["second_score"]), _ptr(st.word), _stream_ptr(dev)))
+    st.record()
+    if check:
+        st.check(wait=True)
+    return out
 
 
 def opposite_mate_windows(g_pos, anchor_rc, anchor_len, opposite_gapped_len, anchor, genome_len, policy=PE_POLICY_FR,

@@ -586,12 +586,14 @@ fm_seed_pipe_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
     }
 }
 
-// keys of tile t -> keys_out[offsets[t] ...]; the last tile also writes the total.  A few LANES per tile: a tile holds a handful of
+// keys of tile t -> keys_out[offsets[t] ...]; the last tile also writes the total (to counts[0], and to tiled_total and offsets[n_tiles] where
+// the caller keeps the offsets: the end of the last tile's span, which later appends to counts[0] do not move).  A few LANES per tile: a tile holds a handful of
 // keys (3.8 per strand on the benchmark), copied one by one while counts and offsets are read coalesced
 // (one wave per tile, the first version, spent 0.2 ms per launch starting 1.4 M waves that copied four keys each).
 __global__ void __launch_bounds__(256)
 fm_seed_compact_kernel(const uint64_t* __restrict__ tile_keys, const uint32_t* __restrict__ tile_counts, const uint32_t* __restrict__ tile_offsets,
-                       const uint32_t n_tiles, const uint32_t slots, uint64_t* __restrict__ keys_out, unsigned int* __restrict__ counts)
+                       const uint32_t n_tiles, const uint32_t slots, uint64_t* __restrict__ keys_out, unsigned int* __restrict__ counts,
+                       unsigned int* __restrict__ tiled_total, uint32_t* __restrict__ offsets_end)
 {
     // four lanes per tile, each copying every fourth key: a tile of the two-strand pass holds ~8 keys (one lane per tile took 0.25 ms
     // there, one per tile and strand 0.17), of the per-strand pass ~4
@@ -602,7 +604,12 @@ fm_seed_compact_kernel(const uint64_t* __restrict__ tile_keys, const uint32_t* _
         const uint32_t n = tile_counts[tile], off = tile_offsets[tile];
         const uint64_t* src = tile_keys + (uint64_t)tile * slots;
         for (uint32_t k = part; k < n; k += 4u) keys_out[off + k] = src[k];
-        if (tile == n_tiles - 1u && part == 0u) counts[0] = off + n;
+        if (tile == n_tiles - 1u && part == 0u)
+        {
+            counts[0] = off + n;
+            if (tiled_total) *tiled_total = off + n;
+            if (offsets_end) *offsets_end = off + n;
+        }
     }
 }
 
@@ -1657,7 +1664,7 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
     const hipError_t e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
     if (e != hipSuccess) { set_error( "seed pass failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
     return NVB_LAUNCH( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
-                       (const uint32_t*)L.tile_offsets, L.tl.n_tiles, L.slots, keys_dev, (unsigned int*)counts_dev );
+                       (const uint32_t*)L.tile_offsets, L.tl.n_tiles, L.slots, keys_dev, (unsigned int*)counts_dev, (unsigned int*)nullptr, (uint32_t*)nullptr );
 }
 
 int nvbio_fm_index_is_canonical(nvbio_fm_index_t index)
@@ -1682,10 +1689,27 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_keys_capacity(const nvbio_string
     return NVBIO_OK;
 }
 
+nvbio_status nvbio_fm_seed_tiles(const nvbio_string_set* seeds, uint32_t* reads_per_tile, uint32_t* n_tiles)
+{
+    NVB_REQUIRE( reads_per_tile && n_tiles, "NULL output pointer" );
+    SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
+    *reads_per_tile = L.tl.rpt; *n_tiles = L.tl.n_tiles;
+    return NVBIO_OK;
+}
+
 nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nvbio_string_set* seeds, uint32_t flags, uint32_t read_len,
                                                 uint64_t* keys_dev, nvbio_uint2* residual_ranges_dev, uint32_t* residual_ids_dev,
                                                 uint32_t residual_capacity, uint32_t* counts_dev, void* temp_dev, uint64_t temp_bytes,
                                                 void* stream)
+{
+    return nvbio_fm_match_seed_diagonals_both_tiled( index, seeds, flags, read_len, keys_dev, residual_ranges_dev, residual_ids_dev, residual_capacity,
+                                                     counts_dev, nullptr, temp_dev, temp_bytes, stream );
+}
+
+nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, const nvbio_string_set* seeds, uint32_t flags, uint32_t read_len,
+                                                      uint64_t* keys_dev, nvbio_uint2* residual_ranges_dev, uint32_t* residual_ids_dev,
+                                                      uint32_t residual_capacity, uint32_t* counts_dev, uint32_t* tile_offsets_dev,
+                                                      void* temp_dev, uint64_t temp_bytes, void* stream)
 {
     NVB_REQUIRE( index != nullptr, "index is NULL" );
     FMIndexImpl* idx = (FMIndexImpl*)index;
@@ -1715,6 +1739,8 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
     NVB_CHECK( temp.alloc_layout( "fm_seed_pass_both", s, "seed pass: out of device memory for %llu bytes of scratch", [&](ScratchLayout& c) { L.carve( c ); },
                                   temp_dev, temp_bytes, "nvbio_fm_match_seed_diagonals_both_temp_bytes" ) );
     uint64_t* tile_keys = L.tile_keys; uint32_t* tile_counts = L.tile_counts; uint32_t* tile_defer = L.tile_defer; uint32_t* defer_counts = L.defer_counts;
+    // the scan of the tile counts goes to the caller's array where it keeps one (n_tiles + 1 entries: the last one is written by the compaction)
+    uint32_t* tile_offsets = tile_offsets_dev ? tile_offsets_dev : L.tile_offsets;
     const DevIndex f = idx->dev();
     unsigned blocks = (L.tl.n_tiles + 3u) / 4u;
     const unsigned cap = (flags >> 16) ? (flags >> 16) * 64u : 256u * 64u;
@@ -1740,10 +1766,11 @@ nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nv
         return idx->cwide ? wide( std::true_type() ) : wide( std::false_type() );
     }, bad_symbol_bits ) );                                      // (packed seeds were required above)
     size_t scan_bytes = L.scan_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, L.tile_offsets, (int)L.tl.n_tiles, s );
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum( L.scan_temp, scan_bytes, (const uint32_t*)tile_counts, tile_offsets, (int)L.tl.n_tiles, s );
     if (e == hipSuccess)
         NVB_CHECK( NVB_LAUNCH( fm_seed_compact_kernel, dim3( grid_for( 4ull * L.tl.n_tiles ) ), block, s, (const uint64_t*)tile_keys, (const uint32_t*)tile_counts,
-                               (const uint32_t*)L.tile_offsets, L.tl.n_tiles, 128u, keys_dev, (unsigned int*)counts_dev ) );
+                               (const uint32_t*)tile_offsets, L.tl.n_tiles, 128u, keys_dev, (unsigned int*)counts_dev, (unsigned int*)counts_dev + 3,
+                               tile_offsets_dev ? tile_offsets_dev + L.tl.n_tiles : (uint32_t*)nullptr ) );
     if (e == hipSuccess && defer)
     {
         // the deferred searches: their slots made dense, then a launch of their own that appends to the keys and the residual lists

@@ -48,6 +48,14 @@ diagonals_to_windows_kernel(const uint64_t* __restrict__ keys, const uint64_t n,
     }
 }
 
+// the selection key of a candidate (diagonal key k, score, window begin, sink.x): see best_candidate_kernel
+__device__ __forceinline__ unsigned long long selection_key(const uint64_t k, const int32_t score, const uint32_t wb, const uint32_t sink_x)
+{
+    const int64_t  s   = (int64_t)score + (1ll << 20);
+    const uint64_t pos = (uint64_t)wb + (uint64_t)sink_x;
+    return ((uint64_t)(s > 0 ? s : 0) << 34) | (k & (1ull << 33)) | (pos & ((1ull << 33) - 1ull));
+}
+
 // best candidate per read: selection key = (score + 2^20, clamped at 0) << 34 | strand << 33 | end position, end position
 // = window begin + sink.x (hit.sink, score_inl.h:127-129); one 64-bit atomic max per candidate into best[read]
 // (fmmap reduces the score per read the same way, examples/fmmap/fmmap.cu:367-376; the key makes the choice unique
@@ -84,9 +92,7 @@ best_candidate_kernel(const uint64_t* __restrict__ keys, const int32_t* __restri
         if (i < n)
         {
             const uint64_t k   = keys[i];
-            const int64_t  s   = (int64_t)scores[i] + (1ll << 20);
-            const uint64_t pos = (uint64_t)wb[i] + (uint64_t)sinks[i].x;
-            sel = ((uint64_t)(s > 0 ? s : 0) << 34) | (k & (1ull << 33)) | (pos & ((1ull << 33) - 1ull));
+            sel = selection_key( k, scores[i], wb[i], sinks[i].x );
             seg = (uint32_t)(k >> 34);
         }
         if (run_max( seg, sel ) && i < n) atomicMax( &best[seg], sel );
@@ -94,17 +100,23 @@ best_candidate_kernel(const uint64_t* __restrict__ keys, const int32_t* __restri
 }
 
 // the per-read selection keys of best_candidate_kernel back into (score, end position, strand); 0 = no candidate
+__device__ __forceinline__ void unpack_best_key(const unsigned long long k, int32_t& score, int64_t& pos, uint8_t& rc)
+{
+    const int64_t sv = (int64_t)(k >> 34);
+    score = (k && sv > 0) ? (int32_t)(sv - (1ll << 20)) : NVBIO_SCORE_MIN;
+    pos   = k ? (int64_t)(k & ((1ull << 33) - 1ull)) : -1ll;
+    rc    = k ? (uint8_t)((k >> 33) & 1ull) : (uint8_t)0;
+}
+
 __global__ void __launch_bounds__(256)
 best_unpack_kernel(const unsigned long long* __restrict__ best, const uint32_t n, int32_t* __restrict__ score, int64_t* __restrict__ pos,
                    uint8_t* __restrict__ rc)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
-        const unsigned long long k = best[i];
-        const int64_t sv = (int64_t)(k >> 34);
-        score[i] = (k && sv > 0) ? (int32_t)(sv - (1ll << 20)) : NVBIO_SCORE_MIN;
-        pos[i]   = k ? (int64_t)(k & ((1ull << 33) - 1ull)) : -1ll;
-        rc[i]    = k ? (uint8_t)((k >> 33) & 1ull) : (uint8_t)0;
+        int32_t s; int64_t p; uint8_t c;
+        unpack_best_key( best[i], s, p, c );
+        score[i] = s; pos[i] = p; rc[i] = c;
     }
 }
 
@@ -117,9 +129,7 @@ best_window_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict_
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
     {
         const uint64_t k   = keys[i];
-        const int64_t  s   = (int64_t)scores[i] + (1ll << 20);
-        const uint64_t pos = (uint64_t)wb[i] + (uint64_t)sinks[i].x;
-        const uint64_t sel = ((uint64_t)(s > 0 ? s : 0) << 34) | (k & (1ull << 33)) | (pos & ((1ull << 33) - 1ull));
+        const uint64_t sel = selection_key( k, scores[i], wb[i], sinks[i].x );
         if (sel != best[k >> 34]) continue;
         atomicMax( &best_wb[k >> 34], (long long)wb[i] );
         if (best_g)
@@ -174,6 +184,17 @@ __device__ __forceinline__ bool distinct_alignments(const uint64_t pos1, const u
     return !(pos1 >= pos2 - (pos2 < dist ? pos2 : dist) && pos1 <= pos2 + dist);
 }
 
+// the key a candidate (selection key `cand`, score sc) competes with for its read's second best, given the read's final best b: 0 = it does not
+__device__ __forceinline__ unsigned long long second_candidate_key(const unsigned long long cand, const int32_t sc, const unsigned long long b,
+                                                                   const uint32_t dist, const int32_t worst_score)
+{
+    if (!(sc > worst_score)) return 0ull;                     // `score > best.m_a2.score()` with a2 initialised to the threshold
+    // not the best itself (or a copy of it: location already held), and distinct from it
+    if (cand != b && distinct_alignments( b & ((1ull << 33) - 1ull), (uint32_t)((b >> 33) & 1ull), cand & ((1ull << 33) - 1ull), (uint32_t)((cand >> 33) & 1ull), dist ))
+        return cand;
+    return 0ull;
+}
+
 __global__ void __launch_bounds__(256)
 second_candidate_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ scores, const uint2* __restrict__ sinks,
                         const uint32_t* __restrict__ wb, const uint64_t n, const unsigned long long* __restrict__ best,
@@ -194,16 +215,8 @@ second_candidate_kernel(const uint64_t* __restrict__ keys, const int32_t* __rest
             // ragged reads: distinct_dist = read_len / 2 and the threshold min_score - 1 of the candidate's own read
             const uint32_t dist        = read_offsets ? (read_offsets[(k >> 34) + 1] - read_offsets[k >> 34]) / 2u : dist_all;
             const int32_t  worst_score = min_scores ? min_scores[k >> 34] - 1 : worst_score_all;
-            if (sc > worst_score)                                  // `score > best.m_a2.score()` with a2 initialised to the threshold
-            {
-                const int64_t  s   = (int64_t)sc + (1ll << 20);
-                const uint64_t pos = ((uint64_t)wb[i] + (uint64_t)sinks[i].x) & ((1ull << 33) - 1ull);
-                const uint64_t cand = ((uint64_t)(s > 0 ? s : 0) << 34) | (k & (1ull << 33)) | pos;
-                const unsigned long long b = best[k >> 34];
-                // not the best itself (or a copy of it: location already held), and distinct from it
-                if (cand != b && distinct_alignments( b & ((1ull << 33) - 1ull), (uint32_t)((b >> 33) & 1ull), pos, (uint32_t)((k >> 33) & 1ull), dist ))
-                    sel = cand;
-            }
+            if (sc > worst_score)
+                sel = second_candidate_key( selection_key( k, sc, wb[i], sinks[i].x ), sc, best[k >> 34], dist, worst_score );
         }
         if (run_max( seg, sel ) && sel != 0ull) atomicMax( &second[seg], sel );
     }
@@ -292,6 +305,17 @@ __device__ __forceinline__ int mapq_v2(const int32_t best_score, const bool has_
     else                               return (best_over >= diff * 0.5f) ? 1 : 0;
 }
 
+// the mapping quality of a read from its best and second-best selection keys; ss = the second-best score (NVBIO_SCORE_MIN: none)
+__device__ __forceinline__ int mapq_of_keys(const unsigned long long b, const unsigned long long s2, const int version, const bool monotone,
+                                            const float max_score, const float min_score, int32_t& ss)
+{
+    const int32_t bs = b  ? (int32_t)((int64_t)(b  >> 34) - (1ll << 20)) : NVBIO_SCORE_MIN;
+    ss = s2 ? (int32_t)((int64_t)(s2 >> 34) - (1ll << 20)) : NVBIO_SCORE_MIN;
+    int q = 0;
+    if (b) q = (version == 3) ? mapq_v3( bs, s2 != 0ull, ss, max_score, min_score ) : mapq_v2( bs, s2 != 0ull, ss, max_score, min_score, monotone );
+    return q;
+}
+
 __global__ void __launch_bounds__(256)
 mapq_kernel(const unsigned long long* __restrict__ best, const unsigned long long* __restrict__ second, const uint32_t n,
             const int version, const bool monotone, const float max_score_all, const float min_score_all,
@@ -303,14 +327,133 @@ mapq_kernel(const unsigned long long* __restrict__ best, const unsigned long lon
         // ragged reads: perfect_score = match x read_len (scoring.h:274) and min_score( read_len ) of the read itself
         const float max_score = read_offsets ? (float)(match * (int32_t)(read_offsets[i + 1] - read_offsets[i])) : max_score_all;
         const float min_score = min_scores ? (float)min_scores[i] : min_score_all;
-        const unsigned long long b = best[i], s2 = second ? second[i] : 0ull;
-        const int32_t bs = b  ? (int32_t)((int64_t)(b  >> 34) - (1ll << 20)) : NVBIO_SCORE_MIN;
-        const int32_t ss = s2 ? (int32_t)((int64_t)(s2 >> 34) - (1ll << 20)) : NVBIO_SCORE_MIN;
-        int q = 0;
-        if (b) q = (version == 3) ? mapq_v3( bs, s2 != 0ull, ss, max_score, min_score ) : mapq_v2( bs, s2 != 0ull, ss, max_score, min_score, monotone );
+        int32_t ss;
+        const int q = mapq_of_keys( best[i], second ? second[i] : 0ull, version, monotone, max_score, min_score, ss );
         if (second_score) second_score[i] = ss;
         mapq[i] = (uint8_t)q;
     }
+}
+
+// best, second best, unpack and mapping quality of every read in ONE pass over the candidates: what best_candidate_kernel, second_candidate_kernel,
+// best_unpack_kernel and mapq_kernel compute, for a candidate list in TILE ORDER (nvbio_finish_reads): tile t holds the candidates
+// [tile_offsets[t], tile_offsets[t+1]) of the reads [t * rpt, (t + 1) * rpt), so a workgroup that owns tiles_per_group consecutive tiles sees every candidate
+// of its reads and reduces them in LDS -- no global atomic, no zero fill, every output stored once.
+//   phase 1: selection key of every candidate of the span, run_max, LDS max into the read's best                 | barrier
+//   phase 2: second_candidate_key against the LDS best, run_max, LDS max into the read's second best              | barrier
+//   phase 3: lanes take reads: keys out, unpack, mapping quality, every per-read output coalesced.
+// The first FINISH_KEPT rounds of 256 candidates keep (read, key, score) in registers for phase 2; a longer span loads the rest again.
+// The precondition is checked, not assumed: offsets that do not tile [0, n) in ascending order, or a candidate whose read is not one of its
+// workgroup's, set *status (and the candidate is left out: the caller must not use the outputs then).
+constexpr uint32_t FINISH_MAX_READS = 192u;                    // reads per workgroup at most: 3 KB of LDS; ~1.1 candidates per read fill one round
+constexpr uint32_t FINISH_KEPT      = 2u;
+__global__ void __launch_bounds__(256)
+finish_reads_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ scores, const uint2* __restrict__ sinks, const uint32_t* __restrict__ wb,
+                    const uint64_t n, const uint32_t* __restrict__ tile_offsets, const uint32_t n_tiles, const uint32_t rpt, const uint32_t tiles_per_group,
+                    const uint32_t n_reads, const uint32_t dist_all, const int32_t worst_score_all, const int version, const bool monotone,
+                    const float max_score_all, const float min_score_all, const int32_t match, const uint32_t* __restrict__ read_offsets,
+                    const int32_t* __restrict__ min_scores, unsigned long long* __restrict__ best, unsigned long long* __restrict__ second,
+                    int32_t* __restrict__ score, int64_t* __restrict__ pos, uint8_t* __restrict__ rc, uint8_t* __restrict__ mapq,
+                    int32_t* __restrict__ second_score, uint32_t* __restrict__ status)
+{
+    __shared__ unsigned long long s_best[FINISH_MAX_READS], s_second[FINISH_MAX_READS];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t t0 = blockIdx.x * tiles_per_group;                                   // (the grid holds ceil( n_tiles / tiles_per_group ) workgroups)
+    const uint32_t t1 = t0 + tiles_per_group < n_tiles ? t0 + tiles_per_group : n_tiles;
+    const uint64_t r0 = (uint64_t)t0 * rpt;
+    const uint64_t r1 = (uint64_t)t1 * rpt < n_reads ? (uint64_t)t1 * rpt : n_reads;
+    const uint32_t nr = r1 > r0 ? (uint32_t)(r1 - r0) : 0u;                             // <= tiles_per_group * rpt <= FINISH_MAX_READS (checked by the host)
+    bool bad = false;
+    // the span of this workgroup's candidates, clamped to the list before anything is read through it
+    uint64_t begin = tile_offsets[t0], end = tile_offsets[t1];
+    if (end > n)     { end = n;     bad = true; }
+    if (begin > end) { begin = end; bad = true; }
+    if (t0 == 0u && begin != 0ull)    bad = true;                                      // the spans must cover the whole list: from 0 ...
+    if (t1 == n_tiles && end != n)    bad = true;                                      // ... to n (keys appended behind the tiles are not in tile order)
+    for (uint32_t r = threadIdx.x; r < nr; r += blockDim.x) { s_best[r] = 0ull; s_second[r] = 0ull; }
+    __syncthreads();
+
+    uint32_t           k_seg[FINISH_KEPT];
+    unsigned long long k_sel[FINISH_KEPT];
+    int32_t            k_sc[FINISH_KEPT];
+    // candidate i of the span: its read within the workgroup (a run of its own beyond the span or outside the reads), selection key and score
+    auto load = [&](const uint64_t i, uint32_t& seg, unsigned long long& sel, int32_t& sc)
+    {
+        seg = 0xFFFFFF00u + lane; sel = 0ull; sc = NVBIO_SCORE_MIN;
+        if (i < end)
+        {
+            // (all four loads issued together: none waits for the key)
+            const uint64_t k   = keys[i];
+            const int32_t  c   = scores[i];
+            const uint32_t w   = wb[i], sx = sinks[i].x;
+            const uint64_t rid = k >> 34;
+            if (rid >= r0 && rid < r1) { sc = c; sel = selection_key( k, c, w, sx ); seg = (uint32_t)(rid - r0); }
+            else bad = true;
+        }
+    };
+    // ---- phase 1: the best of every read ----
+    #pragma unroll
+    for (uint32_t u = 0; u < FINISH_KEPT; ++u)
+    {
+        const uint64_t i0 = begin + u * 256u + (threadIdx.x & ~63u);                    // wave-uniform bound
+        k_seg[u] = 0xFFFFFF00u + lane; k_sel[u] = 0ull; k_sc[u] = NVBIO_SCORE_MIN;
+        if (i0 < end)
+        {
+            load( i0 + lane, k_seg[u], k_sel[u], k_sc[u] );
+            unsigned long long v = k_sel[u];
+            if (run_max( k_seg[u], v ) && v != 0ull) atomicMax( &s_best[k_seg[u]], v );
+        }
+    }
+    for (uint64_t i0 = begin + FINISH_KEPT * 256u + (threadIdx.x & ~63u); i0 < end; i0 += 256u)
+    {
+        uint32_t seg; unsigned long long v; int32_t sc;
+        load( i0 + lane, seg, v, sc );
+        if (run_max( seg, v ) && v != 0ull) atomicMax( &s_best[seg], v );
+    }
+    __syncthreads();
+    // ---- phase 2: the second best, against the read's final best ----
+    auto compete = [&](const uint32_t seg, const unsigned long long sel, const int32_t sc) -> unsigned long long
+    {
+        if (seg >= FINISH_MAX_READS) return 0ull;                                       // no candidate of this workgroup's reads in this lane
+        // ragged reads: distinct_dist = read_len / 2 and the threshold min_score - 1 of the candidate's own read
+        const uint64_t rid = r0 + seg;
+        const uint32_t dist        = read_offsets ? (read_offsets[rid + 1] - read_offsets[rid]) / 2u : dist_all;
+        const int32_t  worst_score = min_scores ? min_scores[rid] - 1 : worst_score_all;
+        return second_candidate_key( sel, sc, s_best[seg], dist, worst_score );
+    };
+    #pragma unroll
+    for (uint32_t u = 0; u < FINISH_KEPT; ++u)
+    {
+        const uint64_t i0 = begin + u * 256u + (threadIdx.x & ~63u);
+        if (i0 < end)
+        {
+            unsigned long long v = compete( k_seg[u], k_sel[u], k_sc[u] );
+            if (run_max( k_seg[u], v ) && v != 0ull) atomicMax( &s_second[k_seg[u]], v );
+        }
+    }
+    for (uint64_t i0 = begin + FINISH_KEPT * 256u + (threadIdx.x & ~63u); i0 < end; i0 += 256u)
+    {
+        uint32_t seg; unsigned long long sel; int32_t sc;
+        load( i0 + lane, seg, sel, sc );
+        unsigned long long v = compete( seg, sel, sc );
+        if (run_max( seg, v ) && v != 0ull) atomicMax( &s_second[seg], v );
+    }
+    __syncthreads();
+    // ---- phase 3: every per-read output, once ----
+    for (uint32_t lr = threadIdx.x; lr < nr; lr += blockDim.x)
+    {
+        const uint64_t r = r0 + lr;
+        const unsigned long long b = s_best[lr], s2 = s_second[lr];
+        // ragged reads: perfect_score = match x read_len (scoring.h:274) and min_score( read_len ) of the read itself
+        const float max_score = read_offsets ? (float)(match * (int32_t)(read_offsets[r + 1] - read_offsets[r])) : max_score_all;
+        const float min_score = min_scores ? (float)min_scores[r] : min_score_all;
+        int32_t s, ss; int64_t p; uint8_t c;
+        unpack_best_key( b, s, p, c );
+        const int q = mapq_of_keys( b, s2, version, monotone, max_score, min_score, ss );
+        best[r] = b; second[r] = s2;
+        score[r] = s; pos[r] = p; rc[r] = c;
+        mapq[r] = (uint8_t)q; second_score[r] = ss;
+    }
+    if (bad) atomicOr( status, 1u );
 }
 
 // opposite-mate window of a paired-end alignment: BestOppositeScoreStream::init_context
@@ -623,6 +766,44 @@ extern "C" nvbio_status nvbio_mapq(int device, const uint64_t* best_dev, const u
     return NVB_LAUNCH( mapq_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream,
                        (const unsigned long long*)best_dev, (const unsigned long long*)second_dev, n_reads, (int)params->version,
                        params->monotone != 0, (float)params->perfect_score, (float)params->min_score, second_scores_dev, mapq_dev, nullptr, nullptr, 0 );
+}
+
+extern "C" nvbio_status nvbio_finish_reads_tiles_per_group(uint32_t reads_per_tile, uint32_t* tiles_per_group)
+{
+    NVB_REQUIRE( tiles_per_group != nullptr, "tiles_per_group is NULL" );
+    NVB_REQUIRE( reads_per_tile >= 1u && reads_per_tile <= FINISH_MAX_READS, "reads_per_tile must be in 1..192" );
+    *tiles_per_group = FINISH_MAX_READS / reads_per_tile;
+    return NVBIO_OK;
+}
+
+extern "C" nvbio_status nvbio_finish_reads(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
+                                           const uint32_t* win_begin_dev, uint64_t n, const uint32_t* tile_offsets_dev, uint32_t n_tiles,
+                                           uint32_t reads_per_tile, uint32_t n_reads, uint32_t distinct_dist, int32_t worst_score,
+                                           const nvbio_mapq_params* params, int32_t match, const uint32_t* read_offsets_dev, const int32_t* min_scores_dev,
+                                           uint64_t* best_dev, uint64_t* second_dev, int32_t* scores_out_dev, int64_t* end_pos_dev, uint8_t* rc_dev,
+                                           uint8_t* mapq_dev, int32_t* second_scores_dev, uint32_t* status_dev, void* stream)
+{
+    if (n_reads == 0) return NVBIO_OK;
+    NVB_REQUIRE( n == 0 || (keys_dev && scores_dev && sinks_dev && win_begin_dev), "NULL device pointer" );
+    NVB_REQUIRE( tile_offsets_dev && best_dev && second_dev && scores_out_dev && end_pos_dev && rc_dev && mapq_dev && second_scores_dev && status_dev,
+                 "NULL device pointer" );
+    NVB_REQUIRE( params != nullptr, "params is NULL" );
+    NVB_REQUIRE( params->version == 2 || params->version == 3, "mapq version must be 2 or 3" );
+    const bool ragged = read_offsets_dev != nullptr;
+    NVB_REQUIRE( ragged == (min_scores_dev != nullptr), "ragged reads need both read_offsets_dev and min_scores_dev" );
+    NVB_REQUIRE( ragged || params->perfect_score > params->min_score, "perfect_score must exceed min_score" );
+    uint32_t tpg = 0;
+    NVB_CHECK( nvbio_finish_reads_tiles_per_group( reads_per_tile, &tpg ) );
+    NVB_REQUIRE( n_tiles >= 1u && (uint64_t)n_tiles * reads_per_tile >= n_reads && (uint64_t)(n_tiles - 1u) * reads_per_tile < n_reads,
+                 "n_tiles must be ceil( n_reads / reads_per_tile )" );
+    NVB_REQUIRE( n < (1ull << 32), "tile offsets are 32-bit: at most 2^32 - 1 candidates" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    const uint32_t groups = (n_tiles + tpg - 1u) / tpg;
+    return NVB_LAUNCH( finish_reads_kernel, dim3( groups ), dim3(256), (hipStream_t)stream, keys_dev, scores_dev, (const uint2*)sinks_dev, win_begin_dev, n,
+                       tile_offsets_dev, n_tiles, reads_per_tile, tpg, n_reads, distinct_dist, worst_score, (int)params->version,
+                       ragged ? match == 0 : params->monotone != 0, ragged ? 0.0f : (float)params->perfect_score, ragged ? 0.0f : (float)params->min_score,
+                       match, read_offsets_dev, min_scores_dev, (unsigned long long*)best_dev, (unsigned long long*)second_dev, scores_out_dev,
+                       end_pos_dev, rc_dev, mapq_dev, second_scores_dev, status_dev );
 }
 
 // sort + unique of candidate keys: what fmmap does with its diagonals before extending them (examples/fmmap/fmmap.cu:320-344:

@@ -226,6 +226,8 @@ private:
 // NVBIO_FM_TABLE_CANONICAL): keys() of both strands tile by tile; the residual seeds of the forward strand in [0, counts()[1]) of
 // residual_ranges() / residual_ids(), of the reverse strand in [capacity(), capacity() + counts()[2]).
 // flags: e.g. NVBIO_FM_INLINE_HITS(4), which keeps the residual lists empty on unique-ish genomes
+// tile_offsets(): n_tiles() + 1 entries, tile t (reads [t * reads_per_tile(), ...)) owns keys()[tile_offsets()[t] .. tile_offsets()[t + 1]);
+// counts()[3] = the keys in tile order (= counts()[0] unless deferred searches appended theirs): what finish_reads() needs
 class SeedPassBoth
 {
 public:
@@ -237,12 +239,17 @@ public:
         m_keys.resize( cap ? cap : 1 ); m_ranges.resize( 2 * n ); m_ids.resize( 2 * n ); m_counts.resize( 6 );
         check( nvbio_fm_match_seed_diagonals_both_temp_bytes( &m_seeds.c, &bytes ) );
         m_temp.resize( bytes );
+        check( nvbio_fm_seed_tiles( &m_seeds.c, &m_rpt, &m_n_tiles ) );
+        m_tile_offsets.resize( (size_t)m_n_tiles + 1 );
     }
     void enact(const fm_index& fmi, uint32_t flags, uint32_t read_len, hipStream_t stream = 0)
     {
-        check( nvbio_fm_match_seed_diagonals_both( fmi.handle(), &m_seeds.c, flags, read_len, m_keys.data(), m_ranges.data(), m_ids.data(),
-                                                   capacity(), m_counts.data(), m_temp.data(), m_temp.size(), stream ) );
+        check( nvbio_fm_match_seed_diagonals_both_tiled( fmi.handle(), &m_seeds.c, flags, read_len, m_keys.data(), m_ranges.data(), m_ids.data(),
+                                                         capacity(), m_counts.data(), m_tile_offsets.data(), m_temp.data(), m_temp.size(), stream ) );
     }
+    const uint32_t*    tile_offsets()    const { return m_tile_offsets.data(); }
+    uint32_t           reads_per_tile()  const { return m_rpt; }
+    uint32_t           n_tiles()         const { return m_n_tiles; }
     uint32_t           capacity()        const { return (uint32_t)m_seeds.size(); }
     const uint64_t*    keys()            const { return m_keys.data(); }
     const nvbio_uint2* residual_ranges() const { return m_ranges.data(); }
@@ -252,9 +259,23 @@ private:
     string_set                 m_seeds;
     device_vector<uint64_t>    m_keys;
     device_vector<nvbio_uint2> m_ranges;
-    device_vector<uint32_t>    m_ids, m_counts;
+    device_vector<uint32_t>    m_ids, m_counts, m_tile_offsets;
     device_vector<uint8_t>     m_temp;
+    uint32_t                   m_rpt = 0, m_n_tiles = 0;
 };
+
+// nvbio_finish_reads over the tile-ordered candidates of a SeedPassBoth (its keys, extended in their order): best / second-best keys, best
+// score, end position and strand, mapping quality and second score of every read in one launch.  status_dev: a device word zeroed once by the
+// caller; nonzero after the call = the list was not in tile order and the outputs must be discarded (the caller reads it where it synchronises).
+inline void finish_reads(const SeedPassBoth& pass, uint64_t n, const int32_t* scores_dev, const nvbio_uint2* sinks_dev, const uint32_t* win_begin_dev,
+                         uint32_t n_reads, uint32_t distinct_dist, int32_t worst_score, const nvbio_mapq_params& mapq, uint64_t* best_dev,
+                         uint64_t* second_dev, int32_t* scores_out_dev, int64_t* end_pos_dev, uint8_t* rc_dev, uint8_t* mapq_dev,
+                         int32_t* second_scores_dev, uint32_t* status_dev, hipStream_t stream = 0, int device = 0)
+{
+    check( nvbio_finish_reads( device, pass.keys(), scores_dev, sinks_dev, win_begin_dev, n, pass.tile_offsets(), pass.n_tiles(), pass.reads_per_tile(),
+                               n_reads, distinct_dist, worst_score, &mapq, 0, nullptr, nullptr, best_dev, second_dev, scores_out_dev, end_pos_dev,
+                               rc_dev, mapq_dev, second_scores_dev, status_dev, stream ) );
+}
 
 template <typename system_tag> class FMIndexFilter;
 

@@ -43,6 +43,9 @@ class SeedExtendParams:
         self.algo_flags = 0                         # nvbio_alignment_batch::algo_flags of the extension (ALN_*: A/B of the exact shortcuts)
         self.defer_heavy = True                     # two-strand seed pass: the searches the table cannot answer (k-mers with more than 8
                                                     # occurrences) run as a dense launch of their own behind the pass (FM_DEFER_HEAVY)
+        self.fused_finish = True                    # two-strand seed pass without residual or appended keys, mapq on: best, second best, unpack and
+                                                    # mapping quality of a batch in ONE launch over its tile-ordered candidates (finish_reads; timer
+                                                    # "finish") instead of reduce + unpack + second + mapq and their two zero fills (A/B: same results)
 
     @classmethod
     def end_to_end(cls, constant_quality=True, **kw):
@@ -181,7 +184,8 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
     second alignment) and "second" (the second-best selection keys): nvBowtie's score_reduce bookkeeping (reduce_inl.h:65-140,
     over the candidates in descending key order) and BowtieMapq2 (mapq.h)."""
     import torch
-    from . import best_candidate_reduce, best_candidate_unpack, best_candidate_windows, diagonals_to_windows, mapq, second_candidate_reduce
+    from . import (FinishStatus, best_candidate_reduce, best_candidate_unpack, best_candidate_windows, diagonals_to_windows, finish_reads, mapq,
+                   second_candidate_reduce)
     dev = fmi.device
     R, M, L = reads.n, reads.read_len, params.seed_len
     geo = _batch_geometry(torch, fmi, reads, params)
@@ -201,11 +205,15 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
 
     ext_flags = (params.algo_flags or 0) | (ALN_RAGGED_READS if ragged else 0)
     aligner = GotohAligner(params.aln_type, params.scheme)
-    top = torch.zeros((R,), dtype=torch.int64, device=dev)      # best selection key per read (0: no candidate)
+    top = None                                                  # best selection key per read (0: no candidate): zero-filled where it is reduced into
+    finish = None                                               # the tile spans of the candidates, where finish_reads can take the whole tail of the step
 
     def extend(keys, tag):
         """candidate windows (genome_infixes, fmmap.cu:169-196; window rule of score_inl.h:100-106), the banded Gotoh of
         every one of them, and the per-read reduction of the selection keys into `top` (one atomic max per candidate)"""
+        nonlocal top
+        if finish is None and top is None:
+            top = torch.zeros((R,), dtype=torch.int64, device=dev)
         e = tick("windows" + tag)
         rid, flags, wb, we = diagonals_to_windows(keys, params.band, M, genome_len, read_offsets=read_off if ragged else None)
         tock(e)
@@ -214,6 +222,9 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
                                flags=flags, device=dev, max_read_len=M, algo_flags=ext_flags or None)
         scores, sinks = BatchedBandedAlignmentScore(params.band, aligner).enact(batch)
         tock(e)
+        if finish is not None:
+            scored.append((keys, scores, sinks, wb))
+            return None
         e = tick("reduce")
         best_candidate_reduce(keys, scores, sinks, wb, top)
         tock(e)
@@ -261,7 +272,11 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
         assert pre["reads"] is reads
         b = pre["b"]
         pre["ev"].synchronize()
+        FinishStatus.of(dev).check()                # (a fused finish of an earlier batch that reported a list out of tile order raises here)
         n_keys, n_rf, n_rr = int(b["host"][0]), int(b["host"][1]), int(b["host"][2])
+        # every key inside its tile's span (none appended by the deferred searches, no residual keys to come): the candidates stay in tile order
+        if params.mapq and getattr(params, "fused_finish", True) and n_keys and n_rf == 0 and n_rr == 0 and int(b["host"][3]) == n_keys:
+            finish = (b["tile_offsets"], b["reads_per_tile"])
         parts = [b["keys"][:n_keys]]
         if n_rf or n_rr:
             # both strands' residual seeds through ONE scan + locate (bit 31 of a seed id flips the strand)
@@ -353,6 +368,28 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
         # memory-bound seed pass was measured: the two kernels serialise, 42-44 ms vs 36 ms per step)
         results.append(extend(keys, "_rc" if strand else "_fw"))
 
+    if finish is not None:
+        # 5. + 6. in one launch over the tile-ordered candidates: best, second best, unpack, mapping quality
+        e = tick("finish")
+        (keys, scores, sinks, wb), = scored
+        min_score = params.min_score_for(M)
+        match = int(params.scheme.c.match)
+        f = finish_reads(keys, scores, sinks, wb, finish[0], finish[1], R, M // 2, min_score - 1, match * M, min_score, match == 0,
+                         params.mapq_version, read_offsets=read_off if ragged else None, min_scores=min_scores, match=match, check=False)
+        tock(e)
+        top, best_score, best_pos, best_rc = f["best"], f["best_score"], f["best_pos"], f["best_rc"]
+        if extras is not None:
+            extras.update(mapq=f["mapq"], second_score=f["second_score"], second=f["second"], best_keys=top)
+            if ragged:
+                extras["min_scores"] = min_scores
+        if return_windows:
+            best_wb = torch.full((R,), -1, dtype=torch.int64, device=dev)
+            best_g = torch.full((R,), -1, dtype=torch.int64, device=dev)
+            best_candidate_windows(keys, scores, sinks, wb, top, best_wb, best_g)
+            return best_score, best_pos, best_rc, int(n_cand), best_wb, best_g
+        return best_score, best_pos, best_rc, int(n_cand)
+    if top is None:
+        top = torch.zeros((R,), dtype=torch.int64, device=dev)
     # 5. best candidate per read (already reduced into `top` by extend): unpack the keys
     e = tick("unpack")
     best_score, best_pos, best_rc = best_candidate_unpack(top)
