@@ -26,6 +26,9 @@ Fixtures:
   ref_fuzz_golden.npz  what the reference returned to every call of tests/test_oracle_vs_reference.py, per
                   test and function in call order, with a crc32 of each call's inputs: the fixture `ref`
                   replays it where oracle/_ref is not built.  Rewrite it whenever those tests change.
+  band31_range_golden.npz  band 31 at the limits of the library's three arithmetic routes (binary16, int16, int32): for either side of every
+                  edge of tests/util.py::RANGE_EDGES a handful of pairs of that very length -- all-mismatch, perfect, shifted to the
+                  band's rim, one long gap, mutated, N's, clipped windows, qualities -- and what the reference scored them.
 """
 import os
 import sys
@@ -647,6 +650,53 @@ def make_fswtb(R):
     print("fswtb_golden.npz: %d cases, %d traced, %d cigar elements" % (len(cases), int(out[:, 0].sum()), int(co[-1])))
 
 
+def band31_range_cases():
+    """(combination, type, scheme, max_read_len, route, pattern, qualities or None, text, kind) for band31_range_golden.npz: 7 jobs per side
+    of every edge (3 at 5,000 rows and more), the kinds rotating from one combination to the next so that every kind and every gap
+    variant occurs; all-mismatch reads of a quality scheme carry the qualities of the largest penalty"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import util
+    cases = []
+    combo = 0
+    for edge in util.RANGE_EDGES:
+        name, _, typ, _, with_q = edge
+        for sv, M, route in util.range_edge_sides(edge):
+            jobs = 3 if M >= 5000 else 7
+            first = (7 * combo) % len(util.RANGE_KINDS)
+            kinds = [("allmm", "mut", "perfect", "gap")[(combo + j) % 4] for j in range(jobs)] if jobs == 3 else None
+            pats, txts, names = util.range_jobs(1000 + combo, [M] * jobs, 31, first=first, kinds=kinds)
+            rng = np.random.default_rng(5000 + combo)
+            for p, t, k in zip(pats, txts, names):
+                q = None
+                if with_q:
+                    q = np.full(M, 63, dtype=np.uint8) if k == "allmm" else rng.integers(0, 64, M, dtype=np.uint8)
+                cases.append((combo, typ, sv, M, route, p, q, t, k))
+            combo += 1
+    return cases
+
+
+def make_band31_range(R):
+    cases = band31_range_cases()
+    n = len(cases)
+    schemes = sorted({c[2] for c in cases})
+    po = np.zeros(n + 1, dtype=np.uint32); to = np.zeros(n + 1, dtype=np.uint32)
+    out = np.zeros((n, 4), dtype=np.int64)
+    quals = []
+    for k, (combo, typ, sv, M, route, pat, q, txt, kind) in enumerate(cases):
+        ok, sc, sk = R.banded_gotoh(31, typ, oracle.Scheme(*sv), pat, txt, q)
+        out[k] = (ok, sc, sk[0], sk[1]); po[k + 1] = po[k] + len(pat); to[k + 1] = to[k] + len(txt)
+        quals.append(q if q is not None else np.zeros(len(pat), np.uint8))
+    path = os.path.join(HERE, "band31_range_golden.npz")
+    np.savez_compressed(path, combo=np.array([c[0] for c in cases], dtype=np.int32), typ=np.array([c[1] for c in cases], dtype=np.int32),
+                        scheme=np.array([schemes.index(c[2]) for c in cases], dtype=np.int32), schemes=np.array(schemes, dtype=np.int32),
+                        max_read_len=np.array([c[3] for c in cases], dtype=np.uint32), route=np.array([c[4] for c in cases]),
+                        kind=np.array([c[8] for c in cases]), has_quals=np.array([c[6] is not None for c in cases], dtype=np.uint8),
+                        pats=np.concatenate([c[5] for c in cases]), quals=np.concatenate(quals), txts=np.concatenate([c[7] for c in cases]),
+                        pat_off=po, txt_off=to, out=out)
+    print("band31_range_golden.npz: %d cases in %d combinations, %d report a score, scores %d..%d, %d bytes"
+          % (n, cases[-1][0] + 1, int(out[:, 0].sum()), out[out[:, 0] == 1, 1].min(), out[:, 1].max(), os.path.getsize(path)))
+
+
 def make_ref_fuzz(R):
     """run every test of tests/test_oracle_vs_reference.py against the live reference, recording what it returns"""
     import importlib.util
@@ -690,4 +740,5 @@ if __name__ == "__main__":
     make_staged(R)
     make_swtb(R)
     make_fswtb(R)
+    make_band31_range(R)
     make_ref_fuzz(R)

@@ -1,5 +1,7 @@
 """The oracle (oracle/nvbio_oracle.c) against the golden vectors the REFERENCE produced
 (tests/golden/*.npz, generator tests/golden/make_golden.py).  CPU only."""
+import os
+
 import numpy as np
 
 import oracle
@@ -158,6 +160,22 @@ def test_banded_gotoh_golden(orc, dp_golden):
                 ok, s, sk = orc.banded_gotoh(int(b), typ, sc, p, t, q)
                 want = g["banded"][i, bi, typ]
                 assert (ok, s, sk[0], sk[1]) == tuple(int(v) for v in want), (i, b, typ)
+
+
+def test_banded_gotoh_range_golden(orc):
+    """band 31 at the lengths and schemes where the library's packed kernels change their arithmetic (tests/util.py::RANGE_EDGES; patterns
+    of up to 7,969 symbols, scores from -7,999 to 45,000): every row of the reference's outputs"""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "band31_range_golden.npz"), allow_pickle=False)
+    n = len(g["pat_off"]) - 1
+    for i in range(n):
+        sc = oracle.Scheme(*[int(v) for v in g["schemes"][g["scheme"][i]]])
+        p = g["pats"][g["pat_off"][i]:g["pat_off"][i + 1]]
+        t = g["txts"][g["txt_off"][i]:g["txt_off"][i + 1]]
+        q = g["quals"][g["pat_off"][i]:g["pat_off"][i + 1]] if g["has_quals"][i] else None
+        assert len(p) == g["max_read_len"][i]
+        ok, s, sk = orc.banded_gotoh(31, int(g["typ"][i]), sc, p, t, q)
+        assert (ok, s, sk[0], sk[1]) == tuple(int(v) for v in g["out"][i]), (i, g["kind"][i])
+    assert n > 300 and g["out"][:, 1].max() == 45000 and (g["out"][:, 1] == -1784).any() and (g["out"][:, 1] == -7998).any()
 
 
 def _tb_scheme(g, i):

@@ -4,6 +4,7 @@ fixture `ref`).  Regenerate the recording with tests/golden/make_golden.py whene
 import numpy as np
 
 import oracle
+from util import RANGE_KINDS, flat_scheme, range_jobs
 
 SCHEMES = [oracle.Scheme.simple(2, -1, -1, -1), oracle.Scheme.simple(0, -5, -8, -3),
            oracle.Scheme.simple(2, -1, -2, -1), oracle.Scheme(2, 2, 6, -8, -3, -8, -3),
@@ -78,6 +79,24 @@ def test_gotoh_fuzz(orc, ref):
             assert np.array_equal(cig, oracle.cigar_from_ops(rops, *rclips) if r == 2 else np.zeros(0, dtype=np.uint16)), (it, typ)
             for blk in range(2):
                 assert ref.full_gotoh(typ, blk, sc, pat, txt, quals, ms) == orc.full_gotoh(typ, blk, sc, pat, txt, quals, ms)
+
+
+def test_gotoh_long_fuzz(orc, ref):
+    """band 31 on patterns of 200 to 8,000 symbols, the lengths at which the library changes its arithmetic among them: one round of
+    the kinds of tests/util.py (all-mismatch, perfect, shifted to the band's rim, one gap of up to 30 symbols, mutated, N's, random,
+    clipped windows) per length, schemes whose scores run to -8,000, to 45,000 and past the reference's int16 stand-in for minus
+    infinity, qualities on every other job"""
+    schemes = SCHEMES[3:] + [oracle.Scheme(*flat_scheme(0, 8)), oracle.Scheme(*flat_scheme(0, 1)), oracle.Scheme(*flat_scheme(1, 1)),
+                             oracle.Scheme(9, 2, 60, -8, -3, -8, -3), oracle.Scheme(0, 2, 8, -8, -3, -8, -3)]
+    rng = np.random.default_rng(13)
+    for li, M in enumerate((200, 223, 224, 500, 968, 969, 1000, 2009, 3000, 5000, 7968, 8000)):
+        jobs = len(RANGE_KINDS) if M <= 1000 else 6
+        pats, txts, kinds = range_jobs(300 + li, [M] * jobs, 31, first=5 * li)
+        for j in range(jobs):
+            quals = rng.integers(0, 64, M, dtype=np.uint8) if j % 2 else None
+            sc = schemes[(li + j) % len(schemes)]
+            for typ in range(3):
+                assert ref.banded_gotoh(31, typ, sc, pats[j], txts[j], quals) == orc.banded_gotoh(31, typ, sc, pats[j], txts[j], quals), (M, kinds[j], typ)
 
 
 def test_whole_path_oracle_equals_reference_code(orc, ref):

@@ -206,3 +206,201 @@ class ReplayedReference:
                 name = key[len(head):-len("__code")]
                 made, recorded = self._next.get(name, 0), len(self._z[head + name + "__crc"])
                 assert made == recorded, "%s: %d of %d recorded calls of %s made" % (self._test, made, recorded, name)
+
+
+# ---------------------------------------------------------------------------------------------
+# inputs for the banded DP at its numeric limits (tests/test_gpu_band31_range.py, tests/golden/make_golden.py: band31_range,
+# tests/test_oracle_vs_reference.py::test_gotoh_long_fuzz)
+# ---------------------------------------------------------------------------------------------
+# the kinds in the order jobs take them: neighbours always differ (the two alignments of a packed lane are jobs 2p and 2p + 1), also
+# round the end of the cycle; 6 of 17 are the extreme ones (all-mismatch, perfect), 5 of 17 ordinary mutated reads
+RANGE_KINDS = ("allmm", "mut", "perfect", "gap", "mut", "allmm", "shift", "mutn", "perfect", "gap", "mut", "random", "allmm", "mut",
+               "clip", "gap", "mut")
+
+
+def _substitute(rng, r, k):
+    if k and len(r):
+        pos = rng.choice(len(r), min(k, len(r)), replace=False)
+        r[pos] = (r[pos] + 1 + rng.integers(0, 3, len(pos))) % 4
+    return r
+
+
+def _mutated(rng, txt, M, W):
+    """a read from somewhere inside the band with 0-5 substitutions and (M > 12) an indel of 1-3 symbols"""
+    d0 = int(rng.integers(3, W - 3)) if W >= 7 else int(rng.integers(0, W))
+    src = txt[d0:]
+    if M > 12:
+        p = int(rng.integers(1, M - 4)); g = int(rng.integers(1, 4))
+        src = txt[min(d0, W - g):]                                   # (a deletion leaves M symbols of the window)
+        r = (np.concatenate([src[:p], src[p + g:]]) if rng.random() < 0.5 else
+             np.concatenate([src[:p], rng.integers(0, 4, g, dtype=np.uint8), src[p:]]))[:M]
+    else:
+        r = src[:M]
+    return _substitute(rng, r.copy(), int(rng.integers(0, 6)))
+
+
+def range_job(rng, kind, M, band=31, variant=0, allow_n=True):
+    """one (pattern as aligned, text window) pair of a kind of RANGE_KINDS for a pattern of M symbols: the window has M + band symbols
+    (BestScoreStream's) unless the kind clips it; `variant` walks through the kind's sub-cases"""
+    W = band; c = W // 2; N = M + W
+    txt = rng.integers(0, 4, N, dtype=np.uint8)
+    if kind == "gap" and M < 4:
+        kind = "shift"
+    if kind == "allmm":                                              # one letter against another: every cell of the band mismatches
+        a = int(rng.integers(0, 4))
+        return np.full(M, a, dtype=np.uint8), np.full(N, (a + 1 + int(rng.integers(0, 3))) % 4, dtype=np.uint8)
+    if kind == "perfect":                                            # on the centre diagonal
+        return txt[c:c + M].copy(), txt
+    if kind == "shift":                                              # window begin off by +-band/2: the best diagonal is the band's first / last
+        d = 0 if variant % 2 == 0 else W - 1
+        return txt[d:d + M].copy(), txt
+    if kind == "gap":                                                # one gap of 1, band/2, band-1 symbols at the start, middle, end; both directions
+        g = (1, max(c, 1), W - 1)[variant % 3]
+        if M < g + 8:
+            g = 1
+        p = (min(2, M - 2), M // 2, M - 2)[(variant // 3) % 3]
+        if (variant // 9) % 2 == 0:                                  # the read lacks g text symbols: the diagonal moves up by g
+            d0 = int(rng.integers(0, W - g))
+            return np.concatenate([txt[d0:d0 + p], txt[d0 + p + g:d0 + g + M]]), txt
+        d0 = int(rng.integers(g, W))                                 # g symbols more in the read: the diagonal moves down by g
+        p = min(p, M - g - 2)
+        return np.concatenate([txt[d0:d0 + p], rng.integers(0, 4, g, dtype=np.uint8), txt[d0 + p:d0 + M - g]]), txt
+    if kind == "random":
+        return rng.integers(0, 4, M, dtype=np.uint8), txt
+    r = _mutated(rng, txt, M, W)
+    if kind == "mutn":
+        k = int(rng.integers(1, 4))
+        if allow_n:
+            r[rng.integers(0, M, k)] = 4
+        else:
+            _substitute(rng, r, k)
+    if kind == "clip":                                               # the window ends early: N < M + band - 1, every third N < M
+        n = M - int(rng.integers(1, 4)) if variant % 3 == 0 else M + W - int(rng.integers(2, max(W - 1, 3)))
+        txt = txt[:max(n, W - 1, 1)]                                 # (below band - 1 symbols the reference's result is undefined)
+    return r, txt
+
+
+def range_jobs(seed, lens, band=31, first=0, allow_n=True, kinds=None):
+    """jobs of the given pattern lengths, job j of kind RANGE_KINDS[(first + j) % 17] (or kinds[j]) -> (patterns, texts, kind names)"""
+    rng = np.random.default_rng(seed)
+    pats, txts, names = [], [], []
+    seen = {}
+    for j, M in enumerate(lens):
+        kind = kinds[j] if kinds is not None else RANGE_KINDS[(first + j) % len(RANGE_KINDS)]
+        v = seen.get(kind, 0); seen[kind] = v + 1
+        p, t = range_job(rng, kind, int(M), band, v + first, allow_n)
+        assert len(p) == M and p.dtype == np.uint8 and t.dtype == np.uint8
+        pats.append(p); txts.append(t); names.append(kind)
+    return pats, txts, np.array(names)
+
+
+def range_layout(pats, txts, quals=None, flags=None):
+    """lay jobs out the way nvBowtie holds them: the windows one after another on one text (the first begins at the text's first symbol, the
+    last ends at its last), the reads stored reversed and / or complemented as each job's flags say (qualities mirrored with them)
+    -> dict(reads, roffs, quals, text, wb, we, flags), symbols one per byte"""
+    n = len(pats)
+    flags = np.zeros(n, dtype=np.uint8) if flags is None else np.asarray(flags, dtype=np.uint8)
+    stored, sq = [], []
+    for j in range(n):
+        r = pats[j]
+        q = quals[j] if quals is not None else None
+        if flags[j] & 2:
+            r = np.where(r < 4, 3 - r, r).astype(np.uint8)
+        if flags[j] & 1:
+            r = r[::-1]; q = q[::-1] if q is not None else None
+        stored.append(r); sq.append(q)
+    roffs = np.zeros(n + 1, dtype=np.uint32); roffs[1:] = np.cumsum([len(p) for p in pats])
+    toffs = np.zeros(n + 1, dtype=np.uint32); toffs[1:] = np.cumsum([len(t) for t in txts])
+    return dict(reads=np.concatenate(stored), roffs=roffs, quals=np.concatenate(sq) if quals is not None else None,
+                text=np.concatenate(txts), wb=toffs[:-1].copy(), we=toffs[1:].copy(), flags=flags)
+
+
+def flat_scheme(match, s):
+    """every penalty the same: the schemes under which a score reaches (rows + band) * step"""
+    return (match, s, s, -s, -s, -s, -s)
+
+
+def scheme_step(sv):
+    """the largest single penalty of a scheme"""
+    return max(sv[1], sv[2], -sv[3], -sv[4], -sv[5], -sv[6])
+
+
+# alignment types as the C-ABI numbers them
+_GLOBAL, _LOCAL, _SEMI_GLOBAL = 0, 1, 2
+
+# the edges of the three band-31 routes: (name, route whose limit it is, type, scheme, base qualities?).  The pattern lengths on either side
+# are not listed: band31_last_admitted() computes them from the admission rules
+RANGE_EDGES = (
+    # binary16 lanes: SEMI_GLOBAL, match 0, (M + 32) * step <= 2040
+    ("f16_flat8", "f16", _SEMI_GLOBAL, flat_scheme(0, 8), False),
+    ("f16_flat10", "f16", _SEMI_GLOBAL, flat_scheme(0, 10), False),
+    ("f16_flat1", "f16", _SEMI_GLOBAL, flat_scheme(0, 1), False),
+    ("f16_flat60", "f16", _SEMI_GLOBAL, flat_scheme(0, 60), False),
+    ("f16_ramp8", "f16", _SEMI_GLOBAL, (0, 2, 8, -8, -3, -8, -3), True),          # mm_max == step, qualities
+    ("f16_asym8", "f16", _SEMI_GLOBAL, (0, 5, 5, -8, -2, -6, -3), False),         # asymmetric gap terms
+    # int16 lanes: (M + 32) * step <= 8000
+    ("i16_sg_flat8", "i16", _SEMI_GLOBAL, flat_scheme(0, 8), False),
+    ("i16_sg_match3_flat8", "i16", _SEMI_GLOBAL, flat_scheme(3, 8), False),
+    ("i16_g_flat8", "i16", _GLOBAL, flat_scheme(0, 8), False),
+    ("i16_g_match8_flat8", "i16", _GLOBAL, flat_scheme(8, 8), False),
+    ("i16_sg_flat40", "i16", _SEMI_GLOBAL, flat_scheme(0, 40), False),
+    ("i16_g_match40_flat40", "i16", _GLOBAL, flat_scheme(40, 40), False),
+    ("i16_sg_flat1", "i16", _SEMI_GLOBAL, flat_scheme(0, 1), False),
+    ("i16_g_flat1", "i16", _GLOBAL, flat_scheme(0, 1), False),
+    ("i16_g_match1_flat1", "i16", _GLOBAL, flat_scheme(1, 1), False),
+    ("i16_sg_flat242", "i16", _SEMI_GLOBAL, flat_scheme(0, 242), False),          # M = 1: the other side is step 243
+    ("i16_g_flat242", "i16", _GLOBAL, flat_scheme(0, 242), False),
+    ("i16_sg_ramp8", "i16", _SEMI_GLOBAL, (0, 3, 8, -8, -3, -8, -3), True),
+    ("i16_g_asym8", "i16", _GLOBAL, (2, 5, 5, -8, -2, -6, -3), False),
+    # int16 lanes, LOCAL: match * M <= 1000, every penalty <= 4096
+    ("i16_local_match2", "i16", _LOCAL, (2, 6, 6, -8, -3, -8, -3), False),
+    ("i16_local_match1", "i16", _LOCAL, (1, 6, 6, -8, -3, -8, -3), False),
+    ("i16_local_match3", "i16", _LOCAL, (3, 6, 6, -8, -8, -8, -8), False),
+    ("i16_local_match5_ramp", "i16", _LOCAL, (5, 2, 6, -5, -3, -7, -2), True),
+    ("i16_local_mm4096", "i16", _LOCAL, (2, 4096, 4096, -8, -3, -8, -3), False),  # the other side is a penalty of 4097
+    ("i16_local_open4096", "i16", _LOCAL, (2, 6, 6, -4096, -3, -8, -3), False),
+    # int32: LOCAL scores past 32,767 (perfect reads of 5,000 symbols score 45,000)
+    ("i32_local_match9", "i32", _LOCAL, (9, 2, 60, -8, -3, -8, -3), False),
+)
+
+
+def band31_route(typ, sv, max_read_len):
+    """which arithmetic nvbio_banded_gotoh_score runs band 31 in for 4- or 2-bit reads on a 2-bit text under default flags: 'f16', 'i16'
+    or 'i32' -- the host's rules (packed_ok() and the binary16 condition of launch_pk_kernel(), csrc/gotoh_banded.hip) restated"""
+    match, mm_min, mm_max, pat_go, pat_ge, txt_go, txt_ge = sv
+    M, lim, step = int(max_read_len), 4096, scheme_step(sv)
+    packed = M > 0 and match >= 0 and 0 <= mm_min <= lim and 0 <= mm_max <= lim and -lim <= pat_go <= 0 and -lim <= pat_ge <= 0
+    if packed and typ == _LOCAL:
+        packed = match * M <= 1000                                   # the sink key (score << 5 | column) fits an int16
+    elif packed:
+        packed = -lim <= txt_go <= 0 and -lim <= txt_ge <= 0 and (M + 32) * max(step, match) <= 8000
+    if not packed:
+        return "i32"
+    if typ == _SEMI_GLOBAL and match == 0 and (M + 32) * step <= 2040 and mm_max <= 400:
+        return "f16"
+    return "i16"
+
+
+def band31_last_admitted(route, typ, sv):
+    """the largest max_read_len the rules admit to `route` under this scheme (None for 'i32': nothing is refused there)"""
+    if route == "f16":
+        return 2040 // scheme_step(sv) - 32
+    if route == "i16":
+        return 1000 // sv[0] if typ == _LOCAL else 8000 // max(scheme_step(sv), sv[0]) - 32
+    return None
+
+
+def range_edge_sides(edge):
+    """an edge of RANGE_EDGES -> ((scheme, max_read_len, route) last admitted, (scheme, max_read_len, route) first refused): the next
+    length, or where the length cannot grow (a penalty at its own limit; M = 1 under step 242) the next penalty"""
+    name, route, typ, sv, _ = edge
+    if route == "i32":
+        return ((sv, 5000, "i32"),)
+    M = band31_last_admitted(route, typ, sv)
+    if name.endswith("4096") or name.endswith("flat242"):
+        over = tuple(v + (1 if v > 0 else -1) if abs(v) == scheme_step(sv) else v for v in sv)
+        sides = ((sv, M, route), (over, M, band31_route(typ, over, M)))
+    else:
+        sides = ((sv, M, route), (sv, M + 1, band31_route(typ, sv, M + 1)))
+    assert band31_route(typ, sides[0][0], sides[0][1]) == route and sides[1][2] != route, name
+    return sides
