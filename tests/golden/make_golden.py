@@ -29,6 +29,9 @@ Fixtures:
   band31_range_golden.npz  band 31 at the limits of the library's three arithmetic routes (binary16, int16, int32): for either side of every
                   edge of tests/util.py::RANGE_EDGES a handful of pairs of that very length -- all-mismatch, perfect, shifted to the
                   band's rim, one long gap, mutated, N's, clipped windows, qualities -- and what the reference scored them.
+  full_range_golden.npz  full-matrix Gotoh at the limits of the library's routes (packed int16, cooperative, int32) and beyond int16, where
+                  the reference's short2 boundary column truncates: a few pairs of the very shape on either side of the edges of
+                  tests/test_gpu_full_range.py, scored by the reference with pattern and with text blocking.
 """
 import os
 import sys
@@ -697,6 +700,69 @@ def make_band31_range(R):
           % (n, cases[-1][0] + 1, int(out[:, 0].sum()), out[out[:, 0] == 1, 1].min(), out[:, 1].max(), os.path.getsize(path)))
 
 
+def full_range_cases():
+    """(combination, type, scheme, max_pattern_len, max_text_len, algorithm flags, route, pattern, qualities or None, text, kind) for
+    full_range_golden.npz: two jobs of the very shape on either side of the short-pattern edges of tests/util.py::FULL_PK_EDGES (the kinds
+    rotating from one combination to the next), of the cooperative kernel's bound at 8 rows, the two points past the edges and the three
+    cases beyond int16 of tests/test_gpu_full_range.py"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import util
+    G, L, SG = oracle.GLOBAL, oracle.LOCAL, oracle.SEMI_GLOBAL
+    pairs = (("allmm", "mut"), ("perfect", "gap"), ("shift", "mutn"), ("allmm", "random"), ("perfect", "mut"), ("shift", "gap"))
+    combos = []                                                      # (type, scheme, M, N, flags, qualities?, kinds)
+    for edge in util.FULL_PK_EDGES:
+        name, typ, _, M0, with_q = edge
+        if M0 is None and name != "l_key_match20":
+            continue                                                 # (patterns of 400 and more symbols: too large a file)
+        for sv, M, N in util.full_pk_edge_sides(edge):
+            combos.append((typ, sv, M, N, util.F_FORCE_PACKED, with_q, ("perfect", "mut") if M0 is None else pairs[len(combos) % len(pairs)]))
+    for typ, sv in ((G, util.flat_scheme(0, 8)), (SG, util.flat_scheme(3, 8))):
+        N = util.full_last_admitted("coop", typ, sv, 8)
+        for side in (0, 1):
+            combos.append((typ, sv, 8, N + side, 0, False, ("allmm", "mut") if typ == G else pairs[len(combos) % len(pairs)]))
+    combos.append((G, util.flat_scheme(0, 8), 8, 3867, 0, False, ("allmm", "mut")))
+    combos.append((L, (2, 3, 3, -5, -2, -5, -2), 1024, 1064, util.F_FORCE_PACKED, False, ("perfect",)))
+    combos.append((G, util.flat_scheme(0, 8), 8, 4200, 0, False, ("allmm", "perfect", "mut")))
+    combos.append((L, (9, 2, 60, -8, -3, -8, -3), 4000, 4040, 0, False, ("perfect", "mut")))
+    combos.append((SG, util.flat_scheme(0, 8), 4200, 4230, 0, False, ("allmm", "mut")))
+    cases = []
+    for combo, (typ, sv, M, N, algo, with_q, kinds) in enumerate(combos):
+        pats, txts, names = util.full_jobs(2000 + combo, [(M, N)] * len(kinds), kinds=list(kinds))
+        rng = np.random.default_rng(7000 + combo)
+        route = util.full_route(typ, sv, 0, M, N, len(kinds), algo, has_quals=with_q)
+        for p, t, k in zip(pats, txts, names):
+            q = None
+            if with_q:
+                q = np.full(M, 63, dtype=np.uint8) if k == "allmm" else rng.integers(0, 64, M, dtype=np.uint8)
+            cases.append((combo, typ, sv, M, N, algo, route, p, q, t, k))
+    return cases
+
+
+def make_full_range(R):
+    cases = full_range_cases()
+    n = len(cases)
+    schemes = sorted({c[2] for c in cases})
+    po = np.zeros(n + 1, dtype=np.uint32); to = np.zeros(n + 1, dtype=np.uint32)
+    out = np.zeros((n, 2, 4), dtype=np.int64)                       # per blocking: ok, score, sink
+    quals = []
+    for k, (combo, typ, sv, M, N, algo, route, pat, q, txt, kind) in enumerate(cases):
+        for blk in range(2):
+            ok, sc, sk = R.full_gotoh(typ, blk, oracle.Scheme(*sv), pat, txt, q)
+            out[k, blk] = (ok, sc, sk[0], sk[1])
+        po[k + 1] = po[k] + len(pat); to[k + 1] = to[k] + len(txt)
+        quals.append(q if q is not None else np.zeros(len(pat), np.uint8))
+    path = os.path.join(HERE, "full_range_golden.npz")
+    np.savez_compressed(path, combo=np.array([c[0] for c in cases], dtype=np.int32), typ=np.array([c[1] for c in cases], dtype=np.int32),
+                        scheme=np.array([schemes.index(c[2]) for c in cases], dtype=np.int32), schemes=np.array(schemes, dtype=np.int32),
+                        max_pattern_len=np.array([c[3] for c in cases], dtype=np.uint32), max_text_len=np.array([c[4] for c in cases], dtype=np.uint32),
+                        algo=np.array([c[5] for c in cases], dtype=np.uint32), route=np.array([c[6] for c in cases]),
+                        kind=np.array([c[10] for c in cases]), has_quals=np.array([c[8] is not None for c in cases], dtype=np.uint8),
+                        pats=np.concatenate([c[7] for c in cases]), quals=np.concatenate(quals), txts=np.concatenate([c[9] for c in cases]),
+                        pat_off=po, txt_off=to, out=out)
+    print("full_range_golden.npz: %d cases in %d combinations, scores %d..%d, %d bytes"
+          % (n, cases[-1][0] + 1, out[:, :, 1].min(), out[:, :, 1].max(), os.path.getsize(path)))
+
+
 def make_ref_fuzz(R):
     """run every test of tests/test_oracle_vs_reference.py against the live reference, recording what it returns"""
     import importlib.util
@@ -708,6 +774,8 @@ def make_ref_fuzz(R):
     O = oracle.Oracle()
     logs = {}
     for name in sorted(n for n in dir(mod) if n.startswith("test_")):
+        if "_live_ref" in getattr(mod, name).__code__.co_varnames[:2]:
+            continue                                                 # (a test that only runs against the live reference)
         rec = util.RecordingReference(R)
         getattr(mod, name)(O, rec)
         logs[name] = rec.log
@@ -741,4 +809,5 @@ if __name__ == "__main__":
     make_swtb(R)
     make_fswtb(R)
     make_band31_range(R)
+    make_full_range(R)
     make_ref_fuzz(R)

@@ -178,6 +178,26 @@ def test_banded_gotoh_range_golden(orc):
     assert n > 300 and g["out"][:, 1].max() == 45000 and (g["out"][:, 1] == -1784).any() and (g["out"][:, 1] == -7998).any()
 
 
+def test_full_gotoh_range_golden(orc):
+    """full-matrix Gotoh at the shapes and schemes where the library changes its kernel (tests/util.py::FULL_PK_EDGES, the cooperative
+    kernel's bound, the points past them) and beyond int16, where the result is what the reference's short2 boundary column leaves of it
+    (GLOBAL -33,600 comes back as 31,936): every row of the reference's outputs, pattern and text blocking"""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "full_range_golden.npz"), allow_pickle=False)
+    n = len(g["pat_off"]) - 1
+    for i in range(n):
+        sc = oracle.Scheme(*[int(v) for v in g["schemes"][g["scheme"][i]]])
+        p = g["pats"][g["pat_off"][i]:g["pat_off"][i + 1]]
+        t = g["txts"][g["txt_off"][i]:g["txt_off"][i + 1]]
+        q = g["quals"][g["pat_off"][i]:g["pat_off"][i + 1]] if g["has_quals"][i] else None
+        assert (len(p), len(t)) == (g["max_pattern_len"][i], g["max_text_len"][i])
+        for blk in range(2):
+            ok, s, sk = orc.full_gotoh(int(g["typ"][i]), blk, sc, p, t, q)
+            assert (ok, s, sk[0], sk[1]) == tuple(int(v) for v in g["out"][i, blk]), (i, blk, g["kind"][i])
+    out = g["out"]
+    assert 60 <= n <= 120 and (out[:, 0, 1] == -11928).any() and (out[:, 0, 1] == -29920).any() and (out[:, 0, 1] == -30936).any()
+    assert (out[:, 0, 1] == 31936).any() and out[:, :, 1].max() > 32767 and (out[:, 0, 1] == 2000).any() and (out[:, 0, 1] == 2048).any()
+
+
 def _tb_scheme(g, i):
     S = len(g["schemes"])
     v = g["known_schemes"][i] if i < int(g["n_known"]) else g["schemes"][i % S]

@@ -2,9 +2,10 @@
 reference sources), elsewhere against what that code returned for the same calls (tests/golden/ref_fuzz_golden.npz, the
 fixture `ref`).  Regenerate the recording with tests/golden/make_golden.py whenever these tests change."""
 import numpy as np
+import pytest
 
 import oracle
-from util import RANGE_KINDS, flat_scheme, range_jobs
+from util import FULL_KINDS, RANGE_KINDS, flat_scheme, full_jobs, full_shapes, range_jobs
 
 SCHEMES = [oracle.Scheme.simple(2, -1, -1, -1), oracle.Scheme.simple(0, -5, -8, -3),
            oracle.Scheme.simple(2, -1, -2, -1), oracle.Scheme(2, 2, 6, -8, -3, -8, -3),
@@ -97,6 +98,34 @@ def test_gotoh_long_fuzz(orc, ref):
             sc = schemes[(li + j) % len(schemes)]
             for typ in range(3):
                 assert ref.banded_gotoh(31, typ, sc, pats[j], txts[j], quals) == orc.banded_gotoh(31, typ, sc, pats[j], txts[j], quals), (M, kinds[j], typ)
+
+
+def test_full_gotoh_range_fuzz(orc, _live_ref):
+    """full-matrix Gotoh, both blockings, on the generator of tests/test_gpu_full_range.py: a round of its kinds at either side of the packed
+    and the cooperative bounds, past them and beyond int16, where the result is what the short2 boundary column leaves of it.  Live only:
+    patterns of 4,000 rows make too large a recording"""
+    if _live_ref is None:
+        pytest.skip("needs the reference's own host code (oracle/_ref)")
+    G, L, SG = oracle.GLOBAL, oracle.LOCAL, oracle.SEMI_GLOBAL
+    shapes = ((G, flat_scheme(0, 8), 9, 1491), (G, flat_scheme(0, 8), 24, 1477), (G, flat_scheme(8, 8), 24, 1476), (G, flat_scheme(0, 1), 9, 11992),
+              (SG, flat_scheme(0, 8), 24, 1476), (SG, flat_scheme(3, 8), 9, 1492), (L, (2, 3, 3, -5, -2, -5, -2), 1001, 1041),
+              (L, (20, 6, 6, -8, -3, -8, -3), 100, 140), (G, flat_scheme(0, 8), 8, 3740), (G, flat_scheme(0, 8), 256, 3493),
+              (SG, flat_scheme(3, 8), 256, 3492), (G, flat_scheme(0, 8), 8, 3867), (L, (2, 3, 3, -5, -2, -5, -2), 1024, 1064),
+              (G, flat_scheme(0, 8), 8, 4200), (G, flat_scheme(0, 8), 8, 4500), (L, (9, 2, 60, -8, -3, -8, -3), 4000, 4040),
+              (SG, flat_scheme(0, 8), 4200, 4230), (G, (2, 2, 6, -8, -3, -8, -3), 3000, 6000))
+    rng = np.random.default_rng(17)
+    beyond = 0
+    for si, (typ, sv, M, N) in enumerate(shapes):
+        jobs = len(FULL_KINDS) if M * N <= 400000 else 5
+        pats, txts, kinds = full_jobs(500 + si, full_shapes(si, M, N, jobs), first=3 * si)
+        for j in range(jobs):
+            quals = rng.integers(0, 64, len(pats[j]), dtype=np.uint8) if j % 2 else None
+            ms = oracle.SCORE_MIN if j % 3 else int(rng.integers(-200, 200))
+            for blk in range(2):
+                got = orc.full_gotoh(typ, blk, oracle.Scheme(*sv), pats[j], txts[j], quals, ms)
+                assert _live_ref.full_gotoh(typ, blk, oracle.Scheme(*sv), pats[j], txts[j], quals, ms) == got, (typ, sv, M, N, kinds[j], blk)
+                beyond += int(abs(got[1]) > 30000 and got[1] != oracle.SCORE_MIN)
+    assert beyond >= 20
 
 
 def test_whole_path_oracle_equals_reference_code(orc, ref):

@@ -404,3 +404,191 @@ def range_edge_sides(edge):
         sides = ((sv, M, route), (sv, M + 1, band31_route(typ, sv, M + 1)))
     assert band31_route(typ, sides[0][0], sides[0][1]) == route and sides[1][2] != route, name
     return sides
+
+
+# ---------------------------------------------------------------------------------------------
+# inputs for the full-matrix DP at the limits of its routes (tests/test_gpu_full_range.py, tests/golden/make_golden.py: full_range,
+# tests/test_oracle_vs_reference.py::test_full_gotoh_range_fuzz)
+# ---------------------------------------------------------------------------------------------
+# the algorithm flags the host rules read, as the C-ABI numbers them
+F_NO_UNGAPPED, F_NO_PACKED, F_FORCE_PACKED, F_PK_STRIPE8, F_NO_NARROW, F_NO_COOP = 1, 4, 8, 256, 512, 32768
+
+# neighbours differ, also round the end of the cycle (two jobs share a lane of the packed kernels); 7 of 17 are extreme (all-mismatch,
+# perfect, shifted to the window's last diagonal), 5 of 17 ordinary mutated reads; the first 15 hold 7 and 4
+FULL_KINDS = ("allmm", "mut", "perfect", "gap", "mut", "allmm", "shift", "mutn", "perfect", "gap", "mut", "random", "allmm", "mut", "shift",
+              "gap", "mut")
+FULL_GAPS = (1, 15, 40)
+
+
+def full_step(sv):
+    """the scheme's largest single term in absolute value, the match bonus among them"""
+    return max(abs(int(v)) for v in sv)
+
+
+def full_job(rng, kind, M, N, variant=0, allow_n=True):
+    """one (pattern as aligned, text window) pair for a pattern of M symbols in a window of N -> (pattern, text, kind): a window shorter
+    than its read holds no kind but an unrelated read ('short')"""
+    if N < M or M == 0:
+        return rng.integers(0, 4, M, dtype=np.uint8), rng.integers(0, 4, N, dtype=np.uint8), "short"
+    txt = rng.integers(0, 4, N, dtype=np.uint8)
+    if kind == "gap" and M < 4:
+        kind = "random"                                              # (no neighbour of a gap job in FULL_KINDS is a random one)
+    if kind == "allmm":                                              # the read is one letter, the text holds the other three
+        a = int(rng.integers(0, 4))
+        return np.full(M, a, dtype=np.uint8), ((a + 1 + rng.integers(0, 3, N)) % 4).astype(np.uint8), kind
+    if kind == "perfect":
+        d = int(rng.integers(0, N - M + 1))
+        return txt[d:d + M].copy(), txt, kind
+    if kind == "shift":                                              # the window's last diagonal: the sink is (N, M)
+        return txt[N - M:].copy(), txt, kind
+    if kind == "gap":                                                # one gap of 1, 15 or 40 symbols, in the pattern or in the text
+        g = FULL_GAPS[variant % 3]
+        in_text = (variant // 3) % 2 == 0 and N >= M + g             # the read lacks g symbols of the window
+        if not in_text and M < g + 8:
+            g = 1
+            in_text = in_text and N >= M + 1
+        p = (min(2, M - 2), M // 2, M - 2)[(variant // 6) % 3]
+        if in_text:
+            d = int(rng.integers(0, N - M - g + 1))
+            return np.concatenate([txt[d:d + p], txt[d + p + g:d + g + M]]), txt, kind
+        p = max(min(p, M - g - 2), 1)
+        d = int(rng.integers(0, N - (M - g) + 1))
+        return np.concatenate([txt[d:d + p], rng.integers(0, 4, g, dtype=np.uint8), txt[d + p:d + M - g]]), txt, kind
+    if kind == "random":
+        return rng.integers(0, 4, M, dtype=np.uint8), txt, kind
+    d = int(rng.integers(0, N - M + 1))                              # mut, mutn: 0-5 substitutions and (M > 12) an indel of 1-3 symbols
+    src = np.concatenate([txt[d:], rng.integers(0, 4, 4, dtype=np.uint8)])
+    if M > 12:
+        p = int(rng.integers(1, M - 4)); g = int(rng.integers(1, 4))
+        r = (np.concatenate([src[:p], src[p + g:]]) if rng.random() < 0.5 else
+             np.concatenate([src[:p], rng.integers(0, 4, g, dtype=np.uint8), src[p:]]))[:M]
+    else:
+        r = src[:M]
+    r = _substitute(rng, r.copy(), int(rng.integers(0, 6)))
+    if kind == "mutn":
+        k = int(rng.integers(1, 4))
+        if allow_n:
+            r[rng.integers(0, M, k)] = 4
+        else:
+            _substitute(rng, r, k)
+    return r, txt, kind
+
+
+def full_jobs(seed, shapes, first=0, allow_n=True, kinds=None):
+    """jobs of the given (M, N) shapes, job j of kind FULL_KINDS[(first + j) % 17] (or kinds[j]) -> (patterns, texts, kind names)"""
+    rng = np.random.default_rng(seed)
+    pats, txts, names, seen = [], [], [], {}
+    for j, (M, N) in enumerate(shapes):
+        kind = kinds[j] if kinds is not None else FULL_KINDS[(first + j) % len(FULL_KINDS)]
+        v = seen.get(kind, 0); seen[kind] = v + 1
+        p, t, kind = full_job(rng, kind, int(M), int(N), v + first, allow_n)
+        assert len(p) == M and len(t) == N and p.dtype == np.uint8 and t.dtype == np.uint8
+        pats.append(p); txts.append(t); names.append(kind)
+    return pats, txts, np.array(names)
+
+
+def full_shapes(seed, M, N, n, dominant=2, of=3, min_text=0):
+    """n shapes: `dominant` of every `of` jobs have the batch's shape (M, N), the others a pattern of 1..M symbols in a window of
+    min_text..N; every 16th of those windows is shorter than its read and every 40th empty (they report nothing)"""
+    rng = np.random.default_rng(seed)
+    shapes, odd = [], 0
+    for j in range(n):
+        if j % of < dominant:
+            shapes.append((M, N))
+            continue
+        m = int(rng.integers(1, M + 1))
+        w = int(rng.integers(max(min_text, m), max(N, m) + 1)) if N >= m else N
+        if min_text == 0 and odd % 16 == 7:
+            w = int(rng.integers(0, m)) if odd % 40 != 39 else 0
+        odd += 1
+        shapes.append((m, min(w, N)))
+    return shapes
+
+
+def _band31_int16_ok(sv, M):
+    """packed_ok( SEMI_GLOBAL, ... ) of csrc/gotoh_banded.hip: what the narrow route asks of the band-31 kernel it borrows"""
+    match, lim = sv[0], 4096
+    pen = (sv[1], sv[2], -sv[3], -sv[4], -sv[5], -sv[6])
+    return M > 0 and match >= 0 and all(0 <= v <= lim for v in pen) and (M + 32) * max(max(pen), match) <= 8000
+
+
+def full_route(typ, sv, blocking, M, N, n, algo=0, has_min_scores=False, read_bits=4, text_bits=2, has_quals=False):
+    """which kernel nvbio_full_gotoh_score gives the DP of a batch of n jobs declared as max_pattern_len = M, max_text_len = N: 'coop',
+    'pk' (two jobs per lane, 8 columns per stripe), 'pk16' (the end-to-end build, 16 columns) or 'i32', behind 'narrow+' where the
+    band-31 route runs in front -- full_score() and full_packed_ok() of csrc/gotoh_full.hip restated.  Only the jobs of shape (M, N) of
+    a 'pk' batch run packed"""
+    match, mm_min, mm_max, pat_go, pat_ge, txt_go, txt_ge = (int(v) for v in sv)
+    step = full_step(sv)
+    pk_bits = text_bits == 2 and read_bits in (2, 4)
+    wanted = (n >= 262144 or bool(algo & F_FORCE_PACKED)) and not algo & F_NO_PACKED and not blocking
+    e2e = typ == _SEMI_GLOBAL and match == 0 and not algo & F_NO_UNGAPPED
+    if (typ in (_GLOBAL, _SEMI_GLOBAL) and not e2e and not wanted and not has_min_scores and pk_bits and 1 <= M <= 256
+            and (M + N + 2) * step <= 30000 and not algo & F_NO_COOP):
+        return "coop"
+    shortcut = (e2e and pk_bits and mm_min >= 0 and mm_max >= 0 and (not has_quals or mm_min == mm_max)
+                and pat_go < 0 and txt_go < 0 and pat_ge <= 0 and txt_ge <= 0)
+    terms_ok = match >= 0 and all(v >= 0 for v in (mm_min, mm_max, -pat_go, -pat_ge, -txt_go, -txt_ge))
+    packed = (wanted and pk_bits and M > 0 and N > 0 and terms_ok and step <= 4096 and (M + N) * step <= 12000
+              and (typ != _LOCAL or match * M <= 2000))
+    narrow = shortcut and not blocking and not algo & (F_NO_NARROW | F_NO_PACKED) and M <= 161 and _band31_int16_ok(sv, M) and pat_ge < 0
+    dp = "i32" if not packed else "pk16" if typ == _SEMI_GLOBAL and match == 0 and not algo & F_PK_STRIPE8 else "pk"
+    return ("narrow+" if narrow else "") + dp
+
+
+def full_last_admitted(route, typ, sv, M=None):
+    """the last max_text_len the rule of `route` admits at max_pattern_len = M; with M = None the last max_pattern_len of the rules that
+    bound the pattern alone: LOCAL's sink key for 'pk' (match * M <= 2000), the cooperative kernel's 256 rows, the narrow route's 161"""
+    step = full_step(sv)
+    if route in ("pk", "pk16"):
+        return 2000 // sv[0] if M is None else 12000 // step - M
+    if route == "coop":
+        return 256 if M is None else 30000 // step - M - 2
+    if route == "narrow":
+        return min(161, 8000 // step - 32)
+    return None
+
+
+def full_layout(pats, txts, quals=None, flags=None):
+    """range_layout() plus what the oracle's batch call takes: the patterns as aligned, one after another, and the offsets of both"""
+    L = range_layout(pats, txts, quals, flags)
+    L["pats"] = np.concatenate(pats)
+    L["pquals"] = np.concatenate(quals) if quals is not None else None
+    L["toffs"] = np.concatenate([L["wb"], L["we"][-1:]]).astype(np.uint32)
+    L["M"] = np.array([len(p) for p in pats], dtype=np.int64)
+    L["N"] = np.array([len(t) for t in txts], dtype=np.int64)
+    return L
+
+
+# the edges of the packed route: (name, type, scheme, max_pattern_len or None for LOCAL's key rule, base qualities?)
+FULL_PK_EDGES = (
+    ("g_flat8_m9", _GLOBAL, flat_scheme(0, 8), 9, False),
+    ("g_flat8_m24", _GLOBAL, flat_scheme(0, 8), 24, False),
+    ("g_match8_flat8_m24", _GLOBAL, flat_scheme(8, 8), 24, False),
+    ("g_flat40_m9", _GLOBAL, flat_scheme(0, 40), 9, False),
+    ("g_flat1_m9", _GLOBAL, flat_scheme(0, 1), 9, False),
+    ("g_flat4096_m1", _GLOBAL, flat_scheme(0, 4096), 1, False),                  # M + N = 2 | 3
+    ("g_penalty4096_m1", _GLOBAL, flat_scheme(0, 4096), 1, False),               # the other side is a penalty of 4097
+    ("g_asym8_m24", _GLOBAL, (2, 5, 5, -8, -2, -6, -3), 24, False),
+    ("sg_flat8_m24", _SEMI_GLOBAL, flat_scheme(0, 8), 24, False),                # match 0: the end-to-end build, 16 columns
+    ("sg_flat8_m9", _SEMI_GLOBAL, flat_scheme(0, 8), 9, False),
+    ("sg_match3_flat8_m9", _SEMI_GLOBAL, flat_scheme(3, 8), 9, False),
+    ("sg_ramp8_m24", _SEMI_GLOBAL, (0, 2, 8, -8, -3, -8, -3), 24, True),
+    ("l_flat8_m24", _LOCAL, flat_scheme(2, 8), 24, False),
+    ("l_key_match2", _LOCAL, (2, 3, 3, -5, -2, -5, -2), None, False),             # M = 1000 | 1001
+    ("l_key_match1", _LOCAL, (1, 2, 2, -2, -1, -2, -1), None, False),             # M = 2000 | 2001
+    ("l_key_match20", _LOCAL, (20, 6, 6, -8, -3, -8, -3), None, False),           # M = 100 | 101
+    ("l_key_match5_ramp", _LOCAL, (5, 2, 6, -5, -3, -7, -2), None, True),         # M = 400 | 401
+)
+
+
+def full_pk_edge_sides(edge):
+    """an edge of FULL_PK_EDGES -> ((scheme, M, N) last admitted, (scheme, M, N) first refused) under NVBIO_ALN_FORCE_PACKED_DP: the
+    next window length; for LOCAL's key rule the next pattern length in a window of M + 40; for the penalty limit the next penalty"""
+    name, typ, sv, M, _ = edge
+    if M is None:
+        M = full_last_admitted("pk", typ, sv)
+        return ((sv, M, M + 40), (sv, M + 1, M + 41))
+    N = full_last_admitted("pk", typ, sv, M)
+    if "penalty" in name:
+        return ((sv, M, N), (tuple(v + (1 if v > 0 else -1) if abs(v) == 4096 else v for v in sv), M, N))
+    return ((sv, M, N), (sv, M, N + 1))
