@@ -869,6 +869,69 @@ nvbio_status nvbio_read_queue_filter(int device, const uint32_t* queue_dev, uint
                                      uint32_t* count_dev, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * nvBowtie's ALL-MAPPING mode (`--mode all`, bowtie2 -a: every placement of a read within max_dist edits), its data-parallel steps
+ * (Aligner::all + score_all, nvBowtie/bowtie2/cuda/aligner_all.h:29-139,141-485).  The reference maps ONE seed index per pass
+ * (map_exact with seed_range = (seed, seed + 1), aligner_all.h:76-94) through the multi-retry map_kernel (mapping_inl.h:563-634), which,
+ * as the reference's code behaves, stores hits at retry == max_reseed only (its other store condition, :627, compares unsigned
+ * range_sum < rep_seeds * 0): the seed of pass `seed` sits at stored offset max_reseed * (seed_freq / (max_reseed + 1)) + seed * seed_freq,
+ * and a pass whose seed would end past the read has none.  The passes share no state, so the calls below take every seed index at once
+ * (or one: seeds_per_read = 1 and first_offset = that seed's offset); the result is the same multiset of alignments.
+ *   fw_ranges_dev / rc_ranges_dev [n_reads x seeds_per_read]: the two nvbio_fm_match calls of the exact mapper over the seeds of the
+ *   STORED (reversed) reads, exactly as nvbio_seed_hits_map takes them.  Hit order: read-major, then seed index, then the forward
+ *   range before the reverse-complemented one, then SA row.  A range counts size & 0xFFFFF rows (SeedHit's 20-bit range_delta,
+ *   seed_hit.h:217, as nvbio_seed_hits_map keeps it); there is no max_hits: one seed per pass never fills a deque of max_hits >= 2.
+ * Scratch is the caller's: every call that needs some has a *_temp_bytes query and fails with NVBIO_ERR_INVALID on less.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct
+{
+    uint32_t seeds_per_read;   /* seed slots per read and strand: the stride of the range arrays                                  */
+    uint32_t first_offset;     /* stored offset of seed 0: max_reseed * (seed_freq / (max_reseed + 1))        (mapping_inl.h:610) */
+    uint32_t seed_interval;    /* seed_freq( read_len )                                                                          */
+    uint32_t seed_len;
+    uint32_t read_len;         /* reads of one length (< 1024: SeedHit keeps positions in 10 bits)                               */
+} nvbio_all_hits_params;
+
+/* gather_ranges + both inclusive_scans of score_all (mapping.cu:29-71, aligner_all.h:209-233) in one scan: slots_dev[2 * n_reads *
+ * seeds_per_read] = the inclusive uint64 scan of the range sizes in hit order; a seed that found nothing or holds an N (empty range) and
+ * a seed slot that ends past the read (mapping_inl.h:611) contribute 0.  *n_hits_dev (device) = the total.  No host synchronisation. */
+nvbio_status nvbio_all_hits_scan_temp_bytes(uint32_t n_reads, uint32_t seeds_per_read, uint64_t* bytes);
+nvbio_status nvbio_all_hits_scan(int device, const nvbio_uint2* fw_ranges_dev, const nvbio_uint2* rc_ranges_dev, uint32_t n_reads,
+                                 const nvbio_all_hits_params* params, uint64_t* slots_dev, uint64_t* n_hits_dev, void* temp_dev, uint64_t temp_bytes,
+                                 void* stream);
+
+/* select_all_kernel (select.cu:91-135) for the hits [begin, end) of the scan, one lane per hit: hits->hit_loc_dev[o - begin] = the SA
+ * row, hits->hit_read_id_dev, hits->hit_seed_dev = packed_seed( pos_in_read, 0, rc, 0 ).  The layout makes read and seed index
+ * arithmetic, so the reference's two binary searches (hit -> range -> read) are one.  hits->n = the room of the queues (>= end - begin);
+ * a hit past the scan's total is not written. */
+nvbio_status nvbio_all_hits_select(int device, const nvbio_uint2* fw_ranges_dev, const nvbio_uint2* rc_ranges_dev, uint32_t n_reads,
+                                   const nvbio_all_hits_params* params, const uint64_t* slots_dev, uint64_t begin, uint64_t end,
+                                   const nvbio_hit_queues* hits, void* stream);
+
+/* What the reference leaves as a TODO (aligner_all.h:357-358: "sub-sort by read_id/RC flag so as to ... allow removing duplicate
+ * extensions"): of the hits->n LOCATED hits (after nvbio_seed_hits_loc) one per distinct (read_id, rc, loc) is kept, in ascending order of
+ * (read_id, rc, loc), at the front of hits_out (which may be `hits` itself; dense queues, idx_queue_dev = NULL); *n_out_dev (device) = how
+ * many.  The kept hits' packed_seed holds the strand only.  Built on nvbio_sort_unique_keys over key = read_id << 33 | rc << 32 | loc. */
+nvbio_status nvbio_all_hits_unique_temp_bytes(uint32_t n, uint64_t* bytes);
+nvbio_status nvbio_all_hits_unique(int device, const nvbio_hit_queues* hits, const nvbio_hit_queues* hits_out, uint32_t* n_out_dev, void* temp_dev,
+                                   uint64_t temp_bytes, void* stream);
+
+/* AllScoreStream::output for every work item (score_inl.h:671-694): work item i scored hit idx_queue[i] (NULL: hit i) with scores_dev[i];
+ * every one with scores_dev[i] >= min_score appends (read_id, rc, loc, score) to the four output arrays from slot out_offset on, IN
+ * WORK-ITEM ORDER (the reference hands out ring-buffer slots through an atomic, in arbitrary order).  *count_dev (device) += the
+ * number accepted; records that would land at or past out_capacity are dropped, the count is not (the cigar_lens convention). */
+nvbio_status nvbio_all_score_output_temp_bytes(uint32_t n, uint64_t* bytes);
+nvbio_status nvbio_all_score_output(int device, const nvbio_hit_queues* hits, const int32_t* scores_dev, int32_t min_score, uint32_t* out_read_id_dev,
+                                    uint8_t* out_rc_dev, uint32_t* out_loc_dev, int32_t* out_score_dev, uint64_t out_offset, uint64_t out_capacity,
+                                    uint64_t* count_dev, void* temp_dev, uint64_t temp_bytes, void* stream);
+
+/* AllTracebackStream::init_context (traceback_inl.h:346-370) for n accepted records: the four per-job arrays of an nvbio_alignment_batch
+ * -- read id, the orientation flags nvbio_score_stream_flatten sets (reads_reversed as there), and the window recomputed from the
+ * record's locus by the scoring stream's rule -- for nvbio_banded_sw_traceback and nvbio_finish_alignment. */
+nvbio_status nvbio_all_traceback_flatten(int device, const uint32_t* rec_read_id_dev, const uint8_t* rec_rc_dev, const uint32_t* rec_loc_dev, uint32_t n,
+                                         const uint32_t* read_index_dev, uint32_t band_len, uint32_t genome_len, uint32_t reads_reversed,
+                                         uint32_t* read_id_dev, uint8_t* flags_dev, uint32_t* win_begin_dev, uint32_t* win_end_dev, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * nvBowtie's PAIRED-END best-approx loop, its data-parallel steps (aligner_best_approx_paired.h:84-200,590-1000): the anchor mate's seed hits
  * are walked as in the single-end loop (deques, select, locate: the calls above); a selected hit's anchor is band-aligned against a
  * threshold derived from the best PAIRS found so far (BestAnchorScoreStream, score_inl.h:143-274; compute_target_score,

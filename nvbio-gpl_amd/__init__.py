@@ -1701,6 +1701,155 @@ def score_reduce_effort(active, hits, read_len, n_ext, params, best, best_rc, tr
                                            _stream_ptr(hits.device)))
 
 
+# ---- nvBowtie's all-mapping mode (include/nvbio_amd.h: nvbio_all_*; host/nvbio_amd/all_mapping.hpp) ---------------------------------
+class _AllHitsParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("seeds_per_read", "first_offset", "seed_interval", "seed_len", "read_len")]
+
+
+class AllHitsParams:
+    """nvbio_all_hits_params: the seed layout of the all-mapping mode (seed j of a read at stored offset first_offset + j * seed_interval)"""
+
+    def __init__(self, seeds_per_read, first_offset, seed_interval, seed_len, read_len):
+        self.c = _AllHitsParams(seeds_per_read, first_offset, seed_interval, seed_len, read_len)
+
+
+def band_length(max_dist):
+    """Aligner::band_length (nvBowtie/bowtie2/cuda/aligner.h:149-158)"""
+    band_len = 4
+    while band_len - 1 < max_dist * 2 + 1:
+        band_len *= 2
+    return band_len - 1
+
+
+def _temp_for(query, *args, device="cuda:0"):
+    b = ctypes.c_uint64(0)
+    _check(query(*args, ctypes.byref(b)))
+    return _torch().empty(max(int(b.value), 256), dtype=_torch().uint8, device=device), b.value
+
+
+def all_hits_scan(fw_ranges, rc_ranges, n_reads, params):
+    """gather_ranges + the scans of score_all (nvbio_all_hits_scan) -> (slots int64 [2 * n_reads * seeds_per_read], n_hits int64 [1]),
+    both on the device: the inclusive scan of the range sizes in hit order and its total"""
+    torch = _torch()
+    dev = fw_ranges.device
+    slots = torch.zeros(2 * n_reads * params.c.seeds_per_read, dtype=torch.int64, device=dev)
+    n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
+    tmp, nb = _temp_for(lib().nvbio_all_hits_scan_temp_bytes, ctypes.c_uint32(n_reads), ctypes.c_uint32(params.c.seeds_per_read), device=dev)
+    _check(lib().nvbio_all_hits_scan(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), ctypes.c_uint32(n_reads), ctypes.byref(params.c),
+                                     _ptr(slots), _ptr(n_hits), _ptr(tmp), ctypes.c_uint64(nb), _stream_ptr(dev)))
+    return slots, n_hits
+
+
+def all_hits_select(fw_ranges, rc_ranges, n_reads, params, slots, begin, end, hits):
+    """select_all_kernel (nvbio_all_hits_select): fills hits.read_id / loc (the SA row) / seed for the hits [begin, end) of the scan"""
+    dev = hits.device
+    hq = hits.c_struct()
+    _check(lib().nvbio_all_hits_select(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), ctypes.c_uint32(n_reads), ctypes.byref(params.c),
+                                       _ptr(slots), ctypes.c_uint64(begin), ctypes.c_uint64(end), ctypes.byref(hq), _stream_ptr(dev)))
+
+
+def all_hits_unique(hits):
+    """nvbio_all_hits_unique, in place: one located hit per distinct (read_id, rc, loc) at the front of the queues, in ascending order
+    -> their number (hits.n is lowered to it)"""
+    torch = _torch()
+    dev = hits.device
+    n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+    tmp, nb = _temp_for(lib().nvbio_all_hits_unique_temp_bytes, ctypes.c_uint32(hits.n), device=dev)
+    hq = hits.c_struct()
+    _check(lib().nvbio_all_hits_unique(FMIndex._dev_index(dev), ctypes.byref(hq), ctypes.byref(hq), _ptr(n_out), _ptr(tmp), ctypes.c_uint64(nb),
+                                       _stream_ptr(dev)))
+    hits.n = int(n_out.item())
+    return hits.n
+
+
+def all_score_output(hits, scores, min_score, out, out_offset, count):
+    """AllScoreStream::output (nvbio_all_score_output): appends (read_id, rc, loc, score) of the hits with score >= min_score to
+    out = (read_id int32, rc uint8, loc int32, score int32) from slot out_offset on, in hit order; count int64 [1] += the number accepted"""
+    dev = hits.device
+    tmp, nb = _temp_for(lib().nvbio_all_score_output_temp_bytes, ctypes.c_uint32(hits.n), device=dev)
+    hq = hits.c_struct()
+    _check(lib().nvbio_all_score_output(FMIndex._dev_index(dev), ctypes.byref(hq), _ptr(scores), ctypes.c_int32(min_score), _ptr(out[0]), _ptr(out[1]),
+                                        _ptr(out[2]), _ptr(out[3]), ctypes.c_uint64(out_offset), ctypes.c_uint64(out[0].numel()), _ptr(count), _ptr(tmp),
+                                        ctypes.c_uint64(nb), _stream_ptr(dev)))
+
+
+def all_traceback_flatten(rec_read_id, rec_rc, rec_loc, read_index, band_len, genome_len, reads_reversed=True):
+    """AllTracebackStream::init_context (nvbio_all_traceback_flatten) -> (read_id, flags, win_begin, win_end) of the accepted records"""
+    torch = _torch()
+    dev = rec_read_id.device
+    n = rec_read_id.numel()
+    ri = _dev_tensor(read_index, torch.int32, dev)
+    rid = torch.empty(n, dtype=torch.int32, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    wb = torch.empty(n, dtype=torch.int32, device=dev)
+    we = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(lib().nvbio_all_traceback_flatten(FMIndex._dev_index(dev), _ptr(rec_read_id), _ptr(rec_rc), _ptr(rec_loc), ctypes.c_uint32(n), _ptr(ri),
+                                             ctypes.c_uint32(band_len), ctypes.c_uint32(genome_len), ctypes.c_uint32(1 if reads_reversed else 0),
+                                             _ptr(rid), _ptr(flags), _ptr(wb), _ptr(we), _stream_ptr(dev)))
+    return rid, flags, wb, we
+
+
+class _AllMappingParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("seed_len", "seed_freq", "max_reseed", "max_dist", "band", "aln_type", "hits_per_batch", "unique",
+                                                "per_seed_passes", "want_cigars")]
+
+
+class _AllMappingOutput(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_uint64)] + [(n, ctypes.c_void_p) for n in ("read_id", "rc", "loc", "score", "win_begin", "source", "sink", "ed",
+                                                                                  "cigars", "cigar_lens", "mds", "mds_lens")] + \
+               [("cigar_stride", ctypes.c_uint32), ("mds_stride", ctypes.c_uint32)]
+
+
+class _AllMappingStats(ctypes.Structure):
+    _fields_ = [("n_hits", ctypes.c_uint64), ("n_scored", ctypes.c_uint64), ("n_alignments", ctypes.c_uint64), ("chunks", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
+class AllMappingParams:
+    """AllMappingParams of host/nvbio_amd/all_mapping.hpp with nvBowtie's defaults; min_score defaults to -max_dist and the scheme to the
+    edit-distance one (0, -1, -1, -1): the mode as the reference ships it"""
+
+    def __init__(self, seed_len=22, seed_freq=0, max_reseed=2, max_dist=15, band=0, aln_type=SEMI_GLOBAL, hits_per_batch=0, unique=False,
+                 per_seed_passes=False, scheme=(0, -1, -1, -1), min_score=None):
+        self.seed_len, self.seed_freq, self.max_reseed, self.max_dist, self.band = seed_len, seed_freq, max_reseed, max_dist, band
+        self.aln_type, self.hits_per_batch, self.unique, self.per_seed_passes = aln_type, hits_per_batch, unique, per_seed_passes
+        self.scheme, self.min_score = tuple(scheme), (-max_dist if min_score is None else min_score)
+
+
+def all_mapping(fmi, genome2, genome_len, stored_reads4, n_reads, read_len, params, capacity, want_cigars=False, cigar_stride=64, mds_stride=0):
+    """nvBowtie's all-mapping mode (Aligner::all, aligner_all.h:29-485) through the C++ host loop nvbio_host_all_mapping: every alignment of
+    every read that reaches params.min_score.  stored_reads4: the reads as nvBowtie stores them (reversed), 4-bit packed, back to back.
+    -> dict(read_id, rc, loc, score [+ win_begin, source, sink, ed, cigars, cigar_lens (, mds, mds_lens)]: device tensors cut to
+    min(n_alignments, capacity) records; n_hits, n_scored, n_alignments, chunks)"""
+    torch = _torch()
+    from .pipeline import _host_lib
+    dev = fmi.device
+    cap = int(capacity)
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+    out = dict(read_id=i32(cap), rc=torch.zeros(cap, dtype=torch.uint8, device=dev), loc=i32(cap), score=i32(cap))
+    if want_cigars:
+        out.update(win_begin=i32(cap), source=i32(cap, 2), sink=i32(cap, 2), ed=i32(cap), cigars=torch.zeros((cap, cigar_stride), dtype=torch.int16, device=dev),
+                   cigar_lens=i32(cap))
+        if mds_stride:
+            out.update(mds=torch.zeros((cap, mds_stride), dtype=torch.uint8, device=dev), mds_lens=i32(cap))
+    o = _AllMappingOutput(cap, *[_ptr(out.get(k)) for k in ("read_id", "rc", "loc", "score", "win_begin", "source", "sink", "ed", "cigars", "cigar_lens",
+                                                            "mds", "mds_lens")], cigar_stride if want_cigars else 0, mds_stride if want_cigars else 0)
+    p = _AllMappingParams(params.seed_len, params.seed_freq, params.max_reseed, params.max_dist, params.band, int(params.aln_type), params.hits_per_batch,
+                          1 if params.unique else 0, 1 if params.per_seed_passes else 0, 1 if want_cigars else 0)
+    sw = _SWScheme(*params.scheme)
+    st = _AllMappingStats()
+    reads = _dev_tensor(stored_reads4, torch.int32, dev)
+    rc = _host_lib().nvbio_host_all_mapping(ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(reads),
+                                            ctypes.c_uint32(n_reads), ctypes.c_uint32(read_len), ctypes.byref(sw), ctypes.c_int32(params.min_score),
+                                            ctypes.byref(p), ctypes.byref(o), _stream_ptr(dev), ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
+    k = min(int(st.n_alignments), cap)
+    res = {name: t[:k] for name, t in out.items()}
+    res.update(n_hits=int(st.n_hits), n_scored=int(st.n_scored), n_alignments=int(st.n_alignments), chunks=int(st.chunks))
+    return res
+
+
 # ---- the generic rank dictionary (nvbio_rank_dictionary_*) -------------------------------------------------------------------------
 class RankDictionary:
     """nvbio::rank_dictionary<2, K, PackedStream<const uint32*|const uint64*, uint8, 2, true>, occ, count_table> over plain word storage

@@ -14,6 +14,7 @@ struct nvbio_host_best_approx_params
 struct nvbio_host_best_approx_stats { uint64_t n_extensions; uint32_t passes, multi_passes, seeding_passes, pad; };
 
 const char* nvbio_host_last_error(void) { return g_err; }
+void nvbio_host_set_error(const char* msg) { strncpy( g_err, msg, sizeof(g_err) - 1 ); g_err[sizeof(g_err) - 1] = 0; }     // for the library's other entry points
 
 // returns 0 on success; best_dev [4 n_reads] int32 (16-byte aligned), best_rc_dev [n_reads]
 int nvbio_host_best_approx(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads4_dev,
