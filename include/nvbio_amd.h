@@ -869,6 +869,63 @@ nvbio_status nvbio_read_queue_filter(int device, const uint32_t* queue_dev, uint
                                      uint32_t* count_dev, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * The same loop over reads of DIFFERENT lengths (a ragged batch: read r = symbols [read_offsets[r], read_offsets[r+1]) of the stored
+ * stream).  nvBowtie's map_kernel computes everything per lane (mapping_inl.h:504-529): read_len = range.y - range.x, the filter
+ * `read_len < params.min_read_len`, seed_freq( read_len ), retry_stride = seed_freq / (max_reseed + 1), and the walk
+ * pos = begin + retry * retry_stride; pos + seed_len <= end; pos += seed_freq.  With M_r the length of read r and L = seed_len:
+ *   S_r     = seed_intervals_dev[r]: seed_freq( M_r ), evaluated by the caller as the reference evaluates it (SimpleFunc in float32,
+ *             params.h:87-100: int( 1 + 1.15f * sqrtf( M_r ) ) by default)
+ *   first_r = seeding_pass * (S_r / (max_reseed + 1))
+ *   seed j of read r at stored offset first_r + j * S_r while first_r + j * S_r + L <= M_r: count_r seeds, possibly none
+ *   a read with M_r < max( min_read_len, L ) is FILTERED: no seeds in any pass, never flagged for reseeding (:510-514); it ends unaligned.
+ *   DIVERGENCE: the reference seeds a read with min_read_len <= M_r < seed_len once, with the whole read (seed_len = min( params.seed_len,
+ *   read_len ), :516); this library treats such a read as filtered.
+ *   A read that passed the filter but has no seed slot left in this pass (M_r < L + first_r) gets an empty deque, and -- range_count == 0 --
+ *   is flagged for reseeding like any read without hits (:549).
+ * The arrays of ranges keep ONE stride for the whole batch, seeds_per_read = the largest count_r of the pass (the caller computes it from
+ * the lengths); slots count_r .. seeds_per_read-1 of a read are ignored.  M_r < 1024 for every read (SeedHit keeps positions in 10 bits,
+ * seed_hit.h:217): the caller checks that, these calls see the lengths on the device only.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct
+{
+    const uint32_t* read_offsets_dev;    /* n_reads + 1 symbol offsets: the batch's sequence_index                               */
+    const uint32_t* seed_intervals_dev;  /* n_reads: S_r                                                                         */
+    uint32_t        seeds_per_read;      /* stride of the per-seed arrays: the largest number of seeds of a read in this pass    */
+    uint32_t        seeding_pass;        /* retry: 0 .. max_reseed                                             (mapping_inl.h:520) */
+    uint32_t        max_reseed;
+    uint32_t        seed_len;
+    uint32_t        min_read_len;        /* params.min_read_len (default 12); the threshold is max( min_read_len, seed_len )      */
+} nvbio_ragged_seed_layout;
+
+/* nvbio_read_queue_begin for a ragged batch (mapping_inl.h:504-529 for the offsets; select_init, aligner_best_approx.h:363-450 for the rest):
+ * seed_offsets_dev[t * seeds_per_read + j] = read_offsets[read] + first_read + j * S_read for the seeds the read has, 0 for the slots it has
+ * not -- a PLAIN string set of n * seeds_per_read strings of seed_len symbols for nvbio_fm_match (offsets_dev = seed_offsets_dev,
+ * fixed_len = seed_len, seeds_per_string = 0), since the seed enumeration of nvbio_string_set bases a read's seeds at its first symbol.
+ * n_symbols = read_offsets[n_reads] (at least seed_len, so that offset 0 names a string inside the stream). */
+nvbio_status nvbio_read_queue_begin_ragged(int device, const uint32_t* queue_dev, uint32_t n, const nvbio_ragged_seed_layout* layout, uint32_t n_symbols,
+                                           uint32_t top_seed, uint32_t max_effort_init, uint32_t* seed_offsets_dev, uint32_t* active_dev, uint32_t* trys_dev,
+                                           void* stream);
+/* nvbio_seed_hits_map for a ragged batch (seed_mapper<EXACT_MAPPING>::enact + map_kernel, mapping_inl.h:193-282,504-556): fw_ranges_dev /
+ * rc_ranges_dev [n_reads x seeds_per_read] over the strings of nvbio_read_queue_begin_ragged; the forward hit's pos_in_read is
+ * M_r - offset - seed_len (:241); deques need nvbio_seed_hits_capacity( seeds_per_read, max_hits ) entries per read; reseed_dev[r] = 0 for a
+ * filtered read, else the rule of :549. */
+nvbio_status nvbio_seed_hits_map_ragged(int device, const nvbio_uint2* fw_ranges_dev, const nvbio_uint2* rc_ranges_dev, const uint32_t* read_queue_dev,
+                                        uint32_t n_reads, const nvbio_ragged_seed_layout* layout, uint32_t max_hits, uint32_t rep_seeds,
+                                        nvbio_uint2* deques_dev, uint32_t* sizes_dev, uint8_t* reseed_dev, void* stream);
+/* init_alignments with every read's own threshold (aligner.h:279-301; min_score( read_len ), aligner_best_approx.h:77):
+ * best_dev[4 r ..] = { min_scores_dev[r], -1, min_scores_dev[r], -1 } */
+nvbio_status nvbio_best_approx_init_ragged(int device, uint32_t n_reads, const int32_t* min_scores_dev, int32_t* best_dev, uint8_t* best_rc_dev, void* stream);
+/* nvbio_score_reduce_effort / _multi with the read's own length in `distinct` (read_len / 2, nvbio/io/alignments_inl.h:26-38; reduce_inl.h:65-140):
+ * read_offsets_dev = the n_reads + 1 symbol offsets; of params only max_effort, min_ext and max_ext are read. */
+nvbio_status nvbio_score_reduce_effort_ragged(int device, const uint32_t* active_dev, const nvbio_hit_queues* hits, const uint32_t* read_offsets_dev,
+                                              uint32_t n_ext, const nvbio_seed_hits_params* params, int32_t* best_dev, uint8_t* best_rc_dev,
+                                              uint32_t* trys_dev, uint32_t* sizes_dev, void* stream);
+nvbio_status nvbio_score_reduce_effort_multi_ragged(int device, const uint32_t* active_dev, uint32_t n_active, const uint32_t* hits_first_dev,
+                                                    const uint32_t* hits_count_dev, const nvbio_hit_queues* hits, const uint32_t* read_offsets_dev,
+                                                    uint32_t n_ext, const nvbio_seed_hits_params* params, int32_t* best_dev, uint8_t* best_rc_dev,
+                                                    uint32_t* trys_dev, uint32_t* sizes_dev, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * nvBowtie's ALL-MAPPING mode (`--mode all`, bowtie2 -a: every placement of a read within max_dist edits), its data-parallel steps
  * (Aligner::all + score_all, nvBowtie/bowtie2/cuda/aligner_all.h:29-139,141-485).  The reference maps ONE seed index per pass
  * (map_exact with seed_range = (seed, seed + 1), aligner_all.h:76-94) through the multi-retry map_kernel (mapping_inl.h:563-634), which,

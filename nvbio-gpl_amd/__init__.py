@@ -104,6 +104,11 @@ class _SeedHitsParams(ctypes.Structure):
                                                 "rep_seeds", "max_effort", "min_ext", "max_ext")]
 
 
+class _RaggedSeedLayout(ctypes.Structure):
+    _fields_ = [("read_offsets_dev", ctypes.c_void_p), ("seed_intervals_dev", ctypes.c_void_p)] + \
+               [(n, ctypes.c_uint32) for n in ("seeds_per_read", "seeding_pass", "max_reseed", "seed_len", "min_read_len")]
+
+
 class _RankDict(ctypes.Structure):
     _fields_ = [("text_dev", ctypes.c_void_p), ("word_bits", ctypes.c_uint32), ("occ_dev", ctypes.c_void_p), ("index_bits", ctypes.c_uint32),
                 ("K", ctypes.c_uint32), ("length", ctypes.c_uint64)]
@@ -1699,6 +1704,54 @@ def score_reduce_effort(active, hits, read_len, n_ext, params, best, best_rc, tr
     _check(lib().nvbio_score_reduce_effort(FMIndex._dev_index(hits.device), _ptr(active), ctypes.byref(hq), ctypes.c_uint32(read_len),
                                            ctypes.c_uint32(n_ext), ctypes.byref(params.c), _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes),
                                            _stream_ptr(hits.device)))
+
+
+# ---- the same calls over reads of different lengths (include/nvbio_amd.h: nvbio_ragged_seed_layout and the *_ragged calls) -------------
+class RaggedSeedLayout:
+    """nvbio_ragged_seed_layout: the seeds of a seeding pass over a ragged batch -- read_offsets int32 [R + 1], seed_intervals int32 [R]
+    (S_r = seed_freq( M_r )), seeds_per_read = the largest seed count of the pass (the stride of the per-seed arrays)"""
+
+    def __init__(self, read_offsets, seed_intervals, seeds_per_read, seeding_pass, max_reseed, seed_len, min_read_len=12):
+        self.read_offsets, self.seed_intervals = read_offsets, seed_intervals          # kept alive
+        self.c = _RaggedSeedLayout(_ptr(read_offsets), _ptr(seed_intervals), seeds_per_read, seeding_pass, max_reseed, seed_len, min_read_len)
+
+
+def read_queue_begin_ragged(queue, n, layout, n_symbols, top_seed, max_effort_init, seed_offsets=None, active=None, trys=None):
+    """nvbio_read_queue_begin_ragged: seed_offsets int32 [n * seeds_per_read] (one explicit offset per seed slot), active int32 [n], trys int32 [R]"""
+    dev = layout.read_offsets.device
+    _check(lib().nvbio_read_queue_begin_ragged(FMIndex._dev_index(dev), _ptr(queue), ctypes.c_uint32(n), ctypes.byref(layout.c), ctypes.c_uint32(n_symbols),
+                                               ctypes.c_uint32(top_seed), ctypes.c_uint32(max_effort_init), _ptr(seed_offsets), _ptr(active), _ptr(trys),
+                                               _stream_ptr(dev)))
+
+
+def seed_hits_map_ragged(fw_ranges, rc_ranges, layout, n_reads, max_hits, rep_seeds, deques, sizes, reseed=None, read_queue=None):
+    """nvbio_seed_hits_map_ragged: the exact mapper's deques for the n_reads reads of read_queue (None: reads 0..n_reads-1) of a ragged batch"""
+    dev = deques.device
+    _check(lib().nvbio_seed_hits_map_ragged(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), _ptr(read_queue), ctypes.c_uint32(n_reads),
+                                            ctypes.byref(layout.c), ctypes.c_uint32(max_hits), ctypes.c_uint32(rep_seeds), _ptr(deques), _ptr(sizes),
+                                            _ptr(reseed), _stream_ptr(dev)))
+
+
+def best_approx_init_ragged(min_scores, best, best_rc):
+    """nvbio_best_approx_init_ragged: best int32 [R, 4] = (min_scores[r], -1, min_scores[r], -1), best_rc uint8 [R] = 0"""
+    dev = best.device
+    _check(lib().nvbio_best_approx_init_ragged(FMIndex._dev_index(dev), ctypes.c_uint32(best.shape[0]), _ptr(min_scores), _ptr(best), _ptr(best_rc),
+                                               _stream_ptr(dev)))
+
+
+def score_reduce_effort_ragged(active, hits, read_offsets, n_ext, params, best, best_rc, trys, sizes):
+    """nvbio_score_reduce_effort_ragged: score_reduce_effort with every read's own length (read_offsets int32 [R + 1]) in `distinct`"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_score_reduce_effort_ragged(FMIndex._dev_index(hits.device), _ptr(active), ctypes.byref(hq), _ptr(read_offsets), ctypes.c_uint32(n_ext),
+                                                  ctypes.byref(params.c), _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
+
+
+def score_reduce_effort_multi_ragged(active, n_active, hits_first, hits_count, hits, read_offsets, n_ext, params, best, best_rc, trys, sizes):
+    """nvbio_score_reduce_effort_multi_ragged: the several-hits-per-read reduction over a ragged batch"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_score_reduce_effort_multi_ragged(FMIndex._dev_index(hits.device), _ptr(active), ctypes.c_uint32(n_active), _ptr(hits_first),
+                                                        _ptr(hits_count), ctypes.byref(hq), _ptr(read_offsets), ctypes.c_uint32(n_ext), ctypes.byref(params.c),
+                                                        _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
 
 
 # ---- nvBowtie's all-mapping mode (include/nvbio_amd.h: nvbio_all_*; host/nvbio_amd/all_mapping.hpp) ---------------------------------

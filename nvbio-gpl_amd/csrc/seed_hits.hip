@@ -18,35 +18,68 @@
 namespace nvbio_amd {
 
 // ---- map: the deques of a batch of reads from the match ranges of their seeds ----
-// Read r (uniform length read_len) has seeds j = 0 .. spr-1 at stored offsets first_off + j * interval; fw / rc hold what
-// match_range returned for the forward scan of the stored read and for its reverse scan complemented (inclusive, empty iff x > y).
-__global__ void __launch_bounds__(256)
-seed_hits_map_kernel(const uint2* __restrict__ fw, const uint2* __restrict__ rc, const uint32_t* __restrict__ queue, const uint32_t n_reads, const uint32_t spr,
-                     const uint32_t first_off, const uint32_t interval, const uint32_t seed_len, const uint32_t read_len, const uint32_t max_hits,
-                     const uint32_t rep_seeds, const uint32_t cap, uint2* __restrict__ deques, uint32_t* __restrict__ sizes,
-                     uint8_t* __restrict__ reseed)
+// Read r has seeds j = 0 .. count-1 at stored offsets first + j * interval; fw / rc hold what match_range returned for the forward
+// scan of the stored read and for its reverse scan complemented (inclusive, empty iff x > y), `stride` slots per read.
+// The layout of a read's seeds is a policy: UniformSeeds (reads of one length: every read the same) or RaggedSeeds (every read its own
+// length, interval, first offset and seed count, as map_kernel computes them per lane, mapping_inl.h:504-529).
+struct SeedLayout { uint32_t count, first, interval, read_len; bool filtered; };
+
+struct UniformSeeds
 {
+    uint32_t spr, first_off, interval, read_len;
+    __device__ __forceinline__ uint32_t stride() const { return spr; }
+    __device__ __forceinline__ SeedLayout operator()(const uint32_t) const { return SeedLayout{ spr, first_off, interval, read_len, false }; }
+};
+// offsets: n_reads + 1 symbol offsets; intervals[r] = seed_freq( read_len_r ); first_r = seeding_pass * (interval_r / passes), passes = max_reseed + 1;
+// a read shorter than min_len is filtered (`read_len < params.min_read_len`, mapping_inl.h:510-514; here also a read shorter than a seed): no seeds
+// and no reseeding; another read whose seeds no longer fit has none in this pass.  Slots count .. stride-1 of a read are not read.
+struct RaggedSeeds
+{
+    const uint32_t* offsets; const uint32_t* intervals;
+    uint32_t spr, seeding_pass, passes, seed_len, min_len;
+    __device__ __forceinline__ uint32_t stride() const { return spr; }
+    __device__ __forceinline__ SeedLayout operator()(const uint32_t r) const
+    {
+        SeedLayout s;
+        s.read_len = offsets[r + 1] - offsets[r];
+        s.interval = intervals[r] ? intervals[r] : 1u;
+        s.first    = seeding_pass * (s.interval / passes);
+        s.filtered = s.read_len < min_len;
+        s.count    = (!s.filtered && s.read_len >= seed_len + s.first) ? (s.read_len - seed_len - s.first) / s.interval + 1u : 0u;
+        if (s.count > spr) s.count = spr;
+        return s;
+    }
+};
+
+template <typename Seeds>
+__global__ void __launch_bounds__(256)
+seed_hits_map_kernel(const uint2* __restrict__ fw, const uint2* __restrict__ rc, const uint32_t* __restrict__ queue, const uint32_t n_reads, const Seeds seeds,
+                     const uint32_t seed_len, const uint32_t max_hits, const uint32_t rep_seeds, const uint32_t cap, uint2* __restrict__ deques,
+                     uint32_t* __restrict__ sizes, uint8_t* __restrict__ reseed)
+{
+    const uint32_t spr = seeds.stride();
     for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_reads; t += gridDim.x * blockDim.x)
     {
         const uint32_t r = queue ? queue[t] : t;
+        const SeedLayout s = seeds( r );
         HitHeap heap; heap.a = deques + (uint64_t)r * cap; heap.n = 0;
         uint32_t range_sum = 0, range_count = 0;
-        for (uint32_t j = 0; j < spr; ++j)
+        for (uint32_t j = 0; j < s.count; ++j)
         {
-            const uint32_t off = first_off + j * interval;
+            const uint32_t off = s.first + j * s.interval;
             #pragma unroll
             for (uint32_t strand = 0; strand < 2u; ++strand)
             {
                 const uint2 g = strand ? rc[(uint64_t)t * spr + j] : fw[(uint64_t)t * spr + j];
                 if (g.x > g.y) continue;
-                const uint32_t pos = strand ? off : read_len - off - seed_len;       // SeedHit::build_flags (mapping_inl.h:241,275)
+                const uint32_t pos = strand ? off : s.read_len - off - seed_len;     // SeedHit::build_flags (mapping_inl.h:241,275)
                 if (heap.n == max_hits) heap.pop_bottom();
                 heap.push( make_uint2( g.x, ((g.y + 1u - g.x) & 0xFFFFFu) | ((pos & 0x3FFu) << 20) | (strand << 30) ) );
                 range_sum += g.y - g.x + 1u; ++range_count;
             }
         }
         sizes[r] = heap.n;
-        if (reseed) reseed[r] = (range_count == 0u || range_sum >= rep_seeds * range_count) ? 1 : 0;
+        if (reseed) reseed[r] = (!s.filtered && (range_count == 0u || range_sum >= rep_seeds * range_count)) ? 1 : 0;
     }
 }
 
@@ -130,9 +163,14 @@ __device__ __forceinline__ bool distinct_loci(const uint32_t pos1, const uint32_
     return !(pos1 >= pos2 - (pos2 < dist ? pos2 : dist) && pos1 <= pos2 + dist);          // io::distinct_alignments, uint32 arithmetic
 }
 
+// The read's length (the distinct distance is read_len / 2) is a policy: UniformLen, or RaggedLen over the batch's n_reads + 1 symbol offsets.
+struct UniformLen { uint32_t len;            __device__ __forceinline__ uint32_t operator()(const uint32_t) const { return len; } };
+struct RaggedLen  { const uint32_t* offsets; __device__ __forceinline__ uint32_t operator()(const uint32_t r) const { return offsets[r + 1] - offsets[r]; } };
+
+template <typename LenOf>
 __global__ void __launch_bounds__(256)
 score_reduce_effort_kernel(const uint32_t* __restrict__ active, const uint32_t n, const int32_t* __restrict__ hit_score, const uint32_t* __restrict__ hit_loc,
-                           const uint32_t* __restrict__ hit_seed, const uint32_t read_len, const uint32_t ext, const uint32_t max_effort,
+                           const uint32_t* __restrict__ hit_seed, const LenOf read_len, const uint32_t ext, const uint32_t max_effort,
                            const uint32_t min_ext, const uint32_t max_ext, int4* __restrict__ best, uint8_t* __restrict__ best_rc,
                            uint32_t* __restrict__ trys, uint32_t* __restrict__ sizes)
 {
@@ -152,7 +190,7 @@ score_reduce_effort_kernel(const uint32_t* __restrict__ active, const uint32_t n
             b.z = b.x; b.w = b.y; b.x = score; b.y = (int32_t)g;
             rcs = rc | (rc1 << 1);
         }
-        else if (score > b.z && distinct_loci( (uint32_t)b.y, rc1, g, rc, read_len / 2u ))
+        else if (score > b.z && distinct_loci( (uint32_t)b.y, rc1, g, rc, read_len( read ) / 2u ))
         {
             trys[read] = max_effort;
             b.z = score; b.w = (int32_t)g;
@@ -250,10 +288,11 @@ seed_hits_select_multi_kernel(const uint32_t* __restrict__ active_in, const uint
 }
 
 // ---- reduce over the hits of every active read, in selection order (score_reduce_kernel's loop, reduce_inl.h:94-134) ----
+template <typename LenOf>
 __global__ void __launch_bounds__(256)
 score_reduce_effort_multi_kernel(const uint32_t* __restrict__ active, const uint32_t n, const uint32_t* __restrict__ hits_first,
                                  const uint32_t* __restrict__ hits_count, const int32_t* __restrict__ hit_score, const uint32_t* __restrict__ hit_loc,
-                                 const uint32_t* __restrict__ hit_seed, const uint32_t read_len, const uint32_t ext, const uint32_t max_effort,
+                                 const uint32_t* __restrict__ hit_seed, const LenOf read_len, const uint32_t ext, const uint32_t max_effort,
                                  const uint32_t min_ext, const uint32_t max_ext, int4* __restrict__ best, uint8_t* __restrict__ best_rc,
                                  uint32_t* __restrict__ trys, uint32_t* __restrict__ sizes)
 {
@@ -264,6 +303,7 @@ score_reduce_effort_multi_kernel(const uint32_t* __restrict__ active, const uint
         int4 b = best[read];
         uint32_t rcs = best_rc[read];
         uint32_t t = trys[read];
+        const uint32_t dist = read_len( read ) / 2u;
         for (uint32_t idx = 0; idx < count; ++idx)
         {
             const uint32_t i = first + idx;
@@ -278,7 +318,7 @@ score_reduce_effort_multi_kernel(const uint32_t* __restrict__ active, const uint
                 b.z = b.x; b.w = b.y; b.x = score; b.y = (int32_t)g;
                 rcs = rc | (rc1 << 1);
             }
-            else if (score > b.z && distinct_loci( (uint32_t)b.y, rc1, g, rc, read_len / 2u ))
+            else if (score > b.z && distinct_loci( (uint32_t)b.y, rc1, g, rc, dist ))
             {
                 t = max_effort;
                 b.z = score; b.w = (int32_t)g;
@@ -317,6 +357,35 @@ read_queue_begin_kernel(const uint32_t* __restrict__ queue, const uint32_t n, co
         if (trys) trys[r] = max_effort_init;                              // select_init
     }
 }
+// the ragged forms: every read's own worst score; every read's own seeds, their offsets written out one by one (seed_offsets[t * stride + j];
+// a slot without a seed gets offset 0 and is never read back by the map kernel)
+__global__ void __launch_bounds__(256)
+best_approx_init_ragged_kernel(const uint32_t n, const int32_t* __restrict__ worst, int4* __restrict__ best, uint8_t* __restrict__ best_rc)
+{
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x)
+    {
+        const int32_t w = worst[r];
+        best[r] = make_int4( w, -1, w, -1 ); best_rc[r] = 0;
+    }
+}
+__global__ void __launch_bounds__(256)
+read_queue_begin_ragged_kernel(const uint32_t* __restrict__ queue, const uint32_t n, const RaggedSeeds seeds, const uint32_t top_seed,
+                               const uint32_t max_effort_init, uint32_t* __restrict__ seed_offsets, uint32_t* __restrict__ active, uint32_t* __restrict__ trys)
+{
+    const uint32_t spr = seeds.stride();
+    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x)
+    {
+        const uint32_t r = queue ? queue[t] : t;
+        if (seed_offsets)
+        {
+            const SeedLayout s = seeds( r );
+            const uint32_t base = seeds.offsets[r] + s.first;
+            for (uint32_t j = 0; j < spr; ++j) seed_offsets[(uint64_t)t * spr + j] = j < s.count ? base + j * s.interval : 0u;
+        }
+        if (active) active[t] = r | (top_seed << 31);
+        if (trys) trys[r] = max_effort_init;
+    }
+}
 struct ReadFlagSet { const uint8_t* flags; __host__ __device__ __forceinline__ bool operator()(const uint32_t r) const { return flags[r] != 0; } };
 
 } // namespace nvbio_amd
@@ -345,9 +414,37 @@ nvbio_status nvbio_seed_hits_map(int device, const nvbio_uint2* fw_ranges_dev, c
     NVB_REQUIRE( p->read_len < 1024u, "SeedHit keeps the seed position in 10 bits (seed_hit.h:217)" );
     uint32_t cap = 0; NVB_CHECK( nvbio_seed_hits_capacity( p->seeds_per_read, p->max_hits, &cap ) );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    return NVB_LAUNCH( seed_hits_map_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, (const uint2*)fw_ranges_dev, (const uint2*)rc_ranges_dev,
-                       read_queue_dev, n_reads, p->seeds_per_read, p->first_offset, p->seed_interval, p->seed_len, p->read_len, p->max_hits, p->rep_seeds, cap,
-                       (uint2*)deques_dev, sizes_dev, reseed_dev );
+    const UniformSeeds seeds = { p->seeds_per_read, p->first_offset, p->seed_interval, p->read_len };
+    return NVB_LAUNCH( seed_hits_map_kernel<UniformSeeds>, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, (const uint2*)fw_ranges_dev,
+                       (const uint2*)rc_ranges_dev, read_queue_dev, n_reads, seeds, p->seed_len, p->max_hits, p->rep_seeds, cap, (uint2*)deques_dev, sizes_dev,
+                       reseed_dev );
+}
+
+static nvbio_status ragged_seeds(const nvbio_ragged_seed_layout* l, RaggedSeeds* out)
+{
+    NVB_REQUIRE( l != nullptr, "layout is NULL" );
+    NVB_REQUIRE( l->read_offsets_dev && l->seed_intervals_dev, "read_offsets_dev and seed_intervals_dev are required" );
+    NVB_REQUIRE( l->seeds_per_read > 0 && l->seed_len > 0, "seeds_per_read and seed_len must be positive" );
+    NVB_REQUIRE( l->seeding_pass <= l->max_reseed, "seeding_pass must not exceed max_reseed" );
+    const RaggedSeeds s = { l->read_offsets_dev, l->seed_intervals_dev, l->seeds_per_read, l->seeding_pass, l->max_reseed + 1u, l->seed_len,
+                            l->min_read_len > l->seed_len ? l->min_read_len : l->seed_len };
+    *out = s;
+    return NVBIO_OK;
+}
+
+nvbio_status nvbio_seed_hits_map_ragged(int device, const nvbio_uint2* fw_ranges_dev, const nvbio_uint2* rc_ranges_dev, const uint32_t* read_queue_dev,
+                                        uint32_t n_reads, const nvbio_ragged_seed_layout* layout, uint32_t max_hits, uint32_t rep_seeds,
+                                        nvbio_uint2* deques_dev, uint32_t* sizes_dev, uint8_t* reseed_dev, void* stream)
+{
+    if (n_reads == 0) return NVBIO_OK;
+    RaggedSeeds seeds; NVB_CHECK( ragged_seeds( layout, &seeds ) );
+    NVB_REQUIRE( fw_ranges_dev && rc_ranges_dev && deques_dev && sizes_dev, "NULL device pointer" );
+    NVB_REQUIRE( max_hits > 0, "max_hits must be positive" );
+    uint32_t cap = 0; NVB_CHECK( nvbio_seed_hits_capacity( layout->seeds_per_read, max_hits, &cap ) );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return NVB_LAUNCH( seed_hits_map_kernel<RaggedSeeds>, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, (const uint2*)fw_ranges_dev,
+                       (const uint2*)rc_ranges_dev, read_queue_dev, n_reads, seeds, layout->seed_len, max_hits, rep_seeds, cap, (uint2*)deques_dev, sizes_dev,
+                       reseed_dev );
 }
 
 nvbio_status nvbio_seed_hits_select(int device, const uint32_t* active_in_dev, uint32_t n_active, const uint32_t* trys_dev, uint32_t capacity,
@@ -382,8 +479,24 @@ nvbio_status nvbio_score_reduce_effort(int device, const uint32_t* active_dev, c
     NVB_REQUIRE( active_dev && hits->hit_score_dev && hits->hit_loc_dev && hits->hit_seed_dev && best_dev && best_rc_dev && trys_dev && sizes_dev, "NULL device pointer" );
     NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    return NVB_LAUNCH( score_reduce_effort_kernel, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, active_dev, hits->n, hits->hit_score_dev,
-                       hits->hit_loc_dev, hits->hit_seed_dev, read_len, n_ext, p->max_effort, p->min_ext, p->max_ext, (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
+    return NVB_LAUNCH( score_reduce_effort_kernel<UniformLen>, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, active_dev, hits->n, hits->hit_score_dev,
+                       hits->hit_loc_dev, hits->hit_seed_dev, UniformLen{ read_len }, n_ext, p->max_effort, p->min_ext, p->max_ext, (int4*)best_dev, best_rc_dev,
+                       trys_dev, sizes_dev );
+}
+
+nvbio_status nvbio_score_reduce_effort_ragged(int device, const uint32_t* active_dev, const nvbio_hit_queues* hits, const uint32_t* read_offsets_dev,
+                                              uint32_t n_ext, const nvbio_seed_hits_params* p, int32_t* best_dev, uint8_t* best_rc_dev, uint32_t* trys_dev,
+                                              uint32_t* sizes_dev, void* stream)
+{
+    NVB_REQUIRE( hits != nullptr && p != nullptr, "NULL argument" );
+    if (hits->n == 0) return NVBIO_OK;
+    NVB_REQUIRE( active_dev && hits->hit_score_dev && hits->hit_loc_dev && hits->hit_seed_dev && best_dev && best_rc_dev && trys_dev && sizes_dev &&
+                 read_offsets_dev, "NULL device pointer" );
+    NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return NVB_LAUNCH( score_reduce_effort_kernel<RaggedLen>, dim3( grid_for( hits->n ) ), dim3(256), (hipStream_t)stream, active_dev, hits->n, hits->hit_score_dev,
+                       hits->hit_loc_dev, hits->hit_seed_dev, RaggedLen{ read_offsets_dev }, n_ext, p->max_effort, p->min_ext, p->max_ext, (int4*)best_dev,
+                       best_rc_dev, trys_dev, sizes_dev );
 }
 
 nvbio_status nvbio_seed_hits_select_multi(int device, const uint32_t* active_in_dev, uint32_t n_active, const uint32_t* trys_dev, uint32_t capacity,
@@ -414,9 +527,25 @@ nvbio_status nvbio_score_reduce_effort_multi(int device, const uint32_t* active_
                  trys_dev && sizes_dev, "NULL device pointer" );
     NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
-    return NVB_LAUNCH( score_reduce_effort_multi_kernel, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, active_dev, n_active, hits_first_dev,
-                       hits_count_dev, hits->hit_score_dev, hits->hit_loc_dev, hits->hit_seed_dev, read_len, n_ext, p->max_effort, p->min_ext, p->max_ext,
-                       (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
+    return NVB_LAUNCH( score_reduce_effort_multi_kernel<UniformLen>, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, active_dev, n_active,
+                       hits_first_dev, hits_count_dev, hits->hit_score_dev, hits->hit_loc_dev, hits->hit_seed_dev, UniformLen{ read_len }, n_ext, p->max_effort,
+                       p->min_ext, p->max_ext, (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
+}
+
+nvbio_status nvbio_score_reduce_effort_multi_ragged(int device, const uint32_t* active_dev, uint32_t n_active, const uint32_t* hits_first_dev,
+                                                    const uint32_t* hits_count_dev, const nvbio_hit_queues* hits, const uint32_t* read_offsets_dev,
+                                                    uint32_t n_ext, const nvbio_seed_hits_params* p, int32_t* best_dev, uint8_t* best_rc_dev,
+                                                    uint32_t* trys_dev, uint32_t* sizes_dev, void* stream)
+{
+    NVB_REQUIRE( hits != nullptr && p != nullptr, "NULL argument" );
+    if (n_active == 0) return NVBIO_OK;
+    NVB_REQUIRE( active_dev && hits_first_dev && hits_count_dev && hits->hit_score_dev && hits->hit_loc_dev && hits->hit_seed_dev && best_dev && best_rc_dev &&
+                 trys_dev && sizes_dev && read_offsets_dev, "NULL device pointer" );
+    NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return NVB_LAUNCH( score_reduce_effort_multi_kernel<RaggedLen>, dim3( grid_for( n_active ) ), dim3(256), (hipStream_t)stream, active_dev, n_active,
+                       hits_first_dev, hits_count_dev, hits->hit_score_dev, hits->hit_loc_dev, hits->hit_seed_dev, RaggedLen{ read_offsets_dev }, n_ext,
+                       p->max_effort, p->min_ext, p->max_ext, (int4*)best_dev, best_rc_dev, trys_dev, sizes_dev );
 }
 
 nvbio_status nvbio_best_approx_init(int device, uint32_t n_reads, int32_t worst_score, int32_t* best_dev, uint8_t* best_rc_dev, void* stream)
@@ -435,6 +564,28 @@ nvbio_status nvbio_read_queue_begin(int device, const uint32_t* queue_dev, uint3
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     return NVB_LAUNCH( read_queue_begin_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, queue_dev, n, read_len, first_offset, top_seed & 1u,
                        max_effort_init, seed_offsets_dev, active_dev, trys_dev );
+}
+
+nvbio_status nvbio_best_approx_init_ragged(int device, uint32_t n_reads, const int32_t* min_scores_dev, int32_t* best_dev, uint8_t* best_rc_dev, void* stream)
+{
+    if (n_reads == 0) return NVBIO_OK;
+    NVB_REQUIRE( min_scores_dev && best_dev && best_rc_dev, "NULL device pointer" );
+    NVB_REQUIRE( ((uintptr_t)best_dev & 15u) == 0, "best_dev must be 16-byte aligned" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return NVB_LAUNCH( best_approx_init_ragged_kernel, dim3( grid_for( n_reads ) ), dim3(256), (hipStream_t)stream, n_reads, min_scores_dev, (int4*)best_dev,
+                       best_rc_dev );
+}
+
+nvbio_status nvbio_read_queue_begin_ragged(int device, const uint32_t* queue_dev, uint32_t n, const nvbio_ragged_seed_layout* layout, uint32_t n_symbols,
+                                           uint32_t top_seed, uint32_t max_effort_init, uint32_t* seed_offsets_dev, uint32_t* active_dev, uint32_t* trys_dev,
+                                           void* stream)
+{
+    if (n == 0) return NVBIO_OK;
+    RaggedSeeds seeds; NVB_CHECK( ragged_seeds( layout, &seeds ) );
+    NVB_REQUIRE( seed_offsets_dev == nullptr || n_symbols >= layout->seed_len, "the reads hold fewer symbols than one seed" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return NVB_LAUNCH( read_queue_begin_ragged_kernel, dim3( grid_for( n ) ), dim3(256), (hipStream_t)stream, queue_dev, n, seeds, top_seed & 1u, max_effort_init,
+                       seed_offsets_dev, active_dev, trys_dev );
 }
 
 nvbio_status nvbio_read_queue_filter(int device, const uint32_t* queue_dev, uint32_t n, const uint8_t* read_flags_dev, uint32_t* queue_out_dev,

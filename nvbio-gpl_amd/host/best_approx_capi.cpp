@@ -40,6 +40,32 @@ int nvbio_host_best_approx(int device, nvbio_fm_index_t fmi, const uint32_t* gen
     }
 }
 
+// the ragged form (best_approx_ragged): read_offsets [n_reads + 1] and min_scores [n_reads] are HOST arrays; a batch holding a read of 1024 symbols or
+// more is refused (returns 1) before anything is launched or written
+int nvbio_host_best_approx_ragged(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads4_dev,
+                                  const uint8_t* quals_dev, uint32_t n_reads, const uint32_t* read_offsets, int aln_type, const nvbio_gotoh_scheme* scheme,
+                                  const int32_t* min_scores, uint32_t min_read_len, const nvbio_host_best_approx_params* p, int32_t* best_dev, uint8_t* best_rc_dev,
+                                  void* stream, nvbio_host_best_approx_stats* stats)
+{
+    try
+    {
+        nvbio_amd_host::BestApproxParams q;
+        q.seed_len = p->seed_len; q.seed_freq = p->seed_freq; q.max_hits = p->max_hits; q.rep_seeds = p->rep_seeds; q.max_effort = p->max_effort;
+        q.max_effort_init = p->max_effort_init; q.min_ext = p->min_ext; q.max_ext = p->max_ext; q.max_reseed = p->max_reseed; q.band = p->band;
+        q.top_seed = p->top_seed; q.batch_size = p->batch_size; q.multi_hit = p->multi_hit;
+        const nvbio_amd_host::BestApproxStats s = nvbio_amd_host::best_approx_ragged( device, fmi, genome2_dev, genome_len, stored_reads4_dev, quals_dev, n_reads,
+                                                                                       read_offsets, (nvbio_alignment_type)aln_type, *scheme, min_scores, q, best_dev,
+                                                                                       best_rc_dev, (hipStream_t)stream, min_read_len );
+        if (stats) { stats->n_extensions = s.n_extensions; stats->passes = s.passes; stats->multi_passes = s.multi_passes; stats->seeding_passes = s.seeding_passes; stats->pad = 0; }
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        strncpy( g_err, e.what(), sizeof(g_err) - 1 ); g_err[sizeof(g_err) - 1] = 0;
+        return 1;
+    }
+}
+
 struct nvbio_host_paired_params { uint32_t policy, min_frag_len, max_frag_len, overlap, unpaired; };
 struct nvbio_host_paired_stats { uint64_t n_extensions, n_opposite; uint32_t passes, multi_passes; };
 

@@ -655,10 +655,105 @@ class NvBowtieParams:
     """the parameters of nvBowtie's best-approx pipeline that decide WHICH loci get extended (bowtie2_cuda_driver.cu:86-141 defaults)"""
 
     def __init__(self, seed_len=22, seed_freq=None, max_hits=100, rep_seeds=1000, max_effort=15, max_effort_init=15, min_ext=30,
-                 max_ext=400, max_reseed=2, band=31, top_seed=0):
+                 max_ext=400, max_reseed=2, band=31, top_seed=0, min_read_len=12):
         self.seed_len, self.seed_freq, self.max_hits, self.rep_seeds = seed_len, seed_freq, max_hits, rep_seeds
         self.max_effort, self.max_effort_init, self.min_ext, self.max_ext = max_effort, max(max_effort_init, max_effort), min_ext, max(max_ext, max_effort)
         self.max_reseed, self.band, self.top_seed = max_reseed, band, top_seed
+        self.min_read_len = min_read_len            # ragged batches only: reads shorter than max( min_read_len, seed_len ) are not seeded (mapping_inl.h:510-514)
+
+
+def _ragged_tables(stored_reads, params, nvb):
+    """host-side view of a ragged batch for the best-approx loop: offsets (uint32 [R + 1]), every read's seed interval S_r = seed_freq( M_r )
+    (float32, as the reference evaluates it) and worst score min_score( M_r ), the longest read, and per seeding pass the largest seed count of
+    a read (the stride of that pass's per-seed arrays).  Raises ValueError for a read of 1024 symbols or more: SeedHit keeps positions in 10 bits."""
+    off = stored_reads.offsets.detach().cpu().numpy().astype(np.int64)
+    lens = np.diff(off)
+    if len(lens) != stored_reads.n or (lens < 0).any():
+        raise ValueError("offsets must hold n_reads + 1 non-decreasing symbol offsets")
+    if len(lens) and int(lens.max()) >= 1024:
+        raise ValueError("a read of 1024 symbols or more: SeedHit keeps the seed position in 10 bits (seed_hit.h:217)")
+    Mmax = int(lens.max()) if len(lens) else 0
+    S = np.full(len(lens), nvb.seed_freq, dtype=np.int64) if nvb.seed_freq else params.interval_table(Mmax)[lens].astype(np.int64)
+    S = np.maximum(S, 1)
+    worst = params.min_score_table(Mmax)[lens].astype(np.int32)
+    L = nvb.seed_len
+    seeded = lens >= max(nvb.min_read_len, L)
+    spr_of = []
+    for p in range(nvb.max_reseed + 1):
+        first = p * (S // (nvb.max_reseed + 1))
+        cnt = np.where(seeded & (lens >= L + first), (lens - L - first) // S + 1, 0)
+        spr_of.append(int(cnt.max()) if len(cnt) else 0)
+    return off.astype(np.uint32), S.astype(np.int32), worst, Mmax, spr_of
+
+
+def _nvbowtie_best_approx_ragged(fmi, genome2, genome_len, stored_reads, params, nvb, stats):
+    """nvbowtie_best_approx over a ragged ReadBatch: every read its own seed interval, first offset, seed count, DP window, distinct distance and
+    worst score (map_kernel works per lane, mapping_inl.h:504-529); reads shorter than max( min_read_len, seed_len ) are filtered"""
+    import torch
+    from . import (FM_COMPLEMENT, FM_SCAN_FORWARD, AlignmentBatch, BatchedBandedAlignmentScore, GotohAligner, HitQueues, PackedStringSet, RaggedSeedLayout,
+                   SeedHitsParams, best_approx_init_ragged, read_queue_begin_ragged, score_reduce_effort_ragged, score_stream_flatten, score_stream_output,
+                   seed_hits_loc, seed_hits_map_ragged, seed_hits_select)
+    dev = fmi.device
+    R, L = stored_reads.n, nvb.seed_len
+    off_h, S_h, worst_h, Mmax, spr_of = _ragged_tables(stored_reads, params, nvb)
+    read_index = stored_reads.offsets.to(torch.int32).contiguous()
+    intervals = torch.from_numpy(S_h).to(dev)
+    best = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    best_rc = torch.zeros(R, dtype=torch.uint8, device=dev)
+    best_approx_init_ragged(torch.from_numpy(worst_h).to(dev), best, best_rc)
+    trys = torch.zeros(R, dtype=torch.int32, device=dev)
+    aligner = GotohAligner(params.aln_type, params.scheme)
+    queue = torch.arange(R, device=dev, dtype=torch.int32)
+    n_extensions = passes = 0
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    for seeding_pass in range(nvb.max_reseed + 1):
+        nq = queue.numel()
+        spr = spr_of[seeding_pass]
+        if nq == 0 or spr == 0:                                       # (first_r grows with the pass: no seed slot now, none later)
+            break
+        lay = RaggedSeedLayout(read_index, intervals, spr, seeding_pass, nvb.max_reseed, L, nvb.min_read_len)
+        sp = SeedHitsParams(spr, 0, L, Mmax, max_hits=nvb.max_hits, rep_seeds=nvb.rep_seeds, max_effort=nvb.max_effort, min_ext=nvb.min_ext, max_ext=nvb.max_ext)
+        cap = sp.capacity()
+        offs = torch.empty(nq * spr, dtype=torch.int32, device=dev)
+        active = torch.empty(nq, dtype=torch.int32, device=dev)
+        read_queue_begin_ragged(queue, nq, lay, int(off_h[-1]), nvb.top_seed, nvb.max_effort_init, offs, active, trys)
+        qs = PackedStringSet(stored_reads.reads4, 4, nq * spr, offsets=offs, fixed_len=L, stride=0, device=dev)
+        fw = fmi.match(qs, FM_SCAN_FORWARD)
+        rc = fmi.match(qs, FM_COMPLEMENT)
+        deques = torch.zeros((R, cap, 2), dtype=torch.int32, device=dev)
+        sizes = torch.zeros(R, dtype=torch.int32, device=dev)
+        reseed = torch.zeros(R, dtype=torch.uint8, device=dev)
+        seed_hits_map_ragged(fw, rc, lay, nq, nvb.max_hits, nvb.rep_seeds, deques, sizes, reseed, read_queue=queue)
+        n_ext = 0
+        while active.numel() and n_ext < nvb.max_ext:
+            na = active.numel()
+            hits = HitQueues(torch.empty(na, dtype=torch.int32, device=dev), torch.empty(na, dtype=torch.int32, device=dev),
+                             torch.empty(na, dtype=torch.int32, device=dev), device=dev)
+            active_out = torch.empty(na, dtype=torch.int32, device=dev)
+            seed_hits_select(active, trys, sp, deques, sizes, hits, active_out, count)
+            nh = int(count.item())
+            if nh == 0:
+                break
+            active = active_out[:nh].contiguous()
+            hits.n = nh
+            pos = fmi.locate(hits.loc[:nh].contiguous())
+            seed_hits_loc(pos, hits)
+            rid, flags, wb, we = score_stream_flatten(hits, read_index, nvb.band, genome_len, reads_reversed=True)
+            batch = AlignmentBatch(stored_reads.reads4, 4, read_index, genome2, 2, wb, we, quals=stored_reads.quals, read_id=rid, flags=flags,
+                                   device=dev, max_read_len=Mmax, algo_flags=ALN_RAGGED_READS)
+            scores, sinks = BatchedBandedAlignmentScore(nvb.band, aligner).enact(batch)
+            score_stream_output(hits, scores, sinks, wb)
+            score_reduce_effort_ragged(active, hits, read_index, n_ext, sp, best, best_rc, trys, sizes)
+            n_ext += 1
+            n_extensions += nh
+            passes += 1
+        queue = queue[reseed[queue.to(torch.int64)] != 0].contiguous()
+    if stats is not None:
+        stats.update(n_extensions=n_extensions, passes=passes)
+    b = best.to(torch.int64)
+    loc = lambda c: torch.where(b[:, c] == -1, b[:, c], b[:, c] & 0xFFFFFFFF)
+    return dict(best_score=best[:, 0].clone(), best_loc=loc(1), best_rc=(best_rc & 1), second_score=best[:, 2].clone(), second_loc=loc(3),
+                second_rc=((best_rc >> 1) & 1), n_extensions=n_extensions, passes=passes)
 
 
 def nvbowtie_best_approx(fmi, genome2, genome_len, stored_reads, params, nvb=None, stats=None):
@@ -669,13 +764,17 @@ def nvbowtie_best_approx(fmi, genome2, genome_len, stored_reads, params, nvb=Non
     in arrival order, counting failed extensions, until a read's hits or its effort run out.  One hit per read and pass (the
     reference switches to several once fewer than half a batch of reads are active: an optimisation that changes no rule but
     the order effort runs out in).  Every data-parallel step is a kernel behind the C ABI; this function is the host loop.
-    stored_reads: ReadBatch of reads stored REVERSED, as nvBowtie loads them (io::REVERSE, nvBowtie.cpp:322).
+    stored_reads: ReadBatch of reads stored REVERSED, as nvBowtie loads them (io::REVERSE, nvBowtie.cpp:322).  A ragged batch (offsets) takes
+    the ragged route: per-read seed interval, first offset, window, distinct distance and worst score; reads shorter than
+    max( nvb.min_read_len, seed_len ) are not seeded and end unaligned; no read may reach 1024 symbols (ValueError).
     Returns dict(best_score, best_loc, best_rc, second_score, second_loc, second_rc) (loc = hit.loc, the diagonal's locus; -1 = none),
     n_extensions, passes."""
     import torch
     from . import (FM_COMPLEMENT, FM_SCAN_FORWARD, AlignmentBatch, BatchedBandedAlignmentScore, GotohAligner, HitQueues, PackedStringSet,
                    SeedHitsParams, score_reduce_effort, score_stream_flatten, score_stream_output, seed_hits_loc, seed_hits_map, seed_hits_select)
     nvb = nvb or NvBowtieParams()
+    if stored_reads.offsets is not None:                              # reads of different lengths: every read its own seeds, window and thresholds
+        return _nvbowtie_best_approx_ragged(fmi, genome2, genome_len, stored_reads, params, nvb, stats)
     dev = fmi.device
     R, M = stored_reads.n, stored_reads.read_len
     L = min(nvb.seed_len, M)
@@ -766,16 +865,8 @@ def _host_lib():
     return _HOST_LIB
 
 
-def nvbowtie_best_approx_host(fmi, genome2, genome_len, stored_reads, params, nvb=None, batch_size=0, multi_hit=True):
-    """nvbowtie_best_approx as the C++ host loop (nvbio_host_best_approx): every data-parallel step behind the C ABI, the loop in C++, two
-    counters read per extension pass through pinned memory, queues allocated once -- and the reference's several-hits-per-read phase
-    (aligner_best_approx.h:487-510; batch_size = its BATCH_SIZE, 0 = the number of reads).  Same return value as nvbowtie_best_approx."""
+def _host_structs():
     import ctypes
-    import torch
-    from . import FMIndex, _ptr, _stream_ptr
-    nvb = nvb or NvBowtieParams()
-    dev = fmi.device
-    R, M = stored_reads.n, stored_reads.read_len
 
     class _P(ctypes.Structure):
         _fields_ = [(k, ctypes.c_uint32) for k in ("seed_len", "seed_freq", "max_hits", "rep_seeds", "max_effort", "max_effort_init", "min_ext", "max_ext",
@@ -784,12 +875,63 @@ def nvbowtie_best_approx_host(fmi, genome2, genome_len, stored_reads, params, nv
     class _S(ctypes.Structure):
         _fields_ = [("n_extensions", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("multi_passes", ctypes.c_uint32), ("seeding_passes", ctypes.c_uint32),
                     ("pad", ctypes.c_uint32)]
+    return _P, _S
 
+
+_HostParams, _HostStats = _host_structs()
+
+
+def host_best_approx_ragged_into(fmi, genome2, genome_len, stored_reads, params, nvb, batch_size, multi_hit, best, best_rc):
+    """nvbio_host_best_approx_ragged (host/nvbio_amd/best_approx.hpp: best_approx_ragged) into the caller's best int32 [R, 4] / best_rc uint8 [R]:
+    the offsets go to the C++ loop on the HOST, with every read's worst score; the loop evaluates seed_freq( M_r ) itself (S(1, 1.15) unless
+    nvb.seed_freq or params.seed_interval fixes one).  Raises RuntimeError, having launched and written nothing, for a read of 1024 symbols or more.
+    Returns the loop's counters."""
+    import ctypes
+    from . import FMIndex, _ptr, _stream_ptr
+    dev = fmi.device
+    R = stored_reads.n
+    off = np.ascontiguousarray(stored_reads.offsets.detach().cpu().numpy().astype(np.uint32))
+    lens = np.diff(off.astype(np.int64))
+    if len(off) != R + 1:
+        raise ValueError("offsets must hold n_reads + 1 symbol offsets")
+    Mmax = int(lens.max()) if R else 0
+    worst = np.ascontiguousarray(params.min_score_table(Mmax)[np.clip(lens, 0, Mmax)].astype(np.int32))
+    p = _HostParams(nvb.seed_len, nvb.seed_freq or params.seed_interval or 0, nvb.max_hits, nvb.rep_seeds, nvb.max_effort, nvb.max_effort_init, nvb.min_ext,
+                    nvb.max_ext, nvb.max_reseed, nvb.band, nvb.top_seed, int(batch_size), 1 if multi_hit else 0)
+    st = _HostStats()
+    rc = _host_lib().nvbio_host_best_approx_ragged(
+        ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_reads.reads4), _ptr(stored_reads.quals),
+        ctypes.c_uint32(R), off.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c),
+        worst.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(nvb.min_read_len), ctypes.byref(p), _ptr(best), _ptr(best_rc), _stream_ptr(dev), ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
+    return st
+
+
+def nvbowtie_best_approx_host(fmi, genome2, genome_len, stored_reads, params, nvb=None, batch_size=0, multi_hit=True):
+    """nvbowtie_best_approx as the C++ host loop (nvbio_host_best_approx): every data-parallel step behind the C ABI, the loop in C++, two
+    counters read per extension pass through pinned memory, queues allocated once -- and the reference's several-hits-per-read phase
+    (aligner_best_approx.h:487-510; batch_size = its BATCH_SIZE, 0 = the number of reads).  Same return value as nvbowtie_best_approx.
+    A ragged ReadBatch (offsets) takes nvbio_host_best_approx_ragged: see host_best_approx_ragged_into."""
+    import ctypes
+    import torch
+    from . import FMIndex, _ptr, _stream_ptr
+    nvb = nvb or NvBowtieParams()
+    dev = fmi.device
+    R, M = stored_reads.n, stored_reads.read_len
+    best = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    best_rc = torch.zeros(R, dtype=torch.uint8, device=dev)
+    if stored_reads.offsets is not None:                              # reads of different lengths: nvbio_host_best_approx_ragged
+        st = host_best_approx_ragged_into(fmi, genome2, genome_len, stored_reads, params, nvb, batch_size, multi_hit, best, best_rc)
+        b = best.to(torch.int64)
+        loc = lambda c: torch.where(b[:, c] == -1, b[:, c], b[:, c] & 0xFFFFFFFF)
+        return dict(best_score=best[:, 0].clone(), best_loc=loc(1), best_rc=(best_rc & 1), second_score=best[:, 2].clone(), second_loc=loc(3),
+                    second_rc=((best_rc >> 1) & 1), n_extensions=int(st.n_extensions), passes=int(st.passes), multi_passes=int(st.multi_passes),
+                    seeding_passes=int(st.seeding_passes))
+    _P, _S = _HostParams, _HostStats
     p = _P(nvb.seed_len, nvb.seed_freq or params.interval_for(M), nvb.max_hits, nvb.rep_seeds, nvb.max_effort, nvb.max_effort_init, nvb.min_ext, nvb.max_ext,
            nvb.max_reseed, nvb.band, nvb.top_seed, int(batch_size), 1 if multi_hit else 0)
     st = _S()
-    best = torch.empty((R, 4), dtype=torch.int32, device=dev)
-    best_rc = torch.zeros(R, dtype=torch.uint8, device=dev)
     rc = _host_lib().nvbio_host_best_approx(
         ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_reads.reads4), _ptr(stored_reads.quals),
         ctypes.c_uint32(R), ctypes.c_uint32(M), ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c), ctypes.c_int32(params.min_score_for(M)),
