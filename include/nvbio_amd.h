@@ -1136,6 +1136,9 @@ enum
                                                magnitude <= 2040; one operation less per cell) would do (A/B)                                           */
     NVBIO_ALN_SPLIT_CHANCES         = 131072, /* band-31 end-to-end scoring: the second chance and the gap chance as two launches, one after the other,
                                                 instead of one launch with the two roles interleaved (chances_e2e31_kernel) (A/B)                      */
+    NVBIO_ALN_NO_PAIRED_GAP_CHANCE  = 262144, /* band-31 end-to-end scoring: the two windows of an indel read (adjacent jobs of one read and strand whose
+                                                windows lie 1..5 columns apart) as two gap-chance jobs instead of one that walks their shared
+                                                diagonals once (gap_chance_e2e31_pair) (A/B)                                                           */
     NVBIO_ALN_NO_NARROW_TRACEBACK   = 64   /* band-31 end-to-end traceback: every DP over the whole band (no band-15 route for the jobs
                                               whose optimal paths provably stay within 7 diagonals of the sink)                  */
 };
@@ -1246,6 +1249,16 @@ nvbio_status nvbio_opposite_mate_windows(int device, const uint32_t* g_pos_dev, 
                                          uint32_t min_frag_len, uint32_t max_frag_len, uint32_t overlap, uint32_t genome_len,
                                          uint32_t* win_begin_dev, uint32_t* win_end_dev, uint8_t* flags_dev, uint8_t* valid_dev,
                                          void* stream);
+
+/* Which jobs of a batch the band-31 end-to-end scorer may hand to its gap chance as ONE job (see NVBIO_ALN_NO_PAIRED_GAP_CHANCE):
+ * partner_dev[i] = the job paired with job i, or 0xFFFFFFFF.  A function of the batch's geometry alone: jobs j and j + 1 are linked iff they
+ * have the same read, the same flags, unclipped windows (win_end - win_begin = read length + 31, read length 1..161) and
+ * 0 < |win_begin[j+1] - win_begin[j]| <= NVBIO_GAP_PAIR_MAX_SHIFT (in either order), and j % 64 != 63 (no pair across a wave's 64 jobs); along a run of linked
+ * jobs the pairs are taken from its lowest job on ((j, j+1), (j+2, j+3), ...; a job left over stays alone).  The scorer runs a pair as one
+ * job only when the first pass sends BOTH to the gap chance and the batch is not declared ragged (NVBIO_ALN_RAGGED_READS); the results never
+ * depend on it. */
+#define NVBIO_GAP_PAIR_MAX_SHIFT 5
+nvbio_status nvbio_banded_gap_pairs(int device, const nvbio_alignment_batch* batch, uint32_t* partner_dev, void* stream);
 
 /* scores_dev[i], sinks_dev[i] = BestSink<int32> (score, (text_end, pattern_end)) after
  * aln::banded_alignment_score<band>( GotohAligner<type>, pattern, quals, text, min_score, sink )

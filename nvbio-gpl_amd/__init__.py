@@ -40,7 +40,7 @@ TRACEBACK_SINKS_GIVEN = 1
 ALN_NO_UNGAPPED_SCORE, ALN_NO_THIRD_CHANCE, ALN_NO_PACKED_DP, ALN_FORCE_PACKED_DP, ALN_NO_UNGAPPED_TRACEBACK, ALN_PK_THREE_WAVES = 1, 2, 4, 8, 16, 32
 ALN_NO_NARROW_TRACEBACK, ALN_NO_SECOND_CHANCE, ALN_PK_STRIPE8, ALN_NO_NARROW_SCORE, ALN_NO_BAND_ROUTE = 64, 128, 256, 512, 1024
 ALN_NO_QUALITY_SHORTCUT, ALN_RAGGED_READS, ALN_NO_LENGTH_SORT, ALN_NO_F16_DP, ALN_NO_COOPERATIVE_DP, ALN_NO_GAP_CHANCE = 2048, 4096, 8192, 16384, 32768, 65536
-ALN_SPLIT_CHANCES = 131072
+ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE = 131072, 262144
 DEFAULT_ALGO_FLAGS = 0          # what an AlignmentBatch is created with unless told otherwise (tests set it for a whole run)
 BACKTRACK_REFERENCE_QUIRKS = 1
 
@@ -1222,6 +1222,20 @@ class BatchedBandedAlignmentScore:
 def batch_banded_alignment_score(band_len, aligner, batch):
     """aln::batch_banded_alignment_score<BAND_LEN> (nvbio/alignment/batched.h:185, batched_inl.h:1046-1086)"""
     return BatchedBandedAlignmentScore(band_len, aligner).enact(batch)
+
+
+GAP_PAIR_MAX_SHIFT = 5
+NO_PARTNER = 0xFFFFFFFF
+
+
+def banded_gap_pairs(batch):
+    """nvbio_banded_gap_pairs: for every job of the batch the job the band-31 end-to-end scorer may run it with as ONE gap-chance job
+    (uint32 on the device, NO_PARTNER where there is none) -- a function of the batch's geometry alone, see ALN_NO_PAIRED_GAP_CHANCE"""
+    torch = _torch()
+    partner = torch.empty(batch.n, dtype=torch.int32, device=batch.device)
+    bs = batch.c_struct()
+    _check(lib().nvbio_banded_gap_pairs(FMIndex._dev_index(batch.device), ctypes.byref(bs), _ptr(partner), _stream_ptr(batch.device)))
+    return partner
 
 
 class BatchedBandedAlignmentTraceback:

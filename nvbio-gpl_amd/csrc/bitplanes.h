@@ -14,6 +14,7 @@ constexpr uint32_t PLANE_MAX_READ = 161u;                        // 3 x 64 bits 
 
 template <int RBITS> struct ReadWords { static constexpr int N = (161 + 15) * RBITS / 32 + 2; uint32_t w[N]; };
 struct TextWords13 { uint32_t w[13]; };
+struct TextWords14 { uint32_t w[14]; };                          // one word more: 209 window symbols at any storage offset
 
 template <int RBITS>
 __device__ __forceinline__ void load_read_words(const void* reads, const uint32_t first, const uint32_t M, ReadWords<RBITS>& out)
@@ -32,6 +33,15 @@ __device__ __forceinline__ void load_text_words13(const void* text, const uint32
     const uint32_t tw0 = (tb & ~15u) >> 4, tw_last = (tb + T - 1u) >> 4;
     #pragma unroll
     for (int j = 0; j < 13; ++j) { const uint32_t widx = tw0 + (uint32_t)j; out.w[j] = twords[widx < tw_last ? widx : tw_last]; }
+}
+
+// T <= 224 - 15 window symbols
+__device__ __forceinline__ void load_text_words14(const void* text, const uint32_t tb, const uint32_t T, TextWords14& out)
+{
+    const uint32_t* __restrict__ twords = (const uint32_t*)text;
+    const uint32_t tw0 = (tb & ~15u) >> 4, tw_last = (tb + T - 1u) >> 4;
+    #pragma unroll
+    for (int j = 0; j < 14; ++j) { const uint32_t widx = tw0 + (uint32_t)j; out.w[j] = twords[widx < tw_last ? widx : tw_last]; }
 }
 
 __device__ __forceinline__ void shr192(uint64_t (&v)[3], const uint32_t sh)
@@ -116,6 +126,33 @@ __device__ __forceinline__ void text_planes208(const TextWords13& tw, const uint
     for (int k = 0; k < 4; ++k) { tlo[k] = 0; thi[k] = 0; }
     #pragma unroll
     for (int j = 0; j < 13; ++j)
+    {
+        const uint32_t w = __brev( tw.w[j] );
+        const uint32_t lo = squeeze2( w >> 1 ), hi = squeeze2( w );
+        const int bitpos = j * 16;
+        tlo[bitpos >> 6] |= (uint64_t)lo << (bitpos & 63);
+        thi[bitpos >> 6] |= (uint64_t)hi << (bitpos & 63);
+    }
+    const uint32_t toff = tb & 15u;
+    if (toff)
+    {
+        #pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            tlo[k] = (tlo[k] >> toff) | (tlo[k + 1] << (64u - toff));
+            thi[k] = (thi[k] >> toff) | (thi[k + 1] << (64u - toff));
+        }
+        tlo[3] >>= toff; thi[3] >>= toff;
+    }
+}
+
+// 224 plane bits (14 packed words), shifted so that bit 0 = window symbol 0
+__device__ __forceinline__ void text_planes224(const TextWords14& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
+{
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) { tlo[k] = 0; thi[k] = 0; }
+    #pragma unroll
+    for (int j = 0; j < 14; ++j)
     {
         const uint32_t w = __brev( tw.w[j] );
         const uint32_t lo = squeeze2( w >> 1 ), hi = squeeze2( w );

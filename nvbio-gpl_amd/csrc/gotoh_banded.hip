@@ -711,21 +711,25 @@ static GapLadder gap_ladder(const int32_t P, const int32_t G, const int32_t go, 
 // range's start + the jobs of the waves before it + its rank in the ballot.  A workgroup walks JOB_LIST_CHUNKS chunks of 256 jobs and
 // reserves once for all of them.  The lists are dense but NOT in ascending job order (workgroups reserve in the order they finish).
 // Counters: `counts` of the "banded_job_list" layout, one 128-byte line each, zeroed on the stream before the first pass.
-constexpr uint32_t JOB_COUNT_STRIDE = 32u;                        // in uint32: counts[0] the DP's list, [32] the second chance's, [64] the third / gap chance's
+constexpr uint32_t JOB_COUNT_STRIDE = 32u;                        // in uint32: counts[0] the DP's list, [32] the second chance's, [64] the third / gap chance's, [96] the gap chance's pairs
+constexpr uint32_t JOB_LIST_COUNT   = 4u;
 #ifndef NVB_JOB_LIST_CHUNKS
 #define NVB_JOB_LIST_CHUNKS 1
 #endif
 constexpr int JOB_LIST_CHUNKS = NVB_JOB_LIST_CHUNKS;              // at most 4 (JobAppend::mine holds a byte per chunk)
 static inline uint32_t job_list_grid(const uint32_t n) { return (n + 256u * JOB_LIST_CHUNKS - 1u) / (256u * JOB_LIST_CHUNKS); }
 
-struct JobLists { uint32_t *dp, *second, *third; uint32_t* counts; };      // list 0, 1, 2 and their counters
+struct JobLists { uint32_t *dp, *second, *third, *pairs; uint32_t* counts; };      // list 0, 1, 2, 3 and their counters
 
 template <int NL>
 struct JobAppend
 {
-    static_assert( NL >= 1 && NL <= 3 && JOB_LIST_CHUNKS >= 1 && JOB_LIST_CHUNKS <= 4, "JobAppend: up to 3 lists, up to 4 chunks" );
+    static_assert( NL >= 1 && NL <= 4 && JOB_LIST_CHUNKS >= 1 && JOB_LIST_CHUNKS <= 4, "JobAppend: up to 4 lists, up to 4 chunks" );
     struct Lds { uint32_t cnt[NL][4 * JOB_LIST_CHUNKS]; uint32_t base[NL]; };
-    uint32_t mine = 0;                                            // chunk k in bits 8k .. 8k+7: (list + 1) << 6 | rank among the wave's jobs for that list
+    // chunk k in bits SLOT k .. SLOT k + SLOT - 1: (list + 1) << 6 | rank among the wave's jobs for that list (a byte holds lists 0 .. 2)
+    static constexpr int SLOT = NL <= 3 ? 8 : 16;
+    typedef typename std::conditional<NL <= 3, uint32_t, uint64_t>::type Mine;
+    Mine mine = 0;
     // chunk k's job of this lane goes on list `which` (-1: on none).  Called by EVERY lane of the workgroup (256 threads), converged.
     __device__ __forceinline__ void note(Lds& lds, const int k, const int which)
     {
@@ -735,7 +739,7 @@ struct JobAppend
         {
             const uint64_t m = __ballot( which == l );
             if (lane == 0) lds.cnt[l][4 * k + wave] = (uint32_t)__popcll( m );
-            if (which == l) mine |= (((uint32_t)(l + 1) << 6) | (uint32_t)__popcll( m & ((1ull << lane) - 1ull) )) << (8 * k);
+            if (which == l) mine |= (Mine)(((uint32_t)(l + 1) << 6) | (uint32_t)__popcll( m & ((1ull << lane) - 1ull) )) << (SLOT * k);
         }
     }
     // reserve and store; job_of( k ) = the id of this lane's job of chunk k.  Called once by every lane of the workgroup, after the last note().
@@ -754,16 +758,105 @@ struct JobAppend
         #pragma unroll
         for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
         {
-            const uint32_t e = (mine >> (8 * k)) & 255u;
+            const uint32_t e = (uint32_t)(mine >> (SLOT * k)) & ((1u << SLOT) - 1u);
             if (e)
             {
                 const uint32_t l = (e >> 6) - 1u;
-                uint32_t* const list = l == 0u ? out.dp : (l == 1u ? out.second : out.third);
+                uint32_t* const list = l == 0u ? out.dp : (l == 1u ? out.second : (l == 2u ? out.third : out.pairs));
                 list[lds.base[l] + lds.cnt[l][4 * k + wave] + (e & 63u)] = job_of( k );
             }
         }
     }
 };
+
+// the same for a kernel whose lanes hold TWO jobs each (a pair of the gap chance) and put either, both or none on out.dp: one ballot round per
+// member, one reservation per workgroup
+struct JobAppendTwo
+{
+    struct Lds { uint32_t cnt[2 * 4 * JOB_LIST_CHUNKS]; uint32_t base; };
+    uint64_t mine = 0;                                            // chunk k, member r in bits 16k + 8r .. + 7: 64 | rank among the wave's jobs of that round
+    __device__ __forceinline__ void note(Lds& lds, const int k, const bool first, const bool second)
+    {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        #pragma unroll
+        for (int r = 0; r < 2; ++r)
+        {
+            const bool on = r ? second : first;
+            const uint64_t m = __ballot( on );
+            if (lane == 0) lds.cnt[4 * (2 * k + r) + wave] = (uint32_t)__popcll( m );
+            if (on) mine |= (uint64_t)(64u | (uint32_t)__popcll( m & ((1ull << lane) - 1ull) )) << (16 * k + 8 * r);
+        }
+    }
+    // job_of( k, r ) = the id of member r of this lane's pair of chunk k
+    template <typename JobOf>
+    __device__ __forceinline__ void flush(Lds& lds, const JobLists& out, JobOf job_of)
+    {
+        __syncthreads();
+        if (threadIdx.x == 0)
+        {
+            uint32_t tot = 0;
+            for (int i = 0; i < 2 * 4 * JOB_LIST_CHUNKS; ++i) { const uint32_t c = lds.cnt[i]; lds.cnt[i] = tot; tot += c; }
+            lds.base = tot ? atomicAdd( out.counts, (unsigned int)tot ) : 0u;
+        }
+        __syncthreads();
+        const uint32_t wave = threadIdx.x >> 6;
+        #pragma unroll
+        for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
+            #pragma unroll
+            for (int r = 0; r < 2; ++r)
+            {
+                const uint32_t e = (uint32_t)(mine >> (16 * k + 8 * r)) & 255u;
+                if (e) out.dp[lds.base + lds.cnt[4 * (2 * k + r) + wave] + (e & 63u)] = job_of( k, r );
+            }
+    }
+};
+
+// ---- the gap chance's pairs ----
+// A read with an indel has exact seeds on two diagonals a few columns apart and reaches this stage as two candidates whose band-31 windows
+// overlap in all but those few columns: 31 - shift of either job's 31 diagonals are the same diagonals of the same read against the same
+// text.  Two such jobs that the first pass BOTH sends to the gap chance go there as one entry (list `pairs`), and gap_chance_e2e31_pair walks
+// the 31 + shift diagonals once for the two.  Which jobs may pair is a function of the batch's geometry alone (nvbio_banded_gap_pairs
+// reports it): jobs j and j + 1 are linked iff they have the same read and flags, unclipped windows of read length + 31 symbols and
+// 0 < |win_begin[j+1] - win_begin[j]| <= PAIR_MAX_SHIFT, and lie in the same wave of the first pass (64 consecutive jobs); a run of linked
+// jobs pairs up from its lowest job.  Nothing is sorted to make candidates adjacent: the seed pass hands a read's candidates over together,
+// strand by strand, in SEED order with equal neighbours dropped (emit_seed_results) -- contiguous, but not ascending in diagonal: a read
+// with an insertion (or a deletion on the other strand) brings its higher diagonal first -- so the rule takes either order of win_begin.
+// PAIR_MAX_SHIFT = 5 covers every gap the gap chance evaluates; the union window then has up to 161 + 31 + 5 = 197 symbols: 14 packed text
+// words (209 symbols at any storage offset) where the single job loads 13.
+constexpr uint32_t PAIR_MAX_SHIFT = NVBIO_GAP_PAIR_MAX_SHIFT;
+
+// +1: `job` is the lower job of a pair (its partner is job + 1), -1: the upper one, 0: neither.  Called by all 64 lanes of a wave whose lane l
+// holds job (job of lane 0) + l; live = the lane has a job at all
+__device__ __forceinline__ int gap_pair_role(const BatchDev& b, const uint32_t job, const bool live)
+{
+    uint32_t rid = 0, fl = 0, tb = 0, whole = 0;
+    if (live)
+    {
+        rid = b.read_id ? b.read_id[job] : job;
+        const uint32_t M = b.read_offsets[rid + 1] - b.read_offsets[rid];
+        fl = b.flags ? b.flags[job] : 0u;
+        tb = b.win_begin[job];
+        whole = (M >= 1u && M <= PLANE_MAX_READ && b.win_end[job] - tb == M + 31u) ? 1u : 0u;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t rid_n = __shfl_down( rid, 1 ), fl_n = __shfl_down( fl, 1 ), tb_n = __shfl_down( tb, 1 ), whole_n = __shfl_down( whole, 1 );
+    const uint32_t shift = tb_n > tb ? tb_n - tb : tb - tb_n;      // (either job may hold the lower window)
+    const bool link = lane < 63u && whole && whole_n && rid_n == rid && fl_n == fl && shift >= 1u && shift <= PAIR_MAX_SHIFT;
+    const uint64_t links = __ballot( link );
+    const uint32_t run = lane ? (uint32_t)__clzll( (long long)~(links << (64u - lane)) ) : 0u;     // linked lanes right below this one
+    const bool lower = link && !(run & 1u);
+    const uint64_t lowers = __ballot( lower );
+    if (lower) return 1;
+    return (lane && ((lowers >> (lane - 1u)) & 1ull)) ? -1 : 0;
+}
+
+__global__ void __launch_bounds__(256)
+gap_pairs_kernel(const BatchDev b, uint32_t* __restrict__ partner)
+{
+    const uint32_t job = blockIdx.x * 256u + threadIdx.x;
+    const int role = gap_pair_role( b, job, job < b.n );
+    if (job < b.n) partner[job] = role ? (role > 0 ? job + 1u : job - 1u) : 0xFFFFFFFFu;
+}
 
 // one job of the pass below: scores / sinks as its MODE says, returns the job's flag (what the kernel stores in need_dp[job])
 template <int RBITS, int MODE, bool QUAL>
@@ -1154,7 +1247,7 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
                       const SchemeDev sc, const JobLists out, const uint32_t third_mask)
 {
     constexpr bool LIST = MODE != 0;
-    constexpr int  NL   = LIST ? 1 : 3;
+    constexpr int  NL   = LIST ? 1 : 4;
     __shared__ int32_t s_pen[QUAL ? 64 : 1];
     __shared__ typename JobAppend<NL>::Lds s_lists;
     const uint32_t n    = LIST ? *job_count : b.n;
@@ -1167,16 +1260,28 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
     }
     JobAppend<NL> app;
     auto job_of = [&](const int k) -> uint32_t { const uint32_t slot = slot0 + 256u * k + threadIdx.x; return LIST ? job_list[slot] : slot; };
+    // (flag 4 goes to the gap chance at all; batches declared ragged keep the stage they had: single jobs only)
+    const bool pairing = ((third_mask >> 4) & 1u) && !(b.algo & (NVBIO_ALN_NO_PAIRED_GAP_CHANCE | NVBIO_ALN_RAGGED_READS));
     #pragma unroll 1
     for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
     {
         int which = -1;
+        uint32_t flag = 0;
         if (slot0 + 256u * k + threadIdx.x < n)
         {
             const uint32_t job  = job_of( k );
-            const uint32_t flag = ungapped_e2e31_job<RBITS,MODE,QUAL>( b, P, G, gap_open, gap_ext, scores, sinks, job, s_pen );
+            flag = ungapped_e2e31_job<RBITS,MODE,QUAL>( b, P, G, gap_open, gap_ext, scores, sinks, job, s_pen );
             need_dp[job] = (uint8_t)flag;
             if (flag) which = LIST ? 0 : (flag == 3u ? 1 : (((third_mask >> flag) & 1u) ? 2 : 0));
+        }
+        if (MODE == 0 && !QUAL && pairing && __any( flag == 4u ))
+        {
+            // two partners (gap_pair_role) that BOTH go to the gap chance go as one entry of list `pairs`, put there by the lower one
+            const uint32_t slot = slot0 + 256u * k + threadIdx.x;
+            const int role = gap_pair_role( b, slot, slot < n );
+            const uint32_t flag_up = __shfl_down( flag, 1 ), flag_dn = __shfl_up( flag, 1 );
+            if (role > 0 && flag == 4u && flag_up == 4u) which = 3;
+            if (role < 0 && flag == 4u && flag_dn == 4u) which = -1;
         }
         app.note( s_lists, k, which );
     }
@@ -1209,6 +1314,9 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
 // batch the pass cost 1.1-1.7 ms for 0.5-1.0 ms of DP saved.  With the ladder taken to four priced mismatches per member (bound 18: two gaps and a
 // mismatch; also built, also green) the DP went 3.9 -> 2.7 ms and the pass cost 2.1: a job costs the pass half a DP and only half of them settle.
 // one job of the gap chance: returns its flag, 0 (settled: scores / sinks written) or 1 (the DP's); has_u: a third-chance job (need_dp = 2)
+// KEEP IN STEP with gap_chance_e2e31_pair below: it repeats this function's plane set-up, last-32-rows words, clean(), walk from both ends,
+// one-gap ladder and two-gap intervals for two jobs at once; a change to any of them here must be made there too
+// (tests/test_gpu_band31_paired_gap_chance.py holds the two to the same oracle).
 template <int RBITS>
 __device__ __forceinline__ uint32_t
 gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
@@ -1461,17 +1569,381 @@ gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const GapLadder lad, co
     return 1u;
 }
 
-// the jobs of job_list (launched over the whole batch's workgroups: those behind the list's end leave before they touch anything); one that
-// ends as 1 goes on out.dp
+// TWO jobs of the gap chance in one: `job` and job + 1, partners by gap_pair_role, both flagged 4 by the first pass -- the same read on the same
+// strand, windows of M + 31 symbols that begin sh = 1 .. PAIR_MAX_SHIFT columns apart; the LOWER job is the one whose window begins first, the
+// UPPER job the other (either may be `job`).  Diagonal d of the upper job IS diagonal D = d + sh of the
+// lower one (the same rows against the same text symbols), so the read's planes are built once, the text's for the union window of M + 31 + sh
+// symbols, and the 31 + sh diagonals D are walked once with the per-diagonal code of gap_chance_e2e31_job (the first and last 32 rows, the walk
+// from both ends where some lane needs it, the packed history, the hot-half test, the two-gap gate).  What a diagonal yields -- its first and
+// last three mismatches -- does not depend on the job; which alignments COUNT does: a job's classes are those whose diagonals all lie in its own
+// band, D in [0, 30] for the lower job, [sh, 30 + sh] for the upper.  Hence two sets of accumulators (c*, the largest end column among the
+// members that reach it -- columns relative to the job's own win_begin --, the two-gap existence bits), each fed by exactly the tests the
+// single job runs at its diagonal d = D resp. D - sh, with the single job's guards taken in the job's own numbering (d >= g, the middle
+// diagonal's neighbours inside 0 .. 30).  The cost of a one-gap member is the same for both; the two-gap intervals differ only next to a
+// band's edge and are otherwise evaluated once.  The wave-level gates are taken over both jobs' diagonals: they only ever skip tests whose
+// outcome is known (see the single job), so a wider gate changes no result.  Each job then settles by the single job's condition with
+// c_unk_n (a flag-4 job: every diagonal of its own band has more than `cap` mismatches).
+// The text planes hold 224 bits and a funnel shift reaches 31: from D = 6 on the planes are kept 4 symbols down (the lowest diagonal still
+// looked at is then the two-gap block's middle one, D - 2 >= 4), which keeps every shift within 0 .. 31 up to D = 35.
+// Returns the two flags: bit 0 `job`'s, bit 1 job + 1's (0: settled, scores / sinks written; 1: the DP's).
+// KEEP IN STEP with gap_chance_e2e31_job above (see the note there): the per-diagonal code is that function's, line for line.
 template <int RBITS>
-__global__ void __launch_bounds__(256)
+__device__ __forceinline__ uint32_t
+gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
+                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job)
+{
+    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
+    const uint32_t first = b.read_offsets[rid];
+    const uint32_t M     = b.read_offsets[rid + 1] - first;
+    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
+    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
+    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
+    const uint32_t tb0 = b.win_begin[job], tb1 = b.win_begin[job + 1u];
+    const uint32_t up    = tb1 > tb0 ? 1u : 0u;                  // which of the two is the upper job: job + up (the lower: job + 1 - up)
+    const uint32_t tb    = up ? tb0 : tb1;
+    const uint32_t sh    = up ? tb1 - tb0 : tb0 - tb1;           // 1 .. PAIR_MAX_SHIFT
+    // (partners flagged 4: 1 <= M <= 161, both windows M + 31 symbols, P > 0, open <= ext < 0)
+
+    uint32_t pl[6], ph[6], pn[6], pm[6], ql[7], qh[7];
+    {
+        uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
+        {
+            ReadWords<RBITS> rw; TextWords14 tw;
+            load_read_words<RBITS>( b.reads, first, M, rw );
+            load_text_words14( b.text, tb, M + 31u + sh, tw );
+            read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
+            text_planes224( tw, tb, tlo, thi );
+        }
+        #pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            const int32_t left = (int32_t)M - 64 * k;
+            const uint64_t mask = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
+            pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
+            ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
+            pm[2*k] = (uint32_t)mask;   pm[2*k+1] = (uint32_t)(mask >> 32);
+            pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
+            ql[2*k] = (uint32_t)tlo[k]; ql[2*k+1] = (uint32_t)(tlo[k] >> 32);
+            qh[2*k] = (uint32_t)thi[k]; qh[2*k+1] = (uint32_t)(thi[k] >> 32);
+        }
+        ql[6] = (uint32_t)tlo[3]; qh[6] = (uint32_t)thi[3];
+    }
+
+    // the cost ladder
+    constexpr int GA = GAP_CHANCE_GA;
+    const int32_t go = gap_open, ge = gap_ext;
+    int32_t cg[GA + 2];                                          // cg[g] = cost of a gap of g symbols
+    #pragma unroll
+    for (int g = 1; g <= GA + 1; ++g) cg[g] = -(go + (g - 1) * ge);
+    cg[0] = 0;
+    const int32_t c_unk = lad.c_unk_n;
+    const int32_t cost11 = 2 * cg[1], cost12 = cg[1] + cg[2];
+
+    // mismatch word k (rows 32 k .. 32 k + 31) of the diagonal that lies x symbols on in the planes as they stand (x is wave-uniform)
+    auto mmw = [&](const int k, const uint32_t x) -> uint32_t {
+        const uint32_t tl = __builtin_amdgcn_alignbit( ql[k + 1], ql[k], x ), th = __builtin_amdgcn_alignbit( qh[k + 1], qh[k], x );
+        return (((pl[k] ^ tl) | (ph[k] ^ th)) & pm[k]) | pn[k];
+    };
+    // the read's LAST 32 rows (rows base .. base + 31; all of them if it has fewer) and the text symbols they can meet, as words of their own:
+    // bit j of (plT, phT, pnT, pmT) = row base + j, bit j of (qlT, qhT) = text symbol base + j
+    const uint32_t base = M >= 32u ? M - 32u : 0u;
+    uint32_t plT, phT, pnT, pmT, qlT[2], qhT[2];
+    {
+        const uint32_t bw = base >> 5, bs = base & 31u;
+        uint32_t a[4] = { 0, 0, 0, 0 }, c[4] = { 0, 0, 0, 0 };
+        #pragma unroll
+        for (int k = 0; k < 6; ++k)
+            if (bw == (uint32_t)k)
+            {
+                a[0] = pl[k]; a[1] = k + 1 < 6 ? pl[k + 1] : 0u; a[2] = ph[k]; a[3] = k + 1 < 6 ? ph[k + 1] : 0u;
+                c[0] = pn[k]; c[1] = k + 1 < 6 ? pn[k + 1] : 0u; c[2] = pm[k]; c[3] = k + 1 < 6 ? pm[k + 1] : 0u;
+            }
+        plT = __builtin_amdgcn_alignbit( a[1], a[0], bs ); phT = __builtin_amdgcn_alignbit( a[3], a[2], bs );
+        pnT = __builtin_amdgcn_alignbit( c[1], c[0], bs ); pmT = __builtin_amdgcn_alignbit( c[3], c[2], bs );
+    }
+    // (the text's two words: 64 symbols from `base` on in the planes as they stand -- taken again when the planes move down, see D == 6 below)
+    auto tail_text = [&]() {
+        const uint32_t bw = base >> 5, bs = base & 31u;
+        uint32_t t[3] = { 0, 0, 0 }, u[3] = { 0, 0, 0 };
+        #pragma unroll
+        for (int k = 0; k < 6; ++k)
+            if (bw == (uint32_t)k)
+            {
+                t[0] = ql[k]; t[1] = k + 1 < 7 ? ql[k + 1] : 0u; t[2] = k + 2 < 7 ? ql[k + 2] : 0u;
+                u[0] = qh[k]; u[1] = k + 1 < 7 ? qh[k + 1] : 0u; u[2] = k + 2 < 7 ? qh[k + 2] : 0u;
+            }
+        qlT[0] = __builtin_amdgcn_alignbit( t[1], t[0], bs ); qlT[1] = __builtin_amdgcn_alignbit( t[2], t[1], bs );
+        qhT[0] = __builtin_amdgcn_alignbit( u[1], u[0], bs ); qhT[1] = __builtin_amdgcn_alignbit( u[2], u[1], bs );
+    };
+    tail_text();
+    // history of the last GA diagonals (slot k: diagonal D - 1 - k): (lead0, lead1, lead2) and (tail0, tail1, tail2) packed a byte each (<= 161)
+    uint32_t Lp[GA], Tp[GA];
+    #pragma unroll
+    for (int k = 0; k < GA; ++k) { Lp[k] = 0; Tp[k] = 0; }
+    // three histories of the last diagonals in one word, a byte each: bit k = diagonal D - 1 - k could be half of a one-gap alignment (`hot`) /
+    // bit 8 + k = it is `long` / bit 16 + k = it has NO `mid` (the two-gap gate, see the single job)
+    uint32_t hist = 0;
+    // c* and the largest end column among the members that reach it, as ONE number per job: cost << 6 | 63 - column
+    // (columns <= 30; a member costs cg[g] + (i + j) P with g <= 5, i + j <= 2, and launch_pk runs only under packed_ok(), which holds every
+    // penalty to 4096: costs stay below 2^15, the key needs them below 2^26 -- a wider limit there must be matched here): the least key is the
+    // least cost and, among equals, the largest column, which is the single job's `c < best || (c == best && end > best_end)`
+    uint32_t best_key[2] = { 0xFFFFFFFFu, 0xFFFFFFFFu };        // [0]: the lower job, [1]: the upper job
+    bool ex11[2] = { false, false }, ex12[2] = { false, false };
+    const int32_t Mi = (int32_t)M;
+    const int32_t hot_thr = (Mi - GA) / 2;
+    uint32_t xo = 0;                                             // the planes stand xo symbols down
+
+    auto clean = [&](const uint32_t x, const int32_t bf, const int32_t bl, const int32_t lo, const int32_t hi) -> bool {
+        if (lo >= hi) return true;
+        if ((bf >= lo && bf < hi) || (bl >= lo && bl < hi)) return false;
+        bool any = false;
+        #pragma unroll
+        for (int k = 0; k < 6; ++k)
+        {
+            const int32_t a0 = lo - 32 * k > 0 ? lo - 32 * k : 0, a1 = hi - 32 * k < 32 ? hi - 32 * k : 32;
+            if (a0 < a1)
+            {
+                const uint32_t hi_m = (a1 >= 32) ? 0xFFFFFFFFu : ((1u << a1) - 1u);
+                const uint32_t lo_m = (1u << a0) - 1u;
+                any = any || ((mmw( k, x ) & hi_m & ~lo_m) != 0u);
+            }
+        }
+        return !any;
+    };
+    auto take = [&](const int j, const int32_t c, const uint32_t end) {
+        const uint32_t key = ((uint32_t)c << 6) | (63u - end);
+        best_key[j] = key < best_key[j] ? key : best_key[j];
+    };
+
+    for (uint32_t D = 0; D <= 32u + PAIR_MAX_SHIFT; ++D)
+    {
+        if (!__any( D <= 32u + sh )) break;                      // (wave-uniform: the largest shift of the wave's pairs)
+        if (D == 6u)
+        {
+            #pragma unroll
+            for (int k = 0; k < 6; ++k)
+            {
+                ql[k] = __builtin_amdgcn_alignbit( ql[k + 1], ql[k], 4u );
+                qh[k] = __builtin_amdgcn_alignbit( qh[k + 1], qh[k], 4u );
+            }
+            ql[6] >>= 4; qh[6] >>= 4;
+            tail_text();
+            xo = 4u;
+        }
+        const uint32_t x = D - xo;                               // <= 31
+        const bool have = D <= 30u + sh;                         // a diagonal of the union window
+        const int32_t dU = (int32_t)D - (int32_t)sh;             // this diagonal in the upper job's numbering
+        const bool haveL = D <= 30u;                             // ... of the lower job's own band (the upper one's: 0 <= dU <= 30)
+        uint32_t f0 = M, f1 = M, f2 = M, l0 = 0xFFFFFFFFu, l1 = 0xFFFFFFFFu, l2 = 0xFFFFFFFFu;
+        bool mid_d = false;
+        if (have)
+        {
+            uint32_t w = mmw( 0, x );
+            if (w) { f0 = (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
+            if (w) { f1 = (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
+            if (w) f2 = (uint32_t)__builtin_ctz( w );
+            const uint32_t tl = __builtin_amdgcn_alignbit( qlT[1], qlT[0], x ), th = __builtin_amdgcn_alignbit( qhT[1], qhT[0], x );
+            w = (((plT ^ tl) | (phT ^ th)) & pmT) | pnT;          // rows base .. base + 31
+            if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = base + t; w &= ~(1u << t); }
+            if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = base + t; w &= ~(1u << t); }
+            if (w) l2 = base + 31u - (uint32_t)__builtin_clz( w );
+            mid_d = M >= 96u && mmw( 1, x ) != 0u;               // a mismatch in rows 32 .. 63, all of them rows of the read and below its last 32
+        }
+        if (__any( have && M > 32u && (f2 == M || l2 == 0xFFFFFFFFu) ))
+        {
+            f0 = f1 = f2 = M; l0 = l1 = l2 = 0xFFFFFFFFu;
+            #pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (__any( have && f2 == M && pm[k] != 0u ))
+                {
+                    uint32_t w = (have && f2 == M) ? mmw( k, x ) : 0u;
+                    if (f0 == M && w) { f0 = 32u * k + (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
+                    if (f0 != M && f1 == M && w) { f1 = 32u * k + (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
+                    if (f1 != M && f2 == M && w) f2 = 32u * k + (uint32_t)__builtin_ctz( w );
+                }
+            #pragma unroll
+            for (int k = 5; k >= 0; --k)
+                if (__any( have && l2 == 0xFFFFFFFFu && pm[k] != 0u ))
+                {
+                    uint32_t w = (have && l2 == 0xFFFFFFFFu) ? mmw( k, x ) : 0u;
+                    if (l0 == 0xFFFFFFFFu && w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = 32u * k + t; w &= ~(1u << t); }
+                    if (l0 != 0xFFFFFFFFu && l1 == 0xFFFFFFFFu && w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = 32u * k + t; w &= ~(1u << t); }
+                    if (l1 != 0xFFFFFFFFu && l2 == 0xFFFFFFFFu && w) l2 = 32u * k + 31u - (uint32_t)__builtin_clz( w );
+                }
+        }
+        const int32_t L0 = (int32_t)f0, L1 = (int32_t)f1, L2 = (int32_t)f2;          // rows before the 1st / 2nd / 3rd mismatch
+        const int32_t T0 = l0 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l0;             // rows after the last / last-but-one / last-but-two
+        const int32_t T1 = l1 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l1;
+        const int32_t T2 = l2 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l2;
+        const bool hot_d = have && (L2 >= hot_thr || T2 >= hot_thr);
+        const bool long_d = have && (L0 >= 30 || T0 >= 30);
+
+        if (__any( have && (hot_d || (hist & 31u) != 0u) ))
+        {
+            #pragma unroll
+            for (int g = 1; g <= GA; ++g)
+                if (have && D >= (uint32_t)g && (hot_d || ((hist >> (g - 1)) & 1u)))
+                {
+                    // the member's two diagonals D - g and D lie in the lower job's band iff D <= 30, in the upper one's iff D - g >= sh
+                    const bool inL = haveL, inU = dU >= g;
+                    const int32_t a0 = (int32_t)(Lp[g - 1] & 255u), a1 = (int32_t)((Lp[g - 1] >> 8) & 255u), a2 = (int32_t)(Lp[g - 1] >> 16);
+                    const int32_t t0 = (int32_t)(Tp[g - 1] & 255u), t1 = (int32_t)((Tp[g - 1] >> 8) & 255u), t2 = (int32_t)(Tp[g - 1] >> 16);
+                    // text gap of g: diagonal D - g (prefix), then D (suffix); ends in column D
+                    if (a2 + T2 >= Mi)
+                    {
+                        const int32_t lead[3] = { a0, a1, a2 }, tail[3] = { T0, T1, T2 };
+                        int32_t c = 0x7FFFFFFF;
+                        #pragma unroll
+                        for (int i = 0; i <= 2; ++i)
+                            #pragma unroll
+                            for (int j = 0; i + j <= 2; ++j)
+                                if (lead[i] + tail[j] >= Mi)
+                                {
+                                    const int32_t v = cg[g] + (i + j) * P;
+                                    c = v < c ? v : c;
+                                }
+                        if (c != 0x7FFFFFFF)
+                        {
+                            if (inL) take( 0, c, D );
+                            if (inU) take( 1, c, (uint32_t)dU );
+                        }
+                    }
+                    // pattern gap of g: diagonal D (prefix), then D - g (suffix); ends in column D - g
+                    if (L2 + t2 + g >= Mi)
+                    {
+                        const int32_t lead[3] = { L0, L1, L2 }, tail[3] = { t0, t1, t2 };
+                        int32_t c = 0x7FFFFFFF;
+                        #pragma unroll
+                        for (int i = 0; i <= 2; ++i)
+                            #pragma unroll
+                            for (int j = 0; i + j <= 2; ++j)
+                                if (lead[i] + tail[j] + g >= Mi)
+                                {
+                                    const int32_t v = cg[g] + (i + j) * P;
+                                    c = v < c ? v : c;
+                                }
+                        if (c != 0x7FFFFFFF)
+                        {
+                            if (inL) take( 0, c, D - (uint32_t)g );
+                            if (inU) take( 1, c, (uint32_t)(dU - g) );
+                        }
+                    }
+                }
+        }
+        // two gaps around the middle diagonal D - 2 (history slot 1), as in the single job: for the lower job it is its diagonal bm = D - 2 at its
+        // iterations d = D in 2 .. 32, for the upper one bm = dU - 2 at d = dU in 2 .. 32; a neighbour counts iff it lies in the job's band
+        const bool actL = D >= 2u && D <= 32u, actU = dU >= 2 && dU <= 32;
+        if (__any( (actL || actU) && (long_d || (hist & 0x20D00u) != 0u) ))        // lng & 0xD, nmid & 2
+        {
+            const int32_t NEG = -(1 << 20), POS = 1 << 20;
+            // the intervals of a job whose iteration this is d (its middle diagonal d - 2), hv: its diagonal d exists
+            auto intervals = [&](const int32_t d, const bool hv, int32_t (&iv)[4]) {
+                const int32_t bm = d - 2;
+                iv[0] = NEG; iv[1] = POS; iv[2] = NEG; iv[3] = POS;                      // lo1, hi1, lo2, hi2
+                if (bm >= 1)       { iv[0] = (int32_t)(Lp[2] & 255u); iv[1] = Mi - (int32_t)(Tp[2] & 255u) - 1; }      // a = bm - 1: text gap in; c = bm - 1: pattern gap out
+                if (bm + 1 <= 30)  { const int32_t p = (int32_t)(Lp[0] & 255u) + 1, q = Mi - (int32_t)(Tp[0] & 255u); iv[0] = p > iv[0] ? p : iv[0]; iv[1] = q < iv[1] ? q : iv[1]; }
+                if (bm >= 2)       { iv[2] = (int32_t)(Lp[3] & 255u); iv[3] = Mi - (int32_t)(Tp[3] & 255u) - 2; }      // a / c = bm - 2
+                if (hv)            { const int32_t p = L0 + 2, q = Mi - T0; iv[2] = p > iv[2] ? p : iv[2]; iv[3] = q < iv[3] ? q : iv[3]; }   // a / c = bm + 2
+            };
+            // the middle diagonal's third mismatch from either end (first / last if it has fewer): a row that is NOT clean
+            const int32_t b2 = (int32_t)(Lp[1] >> 16), b1 = (int32_t)((Lp[1] >> 8) & 255u), b0 = (int32_t)(Lp[1] & 255u);
+            const int32_t bf = b2 < Mi ? b2 : (b1 < Mi ? b1 : b0);
+            const int32_t e2 = (int32_t)(Tp[1] >> 16), e1 = (int32_t)((Tp[1] >> 8) & 255u), e0 = (int32_t)(Tp[1] & 255u);
+            const int32_t et = e2 < Mi ? e2 : (e1 < Mi ? e1 : e0);
+            const int32_t bl = et < Mi ? Mi - 1 - et : NEG;
+            const uint32_t xm = x - 2u;                            // the middle diagonal in the planes as they stand (D >= 2 here)
+            auto tests = [&](const int32_t (&iv)[4], bool& r11, bool& r12) {
+                r11 = false; r12 = false;
+                if (iv[0] > NEG && iv[1] < POS) r11 = clean( xm, bf, bl, iv[0], iv[1] );
+                if (iv[0] > NEG && iv[3] < POS) r12 = clean( xm, bf, bl, iv[0], iv[3] );
+                if (iv[2] > NEG && iv[1] < POS) r12 = r12 || clean( xm, bf, bl, iv[2], iv[1] );
+            };
+            int32_t iv[4];
+            bool r11 = false, r12 = false;
+            if (actL)
+            {
+                intervals( (int32_t)D, haveL, iv );
+                tests( iv, r11, r12 );
+                ex11[0] = ex11[0] || r11; ex12[0] = ex12[0] || r12;
+            }
+            if (actU)
+            {
+                // away from a band's edge the two jobs ask the same questions: all four neighbours of the middle diagonal lie in both bands
+                // iff dU - 2 >= 2 (the upper job's lower edge) and D <= 30 (the lower job's upper edge)
+                if (!(actL && dU >= 4 && D <= 30u))
+                {
+                    intervals( dU, dU <= 30, iv );
+                    tests( iv, r11, r12 );
+                }
+                ex11[1] = ex11[1] || r11; ex12[1] = ex12[1] || r12;
+            }
+        }
+        // shift the history
+        #pragma unroll
+        for (int k = GA - 1; k > 0; --k) { Lp[k] = Lp[k - 1]; Tp[k] = Tp[k - 1]; }
+        Lp[0] = (uint32_t)L0 | ((uint32_t)L1 << 8) | ((uint32_t)L2 << 16);
+        Tp[0] = (uint32_t)T0 | ((uint32_t)T1 << 8) | ((uint32_t)T2 << 16);
+        hist = ((hist << 1) & 0xFEFEFEu) | (hot_d ? 1u : 0u) | (long_d ? 0x100u : 0u) | (mid_d ? 0u : 0x10000u);
+    }
+    uint32_t flags = 0;
+    #pragma unroll
+    for (int j = 0; j < 2; ++j)
+    {
+        const int32_t  best_cost = best_key[j] == 0xFFFFFFFFu ? 0x7FFFFFFF : (int32_t)(best_key[j] >> 6);
+        const uint32_t best_end  = 63u - (best_key[j] & 63u);
+        const bool settled = best_cost < c_unk && !(ex11[j] && cost11 <= best_cost) && !(ex12[j] && cost12 <= best_cost);
+        const uint32_t which = j ? up : 1u - up;                 // 0: `job`, 1: job + 1
+        if (settled) { scores[job + which] = -best_cost; sinks[job + which] = make_uint2( M + best_end, M ); }
+        else flags |= 1u << which;
+    }
+    return flags;
+}
+
+// one workgroup's chunks of list `pairs` (slot0 < n = the list's length): every pair through gap_chance_e2e31_pair, the members it does not
+// settle on out.dp
+template <int RBITS>
+__device__ __forceinline__ void
+gap_chance_pairs_chunks(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
+                        int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
+                        const uint32_t* __restrict__ list_p, const uint32_t n, const uint32_t slot0, const JobLists& out, JobAppendTwo::Lds& lds)
+{
+    JobAppendTwo app;
+    auto job_of = [&](const int k, const int r) -> uint32_t { return list_p[slot0 + 256u * k + threadIdx.x] + (uint32_t)r; };
+    #pragma unroll 1
+    for (int k = 0; k < JOB_LIST_CHUNKS; ++k)
+    {
+        uint32_t flags = 0;
+        if (slot0 + 256u * k + threadIdx.x < n)
+        {
+            const uint32_t job = job_of( k, 0 );
+            flags = gap_chance_e2e31_pair<RBITS>( b, P, lad, gap_open, gap_ext, scores, sinks, job );
+            need_dp[job] = (uint8_t)(flags & 1u); need_dp[job + 1u] = (uint8_t)(flags >> 1);
+        }
+        app.note( lds, k, (flags & 1u) != 0u, (flags & 2u) != 0u );
+    }
+    app.flush( lds, out, job_of );
+}
+
+// the jobs of job_list, then the pairs of list_p (launched over one workgroup more than the whole batch's: those behind the lists' ends leave
+// before they touch anything); one that ends as 1 goes on out.dp
+template <int RBITS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5)))
 gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
                         int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
-                        const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count, const JobLists out)
+                        const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
+                        const uint32_t* __restrict__ list_p, const uint32_t* __restrict__ count_p, const JobLists out)
 {
     __shared__ JobAppend<1>::Lds s_lists;
-    const uint32_t n     = *job_count;
-    const uint32_t slot0 = blockIdx.x * (256u * JOB_LIST_CHUNKS);
+    __shared__ JobAppendTwo::Lds s_two;
+    constexpr uint32_t W = 256u * JOB_LIST_CHUNKS;
+    const uint32_t n = *job_count, np = *count_p;
+    const uint32_t nbp = (np + W - 1u) / W;                          // the pairs' workgroups come first: they run the longest
+    if (blockIdx.x < nbp)
+    {
+        gap_chance_pairs_chunks<RBITS>( b, P, lad, gap_open, gap_ext, scores, sinks, need_dp, list_p, np, blockIdx.x * W, out, s_two );
+        return;
+    }
+    const uint32_t slot0 = (blockIdx.x - nbp) * W;
     if (slot0 >= n) return;                                          // (the whole workgroup)
     JobAppend<1> app;
     auto job_of = [&](const int k) -> uint32_t { return job_list[slot0 + 256u * k + threadIdx.x]; };
@@ -1497,24 +1969,35 @@ gap_chance_e2e31_kernel(const BatchDev b, const int32_t P, const GapLadder lad, 
 // workgroup i is the second chance's iff floor( (i + 1) nb2 / (nb2 + nb3) ) > floor( i nb2 / (nb2 + nb3) ) -- an even interleave, nb2 such
 // workgroups among the first nb2 + nb3, spread over the gap chance's whole duration -- and walks chunk floor( i nb2 / (nb2 + nb3) ) of its
 // list (the gap chance's: i minus that).  The jobs run the device functions of the two separate launches, so every job ends as it does there.
-// (Launched over job_list_grid( b.n ) + 1 workgroups -- the lists are disjoint, so nb2 + nb3 <= that --; those past nb2 + nb3 leave at once.)
+// The gap chance's role has two lists: the pairs of list_p (gap_chance_e2e31_pair; a workgroup holds pairs only, so no wave runs both device
+// functions) and the single jobs of list_t; with nbp workgroups' worth of pairs the role's first nbp workgroups take the pairs, which run
+// the longest.
+// (Launched over job_list_grid( b.n ) + 2 workgroups -- the lists are disjoint and a pair stands for two jobs, so nb2 + nb3 + nbp <= that --;
+// those past nb2 + nb3 + nbp leave at once.)
 template <int RBITS>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5)))
 chances_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
                      const uint32_t* __restrict__ list_s, const uint32_t* __restrict__ count_s,
-                     const uint32_t* __restrict__ list_t, const uint32_t* __restrict__ count_t, const JobLists out)
+                     const uint32_t* __restrict__ list_t, const uint32_t* __restrict__ count_t,
+                     const uint32_t* __restrict__ list_p, const uint32_t* __restrict__ count_p, const JobLists out)
 {
     __shared__ JobAppend<1>::Lds s_lists;
+    __shared__ JobAppendTwo::Lds s_two;
     constexpr uint32_t W = 256u * JOB_LIST_CHUNKS;
-    const uint32_t n2 = *count_s, n3 = *count_t;
-    const uint32_t nb2 = (n2 + W - 1u) / W, nb3 = (n3 + W - 1u) / W, nb = nb2 + nb3;     // (n2, n3 < 2^31: no overflow)
+    const uint32_t n2 = *count_s, n3 = *count_t, np = *count_p;
+    const uint32_t nb2 = (n2 + W - 1u) / W, nbp = (np + W - 1u) / W, nb3 = (n3 + W - 1u) / W + nbp, nb = nb2 + nb3;     // (n2, n3, np < 2^31: no overflow)
     if (blockIdx.x >= nb) return;                                    // (the whole workgroup)
     const uint32_t before = (uint32_t)((uint64_t)blockIdx.x * nb2 / nb);                 // second-chance workgroups in front of this one
     const bool     second = (uint32_t)((uint64_t)(blockIdx.x + 1u) * nb2 / nb) > before;
+    if (!second && blockIdx.x - before < nbp)
+    {
+        gap_chance_pairs_chunks<RBITS>( b, P, lad, gap_open, gap_ext, scores, sinks, need_dp, list_p, np, (blockIdx.x - before) * W, out, s_two );
+        return;
+    }
     const uint32_t n      = second ? n2 : n3;
     const uint32_t* __restrict__ job_list = second ? list_s : list_t;
-    const uint32_t slot0  = (second ? before : blockIdx.x - before) * W;                 // < n: this role has a chunk left (see above)
+    const uint32_t slot0  = (second ? before : blockIdx.x - before - nbp) * W;           // < n: this role has a chunk left (see above)
     JobAppend<1> app;
     auto job_of = [&](const int k) -> uint32_t { return job_list[slot0 + 256u * k + threadIdx.x]; };
     #pragma unroll 1
@@ -1662,7 +2145,7 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         // 3. DP over the rest.  Every kernel puts the jobs it does not settle on the list of the launch that takes them next (JobAppend).
         const int32_t G = sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go;
         const bool third = !(b.algo & NVBIO_ALN_NO_THIRD_CHANCE);
-        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *counts;
+        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *list_p, *counts;
         ScratchBlock aux;
         NVB_CHECK( aux.alloc_layout( "banded_job_list", s, "banded score: out of device memory for the job list", [&](ScratchLayout& c)
         {
@@ -1670,17 +2153,21 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
             job_list = c.take<uint32_t>( b.n );                                              // the DP's jobs
             list_s   = c.take<uint32_t>( b.n );                                              // second-chance jobs
             list_t   = c.take<uint32_t>( b.n );                                              // third-chance / gap-chance jobs
-            counts   = c.take<uint32_t>( 3 * JOB_COUNT_STRIDE );                             // the three lists' lengths, a 128-byte line each
+            list_p   = c.take<uint32_t>( (b.n + 1u) / 2u );                                  // the gap chance's pairs (the lower job of each)
+            counts   = c.take<uint32_t>( JOB_LIST_COUNT * JOB_COUNT_STRIDE );                // the four lists' lengths, a 128-byte line each
         } ) );
-        const JobLists out = { job_list, list_s, list_t, counts };
+        const JobLists out = { job_list, list_s, list_t, list_p, counts };
         const uint32_t* job_count = counts;
         const uint32_t* count_s   = counts + JOB_COUNT_STRIDE;
         const uint32_t* count_t   = counts + 2u * JOB_COUNT_STRIDE;
+        const uint32_t* count_p   = counts + 3u * JOB_COUNT_STRIDE;
         // the jobs a chance can still settle, each list through its own launch; every job ends as 0 or 1.
         //   out.second: need_dp == 3, the second chance.
         //   out.third:  the gap chance's jobs -- need_dp == 4 (no diagonal in reach of the other chances: reads with an indel, mostly) and
         //               need_dp == 2 (third-chance jobs: the gap chance evaluates what the third chance only rules out, with the job's best diagonal as
         //               one more class) -- or, without the gap chance (qualities, NVBIO_ALN_NO_GAP_CHANCE), need_dp == 2 for the third chance.
+        //   out.pairs:  two need_dp == 4 jobs that are partners (gap_pair_role) as ONE entry, the lower job's id; neither is on out.third.
+        //               The gap chance's launch takes them with out.third (NVBIO_ALN_NO_PAIRED_GAP_CHANCE: the first pass makes no pairs).
         // A flag whose launch does not follow (NVBIO_ALN_NO_THIRD_CHANCE: 2; neither launch: none at all) is not in the mask: the first pass hands
         // those jobs to the DP.  (NVBIO_ALN_NO_SECOND_CHANCE keeps the first pass from flagging any 3.)
         const bool gapc = !by_quality && !(b.algo & NVBIO_ALN_NO_GAP_CHANCE);
@@ -1689,7 +2176,7 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         const bool fused = gapc && third && !(b.algo & (NVBIO_ALN_NO_SECOND_CHANCE | NVBIO_ALN_SPLIT_CHANCES));
         const GapLadder lad = gap_ladder( P, G, sc.pat_go, sc.pat_ge );
         const dim3 grid( job_list_grid( b.n ) ), block( 256 );
-        NVB_HIP( hipMemsetAsync( counts, 0, 3 * JOB_COUNT_STRIDE * sizeof(uint32_t), s ) );
+        NVB_HIP( hipMemsetAsync( counts, 0, JOB_LIST_COUNT * JOB_COUNT_STRIDE * sizeof(uint32_t), s ) );
         if (by_quality)
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0,true>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                    (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
@@ -1697,16 +2184,16 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                    (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
         if (fused)
-            NVB_CHECK( NVB_LAUNCH( (chances_e2e31_kernel<RB>), dim3( job_list_grid( b.n ) + 1u ), block, s, b, P, G, lad, sc.pat_go, sc.pat_ge, scores, sinks,
-                                   need_dp, (const uint32_t*)list_s, count_s, (const uint32_t*)list_t, count_t, out ) );
+            NVB_CHECK( NVB_LAUNCH( (chances_e2e31_kernel<RB>), dim3( job_list_grid( b.n ) + 2u ), block, s, b, P, G, lad, sc.pat_go, sc.pat_ge, scores, sinks,
+                                   need_dp, (const uint32_t*)list_s, count_s, (const uint32_t*)list_t, count_t, (const uint32_t*)list_p, count_p, out ) );
         else
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                    (const uint32_t*)list_s, count_s, SchemeDev{}, out, 0u ) );
         if (fused)
             ;                                                        // (list_t went through the launch above)
         else if (gapc)
-            NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), grid, block, s, b, P, lad, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)list_t, count_t, out ) );
+            NVB_CHECK( NVB_LAUNCH( (gap_chance_e2e31_kernel<RB>), dim3( job_list_grid( b.n ) + 1u ), block, s, b, P, lad, sc.pat_go, sc.pat_ge, scores, sinks,
+                                   need_dp, (const uint32_t*)list_t, count_t, (const uint32_t*)list_p, count_p, out ) );
         else if (third)
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,2>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
                                    (const uint32_t*)list_t, count_t, SchemeDev{}, out, 0u ) );
@@ -1847,6 +2334,15 @@ extern "C" nvbio_status nvbio_banded_gotoh_score(int device, uint32_t band, nvbi
     if (b.n == 0) return NVBIO_OK;
     NVB_REQUIRE( scores_dev && sinks_dev, "NULL output pointer" );
     return banded_score( device, band, type, scheme_dev( scheme ), b, batch, scores_dev, sinks_dev, stream );
+}
+
+extern "C" nvbio_status nvbio_banded_gap_pairs(int device, const nvbio_alignment_batch* batch, uint32_t* partner_dev, void* stream)
+{
+    BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
+    if (b.n == 0) return NVBIO_OK;
+    NVB_REQUIRE( partner_dev != nullptr, "NULL output pointer" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return NVB_LAUNCH( gap_pairs_kernel, dim3( (b.n + 255u) / 256u ), dim3( 256 ), (hipStream_t)stream, b, partner_dev );
 }
 
 extern "C" nvbio_status nvbio_banded_gotoh_score_staged(int device, uint32_t band, nvbio_alignment_type type,
