@@ -85,7 +85,8 @@ inline uint32_t band_length(const uint32_t max_dist)                 // Aligner:
 
 // stored_reads4_dev: the reads as nvBowtie stores them (io::REVERSE), 4-bit packed, read r at symbols [r * read_len, (r+1) * read_len).
 // scheme + min_score: the edit-distance scheme (0,-1,-1,-1) with min_score = -max_dist is the mode as the reference ships it
-// (aligner_all_ed.cu:37, scoring.h:165,181).
+// (aligner_all_ed.cu:37, scoring.h:165,181).  n_reads * read_len must stay below 2^32 (the read index is 32-bit): std::invalid_argument otherwise,
+// before anything is launched or written.
 inline AllMappingStats all_mapping(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads4_dev,
                                    uint32_t n_reads, uint32_t read_len, const nvbio_sw_scheme& scheme, int32_t min_score, const AllMappingParams& prm,
                                    const AllMappingOutput& out, hipStream_t stream, const AllMappingCallback& on_chunk = AllMappingCallback())
@@ -93,10 +94,11 @@ inline AllMappingStats all_mapping(int device, nvbio_fm_index_t fmi, const uint3
     using namespace detail;
     AllMappingStats stats;
     const uint32_t R = n_reads, M = read_len;
+    const std::vector<uint32_t> ri = uniform_read_index( R, M );
     if (R == 0 || M == 0) return stats;
     hip( hipSetDevice( device ) );
     const uint32_t L = prm.seed_len < M ? prm.seed_len : M;
-    const uint32_t S = prm.seed_freq ? prm.seed_freq : (uint32_t)(int32_t)(1.0f + 1.15f * sqrtf( (float)M ));      // SimpleFunc (params.h:87-100)
+    const uint32_t S = seed_interval( M, prm.seed_freq );
     const uint32_t first = prm.max_reseed * (S / (prm.max_reseed + 1u));
     const uint32_t max_seeds = M / S;                                                                               // aligner_all.h:72-74
     const uint32_t band = prm.band ? prm.band : band_length( prm.max_dist );
@@ -117,22 +119,13 @@ inline AllMappingStats all_mapping(int device, nvbio_fm_index_t fmi, const uint3
     DevBuf read_index( 4ull * (R + 1) ), offs( 4ull * R ), fw( 8ull * R * spr_max ), rc( 8ull * R * spr_max ), slots( 16ull * R * spr_max ), tmp( tmp_bytes ),
            h_read( 4ull * H ), h_seed( 4ull * H ), h_loc( 4ull * H ), pos( 4ull * H ), j_read( 4ull * H ), j_flags( H ), j_wb( 4ull * H ), j_we( 4ull * H ),
            j_scores( 4ull * H ), j_sinks( 8ull * H ), c_read( 4ull * H ), c_rc( H ), c_loc( 4ull * H ), c_score( 4ull * H ), t_scores( 4ull * Hc ),
-           t_src( 8ull * Hc ), t_sink( 8ull * Hc ), t_ed( 4ull * Hc ), t_cig( 2ull * Hc * cs ), t_lens( 4ull * Hc ), t_mds( Hc * ms ), t_mdslens( 4ull * Hc ),
-           counters( 32 );
-    uint64_t* h_counters = nullptr; hip( hipHostMalloc( (void**)&h_counters, 32, hipHostMallocDefault ) );
-    struct Pinned { uint64_t* p; ~Pinned() { (void)hipHostFree( p ); } } pinned = { h_counters };
-    uint64_t* d_n_hits = counters.as<uint64_t>(); uint64_t* d_count = d_n_hits + 1; uint32_t* d_n_unique = (uint32_t*)(d_n_hits + 2);
-    auto fetch = [&]() {
-        hip( hipMemcpyAsync( h_counters, counters.p, 32, hipMemcpyDeviceToHost, stream ) );
-        hip( hipStreamSynchronize( stream ) );
-    };
-    {   // the read batch's sequence_index
-        std::vector<uint32_t> ri( R + 1 );
-        for (uint32_t r = 0; r <= R; ++r) ri[r] = r * M;
-        hip( hipMemcpyAsync( read_index.p, ri.data(), 4ull * (R + 1), hipMemcpyHostToDevice, stream ) );
-        hip( hipMemsetAsync( counters.p, 0, 32, stream ) );
-        hip( hipStreamSynchronize( stream ) );
-    }
+           t_src( 8ull * Hc ), t_sink( 8ull * Hc ), t_ed( 4ull * Hc ), t_cig( 2ull * Hc * cs ), t_lens( 4ull * Hc ), t_mds( Hc * ms ), t_mdslens( 4ull * Hc );
+    const Counters<uint64_t> counters( 32 );
+    const uint64_t* h_counters = counters.host;
+    uint64_t* d_n_hits = counters.dev.as<uint64_t>(); uint64_t* d_count = d_n_hits + 1; uint32_t* d_n_unique = (uint32_t*)(d_n_hits + 2);
+    auto fetch = [&]() { counters.fetch( stream, 4 ); };
+    hip( hipMemsetAsync( counters.dev.p, 0, 32, stream ) );
+    upload( read_index, ri, stream );                                                                               // the read batch's sequence_index
 
     const uint32_t n_passes = prm.per_seed_passes ? spr_all : 1u;
     for (uint32_t pass = 0; pass < n_passes; ++pass)

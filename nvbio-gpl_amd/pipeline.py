@@ -16,7 +16,9 @@ import math
 import numpy as np
 
 from . import (ALN_RAGGED_READS, FM_COMPLEMENT, FM_SCAN_FORWARD, LOCAL, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
-               BatchedBandedAlignmentScore, FMIndexFilter, GotohAligner, GotohScheme, PackedStringSet)
+               BatchedBandedAlignmentScore, FMIndexFilter, GotohAligner, GotohScheme, HitQueues, PackedStringSet, RaggedSeedLayout, SeedHitsParams,
+               best_approx_init_ragged, read_queue_begin_ragged, score_reduce_effort, score_reduce_effort_ragged, score_stream_flatten, score_stream_output,
+               seed_hits_loc, seed_hits_map, seed_hits_map_ragged, seed_hits_select)
 
 
 class SeedExtendParams:
@@ -686,74 +688,104 @@ def _ragged_tables(stored_reads, params, nvb):
     return off.astype(np.uint32), S.astype(np.int32), worst, Mmax, spr_of
 
 
-def _nvbowtie_best_approx_ragged(fmi, genome2, genome_len, stored_reads, params, nvb, stats):
-    """nvbowtie_best_approx over a ragged ReadBatch: every read its own seed interval, first offset, seed count, DP window, distinct distance and
-    worst score (map_kernel works per lane, mapping_inl.h:504-529); reads shorter than max( min_read_len, seed_len ) are filtered"""
+def _check_uniform_batch(n_reads, read_len):
+    """read r of a uniform batch starts at symbol r * read_len and the read index is 32-bit (as in host/nvbio_amd/best_approx.hpp)"""
+    if n_reads * read_len >= 2 ** 32:
+        raise ValueError("n_reads * read_len must stay below 2^32 symbols (the read index is 32-bit): split the batch")
+
+
+def _best_dict(best, best_rc, **counters):
+    """the loops' return value: best int32 [R, 4] = (a1 score, a1 locus, a2 score, a2 locus), best_rc = a1 strand | a2 strand << 1; locus -1 = none"""
     import torch
-    from . import (FM_COMPLEMENT, FM_SCAN_FORWARD, AlignmentBatch, BatchedBandedAlignmentScore, GotohAligner, HitQueues, PackedStringSet, RaggedSeedLayout,
-                   SeedHitsParams, best_approx_init_ragged, read_queue_begin_ragged, score_reduce_effort_ragged, score_stream_flatten, score_stream_output,
-                   seed_hits_loc, seed_hits_map_ragged, seed_hits_select)
-    dev = fmi.device
-    R, L = stored_reads.n, nvb.seed_len
-    off_h, S_h, worst_h, Mmax, spr_of = _ragged_tables(stored_reads, params, nvb)
-    read_index = stored_reads.offsets.to(torch.int32).contiguous()
-    intervals = torch.from_numpy(S_h).to(dev)
-    best = torch.empty((R, 4), dtype=torch.int32, device=dev)
-    best_rc = torch.zeros(R, dtype=torch.uint8, device=dev)
-    best_approx_init_ragged(torch.from_numpy(worst_h).to(dev), best, best_rc)
-    trys = torch.zeros(R, dtype=torch.int32, device=dev)
-    aligner = GotohAligner(params.aln_type, params.scheme)
-    queue = torch.arange(R, device=dev, dtype=torch.int32)
-    n_extensions = passes = 0
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    for seeding_pass in range(nvb.max_reseed + 1):
-        nq = queue.numel()
-        spr = spr_of[seeding_pass]
-        if nq == 0 or spr == 0:                                       # (first_r grows with the pass: no seed slot now, none later)
-            break
-        lay = RaggedSeedLayout(read_index, intervals, spr, seeding_pass, nvb.max_reseed, L, nvb.min_read_len)
-        sp = SeedHitsParams(spr, 0, L, Mmax, max_hits=nvb.max_hits, rep_seeds=nvb.rep_seeds, max_effort=nvb.max_effort, min_ext=nvb.min_ext, max_ext=nvb.max_ext)
-        cap = sp.capacity()
-        offs = torch.empty(nq * spr, dtype=torch.int32, device=dev)
-        active = torch.empty(nq, dtype=torch.int32, device=dev)
-        read_queue_begin_ragged(queue, nq, lay, int(off_h[-1]), nvb.top_seed, nvb.max_effort_init, offs, active, trys)
-        qs = PackedStringSet(stored_reads.reads4, 4, nq * spr, offsets=offs, fixed_len=L, stride=0, device=dev)
-        fw = fmi.match(qs, FM_SCAN_FORWARD)
-        rc = fmi.match(qs, FM_COMPLEMENT)
-        deques = torch.zeros((R, cap, 2), dtype=torch.int32, device=dev)
-        sizes = torch.zeros(R, dtype=torch.int32, device=dev)
-        reseed = torch.zeros(R, dtype=torch.uint8, device=dev)
-        seed_hits_map_ragged(fw, rc, lay, nq, nvb.max_hits, nvb.rep_seeds, deques, sizes, reseed, read_queue=queue)
-        n_ext = 0
-        while active.numel() and n_ext < nvb.max_ext:
-            na = active.numel()
-            hits = HitQueues(torch.empty(na, dtype=torch.int32, device=dev), torch.empty(na, dtype=torch.int32, device=dev),
-                             torch.empty(na, dtype=torch.int32, device=dev), device=dev)
-            active_out = torch.empty(na, dtype=torch.int32, device=dev)
-            seed_hits_select(active, trys, sp, deques, sizes, hits, active_out, count)
-            nh = int(count.item())
-            if nh == 0:
-                break
-            active = active_out[:nh].contiguous()
-            hits.n = nh
-            pos = fmi.locate(hits.loc[:nh].contiguous())
-            seed_hits_loc(pos, hits)
-            rid, flags, wb, we = score_stream_flatten(hits, read_index, nvb.band, genome_len, reads_reversed=True)
-            batch = AlignmentBatch(stored_reads.reads4, 4, read_index, genome2, 2, wb, we, quals=stored_reads.quals, read_id=rid, flags=flags,
-                                   device=dev, max_read_len=Mmax, algo_flags=ALN_RAGGED_READS)
-            scores, sinks = BatchedBandedAlignmentScore(nvb.band, aligner).enact(batch)
-            score_stream_output(hits, scores, sinks, wb)
-            score_reduce_effort_ragged(active, hits, read_index, n_ext, sp, best, best_rc, trys, sizes)
-            n_ext += 1
-            n_extensions += nh
-            passes += 1
-        queue = queue[reseed[queue.to(torch.int64)] != 0].contiguous()
-    if stats is not None:
-        stats.update(n_extensions=n_extensions, passes=passes)
     b = best.to(torch.int64)
     loc = lambda c: torch.where(b[:, c] == -1, b[:, c], b[:, c] & 0xFFFFFFFF)
     return dict(best_score=best[:, 0].clone(), best_loc=loc(1), best_rc=(best_rc & 1), second_score=best[:, 2].clone(), second_loc=loc(3),
-                second_rc=((best_rc >> 1) & 1), n_extensions=n_extensions, passes=passes)
+                second_rc=((best_rc >> 1) & 1), **counters)
+
+
+class _UniformLayout:
+    """what nvbowtie_best_approx's loop needs to know about a batch of reads of ONE length: read r at symbols [r M, (r + 1) M), one seed interval,
+    first offset, seed count and worst score for all"""
+
+    def __init__(self, fmi, reads, params, nvb):
+        import torch
+        self.R, self.M = reads.n, reads.read_len
+        _check_uniform_batch(self.R, self.M)
+        self.dev, self.reads, self.nvb = fmi.device, reads, nvb
+        dev = self.dev
+        self.L = min(nvb.seed_len, self.M)
+        self.S = nvb.seed_freq or params.interval_for(self.M)
+        self.worst = params.min_score_for(self.M)                     # init_alignments( reads, threshold_score, ... ) (aligner_best_approx.h:77)
+        self.read_index = torch.arange(self.R + 1, device=dev, dtype=torch.int32) * self.M
+        self.batch_args = dict(max_read_len=self.M)
+
+    def init(self, best, best_rc):
+        best[:, 0] = self.worst; best[:, 2] = self.worst; best[:, 1] = -1; best[:, 3] = -1
+
+    def plan(self, seeding_pass):
+        """-> this seeding pass's SeedHitsParams, or None when no read has a seed slot left"""
+        nvb, M, L, S = self.nvb, self.M, self.L, self.S
+        self.first = seeding_pass * (S // (nvb.max_reseed + 1))
+        self.spr = (M - L - self.first) // S + 1 if M >= L + self.first else 0
+        if self.spr <= 0:
+            return None
+        return SeedHitsParams(self.spr, S, L, M, first_offset=self.first, max_hits=nvb.max_hits, rep_seeds=nvb.rep_seeds, max_effort=nvb.max_effort,
+                              min_ext=nvb.min_ext, max_ext=nvb.max_ext)
+
+    def begin(self, queue, nq, trys):
+        """-> the seeds of the queued reads as the string set of the two match_range calls, and the active queue (select_init)"""
+        import torch
+        offs = (queue.to(torch.int64) * self.M + self.first).to(torch.int32).contiguous()
+        trys.fill_(self.nvb.max_effort_init)
+        active = (queue | (self.nvb.top_seed << 31)).contiguous()
+        return PackedStringSet(self.reads.reads4, 4, nq * self.spr, offsets=offs, fixed_len=self.L, stride=self.M, device=self.dev, seeds_per_string=self.spr,
+                               seed_interval=self.S), active
+
+    def map(self, fw, rc, sp, queue, nq, deques, sizes, reseed):
+        seed_hits_map(fw, rc, sp, nq, deques, sizes, reseed, read_queue=queue)
+
+    def reduce(self, active, hits, n_ext, sp, best, best_rc, trys, sizes):
+        score_reduce_effort(active, hits, self.M, n_ext, sp, best, best_rc, trys, sizes)
+
+
+class _RaggedLayout:
+    """the same for a ragged ReadBatch: every read its own seed interval, first offset, seed count, DP window, distinct distance and worst score
+    (map_kernel works per lane, mapping_inl.h:504-529); reads shorter than max( min_read_len, seed_len ) are filtered"""
+
+    def __init__(self, fmi, reads, params, nvb):
+        import torch
+        self.dev, self.reads, self.nvb, self.R, self.L = fmi.device, reads, nvb, reads.n, nvb.seed_len
+        dev = self.dev
+        self.off_h, S_h, worst_h, self.Mmax, self.spr_of = _ragged_tables(reads, params, nvb)
+        self.read_index = reads.offsets.to(torch.int32).contiguous()
+        self.intervals = torch.from_numpy(S_h).to(dev)
+        self.worst = torch.from_numpy(worst_h).to(dev)
+        self.batch_args = dict(max_read_len=self.Mmax, algo_flags=ALN_RAGGED_READS)
+
+    def init(self, best, best_rc):
+        best_approx_init_ragged(self.worst, best, best_rc)
+
+    def plan(self, seeding_pass):
+        nvb = self.nvb
+        self.spr = self.spr_of[seeding_pass]
+        if self.spr == 0:                                             # (first_r grows with the pass: no seed slot now, none later)
+            return None
+        self.lay = RaggedSeedLayout(self.read_index, self.intervals, self.spr, seeding_pass, nvb.max_reseed, self.L, nvb.min_read_len)
+        return SeedHitsParams(self.spr, 0, self.L, self.Mmax, max_hits=nvb.max_hits, rep_seeds=nvb.rep_seeds, max_effort=nvb.max_effort, min_ext=nvb.min_ext,
+                              max_ext=nvb.max_ext)
+
+    def begin(self, queue, nq, trys):
+        import torch
+        offs = torch.empty(nq * self.spr, dtype=torch.int32, device=self.dev)
+        active = torch.empty(nq, dtype=torch.int32, device=self.dev)
+        read_queue_begin_ragged(queue, nq, self.lay, int(self.off_h[-1]), self.nvb.top_seed, self.nvb.max_effort_init, offs, active, trys)
+        return PackedStringSet(self.reads.reads4, 4, nq * self.spr, offsets=offs, fixed_len=self.L, stride=0, device=self.dev), active
+
+    def map(self, fw, rc, sp, queue, nq, deques, sizes, reseed):
+        seed_hits_map_ragged(fw, rc, self.lay, nq, self.nvb.max_hits, self.nvb.rep_seeds, deques, sizes, reseed, read_queue=queue)
+
+    def reduce(self, active, hits, n_ext, sp, best, best_rc, trys, sizes):
+        score_reduce_effort_ragged(active, hits, self.read_index, n_ext, sp, best, best_rc, trys, sizes)
 
 
 def nvbowtie_best_approx(fmi, genome2, genome_len, stored_reads, params, nvb=None, stats=None):
@@ -764,55 +796,40 @@ def nvbowtie_best_approx(fmi, genome2, genome_len, stored_reads, params, nvb=Non
     in arrival order, counting failed extensions, until a read's hits or its effort run out.  One hit per read and pass (the
     reference switches to several once fewer than half a batch of reads are active: an optimisation that changes no rule but
     the order effort runs out in).  Every data-parallel step is a kernel behind the C ABI; this function is the host loop.
-    stored_reads: ReadBatch of reads stored REVERSED, as nvBowtie loads them (io::REVERSE, nvBowtie.cpp:322).  A ragged batch (offsets) takes
-    the ragged route: per-read seed interval, first offset, window, distinct distance and worst score; reads shorter than
-    max( nvb.min_read_len, seed_len ) are not seeded and end unaligned; no read may reach 1024 symbols (ValueError).
+    stored_reads: ReadBatch of reads stored REVERSED, as nvBowtie loads them (io::REVERSE, nvBowtie.cpp:322).  The loop is written once; what
+    differs between reads of one length and a ragged batch (offsets) comes from a layout object (_UniformLayout, _RaggedLayout): the host tables,
+    how a seeding pass begins and maps its seeds, the reduce call and the DP batch's arguments.  The ragged route: per-read seed interval, first
+    offset, window, distinct distance and worst score; reads shorter than max( nvb.min_read_len, seed_len ) are not seeded and end unaligned; no
+    read may reach 1024 symbols (ValueError).  The uniform route: n_reads * read_len must stay below 2^32 (ValueError, before the device is touched).
     Returns dict(best_score, best_loc, best_rc, second_score, second_loc, second_rc) (loc = hit.loc, the diagonal's locus; -1 = none),
     n_extensions, passes."""
     import torch
-    from . import (FM_COMPLEMENT, FM_SCAN_FORWARD, AlignmentBatch, BatchedBandedAlignmentScore, GotohAligner, HitQueues, PackedStringSet,
-                   SeedHitsParams, score_reduce_effort, score_stream_flatten, score_stream_output, seed_hits_loc, seed_hits_map, seed_hits_select)
     nvb = nvb or NvBowtieParams()
-    if stored_reads.offsets is not None:                              # reads of different lengths: every read its own seeds, window and thresholds
-        return _nvbowtie_best_approx_ragged(fmi, genome2, genome_len, stored_reads, params, nvb, stats)
+    layout = (_UniformLayout if stored_reads.offsets is None else _RaggedLayout)(fmi, stored_reads, params, nvb)
     dev = fmi.device
-    R, M = stored_reads.n, stored_reads.read_len
-    L = min(nvb.seed_len, M)
-    S = nvb.seed_freq or params.interval_for(M)
-    retry_stride = S // (nvb.max_reseed + 1)
-    worst = params.min_score_for(M)                                   # init_alignments( reads, threshold_score, ... ) (aligner_best_approx.h:77)
+    R = stored_reads.n
     best = torch.empty((R, 4), dtype=torch.int32, device=dev)
-    best[:, 0] = worst; best[:, 2] = worst; best[:, 1] = -1; best[:, 3] = -1
     best_rc = torch.zeros(R, dtype=torch.uint8, device=dev)
-    trys = torch.empty(R, dtype=torch.int32, device=dev)
-    read_index = torch.arange(R + 1, device=dev, dtype=torch.int32) * M
+    layout.init(best, best_rc)
+    trys = torch.zeros(R, dtype=torch.int32, device=dev)
     aligner = GotohAligner(params.aln_type, params.scheme)
     queue = torch.arange(R, device=dev, dtype=torch.int32)           # seed_queues: the reads of this seeding pass
     n_extensions = passes = 0
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     for seeding_pass in range(nvb.max_reseed + 1):
         nq = queue.numel()
-        if nq == 0:
+        sp = layout.plan(seeding_pass) if nq else None
+        if sp is None:
             break
-        first = seeding_pass * retry_stride
-        spr = (M - L - first) // S + 1 if M >= L + first else 0
-        if spr <= 0:
-            break
-        sp = SeedHitsParams(spr, S, L, M, first_offset=first, max_hits=nvb.max_hits, rep_seeds=nvb.rep_seeds, max_effort=nvb.max_effort,
-                            min_ext=nvb.min_ext, max_ext=nvb.max_ext)
-        cap = sp.capacity()
-        # the two match_range calls of the exact mapper over the seeds of the queued reads
-        offs = (queue.to(torch.int64) * M + first).to(torch.int32).contiguous()
-        qs = PackedStringSet(stored_reads.reads4, 4, nq * spr, offsets=offs, fixed_len=L, stride=M, device=dev, seeds_per_string=spr, seed_interval=S)
+        # the two match_range calls of the exact mapper over the seeds of the queued reads, the deques
+        qs, active = layout.begin(queue, nq, trys)
         fw = fmi.match(qs, FM_SCAN_FORWARD)
         rc = fmi.match(qs, FM_COMPLEMENT)
-        deques = torch.zeros((R, cap, 2), dtype=torch.int32, device=dev)
+        deques = torch.zeros((R, sp.capacity(), 2), dtype=torch.int32, device=dev)
         sizes = torch.zeros(R, dtype=torch.int32, device=dev)
         reseed = torch.zeros(R, dtype=torch.uint8, device=dev)
-        seed_hits_map(fw, rc, sp, nq, deques, sizes, reseed, read_queue=queue)
+        layout.map(fw, rc, sp, queue, nq, deques, sizes, reseed)
         # the extension loop (best_approx_score)
-        trys.fill_(nvb.max_effort_init)                               # select_init
-        active = (queue | (nvb.top_seed << 31)).contiguous()
         n_ext = 0
         while active.numel() and n_ext < nvb.max_ext:
             na = active.numel()
@@ -827,22 +844,19 @@ def nvbowtie_best_approx(fmi, genome2, genome_len, stored_reads, params, nvb=Non
             hits.n = nh
             pos = fmi.locate(hits.loc[:nh].contiguous())
             seed_hits_loc(pos, hits)
-            rid, flags, wb, we = score_stream_flatten(hits, read_index, nvb.band, genome_len, reads_reversed=True)
-            batch = AlignmentBatch(stored_reads.reads4, 4, read_index, genome2, 2, wb, we, quals=stored_reads.quals, read_id=rid, flags=flags,
-                                   device=dev, max_read_len=M)
+            rid, flags, wb, we = score_stream_flatten(hits, layout.read_index, nvb.band, genome_len, reads_reversed=True)
+            batch = AlignmentBatch(stored_reads.reads4, 4, layout.read_index, genome2, 2, wb, we, quals=stored_reads.quals, read_id=rid, flags=flags,
+                                   device=dev, **layout.batch_args)
             scores, sinks = BatchedBandedAlignmentScore(nvb.band, aligner).enact(batch)
             score_stream_output(hits, scores, sinks, wb)
-            score_reduce_effort(active, hits, M, n_ext, sp, best, best_rc, trys, sizes)
+            layout.reduce(active, hits, n_ext, sp, best, best_rc, trys, sizes)
             n_ext += 1
             n_extensions += nh
             passes += 1
         queue = queue[reseed[queue.to(torch.int64)] != 0].contiguous()       # the reads that asked for reseeding go round again
     if stats is not None:
         stats.update(n_extensions=n_extensions, passes=passes)
-    b = best.to(torch.int64)
-    loc = lambda c: torch.where(b[:, c] == -1, b[:, c], b[:, c] & 0xFFFFFFFF)
-    return dict(best_score=best[:, 0].clone(), best_loc=loc(1), best_rc=(best_rc & 1), second_score=best[:, 2].clone(), second_loc=loc(3),
-                second_rc=((best_rc >> 1) & 1), n_extensions=n_extensions, passes=passes)
+    return _best_dict(best, best_rc, n_extensions=n_extensions, passes=passes)
 
 
 # ---- the same loop as a C++ host loop over the C ABI (host/nvbio_amd/best_approx.hpp behind lib/libnvbio_amd_host.so) --------------------------
@@ -881,68 +895,60 @@ def _host_structs():
 _HostParams, _HostStats = _host_structs()
 
 
-def host_best_approx_ragged_into(fmi, genome2, genome_len, stored_reads, params, nvb, batch_size, multi_hit, best, best_rc):
-    """nvbio_host_best_approx_ragged (host/nvbio_amd/best_approx.hpp: best_approx_ragged) into the caller's best int32 [R, 4] / best_rc uint8 [R]:
-    the offsets go to the C++ loop on the HOST, with every read's worst score; the loop evaluates seed_freq( M_r ) itself (S(1, 1.15) unless
-    nvb.seed_freq or params.seed_interval fixes one).  Raises RuntimeError, having launched and written nothing, for a read of 1024 symbols or more.
-    Returns the loop's counters."""
+def _host_params(nvb, seed_freq, batch_size, multi_hit):
+    return _HostParams(nvb.seed_len, seed_freq, nvb.max_hits, nvb.rep_seeds, nvb.max_effort, nvb.max_effort_init, nvb.min_ext, nvb.max_ext, nvb.max_reseed,
+                       nvb.band, nvb.top_seed, int(batch_size), 1 if multi_hit else 0)
+
+
+def host_best_approx_into(fmi, genome2, genome_len, stored_reads, params, nvb, batch_size, multi_hit, best, best_rc):
+    """the C++ host loop (host/nvbio_amd/best_approx.hpp) into the caller's best int32 [R, 4] / best_rc uint8 [R]: nvbio_host_best_approx for reads of
+    one length, nvbio_host_best_approx_ragged for a ragged ReadBatch (offsets).  To the ragged entry the offsets go on the HOST, with every read's
+    worst score; the loop evaluates seed_freq( M_r ) itself (S(1, 1.15) unless nvb.seed_freq or params.seed_interval fixes one).  Raises RuntimeError,
+    having launched and written nothing, for a ragged read of 1024 symbols or more or a uniform batch of 2^32 symbols or more.  Returns the
+    loop's counters."""
     import ctypes
     from . import FMIndex, _ptr, _stream_ptr
     dev = fmi.device
-    R = stored_reads.n
-    off = np.ascontiguousarray(stored_reads.offsets.detach().cpu().numpy().astype(np.uint32))
-    lens = np.diff(off.astype(np.int64))
-    if len(off) != R + 1:
-        raise ValueError("offsets must hold n_reads + 1 symbol offsets")
-    Mmax = int(lens.max()) if R else 0
-    worst = np.ascontiguousarray(params.min_score_table(Mmax)[np.clip(lens, 0, Mmax)].astype(np.int32))
-    p = _HostParams(nvb.seed_len, nvb.seed_freq or params.seed_interval or 0, nvb.max_hits, nvb.rep_seeds, nvb.max_effort, nvb.max_effort_init, nvb.min_ext,
-                    nvb.max_ext, nvb.max_reseed, nvb.band, nvb.top_seed, int(batch_size), 1 if multi_hit else 0)
+    R, M = stored_reads.n, stored_reads.read_len
     st = _HostStats()
-    rc = _host_lib().nvbio_host_best_approx_ragged(
-        ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_reads.reads4), _ptr(stored_reads.quals),
-        ctypes.c_uint32(R), off.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c),
-        worst.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(nvb.min_read_len), ctypes.byref(p), _ptr(best), _ptr(best_rc), _stream_ptr(dev), ctypes.byref(st))
+    head = (ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_reads.reads4), _ptr(stored_reads.quals),
+            ctypes.c_uint32(R))
+    tail = (_ptr(best), _ptr(best_rc), _stream_ptr(dev), ctypes.byref(st))
+    kind = (ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c))
+    if stored_reads.offsets is None:
+        p = _host_params(nvb, nvb.seed_freq or params.interval_for(M), batch_size, multi_hit)
+        rc = _host_lib().nvbio_host_best_approx(*head, ctypes.c_uint32(M), *kind, ctypes.c_int32(params.min_score_for(M)), ctypes.byref(p), *tail)
+    else:
+        off = np.ascontiguousarray(stored_reads.offsets.detach().cpu().numpy().astype(np.uint32))
+        lens = np.diff(off.astype(np.int64))
+        if len(off) != R + 1:
+            raise ValueError("offsets must hold n_reads + 1 symbol offsets")
+        Mmax = int(lens.max()) if R else 0
+        worst = np.ascontiguousarray(params.min_score_table(Mmax)[np.clip(lens, 0, Mmax)].astype(np.int32))
+        p = _host_params(nvb, nvb.seed_freq or params.seed_interval or 0, batch_size, multi_hit)
+        rc = _host_lib().nvbio_host_best_approx_ragged(*head, off.ctypes.data_as(ctypes.c_void_p), *kind, worst.ctypes.data_as(ctypes.c_void_p),
+                                                       ctypes.c_uint32(nvb.min_read_len), ctypes.byref(p), *tail)
     if rc != 0:
         raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
     return st
+
+
+host_best_approx_ragged_into = host_best_approx_into                  # the name it had while it served ragged batches only
 
 
 def nvbowtie_best_approx_host(fmi, genome2, genome_len, stored_reads, params, nvb=None, batch_size=0, multi_hit=True):
     """nvbowtie_best_approx as the C++ host loop (nvbio_host_best_approx): every data-parallel step behind the C ABI, the loop in C++, two
     counters read per extension pass through pinned memory, queues allocated once -- and the reference's several-hits-per-read phase
     (aligner_best_approx.h:487-510; batch_size = its BATCH_SIZE, 0 = the number of reads).  Same return value as nvbowtie_best_approx.
-    A ragged ReadBatch (offsets) takes nvbio_host_best_approx_ragged: see host_best_approx_ragged_into."""
-    import ctypes
+    A ragged ReadBatch (offsets) takes nvbio_host_best_approx_ragged: see host_best_approx_into."""
     import torch
-    from . import FMIndex, _ptr, _stream_ptr
     nvb = nvb or NvBowtieParams()
-    dev = fmi.device
-    R, M = stored_reads.n, stored_reads.read_len
-    best = torch.empty((R, 4), dtype=torch.int32, device=dev)
-    best_rc = torch.zeros(R, dtype=torch.uint8, device=dev)
-    if stored_reads.offsets is not None:                              # reads of different lengths: nvbio_host_best_approx_ragged
-        st = host_best_approx_ragged_into(fmi, genome2, genome_len, stored_reads, params, nvb, batch_size, multi_hit, best, best_rc)
-        b = best.to(torch.int64)
-        loc = lambda c: torch.where(b[:, c] == -1, b[:, c], b[:, c] & 0xFFFFFFFF)
-        return dict(best_score=best[:, 0].clone(), best_loc=loc(1), best_rc=(best_rc & 1), second_score=best[:, 2].clone(), second_loc=loc(3),
-                    second_rc=((best_rc >> 1) & 1), n_extensions=int(st.n_extensions), passes=int(st.passes), multi_passes=int(st.multi_passes),
-                    seeding_passes=int(st.seeding_passes))
-    _P, _S = _HostParams, _HostStats
-    p = _P(nvb.seed_len, nvb.seed_freq or params.interval_for(M), nvb.max_hits, nvb.rep_seeds, nvb.max_effort, nvb.max_effort_init, nvb.min_ext, nvb.max_ext,
-           nvb.max_reseed, nvb.band, nvb.top_seed, int(batch_size), 1 if multi_hit else 0)
-    st = _S()
-    rc = _host_lib().nvbio_host_best_approx(
-        ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_reads.reads4), _ptr(stored_reads.quals),
-        ctypes.c_uint32(R), ctypes.c_uint32(M), ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c), ctypes.c_int32(params.min_score_for(M)),
-        ctypes.byref(p), _ptr(best), _ptr(best_rc), _stream_ptr(dev), ctypes.byref(st))
-    if rc != 0:
-        raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
-    b = best.to(torch.int64)
-    loc = lambda c: torch.where(b[:, c] == -1, b[:, c], b[:, c] & 0xFFFFFFFF)
-    return dict(best_score=best[:, 0].clone(), best_loc=loc(1), best_rc=(best_rc & 1), second_score=best[:, 2].clone(), second_loc=loc(3),
-                second_rc=((best_rc >> 1) & 1), n_extensions=int(st.n_extensions), passes=int(st.passes), multi_passes=int(st.multi_passes),
-                seeding_passes=int(st.seeding_passes))
+    R = stored_reads.n
+    best = torch.empty((R, 4), dtype=torch.int32, device=fmi.device)
+    best_rc = torch.zeros(R, dtype=torch.uint8, device=fmi.device)
+    st = host_best_approx_into(fmi, genome2, genome_len, stored_reads, params, nvb, batch_size, multi_hit, best, best_rc)
+    return _best_dict(best, best_rc, n_extensions=int(st.n_extensions), passes=int(st.passes), multi_passes=int(st.multi_passes),
+                      seeding_passes=int(st.seeding_passes))
 
 
 def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, stored_mates2, params, nvb=None, pe=None, unpaired=True, batch_size=0, multi_hit=True):
@@ -961,18 +967,13 @@ def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, st
     if stored_mates2.n != R:
         raise ValueError("the two mate batches must hold the same number of reads")
 
-    class _P(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_uint32) for k in ("seed_len", "seed_freq", "max_hits", "rep_seeds", "max_effort", "max_effort_init", "min_ext", "max_ext",
-                                                  "max_reseed", "band", "top_seed", "batch_size", "multi_hit")]
-
     class _PE(ctypes.Structure):
         _fields_ = [(k, ctypes.c_uint32) for k in ("policy", "min_frag_len", "max_frag_len", "overlap", "unpaired")]
 
     class _S(ctypes.Structure):
         _fields_ = [("n_extensions", ctypes.c_uint64), ("n_opposite", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("multi_passes", ctypes.c_uint32)]
 
-    p = _P(nvb.seed_len, nvb.seed_freq or 0, nvb.max_hits, nvb.rep_seeds, nvb.max_effort, nvb.max_effort_init, nvb.min_ext, nvb.max_ext, nvb.max_reseed, nvb.band,
-           nvb.top_seed, int(batch_size), 1 if multi_hit else 0)
+    p = _host_params(nvb, nvb.seed_freq or 0, batch_size, multi_hit)
     q = _PE(int(pe.policy), int(pe.min_frag_len), int(pe.max_frag_len), 1 if pe.overlap else 0, 1 if unpaired else 0)
     st = _S()
     best_a = torch.empty((R, 2, 4), dtype=torch.int32, device=dev)
