@@ -1139,6 +1139,8 @@ enum
     NVBIO_ALN_NO_PAIRED_GAP_CHANCE  = 262144, /* band-31 end-to-end scoring: the two windows of an indel read (adjacent jobs of one read and strand whose
                                                 windows lie 1..5 columns apart) as two gap-chance jobs instead of one that walks their shared
                                                 diagonals once (gap_chance_e2e31_pair) (A/B)                                                           */
+    NVBIO_ALN_NO_NARROW_DP          = 524288, /* band-31 end-to-end scoring: every DP job over all 31 columns; the first pass forms no classes of jobs whose
+                                                score bound U* confines the optimal paths to 13 or 17 columns (banded_gotoh_band31_pk_kernel, NARROW) (A/B) */
     NVBIO_ALN_NO_NARROW_TRACEBACK   = 64   /* band-31 end-to-end traceback: every DP over the whole band (no band-15 route for the jobs
                                               whose optimal paths provably stay within 7 diagonals of the sink)                  */
 };
@@ -1268,6 +1270,14 @@ nvbio_status nvbio_banded_gap_pairs(int device, const nvbio_alignment_batch* bat
 nvbio_status nvbio_banded_gotoh_score(int device, uint32_t band, nvbio_alignment_type type,
                                       const nvbio_gotoh_scheme* scheme, const nvbio_alignment_batch* batch,
                                       int32_t* scores_dev, nvbio_uint2* sinks_dev, void* stream);
+
+/* nvbio_banded_gotoh_score plus a report of the route each job took, one byte per job in routes_dev: 0 = settled before the DP (the ungapped
+ * shortcut or one of its chances), 1 = the DP over the full band, 2 = the DP's class A (columns 9..21), 3 = its class B (columns 7..23);
+ * +8 = a class job whose narrow run could not prove itself exact and which the full band redid.  Scores and sinks never depend on the route;
+ * the report exists so that a test can tell which body it exercised. */
+nvbio_status nvbio_banded_gotoh_score_routes(int device, uint32_t band, nvbio_alignment_type type,
+                                             const nvbio_gotoh_scheme* scheme, const nvbio_alignment_batch* batch,
+                                             int32_t* scores_dev, nvbio_uint2* sinks_dev, uint8_t* routes_dev, void* stream);
 
 /* The same through the reference's staged scheduler: BatchedBandedAlignmentScore<band, stream, DeviceStagedThreadScheduler>
  * (nvbio/alignment/batched_banded_inl.h:165-236; work unit StagedAlignmentUnitBase / BandedScoreUnit, batched_stream.h:117-285),

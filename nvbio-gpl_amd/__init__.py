@@ -41,6 +41,8 @@ ALN_NO_UNGAPPED_SCORE, ALN_NO_THIRD_CHANCE, ALN_NO_PACKED_DP, ALN_FORCE_PACKED_D
 ALN_NO_NARROW_TRACEBACK, ALN_NO_SECOND_CHANCE, ALN_PK_STRIPE8, ALN_NO_NARROW_SCORE, ALN_NO_BAND_ROUTE = 64, 128, 256, 512, 1024
 ALN_NO_QUALITY_SHORTCUT, ALN_RAGGED_READS, ALN_NO_LENGTH_SORT, ALN_NO_F16_DP, ALN_NO_COOPERATIVE_DP, ALN_NO_GAP_CHANCE = 2048, 4096, 8192, 16384, 32768, 65536
 ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE = 131072, 262144
+ALN_NO_NARROW_DP = 524288
+ROUTE_SETTLED, ROUTE_FULL_BAND, ROUTE_CLASS_A, ROUTE_CLASS_B, ROUTE_REDONE = 0, 1, 2, 3, 8
 DEFAULT_ALGO_FLAGS = 0          # what an AlignmentBatch is created with unless told otherwise (tests set it for a whole run)
 BACKTRACK_REFERENCE_QUIRKS = 1
 
@@ -1222,6 +1224,20 @@ class BatchedBandedAlignmentScore:
 def batch_banded_alignment_score(band_len, aligner, batch):
     """aln::batch_banded_alignment_score<BAND_LEN> (nvbio/alignment/batched.h:185, batched_inl.h:1046-1086)"""
     return BatchedBandedAlignmentScore(band_len, aligner).enact(batch)
+
+
+def banded_gotoh_score_routes(band_len, aligner, batch):
+    """nvbio_banded_gotoh_score_routes: (scores, sinks) as batch_banded_alignment_score plus one uint8 per job, the route it took:
+    ROUTE_SETTLED, ROUTE_FULL_BAND, ROUTE_CLASS_A or ROUTE_CLASS_B, + ROUTE_REDONE for a class job the full band had to redo"""
+    torch = _torch()
+    scores = torch.empty(batch.n, dtype=torch.int32, device=batch.device)
+    sinks = torch.empty((batch.n, 2), dtype=torch.int32, device=batch.device)
+    routes = torch.empty(batch.n, dtype=torch.uint8, device=batch.device)
+    bs = batch.c_struct()
+    _check(lib().nvbio_banded_gotoh_score_routes(FMIndex._dev_index(batch.device), ctypes.c_uint32(int(band_len)), ctypes.c_int(aligner.type),
+                                                 ctypes.byref(aligner.scheme.c), ctypes.byref(bs), _ptr(scores), _ptr(sinks), _ptr(routes),
+                                                 _stream_ptr(batch.device)))
+    return scores, sinks, routes
 
 
 GAP_PAIR_MAX_SHIFT = 5

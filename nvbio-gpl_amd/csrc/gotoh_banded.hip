@@ -280,22 +280,58 @@ __device__ __forceinline__ uint32_t even_bits64(uint64_t x)
 // size, their sums and maxima are exact there, the mismatch flag becomes 2^-7 (bit 13 of each half) against a penalty scaled by 128 in one
 // v_pk_fma_f16, and h = max( f, d, E ) is ONE v_pk_maximum3_f16: 9 operations per cell instead of 10.  (The -16384 stand-in for the reference's
 // infimum stays where it is under + GE: 16 is the spacing of binary16 there.)
-template <int TYPE, int RBITS, int MINW = 3, bool M0 = false, bool RAGGED = false, bool FP = false>
+// NARROW (the binary16 SEMI_GLOBAL build only; NVBIO_ALN_NO_NARROW_DP runs the build without it): ONE launch over three job lists.  The first pass
+// gives a job that leaves for the DP with a known best diagonal score L = U* (stashed in scores[job]) a class by L alone: with match = 0 every step
+// of a path scores <= 0, so every cell on a path holds H >= the path's final score; L is achievable, so the optimum is >= L and a cell with H < L
+// lies on no optimal path.  Standing delta columns off the best diagonal costs open + (delta - 1) ext, so for a window centred on that diagonal
+// (column 15) everything beyond +-r(L) of it is dead once the free-start paths of row 0 have died: class A = columns 9..21 (w <= 6), class B =
+// columns 7..23 (w <= 8).  A workgroup has one role, taken from blockIdx.x: the full list's workgroups come first, then class B's, then class A's
+// (the shortest jobs fill the tail).  A narrow job runs
+//   1. rows 0 .. NARROW_FULL_ROWS - 1 with the full row body;
+//   2. at row NARROW_FULL_ROWS the qualification, per half of the lane: every outer H and F must be < L; the outer H / Hg / F then become the
+//      infimum (so the report loop at the end needs no change);
+//   3. the remaining rows with the row body over columns LO..HI (column LO takes no E, column HI no F) and a monitor: the running maximum of
+//      what flows from the inner columns into the outer ones -- max( Hg[LO], F[LO] + ext ) of the row before into column LO - 1, and
+//      E' = max( hg, E + ext ) of column HI into column HI + 1;
+//   4. a half that qualified and whose monitor stayed < L reports as the full band does; any other half reports nothing, keeps its stash in
+//      scores[] and puts its job on the redo list, over which the build without NARROW runs behind this launch.
+// Exactness, by induction over the rows from NARROW_FULL_ROWS on: every input of an outer cell is another outer cell or one of the monitored
+// flows, hence < L; all steps are <= 0; so every outer cell is < L.  An inner cell's narrow value is its true value unless both are < L (a path
+// that gives a cell a value >= L runs through cells >= L only: inner ones from row NARROW_FULL_ROWS on, exactly computed ones before).  The
+// optimum is >= L, so it sits in an inner cell of the last row with its true value, and no outer cell can tie it.  L is only a lower bound: a
+// gapped optimum above U* is found like any other.
+constexpr uint32_t NARROW_FULL_ROWS = 24u;                       // three chunks of 8 rows (simulated: no outer column alive at row 24, some at row 16)
+constexpr int NARROW_A_HALF = 6, NARROW_B_HALF = 8;              // half-widths of class A / B around column 15
+struct NarrowJobs { const uint32_t *list_b, *count_b, *list_a, *count_a; uint32_t *redo, *redo_count; };
+
+template <int TYPE, int RBITS, int MINW = 3, bool M0 = false, bool RAGGED = false, bool FP = false, bool NARROW = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MINW, 3)))
 banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __restrict__ scores, uint2* __restrict__ sinks,
-                              const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count)
+                              const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count, const NarrowJobs nj)
 {
     constexpr int BAND = 31;
     constexpr uint32_t RMASK = (1u << RBITS) - 1u;
     static_assert( !FP || (M0 && TYPE != NVBIO_LOCAL), "the binary16 build: match = 0, GLOBAL / SEMI_GLOBAL" );
+    static_assert( !NARROW || (FP && !RAGGED && TYPE == NVBIO_SEMI_GLOBAL), "the narrow roles: the binary16 SEMI_GLOBAL build, equal read lengths" );
     typedef typename PkLanes<FP>::type v2;
     __shared__ int32_t s_mm[64];
     if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
     __syncthreads();
 
     // with a job list (the jobs the ungapped pass could not settle) lane p works on entries 2p and 2p+1 of the list
-    const uint32_t n_jobs = job_list ? *job_count : b.n;
-    const uint32_t pair = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t n_jobs = job_list ? *job_count : b.n;
+    uint32_t group = blockIdx.x;
+    int role = 0;                                                    // 0: the full band, 1: class B, 2: class A (uniform over the workgroup)
+    if (NARROW)
+    {
+        const uint32_t nb_full = (n_jobs + 255u) / 256u, n_b = *nj.count_b, nb_b = (n_b + 255u) / 256u;
+        if (group >= nb_full)
+        {
+            group -= nb_full; role = 1; job_list = nj.list_b; n_jobs = n_b;
+            if (group >= nb_b) { group -= nb_b; role = 2; job_list = nj.list_a; n_jobs = *nj.count_a; }
+        }
+    }
+    const uint32_t pair = group * blockDim.x + threadIdx.x;
     if (2u * pair >= n_jobs) return;
     const uint32_t* __restrict__ rwords = (const uint32_t*)b.reads;
     const uint32_t* __restrict__ twords = (const uint32_t*)b.text;
@@ -344,7 +380,7 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
 
     const uint32_t qadj = (uint32_t)((uintptr_t)b.quals & 3u);      // the quality stream need not be 4-byte aligned
     const uint32_t* __restrict__ qwords = (const uint32_t*)((uintptr_t)b.quals - qadj);
-    const bool has_quals = (b.quals != nullptr);
+    const bool has_quals = !NARROW && (b.quals != nullptr);         // (classes are formed only for batches without qualities)
 
     const v2 GO = pk_of<v2>( sc.pat_go, sc.pat_go ), GE = pk_of<v2>( sc.pat_ge, sc.pat_ge );
     const v2 INF = pk_of<v2>( -16384, -16384 ), ZERO = pk_of<v2>( 0, 0 );
@@ -361,6 +397,8 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
 
     int32_t  best[2]   = { NVBIO_SCORE_MIN, NVBIO_SCORE_MIN };
     uint32_t best_x[2] = { 0xFFFFFFFFu, 0xFFFFFFFFu }, best_y[2] = { 0xFFFFFFFFu, 0xFFFFFFFFu };
+    // the narrow roles: the largest value seen so far that must stay below L -- the outer cells at the qualification, then the monitored flows
+    v2 mon = INF;
 
     // GLOBAL / SEMI_GLOBAL report from the band after an alignment's LAST row (:624-645).  To keep that out
     // of the row loop, a lane whose two alignments have different lengths runs them one after the other
@@ -373,6 +411,11 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
     uint32_t pad[2] = { 0u, 0u };
     if (RAGGED && TYPE != NVBIO_LOCAL) { pad[0] = rows_max - rows_all[0]; pad[1] = rows_max - rows_all[1]; }
 
+    // (one copy of the passes per role: the roles' row bodies then share no registers for their loop invariants -- written as one loop with
+    // the role tested per chunk, the build spilled 64 registers)
+    auto run_passes = [&](auto ROLE_)
+    {
+    constexpr int ROLE = decltype(ROLE_)::value;
     for (int pass = 0; pass < (split ? 2 : 1); ++pass)
     {
         uint32_t rows_u[2];
@@ -442,7 +485,8 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
             H[j] = pk_of<v2>( h0, h0 ); F[j] = INF; Hg[j] = H[j] + GO;
         }
 
-        for (uint32_t r0 = 0; r0 < rows; r0 += 8u)
+        // one chunk of 8 rows over columns LO..HI of the band
+        auto do_chunk = [&](const uint32_t r0, auto LO_, auto HI_)
         {
             // ---- assemble this chunk from the words loaded a chunk ago, then request the next chunk ----
             uint32_t rchunk[2], tchunk[2], tchunk1[2]; int rsh[2], rstep[2];
@@ -476,6 +520,10 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
             if (r0 + 8u < rows) issue_loads( r0 + 8u );
 
             const uint32_t r_end = (r0 + 8u < rows) ? 8u : rows - r0;
+            // the chunk's rows over columns LO..HI of the band (0..30: the whole band)
+            auto chunk_rows = [&](auto LO_, auto HI_)
+            {
+            constexpr int LO = decltype(LO_)::value, HI = decltype(HI_)::value;
             for (uint32_t t = 0; t < r_end; ++t)
             {
                 const uint32_t i = r0 + t;
@@ -556,11 +604,13 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
                 v2 E = ZERO, a = ZERO, tt, ff = INF, dd = ZERO;              // (FP carries f and d of the next cell instead of their maximum)
                 v2s key = pk( -1, -1 );
                 {
-                    const v2 x  = F[1] + GE;
-                    const v2 t0 = flags_of( 0 );
-                    const v2 d  = diag_of( H[0], t0 );
-                    const v2 f  = pk_max( x, Hg[1] );
-                    F[0] = f;
+                    // (narrow: what the row before sends into column LO - 1 of this row, before F[LO] is overwritten)
+                    if (NARROW && LO > 0) mon = pk_max3( mon, Hg[LO], F[LO] + GE );
+                    const v2 x  = F[LO + 1] + GE;
+                    const v2 t0 = flags_of( LO );
+                    const v2 d  = diag_of( H[LO], t0 );
+                    const v2 f  = pk_max( x, Hg[LO + 1] );
+                    F[LO] = f;
                     if (FP) { ff = f; dd = d; tt = ZERO; }
                     else
                     {
@@ -569,35 +619,36 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
                     }
                 }
                 #pragma unroll
-                for (int j = 0; j < BAND; ++j)
+                for (int j = LO; j <= HI; ++j)
                 {
                     constexpr int Z = 0;
                     const int j1 = j + 1, j2 = j + 2;
                     v2 x = INF, d = ZERO, f = INF, t1 = ZERO, tn = ZERO, an = ZERO;
                     uint32_t q1 = 0;
-                    if (j2 < BAND) x  = F[j2] + GE;
+                    if (j2 <= HI) x  = F[j2] + GE;
                     __builtin_amdgcn_sched_barrier( Z );
-                    const v2 h = FP ? ((j == 0) ? pk_max( ff, dd ) : pk_max3( ff, dd, E )) : ((j == 0) ? tt : pk_max( tt, E ));
-                    if (j1 < BAND) q1 = flags_at( j1 );
+                    const v2 h = FP ? ((j == LO) ? pk_max( ff, dd ) : pk_max3( ff, dd, E )) : ((j == LO) ? tt : pk_max( tt, E ));
+                    if (j1 <= HI) q1 = flags_at( j1 );
                     __builtin_amdgcn_sched_barrier( Z );
                     const v2 hg = h + GO;
-                    if (!FP && j1 < BAND) t1 = flags_in( q1 );
-                    if (j2 < BAND) f  = pk_max( x, Hg[j2] );
+                    if (!FP && j1 <= HI) t1 = flags_in( q1 );
+                    if (j2 <= HI) f  = pk_max( x, Hg[j2] );
                     __builtin_amdgcn_sched_barrier( Z );
-                    const v2 En = (j == 0) ? hg : pk_max( hg, a );
+                    const v2 En = (j == LO) ? hg : pk_max( hg, a );
                     if (FP) __builtin_amdgcn_sched_barrier( Z );            // (one cell is an operation shorter: keep E' away from its consumer)
-                    if (FP && j1 < BAND) t1 = flags_in( q1 );
-                    if (j1 < BAND) d  = diag_of( H[j1], t1 );
+                    if (FP && j1 <= HI) t1 = flags_in( q1 );
+                    if (j1 <= HI) d  = diag_of( H[j1], t1 );
                     __builtin_amdgcn_sched_barrier( Z );
-                    if (j1 < BAND) an = En + GE;
+                    if (j1 <= HI) an = En + GE;
+                    if (NARROW && HI < BAND - 1 && j == HI) mon = pk_max( mon, En );      // (narrow: what column HI sends into column HI + 1)
                     if (TYPE == NVBIO_LOCAL) key = pk_max( key, __builtin_bit_cast( v2s, h ) * K32 + pk( j, j ) );
                     __builtin_amdgcn_sched_barrier( Z );
-                    if (j1 < BAND)
+                    if (j1 <= HI)
                     {
-                        if (FP) { ff = (j2 < BAND) ? f : d; dd = d; }
+                        if (FP) { ff = (j2 <= HI) ? f : d; dd = d; }
                         else
                         {
-                            tn = (j2 < BAND) ? pk_max( f, d ) : d;
+                            tn = (j2 <= HI) ? pk_max( f, d ) : d;
                             if (TYPE == NVBIO_LOCAL) tn = pk_max( tn, ZERO );
                         }
                         F[j1] = f;
@@ -615,7 +666,36 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
                     if (i < rows_u[1] && (k1 >> 5) >= best[1]) { best[1] = k1 >> 5; best_x[1] = i + (uint32_t)(k1 & 31) + 1u; best_y[1] = i + 1u; }
                 }
             }
+            };
+            chunk_rows( LO_, HI_ );
+        };
+        typedef std::integral_constant<int,0> C0; typedef std::integral_constant<int,BAND - 1> C30;
+        if (NARROW && ROLE != 0 && rows > NARROW_FULL_ROWS)
+        {
+            // (two loops, so that the narrow body's loop invariants are set up behind the full-band rows, where registers are free)
+            typedef std::integral_constant<int,15 - NARROW_A_HALF> ALO; typedef std::integral_constant<int,15 + NARROW_A_HALF> AHI;
+            typedef std::integral_constant<int,15 - NARROW_B_HALF> BLO; typedef std::integral_constant<int,15 + NARROW_B_HALF> BHI;
+            // the qualification: every outer H and F of a half must be below its L -- they join what the monitor has seen, which is held
+            // against L at the end -- and become the infimum.  (A lane that splits its two alignments over two passes is simply redone:
+            // 0 is below no L.)
+            auto qualify = [&](auto LO_, auto HI_)
+            {
+                constexpr int LO = decltype(LO_)::value, HI = decltype(HI_)::value;
+                #pragma unroll
+                for (int j = 0; j < BAND; ++j)
+                    if (j < LO || j > HI)
+                    {
+                        mon = pk_max3( mon, H[j], F[j] );
+                        H[j] = INF; Hg[j] = INF; F[j] = INF;
+                    }
+                if (split) mon = ZERO;
+            };
+            for (uint32_t r0 = 0; r0 < NARROW_FULL_ROWS; r0 += 8u) do_chunk( r0, C0(), C30() );
+            if (ROLE == 2) { qualify( ALO(), AHI() ); for (uint32_t r0 = NARROW_FULL_ROWS; r0 < rows; r0 += 8u) do_chunk( r0, ALO(), AHI() ); }
+            else           { qualify( BLO(), BHI() ); for (uint32_t r0 = NARROW_FULL_ROWS; r0 < rows; r0 += 8u) do_chunk( r0, BLO(), BHI() ); }
         }
+        else
+            for (uint32_t r0 = 0; r0 < rows; r0 += 8u) do_chunk( r0, C0(), C30() );
 
         // ---- end-of-alignment reports (:624-645); every active half ended at row `rows` (or has no rows) ----
         if (TYPE != NVBIO_LOCAL)
@@ -645,9 +725,22 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
             }
         }
     }
+    };
+    if (NARROW && role == 1)      run_passes( std::integral_constant<int,1>() );
+    else if (NARROW && role == 2) run_passes( std::integral_constant<int,2>() );
+    else                          run_passes( std::integral_constant<int,0>() );
     #pragma unroll
     for (int u = 0; u < 2; ++u)
-        if (valid[u]) { scores[out_id[u]] = best[u]; sinks[out_id[u]] = make_uint2( best_x[u], best_y[u] ); }
+    {
+        if (!valid[u]) continue;
+        // (narrow: L is the first pass's stash; it is < 0, and a half that ran no narrow row has seen nothing)
+        if (NARROW && role != 0 && !((u ? (float)mon.y : (float)mon.x) < (float)scores[out_id[u]]))
+        {
+            nj.redo[atomicAdd( nj.redo_count, 1u )] = out_id[u];     // (rare; scores[] keeps the stash)
+            continue;
+        }
+        scores[out_id[u]] = best[u]; sinks[out_id[u]] = make_uint2( best_x[u], best_y[u] );
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -694,6 +787,32 @@ __host__ __device__ __forceinline__ int32_t gap_chance_unknown_cost(const int32_
 // `cap` is a 64-bit division that every wave used to expand: two v_rcp_f32 and some 160 scalar instructions): c_unk for a job that brings its best diagonal (need_dp = 2)
 // and for one that does not (need_dp = 4: every diagonal has more than `cap` mismatches, so the ungapped class costs >= (cap + 1) P)
 struct GapLadder { int32_t c_unk_u, c_unk_n; };
+// the DP's narrow classes (banded_gotoh_band31_pk_kernel, NARROW), decided by the first pass from U* and the best diagonal alone: with
+// r(L) = the largest delta with open + (delta - 1) ext >= L and w = r(U*) + |best_d - 15|, class A is w <= NARROW_A_HALF, class B
+// w <= NARROW_B_HALF.  The host passes thr_a / thr_b = the least U* with r <= the half-width, open + half ext + 1 (they depend on the scheme
+// only); a window off centre by o columns raises them by -o ext.  thr = 1, which no U* reaches: the route is off.  A class comes out empty by
+// itself for a scheme whose U* of the jobs that leave for the DP all lie below its threshold (cheap gaps: the threshold is close to 0).
+// cnt_max: the first pass counts a diagonal's mismatches exactly up to the larger of its own cap and this, the largest count whose U* is
+// still in class B, so that a job whose best diagonal is out of every chance's reach leaves with its U* known.
+struct NarrowRule { int32_t thr_a, thr_b; uint32_t cnt_max; };
+static NarrowRule narrow_rule(const bool on, const int32_t P, const int32_t go, const int32_t ge)
+{
+    NarrowRule r = { 1, 1, 0u };
+    if (!on || ge >= 0 || P <= 0) return r;
+    const int64_t a = (int64_t)go + (int64_t)NARROW_A_HALF * ge + 1, bb = (int64_t)go + (int64_t)NARROW_B_HALF * ge + 1;
+    if (bb < -2000) return r;                                      // (far outside what the binary16 lanes are admitted for)
+    r.thr_a = (int32_t)a; r.thr_b = (int32_t)bb;
+    r.cnt_max = (uint32_t)((-bb) / P);
+    return r;
+}
+// 0: none, 1: class B, 2: class A
+__device__ __forceinline__ uint32_t narrow_class(const NarrowRule nr, const int64_t U, const uint32_t best_d, const int32_t gap_ext)
+{
+    const int64_t o = best_d > 15u ? best_d - 15u : 15u - best_d;
+    if (o <= NARROW_A_HALF && U >= (int64_t)nr.thr_a - o * gap_ext) return 2u;
+    if (o <= NARROW_B_HALF && U >= (int64_t)nr.thr_b - o * gap_ext) return 1u;
+    return 0u;
+}
 static GapLadder gap_ladder(const int32_t P, const int32_t G, const int32_t go, const int32_t ge)
 {
     const int64_t floor_u = 3 * (int64_t)(G < go ? G : go) - P;
@@ -711,20 +830,21 @@ static GapLadder gap_ladder(const int32_t P, const int32_t G, const int32_t go, 
 // range's start + the jobs of the waves before it + its rank in the ballot.  A workgroup walks JOB_LIST_CHUNKS chunks of 256 jobs and
 // reserves once for all of them.  The lists are dense but NOT in ascending job order (workgroups reserve in the order they finish).
 // Counters: `counts` of the "banded_job_list" layout, one 128-byte line each, zeroed on the stream before the first pass.
-constexpr uint32_t JOB_COUNT_STRIDE = 32u;                        // in uint32: counts[0] the DP's list, [32] the second chance's, [64] the third / gap chance's, [96] the gap chance's pairs
-constexpr uint32_t JOB_LIST_COUNT   = 4u;
+constexpr uint32_t JOB_COUNT_STRIDE = 32u;                        // in uint32: counts[0] the DP's list, [32] the second chance's, [64] the third / gap chance's, [96] the gap chance's pairs,
+                                                                  // [128] / [160] the DP's class B / class A (narrow roles), [192] the narrow roles' redo list
+constexpr uint32_t JOB_LIST_COUNT   = 7u;
 #ifndef NVB_JOB_LIST_CHUNKS
 #define NVB_JOB_LIST_CHUNKS 1
 #endif
-constexpr int JOB_LIST_CHUNKS = NVB_JOB_LIST_CHUNKS;              // at most 4 (JobAppend::mine holds a byte per chunk)
+constexpr int JOB_LIST_CHUNKS = NVB_JOB_LIST_CHUNKS;              // at most 4 (JobAppend::mine holds a byte per chunk for up to 3 lists, 16 bits per chunk in a uint64_t beyond)
 static inline uint32_t job_list_grid(const uint32_t n) { return (n + 256u * JOB_LIST_CHUNKS - 1u) / (256u * JOB_LIST_CHUNKS); }
 
-struct JobLists { uint32_t *dp, *second, *third, *pairs; uint32_t* counts; };      // list 0, 1, 2, 3 and their counters
+struct JobLists { uint32_t *dp, *second, *third, *pairs; uint32_t* counts; uint32_t *class_b, *class_a, *redo; };      // list 0, 1, 2, 3 and the counters; list 4, 5, 6
 
 template <int NL>
 struct JobAppend
 {
-    static_assert( NL >= 1 && NL <= 4 && JOB_LIST_CHUNKS >= 1 && JOB_LIST_CHUNKS <= 4, "JobAppend: up to 4 lists, up to 4 chunks" );
+    static_assert( NL >= 1 && NL <= 6 && JOB_LIST_CHUNKS >= 1 && JOB_LIST_CHUNKS <= 4, "JobAppend: up to 6 lists, up to 4 chunks" );
     struct Lds { uint32_t cnt[NL][4 * JOB_LIST_CHUNKS]; uint32_t base[NL]; };
     // chunk k in bits SLOT k .. SLOT k + SLOT - 1: (list + 1) << 6 | rank among the wave's jobs for that list (a byte holds lists 0 .. 2)
     static constexpr int SLOT = NL <= 3 ? 8 : 16;
@@ -762,7 +882,7 @@ struct JobAppend
             if (e)
             {
                 const uint32_t l = (e >> 6) - 1u;
-                uint32_t* const list = l == 0u ? out.dp : (l == 1u ? out.second : (l == 2u ? out.third : out.pairs));
+                uint32_t* const list = l == 0u ? out.dp : (l == 1u ? out.second : (l == 2u ? out.third : (l == 3u ? out.pairs : (l == 4u ? out.class_b : out.class_a))));
                 list[lds.base[l] + lds.cnt[l][4 * k + wave] + (e & 63u)] = job_of( k );
             }
         }
@@ -862,7 +982,8 @@ gap_pairs_kernel(const BatchDev b, uint32_t* __restrict__ partner)
 template <int RBITS, int MODE, bool QUAL>
 __device__ __forceinline__ uint32_t
 ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
-                   int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const int32_t* s_pen)
+                   int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const int32_t* s_pen,
+                   const NarrowRule nr = NarrowRule{ 1, 1, 0u })
 {
     constexpr bool LIST = MODE != 0;
     const uint32_t rid   = b.read_id ? b.read_id[job] : job;
@@ -940,6 +1061,12 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
         // word instead of six.  The text planes are taken d symbols on with one funnel shift per word (d is a constant of the unrolled loop).
         const int64_t floor_u = 3 * (int64_t)(G < gap_open ? G : gap_open) - P;          // U <= floor_u: DP whatever else holds
         const uint32_t cap = P > 0 ? (uint32_t)((-floor_u - 1) / (int64_t)P) : 0xFFFFFFFEu;   // the largest count with -P cnt > floor_u
+        // (the DP's narrow classes: counts up to nr.cnt_max are kept exact too.  This CHANGES A ROUTE: an unclipped job whose best diagonal has
+        // more than `cap` mismatches but a U* within class B -- 5 at -6 / -8 / -3 -- used to leave with flag 4 for the gap chance, alone or
+        // as a pair member, and now leaves with flag 1 for the DP's class.  For a read with that many substitutions this saves a gap-chance
+        // evaluation that could not settle it; the rare indel read whose best diagonal has exactly that count, which the gap chance would
+        // have settled, costs a class-B DP instead, and its partner goes to the gap chance alone.  Results are the same either way.)
+        const uint32_t cap_x = (!QUAL && nr.cnt_max > cap && N >= M + 30u) ? nr.cnt_max : cap;
         uint32_t cnt_d[QUAL ? 31 : 1];
         #pragma unroll
         for (uint32_t d = 0; d < 31u; ++d)
@@ -950,7 +1077,7 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
                 const uint32_t tl = d ? __builtin_amdgcn_alignbit( ql0[1], ql0[0], d ) : ql0[0], th = d ? __builtin_amdgcn_alignbit( qh0[1], qh0[0], d ) : qh0[0];
                 cnt = (uint32_t)__popc( (((pl[0] ^ tl) | (ph[0] ^ th)) & pm[0]) | pn[0] );
             }
-            const uint32_t thr = QUAL ? cap : (best_cnt < cap ? best_cnt : cap);
+            const uint32_t thr = QUAL ? cap : (best_cnt < cap_x ? best_cnt : cap_x);
             if (__any( on && cnt <= thr ))
             {
                 #pragma unroll
@@ -966,6 +1093,12 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
         }
         if (best_cnt > cap)                                          // (includes: no diagonal evaluated)
         {
+            if (!QUAL && best_cnt <= cap_x)
+            {
+                // out of every chance's reach, but its U* is known and within class B: straight to the DP's narrow role
+                const uint32_t cls = narrow_class( nr, -(int64_t)P * (int64_t)best_cnt, best_d, gap_ext );
+                if (cls) { scores[job] = -P * (int32_t)best_cnt; sinks[job] = make_uint2( M + best_d, M ); return 1u | (cls << 8); }
+            }
             // no diagonal within reach of the three chances: typically a read with an indel.  The gap chance (gap_chance_e2e31_kernel, its own
             // list pass) evaluates the one-gap alignments of such a job exactly; it needs every diagonal inside the text and plain gap terms
             // (not under a quality ramp: see the kernel's header)
@@ -1231,6 +1364,11 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
         scores[job] = (int32_t)U; sinks[job] = make_uint2( M + best_d, M );
         return 0u;
     }
+    if (MODE == 0 && !QUAL && N >= M + 30u)
+    {
+        const uint32_t cls = narrow_class( nr, U, best_d, gap_ext );
+        if (cls) { stash(); return 1u | (cls << 8); }
+    }
     return 1u;
 }
 
@@ -1244,10 +1382,10 @@ __global__ void __launch_bounds__(256)
 ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
                       int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
                       const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
-                      const SchemeDev sc, const JobLists out, const uint32_t third_mask)
+                      const SchemeDev sc, const JobLists out, const uint32_t third_mask, const NarrowRule nr)
 {
     constexpr bool LIST = MODE != 0;
-    constexpr int  NL   = LIST ? 1 : 4;
+    constexpr int  NL   = LIST ? 1 : 6;
     __shared__ int32_t s_pen[QUAL ? 64 : 1];
     __shared__ typename JobAppend<NL>::Lds s_lists;
     const uint32_t n    = LIST ? *job_count : b.n;
@@ -1270,9 +1408,11 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
         if (slot0 + 256u * k + threadIdx.x < n)
         {
             const uint32_t job  = job_of( k );
-            flag = ungapped_e2e31_job<RBITS,MODE,QUAL>( b, P, G, gap_open, gap_ext, scores, sinks, job, s_pen );
+            flag = ungapped_e2e31_job<RBITS,MODE,QUAL>( b, P, G, gap_open, gap_ext, scores, sinks, job, s_pen, nr );
+            const uint32_t cls = flag >> 8;                          // (MODE 0: a flag-1 job's narrow class, 1 = B on list 4, 2 = A on list 5)
+            flag &= 255u;
             need_dp[job] = (uint8_t)flag;
-            if (flag) which = LIST ? 0 : (flag == 3u ? 1 : (((third_mask >> flag) & 1u) ? 2 : 0));
+            if (flag) which = LIST ? 0 : (flag == 3u ? 1 : (((third_mask >> flag) & 1u) ? 2 : (cls ? 3 + (int)cls : 0)));
         }
         if (MODE == 0 && !QUAL && pairing && __any( flag == 4u ))
         {
@@ -2101,38 +2241,71 @@ static nvbio_status sort_jobs_by_length(const BatchDev& b, const uint32_t* job_l
     return NVBIO_OK;
 }
 
+// the route report's bytes (nvbio_banded_gotoh_score_routes; zeroed before): 1 for the jobs of the DP's full list, 3 / 2 for class B / A;
+// REDO: +8 for the jobs of the redo list
+template <bool REDO>
+__global__ void __launch_bounds__(256)
+job_routes_kernel(const JobLists l, const uint32_t n, const bool classes, uint8_t* __restrict__ routes)
+{
+    const uint32_t n_dp = REDO ? 0u : l.counts[0], n_b = (REDO || !classes) ? 0u : l.counts[4u * JOB_COUNT_STRIDE], n_a = (REDO || !classes) ? 0u : l.counts[5u * JOB_COUNT_STRIDE];
+    const uint32_t n_r = (REDO && classes) ? l.counts[6u * JOB_COUNT_STRIDE] : 0u;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    {
+        if (i < n_dp) routes[l.dp[i]] = 1u;
+        if (i < n_b)  routes[l.class_b[i]] = 3u;
+        if (i < n_a)  routes[l.class_a[i]] = 2u;
+        if (i < n_r)  routes[l.redo[i]] |= 8u;
+    }
+}
+
+// the binary16 build is exact while every score stays an integer of magnitude <= 2040 (and the scaled penalties finite)
+template <int TYPE>
+static bool pk_binary16_ok(const BatchDev& b, const SchemeDev& sc)
+{
+    const bool two = (b.algo & NVBIO_ALN_PK_THREE_WAVES) == 0;
+    int64_t step = 0;
+    { const int c[] = { sc.mm_min, sc.mm_max, -sc.pat_go, -sc.pat_ge, -sc.txt_go, -sc.txt_ge }; for (int v : c) if (v > step) step = v; }
+    return two && sc.match == 0 && TYPE == NVBIO_SEMI_GLOBAL && !(b.algo & NVBIO_ALN_NO_F16_DP) && ((int64_t)b.max_read_len + 32) * step <= 2040 && sc.mm_max <= 400;
+}
+
 // the packed kernel's instantiation for this scheme: match = 0 (every end-to-end scheme of nvBowtie) drops one operation per cell
+// narrow: the lists of the narrow roles (the caller has checked that the binary16 build runs and that the batch is not declared ragged)
 template <int TYPE, int RB>
 static nvbio_status launch_pk_kernel(const BatchDev& b, const SchemeDev& sc, const uint32_t pairs, int32_t* scores, uint2* sinks,
-                                     const uint32_t* job_list, const uint32_t* job_count, hipStream_t s)
+                                     const uint32_t* job_list, const uint32_t* job_count, hipStream_t s, const NarrowJobs* narrow = nullptr)
 {
     const dim3 grid( (pairs + 127u) / 128u ), block( 128 );
     const bool two = (b.algo & NVBIO_ALN_PK_THREE_WAVES) == 0;
-    // the binary16 build is exact while every score stays an integer of magnitude <= 2040 (and the scaled penalties finite)
-    int64_t step = 0;
-    { const int c[] = { sc.mm_min, sc.mm_max, -sc.pat_go, -sc.pat_ge, -sc.txt_go, -sc.txt_ge }; for (int v : c) if (v > step) step = v; }
-    const bool fp = two && sc.match == 0 && TYPE == NVBIO_SEMI_GLOBAL && !(b.algo & NVBIO_ALN_NO_F16_DP) && ((int64_t)b.max_read_len + 32) * step <= 2040 && sc.mm_max <= 400;
+    const bool fp = pk_binary16_ok<TYPE>( b, sc );
+    const NarrowJobs nj = {};
+    if (narrow)
+    {
+        // the three lists are disjoint, so their workgroups are at most the whole batch's and one more per list for the ceilings
+        constexpr int T = (TYPE == NVBIO_SEMI_GLOBAL) ? TYPE : NVBIO_SEMI_GLOBAL;      // (SEMI_GLOBAL here: keeps other instantiations out)
+        return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,false,true,true>), dim3( grid.x + 2u ), block, s, b, sc, scores, sinks, job_list, job_count, *narrow );
+    }
     if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS))
     {
         // reads of different lengths (the caller says so): both alignments of a lane in one pass
         constexpr int T = (TYPE == NVBIO_SEMI_GLOBAL) ? TYPE : NVBIO_SEMI_GLOBAL;
-        if (fp) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
-        return         NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+        if (fp) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
+        return         NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
     }
     if (TYPE != NVBIO_LOCAL && sc.match == 0)
     {
         constexpr int T = (TYPE == NVBIO_LOCAL) ? NVBIO_SEMI_GLOBAL : TYPE;      // (never LOCAL here: keeps that instantiation out)
         // (the binary16 build of the GLOBAL kernel spills: SEMI_GLOBAL only)
-        if (fp)  return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<NVBIO_SEMI_GLOBAL,RB,2,true,false,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
-        if (two) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
-        return          NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,3,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+        if (fp)  return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<NVBIO_SEMI_GLOBAL,RB,2,true,false,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
+        if (two) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,2,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
+        return          NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<T,RB,3,true>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
     }
-    if (two) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<TYPE,RB,2,false>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
-    return          NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<TYPE,RB,3,false>), grid, block, s, b, sc, scores, sinks, job_list, job_count );
+    if (two) return NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<TYPE,RB,2,false>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
+    return          NVB_LAUNCH( (banded_gotoh_band31_pk_kernel<TYPE,RB,3,false>), grid, block, s, b, sc, scores, sinks, job_list, job_count, nj );
 }
 
+// routes: the route report of nvbio_banded_gotoh_score_routes (NULL: none), preset to 1 by the caller
 template <int TYPE, int RB>
-static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* scores, uint2* sinks, hipStream_t s)
+static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* scores, uint2* sinks, hipStream_t s, uint8_t* routes)
 {
     const uint32_t pairs = (b.n + 1u) / 2u;
     int32_t P = 0; bool by_quality = false;
@@ -2145,7 +2318,11 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         // 3. DP over the rest.  Every kernel puts the jobs it does not settle on the list of the launch that takes them next (JobAppend).
         const int32_t G = sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go;
         const bool third = !(b.algo & NVBIO_ALN_NO_THIRD_CHANCE);
-        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *list_p, *counts;
+        uint8_t* need_dp; uint32_t *job_list, *list_s, *list_t, *list_p, *counts, *list_b, *list_a, *list_r;
+        // the DP's narrow classes: formed only where the DP that follows is the binary16 build over a batch without qualities that is not declared ragged
+        const NarrowRule nr = narrow_rule( b.quals == nullptr && !(b.algo & (NVBIO_ALN_NO_NARROW_DP | NVBIO_ALN_RAGGED_READS)) && pk_binary16_ok<TYPE>( b, sc ),
+                                           P, sc.pat_go, sc.pat_ge );
+        const bool classes = nr.thr_b != 1;
         ScratchBlock aux;
         NVB_CHECK( aux.alloc_layout( "banded_job_list", s, "banded score: out of device memory for the job list", [&](ScratchLayout& c)
         {
@@ -2154,9 +2331,12 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
             list_s   = c.take<uint32_t>( b.n );                                              // second-chance jobs
             list_t   = c.take<uint32_t>( b.n );                                              // third-chance / gap-chance jobs
             list_p   = c.take<uint32_t>( (b.n + 1u) / 2u );                                  // the gap chance's pairs (the lower job of each)
-            counts   = c.take<uint32_t>( JOB_LIST_COUNT * JOB_COUNT_STRIDE );                // the four lists' lengths, a 128-byte line each
+            counts   = c.take<uint32_t>( JOB_LIST_COUNT * JOB_COUNT_STRIDE );                // the lists' lengths, a 128-byte line each
+            list_b   = c.take<uint32_t>( classes ? b.n : 1u );                               // the DP's class B, class A and their redo list
+            list_a   = c.take<uint32_t>( classes ? b.n : 1u );
+            list_r   = c.take<uint32_t>( classes ? b.n : 1u );
         } ) );
-        const JobLists out = { job_list, list_s, list_t, list_p, counts };
+        const JobLists out = { job_list, list_s, list_t, list_p, counts, list_b, list_a, list_r };
         const uint32_t* job_count = counts;
         const uint32_t* count_s   = counts + JOB_COUNT_STRIDE;
         const uint32_t* count_t   = counts + 2u * JOB_COUNT_STRIDE;
@@ -2179,16 +2359,16 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
         NVB_HIP( hipMemsetAsync( counts, 0, JOB_LIST_COUNT * JOB_COUNT_STRIDE * sizeof(uint32_t), s ) );
         if (by_quality)
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0,true>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask, nr ) );
         else
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,0>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask ) );
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, sc, out, third_mask, nr ) );
         if (fused)
             NVB_CHECK( NVB_LAUNCH( (chances_e2e31_kernel<RB>), dim3( job_list_grid( b.n ) + 2u ), block, s, b, P, G, lad, sc.pat_go, sc.pat_ge, scores, sinks,
                                    need_dp, (const uint32_t*)list_s, count_s, (const uint32_t*)list_t, count_t, (const uint32_t*)list_p, count_p, out ) );
         else
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,1>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)list_s, count_s, SchemeDev{}, out, 0u ) );
+                                   (const uint32_t*)list_s, count_s, SchemeDev{}, out, 0u, NarrowRule{ 1, 1, 0u } ) );
         if (fused)
             ;                                                        // (list_t went through the launch above)
         else if (gapc)
@@ -2196,11 +2376,26 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
                                    need_dp, (const uint32_t*)list_t, count_t, (const uint32_t*)list_p, count_p, out ) );
         else if (third)
             NVB_CHECK( NVB_LAUNCH( (ungapped_e2e31_kernel<RB,2>), grid, block, s, b, P, G, sc.pat_go, sc.pat_ge, scores, sinks, need_dp,
-                                   (const uint32_t*)list_t, count_t, SchemeDev{}, out, 0u ) );
+                                   (const uint32_t*)list_t, count_t, SchemeDev{}, out, 0u, NarrowRule{ 1, 1, 0u } ) );
         const uint32_t* jl = job_list; const uint32_t* jc = job_count; ScratchBlock sorted;
         if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT))
             NVB_CHECK( sort_jobs_by_length( b, job_list, job_count, &jl, &jc, &sorted, s ) );
-        NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s )) );
+        if (classes)
+        {
+            // one launch over the full list, class B and class A; behind it the full band over the (nearly always empty) redo list
+            const NarrowJobs nj = { list_b, counts + 4u * JOB_COUNT_STRIDE, list_a, counts + 5u * JOB_COUNT_STRIDE, list_r, counts + 6u * JOB_COUNT_STRIDE };
+            NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s, &nj )) );
+            NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, list_r, counts + 6u * JOB_COUNT_STRIDE, s )) );
+        }
+        else
+            NVB_CHECK( (launch_pk_kernel<TYPE,RB>( b, sc, pairs, scores, sinks, jl, jc, s )) );
+        if (routes)
+        {
+            const dim3 rgrid( (b.n + 255u) / 256u < 4096u ? (b.n + 255u) / 256u : 4096u );
+            NVB_HIP( hipMemsetAsync( routes, 0, b.n, s ) );
+            NVB_CHECK( NVB_LAUNCH( job_routes_kernel<false>, rgrid, block, s, out, b.n, classes, routes ) );
+            NVB_CHECK( NVB_LAUNCH( job_routes_kernel<true>,  rgrid, block, s, out, b.n, classes, routes ) );
+        }
         return NVBIO_OK;
     }
     if (TYPE == NVBIO_SEMI_GLOBAL && sc.match == 0 && (b.algo & NVBIO_ALN_RAGGED_READS) && !(b.algo & NVBIO_ALN_NO_LENGTH_SORT) && b.n > 1u)
@@ -2214,13 +2409,13 @@ static nvbio_status launch_pk(const BatchDev& b, const SchemeDev& sc, int32_t* s
 
 template <int BAND>
 static nvbio_status launch_score(int type, const BatchDev& b, const SchemeDev& sc, uint32_t rbits, uint32_t tbits,
-                                 int32_t* scores, uint2* sinks, hipStream_t s)
+                                 int32_t* scores, uint2* sinks, hipStream_t s, uint8_t* routes)
 {
     return with_value( AlnTypes(), type, [&](auto TYPE)
     {
         if (BAND == 31 && plain_gotoh( sc ) && packed_ok( TYPE, sc, b.max_read_len ) && !(b.algo & NVBIO_ALN_NO_PACKED_DP) &&
             tbits == 2 && (rbits == 4 || rbits == 2))
-            return rbits == 4 ? launch_pk<TYPE,4>( b, sc, scores, sinks, s ) : launch_pk<TYPE,2>( b, sc, scores, sinks, s );
+            return rbits == 4 ? launch_pk<TYPE,4>( b, sc, scores, sinks, s, routes ) : launch_pk<TYPE,2>( b, sc, scores, sinks, s, routes );
         const dim3 grid( (b.n + 127u) / 128u ), block( 128 );
         return with_bits( BitsAll(), rbits, tbits, [&](auto P)
         {
@@ -2314,14 +2509,27 @@ extern "C" nvbio_status nvbio_banded_gotoh_score_best2(int device, uint32_t band
 }
 
 static nvbio_status banded_score(int device, uint32_t band, int type, const SchemeDev sc, const BatchDev& b, const nvbio_alignment_batch* batch,
-                                 int32_t* scores_dev, nvbio_uint2* sinks_dev, void* stream)
+                                 int32_t* scores_dev, nvbio_uint2* sinks_dev, void* stream, uint8_t* routes_dev = nullptr)
 {
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
+    if (routes_dev) NVB_HIP( hipMemsetAsync( routes_dev, 1, b.n, s ) );      // (every route but the end-to-end shortcut's: the DP over every job)
     return with_value( Bands(), band, [&](auto BAND)
     {
-        return launch_score<BAND>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s );
+        return launch_score<BAND>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (uint2*)sinks_dev, s, routes_dev );
     }, [] { return NVBIO_ERR_UNSUPPORTED; } );                             // (the band was checked)
+}
+
+extern "C" nvbio_status nvbio_banded_gotoh_score_routes(int device, uint32_t band, nvbio_alignment_type type,
+                                                        const nvbio_gotoh_scheme* scheme, const nvbio_alignment_batch* batch,
+                                                        int32_t* scores_dev, nvbio_uint2* sinks_dev, uint8_t* routes_dev, void* stream)
+{
+    NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
+    BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
+    NVB_CHECK( check_band( band, NVBIO_ERR_UNSUPPORTED ) );
+    if (b.n == 0) return NVBIO_OK;
+    NVB_REQUIRE( scores_dev && sinks_dev && routes_dev, "NULL output pointer" );
+    return banded_score( device, band, type, scheme_dev( scheme ), b, batch, scores_dev, sinks_dev, stream, routes_dev );
 }
 
 extern "C" nvbio_status nvbio_banded_gotoh_score(int device, uint32_t band, nvbio_alignment_type type,
