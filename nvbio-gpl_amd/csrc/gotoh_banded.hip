@@ -978,6 +978,38 @@ gap_pairs_kernel(const BatchDev b, uint32_t* __restrict__ partner)
     if (job < b.n) partner[job] = role ? (role > 0 ? job + 1u : job - 1u) : 0xFFFFFFFFu;
 }
 
+// the bit planes of one job as 32-bit words: bit j of word k of (pl, ph, pn, pm) = row 32 k + j of the read (its symbol's low / high bit, N, a row
+// of the read at all; pn holds no bit past the read's end), bit j of word k of (ql, qh) = text symbol 32 k + j of the window
+struct PlaneWords
+{
+    uint32_t pl[6], ph[6], pn[6], pm[6], ql[7], qh[7];
+
+    __device__ __forceinline__ void set(const uint64_t (&rlo)[3], const uint64_t (&rhi)[3], const uint64_t (&rn)[3],
+                                        const uint64_t (&tlo)[4], const uint64_t (&thi)[4], const uint32_t M)
+    {
+        #pragma unroll
+        for (int k = 0; k < 3; ++k)
+        {
+            const int32_t left = (int32_t)M - 64 * k;
+            const uint64_t mask = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
+            pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
+            ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
+            pm[2*k] = (uint32_t)mask;   pm[2*k+1] = (uint32_t)(mask >> 32);
+            pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
+            ql[2*k] = (uint32_t)tlo[k]; ql[2*k+1] = (uint32_t)(tlo[k] >> 32);
+            qh[2*k] = (uint32_t)thi[k]; qh[2*k+1] = (uint32_t)(thi[k] >> 32);
+        }
+        ql[6] = (uint32_t)tlo[3]; qh[6] = (uint32_t)thi[3];
+    }
+    // mismatch word k (rows 32 k .. 32 k + 31) of the diagonal that lies x <= 31 symbols on in the text planes as they stand (x is wave-uniform
+    // wherever this is called: one funnel shift per plane word)
+    __device__ __forceinline__ uint32_t mmw(const int k, const uint32_t x) const
+    {
+        const uint32_t tl = __builtin_amdgcn_alignbit( ql[k + 1], ql[k], x ), th = __builtin_amdgcn_alignbit( qh[k + 1], qh[k], x );
+        return (((pl[k] ^ tl) | (ph[k] ^ th)) & pm[k]) | pn[k];
+    }
+};
+
 // one job of the pass below: scores / sinks as its MODE says, returns the job's flag (what the kernel stores in need_dp[job])
 template <int RBITS, int MODE, bool QUAL>
 __device__ __forceinline__ uint32_t
@@ -1011,37 +1043,14 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
         read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
         text_planes208( tw, tb, tlo, thi );
     }
-    uint64_t rmask[3];
-    #pragma unroll
-    for (int k = 0; k < 3; ++k)
-    {
-        const int32_t left = (int32_t)M - 64 * k;
-        rmask[k] = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
-    }
-
     const uint32_t mb = M + 30u;
     const uint32_t m  = (mb < N ? mb : N) - (M - 1u);
-    // the diagonal loop on 32-bit words: the text planes move down one bit per diagonal (one v_alignbit per word),
-    // a mismatch word is 5 logic ops, and v_bcnt accumulates the count
-    uint32_t pl[6], ph[6], pn[6], pm[6], ql[7], qh[7];
-    #pragma unroll
-    for (int k = 0; k < 3; ++k)
-    {
-        pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
-        ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
-        pm[2*k] = (uint32_t)rmask[k]; pm[2*k+1] = (uint32_t)(rmask[k] >> 32);
-        pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
-    }
-    #pragma unroll
-    for (int k = 0; k < 3; ++k)
-    {
-        ql[2*k] = (uint32_t)tlo[k]; ql[2*k+1] = (uint32_t)(tlo[k] >> 32);
-        qh[2*k] = (uint32_t)thi[k]; qh[2*k+1] = (uint32_t)(thi[k] >> 32);
-    }
-    ql[6] = (uint32_t)tlo[3]; qh[6] = (uint32_t)thi[3];
-    uint32_t ql0[7], qh0[7];
-    #pragma unroll
-    for (int k = 0; k < 7; ++k) { ql0[k] = ql[k]; qh0[k] = qh[k]; }
+    // the diagonal loops on 32-bit words: a mismatch word is 5 logic ops, and v_bcnt accumulates the count.  ql0 / qh0: the text planes as
+    // loaded (diagonal d = d symbols on: one v_alignbit per word); ql / qh: the chances' copy, moved down one bit per diagonal
+    PlaneWords pw;
+    pw.set( rlo, rhi, rn, tlo, thi, M );
+    const uint32_t (&pl)[6] = pw.pl, (&ph)[6] = pw.ph, (&pn)[6] = pw.pn, (&pm)[6] = pw.pm, (&ql0)[7] = pw.ql, (&qh0)[7] = pw.qh;
+    uint32_t ql[7], qh[7];
 
     uint32_t best_cnt = 0xFFFFFFFFu, best_d = 0;
     int64_t U = 0;
@@ -1072,20 +1081,12 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
         for (uint32_t d = 0; d < 31u; ++d)
         {
             const bool on = (d == 0u || d < m);                      // reportable columns are a prefix of 0..30
-            uint32_t cnt;
-            {
-                const uint32_t tl = d ? __builtin_amdgcn_alignbit( ql0[1], ql0[0], d ) : ql0[0], th = d ? __builtin_amdgcn_alignbit( qh0[1], qh0[0], d ) : qh0[0];
-                cnt = (uint32_t)__popc( (((pl[0] ^ tl) | (ph[0] ^ th)) & pm[0]) | pn[0] );
-            }
+            uint32_t cnt = (uint32_t)__popc( pw.mmw( 0, d ) );
             const uint32_t thr = QUAL ? cap : (best_cnt < cap_x ? best_cnt : cap_x);
             if (__any( on && cnt <= thr ))
             {
                 #pragma unroll
-                for (int k = 1; k < 6; ++k)
-                {
-                    const uint32_t tl = d ? __builtin_amdgcn_alignbit( ql0[k + 1], ql0[k], d ) : ql0[k], th = d ? __builtin_amdgcn_alignbit( qh0[k + 1], qh0[k], d ) : qh0[k];
-                    cnt += (uint32_t)__popc( (((pl[k] ^ tl) | (ph[k] ^ th)) & pm[k]) | pn[k] );
-                }
+                for (int k = 1; k < 6; ++k) cnt += (uint32_t)__popc( pw.mmw( k, d ) );
             }
             else cnt = 0xFFFFFFFFu;                                  // (partial, and above every lane's threshold)
             if (QUAL) cnt_d[d] = on ? cnt : 0xFFFFFFFFu;
@@ -1126,9 +1127,7 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
                 #pragma unroll
                 for (int k = 0; k < 6; ++k)
                 {
-                    // the text planes d symbols on (d <= 30 < 32: one funnel shift per word)
-                    const uint32_t tl = __builtin_amdgcn_alignbit( ql0[k + 1], ql0[k], d ), th = __builtin_amdgcn_alignbit( qh0[k + 1], qh0[k], d );
-                    uint32_t mm = (((pl[k] ^ tl) | (ph[k] ^ th)) & pm[k]) | pn[k];
+                    uint32_t mm = pw.mmw( k, d );
                     while (mm)
                     {
                         const uint32_t row = 32u * k + (uint32_t)__builtin_ctz( mm );
@@ -1453,364 +1452,116 @@ ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const 
 // penalty -- costs 14, so a job settles only while its optimum costs 13 or less; the third chance already takes U* >= -11 there, and on the robust
 // batch the pass cost 1.1-1.7 ms for 0.5-1.0 ms of DP saved.  With the ladder taken to four priced mismatches per member (bound 18: two gaps and a
 // mismatch; also built, also green) the DP went 3.9 -> 2.7 ms and the pass cost 2.1: a job costs the pass half a DP and only half of them settle.
-// one job of the gap chance: returns its flag, 0 (settled: scores / sinks written) or 1 (the DP's); has_u: a third-chance job (need_dp = 2)
-// KEEP IN STEP with gap_chance_e2e31_pair below: it repeats this function's plane set-up, last-32-rows words, clean(), walk from both ends,
-// one-gap ladder and two-gap intervals for two jobs at once; a change to any of them here must be made there too
-// (tests/test_gpu_band31_paired_gap_chance.py holds the two to the same oracle).
-template <int RBITS>
-__device__ __forceinline__ uint32_t
-gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
-                     int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const bool has_u)
-{
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = b.win_end[job] - tb;
-    // (flagged by the first pass: 1 <= M <= 161, N >= M + 30, P > 0, open <= ext < 0)
-    // need_dp = 2: a third-chance job -- its best diagonal (2 or 3 mismatches) is in scores / sinks; that ungapped class joins the evaluated ones
-    const int32_t  cu   = has_u ? -scores[job] : 0x7FFFFFFF;
-    const uint32_t cu_end = has_u ? sinks[job].x - M : 0u;
-
-    uint32_t pl[6], ph[6], pn[6], pm[6], ql[7], qh[7];
-    {
-        uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
-        {
-            ReadWords<RBITS> rw; TextWords13 tw;
-            load_read_words<RBITS>( b.reads, first, M, rw );
-            load_text_words13( b.text, tb, N < 192u ? N : 192u, tw );
-            read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
-            text_planes208( tw, tb, tlo, thi );
-        }
-        #pragma unroll
-        for (int k = 0; k < 3; ++k)
-        {
-            const int32_t left = (int32_t)M - 64 * k;
-            const uint64_t mask = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
-            pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
-            ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
-            pm[2*k] = (uint32_t)mask;   pm[2*k+1] = (uint32_t)(mask >> 32);
-            pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
-            ql[2*k] = (uint32_t)tlo[k]; ql[2*k+1] = (uint32_t)(tlo[k] >> 32);
-            qh[2*k] = (uint32_t)thi[k]; qh[2*k+1] = (uint32_t)(thi[k] >> 32);
-        }
-        ql[6] = (uint32_t)tlo[3]; qh[6] = (uint32_t)thi[3];
-    }
-
-    // the cost ladder
-    constexpr int GA = GAP_CHANCE_GA;
-    const int32_t go = gap_open, ge = gap_ext;
-    int32_t cg[GA + 2];                                          // cg[g] = cost of a gap of g symbols
-    #pragma unroll
-    for (int g = 1; g <= GA + 1; ++g) cg[g] = -(go + (g - 1) * ge);
-    cg[0] = 0;
-    const int32_t c_unk = has_u ? lad.c_unk_u : lad.c_unk_n;     // (every OTHER diagonal of a job that brings its best one costs at least c_unk_u)
-    const int32_t cost11 = 2 * cg[1], cost12 = cg[1] + cg[2];
-
-    // mismatch word k (rows 32 k .. 32 k + 31) of diagonal x: the text planes x symbols on (x is wave-uniform: one funnel shift per plane word)
-    auto mmw = [&](const int k, const uint32_t x) -> uint32_t {
-        const uint32_t tl = __builtin_amdgcn_alignbit( ql[k + 1], ql[k], x ), th = __builtin_amdgcn_alignbit( qh[k + 1], qh[k], x );
-        return (((pl[k] ^ tl) | (ph[k] ^ th)) & pm[k]) | pn[k];
-    };
-    // the read's LAST 32 rows (rows base .. base + 31; all of them if it has fewer) and the 62 text symbols they can meet, as words of their own:
-    // bit j of (plT, phT, pnT, pmT) = row base + j, bit j of (qlT, qhT) = text symbol base + j
-    const uint32_t base = M >= 32u ? M - 32u : 0u;
-    uint32_t plT, phT, pnT, pmT, qlT[2], qhT[2];
-    {
-        const uint32_t bw = base >> 5, bs = base & 31u;
-        uint32_t a[4] = { 0, 0, 0, 0 }, c[4] = { 0, 0, 0, 0 }, t[3] = { 0, 0, 0 }, u[3] = { 0, 0, 0 };
-        #pragma unroll
-        for (int k = 0; k < 6; ++k)
-            if (bw == (uint32_t)k)
-            {
-                a[0] = pl[k]; a[1] = k + 1 < 6 ? pl[k + 1] : 0u; a[2] = ph[k]; a[3] = k + 1 < 6 ? ph[k + 1] : 0u;
-                c[0] = pn[k]; c[1] = k + 1 < 6 ? pn[k + 1] : 0u; c[2] = pm[k]; c[3] = k + 1 < 6 ? pm[k + 1] : 0u;
-                t[0] = ql[k]; t[1] = k + 1 < 7 ? ql[k + 1] : 0u; t[2] = k + 2 < 7 ? ql[k + 2] : 0u;
-                u[0] = qh[k]; u[1] = k + 1 < 7 ? qh[k + 1] : 0u; u[2] = k + 2 < 7 ? qh[k + 2] : 0u;
-            }
-        plT = __builtin_amdgcn_alignbit( a[1], a[0], bs ); phT = __builtin_amdgcn_alignbit( a[3], a[2], bs );
-        pnT = __builtin_amdgcn_alignbit( c[1], c[0], bs ); pmT = __builtin_amdgcn_alignbit( c[3], c[2], bs );
-        qlT[0] = __builtin_amdgcn_alignbit( t[1], t[0], bs ); qlT[1] = __builtin_amdgcn_alignbit( t[2], t[1], bs );
-        qhT[0] = __builtin_amdgcn_alignbit( u[1], u[0], bs ); qhT[1] = __builtin_amdgcn_alignbit( u[2], u[1], bs );
-    }
-    auto pen_of = [&](const int32_t) -> int32_t { return P; };   // what a mismatch costs, whatever its row (one penalty for every quality)
-    // history of the last GA diagonals (slot k: diagonal d - 1 - k): (lead0, lead1, lead2) and (tail0, tail1, tail2) packed a byte each (<= 161)
-    uint32_t Lp[GA], Tp[GA];
-    #pragma unroll
-    for (int k = 0; k < GA; ++k) { Lp[k] = 0; Tp[k] = 0; }
-    uint32_t hot = 0;                                            // bit k: slot k's diagonal could be half of a one-gap alignment
-    int32_t best_cost = 0x7FFFFFFF; uint32_t best_end = 0;
-    bool ex11 = false, ex12 = false;
-    uint32_t lng = 0, nmid = 0;                                  // the two-gap gate's history: bit k = diagonal d - 1 - k is `long` / has NO `mid` (below)
-    const int32_t Mi = (int32_t)M;
-    // lead_i(a) + tail_j(c) + g >= M with g <= GA needs one of the two at least (M - GA) / 2: only such diagonals are looked at pair by pair
-    const int32_t hot_thr = (Mi - GA) / 2;
-
-    // no mismatch of diagonal x in rows [lo, hi)?  (lo >= hi: an empty middle segment -- counted as a member.)  f2 / l2: its third mismatch from
-    // either end (M / -1 if it has fewer): nearly always one of them lies inside and no word is looked at
-    auto clean = [&](const uint32_t x, const int32_t bf, const int32_t bl, const int32_t lo, const int32_t hi) -> bool {
-        if (lo >= hi) return true;
-        if ((bf >= lo && bf < hi) || (bl >= lo && bl < hi)) return false;
-        bool any = false;
-        #pragma unroll
-        for (int k = 0; k < 6; ++k)
-        {
-            const int32_t a0 = lo - 32 * k > 0 ? lo - 32 * k : 0, a1 = hi - 32 * k < 32 ? hi - 32 * k : 32;
-            if (a0 < a1)
-            {
-                const uint32_t hi_m = (a1 >= 32) ? 0xFFFFFFFFu : ((1u << a1) - 1u);
-                const uint32_t lo_m = (1u << a0) - 1u;
-                any = any || ((mmw( k, x ) & hi_m & ~lo_m) != 0u);
-            }
-        }
-        return !any;
-    };
-
-    for (uint32_t d = 0; d <= 32u; ++d)
-    {
-        const bool have = d < 31u;
-        // the first three and the last three mismatching rows of diagonal d.  A diagonal that is not the read's own (or its partner across the
-        // indel) holds three mismatches in its first 32 and in its last 32 rows: those two words decide, branch-free; only where some lane of
-        // the wave found fewer are the words walked from both ends, as far as some lane still needs
-        uint32_t f0 = M, f1 = M, f2 = M, l0 = 0xFFFFFFFFu, l1 = 0xFFFFFFFFu, l2 = 0xFFFFFFFFu;
-        bool mid_d = false;
-        if (have)
-        {
-            uint32_t w = mmw( 0, d );
-            if (w) { f0 = (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
-            if (w) { f1 = (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
-            if (w) f2 = (uint32_t)__builtin_ctz( w );
-            const uint32_t tl = __builtin_amdgcn_alignbit( qlT[1], qlT[0], d ), th = __builtin_amdgcn_alignbit( qhT[1], qhT[0], d );
-            w = (((plT ^ tl) | (phT ^ th)) & pmT) | pnT;          // rows base .. base + 31
-            if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = base + t; w &= ~(1u << t); }
-            if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = base + t; w &= ~(1u << t); }
-            if (w) l2 = base + 31u - (uint32_t)__builtin_clz( w );
-            mid_d = M >= 96u && mmw( 1, d ) != 0u;               // a mismatch in rows 32 .. 63, all of them rows of the read and below its last 32
-        }
-        if (have && __any( M > 32u && (f2 == M || l2 == 0xFFFFFFFFu) ))
-        {
-            f0 = f1 = f2 = M; l0 = l1 = l2 = 0xFFFFFFFFu;
-            #pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (__any( f2 == M && pm[k] != 0u ))
-                {
-                    uint32_t w = (f2 == M) ? mmw( k, d ) : 0u;
-                    if (f0 == M && w) { f0 = 32u * k + (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
-                    if (f0 != M && f1 == M && w) { f1 = 32u * k + (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
-                    if (f1 != M && f2 == M && w) f2 = 32u * k + (uint32_t)__builtin_ctz( w );
-                }
-            #pragma unroll
-            for (int k = 5; k >= 0; --k)
-                if (__any( l2 == 0xFFFFFFFFu && pm[k] != 0u ))
-                {
-                    uint32_t w = (l2 == 0xFFFFFFFFu) ? mmw( k, d ) : 0u;
-                    if (l0 == 0xFFFFFFFFu && w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = 32u * k + t; w &= ~(1u << t); }
-                    if (l0 != 0xFFFFFFFFu && l1 == 0xFFFFFFFFu && w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = 32u * k + t; w &= ~(1u << t); }
-                    if (l1 != 0xFFFFFFFFu && l2 == 0xFFFFFFFFu && w) l2 = 32u * k + 31u - (uint32_t)__builtin_clz( w );
-                }
-        }
-        const int32_t L0 = (int32_t)f0, L1 = (int32_t)f1, L2 = (int32_t)f2;          // rows before the 1st / 2nd / 3rd mismatch
-        const int32_t T0 = l0 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l0;             // rows after the last / last-but-one / last-but-two
-        const int32_t T1 = l1 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l1;
-        const int32_t T2 = l2 == 0xFFFFFFFFu ? Mi : Mi - 1 - (int32_t)l2;
-        const bool hot_d = have && (L2 >= hot_thr || T2 >= hot_thr);
-        const bool long_d = have && (L0 >= 30 || T0 >= 30);
-
-        if (have && __any( hot_d || (hot & 31u) != 0u ))
-        {
-            #pragma unroll
-            for (int g = 1; g <= GA; ++g)
-                if (d >= (uint32_t)g && (hot_d || ((hot >> (g - 1)) & 1u)))
-                {
-                    const int32_t a0 = (int32_t)(Lp[g - 1] & 255u), a1 = (int32_t)((Lp[g - 1] >> 8) & 255u), a2 = (int32_t)(Lp[g - 1] >> 16);
-                    const int32_t t0 = (int32_t)(Tp[g - 1] & 255u), t1 = (int32_t)((Tp[g - 1] >> 8) & 255u), t2 = (int32_t)(Tp[g - 1] >> 16);
-                    // text gap of g: diagonal d - g (prefix), then d (suffix); ends in column d
-                    if (a2 + T2 >= Mi)
-                    {
-                        const int32_t pa[2] = { pen_of( a0 ), pen_of( a1 ) };                     // the prefix diagonal's first / second mismatch
-                        const int32_t pt[2] = { pen_of( Mi - 1 - T0 ), pen_of( Mi - 1 - T1 ) };   // the suffix diagonal's last / last-but-one
-                        const int32_t lead[3] = { a0, a1, a2 }, tail[3] = { T0, T1, T2 };
-                        int32_t c = 0x7FFFFFFF;
-                        #pragma unroll
-                        for (int i = 0; i <= 2; ++i)
-                            #pragma unroll
-                            for (int j = 0; i + j <= 2; ++j)
-                                if (lead[i] + tail[j] >= Mi)
-                                {
-                                    const int32_t x = cg[g] + (i > 0 ? pa[0] : 0) + (i > 1 ? pa[1] : 0) + (j > 0 ? pt[0] : 0) + (j > 1 ? pt[1] : 0);
-                                    c = x < c ? x : c;
-                                }
-                        if (c != 0x7FFFFFFF && (c < best_cost || (c == best_cost && d > best_end))) { best_cost = c; best_end = d; }
-                    }
-                    // pattern gap of g: diagonal d (prefix), then d - g (suffix); ends in column d - g
-                    if (L2 + t2 + g >= Mi)
-                    {
-                        const int32_t pa[2] = { pen_of( L0 ), pen_of( L1 ) };
-                        const int32_t pt[2] = { pen_of( Mi - 1 - t0 ), pen_of( Mi - 1 - t1 ) };
-                        const int32_t lead[3] = { L0, L1, L2 }, tail[3] = { t0, t1, t2 };
-                        int32_t c = 0x7FFFFFFF;
-                        #pragma unroll
-                        for (int i = 0; i <= 2; ++i)
-                            #pragma unroll
-                            for (int j = 0; i + j <= 2; ++j)
-                                if (lead[i] + tail[j] + g >= Mi)
-                                {
-                                    const int32_t x = cg[g] + (i > 0 ? pa[0] : 0) + (i > 1 ? pa[1] : 0) + (j > 0 ? pt[0] : 0) + (j > 1 ? pt[1] : 0);
-                                    c = x < c ? x : c;
-                                }
-                        const uint32_t end = d - (uint32_t)g;
-                        if (c != 0x7FFFFFFF && (c < best_cost || (c == best_cost && end > best_end))) { best_cost = c; best_end = end; }
-                    }
-                }
-        }
-        // two gaps around the middle diagonal bm = d - 2 (history slot 1): neighbours bm - 2 (slot 3), bm - 1 (slot 2), bm + 1 (slot 0),
-        // bm + 2 (this diagonal).
-        // THE GATE.  Each test below asks whether bm is clean on [lo, hi) with lo <= lead0(a) + 2 and hi >= M - tail0(c) - 2 for neighbours a, c
-        // of bm.  If no neighbour is `long` (lead0 >= 30 or tail0 >= 30) then lo <= 31 and hi >= M - 31; if besides bm has a `mid` (M >= 96 and a
-        // mismatch in rows 32 .. 63) then M - 31 >= 65, so lo < hi, rows 32 .. 63 lie inside [lo, hi) and bm is NOT clean there: all three tests
-        // are false and ex11 / ex12 stay as they are.  The block is skipped for a diagonal where that holds for EVERY lane of the wave: an
-        // unrelated diagonal has its first and last mismatch within a few rows of the ends and one in any 32 rows, so only the diagonals
-        // around some lane's own ones (and those of the few lanes with M < 96) still run it.  Nothing is approximated: a skipped test is a
-        // test whose outcome is known to be "no member".
-        if (d >= 2u && __any( long_d || (lng & 0xDu) != 0u || (nmid & 2u) != 0u ))
-        {
-            const uint32_t bm = d - 2u;                            // <= 30
-            const int32_t NEG = -(1 << 20), POS = 1 << 20;
-            int32_t lo1 = NEG, lo2 = NEG, hi1 = POS, hi2 = POS;
-            if (bm >= 1u)       { lo1 = (int32_t)(Lp[2] & 255u);    hi1 = Mi - (int32_t)(Tp[2] & 255u) - 1; }      // a = bm - 1: text gap in; c = bm - 1: pattern gap out
-            if (bm + 1u <= 30u) { const int32_t x = (int32_t)(Lp[0] & 255u) + 1, y = Mi - (int32_t)(Tp[0] & 255u); lo1 = x > lo1 ? x : lo1; hi1 = y < hi1 ? y : hi1; }
-            if (bm >= 2u)       { lo2 = (int32_t)(Lp[3] & 255u);    hi2 = Mi - (int32_t)(Tp[3] & 255u) - 2; }      // a / c = bm - 2
-            if (have)           { const int32_t x = L0 + 2, y = Mi - T0; lo2 = x > lo2 ? x : lo2; hi2 = y < hi2 ? y : hi2; }   // a / c = bm + 2
-            // the middle diagonal's third mismatch from either end (first / last if it has fewer): a row that is NOT clean
-            const int32_t b2 = (int32_t)(Lp[1] >> 16), b1 = (int32_t)((Lp[1] >> 8) & 255u), b0 = (int32_t)(Lp[1] & 255u);
-            const int32_t bf = b2 < Mi ? b2 : (b1 < Mi ? b1 : b0);
-            const int32_t e2 = (int32_t)(Tp[1] >> 16), e1 = (int32_t)((Tp[1] >> 8) & 255u), e0 = (int32_t)(Tp[1] & 255u);
-            const int32_t et = e2 < Mi ? e2 : (e1 < Mi ? e1 : e0);
-            const int32_t bl = et < Mi ? Mi - 1 - et : NEG;
-            if (lo1 > NEG && hi1 < POS) ex11 = ex11 || clean( bm, bf, bl, lo1, hi1 );
-            if (lo1 > NEG && hi2 < POS) ex12 = ex12 || clean( bm, bf, bl, lo1, hi2 );
-            if (lo2 > NEG && hi1 < POS) ex12 = ex12 || clean( bm, bf, bl, lo2, hi1 );
-        }
-        // shift the history
-        #pragma unroll
-        for (int k = GA - 1; k > 0; --k) { Lp[k] = Lp[k - 1]; Tp[k] = Tp[k - 1]; }
-        Lp[0] = (uint32_t)L0 | ((uint32_t)L1 << 8) | ((uint32_t)L2 << 16);
-        Tp[0] = (uint32_t)T0 | ((uint32_t)T1 << 8) | ((uint32_t)T2 << 16);
-        hot = (hot << 1) | (hot_d ? 1u : 0u);
-        lng = (lng << 1) | (long_d ? 1u : 0u);
-        nmid = (nmid << 1) | (mid_d ? 0u : 1u);
-    }
-    if (cu < best_cost || (cu == best_cost && cu_end > best_end)) { best_cost = cu; best_end = cu_end; }
-    const bool settled = best_cost < c_unk && !(ex11 && cost11 <= best_cost) && !(ex12 && cost12 <= best_cost);
-    if (settled) { scores[job] = -best_cost; sinks[job] = make_uint2( M + best_end, M ); return 0u; }
-    return 1u;
-}
-
-// TWO jobs of the gap chance in one: `job` and job + 1, partners by gap_pair_role, both flagged 4 by the first pass -- the same read on the same
+// ONE walk for both shapes of gap-chance entry.  PAIR = false: the single job `job` (has_u: a third-chance job, need_dp = 2).
+// PAIR = true: TWO jobs in one, `job` and job + 1, partners by gap_pair_role, both flagged 4 by the first pass -- the same read on the same
 // strand, windows of M + 31 symbols that begin sh = 1 .. PAIR_MAX_SHIFT columns apart; the LOWER job is the one whose window begins first, the
-// UPPER job the other (either may be `job`).  Diagonal d of the upper job IS diagonal D = d + sh of the
-// lower one (the same rows against the same text symbols), so the read's planes are built once, the text's for the union window of M + 31 + sh
-// symbols, and the 31 + sh diagonals D are walked once with the per-diagonal code of gap_chance_e2e31_job (the first and last 32 rows, the walk
-// from both ends where some lane needs it, the packed history, the hot-half test, the two-gap gate).  What a diagonal yields -- its first and
-// last three mismatches -- does not depend on the job; which alignments COUNT does: a job's classes are those whose diagonals all lie in its own
-// band, D in [0, 30] for the lower job, [sh, 30 + sh] for the upper.  Hence two sets of accumulators (c*, the largest end column among the
-// members that reach it -- columns relative to the job's own win_begin --, the two-gap existence bits), each fed by exactly the tests the
-// single job runs at its diagonal d = D resp. D - sh, with the single job's guards taken in the job's own numbering (d >= g, the middle
-// diagonal's neighbours inside 0 .. 30).  The cost of a one-gap member is the same for both; the two-gap intervals differ only next to a
-// band's edge and are otherwise evaluated once.  The wave-level gates are taken over both jobs' diagonals: they only ever skip tests whose
-// outcome is known (see the single job), so a wider gate changes no result.  Each job then settles by the single job's condition with
-// c_unk_n (a flag-4 job: every diagonal of its own band has more than `cap` mismatches).
-// The text planes hold 224 bits and a funnel shift reaches 31: from D = 6 on the planes are kept 4 symbols down (the lowest diagonal still
+// UPPER job the other (either may be `job`).  Diagonal d of the upper job IS diagonal D = d + sh of the lower one (the same rows against the
+// same text symbols), so the read's planes are built once, the text's for the union window of M + 31 + sh symbols, and the 31 + sh diagonals
+// D are walked once.  What a diagonal yields -- its first and last three mismatches -- does not depend on the job; which alignments COUNT
+// does: a job's classes are those whose diagonals all lie in its own band, D in [0, 30] for the lower job, [sh, 30 + sh] for the upper.  Hence
+// one set of accumulators per job (c* and the largest end column among the members that reach it -- columns relative to the job's own
+// win_begin --, the two-gap existence bits), each fed at the job's own diagonal d = D resp. D - sh with its guards in the job's own numbering
+// (d >= g, the middle diagonal's neighbours inside 0 .. 30).  The cost of a one-gap member is the same for both; the two-gap intervals differ
+// only next to a band's edge and are otherwise evaluated once.  The single job is the pair's degenerate case: sh = 0, the lower job alone,
+// diagonals 0 .. 32, 13 text words, and the third-chance join (below), which only it has.
+// The wave-level gates are taken over every job's diagonals: they only ever skip tests whose outcome is known, so a wider gate changes no
+// result.  Each job settles with c_unk_n (a flag-4 job: every diagonal of its own band has more than `cap` mismatches), a third-chance job
+// with c_unk_u.
+// The pair's text planes hold 224 bits and a funnel shift reaches 31: from D = 6 on they are kept 4 symbols down (the lowest diagonal still
 // looked at is then the two-gap block's middle one, D - 2 >= 4), which keeps every shift within 0 .. 31 up to D = 35.
-// Returns the two flags: bit 0 `job`'s, bit 1 job + 1's (0: settled, scores / sinks written; 1: the DP's).
-// KEEP IN STEP with gap_chance_e2e31_job above (see the note there): the per-diagonal code is that function's, line for line.
-template <int RBITS>
+// Returns the flags (0: settled, scores / sinks written; 1: the DP's): bit 0 `job`'s, PAIR: bit 1 job + 1's.
+template <int RBITS, bool PAIR>
 __device__ __forceinline__ uint32_t
-gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
-                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job)
+gap_chance_e2e31_walk(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
+                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const bool has_u)
 {
+    constexpr int NJ = PAIR ? 2 : 1;                             // accumulator sets: [0] the lower (or only) job, [1] the upper job
     const uint32_t rid   = b.read_id ? b.read_id[job] : job;
     const uint32_t first = b.read_offsets[rid];
     const uint32_t M     = b.read_offsets[rid + 1] - first;
     const uint32_t fl    = b.flags ? b.flags[job] : 0u;
     const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
     const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb0 = b.win_begin[job], tb1 = b.win_begin[job + 1u];
-    const uint32_t up    = tb1 > tb0 ? 1u : 0u;                  // which of the two is the upper job: job + up (the lower: job + 1 - up)
-    const uint32_t tb    = up ? tb0 : tb1;
-    const uint32_t sh    = up ? tb1 - tb0 : tb0 - tb1;           // 1 .. PAIR_MAX_SHIFT
-    // (partners flagged 4: 1 <= M <= 161, both windows M + 31 symbols, P > 0, open <= ext < 0)
+    // (flagged by the first pass: 1 <= M <= 161, N >= M + 30 -- partners: both windows M + 31 symbols --, P > 0, open <= ext < 0)
+    uint32_t tb = b.win_begin[job], up = 0u, sh = 0u;
+    if constexpr (PAIR)
+    {
+        const uint32_t tb1 = b.win_begin[job + 1u];
+        up = tb1 > tb ? 1u : 0u;                                 // which of the two is the upper job: job + up (the lower: job + 1 - up)
+        sh = up ? tb1 - tb : tb - tb1;                           // 1 .. PAIR_MAX_SHIFT
+        tb = up ? tb : tb1;
+    }
+    // c* and the largest end column among the members that reach it, as ONE number per job: cost << 6 | 63 - column
+    // (columns <= 30; a member costs cg[g] + (i + j) P with g <= 5, i + j <= 2, and launch_pk runs only under packed_ok(), which holds every
+    // penalty to 4096: costs stay below 2^15, the key needs them below 2^26 -- a wider limit there must be matched here): the least key is the
+    // least cost and, among equals, the largest column, as BestSink's `<=`
+    uint32_t best_key[NJ];
+    #pragma unroll
+    for (int j = 0; j < NJ; ++j) best_key[j] = 0xFFFFFFFFu;
+    auto take = [&](const int j, const int32_t c, const uint32_t end) {
+        const uint32_t key = ((uint32_t)c << 6) | (63u - end);
+        best_key[j] = key < best_key[j] ? key : best_key[j];
+    };
+    // need_dp = 2: a third-chance job -- its best diagonal (2 or 3 mismatches) is in scores / sinks; that ungapped class joins the evaluated ones
+    if (!PAIR && has_u) take( 0, -scores[job], sinks[job].x - M );
 
-    uint32_t pl[6], ph[6], pn[6], pm[6], ql[7], qh[7];
+    PlaneWords pw;
     {
         uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
+        ReadWords<RBITS> rw;
+        load_read_words<RBITS>( b.reads, first, M, rw );
+        if constexpr (PAIR)
         {
-            ReadWords<RBITS> rw; TextWords14 tw;
-            load_read_words<RBITS>( b.reads, first, M, rw );
+            TextWords14 tw;
             load_text_words14( b.text, tb, M + 31u + sh, tw );
             read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
             text_planes224( tw, tb, tlo, thi );
         }
-        #pragma unroll
-        for (int k = 0; k < 3; ++k)
+        else
         {
-            const int32_t left = (int32_t)M - 64 * k;
-            const uint64_t mask = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
-            pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
-            ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
-            pm[2*k] = (uint32_t)mask;   pm[2*k+1] = (uint32_t)(mask >> 32);
-            pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
-            ql[2*k] = (uint32_t)tlo[k]; ql[2*k+1] = (uint32_t)(tlo[k] >> 32);
-            qh[2*k] = (uint32_t)thi[k]; qh[2*k+1] = (uint32_t)(thi[k] >> 32);
+            TextWords13 tw;
+            const uint32_t N = b.win_end[job] - tb;
+            load_text_words13( b.text, tb, N < 192u ? N : 192u, tw );
+            read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
+            text_planes208( tw, tb, tlo, thi );
         }
-        ql[6] = (uint32_t)tlo[3]; qh[6] = (uint32_t)thi[3];
+        pw.set( rlo, rhi, rn, tlo, thi, M );
     }
 
     // the cost ladder
     constexpr int GA = GAP_CHANCE_GA;
-    const int32_t go = gap_open, ge = gap_ext;
-    int32_t cg[GA + 2];                                          // cg[g] = cost of a gap of g symbols
+    int32_t cg[GA + 1];                                          // cg[g] = cost of a gap of g symbols
     #pragma unroll
-    for (int g = 1; g <= GA + 1; ++g) cg[g] = -(go + (g - 1) * ge);
-    cg[0] = 0;
-    const int32_t c_unk = lad.c_unk_n;
+    for (int g = 1; g <= GA; ++g) cg[g] = -(gap_open + (g - 1) * gap_ext);
+    const int32_t c_unk = (!PAIR && has_u) ? lad.c_unk_u : lad.c_unk_n;     // (every OTHER diagonal of a job that brings its best one costs at least c_unk_u)
     const int32_t cost11 = 2 * cg[1], cost12 = cg[1] + cg[2];
 
-    // mismatch word k (rows 32 k .. 32 k + 31) of the diagonal that lies x symbols on in the planes as they stand (x is wave-uniform)
-    auto mmw = [&](const int k, const uint32_t x) -> uint32_t {
-        const uint32_t tl = __builtin_amdgcn_alignbit( ql[k + 1], ql[k], x ), th = __builtin_amdgcn_alignbit( qh[k + 1], qh[k], x );
-        return (((pl[k] ^ tl) | (ph[k] ^ th)) & pm[k]) | pn[k];
-    };
     // the read's LAST 32 rows (rows base .. base + 31; all of them if it has fewer) and the text symbols they can meet, as words of their own:
     // bit j of (plT, phT, pnT, pmT) = row base + j, bit j of (qlT, qhT) = text symbol base + j
     const uint32_t base = M >= 32u ? M - 32u : 0u;
+    const uint32_t bw = base >> 5, bs = base & 31u;
     uint32_t plT, phT, pnT, pmT, qlT[2], qhT[2];
     {
-        const uint32_t bw = base >> 5, bs = base & 31u;
         uint32_t a[4] = { 0, 0, 0, 0 }, c[4] = { 0, 0, 0, 0 };
         #pragma unroll
         for (int k = 0; k < 6; ++k)
             if (bw == (uint32_t)k)
             {
-                a[0] = pl[k]; a[1] = k + 1 < 6 ? pl[k + 1] : 0u; a[2] = ph[k]; a[3] = k + 1 < 6 ? ph[k + 1] : 0u;
-                c[0] = pn[k]; c[1] = k + 1 < 6 ? pn[k + 1] : 0u; c[2] = pm[k]; c[3] = k + 1 < 6 ? pm[k + 1] : 0u;
+                a[0] = pw.pl[k]; a[1] = k + 1 < 6 ? pw.pl[k + 1] : 0u; a[2] = pw.ph[k]; a[3] = k + 1 < 6 ? pw.ph[k + 1] : 0u;
+                c[0] = pw.pn[k]; c[1] = k + 1 < 6 ? pw.pn[k + 1] : 0u; c[2] = pw.pm[k]; c[3] = k + 1 < 6 ? pw.pm[k + 1] : 0u;
             }
         plT = __builtin_amdgcn_alignbit( a[1], a[0], bs ); phT = __builtin_amdgcn_alignbit( a[3], a[2], bs );
         pnT = __builtin_amdgcn_alignbit( c[1], c[0], bs ); pmT = __builtin_amdgcn_alignbit( c[3], c[2], bs );
     }
-    // (the text's two words: 64 symbols from `base` on in the planes as they stand -- taken again when the planes move down, see D == 6 below)
+    // (the text's two words: 64 symbols from `base` on in the planes as they stand -- taken again when the pair's planes move down, see D == 6 below)
     auto tail_text = [&]() {
-        const uint32_t bw = base >> 5, bs = base & 31u;
         uint32_t t[3] = { 0, 0, 0 }, u[3] = { 0, 0, 0 };
         #pragma unroll
         for (int k = 0; k < 6; ++k)
             if (bw == (uint32_t)k)
             {
-                t[0] = ql[k]; t[1] = k + 1 < 7 ? ql[k + 1] : 0u; t[2] = k + 2 < 7 ? ql[k + 2] : 0u;
-                u[0] = qh[k]; u[1] = k + 1 < 7 ? qh[k + 1] : 0u; u[2] = k + 2 < 7 ? qh[k + 2] : 0u;
+                t[0] = pw.ql[k]; t[1] = k + 1 < 7 ? pw.ql[k + 1] : 0u; t[2] = k + 2 < 7 ? pw.ql[k + 2] : 0u;
+                u[0] = pw.qh[k]; u[1] = k + 1 < 7 ? pw.qh[k + 1] : 0u; u[2] = k + 2 < 7 ? pw.qh[k + 2] : 0u;
             }
         qlT[0] = __builtin_amdgcn_alignbit( t[1], t[0], bs ); qlT[1] = __builtin_amdgcn_alignbit( t[2], t[1], bs );
         qhT[0] = __builtin_amdgcn_alignbit( u[1], u[0], bs ); qhT[1] = __builtin_amdgcn_alignbit( u[2], u[1], bs );
@@ -1821,18 +1572,18 @@ gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, c
     #pragma unroll
     for (int k = 0; k < GA; ++k) { Lp[k] = 0; Tp[k] = 0; }
     // three histories of the last diagonals in one word, a byte each: bit k = diagonal D - 1 - k could be half of a one-gap alignment (`hot`) /
-    // bit 8 + k = it is `long` / bit 16 + k = it has NO `mid` (the two-gap gate, see the single job)
+    // bit 8 + k = it is `long` / bit 16 + k = it has NO `mid` (the two-gap gate, below)
     uint32_t hist = 0;
-    // c* and the largest end column among the members that reach it, as ONE number per job: cost << 6 | 63 - column
-    // (columns <= 30; a member costs cg[g] + (i + j) P with g <= 5, i + j <= 2, and launch_pk runs only under packed_ok(), which holds every
-    // penalty to 4096: costs stay below 2^15, the key needs them below 2^26 -- a wider limit there must be matched here): the least key is the
-    // least cost and, among equals, the largest column, which is the single job's `c < best || (c == best && end > best_end)`
-    uint32_t best_key[2] = { 0xFFFFFFFFu, 0xFFFFFFFFu };        // [0]: the lower job, [1]: the upper job
-    bool ex11[2] = { false, false }, ex12[2] = { false, false };
+    bool ex11[NJ], ex12[NJ];
+    #pragma unroll
+    for (int j = 0; j < NJ; ++j) { ex11[j] = false; ex12[j] = false; }
     const int32_t Mi = (int32_t)M;
+    // lead_i(a) + tail_j(c) + g >= M with g <= GA needs one of the two at least (M - GA) / 2: only such diagonals are looked at pair by pair
     const int32_t hot_thr = (Mi - GA) / 2;
     uint32_t xo = 0;                                             // the planes stand xo symbols down
 
+    // no mismatch of the diagonal x symbols on in rows [lo, hi)?  (lo >= hi: an empty middle segment -- counted as a member.)  bf / bl: its third
+    // mismatch from either end (first / last if it has fewer): nearly always one of them lies inside and no word is looked at
     auto clean = [&](const uint32_t x, const int32_t bf, const int32_t bl, const int32_t lo, const int32_t hi) -> bool {
         if (lo >= hi) return true;
         if ((bf >= lo && bf < hi) || (bl >= lo && bl < hi)) return false;
@@ -1845,40 +1596,42 @@ gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, c
             {
                 const uint32_t hi_m = (a1 >= 32) ? 0xFFFFFFFFu : ((1u << a1) - 1u);
                 const uint32_t lo_m = (1u << a0) - 1u;
-                any = any || ((mmw( k, x ) & hi_m & ~lo_m) != 0u);
+                any = any || ((pw.mmw( k, x ) & hi_m & ~lo_m) != 0u);
             }
         }
         return !any;
     };
-    auto take = [&](const int j, const int32_t c, const uint32_t end) {
-        const uint32_t key = ((uint32_t)c << 6) | (63u - end);
-        best_key[j] = key < best_key[j] ? key : best_key[j];
-    };
 
-    for (uint32_t D = 0; D <= 32u + PAIR_MAX_SHIFT; ++D)
+    for (uint32_t D = 0; D <= 32u + (PAIR ? PAIR_MAX_SHIFT : 0u); ++D)
     {
-        if (!__any( D <= 32u + sh )) break;                      // (wave-uniform: the largest shift of the wave's pairs)
-        if (D == 6u)
+        if constexpr (PAIR)
         {
-            #pragma unroll
-            for (int k = 0; k < 6; ++k)
+            if (!__any( D <= 32u + sh )) break;                  // (wave-uniform: the largest shift of the wave's pairs)
+            if (D == 6u)
             {
-                ql[k] = __builtin_amdgcn_alignbit( ql[k + 1], ql[k], 4u );
-                qh[k] = __builtin_amdgcn_alignbit( qh[k + 1], qh[k], 4u );
+                #pragma unroll
+                for (int k = 0; k < 6; ++k)
+                {
+                    pw.ql[k] = __builtin_amdgcn_alignbit( pw.ql[k + 1], pw.ql[k], 4u );
+                    pw.qh[k] = __builtin_amdgcn_alignbit( pw.qh[k + 1], pw.qh[k], 4u );
+                }
+                pw.ql[6] >>= 4; pw.qh[6] >>= 4;
+                tail_text();
+                xo = 4u;
             }
-            ql[6] >>= 4; qh[6] >>= 4;
-            tail_text();
-            xo = 4u;
         }
         const uint32_t x = D - xo;                               // <= 31
-        const bool have = D <= 30u + sh;                         // a diagonal of the union window
+        const bool have = D <= 30u + sh;                         // a diagonal of the (union) window
         const int32_t dU = (int32_t)D - (int32_t)sh;             // this diagonal in the upper job's numbering
         const bool haveL = D <= 30u;                             // ... of the lower job's own band (the upper one's: 0 <= dU <= 30)
+        // the first three and the last three mismatching rows of diagonal D.  A diagonal that is not the read's own (or its partner across the
+        // indel) holds three mismatches in its first 32 and in its last 32 rows: those two words decide, branch-free; only where some lane of
+        // the wave found fewer are the words walked from both ends, as far as some lane still needs
         uint32_t f0 = M, f1 = M, f2 = M, l0 = 0xFFFFFFFFu, l1 = 0xFFFFFFFFu, l2 = 0xFFFFFFFFu;
         bool mid_d = false;
         if (have)
         {
-            uint32_t w = mmw( 0, x );
+            uint32_t w = pw.mmw( 0, x );
             if (w) { f0 = (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
             if (w) { f1 = (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
             if (w) f2 = (uint32_t)__builtin_ctz( w );
@@ -1887,25 +1640,25 @@ gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, c
             if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = base + t; w &= ~(1u << t); }
             if (w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = base + t; w &= ~(1u << t); }
             if (w) l2 = base + 31u - (uint32_t)__builtin_clz( w );
-            mid_d = M >= 96u && mmw( 1, x ) != 0u;               // a mismatch in rows 32 .. 63, all of them rows of the read and below its last 32
+            mid_d = M >= 96u && pw.mmw( 1, x ) != 0u;            // a mismatch in rows 32 .. 63, all of them rows of the read and below its last 32
         }
         if (__any( have && M > 32u && (f2 == M || l2 == 0xFFFFFFFFu) ))
         {
             f0 = f1 = f2 = M; l0 = l1 = l2 = 0xFFFFFFFFu;
             #pragma unroll
             for (int k = 0; k < 6; ++k)
-                if (__any( have && f2 == M && pm[k] != 0u ))
+                if (__any( have && f2 == M && pw.pm[k] != 0u ))
                 {
-                    uint32_t w = (have && f2 == M) ? mmw( k, x ) : 0u;
+                    uint32_t w = (have && f2 == M) ? pw.mmw( k, x ) : 0u;
                     if (f0 == M && w) { f0 = 32u * k + (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
                     if (f0 != M && f1 == M && w) { f1 = 32u * k + (uint32_t)__builtin_ctz( w ); w &= w - 1u; }
                     if (f1 != M && f2 == M && w) f2 = 32u * k + (uint32_t)__builtin_ctz( w );
                 }
             #pragma unroll
             for (int k = 5; k >= 0; --k)
-                if (__any( have && l2 == 0xFFFFFFFFu && pm[k] != 0u ))
+                if (__any( have && l2 == 0xFFFFFFFFu && pw.pm[k] != 0u ))
                 {
-                    uint32_t w = (have && l2 == 0xFFFFFFFFu) ? mmw( k, x ) : 0u;
+                    uint32_t w = (have && l2 == 0xFFFFFFFFu) ? pw.mmw( k, x ) : 0u;
                     if (l0 == 0xFFFFFFFFu && w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l0 = 32u * k + t; w &= ~(1u << t); }
                     if (l0 != 0xFFFFFFFFu && l1 == 0xFFFFFFFFu && w) { const uint32_t t = 31u - (uint32_t)__builtin_clz( w ); l1 = 32u * k + t; w &= ~(1u << t); }
                     if (l1 != 0xFFFFFFFFu && l2 == 0xFFFFFFFFu && w) l2 = 32u * k + 31u - (uint32_t)__builtin_clz( w );
@@ -1925,55 +1678,59 @@ gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, c
                 if (have && D >= (uint32_t)g && (hot_d || ((hist >> (g - 1)) & 1u)))
                 {
                     // the member's two diagonals D - g and D lie in the lower job's band iff D <= 30, in the upper one's iff D - g >= sh
-                    const bool inL = haveL, inU = dU >= g;
+                    const bool inL = haveL, inU = PAIR && dU >= g;
                     const int32_t a0 = (int32_t)(Lp[g - 1] & 255u), a1 = (int32_t)((Lp[g - 1] >> 8) & 255u), a2 = (int32_t)(Lp[g - 1] >> 16);
                     const int32_t t0 = (int32_t)(Tp[g - 1] & 255u), t1 = (int32_t)((Tp[g - 1] >> 8) & 255u), t2 = (int32_t)(Tp[g - 1] >> 16);
-                    // text gap of g: diagonal D - g (prefix), then D (suffix); ends in column D
-                    if (a2 + T2 >= Mi)
-                    {
-                        const int32_t lead[3] = { a0, a1, a2 }, tail[3] = { T0, T1, T2 };
+                    // the cheapest member of a gap of g with a prefix of `lead` rows, a suffix of `tail` rows and `more` rows between them
+                    auto cheapest = [&](const int32_t (&lead)[3], const int32_t (&tail)[3], const int32_t more) -> int32_t {
                         int32_t c = 0x7FFFFFFF;
                         #pragma unroll
                         for (int i = 0; i <= 2; ++i)
                             #pragma unroll
                             for (int j = 0; i + j <= 2; ++j)
-                                if (lead[i] + tail[j] >= Mi)
+                                if (lead[i] + tail[j] + more >= Mi)
                                 {
                                     const int32_t v = cg[g] + (i + j) * P;
                                     c = v < c ? v : c;
                                 }
+                        return c;
+                    };
+                    // text gap of g: diagonal D - g (prefix), then D (suffix); ends in column D
+                    if (a2 + T2 >= Mi)
+                    {
+                        const int32_t lead[3] = { a0, a1, a2 }, tail[3] = { T0, T1, T2 };
+                        const int32_t c = cheapest( lead, tail, 0 );
                         if (c != 0x7FFFFFFF)
                         {
                             if (inL) take( 0, c, D );
-                            if (inU) take( 1, c, (uint32_t)dU );
+                            if constexpr (PAIR) if (inU) take( 1, c, (uint32_t)dU );
                         }
                     }
                     // pattern gap of g: diagonal D (prefix), then D - g (suffix); ends in column D - g
                     if (L2 + t2 + g >= Mi)
                     {
                         const int32_t lead[3] = { L0, L1, L2 }, tail[3] = { t0, t1, t2 };
-                        int32_t c = 0x7FFFFFFF;
-                        #pragma unroll
-                        for (int i = 0; i <= 2; ++i)
-                            #pragma unroll
-                            for (int j = 0; i + j <= 2; ++j)
-                                if (lead[i] + tail[j] + g >= Mi)
-                                {
-                                    const int32_t v = cg[g] + (i + j) * P;
-                                    c = v < c ? v : c;
-                                }
+                        const int32_t c = cheapest( lead, tail, g );
                         if (c != 0x7FFFFFFF)
                         {
                             if (inL) take( 0, c, D - (uint32_t)g );
-                            if (inU) take( 1, c, (uint32_t)(dU - g) );
+                            if constexpr (PAIR) if (inU) take( 1, c, (uint32_t)(dU - g) );
                         }
                     }
                 }
         }
-        // two gaps around the middle diagonal D - 2 (history slot 1), as in the single job: for the lower job it is its diagonal bm = D - 2 at its
-        // iterations d = D in 2 .. 32, for the upper one bm = dU - 2 at d = dU in 2 .. 32; a neighbour counts iff it lies in the job's band
-        const bool actL = D >= 2u && D <= 32u, actU = dU >= 2 && dU <= 32;
-        if (__any( (actL || actU) && (long_d || (hist & 0x20D00u) != 0u) ))        // lng & 0xD, nmid & 2
+        // two gaps around the middle diagonal D - 2 (history slot 1): neighbours D - 4 (slot 3), D - 3 (slot 2), D - 1 (slot 0), D (this diagonal).
+        // For the lower job it is its diagonal bm = D - 2 at its iterations d = D in 2 .. 32, for the upper one bm = dU - 2 at d = dU in 2 .. 32;
+        // a neighbour counts iff it lies in the job's band.
+        // THE GATE.  Each test below asks whether bm is clean on [lo, hi) with lo <= lead0(a) + 2 and hi >= M - tail0(c) - 2 for neighbours a, c
+        // of bm.  If no neighbour is `long` (lead0 >= 30 or tail0 >= 30) then lo <= 31 and hi >= M - 31; if besides bm has a `mid` (M >= 96 and a
+        // mismatch in rows 32 .. 63) then M - 31 >= 65, so lo < hi, rows 32 .. 63 lie inside [lo, hi) and bm is NOT clean there: all three tests
+        // are false and ex11 / ex12 stay as they are.  The block is skipped for a diagonal where that holds for EVERY lane of the wave: an
+        // unrelated diagonal has its first and last mismatch within a few rows of the ends and one in any 32 rows, so only the diagonals
+        // around some lane's own ones (and those of the few lanes with M < 96) still run it.  Nothing is approximated: a skipped test is a
+        // test whose outcome is known to be "no member".
+        const bool actL = D >= 2u && D <= 32u, actU = PAIR && dU >= 2 && dU <= 32;
+        if (__any( (actL || actU) && (long_d || (hist & 0x20D00u) != 0u) ))        // `long`: slots 0, 2, 3 or this diagonal; no `mid`: slot 1
         {
             const int32_t NEG = -(1 << 20), POS = 1 << 20;
             // the intervals of a job whose iteration this is d (its middle diagonal d - 2), hv: its diagonal d exists
@@ -2006,17 +1763,18 @@ gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, c
                 tests( iv, r11, r12 );
                 ex11[0] = ex11[0] || r11; ex12[0] = ex12[0] || r12;
             }
-            if (actU)
-            {
-                // away from a band's edge the two jobs ask the same questions: all four neighbours of the middle diagonal lie in both bands
-                // iff dU - 2 >= 2 (the upper job's lower edge) and D <= 30 (the lower job's upper edge)
-                if (!(actL && dU >= 4 && D <= 30u))
+            if constexpr (PAIR)
+                if (actU)
                 {
-                    intervals( dU, dU <= 30, iv );
-                    tests( iv, r11, r12 );
+                    // away from a band's edge the two jobs ask the same questions: all four neighbours of the middle diagonal lie in both bands
+                    // iff dU - 2 >= 2 (the upper job's lower edge) and D <= 30 (the lower job's upper edge)
+                    if (!(actL && dU >= 4 && D <= 30u))
+                    {
+                        intervals( dU, dU <= 30, iv );
+                        tests( iv, r11, r12 );
+                    }
+                    ex11[1] = ex11[1] || r11; ex12[1] = ex12[1] || r12;
                 }
-                ex11[1] = ex11[1] || r11; ex12[1] = ex12[1] || r12;
-            }
         }
         // shift the history
         #pragma unroll
@@ -2027,16 +1785,34 @@ gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, c
     }
     uint32_t flags = 0;
     #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NJ; ++j)
     {
         const int32_t  best_cost = best_key[j] == 0xFFFFFFFFu ? 0x7FFFFFFF : (int32_t)(best_key[j] >> 6);
         const uint32_t best_end  = 63u - (best_key[j] & 63u);
         const bool settled = best_cost < c_unk && !(ex11[j] && cost11 <= best_cost) && !(ex12[j] && cost12 <= best_cost);
-        const uint32_t which = j ? up : 1u - up;                 // 0: `job`, 1: job + 1
+        const uint32_t which = j ? up : (PAIR ? 1u - up : 0u);   // 0: `job`, 1: job + 1
         if (settled) { scores[job + which] = -best_cost; sinks[job + which] = make_uint2( M + best_end, M ); }
         else flags |= 1u << which;
     }
     return flags;
+}
+
+// the single job (has_u: a third-chance job, need_dp = 2): returns its flag
+template <int RBITS>
+__device__ __forceinline__ uint32_t
+gap_chance_e2e31_job(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
+                     int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const bool has_u)
+{
+    return gap_chance_e2e31_walk<RBITS,false>( b, P, lad, gap_open, gap_ext, scores, sinks, job, has_u );
+}
+
+// the pair `job`, job + 1: returns the two flags
+template <int RBITS>
+__device__ __forceinline__ uint32_t
+gap_chance_e2e31_pair(const BatchDev& b, const int32_t P, const GapLadder lad, const int32_t gap_open, const int32_t gap_ext,
+                      int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job)
+{
+    return gap_chance_e2e31_walk<RBITS,true>( b, P, lad, gap_open, gap_ext, scores, sinks, job, false );
 }
 
 // one workgroup's chunks of list `pairs` (slot0 < n = the list's length): every pair through gap_chance_e2e31_pair, the members it does not

@@ -13,6 +13,11 @@ of these, so a job's optimum lies in the class iff its score is the negative of 
 have BOTH jobs' optimum in the class and at least a tenth have AT LEAST ONE job's optimum outside it (`one outside` below counts those), decided
 under that one scheme; the other schemes score the same batches.
 
+The pair and the single job share one walk (gap_chance_e2e31_walk), so the pair also runs at the read lengths where the plane words end
+differently from M = 150 (PAIR_LENGTHS, one small indel grid each).  A pair takes the paired route only if the first pass flags BOTH jobs 4:
+with penalty 6 it keeps counts up to 5 exact, so both need more than 5 mismatches on every one of their 31 diagonals.  Per such batch at least
+two fifths of the pairs are of that kind, and at least one eighth of the pairs are of that kind with both optima in the class.
+
 What this test cannot see is whether a pair went through gap_chance_e2e31_pair or through two single jobs: the results are the same by design
 and the lists' lengths stay on the device.  It pins which jobs MAY pair (nvbio_banded_gap_pairs) and that every way of scoring agrees with the
 oracle; that the paired route runs is seen in the step's time with and without ALN_NO_PAIRED_GAP_CHANCE (profiles/r08_ab_bench.json)."""
@@ -28,6 +33,9 @@ SCHEMES = ((0, 6, 6, -8, -3, -8, -3), (0, 2, 2, -5, -1, -5, -1), (0, 4, 4, -6, -
 IN_CLASS = (-8, -11, -14, -17, -20)                                 # under SCHEMES[0], see above
 ROWS = (5, 31, 32, 33, 75, 117, 118, 144)                           # edges of the first / last 32-row words and of the hot halves (M = 150)
 SPACING = 400
+# read lengths at which the pair's plane words end differently from M = 150: the edges of the 32-row words, of base = M - 32, of the `mid` rule at
+# 96 and of the second 64-bit plane
+PAIR_LENGTHS = (20, 31, 32, 33, 63, 64, 65, 95, 97, 127, 128, 129)
 
 
 def _subst(rng, r, k):
@@ -71,7 +79,7 @@ class _Jobs:
         if clip_last:                                               # the text ends one symbol short of the last job's window
             text = text[:int(we[-1]) - 1]; we[-1] = len(text)
         return dict(reads=orc.pack4(np.concatenate(self.reads)), roffs=roffs, text=orc.pack2(text), wb=wb, we=we, rid=rid, fl=fl, n=len(jobs),
-                    max_len=int(lens.max()))
+                    max_len=int(lens.max()), read_syms=self.reads, text_syms=text)
 
 
 def _grid(orc, seed, R, M=150, gs=range(1, 8), lead=0, edge=False, repeats=False):
@@ -151,9 +159,18 @@ def _singles(orc, seed, R, M=150):
     return b.finish(orc)
 
 
+def _every_diagonal_above(d, M, cnt):
+    """per job of a _grid batch (forward reads of one length M): all 31 diagonals of its window hold more than cnt mismatches"""
+    win = d["text_syms"][d["wb"][:, None].astype(np.int64) + np.arange(M + 30)]
+    reads = np.stack(d["read_syms"])[d["rid"]]
+    return np.all([(win[:, k:k + M] != reads).sum(axis=1) > cnt for k in range(31)], axis=0)
+
+
 def _cases(orc):
     # (batch, schemes, an indel batch whose mix is checked)
+    edges = {"pair_length_%d" % M: (_grid(orc, 900 + M, 640, M=M), SCHEMES[:1], False) for M in PAIR_LENGTHS}
     return {
+        **edges,
         "indel_grid": (_grid(orc, 81, 3000), SCHEMES, True),
         "every_job_a_pair_member": (_grid(orc, 82, 3008, gs=range(1, 6)), SCHEMES[:1], True),
         "wave_boundary_inside_a_pair": (_grid(orc, 83, 130, lead=1), SCHEMES[:2], True),
@@ -185,6 +202,14 @@ def test_paired_gap_chance_equals_the_oracle_four_ways(amd, orc):
         print(name, "jobs", d["n"], "pairs", len(lower), "both in the class", both_in, "one outside", one_out)
         if indel_batch:
             assert 3 * both_in >= len(lower) and 10 * one_out >= len(lower), (name, len(lower), both_in, one_out)
+        if name.startswith("pair_length_"):
+            # the pairs that take the paired route: under SCHEMES[0] (penalty 6) the first pass keeps counts up to 5 exact and flags 4 only above
+            # that, so BOTH jobs need more than 5 mismatches on every one of their 31 diagonals
+            far = _every_diagonal_above(d, int(name[len("pair_length_"):]), 5)
+            routed = far[lower] & far[lower + 1]
+            routed_in = int((routed & np.isin(s0[lower], IN_CLASS) & np.isin(s0[lower + 1], IN_CLASS)).sum())
+            print(name, "pairs with both jobs flagged 4", int(routed.sum()), "of them both optima in the class", routed_in)
+            assert 5 * int(routed.sum()) >= 2 * len(lower) and 8 * routed_in >= len(lower), (name, len(lower), int(routed.sum()), routed_in)
         if name == "every_job_a_pair_member":
             assert 2 * len(lower) == d["n"]
         if name == "no_pairs":
