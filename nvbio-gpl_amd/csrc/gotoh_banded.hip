@@ -39,24 +39,21 @@ banded_gotoh_kernel(const BatchDev b, const SchemeDev sc, int32_t* __restrict__ 
                     const uint32_t distinct_dist, int32_t* __restrict__ scores2, uint2* __restrict__ sinks2,
                     const int32_t* __restrict__ min_scores, const int32_t min_score_all)
 {
-    // mismatch score per quality value, computed once per workgroup
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
 
+    // (the header by hand, not load_job + scored_text_len: loading win_end unconditionally costs the LOCAL Best2Sink band-15 build on
+    // 8-bit reads two registers, 64 -> 66, and with them a wave; notes/history.md, Round 11)
     const uint32_t rid   = b.read_id ? b.read_id[job] : job;
     const uint32_t first = b.read_offsets[rid];
     const uint32_t M     = b.read_offsets[rid + 1] - first;
     const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
     const uint32_t tb    = b.win_begin[job];
-    // a pattern longer than the batch's declared max_read_len is rejected -- nothing reported, as for a text shorter than the
-    // pattern -- in every kernel alike: the packed kernels rely on that bound for their 16-bit scores
-    const uint32_t N     = (b.max_read_len && M > b.max_read_len) ? 0u : b.win_end[job] - tb;
+    const uint32_t N     = (b.max_read_len && M > b.max_read_len) ? 0u : b.win_end[job] - tb;        // the rule of scored_text_len
+    const AlnJob   J{ first, M, tb, N, fl, (fl & NVBIO_READ_REVERSE) != 0, (fl & NVBIO_READ_COMPLEMENT) != 0 };
 
     int32_t  best   = NVBIO_SCORE_MIN;
     uint32_t best_x = 0xFFFFFFFFu, best_y = 0xFFFFFFFFu;
@@ -121,11 +118,9 @@ banded_gotoh_kernel(const BatchDev b, const SchemeDev sc, int32_t* __restrict__ 
                 F[j] = (int32_t)(int16_t)max2( F[j], -32768 + 32 );
             }
         }
-        const uint32_t pidx = rev ? first + M - 1u - i : first + i;
-        uint32_t q = prd.get( pidx );
-        if (comp && q < 4u) q = 3u - q;
-        const uint32_t qq = b.quals ? b.quals[pidx] : 0u;
-        const int32_t  S  = s_mm[qq < 63u ? qq : 63u];          // qualities >= 40 all map to mm_max
+        uint32_t pidx;
+        const uint32_t q = pattern_symbol( prd, J, i, &pidx );
+        const int32_t  S = pattern_mismatch( b.quals, s_mm, pidx );
 
         // new text symbol entering column BAND-1 (gotoh_banded_inl.h:569-570)
         const uint32_t g_new = (i + (uint32_t)(BAND - 1) < N) ? trd.get( tb + i + (BAND - 1) ) : 255u;
@@ -315,8 +310,7 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
     static_assert( !NARROW || (FP && !RAGGED && TYPE == NVBIO_SEMI_GLOBAL), "the narrow roles: the binary16 SEMI_GLOBAL build, equal read lengths" );
     typedef typename PkLanes<FP>::type v2;
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     // with a job list (the jobs the ungapped pass could not settle) lane p works on entries 2p and 2p+1 of the list
     uint32_t n_jobs = job_list ? *job_count : b.n;
@@ -346,14 +340,9 @@ banded_gotoh_band31_pk_kernel(const BatchDev b, const SchemeDev sc, int32_t* __r
         const uint32_t ss  = valid[u] ? slot : 2u * pair;
         const uint32_t jj  = job_list ? job_list[ss] : ss;
         out_id[u] = jj;
-        const uint32_t rid = b.read_id ? b.read_id[jj] : jj;
-        first[u] = b.read_offsets[rid];
-        M[u]     = b.read_offsets[rid + 1] - first[u];
-        const uint32_t fl = b.flags ? b.flags[jj] : 0u;
-        rev[u]  = (fl & NVBIO_READ_REVERSE) != 0;
-        comp[u] = (fl & NVBIO_READ_COMPLEMENT) != 0;
-        tb[u]   = b.win_begin[jj];
-        N[u]    = (b.max_read_len && M[u] > b.max_read_len) ? 0u : b.win_end[jj] - tb[u];     // too long for the declared bound: rejected
+        const AlnJob J = load_job( b, jj );
+        first[u] = J.first; M[u] = J.M; rev[u] = J.rev; comp[u] = J.comp; tb[u] = J.tb;
+        N[u]     = scored_text_len( b, J );
         // rows this alignment really computes: none when the text is shorter than the pattern (nothing reported)
         rows_all[u] = (valid[u] && N[u] >= M[u]) ? M[u] : 0u;
     }
@@ -1018,14 +1007,9 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
                    const NarrowRule nr = NarrowRule{ 1, 1, 0u })
 {
     constexpr bool LIST = MODE != 0;
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = (b.max_read_len && M > b.max_read_len) ? 0u : b.win_end[job] - tb;       // too long for the declared bound: rejected
+    const AlnJob   J = load_job( b, job );
+    const uint32_t first = J.first, M = J.M, tb = J.tb, N = scored_text_len( b, J );
+    const bool     rev = J.rev, comp = J.comp;
 
     if (N < M)                                                   // nothing reported (gotoh_banded_inl.h:422-423)
     {
@@ -1476,14 +1460,11 @@ gap_chance_e2e31_walk(const BatchDev& b, const int32_t P, const GapLadder lad, c
                       int32_t* __restrict__ scores, uint2* __restrict__ sinks, const uint32_t job, const bool has_u)
 {
     constexpr int NJ = PAIR ? 2 : 1;                             // accumulator sets: [0] the lower (or only) job, [1] the upper job
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
+    const AlnJob   J = load_job( b, job );
+    const uint32_t first = J.first, M = J.M;
+    const bool     rev = J.rev, comp = J.comp;
     // (flagged by the first pass: 1 <= M <= 161, N >= M + 30 -- partners: both windows M + 31 symbols --, P > 0, open <= ext < 0)
-    uint32_t tb = b.win_begin[job], up = 0u, sh = 0u;
+    uint32_t tb = J.tb, up = 0u, sh = 0u;
     if constexpr (PAIR)
     {
         const uint32_t tb1 = b.win_begin[job + 1u];
@@ -1960,10 +1941,7 @@ static bool packed_ok(const int type, const SchemeDev& sc, const uint32_t max_re
     if (type == NVBIO_LOCAL) return (uint64_t)sc.match * max_read_len <= 1000u;
     if (sc.txt_go > 0 || sc.txt_ge > 0 || sc.txt_go < -lim || sc.txt_ge < -lim) return false;
     // |score| <= (rows + band) * (largest single step) must stay far from -16384
-    int64_t step = sc.match;
-    const int c[] = { sc.mm_min, sc.mm_max, -sc.pat_go, -sc.pat_ge, -sc.txt_go, -sc.txt_ge };
-    for (int v : c) if (v > step) step = v;
-    return ((int64_t)max_read_len + 32) * step <= 8000;
+    return ((int64_t)max_read_len + 32) * scheme_max_step( sc ) <= 8000;
 }
 
 struct IsTwo { __host__ __device__ __forceinline__ uint8_t operator()(const uint8_t v) const { return v == 2u ? 1u : 0u; } };
@@ -1984,8 +1962,7 @@ job_length_keys_kernel(const BatchDev b, const uint32_t* __restrict__ jobs, cons
         if (i < n)
         {
             const uint32_t job = jobs ? jobs[i] : i;
-            const uint32_t rid = b.read_id ? b.read_id[job] : job;
-            const uint32_t M   = b.read_offsets[rid + 1] - b.read_offsets[rid];
+            const uint32_t M = read_len( b, job );
             key = M < 0xFFFEu ? M : 0xFFFEu;
         }
         keys[i] = (uint16_t)key;
@@ -2039,9 +2016,7 @@ template <int TYPE>
 static bool pk_binary16_ok(const BatchDev& b, const SchemeDev& sc)
 {
     const bool two = (b.algo & NVBIO_ALN_PK_THREE_WAVES) == 0;
-    int64_t step = 0;
-    { const int c[] = { sc.mm_min, sc.mm_max, -sc.pat_go, -sc.pat_ge, -sc.txt_go, -sc.txt_ge }; for (int v : c) if (v > step) step = v; }
-    return two && sc.match == 0 && TYPE == NVBIO_SEMI_GLOBAL && !(b.algo & NVBIO_ALN_NO_F16_DP) && ((int64_t)b.max_read_len + 32) * step <= 2040 && sc.mm_max <= 400;
+    return two && sc.match == 0 && TYPE == NVBIO_SEMI_GLOBAL && !(b.algo & NVBIO_ALN_NO_F16_DP) && ((int64_t)b.max_read_len + 32) * scheme_max_step( sc ) <= 2040 && sc.mm_max <= 400;
 }
 
 // the packed kernel's instantiation for this scheme: match = 0 (every end-to-end scheme of nvBowtie) drops one operation per cell

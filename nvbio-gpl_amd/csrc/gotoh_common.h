@@ -104,4 +104,90 @@ __device__ __forceinline__ int32_t mismatch_score(const SchemeDev& sc, const uin
 __device__ __forceinline__ int32_t max2(int32_t a, int32_t b) { return a > b ? a : b; }
 __device__ __forceinline__ int32_t max3(int32_t a, int32_t b, int32_t c) { return max2( max2( a, b ), c ); }
 
+// the largest magnitude of a single step of the scheme: what the int16 / binary16 range checks of the host multiply by the path length.
+// (The Smith-Waterman aligner's terms enter through scheme_dev / as_gotoh.)
+inline int64_t scheme_max_step(const SchemeDev& sc)
+{
+    int64_t step = 0;
+    const int64_t c[] = { sc.match, sc.mm_min, sc.mm_max, sc.pat_go, sc.pat_ge, sc.txt_go, sc.txt_ge };
+    for (int64_t v : c) { if (v < 0) v = -v; if (v > step) step = v; }
+    return step;
+}
+
+// launches over `n` slots, at most `cap` per launch: f( begin, jobs ) until one fails
+template <typename F>
+inline nvbio_status for_each_chunk(const uint64_t n, const uint64_t cap, F f)
+{
+    nvbio_status st = NVBIO_OK;
+    for (uint64_t begin = 0; begin < n && st == NVBIO_OK; begin += cap)
+        st = f( (uint32_t)begin, (uint32_t)((n - begin) < cap ? (n - begin) : cap) );
+    return st;
+}
+
+// ---- the job as the kernels see it --------------------------------------------------------------------------------------------------
+// pattern = symbols [first, first + M) of the read stream, read backwards (rev) and complemented (comp) as the job's flag byte `fl` says;
+// text = the N symbols from tb on, N as the window stores it
+struct AlnJob
+{
+    uint32_t first, M, tb, N, fl; bool rev, comp;
+};
+__device__ __forceinline__ uint32_t read_len(const BatchDev& b, const uint32_t job)
+{
+    const uint32_t rid = b.read_id ? b.read_id[job] : job;
+    return b.read_offsets[rid + 1] - b.read_offsets[rid];
+}
+__device__ __forceinline__ AlnJob load_job(const BatchDev& b, const uint32_t job)
+{
+    AlnJob j;
+    const uint32_t rid = b.read_id ? b.read_id[job] : job;
+    j.first = b.read_offsets[rid];
+    j.M     = b.read_offsets[rid + 1] - j.first;
+    j.fl    = b.flags ? b.flags[job] : 0u;
+    j.rev   = (j.fl & NVBIO_READ_REVERSE) != 0;
+    j.comp  = (j.fl & NVBIO_READ_COMPLEMENT) != 0;
+    j.tb    = b.win_begin[job];
+    j.N     = b.win_end[job] - j.tb;
+    return j;
+}
+// The scorers' rule: a pattern longer than the batch's declared max_read_len is rejected -- nothing reported, as for a text shorter than
+// the pattern -- in every scoring kernel alike: the packed kernels rely on that bound for their 16-bit scores.  (The tracebacks keep N
+// and flag such a job with cigar_lens = 0xFFFFFFFF; the full-matrix scorer is bounded by its max_M / max_N instead.)
+__device__ __forceinline__ uint32_t scored_text_len(const BatchDev& b, const AlnJob& J)
+{
+    return (b.max_read_len && J.M > b.max_read_len) ? 0u : J.N;
+}
+
+// row i of the pattern: its symbol as the DP compares it, and the storage index (of the symbol and of its quality) in *pidx
+template <typename Reader>
+__device__ __forceinline__ uint32_t pattern_symbol(Reader& prd, const AlnJob& J, const uint32_t i, uint32_t* pidx)
+{
+    *pidx = J.rev ? J.first + J.M - 1u - i : J.first + i;
+    const uint32_t q = prd.get( *pidx );
+    return (J.comp && q < 4u) ? 3u - q : q;
+}
+// the mismatch score of the row stored at pidx, from the workgroup's table (qualities >= 40 all map to mm_max)
+__device__ __forceinline__ int32_t pattern_mismatch(const uint8_t* quals, const int32_t* s_mm, const uint32_t pidx)
+{
+    const uint32_t qq = quals ? quals[pidx] : 0u;
+    return s_mm[qq < 63u ? qq : 63u];
+}
+// mismatch score per quality value, computed once per workgroup into a __shared__ int32_t[64].  Holds a barrier: every thread of the
+// workgroup calls it, before any early return.
+__device__ __forceinline__ void fill_mismatch_table(int32_t* s_mm, const SchemeDev& sc)
+{
+    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
+    __syncthreads();
+}
+
+// slot t of a launch over `jobs` slots from job_begin on: with a job list (the jobs an earlier pass could not settle, its length on the
+// device) entry job_begin + t of the list, else job job_begin + t.  False where the slot holds no job.
+__device__ __forceinline__ bool slot_job(const uint32_t* job_list, const uint32_t* job_count, const uint32_t job_begin, const uint32_t t,
+                                         const uint32_t jobs, uint32_t* job)
+{
+    if (t >= jobs) return false;
+    if (job_list && job_begin + t >= *job_count) return false;
+    *job = job_list ? job_list[job_begin + t] : job_begin + t;
+    return true;
+}
+
 } // namespace nvbio_amd

@@ -58,33 +58,18 @@ full_gotoh_kernel(const BatchDev b, const SchemeDev sc, const uint32_t job_begin
                   const uint32_t distinct_dist, int32_t* __restrict__ scores2, uint2* __restrict__ sinks2)
 {
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;   // slot inside this launch
-    if (t >= jobs) return;
-    // with a job list (the jobs the ungapped pass could not settle) slot t is entry job_begin + t of the list
-    if (job_list && job_begin + t >= *job_count) return;
-    const uint32_t job = job_list ? job_list[job_begin + t] : job_begin + t;
+    uint32_t job;
+    if (!slot_job( job_list, job_count, job_begin, t, jobs, &job )) return;
 
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = b.win_end[job] - tb;
+    const AlnJob   J = load_job( b, job );
+    const uint32_t M = J.M, tb = J.tb, N = J.N;
     const int32_t  min_score = min_scores ? min_scores[job] : NVBIO_SCORE_MIN;
 
     SymbolReader<TBITS> trd( b.text );
     SymbolReader<RBITS> prd( b.reads );
-    auto pattern = [&](const uint32_t i, uint32_t& q, uint32_t& qq) {
-        const uint32_t idx = rev ? first + M - 1u - i : first + i;
-        q = prd.get( idx );
-        if (comp && q < 4u) q = 3u - q;
-        qq = b.quals ? b.quals[idx] : 0u;
-    };
 
     // F runs down the rows of a stripe, E along it: with pattern blocking the rows are text positions (F = the text advancing
     // alone), with text blocking they are pattern positions.  The Gotoh aligner charges the same terms to both (SchemeDev).
@@ -127,7 +112,7 @@ full_gotoh_kernel(const BatchDev b, const SchemeDev sc, const uint32_t job_begin
             if (block + j < cols)
             {
                 if (TEXT_BLOCKING) c_sym[j] = trd.get( tb + block + j );
-                else { uint32_t q, qq; pattern( block + j, q, qq ); c_sym[j] = q; c_mm[j] = s_mm[qq < 63u ? qq : 63u]; }
+                else { uint32_t idx; c_sym[j] = pattern_symbol( prd, J, block + j, &idx ); c_mm[j] = pattern_mismatch( b.quals, s_mm, idx ); }
             }
         }
         #pragma unroll
@@ -144,7 +129,7 @@ full_gotoh_kernel(const BatchDev b, const SchemeDev sc, const uint32_t job_begin
         for (uint32_t i = 0; i < rows; ++i)
         {
             uint32_t r_sym = 0; int32_t r_mm = 0;               // the row's symbol
-            if (TEXT_BLOCKING) { uint32_t q, qq; pattern( i, q, qq ); r_sym = q; r_mm = s_mm[qq < 63u ? qq : 63u]; }
+            if (TEXT_BLOCKING) { uint32_t idx; r_sym = pattern_symbol( prd, J, i, &idx ); r_mm = pattern_mismatch( b.quals, s_mm, idx ); }
             else                 r_sym = trd.get( tb + i );
 
             // update_row (gotoh_inl.h:458-575 / :852-969)
@@ -268,8 +253,7 @@ full_gotoh_coop_kernel(const BatchDev b, const SchemeDev sc, const bool text_blo
 {
     static_assert( TYPE != NVBIO_LOCAL && (L == 4 || L == 8 || L == 16), "GLOBAL / SEMI_GLOBAL; the lanes of a job inside one DPP row" );
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t gl  = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t l   = gl % L;
@@ -277,14 +261,8 @@ full_gotoh_coop_kernel(const BatchDev b, const SchemeDev sc, const bool text_blo
     const bool     valid = jid < b.n;
     const uint32_t job = valid ? jid : b.n - 1u;                // (lanes past the batch repeat its last job and report nothing)
 
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = b.win_end[job] - tb;
+    const AlnJob   J = load_job( b, job );
+    const uint32_t M = J.M, tb = J.tb, N = J.N;
     const bool     fits  = M >= 1u && M <= (uint32_t)(L * W);
 
     // border terms: a pattern prefix of length n scores po + pe (n - 1), a text prefix to + te (n - 1) (GLOBAL only; free otherwise)
@@ -302,15 +280,8 @@ full_gotoh_coop_kernel(const BatchDev b, const SchemeDev sc, const bool text_blo
         for (int k = 0; k < W; ++k)
         {
             const uint32_t j = c0 + (uint32_t)k;
-            uint32_t q = 4u, qq = 0u;                            // (columns past the pattern: a symbol that matches nothing)
-            if (j < M)
-            {
-                const uint32_t idx = rev ? first + M - 1u - j : first + j;
-                q = prd.get( idx );
-                if (comp && q < 4u) q = 3u - q;
-                qq = b.quals ? b.quals[idx] : 0u;
-            }
-            psym[k] = q; pmm[k] = s_mm[qq < 63u ? qq : 63u];
+            psym[k] = 4u; pmm[k] = s_mm[0];                      // (columns past the pattern: a symbol that matches nothing)
+            if (j < M) { uint32_t idx; psym[k] = pattern_symbol( prd, J, j, &idx ); pmm[k] = pattern_mismatch( b.quals, s_mm, idx ); }
             H[k] = po + pe * (int32_t)j;                         // prefix length j + 1
             F[k] = infimum;
         }
@@ -470,14 +441,9 @@ ungapped_full_e2e_kernel(const BatchDev b, const int32_t P, const int32_t G, con
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (MODE == 0 ? slot >= b.n : slot >= *job_count) return;
     const uint32_t job = MODE == 0 ? slot : job_list[slot];
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = b.win_end[job] - tb;
+    const AlnJob   J = load_job( b, job );
+    const uint32_t first = J.first, M = J.M, tb = J.tb, N = J.N;
+    const bool     rev = J.rev, comp = J.comp;
     if (M == 0u || M > 161u || N < M || N > 528u) { need_dp[job] = 1; return; }
 
     uint32_t pl[6], ph[6], pn[6], pm[6], tl[18], th[18];
@@ -659,8 +625,7 @@ narrow_jobs_kernel(const BatchDev b, const uint8_t* __restrict__ need_dp, const 
 {
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
-    const uint32_t rid = b.read_id ? b.read_id[job] : job;
-    const uint32_t M   = b.read_offsets[rid + 1] - b.read_offsets[rid];
+    const uint32_t M   = read_len( b, job );
     const uint32_t tb  = b.win_begin[job];
     const uint32_t N   = b.win_end[job] - tb;
     const bool ok = need_dp[job] == 1 && M >= 1u && M <= 161u && N <= 528u && N >= M + 30u;      // (what the shortcut kernel looked at, and room for a band)
@@ -684,14 +649,9 @@ narrow_check_kernel(const BatchDev b, const int32_t P, const int32_t gap_open, c
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= *job_count) return;
     const uint32_t job   = job_list[slot];
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = b.win_end[job] - tb;
+    const AlnJob   J = load_job( b, job );
+    const uint32_t first = J.first, M = J.M, tb = J.tb, N = J.N;
+    const bool     rev = J.rev, comp = J.comp;
     const int32_t  L     = scores[job];                          // the band's score
     const int32_t  min_score = min_scores ? min_scores[job] : NVBIO_SCORE_MIN;
     // the bounds of step 2
@@ -808,8 +768,7 @@ full_gotoh_pb_pk_kernel(const BatchDev b, const SchemeDev sc, const uint32_t M, 
                         const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count)
 {
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;   // pair slot inside this launch
     if (t >= pairs) return;
@@ -823,12 +782,8 @@ full_gotoh_pb_pk_kernel(const BatchDev b, const SchemeDev sc, const uint32_t M, 
     {
         valid[u] = slot0 + u < n_jobs;
         job[u]   = job_list[valid[u] ? slot0 + u : slot0];
-        const uint32_t rid = b.read_id ? b.read_id[job[u]] : job[u];
-        first[u] = b.read_offsets[rid];
-        const uint32_t fl = b.flags ? b.flags[job[u]] : 0u;
-        rev[u]  = (fl & NVBIO_READ_REVERSE) != 0;
-        comp[u] = (fl & NVBIO_READ_COMPLEMENT) != 0;
-        tb[u]   = b.win_begin[job[u]];
+        const AlnJob J = load_job( b, job[u] );                  // (M and N are the launch's)
+        first[u] = J.first; rev[u] = J.rev; comp[u] = J.comp; tb[u] = J.tb;
         min_score[u] = min_scores ? min_scores[job[u]] : NVBIO_SCORE_MIN;
     }
 
@@ -982,8 +937,7 @@ full_gotoh_pb_pk16_kernel(const BatchDev b, const SchemeDev sc, const uint32_t M
 {
     constexpr int W = 16;
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;   // pair slot inside this launch
     if (t >= pairs) return;
@@ -997,12 +951,8 @@ full_gotoh_pb_pk16_kernel(const BatchDev b, const SchemeDev sc, const uint32_t M
     {
         valid[u] = slot0 + u < n_jobs;
         job[u]   = job_list[valid[u] ? slot0 + u : slot0];
-        const uint32_t rid = b.read_id ? b.read_id[job[u]] : job[u];
-        first[u] = b.read_offsets[rid];
-        const uint32_t fl = b.flags ? b.flags[job[u]] : 0u;
-        rev[u]  = (fl & NVBIO_READ_REVERSE) != 0;
-        comp[u] = (fl & NVBIO_READ_COMPLEMENT) != 0;
-        tb[u]   = b.win_begin[job[u]];
+        const AlnJob J = load_job( b, job[u] );                  // (M and N are the launch's)
+        first[u] = J.first; rev[u] = J.rev; comp[u] = J.comp; tb[u] = J.tb;
         min_score[u] = min_scores ? min_scores[job[u]] : NVBIO_SCORE_MIN;
     }
     SymbolReader<RBITS> prd0( b.reads ), prd1( b.reads );
@@ -1200,8 +1150,7 @@ classify_shape_kernel(const BatchDev b, const uint32_t M0, const uint32_t N0, co
 {
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
-    const uint32_t rid = b.read_id ? b.read_id[job] : job;
-    const uint32_t M = b.read_offsets[rid + 1] - b.read_offsets[rid];
+    const uint32_t M = read_len( b, job );
     const uint32_t N = b.win_end[job] - b.win_begin[job];
     const bool need = need_dp ? need_dp[job] != 0 : true;
     const bool uni  = (M == M0 && N == N0);
@@ -1213,9 +1162,8 @@ static bool full_packed_ok(const int type, const SchemeDev& sc, const uint32_t M
 {
     if (M == 0 || N == 0) return false;
     if (sc.match < 0 || sc.mm_min < 0 || sc.mm_max < 0) return false;
-    int64_t step = sc.match;
-    const int64_t c[] = { sc.mm_min, sc.mm_max, -(int64_t)sc.pat_go, -(int64_t)sc.pat_ge, -(int64_t)sc.txt_go, -(int64_t)sc.txt_ge };
-    for (int64_t v : c) { if (v < 0) return false; if (v > step) step = v; }       // gap terms must be <= 0, penalties >= 0
+    if (sc.pat_go > 0 || sc.pat_ge > 0 || sc.txt_go > 0 || sc.txt_ge > 0) return false;          // gap terms must be <= 0, penalties >= 0
+    const int64_t step = scheme_max_step( sc );
     if (step > 4096) return false;
     if (((int64_t)M + N) * step > 12000) return false;
     if (type == NVBIO_LOCAL && (int64_t)sc.match * M > 2000) return false;          // (score << 4 | column) must fit an int16
@@ -1279,9 +1227,7 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
     //      apply, without the stripe early exit; packed 2- / 4-bit reads in a 2-bit text; every value inside the int16 range of the reference's
     //      boundary cells.  Batches large enough for the two-jobs-per-lane kernel keep that one.
     {
-        int64_t step = sc.match > 0 ? sc.match : -(int64_t)sc.match;
-        const int64_t cc[] = { sc.mm_min, sc.mm_max, sc.pat_go, sc.pat_ge, sc.txt_go, sc.txt_ge };
-        for (int64_t v : cc) { const int64_t a = v < 0 ? -v : v; if (a > step) step = a; }
+        const int64_t step = scheme_max_step( sc );
         const bool pk_bits  = batch->text_bits == 2 && (batch->read_bits == 4 || batch->read_bits == 2);
         const bool e2e      = type == NVBIO_SEMI_GLOBAL && sc.match == 0 && !(b.algo & NVBIO_ALN_NO_UNGAPPED_SCORE);      // (the shortcut's ground)
         const bool pk_route = !text_blocking && (b.n >= 262144u || (b.algo & NVBIO_ALN_FORCE_PACKED_DP)) && !(b.algo & NVBIO_ALN_NO_PACKED_DP);
@@ -1446,14 +1392,13 @@ static nvbio_status full_score(int device, int type, int text_blocking, const Sc
 #undef NVB_PK
         }
     }
-    for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
+    if (st != NVBIO_OK) return st;
+    return for_each_chunk( b.n, cap_jobs, [&](const uint32_t begin, const uint32_t jobs)
     {
-        const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
-        st = text_blocking ?
-            launch_dp<true> ( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count ) :
-            launch_dp<false>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count );
-    }
-    return st;
+        return text_blocking ?
+            launch_dp<true> ( type, b, sc, batch->read_bits, batch->text_bits, begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count ) :
+            launch_dp<false>( type, b, sc, batch->read_bits, batch->text_bits, begin, jobs, min_scores_dev, column, scores_dev, (uint2*)sinks_dev, s, job_list, job_count );
+    } );
 }
 
 extern "C" nvbio_status nvbio_full_gotoh_score(int device, nvbio_alignment_type type, int text_blocking,
@@ -1506,16 +1451,13 @@ extern "C" nvbio_status nvbio_full_gotoh_score_best2(int device, nvbio_alignment
     ScratchBlock temp;
     NVB_CHECK( temp.alloc( "full_best2_columns", cap_jobs * rows * sizeof(uint32_t), s, "full Gotoh: out of device memory for %llu boundary columns", (unsigned long long)cap_jobs ) );
     uint32_t* column = (uint32_t*)temp.get();
-    nvbio_status st = NVBIO_OK;
-    for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
+    return for_each_chunk( b.n, cap_jobs, [&](const uint32_t begin, const uint32_t jobs)
     {
-        const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
-        st = text_blocking ? launch_best2<true> ( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist,
-                                                  scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s )
-                           : launch_best2<false>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, min_scores_dev, column, distinct_dist,
-                                                  scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
-    }
-    return st;
+        return text_blocking ? launch_best2<true> ( type, b, sc, batch->read_bits, batch->text_bits, begin, jobs, min_scores_dev, column, distinct_dist,
+                                                    scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s )
+                             : launch_best2<false>( type, b, sc, batch->read_bits, batch->text_bits, begin, jobs, min_scores_dev, column, distinct_dist,
+                                                    scores_dev, (uint2*)sinks_dev, scores2_dev, (uint2*)sinks2_dev, s );
+    } );
 }
 
 extern "C" nvbio_status nvbio_full_sw_score(int device, nvbio_alignment_type type, int text_blocking,

@@ -15,14 +15,13 @@
 // whose optimum is reached by the diagonal through the sink alone are traced without a DP (the tie rule of
 // gotoh_inl.h:529-531 resolves the diagonal's ties to SUBSTITUTION, as in the banded case).  Identical to the reference
 // while scores fit its int16 checkpoints (host check).
-#include "gotoh_common.h"
+#include "gotoh_traceback_common.h"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>
 
 namespace nvbio_amd {
 namespace {
 
-enum : uint32_t { D_SUB = 0u, D_INS = 1u, D_DEL = 2u, D_SINK = 3u, D_INS_EXT = 4u, D_DEL_EXT = 8u };
 constexpr int STRIPE = 8;
 
 struct Sink
@@ -38,24 +37,6 @@ __device__ __forceinline__ uint32_t pack_cell(const int32_t h, const int32_t e) 
 __device__ __forceinline__ int32_t  cell_h(const uint32_t c) { return (int32_t)(int16_t)(c & 0xFFFFu); }
 __device__ __forceinline__ int32_t  cell_e(const uint32_t c) { return (int32_t)(int16_t)(c >> 16); }
 
-struct JobInfo
-{
-    uint32_t first, M, tb, N; bool rev, comp;
-};
-__device__ __forceinline__ JobInfo load_job(const BatchDev& b, const uint32_t job)
-{
-    JobInfo j;
-    const uint32_t rid = b.read_id ? b.read_id[job] : job;
-    j.first = b.read_offsets[rid];
-    j.M     = b.read_offsets[rid + 1] - j.first;
-    const uint32_t fl = b.flags ? b.flags[job] : 0u;
-    j.rev  = (fl & NVBIO_READ_REVERSE) != 0;
-    j.comp = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    j.tb   = b.win_begin[job];
-    j.N    = b.win_end[job] - j.tb;
-    return j;
-}
-
 // ---- forward DP with direction vectors + walk back ------------------------------------------------------------------
 template <int TYPE, int RBITS, int TBITS>
 __global__ void __launch_bounds__(128)
@@ -67,29 +48,23 @@ full_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32_t
                             const uint8_t* __restrict__ band_code, const uint32_t given_sinks)
 {
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= jobs) return;
-    if (job_list && job_begin + t >= *job_count) return;
-    const uint32_t job = job_list ? job_list[job_begin + t] : job_begin + t;
+    uint32_t job;
+    if (!slot_job( job_list, job_count, job_begin, t, jobs, &job )) return;
     // given_sinks (the linear-gap Smith-Waterman aligner): score and sink are the scoring pass's -- which sweeps the matrix in its own
     // logical stripes of 16 columns (sw/sw_inl.h:1322-1325), what decides LOCAL ties and the early exit -- and this kernel only has to
     // supply the direction vectors, which do not depend on the sweep
-    if (given_sinks && (sinks[job].x == 0xFFFFFFFFu || sinks[job].y == 0xFFFFFFFFu))
-    {
-        sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); cigar_lens[job] = 0;
-        return;
-    }
-    const JobInfo J = load_job( b, job );
+    if (given_sinks && (sinks[job].x == 0xFFFFFFFFu || sinks[job].y == 0xFFFFFFFFu)) { nothing_traced( sources, cigar_lens, job, 0u ); return; }
+    const AlnJob J = load_job( b, job );
     const uint32_t M = J.M, N = J.N;
     const int32_t min_score = min_scores ? min_scores[job] : NVBIO_SCORE_MIN;
 
     if (M > max_M || N > max_N)                                  // would overrun the scratch: skipped, flagged
     {
-        scores[job] = NVBIO_SCORE_MIN; sinks[job] = sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu );
-        cigar_lens[job] = 0xFFFFFFFFu;
+        scores[job] = NVBIO_SCORE_MIN; sinks[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu );
+        nothing_traced( sources, cigar_lens, job, 0xFFFFFFFFu );
         return;
     }
 
@@ -155,11 +130,9 @@ full_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32_t
         for (int j = 0; j < STRIPE; ++j)
             if (block + j < M)
             {
-                const uint32_t idx = J.rev ? J.first + M - 1u - (block + j) : J.first + block + j;
-                uint32_t q = prd.get( idx );
-                if (J.comp && q < 4u) q = 3u - q;
-                const uint32_t qq = b.quals ? b.quals[idx] : 0u;
-                c_sym[j] = q; c_mm[j] = s_mm[qq < 63u ? qq : 63u];
+                uint32_t idx;
+                c_sym[j] = pattern_symbol( prd, J, block + j, &idx );
+                c_mm[j]  = pattern_mismatch( b.quals, s_mm, idx );
             }
         #pragma unroll
         for (int j = 0; j <= STRIPE; ++j)
@@ -252,18 +225,11 @@ full_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32_t
     if (given_sinks) { sink.score = scores[job]; sink.x = sinks[job].x; sink.y = sinks[job].y; }
     scores[job] = sink.score;
     sinks[job]  = make_uint2( sink.x, sink.y );
-    if (sink.x == 0xFFFFFFFFu || sink.y == 0xFFFFFFFFu)
-    {
-        sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); cigar_lens[job] = 0;
-        return;
-    }
+    if (sink.x == 0xFFFFFFFFu || sink.y == 0xFFFFFFFFu) { nothing_traced( sources, cigar_lens, job, 0u ); return; }
 
     // ---- the walk (gotoh_inl.h:1599-1638), the implicit first row / column (alignment_inl.h:437-452) --------------
-    uint16_t* cig = cigars + (size_t)job * cigar_stride;
-    uint32_t  clen = 0, prev = 255u, run = 0;
-    auto emit = [&](const uint32_t type, const uint32_t len) { if (clen < cigar_stride) cig[clen] = (uint16_t)(type | (len << 2)); ++clen; };
-    auto push = [&](const uint32_t op) { if (op == prev) ++run; else { if (run) emit( prev, run ); prev = op; run = 1u; } };
-    if (M - sink.y) emit( 3u, M - sink.y );
+    CigarWriter cw( cigars, cigar_stride, job );
+    cw.clip( M - sink.y );
 
     int32_t row = (int32_t)sink.x, ccol = (int32_t)sink.y - 1;
     uint32_t state = 0;
@@ -279,24 +245,24 @@ full_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32_t
         }
         const uint32_t op = (word >> (4 * (ccol & 7))) & 15u, h_op = op & 3u;
         if (TYPE == NVBIO_LOCAL && state == 0u && h_op == D_SINK) break;
-        if (state == 1u)      { if ((op & D_INS_EXT) == 0u) state = 0u; --ccol; push( D_INS ); }
-        else if (state == 2u) { if ((op & D_DEL_EXT) == 0u) state = 0u; --row;  push( D_DEL ); }
+        if (state == 1u)      { if ((op & D_INS_EXT) == 0u) state = 0u; --ccol; cw.push( D_INS ); }
+        else if (state == 2u) { if ((op & D_DEL_EXT) == 0u) state = 0u; --row;  cw.push( D_DEL ); }
         else
         {
             if (h_op == D_INS)      state = 1u;
             else if (h_op == D_DEL) state = 2u;
-            else { --ccol; --row; push( D_SUB ); }
+            else { --ccol; --row; cw.push( D_SUB ); }
         }
     }
     uint32_t sx = (uint32_t)row, sy = (uint32_t)(ccol + 1);
     if (TYPE == NVBIO_SEMI_GLOBAL || TYPE == NVBIO_GLOBAL)
-        if (sx == 0u) for (; sy > 0u; --sy) push( D_INS );
+        if (sx == 0u) for (; sy > 0u; --sy) cw.push( D_INS );
     if (TYPE == NVBIO_GLOBAL)
-        if (sy == 0u) for (; sx > 0u; --sx) push( D_DEL );
-    if (run) emit( prev, run );
-    if (sy) emit( 3u, sy );
+        if (sy == 0u) for (; sx > 0u; --sx) cw.push( D_DEL );
+    cw.flush();
+    cw.clip( sy );
     sources[job]    = make_uint2( sx, sy );
-    cigar_lens[job] = clen;
+    cigar_lens[job] = cw.length();
 }
 
 // ---- ungapped shortcut: the diagonal through the sink ---------------------------------------------------------------
@@ -313,23 +279,21 @@ ungapped_full_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint3
                                const int32_t gap_open_min, const int32_t gap_ext_min)
 {
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
-    const JobInfo J = load_job( b, job );
+    const AlnJob J = load_job( b, job );
     const uint2   sink = sinks[job];
     const int32_t best = scores[job];
     need_dp[job] = 0;
-    if (J.M > max_M || J.N > max_N) { sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); cigar_lens[job] = 0xFFFFFFFFu; return; }
-    if (sink.x == 0xFFFFFFFFu || sink.y == 0xFFFFFFFFu) { sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); cigar_lens[job] = 0; return; }
+    if (J.M > max_M || J.N > max_N) { nothing_traced( sources, cigar_lens, job, 0xFFFFFFFFu ); return; }
+    if (sink.x == 0xFFFFFFFFu || sink.y == 0xFFFFFFFFu) { nothing_traced( sources, cigar_lens, job, 0u ); return; }
     // the DP, over the rows within G diagonals of the sink's when G can be bounded (end-to-end, match bonus 0, gap_ext_min > 0: see
     // full_gotoh_traceback_kernel): need_dp = 2 + G, else 1.  (One job over all rows in a launch of restricted ones is the launch's time.)
     auto dp_code = [&]() -> uint8_t {
         if (TYPE == NVBIO_SEMI_GLOBAL && gap_ext_min > 0 && sink.y == J.M && best <= 0)
         {
-            const int32_t a = -best;
-            const int32_t G = a < gap_open_min ? 0 : (a - gap_open_min) / gap_ext_min + 1;
+            const int32_t G = e2e_gap_bound( best, gap_open_min, gap_ext_min );
             if (G <= 250) return (uint8_t)(2 + G);
         }
         return (uint8_t)1;
@@ -343,27 +307,18 @@ ungapped_full_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint3
     const uint32_t kmax = sink.x < sink.y ? sink.x : sink.y;
     while (k < kmax && !found)
     {
-        const uint32_t pc  = sink.y - 1u - k;                    // pattern column, text row sink.x - 1 - k
-        const uint32_t idx = J.rev ? J.first + J.M - 1u - pc : J.first + pc;
-        uint32_t q = prd.get( idx );
-        if (J.comp && q < 4u) q = 3u - q;
-        const uint32_t qq = b.quals ? b.quals[idx] : 0u;
-        const uint32_t g  = trd.get( J.tb + sink.x - 1u - k );
-        Q += (g == q) ? sc.match : s_mm[qq < 63u ? qq : 63u];
+        uint32_t idx;                                            // pattern column sink.y - 1 - k, text row sink.x - 1 - k
+        const uint32_t q = pattern_symbol( prd, J, sink.y - 1u - k, &idx );
+        const int32_t  S = pattern_mismatch( b.quals, s_mm, idx );
+        const uint32_t g = trd.get( J.tb + sink.x - 1u - k );
+        Q += (g == q) ? sc.match : S;
         ++k;
         if (TYPE == NVBIO_LOCAL && Q == best) found = true;
     }
     if (TYPE == NVBIO_SEMI_GLOBAL) found = (k == sink.y && Q == best);
     if (!found) { need_dp[job] = dp_code(); return; }
 
-    uint16_t* cig = cigars + (size_t)job * cigar_stride;
-    uint32_t  clen = 0;
-    auto emit = [&](const uint32_t type, const uint32_t len) { if (clen < cigar_stride) cig[clen] = (uint16_t)(type | (len << 2)); ++clen; };
-    if (J.M - sink.y) emit( 3u, J.M - sink.y );
-    if (k)            emit( D_SUB, k );
-    if (sink.y - k)   emit( 3u, sink.y - k );
-    sources[job]    = make_uint2( sink.x - k, sink.y - k );
-    cigar_lens[job] = clen;
+    write_diagonal_cigar( sources, cigars, cigar_stride, cigar_lens, job, J.M, sink, k );
 }
 
 // ---- finish_alignment: edit distance + MDS byte stream of a traced alignment (nvBowtie traceback_inl.h:536-705) --------
@@ -382,7 +337,7 @@ finish_alignment_kernel(const BatchDev b, const uint2* __restrict__ sources, con
         if (mds_lens) mds_lens[job] = 0u;
         return;
     }
-    const JobInfo J = load_job( b, job );
+    const AlnJob J = load_job( b, job );
     SymbolReader<TBITS> trd( b.text );
     SymbolReader<RBITS> prd( b.reads );
     const uint16_t* cig = cigars + (size_t)job * cigar_stride;
@@ -404,11 +359,7 @@ finish_alignment_kernel(const BatchDev b, const uint2* __restrict__ sources, con
             if (t != 2u) ++j;
             if (t == 0u || t == 2u) ++k;
             uint32_t readc = 255u, refc = 255u;
-            if (t != 2u && j <= J.M)
-            {
-                readc = prd.get( J.rev ? J.first + J.M - j : J.first + j - 1u );
-                if (J.comp && readc < 4u) readc = 3u - readc;
-            }
+            if (t != 2u && j <= J.M) { uint32_t idx; readc = pattern_symbol( prd, J, j - 1u, &idx ); }
             if ((t == 0u || t == 2u) && k <= J.N) refc = trd.get( J.tb + k - 1u );
             if (t == 0u)
             {
@@ -444,7 +395,7 @@ tb_band_route_kernel(const BatchDev b, uint8_t* __restrict__ need_dp, const uint
 {
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
-    const JobInfo J = load_job( b, job );
+    const AlnJob J = load_job( b, job );
     const uint32_t code = need_dp[job];
     const uint2 sink = sinks[job];
     bool ok = code >= 2u && code - 2u <= 7u && sink.y == J.M && sink.x >= sink.y && J.N >= J.M + 14u;
@@ -520,25 +471,16 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
                                         uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream)
 {
     NVB_REQUIRE( gotoh != nullptr || sw != nullptr, "scheme is NULL" );
-    nvbio_gotoh_scheme as_gotoh;                                 // the magnitudes of the scheme, for the int16 bound below
-    if (sw) as_gotoh = nvbio_gotoh_scheme{ sw->match, -sw->mismatch, -sw->mismatch, sw->deletion, sw->deletion, sw->insertion, sw->insertion };
-    const nvbio_gotoh_scheme* scheme = gotoh ? gotoh : &as_gotoh;
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
     if (b.n == 0) return NVBIO_OK;
     NVB_REQUIRE( type == NVBIO_GLOBAL || type == NVBIO_LOCAL || type == NVBIO_SEMI_GLOBAL, "invalid alignment type" );
     NVB_REQUIRE( scores_dev && sources_dev && sinks_dev && cigar_lens_dev, "NULL output pointer" );
     NVB_REQUIRE( cigars_dev != nullptr || cigar_stride == 0, "cigars_dev is NULL" );
     NVB_REQUIRE( max_pattern_len > 0 && max_text_len > 0, "max_pattern_len / max_text_len must bound the jobs (they size the scratch)" );
+    if (!int16_checkpoints_ok( gotoh ? *gotoh : as_gotoh( *sw ), (int64_t)max_pattern_len + max_text_len + 1 ))
     {
-        int64_t step = scheme->match < 0 ? -(int64_t)scheme->match : scheme->match;
-        const int64_t c[] = { scheme->mm_min, scheme->mm_max, -(int64_t)scheme->pat_gap_open, -(int64_t)scheme->pat_gap_ext,
-                              -(int64_t)scheme->txt_gap_open, -(int64_t)scheme->txt_gap_ext };
-        for (int64_t v : c) { if (v < 0) v = -v; if (v > step) step = v; }
-        if (((int64_t)max_pattern_len + max_text_len + 1) * step > 30000)
-        {
-            set_error( "full traceback: scores of %u x %u jobs under this scheme can overflow the reference's int16 checkpoints", max_pattern_len, max_text_len );
-            return NVBIO_ERR_UNSUPPORTED;
-        }
+        set_error( "full traceback: scores of %u x %u jobs under this scheme can overflow the reference's int16 checkpoints", max_pattern_len, max_text_len );
+        return NVBIO_ERR_UNSUPPORTED;
     }
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
@@ -555,9 +497,8 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
     uint32_t *job_list = nullptr, *job_count = nullptr; ScratchBlock aux; uint8_t* need_dp = nullptr;
     uint32_t *band_list = nullptr, *band_count = nullptr, *band_wb = nullptr, *band_we = nullptr; uint8_t* band_route = nullptr;
     // the row-restricted DP applies to nvBowtie's end-to-end mode (see full_gotoh_traceback_kernel)
-    const int32_t go_min = -(sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go), ge_min = -(sc.pat_ge > sc.txt_ge ? sc.pat_ge : sc.txt_ge);
-    const bool narrow = type == NVBIO_SEMI_GLOBAL && sc.match == 0 && sc.mm_min >= 0 && sc.mm_max >= 0 && plain_gotoh( sc ) &&
-                        ge_min > 0 && go_min >= ge_min && !(b.algo & NVBIO_ALN_NO_NARROW_TRACEBACK);
+    int32_t go_min, ge_min;
+    const bool narrow = narrow_e2e( sc, type, b.algo, &go_min, &ge_min );
     const bool band_ok = narrow && shortcut && !(b.algo & NVBIO_ALN_NO_BAND_ROUTE);
     if (shortcut)
     {
@@ -626,21 +567,20 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
             st = NVB_LAUNCH( tb_band_fixup_kernel, dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b, (const uint32_t*)band_wb, (const uint32_t*)band_list,
                              (const uint32_t*)band_count, (uint2*)sources_dev, (uint2*)sinks_dev );
     }
-    for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
+    if (st != NVBIO_OK) return st;
+    return for_each_chunk( b.n, cap_jobs, [&](const uint32_t begin, const uint32_t jobs)
     {
-        const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
         uint32_t* column = (uint32_t*)scratch;
         const uint64_t jobs64 = ((uint64_t)jobs + 63u) & ~63ull;                  // whole waves own scratch
         uint32_t* dirs   = column + (size_t)jobs64 * max_text_len;
         const dim3 grid( (jobs + 127u) / 128u ), block( 128 );
-        st = with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
+        return with_value( AlnTypes(), type, [&](auto TYPE) { return with_bits( BitsAll(), rb, tbits, [&](auto P)
         {
-            return NVB_LAUNCH( (full_gotoh_traceback_kernel<TYPE,P.r,P.t>), grid, block, s, b, sc, max_pattern_len, max_text_len, (uint32_t)begin, jobs,
+            return NVB_LAUNCH( (full_gotoh_traceback_kernel<TYPE,P.r,P.t>), grid, block, s, b, sc, max_pattern_len, max_text_len, begin, jobs,
                                (const uint32_t*)job_list, (const uint32_t*)job_count, min_scores_dev, column, dirs, scores_dev, (uint2*)sources_dev,
                                (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, (const uint8_t*)(narrow ? need_dp : nullptr), sw ? 1u : 0u );
         }, [&] { return invalid_bits( rb, tbits ); } ); }, [&] { return invalid_type( type ); } );          // (the type and the pair were checked)
-    }
-    return st;
+    } );
 }
 
 extern "C" nvbio_status nvbio_full_gotoh_traceback(int device, nvbio_alignment_type type, const nvbio_gotoh_scheme* scheme,

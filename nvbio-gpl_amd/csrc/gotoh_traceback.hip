@@ -18,7 +18,7 @@
 // again coalesced across the wave, and run-length encodes straight into the caller's CIGAR array.
 // The two are identical as long as every score fits the reference's int16 checkpoints, which the
 // host checks from the scheme and the batch's max_read_len (else NVBIO_ERR_UNSUPPORTED).
-#include "gotoh_common.h"
+#include "gotoh_traceback_common.h"
 #include "bitplanes.h"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>
@@ -26,8 +26,6 @@
 namespace nvbio_amd {
 
 namespace {
-
-enum : uint32_t { D_SUB = 0u, D_INS = 1u, D_DEL = 2u, D_SINK = 3u, D_INS_EXT = 4u, D_DEL_EXT = 8u };
 
 template <int BAND, int TYPE, int RBITS, int TBITS>
 __global__ void __launch_bounds__(128)
@@ -41,35 +39,27 @@ banded_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32
     constexpr int WORDS = (BAND + 7) / 8;                        // 32-bit words of direction nibbles per row
 
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;   // slot inside this launch
-    if (t >= jobs) return;
-    // with a job list (the jobs the ungapped pass could not settle) slot t of this launch is entry
-    // job_begin + t of the list, and the list's length lives on the device
-    if (job_list && job_begin + t >= *job_count) return;
-    const uint32_t job = job_list ? job_list[job_begin + t] : job_begin + t;
+    uint32_t job;
+    if (!slot_job( job_list, job_count, job_begin, t, jobs, &job )) return;
 
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
+    const AlnJob J = load_job( b, job );
+    const uint32_t M = J.M;
     // band_off (a band-15 / band-7 launch over jobs of a band-31 batch, see the narrow-band route at the entry point): this job's band covers
     // columns [off, off + BAND) of the band the batch asked for -- the window begins `off` symbols later, sink and source move back by it
     const uint32_t off   = band_off ? band_off[job] : 0u;
-    const uint32_t tb    = b.win_begin[job] + off;
-    const uint32_t N     = b.win_end[job] - tb;
+    const uint32_t tb    = J.tb + off;
+    const uint32_t N     = J.N - off;
 
     int32_t  best   = NVBIO_SCORE_MIN;
     uint32_t best_x = 0xFFFFFFFFu, best_y = 0xFFFFFFFFu;
 
     if (M > b.max_read_len)                                      // would overrun the direction-vector scratch: skip, flagged
     {
-        scores[job] = best; sinks[job] = sources[job] = make_uint2( best_x, best_y );
-        cigar_lens[job] = 0xFFFFFFFFu;
+        scores[job] = best; sinks[job] = make_uint2( best_x, best_y );
+        nothing_traced( sources, cigar_lens, job, 0xFFFFFFFFu );
         return;
     }
 
@@ -107,11 +97,9 @@ banded_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32
 
         for (uint32_t i = 0; i < M; ++i)
         {
-            const uint32_t pidx = rev ? first + M - 1u - i : first + i;
-            uint32_t q = prd.get( pidx );
-            if (comp && q < 4u) q = 3u - q;
-            const uint32_t qq = b.quals ? b.quals[pidx] : 0u;
-            const int32_t  S  = s_mm[qq < 63u ? qq : 63u];
+            uint32_t pidx;
+            const uint32_t q = pattern_symbol( prd, J, i, &pidx );
+            const int32_t  S = pattern_mismatch( b.quals, s_mm, pidx );
 
             const uint32_t g_new = (i + (uint32_t)(BAND - 1) < N) ? trd.get( tb + i + (BAND - 1) ) : 255u;
 
@@ -213,26 +201,15 @@ banded_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32
 
     scores[job] = best;
     sinks[job]  = make_uint2( best_x == 0xFFFFFFFFu ? best_x : best_x + off, best_y );
-    if (best_x == 0xFFFFFFFFu || best_y == 0xFFFFFFFFu)         // banded_inl.h:376-379: nothing to trace
-    {
-        sources[job]    = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu );
-        cigar_lens[job] = 0;
-        return;
-    }
+    if (best_x == 0xFFFFFFFFu || best_y == 0xFFFFFFFFu) { nothing_traced( sources, cigar_lens, job, 0u ); return; }
 
     // ---- the walk back (gotoh_banded_inl.h:884-947), run-length encoded as nvBowtie's Backtracker does ----
-    uint16_t* cig = cigars + (size_t)job * cigar_stride;
-    uint32_t  clen = 0;
-    auto emit = [&](const uint32_t type, const uint32_t len) {
-        if (clen < cigar_stride) cig[clen] = (uint16_t)(type | (len << 2));
-        ++clen;
-    };
-    if (M - best_y) emit( 3u, M - best_y );                      // clip the end of the pattern (banded_inl.h:382)
+    CigarWriter cw( cigars, cigar_stride, job );
+    cw.clip( M - best_y );                                       // clip the end of the pattern (banded_inl.h:382)
 
     int32_t  entry = (int32_t)(best_x - best_y);
     int32_t  row   = (int32_t)best_y - 1;
     uint32_t state = 0;                                          // HSTATE 0, ESTATE 1, FSTATE 2
-    uint32_t prev = 255u, run = 0;
     uint32_t src_x = 0, src_y = 0;
     bool     found = false;
 
@@ -260,27 +237,21 @@ banded_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32
             src_y = (uint32_t)row + 1u; src_x = (uint32_t)entry + src_y; found = true;
             break;
         }
-        uint32_t push = 255u;
-        if (state == 1u)      { if ((op & D_INS_EXT) == 0u) state = 0u; --entry; push = D_DEL; }
-        else if (state == 2u) { if ((op & D_DEL_EXT) == 0u) state = 0u; ++entry; --row; push = D_INS; }
+        if (state == 1u)      { if ((op & D_INS_EXT) == 0u) state = 0u; --entry; cw.push( D_DEL ); }
+        else if (state == 2u) { if ((op & D_DEL_EXT) == 0u) state = 0u; ++entry; --row; cw.push( D_INS ); }
         else
         {
             if (h_op == D_DEL)      state = 1u;
             else if (h_op == D_INS) state = 2u;
-            else { --row; push = D_SUB; }
-        }
-        if (push != 255u)
-        {
-            if (push == prev) ++run;
-            else { if (run) emit( prev, run ); prev = push; run = 1u; }
+            else { --row; cw.push( D_SUB ); }
         }
     }
-    if (run) emit( prev, run );
+    cw.flush();
     if (!found) { src_y = 0u; src_x = (uint32_t)entry; }
-    if (src_y) emit( 3u, src_y );                                // clip the beginning (banded_inl.h:413)
+    cw.clip( src_y );                                            // clip the beginning (banded_inl.h:413)
 
     sources[job]    = make_uint2( src_x + off, src_y );
-    cigar_lens[job] = clen;
+    cigar_lens[job] = cw.length();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -303,30 +274,19 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
                           uint8_t* __restrict__ band_off, const int32_t gap_open_min, const int32_t gap_ext_min)
 {
     __shared__ int32_t s_mm[64];
-    if (threadIdx.x < 64) s_mm[threadIdx.x] = mismatch_score( sc, threadIdx.x );
-    __syncthreads();
+    fill_mismatch_table( s_mm, sc );
 
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
 
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0;
-    const bool     comp  = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = b.win_end[job] - tb;
+    const AlnJob   J = load_job( b, job );
+    const uint32_t first = J.first, M = J.M, tb = J.tb, N = J.N;
     const uint2    sink  = sinks[job];
     const int32_t  best  = scores[job];
 
     need_dp[job] = 0;
-    if (M > b.max_read_len) { sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); cigar_lens[job] = 0xFFFFFFFFu; return; }
-    if (sink.x == 0xFFFFFFFFu || sink.y == 0xFFFFFFFFu)
-    {
-        sources[job] = make_uint2( 0xFFFFFFFFu, 0xFFFFFFFFu ); cigar_lens[job] = 0;
-        return;
-    }
+    if (M > b.max_read_len) { nothing_traced( sources, cigar_lens, job, 0xFFFFFFFFu ); return; }
+    if (sink.x == 0xFFFFFFFFu || sink.y == 0xFFFFFFFFu) { nothing_traced( sources, cigar_lens, job, 0u ); return; }
 
     constexpr bool PACKED = !(BAND == 3 || BAND == 5 || BAND == 7 || BAND == 15);
     const uint32_t entry = sink.x - sink.y;
@@ -351,7 +311,7 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
             ReadWords<RB> rw; TextWords13 tw;
             load_read_words<RB>( b.reads, first, M, rw );
             load_text_words13( b.text, tb, N < 192u ? N : 192u, tw );
-            read_planes192<RB>( rw, first, M, rev, comp, rlo, rhi, rn );
+            read_planes192<RB>( rw, first, M, J.rev, J.comp, rlo, rhi, rn );
             text_planes208( tw, tb, tlo, thi );
             uint32_t cnt = 0;
             #pragma unroll
@@ -370,32 +330,28 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
     }
     for (int32_t row = (int32_t)sink.y - 1; row >= 0 && !found && !counted; --row)
     {
-        const uint32_t pidx = rev ? first + M - 1u - (uint32_t)row : first + (uint32_t)row;
-        uint32_t q = prd.get( pidx );
-        if (comp && q < 4u) q = 3u - q;
-        const uint32_t qq = b.quals ? b.quals[pidx] : 0u;
+        uint32_t pidx;
+        const uint32_t q  = pattern_symbol( prd, J, (uint32_t)row, &pidx );
+        const int32_t  S  = pattern_mismatch( b.quals, s_mm, pidx );
         const uint32_t ti = (uint32_t)row + entry;
         const uint32_t g  = ti < N ? trd.get( tb + ti ) : 255u;
         const bool eq = (entry == (uint32_t)(BAND - 1) || !PACKED) ? (g == q) : (q < 4u && (g & 3u) == q);
-        Q += eq ? sc.match : s_mm[qq < 63u ? qq : 63u];
+        Q += eq ? sc.match : S;
         ++k;
         if (TYPE == NVBIO_LOCAL && Q == best) found = true;
     }
     if (TYPE != NVBIO_LOCAL) found = (H0 + Q == best);
     if (!found)
     {
-        // Narrow-band route (band 31, end-to-end, match bonus 0; gap_open_min >= gap_ext_min > 0 are the cheapest open / extension
-        // penalties): every step of a path scores <= 0, so a path that reaches the known optimum S* holds gaps of at most
-        // G = (|S*| - open) / ext + 1 symbols in all (none if |S*| < open) and stays within G diagonals of the column it ends in.  With
-        // G <= 7 all of them fit a band of 15 around the sink's diagonal: the DP over that band alone gives every cell ON such a path
+        // Narrow-band route (band 31, end-to-end, match bonus 0): a path that reaches the known optimum S* stays within
+        // G = e2e_gap_bound() diagonals of the column it ends in.  With G <= 7 all of them fit a band of 15 around the sink's diagonal: the DP over that band alone gives every cell ON such a path
         // its exact value (its best predecessor is on one too) and can only lower the alternatives a direction rule compares it with,
         // never one that ties -- a tie would be another optimal path, inside the band as well -- so the directions along the traced
         // path, hence the CIGAR, are those of the full band at half the cells.  (N >= M + 30: no sentinel column is involved.)
         uint8_t code = 1;
         if (BAND == 31 && TYPE == NVBIO_SEMI_GLOBAL && band_off && gap_ext_min > 0 && sink.y == M && N >= M + 30u && best <= 0)
         {
-            const int32_t a = -best;
-            const int32_t G = a < gap_open_min ? 0 : (a - gap_open_min) / gap_ext_min + 1;
+            const int32_t G = e2e_gap_bound( best, gap_open_min, gap_ext_min );
             if (G <= 3)                                                    // a band of 7 (one short indel and at most one mismatch)
             {
                 code = 3;
@@ -411,17 +367,7 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
         return;
     }
 
-    uint16_t* cig = cigars + (size_t)job * cigar_stride;
-    uint32_t  clen = 0;
-    auto emit = [&](const uint32_t type, const uint32_t len) {
-        if (clen < cigar_stride) cig[clen] = (uint16_t)(type | (len << 2));
-        ++clen;
-    };
-    if (M - sink.y) emit( 3u, M - sink.y );
-    if (k)          emit( D_SUB, k );
-    if (sink.y - k) emit( 3u, sink.y - k );
-    sources[job]    = make_uint2( sink.x - k, sink.y - k );
-    cigar_lens[job] = clen;
+    write_diagonal_cigar( sources, cigars, cigar_stride, cigar_lens, job, M, sink, k );
 }
 
 template <int BAND>
@@ -457,7 +403,7 @@ nvbio_status launch_dp(int type, const BatchDev& b, const SchemeDev& sc, uint32_
 }
 
 inline uint64_t row_bytes(const uint32_t band) { return (uint64_t)((band + 7u) / 8u) * sizeof(uint32_t); }
-template <int CODE> struct IsCode { __host__ __device__ __forceinline__ uint8_t operator()(const uint8_t v) const { return v == (uint8_t)CODE ? 1u : 0u; } };
+struct IsCode { uint8_t code; __host__ __device__ __forceinline__ uint8_t operator()(const uint8_t v) const { return v == code ? 1u : 0u; } };
 
 } // anonymous namespace
 
@@ -471,14 +417,11 @@ nvbio_status banded15_full_ties_traceback(const BatchDev& b, const SchemeDev& sc
     const uint64_t per_job = (uint64_t)b.max_read_len * row_bytes( 15 );
     const uint64_t cap = dirs_bytes / (per_job ? per_job : 1u);
     if (cap < 64u) { set_error( "full traceback: scratch too small for the band-15 route" ); return NVBIO_ERR_INVALID; }
-    nvbio_status st = NVBIO_OK;
-    for (uint64_t begin = 0; begin < max_jobs && st == NVBIO_OK; begin += cap)
+    return for_each_chunk( max_jobs, cap, [&](const uint32_t begin, const uint32_t jobs)
     {
-        const uint32_t jobs = (uint32_t)((max_jobs - begin) < cap ? (max_jobs - begin) : cap);
-        st = launch_dp<15>( NVBIO_SEMI_GLOBAL, b, sc, rbits, tbits, (uint32_t)begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s,
-                            nullptr, 1u );
-    }
-    return st;
+        return launch_dp<15>( NVBIO_SEMI_GLOBAL, b, sc, rbits, tbits, begin, jobs, job_list, job_count, dirs, scores, sources, sinks, cigars, stride, lens, s,
+                              nullptr, 1u );
+    } );
 }
 } // namespace nvbio_amd
 
@@ -501,9 +444,6 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
                                           uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream)
 {
     NVB_REQUIRE( gotoh != nullptr || sw != nullptr, "scheme is NULL" );
-    nvbio_gotoh_scheme as_gotoh;                                 // the magnitudes of the scheme, for the int16 bound below
-    if (sw) as_gotoh = nvbio_gotoh_scheme{ sw->match, -sw->mismatch, -sw->mismatch, sw->deletion, sw->deletion, sw->insertion, sw->insertion };
-    const nvbio_gotoh_scheme* scheme = gotoh ? gotoh : &as_gotoh;
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
     if (b.n == 0) return NVBIO_OK;
     NVB_CHECK( check_band( band, NVBIO_ERR_INVALID ) );
@@ -511,18 +451,10 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
     NVB_REQUIRE( cigars_dev != nullptr || cigar_stride == 0, "cigars_dev is NULL" );
     NVB_REQUIRE( b.max_read_len > 0, "batch.max_read_len must bound the pattern lengths (it sizes the direction-vector scratch)" );
 
-    // the reference re-derives the direction vectors from int16 checkpoints (clamped at -32736,
-    // gotoh_banded_inl.h:216-222); the single pass here equals that iff no score can leave that range
+    if (!int16_checkpoints_ok( gotoh ? *gotoh : as_gotoh( *sw ), (int64_t)b.max_read_len + band + 1 ))
     {
-        int64_t step = scheme->match < 0 ? -(int64_t)scheme->match : scheme->match;
-        const int64_t c[] = { scheme->mm_min, scheme->mm_max, -(int64_t)scheme->pat_gap_open, -(int64_t)scheme->pat_gap_ext,
-                              -(int64_t)scheme->txt_gap_open, -(int64_t)scheme->txt_gap_ext };
-        for (int64_t v : c) { if (v < 0) v = -v; if (v > step) step = v; }
-        if (((int64_t)b.max_read_len + band + 1) * step > 30000)
-        {
-            set_error( "banded traceback: scores of %u-symbol reads under this scheme can overflow the reference's int16 checkpoints", b.max_read_len );
-            return NVBIO_ERR_UNSUPPORTED;
-        }
+        set_error( "banded traceback: scores of %u-symbol reads under this scheme can overflow the reference's int16 checkpoints", b.max_read_len );
+        return NVBIO_ERR_UNSUPPORTED;
     }
 
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
@@ -532,18 +464,15 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
     // ---- 1. scoring pass (the packed 16-bit kernel when the scheme allows) + 2. the ungapped shortcut ----------
     // (the diagonal shortcut of a LOCAL job rests on the walk stopping at the first SINK cell: not for the Smith-Waterman aligner)
     const bool shortcut = !(b.algo & NVBIO_ALN_NO_UNGAPPED_TRACEBACK) && !(sw && type == NVBIO_LOCAL);
-    uint8_t*  need_dp   = nullptr;      // [n] flags: 0 settled, 1 the DP, 2 / 3 the DP over a band of 15 / 7 (band 31 only)
-    uint32_t* job_list  = nullptr;      // [n] compacted job ids
-    uint32_t* job_count = nullptr;      // [1]
+    uint8_t*  need_dp   = nullptr;      // [n] flags: 0 settled, else the code of the route that takes the job
     uint8_t*  band_off  = nullptr;      // [n] narrow-band route: first column of the job's band of 15 / 7
-    uint32_t* job_list2 = nullptr;      // [n], [1]: the jobs of the band-15 route
-    uint32_t* job_count2 = nullptr;
-    uint32_t* job_list3 = nullptr;      // ... and of the band-7 route
-    uint32_t* job_count3 = nullptr;
+    // the DP's routes, in the order of their launches: need_dp code, band, compacted job ids [n] and their number [1] (on the device)
+    struct Route { uint8_t code; uint32_t band; uint32_t* list; uint32_t* count; };
+    Route routes[3] = { { 1, band, nullptr, nullptr }, { 2, 15u, nullptr, nullptr }, { 3, 7u, nullptr, nullptr } };
     // the narrow-band route applies to nvBowtie's end-to-end mode (see ungapped_traceback_kernel)
-    const int32_t go_min = -(sc.pat_go > sc.txt_go ? sc.pat_go : sc.txt_go), ge_min = -(sc.pat_ge > sc.txt_ge ? sc.pat_ge : sc.txt_ge);
-    const bool narrow = band == 31 && type == NVBIO_SEMI_GLOBAL && sc.match == 0 && sc.mm_min >= 0 && sc.mm_max >= 0 && plain_gotoh( sc ) &&
-                        ge_min > 0 && go_min >= ge_min && !(b.algo & NVBIO_ALN_NO_NARROW_TRACEBACK);
+    int32_t go_min, ge_min;
+    const bool narrow = narrow_e2e( sc, type, b.algo, &go_min, &ge_min ) && band == 31;
+    const uint32_t n_routes = (narrow && shortcut) ? 3u : 1u;
     ScratchBlock aux;
     if (shortcut)
     {
@@ -556,15 +485,11 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         void* sel_temp;
         NVB_CHECK( aux.alloc_layout( "banded_tb_job_list", s, "banded traceback: out of device memory for the job list", [&](ScratchLayout& c)
         {
-            need_dp    = c.take<uint8_t>( b.n );
-            job_list   = c.take<uint32_t>( b.n );
-            job_count  = c.take<uint32_t>( 1 );
-            band_off   = c.take<uint8_t>( b.n );
-            job_list2  = c.take<uint32_t>( b.n );
-            job_count2 = c.take<uint32_t>( 1 );
-            job_list3  = c.take<uint32_t>( b.n );
-            job_count3 = c.take<uint32_t>( 1 );
-            sel_temp   = c.take<uint8_t>( sel_bytes );
+            need_dp = c.take<uint8_t>( b.n );
+            routes[0].list = c.take<uint32_t>( b.n ); routes[0].count = c.take<uint32_t>( 1 );
+            band_off = c.take<uint8_t>( b.n );
+            for (int r = 1; r < 3; ++r) { routes[r].list = c.take<uint32_t>( b.n ); routes[r].count = c.take<uint32_t>( 1 ); }
+            sel_temp = c.take<uint8_t>( sel_bytes );
         } ) );
         const nvbio_status st1 = with_value( Bands(), band, [&](auto BAND)
         {
@@ -572,14 +497,13 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
                                           cigars_dev, cigar_stride, cigar_lens_dev, need_dp, narrow ? band_off : nullptr, go_min, ge_min, s );
         }, [] { return NVBIO_ERR_INVALID; } );                                // (the band was checked)
         NVB_CHECK( st1 );
-        // ---- 3. the jobs that do need the DP, compacted (their number stays on the device) ----
-        hipcub::TransformInputIterator<uint8_t, IsCode<1>, const uint8_t*> is_full( need_dp, IsCode<1>() );
-        hipcub::TransformInputIterator<uint8_t, IsCode<2>, const uint8_t*> is_narrow( need_dp, IsCode<2>() );
-        hipError_t e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is_full, job_list, job_count, (int)b.n, s );
-        if (e == hipSuccess && narrow) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is_narrow, job_list2, job_count2, (int)b.n, s );
-        hipcub::TransformInputIterator<uint8_t, IsCode<3>, const uint8_t*> is_narrow7( need_dp, IsCode<3>() );
-        if (e == hipSuccess && narrow) e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is_narrow7, job_list3, job_count3, (int)b.n, s );
-        if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+        // ---- 3. the jobs that do need the DP, compacted route by route (their numbers stay on the device) ----
+        for (uint32_t r = 0; r < n_routes; ++r)
+        {
+            hipcub::TransformInputIterator<uint8_t, IsCode, const uint8_t*> is_route( need_dp, IsCode{ routes[r].code } );
+            const hipError_t e = hipcub::DeviceSelect::Flagged( sel_temp, sel_bytes, ids, is_route, routes[r].list, routes[r].count, (int)b.n, s );
+            if (e != hipSuccess) { set_error( "DeviceSelect failed: %s", hipGetErrorString( e ) ); return NVBIO_ERR_HIP; }
+        }
     }
 
     // ---- 4. the DP with direction vectors + walk back, over the job list (or every job) ----
@@ -604,33 +528,21 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
         NVB_CHECK( owned.alloc( "banded_tb_dirs", cap_jobs * per_job, s, "banded traceback: out of device memory for %llu direction matrices", (unsigned long long)cap_jobs ) );
         dirs = (uint32_t*)owned.get();
     }
+    // the full band over its list, then the jobs of the narrow-band routes: the band-15 / band-7 kernel over theirs, as many more per
+    // launch as fit the same scratch
     nvbio_status st = NVBIO_OK;
-    for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap_jobs)
+    for (uint32_t r = 0; r < n_routes && st == NVBIO_OK; ++r)
     {
-        const uint32_t jobs = (uint32_t)((b.n - begin) < cap_jobs ? (b.n - begin) : cap_jobs);
-        st = with_value( Bands(), band, [&](auto BAND)
+        const Route& rt = routes[r];
+        const uint64_t cap = cap_jobs * per_job / ((uint64_t)b.max_read_len * row_bytes( rt.band ));
+        st = for_each_chunk( b.n, cap, [&](const uint32_t begin, const uint32_t jobs)
         {
-            return launch_dp<BAND>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list, job_count, dirs, scores_dev,
-                                    (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s );
-        }, [] { return NVBIO_ERR_INVALID; } );                                // (the band was checked)
-    }
-    if (narrow && shortcut)
-    {
-        // the jobs of the narrow-band route: the band-15 kernel over their list, twice as many per launch in the same scratch
-        const uint64_t cap2 = cap_jobs * per_job / ((uint64_t)b.max_read_len * row_bytes( 15 ));
-        for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap2)
-        {
-            const uint32_t jobs = (uint32_t)((b.n - begin) < cap2 ? (b.n - begin) : cap2);
-            st = launch_dp<15>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list2, job_count2, dirs, scores_dev,
-                                  (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s, band_off );
-        }
-        const uint64_t cap3 = cap_jobs * per_job / ((uint64_t)b.max_read_len * row_bytes( 7 ));
-        for (uint64_t begin = 0; begin < b.n && st == NVBIO_OK; begin += cap3)
-        {
-            const uint32_t jobs = (uint32_t)((b.n - begin) < cap3 ? (b.n - begin) : cap3);
-            st = launch_dp<7>( type, b, sc, batch->read_bits, batch->text_bits, (uint32_t)begin, jobs, job_list3, job_count3, dirs, scores_dev,
-                                 (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s, band_off );
-        }
+            return with_value( Bands(), (int)rt.band, [&](auto BAND)
+            {
+                return launch_dp<BAND>( type, b, sc, batch->read_bits, batch->text_bits, begin, jobs, rt.list, rt.count, dirs, scores_dev,
+                                        (uint2*)sources_dev, (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, s, r ? band_off : nullptr );
+            }, [] { return NVBIO_ERR_INVALID; } );                            // (the band was checked)
+        } );
     }
     return st;
 }

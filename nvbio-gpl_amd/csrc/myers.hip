@@ -22,13 +22,8 @@ banded_myers_kernel(const BatchDev b, const uint32_t band, const int type, const
 {
     const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= b.n) return;
-    const uint32_t rid   = b.read_id ? b.read_id[job] : job;
-    const uint32_t first = b.read_offsets[rid];
-    const uint32_t M     = b.read_offsets[rid + 1] - first;
-    const uint32_t fl    = b.flags ? b.flags[job] : 0u;
-    const bool     rev   = (fl & NVBIO_READ_REVERSE) != 0, comp = (fl & NVBIO_READ_COMPLEMENT) != 0;
-    const uint32_t tb    = b.win_begin[job];
-    const uint32_t N     = (b.max_read_len && M > b.max_read_len) ? 0u : b.win_end[job] - tb;
+    const AlnJob   J  = load_job( b, job );
+    const uint32_t M  = J.M, tb = J.tb, N = scored_text_len( b, J );
 
     int32_t  best = NVBIO_SCORE_MIN;
     uint32_t bx = 0xFFFFFFFFu, by = 0xFFFFFFFFu;
@@ -37,10 +32,6 @@ banded_myers_kernel(const BatchDev b, const uint32_t band, const int type, const
         const int32_t min_score = (int32_t)(int16_t)min_score32;            // `const int16 min_score`
         SymbolReader<RBITS> pr( b.reads );
         SymbolReader<TBITS> tr( b.text );
-        auto pattern = [&](const uint32_t i) -> uint32_t {
-            const uint32_t c = pr.get( rev ? first + M - 1u - i : first + i );
-            return (comp && c < 4u) ? 3u - c : c;
-        };
         uint32_t B0 = 0, B1 = 0, B2 = 0, B3 = 0, B4 = 0;                     // MyersBitVectors<5>
         uint32_t VP = 0xFFFFFFFFu, VN = 0u;
         int32_t  dist = 0;
@@ -61,7 +52,8 @@ banded_myers_kernel(const BatchDev b, const uint32_t band, const int type, const
         for (uint32_t i = 0; i < last; ++i)
         {
             B0 >>= 1; B1 >>= 1; B2 >>= 1; B3 >>= 1; B4 >>= 1;
-            const uint32_t p = pattern( i );
+            uint32_t pidx;
+            const uint32_t p = pattern_symbol( pr, J, i, &pidx );
             B0 |= p == 0u ? top : 0u; B1 |= p == 1u ? top : 0u; B2 |= p == 2u ? top : 0u; B3 |= p == 3u ? top : 0u; B4 |= p == 4u ? top : 0u;
             uint32_t D0, HP, HN;
             column( match_vector( tr.get( tb + i ) ), D0, HP, HN );

@@ -309,6 +309,9 @@ def test_full_traceback_edge_cases(amd, orc):
         # a job beyond the declared bounds is skipped and flagged, the others are traced
         sc, src, snk, cig, ln = tb.enact(batch, 40, 90, cigar_stride=32)
         assert amd.u32(ln)[1] == 0xFFFFFFFF and amd.u32(ln)[0] == 1 and int(sc[0]) == 0
+        assert tuple(amd.u32(src)[1]) == (0xFFFFFFFF, 0xFFFFFFFF)
+        if hasattr(al, "sw"):                                     # every job of the Smith-Waterman aligner takes the DP kernel, which reports nothing for it
+            assert int(sc[1]) == oracle.SCORE_MIN and tuple(amd.u32(snk)[1]) == (0xFFFFFFFF, 0xFFFFFFFF)
     with pytest.raises(amd.NvbioError):                            # scores could overflow the int16 checkpoints
         amd.BatchedAlignmentTraceback(amd.make_smith_waterman_aligner(oracle.LOCAL, amd.SimpleSmithWatermanScheme(300, -300, -300, -300))).enact(batch, 60, 90)
 
@@ -439,3 +442,163 @@ def test_full_traceback_opposite_mate_shape(amd, orc, typ, tb_mode):
             assert sc[j] == s_ and tuple(snk[j]) == wsnk and tuple(src[j]) == wsrc and ln[j] == len(wc), (j, kw.keys())
             m = min(int(ln[j]), 40)                                 # elements beyond the stride are dropped, the count is not
             assert np.array_equal(cig[j, :m], wc[:m]), j
+
+
+# ---- what the two tracebacks share: the CIGAR writer and the rule for a read longer than the declared bound ------------------------
+E2E = (0, 6, 6, -8, -3, -8, -3)
+ONES = (0xFFFFFFFF, 0xFFFFFFFF)
+_shared = {}
+
+
+def _edited_reads(rng, text, starts, M, every=4):
+    """reads of M symbols planted at `starts`; every fourth carries a 2-symbol deletion, a substitution and a 1-symbol insertion, each at
+    least 8 symbols from the next (a deletion and a substitution alone make three CIGAR elements, M D M: io::Cigar's M covers a mismatch;
+    the insertion makes them five)"""
+    reads = []
+    for j, s in enumerate(starts):
+        if j % every:
+            reads.append(text[s:s + M].copy())
+            continue
+        a = int(rng.integers(6, 11)); c = a + 8 + int(rng.integers(0, 4)); b = c + 8 + int(rng.integers(0, 4))
+        r = np.concatenate([text[s:s + a], text[s + a + 2:s + M + 1]])          # M - 1 symbols
+        r[c] = (r[c] + 1 + rng.integers(0, 3)) & 3
+        reads.append(np.concatenate([r[:b], rng.integers(0, 4, 1, dtype=np.uint8), r[b:]]).astype(np.uint8))
+    return reads
+
+
+def _long_cigar_jobs(orc):
+    """256 reads of 40 symbols (4-bit) in a 2-bit text, band-31 windows and 90-symbol windows (the first 128 jobs) around them, and the
+    oracle's tracebacks at a stride no CIGAR reaches -- computed once, shared, never modified"""
+    if "cigar" not in _shared:
+        rng = np.random.default_rng(11)
+        R, M = 256, 40
+        text = rng.integers(0, 4, 200 * R + 400, dtype=np.uint8)
+        starts = 100 + 200 * np.arange(R) + rng.integers(0, 50, R)
+        reads = _edited_reads(rng, text, starts, M)
+        flat = np.concatenate(reads)
+        roffs = (np.arange(R + 1) * M).astype(np.uint32)
+        wb = (starts - 15).astype(np.uint32); we = (wb + M + 31).astype(np.uint32)
+        banded = orc.banded_gotoh_traceback_packed_batch(31, oracle.SEMI_GLOBAL, oracle.Scheme(*E2E), orc.pack4(flat), roffs, orc.pack2(text), wb, we, 48)
+        fb = (starts[:128] - 25).astype(np.uint32); fe = (fb + 90).astype(np.uint32)
+        full = [orc.full_gotoh_traceback(oracle.SEMI_GLOBAL, oracle.Scheme(*E2E), reads[j], text[fb[j]:fe[j]]) for j in range(128)]
+        for v in banded:
+            v.setflags(write=False)
+        _shared["cigar"] = dict(M=M, text=text, flat=flat, roffs=roffs, wb=wb, we=we, banded=banded, fb=fb, fe=fe, full=full)
+    return _shared["cigar"]
+
+
+@pytest.mark.parametrize("algo", ["default", "dp-only"])
+@pytest.mark.parametrize("family", ["banded", "full"])
+def test_cigar_longer_than_its_row(amd, orc, family, algo):
+    """CigarWriter counts the elements it has no room for: with cigar_stride = 2, cigar_lens, scores, sources and sinks are those of
+    the stride-48 run, the two stored elements are its first two, and finish_alignment marks exactly the truncated rows.  (The
+    reads carry a 1-symbol insertion besides the deletion and the substitution: those two alone give M D M, three elements.)"""
+    d = _long_cigar_jobs(orc)
+    M = d["M"]
+    # the input condition, from the oracle alone
+    if family == "banded":
+        n, wb, we = 256, d["wb"], d["we"]
+        o_sc, o_src, o_snk, o_cig, o_len = d["banded"]
+    else:
+        n, wb, we = 128, d["fb"], d["fe"]
+        o_sc = np.array([f[1] for f in d["full"]]); o_src = np.array([f[2] for f in d["full"]]); o_snk = np.array([f[3] for f in d["full"]])
+        o_len = np.array([len(f[4]) for f in d["full"]])
+        o_cig = np.zeros((n, 48), dtype=np.uint16)
+        for j, f in enumerate(d["full"]):
+            o_cig[j, :len(f[4])] = f[4]
+    assert (o_len >= 4).sum() >= 32 and (o_len >= 1).all() and o_len.max() <= 48
+    assert (o_len <= 2).sum() >= 32                               # rows that fit a stride of 2 are in as well
+
+    flags = amd.ALN_NO_UNGAPPED_TRACEBACK if algo == "dp-only" else 0
+    batch = amd.AlignmentBatch(orc.pack4(d["flat"]), 4, d["roffs"][:n + 1], orc.pack2(d["text"]), 2, wb, we, max_read_len=M, algo_flags=flags)
+    al = amd.make_gotoh_aligner(oracle.SEMI_GLOBAL, _scheme(amd, E2E))
+    run = (lambda st: amd.BatchedBandedAlignmentTraceback(31, al).enact(batch, cigar_stride=st)) if family == "banded" else \
+          (lambda st: amd.BatchedAlignmentTraceback(al).enact(batch, M, 90, cigar_stride=st))
+    sc, src, snk, cig, ln = run(48)
+    assert np.array_equal(sc.cpu().numpy(), o_sc) and np.array_equal(amd.u32(src), o_src) and np.array_equal(amd.u32(snk), o_snk)
+    assert np.array_equal(amd.u32(ln), o_len) and np.array_equal(cig.cpu().numpy().view(np.uint16), o_cig)
+    sc2, src2, snk2, cig2, ln2 = run(2)
+    assert np.array_equal(amd.u32(ln2), o_len)                    # counted, not written
+    assert np.array_equal(cig2.cpu().numpy().view(np.uint16), o_cig[:, :2])
+    assert np.array_equal(sc2.cpu().numpy(), o_sc) and np.array_equal(amd.u32(src2), o_src) and np.array_equal(amd.u32(snk2), o_snk)
+    ed, mds, ml = amd.finish_alignment(batch, src2, cig2, ln2, mds_stride=64)
+    ed, ml = amd.u32(ed), amd.u32(ml)
+    assert np.array_equal(ed == 0xFFFFFFFF, o_len > 2) and np.array_equal(ml == 0, o_len > 2)
+
+
+def _long_read_jobs(orc):
+    """130 jobs, max_read_len = 40: jobs 0 and 129 have 41 symbols; band-31 and 90-symbol windows; the oracle knows no bound"""
+    if "long" not in _shared:
+        rng = np.random.default_rng(23)
+        R, L = 130, 40
+        lens = np.full(R, L); lens[0] = lens[R - 1] = L + 1
+        text = rng.integers(0, 4, 200 * R + 400, dtype=np.uint8)
+        starts = 100 + 200 * np.arange(R) + rng.integers(0, 50, R)
+        reads = _edited_reads(rng, text, starts, L)
+        reads[0] = text[starts[0]:starts[0] + L + 1].copy(); reads[R - 1] = text[starts[R - 1]:starts[R - 1] + L + 1].copy()
+        flat = np.concatenate(reads)
+        roffs = np.zeros(R + 1, dtype=np.uint32); roffs[1:] = np.cumsum(lens)
+        wb = (starts - 15).astype(np.uint32); we = (wb + lens + 31).astype(np.uint32)
+        banded = orc.banded_gotoh_traceback_packed_batch(31, oracle.SEMI_GLOBAL, oracle.Scheme(*E2E), orc.pack4(flat), roffs, orc.pack2(text), wb, we, 16)
+        fb = (starts - 25).astype(np.uint32); fe = (fb + 90).astype(np.uint32)
+        full = [orc.full_gotoh_traceback(oracle.SEMI_GLOBAL, oracle.Scheme(*E2E), reads[j], text[fb[j]:fe[j]]) for j in range(R)]
+        myers = [orc.banded_myers(31, oracle.SEMI_GLOBAL, reads[j], text[wb[j]:we[j]], -32768) for j in range(R)]
+        for v in banded:
+            v.setflags(write=False)
+        _shared["long"] = dict(L=L, R=R, text=text, flat=flat, roffs=roffs, reads=reads, wb=wb, we=we, banded=banded, fb=fb, fe=fe, full=full, myers=myers)
+    return _shared["long"]
+
+
+@pytest.mark.parametrize("family", ["banded-traceback", "full-traceback", "banded-score", "myers"])
+def test_read_longer_than_declared_bound(amd, orc, family):
+    """the rule each family keeps for a read longer than the batch's declared bound, in the first and in the last launch of a batch that
+    takes several (caller scratch for 64 jobs): the tracebacks flag the job (cigar_lens = 0xFFFFFFFF) and report nothing, the banded
+    scorer and Myers report nothing; every other job equals the oracle.  The tracebacks run with ALN_NO_UNGAPPED_TRACEBACK, so that the DP
+    kernels themselves meet the job -- and because the full-matrix traceback's scoring pass knows no bound: behind the shortcut it leaves
+    its own score and sink for the flagged job, as before this test existed -- and the banded one with the default flags as well."""
+    import torch
+    d = _long_read_jobs(orc)
+    L, R = d["L"], d["R"]
+    long_jobs = np.array([0, R - 1]); rest = np.arange(1, R - 1)
+    lens = np.diff(d["roffs"].astype(np.int64))
+    assert R == 130 and (lens[long_jobs] == L + 1).all() and (lens[rest] == L).all()
+    assert (d["banded"][4][rest] >= 1).all() and (d["banded"][4][rest] >= 4).any()          # traced everywhere, gapped ones among them
+
+    al = amd.make_gotoh_aligner(oracle.SEMI_GLOBAL, _scheme(amd, E2E))
+    mk = lambda wb, we, flags=0: amd.AlignmentBatch(orc.pack4(d["flat"]), 4, d["roffs"], orc.pack2(d["text"]), 2, wb, we, max_read_len=L, algo_flags=flags)
+    if family in ("banded-traceback", "full-traceback"):
+        for flags in ((amd.ALN_NO_UNGAPPED_TRACEBACK, 0) if family == "banded-traceback" else (amd.ALN_NO_UNGAPPED_TRACEBACK,)):
+            if family == "banded-traceback":
+                batch = mk(d["wb"], d["we"], flags)
+                op = amd.BatchedBandedAlignmentTraceback(31, al)
+                temp = torch.empty(64 * L * 16, dtype=torch.uint8, device="cuda:0")
+                sc, src, snk, cig, ln = op.enact(batch, cigar_stride=16, temp=temp)
+                o_sc, o_src, o_snk, o_cig, o_len = d["banded"]
+            else:
+                batch = mk(d["fb"], d["fe"], flags)
+                op = amd.BatchedAlignmentTraceback(al)
+                need = op.min_temp_storage(batch, L, 90)                # whole waves: 192 jobs' worth
+                temp = torch.empty(need // 3, dtype=torch.uint8, device="cuda:0")
+                sc, src, snk, cig, ln = op.enact(batch, L, 90, cigar_stride=16, temp=temp)
+                o_sc = np.array([f[1] for f in d["full"]]); o_src = np.array([f[2] for f in d["full"]]); o_snk = np.array([f[3] for f in d["full"]])
+                o_len = np.array([len(f[4]) for f in d["full"]])
+                o_cig = np.zeros((R, 16), dtype=np.uint16)
+                for j, f in enumerate(d["full"]):
+                    o_cig[j, :len(f[4])] = f[4]
+            sc, src, snk, ln, cig = sc.cpu().numpy(), amd.u32(src), amd.u32(snk), amd.u32(ln), cig.cpu().numpy().view(np.uint16)
+            for j in long_jobs:
+                assert ln[j] == 0xFFFFFFFF and sc[j] == oracle.SCORE_MIN and tuple(src[j]) == ONES and tuple(snk[j]) == ONES, (flags, j)
+            assert np.array_equal(sc[rest], o_sc[rest]) and np.array_equal(src[rest], o_src[rest]) and np.array_equal(snk[rest], o_snk[rest]), flags
+            assert np.array_equal(ln[rest], o_len[rest]) and np.array_equal(cig[rest], o_cig[rest]), flags
+    else:
+        batch = mk(d["wb"], d["we"])
+        if family == "banded-score":
+            sc, snk = amd.batch_banded_alignment_score(31, al, batch)
+            o_sc, o_snk = d["banded"][0], d["banded"][2]
+        else:
+            sc, snk = amd.batch_banded_myers_score(31, amd.SEMI_GLOBAL, batch, -32768)
+            o_sc = np.array([m[1] for m in d["myers"]]); o_snk = np.array([[m[2][0] & 0xFFFFFFFF, m[2][1] & 0xFFFFFFFF] for m in d["myers"]])
+        sc, snk = sc.cpu().numpy(), amd.u32(snk)
+        for j in long_jobs:
+            assert sc[j] == oracle.SCORE_MIN and tuple(snk[j]) == ONES, j
+        assert np.array_equal(sc[rest], o_sc[rest]) and np.array_equal(snk[rest], o_snk[rest])
