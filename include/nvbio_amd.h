@@ -141,6 +141,7 @@ enum
     NVBIO_FM_TABLE_CANONICAL_WIDE = 16, /* NVBIO_FM_TABLE_CANONICAL with 16-byte entries: a k-mer with TWO occurrences (of either orientation) has
                                        both rows in its entry, so that only k-mers with three or more take the second gather (1.07 instead
                                        of 1.25 sectors per seed window on a 3 Gbp text; 128 GiB at k = 17)                         */
+    NVBIO_FM_TABLE_NO_TEXT_PLANES = 32, /* a handle that keeps the text does not also keep it as bit planes (nvbio_fm_index_text_planes: none)  */
     NVBIO_FM_TABLE_CANONICAL  = 8   /* instead of the direct table: ONE table for a k-mer and its reverse complement (kmer_len odd; 64 GiB at
                                        k = 17 where the direct table takes 128), serving nvbio_fm_match_seed_diagonals_both; the plain table of
                                        (kmer_len - 1)-mers is kept for match().  Needs sa_int = 1.                                */
@@ -168,6 +169,20 @@ nvbio_status nvbio_fm_index_get_view(nvbio_fm_index_t index, nvbio_fm_index_view
 nvbio_status nvbio_fm_index_export(nvbio_fm_index_t index, uint32_t* bwt_occ_out_dev, uint32_t* ssa_out_dev, void* stream);
 /* bytes of HBM owned by the handle (k-mer table, and the index arrays if it was built here) */
 nvbio_status nvbio_fm_index_device_bytes(nvbio_fm_index_t index, uint64_t* bytes);
+
+/* The text as bit planes, the constant input of the band-31 end-to-end passes (nvbio_alignment_batch::text_planes_dev).
+ * A unit is 16 bytes, (lo64, hi64) of 64 consecutive symbols: bit j of lo64 / hi64 = the low / high bit of symbol 64 u + j.
+ * Line L (128 bytes) holds units 4 L .. 4 L + 7, i.e. symbols 256 L .. 256 L + 511 -- consecutive lines overlap by half, so
+ * the up to 197 symbols a job looks at, from any symbol tb on, lie in the ONE line tb >> 8.  ((length + 255) >> 8) + 1 lines
+ * (twice the packed text: 1.5 GB at 3 Gbp); every bit at or beyond `length` is zero.
+ * nvbio_text_planes_build: one streaming pass over the 2-bit big-endian packed text ((length + 15) / 16 words are read) into
+ * the caller's buffer of nvbio_text_planes_bytes bytes, which must be 128-byte aligned (NVBIO_ERR_INVALID otherwise). */
+nvbio_status nvbio_text_planes_bytes(uint32_t length, uint64_t* bytes);
+nvbio_status nvbio_text_planes_build(int device, const uint32_t* text2_dev, uint32_t length, void* planes_dev, void* stream);
+/* The planes a handle keeps: one that keeps the text (nvbio_fm_index_build with sa_int = 1) builds them from its copy unless
+ * NVBIO_FM_TABLE_NO_TEXT_PLANES is set, and counts them in nvbio_fm_index_device_bytes.  *planes_dev = NULL (and *length = 0)
+ * where there are none.  Like the handle itself they describe the text as it was when the index was built. */
+nvbio_status nvbio_fm_index_text_planes(nvbio_fm_index_t index, const void** planes_dev, uint32_t* length);
 
 /* A set of query strings in HBM: the string-set concept FMIndexFilter::rank consumes
  * (nvbio/fmindex/filter.h:52-231) flattened to arrays.
@@ -1098,6 +1113,13 @@ typedef struct
     uint32_t        algo_flags;        /* NVBIO_ALN_*: which of the library's exact shortcuts / kernel variants a
                                           call may use (0 = all; A/B measurements and tests -- results are
                                           identical with every combination)                                  */
+    const void*     text_planes_dev;   /* the text as bit planes (nvbio_text_planes_build, or a handle's:
+                                          nvbio_fm_index_text_planes), or NULL (what zero-initialising the struct
+                                          gives): band-31 end-to-end scoring and its traceback then take a window's
+                                          planes with four 16-byte loads from one 128-byte line instead of building
+                                          them from 13 packed words per job.  Meaningful with text_bits == 2 only,
+                                          128-byte aligned.  The planes describe the text AS IT WAS WHEN THEY WERE
+                                          BUILT: pass them only with that very text.  Results are identical.        */
 } nvbio_alignment_batch;
 
 
@@ -1141,6 +1163,8 @@ enum
                                                 diagonals once (gap_chance_e2e31_pair) (A/B)                                                           */
     NVBIO_ALN_NO_NARROW_DP          = 524288, /* band-31 end-to-end scoring: every DP job over all 31 columns; the first pass forms no classes of jobs whose
                                                 score bound U* confines the optimal paths to 13 or 17 columns (banded_gotoh_band31_pk_kernel, NARROW) (A/B) */
+    NVBIO_ALN_NO_TEXT_PLANES        = 1048576, /* band-31 end-to-end scoring and traceback: ignore the batch's text_planes_dev and build every window's
+                                                 planes from the packed text, as a batch without planes does (A/B)                                     */
     NVBIO_ALN_NO_NARROW_TRACEBACK   = 64   /* band-31 end-to-end traceback: every DP over the whole band (no band-15 route for the jobs
                                               whose optimal paths provably stay within 7 diagonals of the sink)                  */
 };

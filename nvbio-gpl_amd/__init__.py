@@ -34,6 +34,7 @@ GLOBAL, LOCAL, SEMI_GLOBAL = 0, 1, 2
 SCORE_MIN = -(1 << 30)
 FM_SCAN_FORWARD, FM_COMPLEMENT, FM_NO_KMER_TABLE, FM_NO_VERIFY, FM_COUNT_SECTORS, FM_NO_PIPELINE, FM_DEFER_HEAVY = 1, 2, 4, 8, 16, 32, 64
 FM_TABLE_NO_DIRECT, FM_TABLE_NO_CONTEXT, FM_TABLE_NO_GROUPS, FM_TABLE_CANONICAL, FM_TABLE_CANONICAL_WIDE = 1, 2, 4, 8, 16      # nvbio_fm_build_options::table_flags
+FM_TABLE_NO_TEXT_PLANES = 32
 READ_REVERSE, READ_COMPLEMENT = 1, 2
 TRACEBACK_SINKS_GIVEN = 1
 # nvbio_alignment_batch::algo_flags (which exact shortcuts / kernel variants a call may use; results do not depend on them)
@@ -42,6 +43,7 @@ ALN_NO_NARROW_TRACEBACK, ALN_NO_SECOND_CHANCE, ALN_PK_STRIPE8, ALN_NO_NARROW_SCO
 ALN_NO_QUALITY_SHORTCUT, ALN_RAGGED_READS, ALN_NO_LENGTH_SORT, ALN_NO_F16_DP, ALN_NO_COOPERATIVE_DP, ALN_NO_GAP_CHANCE = 2048, 4096, 8192, 16384, 32768, 65536
 ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE = 131072, 262144
 ALN_NO_NARROW_DP = 524288
+ALN_NO_TEXT_PLANES = 1048576
 ROUTE_SETTLED, ROUTE_FULL_BAND, ROUTE_CLASS_A, ROUTE_CLASS_B, ROUTE_REDONE = 0, 1, 2, 3, 8
 DEFAULT_ALGO_FLAGS = 0          # what an AlignmentBatch is created with unless told otherwise (tests set it for a whole run)
 BACKTRACK_REFERENCE_QUIRKS = 1
@@ -92,7 +94,8 @@ class _Batch(ctypes.Structure):
                 ("read_id_dev", ctypes.c_void_p), ("flags_dev", ctypes.c_void_p),
                 ("text_dev", ctypes.c_void_p), ("text_bits", ctypes.c_uint32),
                 ("win_begin_dev", ctypes.c_void_p), ("win_end_dev", ctypes.c_void_p), ("n", ctypes.c_uint32),
-                ("max_read_len", ctypes.c_uint32), ("algo_flags", ctypes.c_uint32)]
+                ("max_read_len", ctypes.c_uint32), ("algo_flags", ctypes.c_uint32),
+                ("text_planes_dev", ctypes.c_void_p)]
 
 
 class _HitQueues(ctypes.Structure):
@@ -257,6 +260,8 @@ class FMIndex:
 
     def __init__(self, handle, device, keep=()):
         self._h, self.device, self._keep = handle, device, keep
+        self._text_src = None                        # (data_ptr, length) of the text build() was given: what text_planes() describe
+        self._text_planes = None                     # text_planes() of a built handle, asked once: constant while the handle lives
 
     @staticmethod
     def _dev_index(device):
@@ -295,7 +300,10 @@ class FMIndex:
                              0 if bucket_symbols is None else 1 + int(bucket_symbols))
         _check(lib().nvbio_fm_index_build(_ptr(t), ctypes.c_uint32(length), cls._dev_index(device),
                                           ctypes.byref(opts), _stream_ptr(device), ctypes.byref(h)))
-        return cls(h, device, keep=(t,))
+        fmi = cls(h, device, keep=(t,))
+        fmi._text_src = (t.data_ptr(), int(length))
+        fmi._text_planes = fmi.text_planes()
+        return fmi
 
     @classmethod
     def load(cls, bwt_path, sa_path=None, kmer_len=0, device="cuda:0"):
@@ -350,6 +358,20 @@ class FMIndex:
         b = ctypes.c_uint64()
         _check(lib().nvbio_fm_index_device_bytes(self._h, ctypes.byref(b)))
         return b.value
+
+    def text_planes(self):
+        """nvbio_fm_index_text_planes: (device pointer, length) of the text as bit planes -- what AlignmentBatch(text_planes=) takes, valid
+        while the handle lives -- or None for a handle without them (no text kept, or built with FM_TABLE_NO_TEXT_PLANES)"""
+        p, n = ctypes.c_void_p(), ctypes.c_uint32()
+        _check(lib().nvbio_fm_index_text_planes(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return (p.value, n.value) if p.value else None
+
+    def text_planes_of(self, text2, length):
+        """text_planes()'s pointer if the handle was built from this very text -- the same device address and length -- else None
+        (no call into the library: build() asked once)"""
+        tp = self._text_planes if self._h is not None else None
+        same = tp is not None and self._text_src == (text2.data_ptr(), int(length)) and tp[1] == int(length)
+        return tp[0] if same else None
 
     # -- free functions of nvbio/fmindex/fmindex.h:370-557 ---------------------------------------
     def match(self, queries, flags=0, want_blocks=False):
@@ -1147,9 +1169,12 @@ class AlignmentBatch:
     """The flattened stream of alignment jobs (see nvbio_alignment_batch)."""
 
     def __init__(self, reads, read_bits, read_offsets, text, text_bits, win_begin, win_end, quals=None, read_id=None,
-                 flags=None, device="cuda:0", max_read_len=0, algo_flags=None):
+                 flags=None, device="cuda:0", max_read_len=0, algo_flags=None, text_planes=None):
+        """text_planes: the text as bit planes -- a device pointer (FMIndex.text_planes()[0], FMIndex.text_planes_of) or a uint8 tensor
+        filled by build_text_planes -- of THIS text as it stands, or None"""
         torch = _torch()
         self.device = device
+        self.text_planes = text_planes
         self.algo_flags = DEFAULT_ALGO_FLAGS if algo_flags is None else int(algo_flags)
         self.read_bits, self.text_bits = int(read_bits), int(text_bits)
         self.reads = _dev_tensor(reads, torch.uint8 if read_bits == 8 else torch.int32, device)
@@ -1169,7 +1194,25 @@ class AlignmentBatch:
     def c_struct(self):
         return _Batch(_ptr(self.reads), self.read_bits, _ptr(self.read_offsets), _ptr(self.quals), _ptr(self.read_id),
                       _ptr(self.flags), _ptr(self.text), self.text_bits, _ptr(self.win_begin), _ptr(self.win_end),
-                      self.n, self.max_read_len, self.algo_flags)
+                      self.n, self.max_read_len, self.algo_flags,
+                      ctypes.c_void_p(self.text_planes.data_ptr() if hasattr(self.text_planes, "data_ptr") else self.text_planes))
+
+
+def text_planes_bytes(length):
+    b = ctypes.c_uint64()
+    _check(lib().nvbio_text_planes_bytes(ctypes.c_uint32(length), ctypes.byref(b)))
+    return b.value
+
+
+def build_text_planes(text2, length, device="cuda:0", out=None):
+    """nvbio_text_planes_build: the 2-bit packed text as bit planes (include/nvbio_amd.h: the layout), a uint8 tensor of
+    text_planes_bytes(length) bytes; `out`: the caller's buffer (128-byte aligned) instead of a fresh one"""
+    torch = _torch()
+    t = _dev_tensor(text2, torch.int32, device)
+    if out is None:
+        out = torch.empty(text_planes_bytes(length), dtype=torch.uint8, device=device)
+    _check(lib().nvbio_text_planes_build(FMIndex._dev_index(device), _ptr(t), ctypes.c_uint32(length), _ptr(out), _stream_ptr(device)))
+    return out
 
 
 DEVICE_THREAD_SCHEDULER = "DeviceThreadScheduler"

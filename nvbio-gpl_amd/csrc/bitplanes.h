@@ -13,8 +13,8 @@ namespace nvbio_amd {
 constexpr uint32_t PLANE_MAX_READ = 161u;                        // 3 x 64 bits hold 161 symbols at any storage offset
 
 template <int RBITS> struct ReadWords { static constexpr int N = (161 + 15) * RBITS / 32 + 2; uint32_t w[N]; };
-struct TextWords13 { uint32_t w[13]; };
-struct TextWords14 { uint32_t w[14]; };                          // one word more: 209 window symbols at any storage offset
+// (the loaders and converters of the packed text words, 13 of them or 14 -- one word more: 209 window symbols at any storage offset --,
+// take any struct with that many words w[]: a job keeps them in the TextUnits below, which holds the text's bit planes if its batch carries them)
 
 template <int RBITS>
 __device__ __forceinline__ void load_read_words(const void* reads, const uint32_t first, const uint32_t M, ReadWords<RBITS>& out)
@@ -27,7 +27,8 @@ __device__ __forceinline__ void load_read_words(const void* reads, const uint32_
 }
 
 // T = number of window symbols that will be looked at (<= 192 + 15 - offset)
-__device__ __forceinline__ void load_text_words13(const void* text, const uint32_t tb, const uint32_t T, TextWords13& out)
+template <typename W>
+__device__ __forceinline__ void load_text_words13(const void* text, const uint32_t tb, const uint32_t T, W& out)
 {
     const uint32_t* __restrict__ twords = (const uint32_t*)text;
     const uint32_t tw0 = (tb & ~15u) >> 4, tw_last = (tb + T - 1u) >> 4;
@@ -36,7 +37,8 @@ __device__ __forceinline__ void load_text_words13(const void* text, const uint32
 }
 
 // T <= 224 - 15 window symbols
-__device__ __forceinline__ void load_text_words14(const void* text, const uint32_t tb, const uint32_t T, TextWords14& out)
+template <typename W>
+__device__ __forceinline__ void load_text_words14(const void* text, const uint32_t tb, const uint32_t T, W& out)
 {
     const uint32_t* __restrict__ twords = (const uint32_t*)text;
     const uint32_t tw0 = (tb & ~15u) >> 4, tw_last = (tb + T - 1u) >> 4;
@@ -120,7 +122,8 @@ __device__ __forceinline__ void read_planes192(const ReadWords<RBITS>& rw, const
 }
 
 // 208 plane bits (13 packed words), shifted so that bit 0 = window symbol 0; the top word holds the remainder
-__device__ __forceinline__ void text_planes208(const TextWords13& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
+template <typename W>
+__device__ __forceinline__ void text_planes208(const W& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
 {
     #pragma unroll
     for (int k = 0; k < 4; ++k) { tlo[k] = 0; thi[k] = 0; }
@@ -146,8 +149,58 @@ __device__ __forceinline__ void text_planes208(const TextWords13& tw, const uint
     }
 }
 
+// ---- the text kept as bit planes (nvbio_text_planes_build, fm_build.hip) ---------------------------------------------------------
+// A unit is 16 bytes, (lo64, hi64) of 64 consecutive text symbols: bit j of lo64 / hi64 = the low / high bit of symbol 64 u + j.  Line L
+// (128 bytes, 128-byte aligned) holds units 4 L .. 4 L + 7, i.e. symbols 256 L .. 256 L + 511: consecutive lines overlap by half, the
+// array has ((n + 255) >> 8) + 1 lines, and every bit at or beyond symbol n is zero.
+constexpr uint32_t TEXT_PLANE_LINE_BYTES = 128u;
+inline __host__ __device__ uint64_t text_plane_lines(const uint32_t n) { return (((uint64_t)n + 255u) >> 8) + 1u; }
+
+// The planes of the UNITS * 64 - 63 or more symbols from tb on, in the form text_planes208 / text_planes224 return: UNITS aligned 16-byte
+// loads from ONE line (load_text_units: issued with the read's loads), then a funnel shift by tb & 63 on 32-bit halves (text_planes_units).  Bits past the text's end are zero, bits past the window's end are
+// the text's next symbols (the caller masks them, as with the packed words).
+// Extent: the window begins in line tb >> 8 at unit u0 = (tb & 255) >> 6 <= 3 with shift s = tb & 63 <= 63, so E symbols end in unit
+// u0 + ((s + E - 1) >> 6).  A single job looks at E <= 192 symbols: s + E - 1 <= 254, 4 units, last index <= 6.  A gap-chance pair looks
+// at E <= 161 + 31 + 5 = 197: s + E - 1 <= 259, 5 units, last index <= 7 -- always inside the line's 8 units.
+// w[4 j .. 4 j + 3] = unit j as loaded: lo64's two words, hi64's two words (or, in a batch without planes, the 13 / 14 packed words)
+template <int UNITS> struct TextUnits { uint32_t w[4 * UNITS]; };
+
+// (units FROM .. TO - 1 of the window: a kernel that has no registers to spare for all of them beside the read's words in flight takes the
+// last one -- a hit in the line the others brought -- once the read's words are consumed)
+template <int UNITS, int FROM = 0, int TO = UNITS>
+__device__ __forceinline__ void load_text_units(const void* planes, const uint32_t tb, TextUnits<UNITS>& out)
+{
+    static_assert( UNITS == 4 || UNITS == 5, "4 units hold 192 symbols at any shift, 5 units hold 197" );
+    static_assert( 3 + UNITS - 1 <= 7, "the last unit of a window lies in the line its first unit lies in" );
+    typedef uint32_t unit_t __attribute__((ext_vector_type(4)));  // one global_load_dwordx4
+    const unit_t* __restrict__ p = (const unit_t*)planes + ((size_t)(tb >> 8) * 8u + ((tb & 255u) >> 6));
+    #pragma unroll
+    for (int j = FROM; j < TO; ++j) { const unit_t v = p[j]; out.w[4*j] = v.x; out.w[4*j+1] = v.y; out.w[4*j+2] = v.z; out.w[4*j+3] = v.w; }
+}
+
+template <int UNITS>
+__device__ __forceinline__ void text_planes_units(const TextUnits<UNITS>& tu, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
+{
+    const uint32_t s = tb & 63u;
+    const uint32_t up = s >= 32u ? 0xFFFFFFFFu : 0u;             // v_alignbit takes s & 31: the other 32 by choosing the words (one v_bfi
+                                                                 // each; written as a mask so that it stays a choice between registers)
+    // word i of the lo / hi plane as loaded, zeros past the last unit
+    auto lo = [&](const int i) { return i < 2 * UNITS ? tu.w[4 * (i >> 1) + (i & 1)] : 0u; };
+    auto hi = [&](const int i) { return i < 2 * UNITS ? tu.w[4 * (i >> 1) + 2 + (i & 1)] : 0u; };
+    uint32_t a[9], c[9];
+    #pragma unroll
+    for (int i = 0; i < 9; ++i) { a[i] = (lo( i + 1 ) & up) | (lo( i ) & ~up); c[i] = (hi( i + 1 ) & up) | (hi( i ) & ~up); }
+    #pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        tlo[k] = (uint64_t)__builtin_amdgcn_alignbit( a[2*k+1], a[2*k], s ) | ((uint64_t)__builtin_amdgcn_alignbit( a[2*k+2], a[2*k+1], s ) << 32);
+        thi[k] = (uint64_t)__builtin_amdgcn_alignbit( c[2*k+1], c[2*k], s ) | ((uint64_t)__builtin_amdgcn_alignbit( c[2*k+2], c[2*k+1], s ) << 32);
+    }
+}
+
 // 224 plane bits (14 packed words), shifted so that bit 0 = window symbol 0
-__device__ __forceinline__ void text_planes224(const TextWords14& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
+template <typename W>
+__device__ __forceinline__ void text_planes224(const W& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
 {
     #pragma unroll
     for (int k = 0; k < 4; ++k) { tlo[k] = 0; thi[k] = 0; }

@@ -21,6 +21,7 @@
 //      pass each over the sorted positions.
 #include "fm_device.h"
 #include "build_prims.h"
+#include "bitplanes.h"
 #include <vector>
 #include <stdlib.h>
 #include <stdio.h>
@@ -651,6 +652,53 @@ extern "C" nvbio_status nvbio_fm_index_build(const uint32_t* text2_dev, uint32_t
     NVB_REQUIRE( !options || options->bucket_symbols <= 5u, "bucket_symbols must be 0 (automatic) or 1 + a value in 0..4" );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     return build_impl( text2_dev, length, device, kmer_len, sa_int, max_lcp, verify, options ? options->table_flags : 0u, options ? options->bucket_symbols : 0u, (hipStream_t)stream, out );
+}
+
+// ---- the text as bit planes (bitplanes.h: the layout, load_text_units) ------------------------------------------------------------
+// one thread per 16-byte unit (64 symbols, 4 packed words): squeezed as text_planes208 does it per job, stored into the one or two lines
+// that hold the unit -- line u / 4 at slot u % 4, and line u / 4 - 1 at slot u % 4 + 4.  Units past the text (the last lines' padding) and
+// bits at or beyond n are zero.
+__global__ void __launch_bounds__(256)
+text_planes_kernel(const uint32_t* __restrict__ text, const uint32_t n, const uint32_t n_words, const uint64_t n_lines, uint4* __restrict__ planes)
+{
+    const uint64_t n_units = n_lines * 4u + 4u;                  // the last line's last unit is 4 (n_lines - 1) + 7
+    for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n_units; u += (uint64_t)gridDim.x * blockDim.x)
+    {
+        uint64_t lo = 0, hi = 0;
+        #pragma unroll
+        for (int j = 0; j < 4; ++j)
+        {
+            const uint64_t widx = u * 4u + (uint64_t)j;
+            const uint32_t w = __brev( widx < n_words ? text[widx] : 0u );
+            lo |= (uint64_t)squeeze2( w >> 1 ) << (16 * j);
+            hi |= (uint64_t)squeeze2( w ) << (16 * j);
+        }
+        const uint64_t sym0 = u * 64u;
+        const uint64_t keep = sym0 >= n ? 0ull : (n - sym0 >= 64u ? ~0ull : ((1ull << (n - sym0)) - 1ull));
+        lo &= keep; hi &= keep;
+        const uint4 unit = make_uint4( (uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32) );
+        const uint64_t line = u >> 2, slot = u & 3u;
+        if (line < n_lines) planes[line * 8u + slot] = unit;
+        if (line >= 1u && line - 1u < n_lines) planes[(line - 1u) * 8u + slot + 4u] = unit;
+    }
+}
+
+extern "C" nvbio_status nvbio_text_planes_bytes(uint32_t length, uint64_t* bytes)
+{
+    NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
+    *bytes = text_plane_lines( length ) * TEXT_PLANE_LINE_BYTES;
+    return NVBIO_OK;
+}
+
+extern "C" nvbio_status nvbio_text_planes_build(int device, const uint32_t* text2_dev, uint32_t length, void* planes_dev, void* stream)
+{
+    NVB_REQUIRE( text2_dev && planes_dev, "text2_dev/planes_dev is NULL" );
+    NVB_REQUIRE( length > 0, "empty text" );
+    NVB_REQUIRE( ((uintptr_t)planes_dev & (TEXT_PLANE_LINE_BYTES - 1u)) == 0, "planes_dev must be 128-byte aligned" );
+    DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    const uint64_t n_lines = text_plane_lines( length );
+    return NVB_LAUNCH( text_planes_kernel, dim3( grid_for( n_lines * 4u + 4u ) ), dim3(256), (hipStream_t)stream, text2_dev, length,
+                       (uint32_t)(((uint64_t)length + 15u) / 16u), n_lines, (uint4*)planes_dev );
 }
 
 extern "C" nvbio_status nvbio_suffix_sort(const uint32_t* text2_dev, uint32_t length, int device, uint32_t* sa_dev, void* stream)

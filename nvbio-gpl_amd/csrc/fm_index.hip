@@ -46,6 +46,7 @@ struct FMIndexImpl
     uint64_t             owned_bytes;
     uint32_t*            isa;         // owned, optional (verify mode)
     uint32_t*            text;        // owned, optional (verify mode)
+    void*                planes;      // owned, optional: the text as bit planes (nvbio_text_planes_build), for the alignment batches
 
     DevIndex dev() const
     {
@@ -1276,9 +1277,30 @@ nvbio_status fm_index_adopt(const nvbio_fm_index_view* view, int device, uint32_
     idx->isa = isa; idx->text = text;
     if (isa)  idx->owned_bytes += ((uint64_t)view->length + 1u) * 4ull;
     if (text) idx->owned_bytes += (((uint64_t)view->length + 15u) / 16u) * 4ull;
-    const nvbio_status st = build_kmer_table( idx, kmer_len, stream );
+    idx->planes = nullptr;
+    nvbio_status st = build_kmer_table( idx, kmer_len, stream );
+    const bool tables = st == NVBIO_OK;                         // (a failed table build has released its own)
+    if (st == NVBIO_OK && text && !(table_flags & NVBIO_FM_TABLE_NO_TEXT_PLANES))
+    {
+        // the text once more as bit planes: what the band-31 passes of every batch would otherwise rebuild per job
+        uint64_t bytes = 0;
+        (void)nvbio_text_planes_bytes( view->length, &bytes );
+        if (hipMalloc( &idx->planes, bytes ) != hipSuccess) { idx->planes = nullptr; set_error( "out of device memory (text planes, %llu bytes)", (unsigned long long)bytes ); st = NVBIO_ERR_NOMEM; }
+        else st = nvbio_text_planes_build( device, text, view->length, idx->planes, stream );
+        if (st == NVBIO_OK && hipStreamSynchronize( stream ) != hipSuccess) { set_error( "text planes build failed" ); st = NVBIO_ERR_HIP; }
+        if (st == NVBIO_OK) idx->owned_bytes += bytes;
+    }
     if (st != NVBIO_OK)
     {
+        if (idx->planes) (void)hipFree( idx->planes );
+        if (tables)
+        {
+            if (idx->ktab)  (void)hipFree( idx->ktab );
+            if (idx->dtab)  (void)hipFree( idx->dtab );
+            if (idx->side)  (void)hipFree( idx->side );
+            if (idx->ctab)  (void)hipFree( idx->ctab );
+            if (idx->cside) (void)hipFree( idx->cside );
+        }
         if (owns) { (void)hipFree( (void*)view->bwt_occ_dev ); (void)hipFree( (void*)view->ssa_dev ); }
         if (isa)  (void)hipFree( isa );
         if (text) (void)hipFree( text );
@@ -1332,6 +1354,7 @@ nvbio_status nvbio_fm_index_destroy(nvbio_fm_index_t index)
     if (idx->cside) (void)hipFree( idx->cside );
     if (idx->isa)  (void)hipFree( idx->isa );
     if (idx->text) (void)hipFree( idx->text );
+    if (idx->planes) (void)hipFree( idx->planes );
     if (idx->owns_arrays) { (void)hipFree( (void*)idx->view.bwt_occ_dev ); (void)hipFree( (void*)idx->view.ssa_dev ); }
     delete idx;
     return NVBIO_OK;
@@ -1360,6 +1383,15 @@ nvbio_status nvbio_fm_index_device_bytes(nvbio_fm_index_t index, uint64_t* bytes
 {
     NVB_REQUIRE( index && bytes, "index/bytes is NULL" );
     *bytes = ((FMIndexImpl*)index)->owned_bytes;
+    return NVBIO_OK;
+}
+
+nvbio_status nvbio_fm_index_text_planes(nvbio_fm_index_t index, const void** planes_dev, uint32_t* length)
+{
+    NVB_REQUIRE( index && planes_dev && length, "index/planes_dev/length is NULL" );
+    const FMIndexImpl* idx = (const FMIndexImpl*)index;
+    *planes_dev = idx->planes;
+    *length     = idx->planes ? idx->view.length : 0u;
     return NVBIO_OK;
 }
 

@@ -1021,11 +1021,19 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
     // bit planes of the read and of the window (bitplanes.h); all loads first, then the bit work
     uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
     {
-        ReadWords<RBITS> rw; TextWords13 tw;
+        // (the window's planes from the text's, where the batch carries them -- the text as the index build left it, one line per window --,
+        // else from its 13 packed words; b.text_planes is wave-uniform)
+        ReadWords<RBITS> rw; TextUnits<4> tu;
         load_read_words<RBITS>( b.reads, first, M, rw );
-        load_text_words13( b.text, tb, N < 192u ? N : 192u, tw );
+        if (b.text_planes) load_text_units<4,0,3>( b.text_planes, tb, tu );
+        else               load_text_words13( b.text, tb, N < 192u ? N : 192u, tu );
         read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
-        text_planes208( tw, tb, tlo, thi );
+        if (b.text_planes)
+        {
+            load_text_units<4,3,4>( b.text_planes, tb, tu );     // (see load_text_units: 7 waves per SIMD leave 72 registers)
+            text_planes_units<4>( tu, tb, tlo, thi );
+        }
+        else text_planes208( tu, tb, tlo, thi );
     }
     const uint32_t mb = M + 30u;
     const uint32_t m  = (mb < N ? mb : N) - (M - 1u);
@@ -1361,7 +1369,11 @@ ungapped_e2e31_job(const BatchDev& b, const int32_t P, const int32_t G, const in
 // MODE 1 / 2: the jobs of job_list; one that ends as 1 goes on out.dp.  (Launched over the whole batch's workgroups: those behind the
 //   list's end leave before they touch anything.)
 template <int RBITS, int MODE, bool QUAL = false>
-__global__ void __launch_bounds__(256)
+// (the first pass proper keeps its 7 waves per SIMD, i.e. 72 registers: left alone the allocator takes 73 on the route over the text's planes.
+// Under a forced minimum a job that outgrows the budget SPILLS instead of losing a wave, and nothing says so at build time: after any edit of
+// ungapped_e2e31_job or of what it inlines, run scripts/resource_report.py again and hold it against profiles/r12_resource_usage.txt --
+// scratch 0, spills 0 for every instantiation.  The (1) of the other instantiations asks for nothing: their figures are the parent's.)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == 0 && !QUAL) ? 7 : 1)))
 ungapped_e2e31_kernel(const BatchDev b, const int32_t P, const int32_t G, const int32_t gap_open, const int32_t gap_ext,
                       int32_t* __restrict__ scores, uint2* __restrict__ sinks, uint8_t* __restrict__ need_dp,
                       const uint32_t* __restrict__ job_list, const uint32_t* __restrict__ job_count,
@@ -1491,21 +1503,19 @@ gap_chance_e2e31_walk(const BatchDev& b, const int32_t P, const GapLadder lad, c
         uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
         ReadWords<RBITS> rw;
         load_read_words<RBITS>( b.reads, first, M, rw );
-        if constexpr (PAIR)
-        {
-            TextWords14 tw;
-            load_text_words14( b.text, tb, M + 31u + sh, tw );
-            read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
-            text_planes224( tw, tb, tlo, thi );
-        }
+        // (b.text_planes is wave-uniform; the pair's union window: 5 units, see load_text_units)
+        TextUnits<PAIR ? 5 : 4> tu;
+        if (b.text_planes) load_text_units<PAIR ? 5 : 4>( b.text_planes, tb, tu );
+        else if constexpr (PAIR) load_text_words14( b.text, tb, M + 31u + sh, tu );
         else
         {
-            TextWords13 tw;
             const uint32_t N = b.win_end[job] - tb;
-            load_text_words13( b.text, tb, N < 192u ? N : 192u, tw );
-            read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
-            text_planes208( tw, tb, tlo, thi );
+            load_text_words13( b.text, tb, N < 192u ? N : 192u, tu );
         }
+        read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
+        if (b.text_planes) text_planes_units<PAIR ? 5 : 4>( tu, tb, tlo, thi );
+        else if constexpr (PAIR) text_planes224( tu, tb, tlo, thi );
+        else text_planes208( tu, tb, tlo, thi );
         pw.set( rlo, rhi, rn, tlo, thi, M );
     }
 
@@ -2218,6 +2228,10 @@ nvbio_status make_batch(const nvbio_alignment_batch* in, BatchDev* b)
     b->reads = in->reads_dev; b->read_offsets = in->read_offsets_dev; b->quals = in->quals_dev;
     b->read_id = in->read_id_dev; b->flags = in->flags_dev; b->text = in->text_dev;
     b->win_begin = in->win_begin_dev; b->win_end = in->win_end_dev; b->n = in->n; b->max_read_len = in->max_read_len; b->algo = in->algo_flags;
+    // the text's bit planes (nvbio_text_planes_build): only with the packed 2-bit text they were built from, and not under the A/B flag
+    const bool planes = in->text_planes_dev && in->text_bits == 2 && !(in->algo_flags & NVBIO_ALN_NO_TEXT_PLANES);
+    NVB_REQUIRE( !planes || ((uintptr_t)in->text_planes_dev & 127u) == 0, "text_planes_dev must be 128-byte aligned" );
+    b->text_planes = planes ? in->text_planes_dev : nullptr;
     return NVBIO_OK;
 }
 

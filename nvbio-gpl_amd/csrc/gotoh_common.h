@@ -18,6 +18,7 @@ struct BatchDev
     uint32_t        n;
     uint32_t        max_read_len;
     uint32_t        algo;              // NVBIO_ALN_* (host-side kernel selection only)
+    const void*     text_planes;       // the text as bit planes (bitplanes.h: load_text_units), or NULL: the packed words are converted per job
 };
 
 // Scoring scheme as the kernels see it.  The reference's Gotoh kernels take BOTH gap recurrences from the pattern-gap terms and

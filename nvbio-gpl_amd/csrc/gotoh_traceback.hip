@@ -267,7 +267,9 @@ banded_gotoh_traceback_kernel(const BatchDev b, const SchemeDev sc, const uint32
 // (2-bit cached) column < 30 sees as 3 (alignment_base_inl.h:66-90).
 // ---------------------------------------------------------------------------------------------
 template <int BAND, int TYPE, int RBITS, int TBITS>
-__global__ void __launch_bounds__(256)
+// (the plane route of 4-bit reads keeps its 7 waves per SIMD, as the first scoring pass does: see ungapped_e2e31_kernel, also for the check
+// to repeat after any edit -- scripts/resource_report.py against profiles/r12_resource_usage.txt, scratch 0 and spills 0)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BAND == 31 && TYPE != NVBIO_LOCAL && TBITS == 2 && RBITS == 4) ? 7 : 1)))
 ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* __restrict__ scores, const uint2* __restrict__ sinks,
                           uint2* __restrict__ sources, uint16_t* __restrict__ cigars, const uint32_t cigar_stride,
                           uint32_t* __restrict__ cigar_lens, uint8_t* __restrict__ need_dp,
@@ -308,11 +310,17 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
         {
             constexpr int RB = (RBITS == 2 || RBITS == 4) ? RBITS : 4;
             uint64_t rlo[3], rhi[3], rn[3], tlo[4], thi[4];
-            ReadWords<RB> rw; TextWords13 tw;
+            ReadWords<RB> rw; TextUnits<4> tu;
             load_read_words<RB>( b.reads, first, M, rw );
-            load_text_words13( b.text, tb, N < 192u ? N : 192u, tw );
+            if (b.text_planes) load_text_units<4,0,3>( b.text_planes, tb, tu );              // (wave-uniform)
+            else               load_text_words13( b.text, tb, N < 192u ? N : 192u, tu );
             read_planes192<RB>( rw, first, M, J.rev, J.comp, rlo, rhi, rn );
-            text_planes208( tw, tb, tlo, thi );
+            if (b.text_planes)
+            {
+                load_text_units<4,3,4>( b.text_planes, tb, tu );                             // (as the first scoring pass: 7 waves per SIMD)
+                text_planes_units<4>( tu, tb, tlo, thi );
+            }
+            else text_planes208( tu, tb, tlo, thi );
             uint32_t cnt = 0;
             #pragma unroll
             for (int w = 0; w < 3; ++w)

@@ -95,6 +95,10 @@ int main(int argc, char** argv)
         check_hip( hipDeviceSynchronize(), "sync" );
         const double build_s = std::chrono::duration<double>( std::chrono::steady_clock::now() - tb0 ).count();
 
+        // the text as bit planes, kept by the handle (built from this very d_genome): the alignment batches below carry them
+        const void* text_planes = nullptr; uint32_t planes_len = 0;
+        check( nvbio_fm_index_text_planes( fmi.handle(), &text_planes, &planes_len ) );
+
         // ---- the step ----
         const uint32_t L = 22, S = (uint32_t)(1.0 + 1.15 * std::sqrt( (double)M )), BAND = 31;
         const string_set seeds = string_set::seeds( d_reads.data(), 4, M, R, L, S );
@@ -178,6 +182,7 @@ int main(int argc, char** argv)
                 nvbio_alignment_batch b; memset( &b, 0, sizeof(b) );
                 b.reads_dev = d_reads.data(); b.read_bits = 4; b.read_offsets_dev = offs.data(); b.read_id_dev = rid.data(); b.flags_dev = flags.data();
                 b.text_dev = d_genome.data(); b.text_bits = 2; b.win_begin_dev = wb.data(); b.win_end_dev = we.data(); b.n = (uint32_t)n; b.max_read_len = M; b.algo_flags = algo_flags;
+                b.text_planes_dev = planes_len == N ? text_planes : nullptr;
                 if (poison)
                 {
                     check_hip( hipMemsetAsync( scores.data(), 0x5A, (size_t)n * sizeof(int32_t), 0 ), "hipMemsetAsync" );

@@ -206,6 +206,9 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
             b.record()
 
     ext_flags = (params.algo_flags or 0) | (ALN_RAGGED_READS if ragged else 0)
+    # the handle's bit planes of the text, if it was built from this very genome2 (same address and length): the planes describe the
+    # text as it was then, so any other tensor -- a clone included -- goes without
+    text_planes = fmi.text_planes_of(genome2, genome_len)
     aligner = GotohAligner(params.aln_type, params.scheme)
     top = None                                                  # best selection key per read (0: no candidate): zero-filled where it is reduced into
     finish = None                                               # the tile spans of the candidates, where finish_reads can take the whole tail of the step
@@ -221,7 +224,7 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
         tock(e)
         e = tick("extend" + tag)
         batch = AlignmentBatch(reads.reads4, 4, read_off, genome2, 2, wb, we, quals=reads.quals, read_id=rid,
-                               flags=flags, device=dev, max_read_len=M, algo_flags=ext_flags or None)
+                               flags=flags, device=dev, max_read_len=M, algo_flags=ext_flags or None, text_planes=text_planes)
         scores, sinks = BatchedBandedAlignmentScore(params.band, aligner).enact(batch)
         tock(e)
         if finish is not None:
@@ -431,12 +434,13 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
     return best_score, best_pos, best_rc, int(n_cand)
 
 
-def traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, cigar_stride=32, timers=None):
+def traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, cigar_stride=32, timers=None, text_planes=None):
     """nvBowtie's banded_traceback_best (traceback_inl.h:191-247) over ALL reads of the batch, job r = read r, the batch built on the
     device from the per-read best keys (extras["best_keys"] of seed_and_extend) and best_wb: no compaction, no host round trip.
     The scoring pass's score and sink are handed over (end-to-end; a LOCAL alignment is re-scored by the traceback).  Returns
     (scores [R], align_pos [R] int64 = text position where the alignment starts, sources, sinks, cigars [R, cigar_stride], cigar_lens
-    [R]); a read that did not align has cigar_len 0 and sink (-1, -1)."""
+    [R]); a read that did not align has cigar_len 0 and sink (-1, -1).  text_planes: genome2's bit planes (AlignmentBatch; what
+    fmi.text_planes_of(genome2, genome_len) gives, as seed_and_extend takes them), or None."""
     import torch
     from . import BatchedBandedAlignmentTraceback, traceback_best_batch
     dev = best_keys.device
@@ -455,7 +459,8 @@ def traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, c
         read_off = getattr(reads, "_read_off", None)
         if read_off is None:
             read_off = reads._read_off = torch.arange(R + 1, device=dev, dtype=torch.int32) * M
-    batch = AlignmentBatch(reads.reads4, 4, read_off, genome2, 2, wb, we, quals=reads.quals, flags=flags, device=dev, max_read_len=M)
+    batch = AlignmentBatch(reads.reads4, 4, read_off, genome2, 2, wb, we, quals=reads.quals, flags=flags, device=dev, max_read_len=M,
+                           text_planes=text_planes)
     known = dict(scores=scores, sinks=sinks) if params.aln_type != LOCAL else {}
     op = BatchedBandedAlignmentTraceback(params.band, GotohAligner(params.aln_type, params.scheme))
     # the direction vectors of the gapped alignments (a minority) go to the persistent scratch: a multi-GiB allocation
