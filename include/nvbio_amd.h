@@ -1347,6 +1347,19 @@ nvbio_status nvbio_banded_gotoh_traceback(int device, uint32_t band, nvbio_align
                                           uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
                                           uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream);
 
+/* nvbio_banded_gotoh_traceback plus a report of the route each job took, in the manner of nvbio_banded_gotoh_score_routes.  routes_dev, one
+ * byte per job: 0 = the ungapped shortcut settled the job, or nothing was traced; 1 = the DP over the full band; 2 = the DP over 15 columns;
+ * 3 = the DP over 7 columns (the narrow routes: band 31, SEMI_GLOBAL, match bonus 0, a window of pattern_len + 30 symbols or more, the gap
+ * bound drawn from the score at most 7 / 3).  With NVBIO_ALN_NO_UNGAPPED_TRACEBACK every job reaches the DP and reports 1.  band_off_dev,
+ * one byte per job: the first column of the job's narrow band for routes 2 and 3, 0 otherwise.  Either pointer may be NULL.  The other
+ * outputs never depend on the report; it exists so that a test can tell which kernel body produced a CIGAR. */
+nvbio_status nvbio_banded_gotoh_traceback_routes(int device, uint32_t band, nvbio_alignment_type type,
+                                                 const nvbio_gotoh_scheme* scheme, const nvbio_alignment_batch* batch,
+                                                 int32_t* scores_dev, nvbio_uint2* sources_dev, nvbio_uint2* sinks_dev,
+                                                 uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
+                                                 uint32_t flags, void* temp_dev, uint64_t temp_bytes,
+                                                 uint8_t* routes_dev, uint8_t* band_off_dev, void* stream);
+
 /* The same for the linear-gap SmithWatermanAligner (and so for the EditDistanceAligner's scheme (0, -1, -1, -1)):
  * aln::banded_alignment_traceback<band, MAX_PATTERN_LEN, CHECKPOINTS>( SmithWatermanAligner<type>, ... ) (nvbio/alignment/banded_inl.h:354-417
  * over sw/sw_banded_inl.h:281-520 and its walk, :741-797), deletion and insertion costs unequal or not.  As the reference's code behaves,

@@ -1283,6 +1283,33 @@ def banded_gotoh_score_routes(band_len, aligner, batch):
     return scores, sinks, routes
 
 
+TB_ROUTE_SETTLED, TB_ROUTE_FULL_BAND, TB_ROUTE_BAND15, TB_ROUTE_BAND7 = 0, 1, 2, 3
+
+
+def banded_gotoh_traceback_routes(band_len, aligner, batch, cigar_stride=64, temp=None, scores=None, sinks=None):
+    """nvbio_banded_gotoh_traceback_routes: (scores, sources, sinks, cigars, lens) as BatchedBandedAlignmentTraceback.enact plus two
+    uint8 per job: the route it took (TB_ROUTE_SETTLED -- the ungapped shortcut, or nothing traced --, TB_ROUTE_FULL_BAND,
+    TB_ROUTE_BAND15 or TB_ROUTE_BAND7) and, for the two narrow routes, the first column of its band (0 otherwise)"""
+    torch = _torch()
+    n, dev = batch.n, batch.device
+    given = scores is not None and sinks is not None
+    if not given:
+        scores = torch.empty(n, dtype=torch.int32, device=dev)
+        sinks = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    sources = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    cigars = torch.zeros((n, cigar_stride), dtype=torch.int16, device=dev)
+    lens = torch.empty(n, dtype=torch.int32, device=dev)
+    routes = torch.empty(n, dtype=torch.uint8, device=dev)
+    band_off = torch.empty(n, dtype=torch.uint8, device=dev)
+    bs = batch.c_struct()
+    _check(lib().nvbio_banded_gotoh_traceback_routes(
+        FMIndex._dev_index(dev), ctypes.c_uint32(int(band_len)), ctypes.c_int(aligner.type), ctypes.byref(aligner.scheme.c), ctypes.byref(bs),
+        _ptr(scores), _ptr(sources), _ptr(sinks), _ptr(cigars), ctypes.c_uint32(cigar_stride), _ptr(lens),
+        ctypes.c_uint32(TRACEBACK_SINKS_GIVEN if given else 0), _ptr(temp),
+        ctypes.c_uint64(0 if temp is None else temp.numel() * temp.element_size()), _ptr(routes), _ptr(band_off), _stream_ptr(dev)))
+    return scores, sources, sinks, cigars, lens, routes, band_off
+
+
 GAP_PAIR_MAX_SHIFT = 5
 NO_PARTNER = 0xFFFFFFFF
 

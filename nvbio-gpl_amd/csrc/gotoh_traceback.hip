@@ -449,7 +449,8 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
                                           const nvbio_gotoh_scheme* gotoh, const nvbio_sw_scheme* sw, const nvbio_alignment_batch* batch,
                                           int32_t* scores_dev, nvbio_uint2* sources_dev, nvbio_uint2* sinks_dev,
                                           uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
-                                          uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream)
+                                          uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream,
+                                          uint8_t* routes_dev = nullptr, uint8_t* band_off_dev = nullptr)
 {
     NVB_REQUIRE( gotoh != nullptr || sw != nullptr, "scheme is NULL" );
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
@@ -499,6 +500,8 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
             for (int r = 1; r < 3; ++r) { routes[r].list = c.take<uint32_t>( b.n ); routes[r].count = c.take<uint32_t>( 1 ); }
             sel_temp = c.take<uint8_t>( sel_bytes );
         } ) );
+        // (the kernel writes band_off for the jobs of the narrow routes alone: a report reads 0 for the others)
+        if (band_off_dev && narrow) NVB_HIP( hipMemsetAsync( band_off, 0, b.n, s ) );
         const nvbio_status st1 = with_value( Bands(), band, [&](auto BAND)
         {
             return launch_ungapped<BAND>( type, b, sc, batch->read_bits, batch->text_bits, scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev,
@@ -552,6 +555,17 @@ static nvbio_status banded_traceback_impl(int device, uint32_t band, nvbio_align
             }, [] { return NVBIO_ERR_INVALID; } );                            // (the band was checked)
         } );
     }
+    // ---- 5. the route report (nvbio_banded_gotoh_traceback_routes): the need_dp codes and the narrow routes' band_off, copied out ----
+    if (st == NVBIO_OK && routes_dev)
+    {
+        if (shortcut) NVB_HIP( hipMemcpyAsync( routes_dev, need_dp, b.n, hipMemcpyDeviceToDevice, s ) );
+        else          NVB_HIP( hipMemsetAsync( routes_dev, 1, b.n, s ) );
+    }
+    if (st == NVBIO_OK && band_off_dev)
+    {
+        if (shortcut && narrow) NVB_HIP( hipMemcpyAsync( band_off_dev, band_off, b.n, hipMemcpyDeviceToDevice, s ) );
+        else                    NVB_HIP( hipMemsetAsync( band_off_dev, 0, b.n, s ) );
+    }
     return st;
 }
 
@@ -564,6 +578,18 @@ extern "C" nvbio_status nvbio_banded_gotoh_traceback(int device, uint32_t band, 
     NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
     return banded_traceback_impl( device, band, type, scheme, nullptr, batch, scores_dev, sources_dev, sinks_dev, cigars_dev, cigar_stride,
                                   cigar_lens_dev, flags, temp_dev, temp_bytes, stream );
+}
+
+extern "C" nvbio_status nvbio_banded_gotoh_traceback_routes(int device, uint32_t band, nvbio_alignment_type type,
+                                                            const nvbio_gotoh_scheme* scheme, const nvbio_alignment_batch* batch,
+                                                            int32_t* scores_dev, nvbio_uint2* sources_dev, nvbio_uint2* sinks_dev,
+                                                            uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
+                                                            uint32_t flags, void* temp_dev, uint64_t temp_bytes,
+                                                            uint8_t* routes_dev, uint8_t* band_off_dev, void* stream)
+{
+    NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
+    return banded_traceback_impl( device, band, type, scheme, nullptr, batch, scores_dev, sources_dev, sinks_dev, cigars_dev, cigar_stride,
+                                  cigar_lens_dev, flags, temp_dev, temp_bytes, stream, routes_dev, band_off_dev );
 }
 
 extern "C" nvbio_status nvbio_banded_sw_traceback(int device, uint32_t band, nvbio_alignment_type type,

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import oracle
-from util import FULL_KINDS, RANGE_KINDS, flat_scheme, full_jobs, full_shapes, range_jobs
+from util import FULL_KINDS, LIMIT_SCHEMES, RANGE_KINDS, flat_scheme, full_jobs, full_shapes, limit_jobs, limit_thin, range_jobs
 
 SCHEMES = [oracle.Scheme.simple(2, -1, -1, -1), oracle.Scheme.simple(0, -5, -8, -3),
            oracle.Scheme.simple(2, -1, -2, -1), oracle.Scheme(2, 2, 6, -8, -3, -8, -3),
@@ -98,6 +98,30 @@ def test_gotoh_long_fuzz(orc, ref):
             sc = schemes[(li + j) % len(schemes)]
             for typ in range(3):
                 assert ref.banded_gotoh(31, typ, sc, pats[j], txts[j], quals) == orc.banded_gotoh(31, typ, sc, pats[j], txts[j], quals), (M, kinds[j], typ)
+
+
+def test_traceback_limit_fuzz(orc, ref):
+    """the banded traceback on a thinned round of the generator of tests/test_gpu_traceback_routes.py: one job of every kind, read length,
+    window length and overhang (fill and diagonal) under every scheme of util.LIMIT_SCHEMES, end to end; the overhang jobs, where the
+    reference reads the sentinel past a clipped window's end, under LOCAL and GLOBAL as well"""
+    J = limit_jobs(20261)
+    idx = limit_thin(J)
+    kinds = set(J["kind"][idx])
+    assert kinds == set(J["kind"]) and len(idx) >= 60 and {(int(m), int(w)) for m, w in zip(J["M"][idx], J["win"][idx])} >= {
+        (33, 31), (64, 31), (64, 30), (64, 29), (160, 31), (161, 31), (162, 31)}
+    traced_past_end = 0
+    for name, sv, with_q in LIMIT_SCHEMES:
+        sc = oracle.Scheme(*sv)
+        for j in idx:
+            pat, txt, quals = J["pats"][j], J["txts"][j], J["quals"][j] if with_q else None
+            for typ in ((oracle.SEMI_GLOBAL, oracle.LOCAL, oracle.GLOBAL) if J["kind"][j] == "overhang" else (oracle.SEMI_GLOBAL,)):
+                r, rs, rsrc, rsnk, rops, rclips = ref.banded_gotoh_traceback(31, typ, sc, pat, txt, quals)
+                ok, s, src, snk, cig, ops = orc.banded_gotoh_traceback(31, typ, sc, pat, txt, quals)
+                assert (ok, s, src, snk) == (1 if r == 2 else 0, rs, rsrc, rsnk), (name, j, typ)
+                assert np.array_equal(ops, rops), (name, j, typ)
+                assert np.array_equal(cig, oracle.cigar_from_ops(rops, *rclips) if r == 2 else np.zeros(0, dtype=np.uint16)), (name, j, typ)
+                traced_past_end += int(ok and snk[0] > len(txt))
+    assert traced_past_end >= 5                                                 # LOCAL sinks on the sentinel, read as 3
 
 
 def test_full_gotoh_range_fuzz(orc, _live_ref):

@@ -592,3 +592,142 @@ def full_pk_edge_sides(edge):
     if "penalty" in name:
         return ((sv, M, N), (tuple(v + (1 if v > 0 else -1) if abs(v) == 4096 else v for v in sv), M, N))
     return ((sv, M, N), (sv, M, N + 1))
+
+
+# ---------------------------------------------------------------------------------------------
+# inputs for the banded traceback at the limits of its routes (tests/test_gpu_traceback_routes.py,
+# tests/test_oracle_vs_reference.py::test_traceback_limit_fuzz)
+# ---------------------------------------------------------------------------------------------
+# (name, scheme, base qualities?): equal gap kinds; the text gap cheaper and its mirror (go_min / ge_min come from the cheaper kind); a
+# quality ramp (a mismatch costs 2 to 6: the plane count stands aside); one the narrow route must refuse (match bonus 1)
+LIMIT_SCHEMES = (
+    ("equal", (0, 6, 6, -8, -3, -8, -3), False),
+    ("cheap_txt", (0, 6, 6, -11, -4, -6, -2), False),
+    ("cheap_pat", (0, 6, 6, -6, -2, -11, -4), False),
+    ("ramp", (0, 2, 6, -8, -3, -8, -3), True),
+    ("refused", (1, 3, 3, -8, -3, -8, -3), False),
+)
+LIMIT_M = 64                                                         # the read length of the bulk of the jobs
+LIMIT_READ_LENS = (33, 64, 160, 161, 162)                            # 161 | 162: the plane count's limit; 33: an 8-symbol gap with clean flanks
+LIMIT_WINDOWS = (31, 30, 29)                                         # window = M + this: M + 29 is the first the narrow routes refuse
+LIMIT_GAP_KINDS = ("del", "ins", "del+sub", "ins+sub", "split")
+LIMIT_FILLS = (3, 0, 4)                                              # what an overhang holds: the sentinel's low bits, another letter, N
+LIMIT_SUB_QUALS = (0, 63, 10)                                        # the substituted symbol's quality: a ramp (2..6) charges 2, 6, 3
+
+
+def _limit_path(rng, txt, M, d0, steps):
+    """the read that follows `txt` from diagonal d0 on through `steps` = [("D", a) | ("I", b), ...] (D: the read lacks a text symbols, the
+    diagonal moves up; I: b symbols more in the read, it moves down), 6 to 8 clean symbols in front of each and 7 or more behind the last
+    -> (read, last diagonal, read positions free for a substitution)"""
+    read, t, free = [], d0, []
+    room = M - sum(n for k, n in steps if k == "I")
+    flank = max(6, min(8, (room - 7) // len(steps))) if steps else 0
+    for k, n in steps:
+        f = int(rng.integers(6, flank + 1)) if flank > 6 else 6
+        free += list(range(len(read) + 2, len(read) + f - 2))
+        read += list(txt[t:t + f]); t += f
+        if k == "D":
+            t += n
+        else:                                                        # inserted symbols differ from the text symbol the first would meet
+            ins = rng.integers(0, 4, n)
+            ins[0] = (int(txt[t]) + 1 + int(rng.integers(0, 3))) % 4
+            read += list(ins)
+    rest = M - len(read)
+    assert rest >= 7 or not steps, (M, steps)
+    free += list(range(len(read) + 2, M - 2))
+    read += list(txt[t:t + rest]); t += rest
+    assert len(read) == M and t <= len(txt)
+    return np.array(read, dtype=np.uint8), t - M, free
+
+
+def limit_jobs(seed):
+    """jobs built so that the intended alignment of each ends on a chosen diagonal e of band 31, deterministic from the seed -> dict of
+    per-job lists / arrays: pats (as aligned), txts (the window), quals, kind, e, L (gap symbols; substitutions of an ungapped job; overhang
+    symbols), M, win (window length - M), fill (overhang jobs, else -1).
+
+      del, ins            one gap of L = 1..8 symbols ending on e = 0..30, wherever the path stays inside columns 0..30
+      del+sub, ins+sub    the same with one substitution (its quality cycles through LIMIT_SUB_QUALS)
+      split               the gap as two of opposite kind, L = a + b, in both orders
+      ungapped            0..3 substitutions on every e
+      overhang            a read that matches the last M - L symbols of a window clipped by the text's end on diagonal e (window = e + M - L
+                          symbols) and then holds L = 1..5 more: all 3, all 0 or all N.  e in {0, 15, 29, 30} and e = L, the lowest diagonal
+                          whose window still holds the read (at e = 0 it does not: nothing is reported)
+    The bulk has M = LIMIT_M in windows of M + 31; every third gap job comes again in windows of M + 30 and M + 29, every fourth at each other
+    read length of LIMIT_READ_LENS."""
+    rng = np.random.default_rng(seed)
+    J = dict(pats=[], txts=[], quals=[], kind=[], e=[], L=[], M=[], win=[], fill=[])
+    nsub = [0]
+
+    def add(kind, pat, txt, e, L, M, win, fill=-1, subs=()):
+        q = rng.integers(0, 64, M, dtype=np.uint8)
+        for p in subs:
+            q[p] = LIMIT_SUB_QUALS[nsub[0] % 3]; nsub[0] += 1
+        for key, v in zip(("pats", "txts", "quals", "kind", "e", "L", "M", "win", "fill"), (pat, txt, q, kind, e, L, M, win, fill)):
+            J[key].append(v)
+
+    def gap_jobs(M, win, pick):
+        for e in range(31):
+            for L in range(1, 9):
+                if not pick(e, L):
+                    continue
+                plans = [("del", [("D", L)], e - L), ("ins", [("I", L)], e + L)]
+                if L > 1:
+                    a = e % (L - 1) + 1; b = L - a
+                    plans += [("split", [("D", a), ("I", b)], e + b - a), ("split", [("I", a), ("D", b)], e - b + a)]
+                for kind, steps, d0 in plans:
+                    d, inside = d0, 0 <= d0 <= 30
+                    for k, n in steps:
+                        d += n if k == "D" else -n
+                        inside = inside and 0 <= d <= 30
+                    if not inside or e + M > M + win:                # (the path leaves the band, or the window)
+                        continue
+                    for sub in ((0, 1) if kind != "split" else (0,)):
+                        txt = rng.integers(0, 4, M + win, dtype=np.uint8)
+                        pat, end, free = _limit_path(rng, txt, M, d0, steps)
+                        assert end == e
+                        subs = ()
+                        if sub:
+                            p = int(free[int(rng.integers(0, len(free)))])
+                            pat[p] = (pat[p] + 1 + rng.integers(0, 3)) % 4; subs = (p,)
+                        add(kind + ("+sub" if sub else ""), pat, txt, e, L, M, win, subs=subs)
+
+    gap_jobs(LIMIT_M, 31, lambda e, L: True)
+    for win in LIMIT_WINDOWS[1:]:
+        gap_jobs(LIMIT_M, win, lambda e, L: (e + L) % 3 == 0 or e >= 29)
+    for i, M in enumerate(m for m in LIMIT_READ_LENS if m != LIMIT_M):
+        gap_jobs(M, 31, lambda e, L: (e * 8 + L) % 4 == i)
+    for M in (LIMIT_M, 161, 162):
+        for e in range(31):
+            for s in range(4):
+                txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                pat = txt[e:e + M].copy()
+                subs = tuple(int(p) for p in rng.choice(M, s, replace=False))
+                for p in subs:
+                    pat[p] = (pat[p] + 1 + rng.integers(0, 3)) % 4
+                add("ungapped", pat, txt, e, s, M, 31, subs=subs)
+    M = LIMIT_M
+    for k in range(1, 6):
+        for e in (0, k, 15, 29, 30):
+            for fill in LIMIT_FILLS:
+                txt = rng.integers(0, 4, e + M - k, dtype=np.uint8)
+                txt[-1] = (fill + 1) % 4 if fill < 4 else txt[-1]     # (the text's last symbol is not the overhang's: the diagonal's matches end there)
+                pat = np.concatenate([txt[e:], np.full(k, fill, dtype=np.uint8)])
+                add("overhang", pat, txt, e, k, M, e - k, fill=fill)
+    for key in ("kind", "e", "L", "M", "win", "fill"):
+        J[key] = np.array(J[key])
+    return J
+
+
+def limit_select(J, idx):
+    """the jobs `idx` of limit_jobs()' result"""
+    idx = np.asarray(idx)
+    return {k: ([v[i] for i in idx] if isinstance(v, list) else v[idx]) for k, v in J.items()}
+
+
+def limit_thin(J):
+    """one job of every (kind, read length, window length, overhang fill and diagonal) of limit_jobs()' result, from the middle of each group"""
+    groups = {}
+    for j in range(len(J["kind"])):
+        over = J["kind"][j] == "overhang"
+        groups.setdefault((J["kind"][j], int(J["M"][j]), int(J["win"][j]) if not over else int(J["e"][j]), int(J["fill"][j])), []).append(j)
+    return np.array(sorted(g[len(g) // 2] for g in groups.values()))
