@@ -1047,6 +1047,47 @@ nvbio_status nvbio_pe_score_reduce(int device, const nvbio_pe_params* params, co
                                    const uint32_t* hits_count_dev, const nvbio_hit_queues* hits, const int32_t* hit_opposite_score_dev,
                                    const uint32_t* hit_opposite_loc_dev, const uint32_t* hit_opposite_sink_dev, uint32_t n_ext, int32_t* best_a_dev,
                                    int32_t* best_o_dev, uint32_t* trys_dev, uint32_t* sizes_dev, void* stream);
+
+/* -------------------------------------------------------------------------------------------
+ * The same paired loop over mates of DIFFERENT lengths (two ragged batches: mate m of pair r = symbols [offsets_m[r], offsets_m[r+1]) of its
+ * stored stream).  The reference's streams are per read throughout: BestAnchorScoreStream and BestOppositeScoreStream take both mates' lengths
+ * from each read's own range and evaluate perfect_score( len ) and min_score( len ) per read (score_inl.h:206-213, :341-347), the opposite
+ * mate's gap allowance is max_text_gaps( aligner, min_score, o_len ) (:398-399), and score_reduce_paired_kernel's `distinct` distance is
+ * read_len / 2 of the ANCHOR read (reduce_inl.h:184-185,240,271); the seeds come from map_kernel, per lane (mapping_inl.h:504-529).  So nothing
+ * is approximated: with A_r / O_r the lengths of pair r's anchor / opposite mate,
+ *   init              best_a[r] / best_o[r] start from min_scores_mate1_dev[r] / min_scores_mate2_dev[r] (`mate` in the rc slot, as nvbio_pe_init)
+ *   anchor flatten    window end begin + band + A_r (clamped); target_pair from a_worst[r] + o_worst[r] while no second pair exists;
+ *                     target_mate = max( target_pair - match * O_r, a_worst[r] )
+ *   opposite flatten  threshold from o_worst[r]; run = !(min_score > match * O_r); max_text_gaps' loop bounded by O_r; the fragment window from
+ *                     A_r and O_r + gaps; policy, min / max fragment, overlap, clamping and the `visited` tests as in the uniform call
+ *   reduce            distinct distance A_r / 2 in the paired branch and in the unpaired fallback; everything else as nvbio_pe_score_reduce
+ * The ragged calls take nvbio_pe_params -- whose anchor_len, opposite_len and the four perfect / min scores they IGNORE -- and the tables below.
+ * min_scores_mate{1,2}_dev[r] = scheme.min_score( length of that mate of pair r ), evaluated by the caller as for nvbio_best_approx_init_ragged;
+ * they are given by MATE, the offsets by ROLE: the caller swaps the offsets when the anchor changes, not the min scores.
+ * nvbio_pe_anchor_output and nvbio_pe_opposite_output read no length and serve both forms.  The anchor's seeds are those of the single-end
+ * ragged loop over the anchor mate's offsets (nvbio_read_queue_begin_ragged, nvbio_seed_hits_map_ragged, with their filter: a mate shorter
+ * than max( min_read_len, seed_len ) contributes no seeds while it is the anchor, and is still aligned as the opposite mate of its partner's
+ * hits).  Every mate is shorter than 1024 symbols (seed_hit.h:217): the caller checks that, these calls see the lengths on the device only.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct
+{
+    const uint32_t* anchor_offsets_dev;      /* n_reads + 1 symbol offsets of the mate that is the anchor (params->anchor)      */
+    const uint32_t* opposite_offsets_dev;    /* n_reads + 1 symbol offsets of the other mate                                    */
+    const int32_t*  min_scores_mate1_dev;    /* n_reads: scheme.min_score( len ) of mate 1 of every pair                        */
+    const int32_t*  min_scores_mate2_dev;    /* n_reads: the same for mate 2                                                    */
+} nvbio_pe_ragged;
+/* of `ragged` only the two min-score arrays are read */
+nvbio_status nvbio_pe_init_ragged(int device, uint32_t n_reads, const nvbio_pe_ragged* ragged, int32_t* best_a_dev, int32_t* best_o_dev, void* stream);
+nvbio_status nvbio_pe_anchor_flatten_ragged(int device, const nvbio_pe_params* params, const nvbio_pe_ragged* ragged, const nvbio_hit_queues* hits,
+                                            const int32_t* best_a_dev, const int32_t* best_o_dev, uint32_t* read_id_dev, uint8_t* flags_dev,
+                                            uint32_t* win_begin_dev, uint32_t* win_end_dev, int32_t* min_scores_dev, void* stream);
+nvbio_status nvbio_pe_opposite_flatten_ragged(int device, const nvbio_pe_params* params, const nvbio_pe_ragged* ragged, const uint32_t* queue_dev, uint32_t n,
+                                              const nvbio_hit_queues* hits, const int32_t* best_a_dev, const int32_t* best_o_dev, uint32_t* read_id_dev,
+                                              uint8_t* flags_dev, uint32_t* win_begin_dev, uint32_t* win_end_dev, int32_t* min_scores_dev, void* stream);
+nvbio_status nvbio_pe_score_reduce_ragged(int device, const nvbio_pe_params* params, const nvbio_pe_ragged* ragged, const uint32_t* active_dev, uint32_t n_active,
+                                          const uint32_t* hits_first_dev, const uint32_t* hits_count_dev, const nvbio_hit_queues* hits,
+                                          const int32_t* hit_opposite_score_dev, const uint32_t* hit_opposite_loc_dev, const uint32_t* hit_opposite_sink_dev,
+                                          uint32_t n_ext, int32_t* best_a_dev, int32_t* best_o_dev, uint32_t* trys_dev, uint32_t* sizes_dev, void* stream);
 /* queue_out_dev = the indices i in [0, n) with flags_dev[i] != 0, in order; *count_dev (device) = how many */
 nvbio_status nvbio_select_flagged_indices(int device, const uint8_t* flags_dev, uint32_t n, uint32_t* queue_out_dev, uint32_t* count_dev, void* stream);
 

@@ -1854,6 +1854,67 @@ def score_reduce_effort_multi_ragged(active, n_active, hits_first, hits_count, h
                                                         _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
 
 
+# ---- the paired loop's steps over mates of different lengths (include/nvbio_amd.h: nvbio_pe_ragged and the nvbio_pe_*_ragged calls) ----
+class _PeParams(ctypes.Structure):
+    _fields_ = [("anchor", ctypes.c_uint32), ("anchor_len", ctypes.c_uint32), ("opposite_len", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("anchor_perfect_score", "opposite_perfect_score", "anchor_min_score", "opposite_min_score", "score_limit",
+                                              "worst_score", "match", "txt_gap_open", "txt_gap_ext")] + \
+               [(n, ctypes.c_uint32) for n in ("band", "genome_len", "policy", "min_frag_len", "max_frag_len", "overlap", "unpaired", "max_effort", "min_ext",
+                                               "max_ext")]
+
+
+class _PeRagged(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("anchor_offsets_dev", "opposite_offsets_dev", "min_scores_mate1_dev", "min_scores_mate2_dev")]
+
+
+class PeRaggedParams:
+    """nvbio_pe_params as the ragged calls read it (the uniform lengths and scores stay 0: they are ignored) with nvBowtie's defaults"""
+
+    def __init__(self, anchor, scheme, genome_len, band=31, policy=1, min_frag_len=0, max_frag_len=500, overlap=True, unpaired=True, max_effort=15,
+                 min_ext=30, max_ext=400):
+        self.c = _PeParams(anchor, 0, 0, 0, 0, 0, 0, -(1 << 30), -65536, scheme.c.match, scheme.c.txt_gap_open, scheme.c.txt_gap_ext, band, genome_len, policy,
+                           min_frag_len, max_frag_len, 1 if overlap else 0, 1 if unpaired else 0, max_effort, min_ext, max_ext)
+
+
+class PeRagged:
+    """nvbio_pe_ragged: the anchor / opposite mate's offsets int32 [R + 1] (by ROLE) and min_score( len ) of every mate 1 / mate 2 int32 [R] (by MATE)"""
+
+    def __init__(self, anchor_offsets, opposite_offsets, min_scores_mate1, min_scores_mate2):
+        self.tensors = (anchor_offsets, opposite_offsets, min_scores_mate1, min_scores_mate2)          # kept alive
+        self.c = _PeRagged(*[_ptr(t) for t in self.tensors])
+
+
+def pe_init_ragged(ragged, best_a, best_o):
+    """nvbio_pe_init_ragged: best_a / best_o int32 [R, 2, 4] = unaligned at min_scores_mate1[r] / min_scores_mate2[r]"""
+    dev = best_a.device
+    _check(lib().nvbio_pe_init_ragged(FMIndex._dev_index(dev), ctypes.c_uint32(best_a.shape[0]), ctypes.byref(ragged.c), _ptr(best_a), _ptr(best_o),
+                                      _stream_ptr(dev)))
+
+
+def pe_anchor_flatten_ragged(params, ragged, hits, best_a, best_o, read_id, flags, win_begin, win_end, min_scores):
+    """nvbio_pe_anchor_flatten_ragged: the per-job arrays of the anchor's banded DP (int32 [hits.n], flags uint8) and the hits' min scores"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_anchor_flatten_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), ctypes.byref(hq), _ptr(best_a),
+                                                _ptr(best_o), _ptr(read_id), _ptr(flags), _ptr(win_begin), _ptr(win_end), _ptr(min_scores),
+                                                _stream_ptr(hits.device)))
+
+
+def pe_opposite_flatten_ragged(params, ragged, queue, n, hits, best_a, best_o, read_id, flags, win_begin, win_end, min_scores):
+    """nvbio_pe_opposite_flatten_ragged: the same for the opposite mate of the n hits of queue (those whose anchor passed)"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_opposite_flatten_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(queue), ctypes.c_uint32(n),
+                                                  ctypes.byref(hq), _ptr(best_a), _ptr(best_o), _ptr(read_id), _ptr(flags), _ptr(win_begin), _ptr(win_end),
+                                                  _ptr(min_scores), _stream_ptr(hits.device)))
+
+
+def pe_score_reduce_ragged(params, ragged, active, n_active, hits_first, hits_count, hits, hit_oscore, hit_oloc, hit_osink, n_ext, best_a, best_o, trys, sizes):
+    """nvbio_pe_score_reduce_ragged: score_reduce_paired with the anchor read's own length in `distinct`"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_score_reduce_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(active), ctypes.c_uint32(n_active),
+                                              _ptr(hits_first), _ptr(hits_count), ctypes.byref(hq), _ptr(hit_oscore), _ptr(hit_oloc), _ptr(hit_osink),
+                                              ctypes.c_uint32(n_ext), _ptr(best_a), _ptr(best_o), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
+
+
 # ---- nvBowtie's all-mapping mode (include/nvbio_amd.h: nvbio_all_*; host/nvbio_amd/all_mapping.hpp) ---------------------------------
 class _AllHitsParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("seeds_per_read", "first_offset", "seed_interval", "seed_len", "read_len")]

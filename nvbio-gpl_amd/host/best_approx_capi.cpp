@@ -81,4 +81,23 @@ int nvbio_host_best_approx_paired(int device, nvbio_fm_index_t fmi, const uint32
         if (stats) { stats->n_extensions = s.n_extensions; stats->n_opposite = s.n_opposite; stats->passes = s.passes; stats->multi_passes = s.multi_passes; } } );
 }
 
+// the paired-end form over mates of different lengths (best_approx_paired_ragged): read_offsets1 / read_offsets2 [n_reads + 1] and min_scores1 / min_scores2
+// [n_reads] are HOST arrays; a missing table, decreasing offsets, an empty mate or a mate of 1024 symbols or more in either batch is refused (returns 1)
+// before anything is launched or written
+int nvbio_host_best_approx_paired_ragged(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads1_dev,
+                                         const uint32_t* stored_reads2_dev, const uint8_t* quals1_dev, const uint8_t* quals2_dev, uint32_t n_reads,
+                                         const uint32_t* read_offsets1, const uint32_t* read_offsets2, int aln_type, const nvbio_gotoh_scheme* scheme,
+                                         const int32_t* min_scores1, const int32_t* min_scores2, uint32_t min_read_len, const nvbio_host_best_approx_params* p,
+                                         const nvbio_host_paired_params* pe, int32_t* best_a_dev, int32_t* best_o_dev, void* stream, nvbio_host_paired_stats* stats)
+{
+    return guarded( [&] {
+        nvbio_amd_host::PairedParams pp; pp.policy = pe->policy; pp.min_frag_len = pe->min_frag_len; pp.max_frag_len = pe->max_frag_len; pp.overlap = pe->overlap; pp.unpaired = pe->unpaired;
+        const uint32_t* reads[2] = { stored_reads1_dev, stored_reads2_dev }; const uint8_t* quals[2] = { quals1_dev, quals2_dev };
+        const uint32_t* offs[2] = { read_offsets1, read_offsets2 }; const int32_t* worst[2] = { min_scores1, min_scores2 };
+        const nvbio_amd_host::PairedStats s = nvbio_amd_host::best_approx_paired_ragged( device, fmi, genome2_dev, genome_len, reads, quals, n_reads, offs,
+                                                                                         (nvbio_alignment_type)aln_type, *scheme, worst, params_of( p ), pp, best_a_dev,
+                                                                                         best_o_dev, (hipStream_t)stream, min_read_len );
+        if (stats) { stats->n_extensions = s.n_extensions; stats->n_opposite = s.n_opposite; stats->passes = s.passes; stats->multi_passes = s.multi_passes; } } );
+}
+
 } // extern "C"

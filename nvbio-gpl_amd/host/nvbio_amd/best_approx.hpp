@@ -7,9 +7,10 @@
 // (active reads, selected hits) through pinned memory -- they size the next launches -- and nothing else; queues are allocated once per
 // call, at their worst-case size (a batch of reads, BATCH_SIZE hits).
 //
-// The loop is written ONCE (detail::seed_extend_loop) and has three routes -- best_approx (reads of one length), best_approx_ragged (reads of
-// different lengths) and best_approx_paired (two mates, the loop once per anchor) -- each of which hands it what actually differs: the plan of a
-// seeding pass, how a pass begins and maps its seeds, how the selected hits are scored, and the reduce call.
+// The loop is written ONCE (detail::seed_extend_loop) and has four routes -- best_approx (reads of one length), best_approx_ragged (reads of
+// different lengths), best_approx_paired (two mates, the loop once per anchor) and best_approx_paired_ragged (two mates of different lengths) --
+// each of which hands it what actually differs: the plan of a seeding pass, how a pass begins and maps its seeds, how the selected hits are
+// scored, and the reduce call.
 //
 // LIMIT of the uniform routes (best_approx, both mates of best_approx_paired, all_mapping): read r starts at symbol r * read_len of the stored
 // stream and the read index is 32-bit, so n_reads * read_len must stay below 2^32; a larger batch throws std::invalid_argument before any HIP or
@@ -220,6 +221,97 @@ inline void score_single_end(const Loop& c, const LoopBufs& b, const uint32_t* s
     ok( nvbio_banded_gotoh_score( c.device, c.prm.band, c.aln_type, &c.scheme, &batch, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), c.stream ) );
     ok( nvbio_score_stream_output( c.device, &hq, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), b.j_wb.as<uint32_t>(), -65536, c.stream ) );
 }
+
+// the seeds of a RAGGED batch (best_approx_ragged, and either mate of best_approx_paired_ragged as the anchor).  The constructor takes the host tables
+// -- every read's seed interval, per seeding pass the largest seed count of a read, the longest read -- and throws std::invalid_argument for offsets
+// that decrease or a read of 1024 symbols or more: before anything touches the device.  read_index_dev / intervals_dev are the caller's uploads.
+struct RaggedSeeds
+{
+    const uint32_t* offsets; uint32_t R, L, min_read_len, Mmax = 0, spr_max = 0; bool has_empty = false;     // has_empty: a read of no symbols
+    std::vector<uint32_t> intervals, spr_of;
+    const uint32_t* read_index_dev = nullptr; const uint32_t* intervals_dev = nullptr;
+    nvbio_ragged_seed_layout lay; nvbio_seed_hits_params sp;
+    RaggedSeeds(const std::string& who, uint32_t n_reads, const uint32_t* read_offsets, const BestApproxParams& prm, uint32_t min_read_len_)
+        : offsets( read_offsets ), R( n_reads ), L( prm.seed_len ), min_read_len( min_read_len_ ), intervals( n_reads ), spr_of( prm.max_reseed + 1u, 0u ), lay(), sp()
+    {
+        const uint32_t min_len = min_read_len > L ? min_read_len : L;
+        const uint32_t n_pass = prm.max_reseed + 1u;
+        // a length is below 1024, so the interval and the seed counts are taken once per LENGTH the batch holds, not once per read
+        uint32_t interval_of[1024] = {};                    // 0: the batch holds no read of this length
+        for (uint32_t r = 0; r < R; ++r)
+        {
+            if (read_offsets[r + 1] < read_offsets[r]) throw std::invalid_argument( who + ": read_offsets must not decrease" );
+            const uint32_t M = read_offsets[r + 1] - read_offsets[r];
+            if (M >= 1024u) throw std::invalid_argument( who + ": a read of 1024 symbols or more (SeedHit keeps the seed position in 10 bits, seed_hit.h:217)" );
+            if (interval_of[M] == 0u) { const uint32_t S = seed_interval( M, prm.seed_freq ); interval_of[M] = S ? S : 1u; }
+            intervals[r] = interval_of[M];
+        }
+        has_empty = interval_of[0] != 0u;
+        for (uint32_t M = 0; M < 1024u; ++M)
+        {
+            const uint32_t S = interval_of[M];
+            if (S == 0u) continue;
+            Mmax = M;
+            if (M < min_len) continue;
+            for (uint32_t p = 0; p < n_pass; ++p)
+            {
+                const uint32_t first = p * (S / n_pass);
+                if (M < L + first) break;
+                const uint32_t spr = (M - L - first) / S + 1u;
+                if (spr > spr_of[p]) spr_of[p] = spr;
+                if (spr > spr_max) spr_max = spr;
+            }
+        }
+    }
+    uint32_t plan(const Loop& c, uint32_t pass)
+    {
+        const uint32_t spr = spr_of[pass];
+        lay = { read_index_dev, intervals_dev, spr, pass, c.prm.max_reseed, L, min_read_len };
+        sp = { spr, 0u, 0u, L, Mmax, c.prm.max_hits, c.prm.rep_seeds, c.prm.max_effort, c.prm.min_ext, c.max_ext };
+        return spr;
+    }
+    nvbio_string_set begin(const Loop& c, const LoopBufs& b, const uint32_t* stored_reads4_dev, const uint32_t* queue, uint32_t nq) const
+    {
+        ok( nvbio_read_queue_begin_ragged( c.device, queue, nq, &lay, offsets[R], c.prm.top_seed, c.max_effort_init, b.offs.as<uint32_t>(), b.active_a.as<uint32_t>(),
+                                           b.trys.as<uint32_t>(), c.stream ) );
+        return nvbio_string_set{ stored_reads4_dev, 4u, b.offs.as<uint32_t>(), 0u, L, 0u, nq * lay.seeds_per_read, 0u, 0u, nullptr };
+    }
+    void map(const Loop& c, const LoopBufs& b, const uint32_t* queue, uint32_t nq) const
+    {
+        ok( nvbio_seed_hits_map_ragged( c.device, b.fw.as<nvbio_uint2>(), b.rc.as<nvbio_uint2>(), queue, nq, &lay, c.prm.max_hits, c.prm.rep_seeds, b.deques.as<nvbio_uint2>(),
+                                        b.sizes.as<uint32_t>(), b.reseed.as<uint8_t>(), c.stream ) );
+    }
+};
+
+// one mate of a paired batch as the DP calls see it
+struct MateReads { const uint32_t* stored_reads4_dev; const uint8_t* quals_dev; const uint32_t* read_index_dev; uint32_t max_len; };
+
+// paired scoring of the selected hits (BestAnchorScoreStream, BestOppositeScoreStream): the anchor band-aligned against the pair-derived threshold,
+// the opposite mate by full-matrix DP for the hits whose anchor passed (the third counter); -> how many those were.  The two flatten calls are the
+// route's: flatten_anchor(), flatten_opposite( n_opp ), over the buffers of `b`.
+template <typename FlattenAnchor, typename FlattenOpposite>
+inline uint32_t score_paired(const Loop& c, const LoopBufs& b, const nvbio_pe_params& pp, uint32_t max_frag_len, const MateReads& a, const MateReads& o,
+                             uint32_t anchor_algo_flags, const nvbio_hit_queues& hq, uint32_t n_hits, FlattenAnchor flatten_anchor, FlattenOpposite flatten_opposite)
+{
+    flatten_anchor();
+    nvbio_alignment_batch ab = { a.stored_reads4_dev, 4u, a.read_index_dev, a.quals_dev, b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(), c.genome2_dev,
+                                 2u, b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), n_hits, a.max_len, anchor_algo_flags };
+    ok( nvbio_banded_gotoh_score( c.device, c.prm.band, c.aln_type, &c.scheme, &ab, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), c.stream ) );
+    ok( nvbio_pe_anchor_output( c.device, &pp, &hq, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), b.j_wb.as<uint32_t>(), b.j_min.as<int32_t>(),
+                                b.h_oscore.as<int32_t>(), b.valid.as<uint8_t>(), c.stream ) );
+    ok( nvbio_select_flagged_indices( c.device, b.valid.as<uint8_t>(), n_hits, b.oqueue.as<uint32_t>(), b.counts.dev.as<uint32_t>() + 2, c.stream ) );
+    b.counts.fetch( c.stream, 1, 2 );
+    const uint32_t n_opp = b.counts.host[2];
+    if (n_opp == 0) return 0u;
+    flatten_opposite( n_opp );
+    nvbio_alignment_batch ob = { o.stored_reads4_dev, 4u, o.read_index_dev, o.quals_dev, b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(),
+                                 c.genome2_dev, 2u, b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), n_opp, o.max_len, 0u };
+    ok( nvbio_full_gotoh_score( c.device, c.aln_type, 0 /* pattern blocking */, &c.scheme, &ob, o.max_len, max_frag_len, b.j_min.as<int32_t>(),
+                                b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), nullptr, 0, c.stream ) );
+    ok( nvbio_pe_opposite_output( c.device, &pp, b.oqueue.as<uint32_t>(), n_opp, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), b.j_wb.as<uint32_t>(),
+                                  b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), b.h_oscore.as<int32_t>(), b.h_oloc.as<uint32_t>(), b.h_osink.as<uint32_t>(), c.stream ) );
+    return n_opp;
+}
 } // namespace detail
 
 // The route for reads of ONE length.
@@ -273,32 +365,11 @@ inline BestApproxStats best_approx_ragged(int device, nvbio_fm_index_t fmi, cons
                                           uint8_t* best_rc_dev, hipStream_t stream, uint32_t min_read_len = 12)
 {
     using namespace detail;
-    const uint32_t R = n_reads, L = prm.seed_len;
+    const uint32_t R = n_reads;
     if (R == 0) return BestApproxStats();
     if (read_offsets == nullptr || min_scores == nullptr) throw std::invalid_argument( "best_approx_ragged: read_offsets and min_scores are required" );
-    if (L == 0) throw std::invalid_argument( "best_approx_ragged: seed_len must be positive" );
-    const uint32_t min_len = min_read_len > L ? min_read_len : L;
-    const uint32_t n_pass = prm.max_reseed + 1u;
-    std::vector<uint32_t> intervals( R ), spr_of( n_pass, 0u );
-    uint32_t Mmax = 0, spr_max = 0;
-    for (uint32_t r = 0; r < R; ++r)
-    {
-        if (read_offsets[r + 1] < read_offsets[r]) throw std::invalid_argument( "best_approx_ragged: read_offsets must not decrease" );
-        const uint32_t M = read_offsets[r + 1] - read_offsets[r];
-        if (M >= 1024u) throw std::invalid_argument( "best_approx_ragged: a read of 1024 symbols or more (SeedHit keeps the seed position in 10 bits, seed_hit.h:217)" );
-        const uint32_t S = seed_interval( M, prm.seed_freq );
-        intervals[r] = S ? S : 1u;
-        if (M > Mmax) Mmax = M;
-        if (M < min_len) continue;
-        for (uint32_t p = 0; p < n_pass; ++p)
-        {
-            const uint32_t first = p * (intervals[r] / n_pass);
-            if (M < L + first) break;
-            const uint32_t spr = (M - L - first) / intervals[r] + 1u;
-            if (spr > spr_of[p]) spr_of[p] = spr;
-            if (spr > spr_max) spr_max = spr;
-        }
-    }
+    if (prm.seed_len == 0) throw std::invalid_argument( "best_approx_ragged: seed_len must be positive" );
+    RaggedSeeds seeds( "best_approx_ragged", R, read_offsets, prm, min_read_len );
     hip( hipSetDevice( device ) );
     const Loop c( device, fmi, genome2_dev, genome_len, aln_type, scheme, prm, R, stream );
     const DevBuf read_index( 4ull * (R + 1) ), worst( 4ull * R );
@@ -306,31 +377,22 @@ inline BestApproxStats best_approx_ragged(int device, nvbio_fm_index_t fmi, cons
     hip( hipMemcpyAsync( worst.p, min_scores, 4ull * R, hipMemcpyHostToDevice, stream ) );
     hip( hipStreamSynchronize( stream ) );
     ok( nvbio_best_approx_init_ragged( device, R, worst.as<int32_t>(), best_dev, best_rc_dev, stream ) );
-    if (spr_max == 0) { hip( hipStreamSynchronize( stream ) ); return BestApproxStats(); }
+    if (seeds.spr_max == 0) { hip( hipStreamSynchronize( stream ) ); return BestApproxStats(); }
 
-    uint32_t cap = 0; ok( nvbio_seed_hits_capacity( spr_max, prm.max_hits, &cap ) );
+    uint32_t cap = 0; ok( nvbio_seed_hits_capacity( seeds.spr_max, prm.max_hits, &cap ) );
     const DevBuf ivals( 4ull * R );
-    const LoopBufs b( c, (uint64_t)R * spr_max, spr_max, cap, false );            // one explicit offset per seed
-    upload( ivals, intervals, stream );
-    nvbio_ragged_seed_layout lay; nvbio_seed_hits_params sp;
+    const LoopBufs b( c, (uint64_t)R * seeds.spr_max, seeds.spr_max, cap, false );            // one explicit offset per seed
+    upload( ivals, seeds.intervals, stream );
+    seeds.read_index_dev = read_index.as<uint32_t>(); seeds.intervals_dev = ivals.as<uint32_t>();
     const BestApproxStats stats = seed_extend_loop( c, b,
-        [&](uint32_t pass) {
-            const uint32_t spr = spr_of[pass];
-            lay = { read_index.as<uint32_t>(), ivals.as<uint32_t>(), spr, pass, prm.max_reseed, L, min_read_len };
-            sp = { spr, 0u, 0u, L, Mmax, prm.max_hits, prm.rep_seeds, prm.max_effort, prm.min_ext, c.max_ext };
-            return spr; },
-        [&](const uint32_t* queue, uint32_t nq) {
-            ok( nvbio_read_queue_begin_ragged( device, queue, nq, &lay, read_offsets[R], prm.top_seed, c.max_effort_init, b.offs.as<uint32_t>(), b.active_a.as<uint32_t>(),
-                                               b.trys.as<uint32_t>(), stream ) );
-            return nvbio_string_set{ stored_reads4_dev, 4u, b.offs.as<uint32_t>(), 0u, L, 0u, nq * lay.seeds_per_read, 0u, 0u, nullptr }; },
-        [&](const uint32_t* queue, uint32_t nq) {
-            ok( nvbio_seed_hits_map_ragged( device, b.fw.as<nvbio_uint2>(), b.rc.as<nvbio_uint2>(), queue, nq, &lay, prm.max_hits, prm.rep_seeds, b.deques.as<nvbio_uint2>(),
-                                            b.sizes.as<uint32_t>(), b.reseed.as<uint8_t>(), stream ) ); },
+        [&](uint32_t pass) { return seeds.plan( c, pass ); },
+        [&](const uint32_t* queue, uint32_t nq) { return seeds.begin( c, b, stored_reads4_dev, queue, nq ); },
+        [&](const uint32_t* queue, uint32_t nq) { seeds.map( c, b, queue, nq ); },
         [&](const nvbio_hit_queues& hq, uint32_t) {
-            score_single_end( c, b, stored_reads4_dev, quals_dev, read_index.as<uint32_t>(), Mmax, NVBIO_ALN_RAGGED_READS, hq ); },
+            score_single_end( c, b, stored_reads4_dev, quals_dev, read_index.as<uint32_t>(), seeds.Mmax, NVBIO_ALN_RAGGED_READS, hq ); },
         [&](const uint32_t* active, uint32_t n_active, const nvbio_hit_queues& hq, uint32_t n_ext) {
             ok( nvbio_score_reduce_effort_multi_ragged( device, active, n_active, b.hits_first.as<uint32_t>(), b.hits_count.as<uint32_t>(), &hq, read_index.as<uint32_t>(),
-                                                        n_ext, &sp, best_dev, best_rc_dev, b.trys.as<uint32_t>(), b.sizes.as<uint32_t>(), stream ) ); } );
+                                                        n_ext, &seeds.sp, best_dev, best_rc_dev, b.trys.as<uint32_t>(), b.sizes.as<uint32_t>(), stream ) ); } );
     hip( hipStreamSynchronize( stream ) );
     return stats;
 }
@@ -368,6 +430,8 @@ inline PairedStats best_approx_paired(int device, nvbio_fm_index_t fmi, const ui
     const LoopBufs b( c, R, spr_max, cap_max, true );                             // one set of queues for both anchors
     for (int m = 0; m < 2; ++m) upload( read_index[m], ri[m], stream );
     ok( nvbio_pe_init( device, R, worst_score[0], worst_score[1], best_a_dev, best_o_dev, stream ) );
+    const MateReads mates[2] = { { stored_reads4_dev[0], quals_dev[0], read_index[0].as<uint32_t>(), read_len[0] },
+                                 { stored_reads4_dev[1], quals_dev[1], read_index[1].as<uint32_t>(), read_len[1] } };
 
     for (uint32_t anchor = 0; anchor < 2; ++anchor)
     {
@@ -382,32 +446,94 @@ inline PairedStats best_approx_paired(int device, nvbio_fm_index_t fmi, const ui
             [&](const uint32_t* queue, uint32_t nq) { return seeds.begin( c, b, stored_reads4_dev[a], queue, nq ); },
             [&](const uint32_t* queue, uint32_t nq) { seeds.map( c, b, queue, nq ); },
             [&](const nvbio_hit_queues& hq, uint32_t n_hits) {
-                // anchor: band-aligned against the pair-derived threshold
-                ok( nvbio_pe_anchor_flatten( device, &pp, &hq, best_a_dev, best_o_dev, b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(), b.j_wb.as<uint32_t>(),
-                                             b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), stream ) );
-                nvbio_alignment_batch ab = { stored_reads4_dev[a], 4u, read_index[a].as<uint32_t>(), quals_dev[a], b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(), genome2_dev,
-                                             2u, b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), n_hits, M, 0u };
-                ok( nvbio_banded_gotoh_score( device, prm.band, aln_type, &scheme, &ab, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), stream ) );
-                ok( nvbio_pe_anchor_output( device, &pp, &hq, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), b.j_wb.as<uint32_t>(), b.j_min.as<int32_t>(),
-                                            b.h_oscore.as<int32_t>(), b.valid.as<uint8_t>(), stream ) );
-                // opposite mate: full-matrix DP for the hits whose anchor passed (the third counter)
-                ok( nvbio_select_flagged_indices( device, b.valid.as<uint8_t>(), n_hits, b.oqueue.as<uint32_t>(), b.counts.dev.as<uint32_t>() + 2, stream ) );
-                b.counts.fetch( stream, 1, 2 );
-                const uint32_t n_opp = b.counts.host[2];
-                stats.n_opposite += n_opp;
-                if (n_opp == 0) return;
-                ok( nvbio_pe_opposite_flatten( device, &pp, b.oqueue.as<uint32_t>(), n_opp, &hq, best_a_dev, best_o_dev, b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(),
-                                               b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), stream ) );
-                nvbio_alignment_batch ob = { stored_reads4_dev[o], 4u, read_index[o].as<uint32_t>(), quals_dev[o], b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(),
-                                             genome2_dev, 2u, b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), n_opp, Mo, 0u };
-                ok( nvbio_full_gotoh_score( device, aln_type, 0 /* pattern blocking */, &scheme, &ob, Mo, pe.max_frag_len, b.j_min.as<int32_t>(),
-                                            b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), nullptr, 0, stream ) );
-                ok( nvbio_pe_opposite_output( device, &pp, b.oqueue.as<uint32_t>(), n_opp, b.j_scores.as<int32_t>(), b.j_sinks.as<nvbio_uint2>(), b.j_wb.as<uint32_t>(),
-                                              b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), b.h_oscore.as<int32_t>(), b.h_oloc.as<uint32_t>(), b.h_osink.as<uint32_t>(), stream ) ); },
+                stats.n_opposite += score_paired( c, b, pp, pe.max_frag_len, mates[a], mates[o], 0u, hq, n_hits,
+                    [&] { ok( nvbio_pe_anchor_flatten( device, &pp, &hq, best_a_dev, best_o_dev, b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(), b.j_wb.as<uint32_t>(),
+                                                       b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), stream ) ); },
+                    [&](uint32_t n_opp) { ok( nvbio_pe_opposite_flatten( device, &pp, b.oqueue.as<uint32_t>(), n_opp, &hq, best_a_dev, best_o_dev, b.j_read.as<uint32_t>(),
+                                                                         b.j_flags.as<uint8_t>(), b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), stream ) ); } ); },
             [&](const uint32_t* active, uint32_t n_active, const nvbio_hit_queues& hq, uint32_t n_ext) {
                 ok( nvbio_pe_score_reduce( device, &pp, active, n_active, b.hits_first.as<uint32_t>(), b.hits_count.as<uint32_t>(), &hq, b.h_oscore.as<int32_t>(),
                                            b.h_oloc.as<uint32_t>(), b.h_osink.as<uint32_t>(), n_ext, best_a_dev, best_o_dev, b.trys.as<uint32_t>(), b.sizes.as<uint32_t>(),
                                            stream ) ); } );
+        stats.n_extensions += s.n_extensions; stats.passes += s.passes; stats.multi_passes += s.multi_passes;
+    }
+    hip( hipStreamSynchronize( stream ) );
+    return stats;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The paired loop over mates of DIFFERENT lengths: mate m of pair r = stored symbols [read_offsets[m][r], read_offsets[m][r+1]) of stored_reads4_dev[m].
+// The reference is per read throughout (include/nvbio_amd.h, nvbio_pe_ragged), so this is the same algorithm with per-pair tables: per anchor the
+// seeds of the single-end ragged route over the ANCHOR mate's offsets (S_r, first_r and the per-pass seed count from the host), the paired route's
+// scoring with the ragged flatten calls -- the banded call told the longest anchor mate and NVBIO_ALN_RAGGED_READS, the full-matrix call bounded by the
+// longest opposite mate -- and the ragged reduce; nvbio_pe_anchor_output / nvbio_pe_opposite_output read no length and are the uniform route's.  One
+// set of queues for both anchors, three pinned counters per extension pass.
+// The FILTER is the single-end one and applies to seeding only: a mate with M_r < max( min_read_len, seed_len ) contributes no seeds while it is the
+// anchor (an empty deque in every pass, never reseeded) and is still aligned as the opposite mate of its partner's hits; a pair whose both mates are
+// filtered ends as initialised.  DIVERGENCE, inherited: the reference would seed a mate with min_read_len <= M_r < seed_len once with the whole read
+// (mapping_inl.h:516).  Seeding of an anchor stops only when no read of the batch has a seed slot left.
+// REFUSED with std::invalid_argument, before any HIP or library call and with nothing written: missing tables; offsets that decrease; a mate of 1024
+// symbols or more in either batch (seed_hit.h:217); an empty mate, M_r == 0 (no placement is defined for it).
+// min_scores[m][r] = scheme.min_score( M_r of mate m ); both tables and both offset arrays are HOST arrays.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+inline PairedStats best_approx_paired_ragged(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* const stored_reads4_dev[2],
+                                             const uint8_t* const quals_dev[2], uint32_t n_reads, const uint32_t* const read_offsets[2], nvbio_alignment_type aln_type,
+                                             const nvbio_gotoh_scheme& scheme, const int32_t* const min_scores[2], const BestApproxParams& prm, const PairedParams& pe,
+                                             int32_t* best_a_dev, int32_t* best_o_dev, hipStream_t stream, uint32_t min_read_len = 12)
+{
+    using namespace detail;
+    PairedStats stats;
+    const uint32_t R = n_reads;
+    if (R == 0) return stats;
+    if (read_offsets == nullptr || min_scores == nullptr || read_offsets[0] == nullptr || read_offsets[1] == nullptr || min_scores[0] == nullptr || min_scores[1] == nullptr)
+        throw std::invalid_argument( "best_approx_paired_ragged: read_offsets and min_scores of both mates are required" );
+    if (prm.seed_len == 0) throw std::invalid_argument( "best_approx_paired_ragged: seed_len must be positive" );
+    RaggedSeeds mate_seeds[2] = { RaggedSeeds( "best_approx_paired_ragged", R, read_offsets[0], prm, min_read_len ),
+                                  RaggedSeeds( "best_approx_paired_ragged", R, read_offsets[1], prm, min_read_len ) };
+    if (mate_seeds[0].has_empty || mate_seeds[1].has_empty) throw std::invalid_argument( "best_approx_paired_ragged: an empty mate (no placement is defined for it)" );
+    hip( hipSetDevice( device ) );
+    const Loop c( device, fmi, genome2_dev, genome_len, aln_type, scheme, prm, R, stream );
+    uint32_t spr_max = 1, cap_max = 0;
+    for (int m = 0; m < 2; ++m) if (mate_seeds[m].spr_max > spr_max) spr_max = mate_seeds[m].spr_max;
+    ok( nvbio_seed_hits_capacity( spr_max, prm.max_hits, &cap_max ) );
+    const DevBuf read_index[2] = { DevBuf( 4ull * (R + 1) ), DevBuf( 4ull * (R + 1) ) }, worst[2] = { DevBuf( 4ull * R ), DevBuf( 4ull * R ) },
+                 ivals[2] = { DevBuf( 4ull * R ), DevBuf( 4ull * R ) };
+    const LoopBufs b( c, (uint64_t)R * spr_max, spr_max, cap_max, true );         // one set of queues for both anchors, one explicit offset per seed
+    for (int m = 0; m < 2; ++m)
+    {
+        hip( hipMemcpyAsync( read_index[m].p, read_offsets[m], 4ull * (R + 1), hipMemcpyHostToDevice, stream ) );
+        hip( hipMemcpyAsync( worst[m].p, min_scores[m], 4ull * R, hipMemcpyHostToDevice, stream ) );
+        upload( ivals[m], mate_seeds[m].intervals, stream );
+        mate_seeds[m].read_index_dev = read_index[m].as<uint32_t>(); mate_seeds[m].intervals_dev = ivals[m].as<uint32_t>();
+    }
+    const MateReads mates[2] = { { stored_reads4_dev[0], quals_dev[0], read_index[0].as<uint32_t>(), mate_seeds[0].Mmax },
+                                 { stored_reads4_dev[1], quals_dev[1], read_index[1].as<uint32_t>(), mate_seeds[1].Mmax } };
+    nvbio_pe_ragged rg = { nullptr, nullptr, worst[0].as<int32_t>(), worst[1].as<int32_t>() };
+    ok( nvbio_pe_init_ragged( device, R, &rg, best_a_dev, best_o_dev, stream ) );
+
+    for (uint32_t anchor = 0; anchor < 2; ++anchor)
+    {
+        const uint32_t a = anchor, o = 1u - anchor;
+        RaggedSeeds& seeds = mate_seeds[a];
+        rg.anchor_offsets_dev = mates[a].read_index_dev; rg.opposite_offsets_dev = mates[o].read_index_dev;
+        const nvbio_pe_params pp = { anchor, 0u, 0u, 0, 0, 0, 0, NVBIO_SCORE_MIN, -65536,          // the lengths and scores come from `rg`
+                                     scheme.match, scheme.txt_gap_open, scheme.txt_gap_ext, prm.band, genome_len, pe.policy, pe.min_frag_len, pe.max_frag_len,
+                                     pe.overlap, pe.unpaired, prm.max_effort, prm.min_ext, c.max_ext };
+        const BestApproxStats s = seed_extend_loop( c, b,
+            [&](uint32_t pass) { return seeds.plan( c, pass ); },
+            [&](const uint32_t* queue, uint32_t nq) { return seeds.begin( c, b, stored_reads4_dev[a], queue, nq ); },
+            [&](const uint32_t* queue, uint32_t nq) { seeds.map( c, b, queue, nq ); },
+            [&](const nvbio_hit_queues& hq, uint32_t n_hits) {
+                stats.n_opposite += score_paired( c, b, pp, pe.max_frag_len, mates[a], mates[o], NVBIO_ALN_RAGGED_READS, hq, n_hits,
+                    [&] { ok( nvbio_pe_anchor_flatten_ragged( device, &pp, &rg, &hq, best_a_dev, best_o_dev, b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(),
+                                                              b.j_wb.as<uint32_t>(), b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), stream ) ); },
+                    [&](uint32_t n_opp) { ok( nvbio_pe_opposite_flatten_ragged( device, &pp, &rg, b.oqueue.as<uint32_t>(), n_opp, &hq, best_a_dev, best_o_dev,
+                                                                                b.j_read.as<uint32_t>(), b.j_flags.as<uint8_t>(), b.j_wb.as<uint32_t>(),
+                                                                                b.j_we.as<uint32_t>(), b.j_min.as<int32_t>(), stream ) ); } ); },
+            [&](const uint32_t* active, uint32_t n_active, const nvbio_hit_queues& hq, uint32_t n_ext) {
+                ok( nvbio_pe_score_reduce_ragged( device, &pp, &rg, active, n_active, b.hits_first.as<uint32_t>(), b.hits_count.as<uint32_t>(), &hq, b.h_oscore.as<int32_t>(),
+                                                  b.h_oloc.as<uint32_t>(), b.h_osink.as<uint32_t>(), n_ext, best_a_dev, best_o_dev, b.trys.as<uint32_t>(),
+                                                  b.sizes.as<uint32_t>(), stream ) ); } );
         stats.n_extensions += s.n_extensions; stats.passes += s.passes; stats.multi_passes += s.multi_passes;
     }
     hip( hipStreamSynchronize( stream ) );

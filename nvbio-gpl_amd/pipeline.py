@@ -956,11 +956,30 @@ def nvbowtie_best_approx_host(fmi, genome2, genome_len, stored_reads, params, nv
                       seeding_passes=int(st.seeding_passes))
 
 
-def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, stored_mates2, params, nvb=None, pe=None, unpaired=True, batch_size=0, multi_hit=True):
+def _mate_tables(mate, params):
+    """host-side view of one mate batch for the ragged paired loop: offsets uint32 [R + 1] -- its own, or arange( R + 1 ) * read_len -- and every read's
+    worst score min_score( M_r ) int32 [R].  A length the loop refuses (1024 or more; a decreasing pair of offsets wraps to one) takes the table's last
+    entry: the loop throws before it reads it."""
+    if mate.offsets is None:
+        off = np.arange(mate.n + 1, dtype=np.uint32) * np.uint32(mate.read_len)
+    else:
+        off = np.ascontiguousarray(mate.offsets.detach().cpu().numpy()).view(np.uint32)
+        if len(off) != mate.n + 1:
+            raise ValueError("offsets must hold n_reads + 1 symbol offsets")
+    lens = np.minimum(np.diff(off), np.uint32(1024))
+    return off, params.min_score_table(int(lens.max()) if len(lens) else 0)[lens]
+
+
+def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, stored_mates2, params, nvb=None, pe=None, unpaired=True, batch_size=0, multi_hit=True,
+                                     out=None):
     """nvBowtie's PAIRED-END best-approx loop (Aligner::best_approx, aligner_best_approx_paired.h:84-200,590-1000) as the C++ host loop
     nvbio_host_best_approx_paired: for anchor = mate 1, then mate 2, the single-end loop over the anchor's seed hits with every selected hit scored as
     a pair -- the anchor against a threshold that tightens with the pairs found so far (compute_target_score), the opposite mate by full-matrix DP in
     its fragment window for the hits whose anchor passed, score_reduce_paired keeping the best two pairs (or per-mate bests while unpaired).
+    Mates of DIFFERENT lengths: when either ReadBatch has offsets the call takes nvbio_host_best_approx_paired_ragged (a batch without offsets is
+    handed over as arange( R + 1 ) * read_len): every pair its own lengths, thresholds, seed interval and distinct distance; a mate shorter than
+    max( nvb.min_read_len, seed_len ) is not seeded but still aligned as its partner's opposite mate.  Raises RuntimeError, having launched and written
+    nothing, for a mate of 1024 symbols or more, an empty mate or decreasing offsets.  out: the caller's (best_a, best_o) to write into, or None.
     -> dict( best_a, best_o [R, 2, 4] int32 = { score, position, sink offset, rc | mate << 1 | paired << 2 } x { best, second }, counters )."""
     import ctypes
     import torch
@@ -981,13 +1000,20 @@ def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, st
     p = _host_params(nvb, nvb.seed_freq or 0, batch_size, multi_hit)
     q = _PE(int(pe.policy), int(pe.min_frag_len), int(pe.max_frag_len), 1 if pe.overlap else 0, 1 if unpaired else 0)
     st = _S()
-    best_a = torch.empty((R, 2, 4), dtype=torch.int32, device=dev)
-    best_o = torch.empty((R, 2, 4), dtype=torch.int32, device=dev)
-    rc = _host_lib().nvbio_host_best_approx_paired(
-        ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_mates1.reads4), _ptr(stored_mates2.reads4),
-        _ptr(stored_mates1.quals), _ptr(stored_mates2.quals), ctypes.c_uint32(R), ctypes.c_uint32(M1), ctypes.c_uint32(M2), ctypes.c_int(int(params.aln_type)),
-        ctypes.byref(params.scheme.c), ctypes.c_int32(params.min_score_for(M1)), ctypes.c_int32(params.min_score_for(M2)), ctypes.byref(p), ctypes.byref(q),
-        _ptr(best_a), _ptr(best_o), _stream_ptr(dev), ctypes.byref(st))
+    best_a, best_o = out or (torch.empty((R, 2, 4), dtype=torch.int32, device=dev), torch.empty((R, 2, 4), dtype=torch.int32, device=dev))
+    head = (ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_mates1.reads4), _ptr(stored_mates2.reads4),
+            _ptr(stored_mates1.quals), _ptr(stored_mates2.quals), ctypes.c_uint32(R))
+    kind = (ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c))
+    tail = (ctypes.byref(p), ctypes.byref(q), _ptr(best_a), _ptr(best_o), _stream_ptr(dev), ctypes.byref(st))
+    if stored_mates1.offsets is None and stored_mates2.offsets is None:
+        rc = _host_lib().nvbio_host_best_approx_paired(*head, ctypes.c_uint32(M1), ctypes.c_uint32(M2), *kind, ctypes.c_int32(params.min_score_for(M1)),
+                                                       ctypes.c_int32(params.min_score_for(M2)), *tail)
+    else:
+        # mates of different lengths (nvbio_host_best_approx_paired_ragged): both mates' offsets and per-read worst scores go on the HOST
+        off, worst = zip(*[_mate_tables(m, params) for m in (stored_mates1, stored_mates2)])
+        host_ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        rc = _host_lib().nvbio_host_best_approx_paired_ragged(*head, host_ptr(off[0]), host_ptr(off[1]), *kind, host_ptr(worst[0]), host_ptr(worst[1]),
+                                                              ctypes.c_uint32(nvb.min_read_len), *tail)
     if rc != 0:
         raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
     return dict(best_a=best_a, best_o=best_o, n_extensions=int(st.n_extensions), n_opposite=int(st.n_opposite), passes=int(st.passes),
@@ -999,6 +1025,7 @@ def nvbowtie_paired_traceback(genome2, genome_len, stored_mates1, stored_mates2,
     opposite mate, traceback_inl.h:191-275): for every pair the loop found (best_a[:, 0] paired), the anchor mate is traced back through the banded
     traceback in the window BestAnchorScoreStream scored it in, the opposite mate through the full-matrix traceback from its window's begin to the
     column its alignment ends in -- scores and sinks are the loop's, so neither scoring pass is repeated.
+    Mates of different lengths (a ReadBatch with offsets): every read's window end and sink row come from its own length.
     loop: the dict of nvbowtie_best_approx_paired_host.  -> dict( paired [R] bool; per mate m = 1, 2: begin{m} (text position where the alignment
     starts, -1 unpaired), rc{m}, score{m}, cigars{m} [R, cigar_stride] (io::Cigar runs, backtracking order), cigar_lens{m} )."""
     import torch
@@ -1007,6 +1034,15 @@ def nvbowtie_paired_traceback(genome2, genome_len, stored_mates1, stored_mates2,
     dev = loop["best_a"].device
     R = stored_mates1.n
     mates = (stored_mates1, stored_mates2)
+
+    def layout_of(mate):                                               # -> (offsets int32 [R + 1], lengths int64 [R], the longest read)
+        if mate.offsets is None:
+            return torch.arange(R + 1, device=dev, dtype=torch.int32) * mate.read_len, torch.full((R,), mate.read_len, dtype=torch.int64, device=dev), mate.read_len
+        off = mate.offsets.to(device=dev, dtype=torch.int32).contiguous()
+        lens = (off[1:].to(torch.int64) & 0xFFFFFFFF) - (off[:-1].to(torch.int64) & 0xFFFFFFFF)
+        return off, lens, int(lens.max().item())
+
+    layouts = (layout_of(stored_mates1), layout_of(stored_mates2))
     a1 = loop["best_a"][:, 0].to(torch.int64); o1 = loop["best_o"][:, 0].to(torch.int64)
     paired = (((a1[:, 3] >> 2) & 1) == 1) & (a1[:, 1] != -1)
     out = {"paired": paired}
@@ -1029,16 +1065,16 @@ def nvbowtie_paired_traceback(genome2, genome_len, stored_mates1, stored_mates2,
         if ids.numel() == 0:
             continue
         a, o = mates[am], mates[1 - am]
+        (a_off, a_lens, a_max), (o_off, o_lens, o_max) = layouts[am], layouts[1 - am]
         rid32 = ids.to(torch.int32)
         # anchor: the band window of pe_anchor_flatten around hit.loc; sink.x = hit.sink - window begin
         g = a1[ids, 1] & 0xFFFFFFFF
         a_rc = (a1[ids, 3] & 1).to(torch.uint8)
         wb = torch.where(g > nvb.band // 2, g - nvb.band // 2, torch.zeros_like(g))
-        we = torch.clamp(wb + nvb.band + a.read_len, max=genome_len)
+        we = torch.clamp(wb + nvb.band + a_lens[ids], max=genome_len)
         sx = g + (a1[ids, 2] & 0xFFFFFFFF) - wb
-        a_off = torch.arange(R + 1, device=dev, dtype=torch.int32) * a.read_len
-        batch = AlignmentBatch(a.reads4, 4, a_off, genome2, 2, i32(wb), i32(we), quals=a.quals, read_id=rid32, flags=flags_of(a_rc), device=dev, max_read_len=a.read_len)
-        sinks = torch.stack([i32(sx), torch.full_like(i32(sx), a.read_len)], dim=1).contiguous()
+        batch = AlignmentBatch(a.reads4, 4, a_off, genome2, 2, i32(wb), i32(we), quals=a.quals, read_id=rid32, flags=flags_of(a_rc), device=dev, max_read_len=a_max)
+        sinks = torch.stack([i32(sx), a_lens[ids].to(torch.int32)], dim=1).contiguous()
         _, src, _, cig, ln = BatchedBandedAlignmentTraceback(nvb.band, aligner).enact(batch, cigar_stride=cigar_stride, scores=a1[ids, 0].to(torch.int32).contiguous(), sinks=sinks)
         k = am + 1
         out["begin%d" % k][ids] = wb + (src[:, 0].to(torch.int64) & 0xFFFFFFFF)
@@ -1048,11 +1084,10 @@ def nvbowtie_paired_traceback(genome2, genome_len, stored_mates1, stored_mates2,
         ob = o1[ids, 1] & 0xFFFFFFFF
         osx = o1[ids, 2] & 0xFFFFFFFF
         o_rc = (o1[ids, 3] & 1).to(torch.uint8)
-        o_off = torch.arange(R + 1, device=dev, dtype=torch.int32) * o.read_len
-        batch = AlignmentBatch(o.reads4, 4, o_off, genome2, 2, i32(ob), i32(ob + osx), quals=o.quals, read_id=rid32, flags=flags_of(o_rc), device=dev, max_read_len=o.read_len)
-        sinks = torch.stack([i32(osx), torch.full_like(i32(osx), o.read_len)], dim=1).contiguous()
+        batch = AlignmentBatch(o.reads4, 4, o_off, genome2, 2, i32(ob), i32(ob + osx), quals=o.quals, read_id=rid32, flags=flags_of(o_rc), device=dev, max_read_len=o_max)
+        sinks = torch.stack([i32(osx), o_lens[ids].to(torch.int32)], dim=1).contiguous()
         max_text = int(osx.max().item()) if ids.numel() else 1
-        _, src, _, cig, ln = BatchedAlignmentTraceback(aligner).enact(batch, o.read_len, max(max_text, 1), cigar_stride=cigar_stride,
+        _, src, _, cig, ln = BatchedAlignmentTraceback(aligner).enact(batch, o_max, max(max_text, 1), cigar_stride=cigar_stride,
                                                                      scores=o1[ids, 0].to(torch.int32).contiguous(), sinks=sinks)
         k = 2 - am
         out["begin%d" % k][ids] = ob + (src[:, 0].to(torch.int64) & 0xFFFFFFFF)
