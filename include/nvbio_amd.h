@@ -142,6 +142,7 @@ enum
                                        both rows in its entry, so that only k-mers with three or more take the second gather (1.07 instead
                                        of 1.25 sectors per seed window on a 3 Gbp text; 128 GiB at k = 17)                         */
     NVBIO_FM_TABLE_NO_TEXT_PLANES = 32, /* a handle that keeps the text does not also keep it as bit planes (nvbio_fm_index_text_planes: none)  */
+    NVBIO_FM_TABLE_NO_SEED_LOCUS = 64,  /* a handle with the canonical table does not build the seed locus lines (nvbio_fm_index_seed_locus: none) */
     NVBIO_FM_TABLE_CANONICAL  = 8   /* instead of the direct table: ONE table for a k-mer and its reverse complement (kmer_len odd; 64 GiB at
                                        k = 17 where the direct table takes 128), serving nvbio_fm_match_seed_diagonals_both; the plain table of
                                        (kmer_len - 1)-mers is kept for match().  Needs sa_int = 1.                                */
@@ -183,6 +184,26 @@ nvbio_status nvbio_text_planes_build(int device, const uint32_t* text2_dev, uint
  * NVBIO_FM_TABLE_NO_TEXT_PLANES is set, and counts them in nvbio_fm_index_device_bytes.  *planes_dev = NULL (and *length = 0)
  * where there are none.  Like the handle itself they describe the text as it was when the index was built. */
 nvbio_status nvbio_fm_index_text_planes(nvbio_fm_index_t index, const void** planes_dev, uint32_t* length);
+
+/* The seed locus lines of the two-strand seed pass (nvbio_fm_match_seed_diagonals_both): the text's bit planes beside a uniqueness
+ * plane u for ONE seed length, so that a read placed by its first seed settles its other seeds from one 128-byte line.
+ * A unit is 24 bytes, (lo64, hi64, u64) of 64 consecutive symbols: lo64 / hi64 as in the text planes, bit j of u64 = u[64 unit + j].
+ * Line L (128 bytes) holds units 2 L .. 2 L + 4, i.e. symbols 128 L .. 128 L + 319, then 8 zero bytes: a read of up to 193 symbols
+ * that begins at symbol P0 lies in the ONE line P0 >> 7.  (length >> 7) + 1 lines (3.0 GB at 3 Gbp); every bit at or beyond
+ * `length` is zero.  u[x] = 1 only if text[x, x + seed_len) occurs exactly once in the text and its reverse complement nowhere --
+ * precisely: iff the canonical table answers that window with the forward hit x alone and its reverse complement with the
+ * reverse-strand hit x alone, neither through a k-mer with more than 8 occurrences; u is 0 in the last seed_len - 1 positions.
+ * nvbio_seed_locus_build: one gather pass over the text positions into the caller's buffer of nvbio_seed_locus_bytes bytes, which
+ * must be 128-byte aligned (NVBIO_ERR_INVALID otherwise); the handle needs the canonical table and the text
+ * (NVBIO_FM_TABLE_CANONICAL, sa_int = 1), seed_len lies in [kmer_len, kmer_len + 7].
+ * The lines a handle keeps: such a handle builds them for seed_len = 22 where kmer_len <= 22 <= kmer_len + 7, unless
+ * NVBIO_FM_TABLE_NO_SEED_LOCUS is set, and counts them in nvbio_fm_index_device_bytes.  nvbio_fm_index_seed_locus hands them out
+ * (*lines_dev = NULL and *seed_len = 0 where there are none); nvbio_fm_index_build_seed_locus builds them, or rebuilds them for
+ * another seed length (it synchronises the stream; no seed pass of the handle may be in flight). */
+nvbio_status nvbio_seed_locus_bytes(uint32_t length, uint64_t* bytes);
+nvbio_status nvbio_seed_locus_build(nvbio_fm_index_t index, uint32_t seed_len, void* lines_dev, void* stream);
+nvbio_status nvbio_fm_index_seed_locus(nvbio_fm_index_t index, const void** lines_dev, uint32_t* seed_len);
+nvbio_status nvbio_fm_index_build_seed_locus(nvbio_fm_index_t index, uint32_t seed_len, void* stream);
 
 /* A set of query strings in HBM: the string-set concept FMIndexFilter::rank consumes
  * (nvbio/fmindex/filter.h:52-231) flattened to arrays.
@@ -374,6 +395,17 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
  * keys_dev, without the adjacent-duplicate removal).  For repeat-rich references; on a unique-ish one it costs three short launches.
  * Ragged reads (seeds->seed_intervals_dev): read_len is ignored, every read's length comes from its offsets. */
 #define NVBIO_FM_DEFER_HEAVY 64u
+/* The locus path.  Where the handle keeps seed locus lines for seeds->fixed_len (nvbio_fm_index_seed_locus) and read_len <= 193 (ragged
+ * reads: read by read), only a read's FIRST seed gathers its table entry at once; if it has exactly one hit over both strands, every
+ * other seed of the read is compared with the text on that hit's diagonal in the read's one locus line, and is settled without a table
+ * gather where the text equals it and u = 1 there -- which proves that the table would have answered with that one hit.  All other
+ * seeds gather and resolve as ever: same keys, residual and deferred entries, in the same order.
+ * NVBIO_FM_NO_SEED_LOCUS: the pass without that path (A/B measurements, tests).
+ * NVBIO_FM_COUNT_LOCUS (with NVBIO_FM_COUNT_SECTORS only): counts_dev has 10 words; words 6..9 = reads whose first seed placed them |
+ * seeds settled on the locus | seeds of such reads that gathered after all | seeds of the other reads (the last three over the seeds
+ * behind a read's first; all zero where the path is off).  The sectors of NVBIO_FM_COUNT_SECTORS count a read's locus line once. */
+#define NVBIO_FM_NO_SEED_LOCUS 128u
+#define NVBIO_FM_COUNT_LOCUS 4096u
 nvbio_status nvbio_fm_match_seed_diagonals_both_temp_bytes(const nvbio_string_set* seeds, uint64_t* bytes);
 nvbio_status nvbio_fm_match_seed_diagonals_both_keys_capacity(const nvbio_string_set* seeds, uint64_t* n_keys);
 nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nvbio_string_set* seeds, uint32_t flags, uint32_t read_len,

@@ -35,6 +35,8 @@ SCORE_MIN = -(1 << 30)
 FM_SCAN_FORWARD, FM_COMPLEMENT, FM_NO_KMER_TABLE, FM_NO_VERIFY, FM_COUNT_SECTORS, FM_NO_PIPELINE, FM_DEFER_HEAVY = 1, 2, 4, 8, 16, 32, 64
 FM_TABLE_NO_DIRECT, FM_TABLE_NO_CONTEXT, FM_TABLE_NO_GROUPS, FM_TABLE_CANONICAL, FM_TABLE_CANONICAL_WIDE = 1, 2, 4, 8, 16      # nvbio_fm_build_options::table_flags
 FM_TABLE_NO_TEXT_PLANES = 32
+FM_TABLE_NO_SEED_LOCUS = 64
+FM_NO_SEED_LOCUS, FM_COUNT_LOCUS = 128, 4096           # nvbio_fm_match_seed_diagonals_both: the pass without the locus path / its route counts
 READ_REVERSE, READ_COMPLEMENT = 1, 2
 TRACEBACK_SINKS_GIVEN = 1
 # nvbio_alignment_batch::algo_flags (which exact shortcuts / kernel variants a call may use; results do not depend on them)
@@ -44,6 +46,7 @@ ALN_NO_QUALITY_SHORTCUT, ALN_RAGGED_READS, ALN_NO_LENGTH_SORT, ALN_NO_F16_DP, AL
 ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE = 131072, 262144
 ALN_NO_NARROW_DP = 524288
 ALN_NO_TEXT_PLANES = 1048576
+SEED_NO_LOCUS = 2097152           # not an alignment flag: in SeedExtendParams.algo_flags it makes pipeline.seed_pass_begin pass FM_NO_SEED_LOCUS (A/B)
 ROUTE_SETTLED, ROUTE_FULL_BAND, ROUTE_CLASS_A, ROUTE_CLASS_B, ROUTE_REDONE = 0, 1, 2, 3, 8
 DEFAULT_ALGO_FLAGS = 0          # what an AlignmentBatch is created with unless told otherwise (tests set it for a whole run)
 BACKTRACK_REFERENCE_QUIRKS = 1
@@ -366,6 +369,23 @@ class FMIndex:
         _check(lib().nvbio_fm_index_text_planes(self._h, ctypes.byref(p), ctypes.byref(n)))
         return (p.value, n.value) if p.value else None
 
+    def seed_locus(self):
+        """nvbio_fm_index_seed_locus: (device pointer, seed length) of the seed locus lines the handle keeps -- what lets the two-strand seed
+        pass settle a read's other seeds once its first seed has placed it -- or None for a handle without them"""
+        p, n = ctypes.c_void_p(), ctypes.c_uint32()
+        _check(lib().nvbio_fm_index_seed_locus(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return (p.value, n.value) if p.value else None
+
+    def build_seed_locus(self, seed_len, out=None):
+        """out is None: nvbio_fm_index_build_seed_locus -- the handle builds its own lines, or rebuilds them for another seed length
+        (kmer_len .. kmer_len + 7; no seed pass of the handle may be in flight).  out: a 128-byte aligned uint8 tensor of
+        seed_locus_bytes(length) bytes -- nvbio_seed_locus_build fills it instead and the handle's own lines stay as they are; returns out"""
+        if out is None:
+            _check(lib().nvbio_fm_index_build_seed_locus(self._h, ctypes.c_uint32(seed_len), _stream_ptr(self.device)))
+            return None
+        _check(lib().nvbio_seed_locus_build(self._h, ctypes.c_uint32(seed_len), _ptr(out), _stream_ptr(self.device)))
+        return out
+
     def text_planes_of(self, text2, length):
         """text_planes()'s pointer if the handle was built from this very text -- the same device address and length -- else None
         (no call into the library: build() asked once)"""
@@ -455,7 +475,9 @@ class FMIndex:
     def match_seed_diagonals_both(self, seeds, read_len, buffers=None, flags=0, grid_blocks=0, inline_hits=0, defer_heavy=False):
         """the seed pass of BOTH strands in one launch over the canonical table (nvbio_fm_match_seed_diagonals_both) -> the buffers dict:
         "keys" int64 (the first counts[0]: both strands, tile by tile), "ranges" int32 [2 n, 2] / "ids" int32 [2 n]: residual seeds on
-        several rows, forward strand in [0, counts[1]), reverse strand in [n, n + counts[2]); "counts" int32 [6] on the device.
+        several rows, forward strand in [0, counts[1]), reverse strand in [n, n + counts[2]); "counts" int32 [10] on the device
+        ([4:6]: FM_COUNT_SECTORS' uint64, [6:10]: FM_COUNT_LOCUS' route counts).
+        flags: FM_NO_SEED_LOCUS runs the pass without the locus path (seed_locus(): same results either way).
         inline_hits (2..4): a search that ends on up to that many rows leaves all their keys in "keys" instead of a residual entry.
         "tile_offsets" int32 [n_tiles + 1]: tile t (the reads [t * reads_per_tile, (t + 1) * reads_per_tile)) owns keys[tile_offsets[t] :
         tile_offsets[t + 1]]; counts[3] = tile_offsets[n_tiles], the keys in tile order (deferred searches append theirs behind them)."""
@@ -471,7 +493,7 @@ class FMIndex:
             buffers["keys"] = torch.empty(max(int(cap.value), 1), dtype=torch.int64, device=self.device)
             buffers["ranges"] = torch.empty((2 * n, 2), dtype=torch.int32, device=self.device)
             buffers["ids"] = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-            buffers["counts"] = torch.empty(6, dtype=torch.int32, device=self.device)     # [4:6]: FM_COUNT_SECTORS' uint64
+            buffers["counts"] = torch.zeros(10, dtype=torch.int32, device=self.device)    # [4:6]: FM_COUNT_SECTORS' uint64, [6:10]: FM_COUNT_LOCUS
             nb = ctypes.c_uint64(0)
             _check(lib().nvbio_fm_match_seed_diagonals_both_temp_bytes(ctypes.byref(qs), ctypes.byref(nb)))
             buffers["temp"] = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
@@ -1196,6 +1218,13 @@ class AlignmentBatch:
                       _ptr(self.flags), _ptr(self.text), self.text_bits, _ptr(self.win_begin), _ptr(self.win_end),
                       self.n, self.max_read_len, self.algo_flags,
                       ctypes.c_void_p(self.text_planes.data_ptr() if hasattr(self.text_planes, "data_ptr") else self.text_planes))
+
+
+def seed_locus_bytes(length):
+    """nvbio_seed_locus_bytes: the size of the seed locus lines of a text (FMIndex.build_seed_locus(out=))"""
+    b = ctypes.c_uint64()
+    _check(lib().nvbio_seed_locus_bytes(ctypes.c_uint32(length), ctypes.byref(b)))
+    return b.value
 
 
 def text_planes_bytes(length):

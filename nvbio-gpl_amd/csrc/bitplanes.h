@@ -198,6 +198,49 @@ __device__ __forceinline__ void text_planes_units(const TextUnits<UNITS>& tu, co
     }
 }
 
+// ---- the seed locus lines (nvbio_seed_locus_build, fm_index.hip) ------------------------------------------------------------------
+// The text's bit planes once more, beside a uniqueness plane u for ONE seed length: u[x] = 1 only if text[x, x + len) occurs once in the
+// text, its reverse complement nowhere, and the canonical table answers both of them from its rows (fm_canon_inl.h: seed_locus_kernel).
+// A unit is 24 bytes, (lo64, hi64, u64) of 64 consecutive text symbols: lo64 / hi64 as in the planes above, bit j of u64 = u[64 unit + j].
+// Line L (128 bytes, 128-byte aligned) holds units 2 L .. 2 L + 4, i.e. symbols 128 L .. 128 L + 319, then 8 zero bytes; the array has
+// (n >> 7) + 1 lines and every bit at or beyond symbol n is zero.
+// Extent: a read placed at text position P0 lies in line P0 >> 7 from symbol offset P0 & 127 <= 127 on, so a read of M symbols ends at or
+// before offset 127 + M - 1 <= 319 for M <= 193: ONE line holds every seed window of the read.
+constexpr uint32_t SEED_LOCUS_LINE_BYTES = 128u;
+constexpr uint32_t SEED_LOCUS_UNITS      = 5u;                   // units of 64 symbols in a line
+constexpr uint32_t SEED_LOCUS_MAX_READ   = 193u;
+inline __host__ __device__ uint64_t seed_locus_lines(const uint32_t n) { return ((uint64_t)n >> 7) + 1u; }
+
+// the unit that holds symbol x of the read at `base` (x >= base, x + len - 1 <= base + SEED_LOCUS_MAX_READ - 1) and the planes of the next one
+struct LocusUnits { uint64_t lo0, hi0, u0, lo1, hi1; };
+
+__device__ __forceinline__ void load_locus_units(const void* __restrict__ lines, const uint32_t base, const uint32_t x, LocusUnits& out)
+{
+    static_assert( 127u + SEED_LOCUS_MAX_READ - 1u <= 64u * SEED_LOCUS_UNITS - 1u, "the last symbol of a read lies in the line its first symbol lies in" );
+    static_assert( 24u * SEED_LOCUS_UNITS <= SEED_LOCUS_LINE_BYTES, "a line holds its units" );
+    const uint32_t line = base >> 7, unit = (x - (line << 7)) >> 6;                      // unit <= 4
+    const uint64_t* __restrict__ p = (const uint64_t*)lines + (size_t)line * 16u;
+    const uint32_t next = unit + 1u < SEED_LOCUS_UNITS ? unit + 1u : unit;               // (a window that crosses into the next unit has one)
+    out.lo0 = p[3u * unit]; out.hi0 = p[3u * unit + 1u]; out.u0 = p[3u * unit + 2u];
+    out.lo1 = p[3u * next]; out.hi1 = p[3u * next + 1u];
+}
+
+// every 2nd bit of v (positions 0, 2, .., 62) squeezed into 32 bits
+__device__ __forceinline__ uint64_t squeeze2_64(const uint64_t v)
+{
+    return (uint64_t)squeeze2( (uint32_t)v ) | ((uint64_t)squeeze2( (uint32_t)(v >> 32) ) << 16);
+}
+
+// does text[x, x + len) equal the len <= 32 symbols T (symbol t at bits [2 t, +2)), with u[x] set?
+__device__ __forceinline__ bool locus_answers(const LocusUnits& lu, const uint32_t x, const uint32_t len, const uint64_t T)
+{
+    const uint32_t s = x & 63u;
+    const uint64_t lo = s ? (lu.lo0 >> s) | (lu.lo1 << (64u - s)) : lu.lo0;
+    const uint64_t hi = s ? (lu.hi0 >> s) | (lu.hi1 << (64u - s)) : lu.hi0;
+    const uint64_t mask = (1ull << len) - 1ull;
+    return ((((lo ^ squeeze2_64( T )) | (hi ^ squeeze2_64( T >> 1 ))) & mask) == 0ull) && ((lu.u0 >> s) & 1ull);
+}
+
 // 224 plane bits (14 packed words), shifted so that bit 0 = window symbol 0
 template <typename W>
 __device__ __forceinline__ void text_planes224(const W& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])

@@ -223,6 +223,207 @@ static nvbio_status build_canonical_table(FMIndexImpl* idx, const uint32_t k, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// a window against the rows of its entry.  The window is V, its len symbols with symbol t at bits [2 t, +2) (seed_bits_from_words, fwd =
+// false); qo = 1 if the table holds the reverse complement of its last k symbols; want = its first r = len - k symbols as a flank.
+// ---------------------------------------------------------------------------------------------
+// is row (P, C) a hit?  rev: of the reverse strand; v: where the window (rev: its reverse complement) begins in the text
+__device__ __forceinline__ bool canon_row_hit(const uint32_t P, const uint32_t C, const uint32_t qo, const uint32_t want, const uint32_t fshift,
+                                              const uint32_t r, const uint32_t len, const uint32_t length, bool& rev, uint32_t& v)
+{
+    const uint32_t pay = C - DTAB_MARK;
+    const uint32_t o = (pay >> 28) & 1u;
+    const uint32_t flank = qo ? (pay & 0x3FFFu) : ((pay >> 14) & 0x3FFFu);
+    if ((flank >> fshift) != want) return false;
+    rev = (o ^ qo) != 0u;
+    if (rev ? ((uint64_t)P + len > length) : (P < r)) return false;
+    v = rev ? P : P - r;
+    return true;
+}
+
+__device__ __forceinline__ uint4 canon_entry(const DevIndex& f, const uint64_t V, const uint32_t len, const bool wide, uint32_t& qo)
+{
+    const uint32_t k = f.ckmer;
+    const uint64_t key = V >> (2u * (len - k));
+    qo = (uint32_t)(key >> k) & 1u;
+    const uint64_t idx = canon_index( qo ? canon_revcomp( key, k ) : key, k );
+    if (wide) return ((const uint4*)f.ctab)[idx];
+    const uint2 e = f.ctab[idx];
+    return make_uint4( e.x, e.y, 0u, 0u );
+}
+
+// The hits of a window among the rows of its entry e, the group gathered here: nf on the forward strand (the last one at vf), nr on the
+// reverse strand (at vr).  false: the table does not answer (more than 8 occurrences).  The counting form of fm_seed_both_kernel's stage 3,
+// for the two places that only ask "exactly one hit, and where": the builder of the locus lines and the anchor of a read.
+struct CanonHits { uint32_t nf, nr, vf, vr; };
+__device__ __forceinline__ bool canon_lookup(const DevIndex& f, const uint64_t V, const uint32_t len, const uint32_t qo, const uint4 e, CanonHits& h)
+{
+    const uint32_t r = len - f.ckmer, rmask = (1u << (2u * r)) - 1u, fshift = 2u * (CTAB_FLANK - r);
+    h.nf = h.nr = h.vf = h.vr = 0u;
+    if (e.y < DTAB_MARK) return e.x > e.y;
+    const uint32_t rest = (uint32_t)V & rmask, want = qo ? (~rest & rmask) : rest;
+    auto row = [&](const uint32_t P, const uint32_t C) {
+        bool rev; uint32_t v;
+        if (!canon_row_hit( P, C, qo, want, fshift, r, len, f.length, rev, v )) return;
+        h.nr += rev ? 1u : 0u; h.vr = rev ? v : h.vr;                    // (selects between registers: a store through a chosen
+        h.nf += rev ? 0u : 1u; h.vf = rev ? h.vf : v;                    // address would put the struct into scratch)
+    };
+    if (e.x < DTAB_MARK) { row( e.x, e.y ); if (e.w >= DTAB_MARK) row( e.z, e.w ); }
+    else
+    {
+        const uint32_t m = e.y - DTAB_MARK;
+        const uint4* g4 = (const uint4*)(f.cside + 4ull * (e.x - DTAB_MARK));
+        #pragma unroll
+        for (uint32_t t = 0; t < CTAB_ROWS_MAX; t += 2u)
+            if (t < m) { const uint4 g = g4[t >> 1]; row( g.x, g.y ); if (t + 1u < m) row( g.z, g.w ); }
+    }
+    return true;
+}
+
+// The locus lines (bitplanes.h: the layout) for seeds of len symbols: one wave per unit of 64 text positions.  u[x] = 1 iff the table,
+// asked as the seed pass asks it, answers the window T = text[x, x + len) with exactly the forward hit x and no reverse hit, AND answers
+// rc(T) with exactly the reverse hit x and no forward hit.  The two lookups read different entries -- T's is that of its last k symbols,
+// rc(T)'s that of T's first k -- and a lane of the seed pass holds T when its read lies on the forward strand and rc(T) when it lies on the
+// reverse strand: either one with more than 8 occurrences sends the lane to the ordinary search (deferred: another key order), so
+// neither may.  Rows are exact (k-mer + flank = the whole window), so u[x] = 1 implies occ(T) + occ(rc(T)) = 1, and the two agree
+// wherever neither k-mer is heavy.
+__global__ void __launch_bounds__(256)
+seed_locus_kernel(const DevIndex f, const uint32_t len, const uint32_t wide, const uint64_t n_units, const uint64_t n_lines, uint64_t* __restrict__ lines)
+{
+    const uint32_t lane = threadIdx.x & 63u, n = f.length;
+    for (uint64_t unit = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); unit < n_units; unit += (uint64_t)gridDim.x * 4u)
+    {
+        const uint64_t x64 = unit * 64u + lane;
+        const uint32_t sym = x64 < n ? text_symbol( f.text, (uint32_t)x64 ) : 0u;
+        bool uq = false;
+        if (x64 + len <= n)
+        {
+            const uint32_t x = (uint32_t)x64;
+            uint64_t V; uint32_t qo; CanonHits h;
+            (void)seed_bits_from_words<2>( load_seed_words<2>( f.text, x, len ), x, len, false, false, V );
+            uint4 e = canon_entry( f, V, len, wide != 0u, qo );
+            uq = canon_lookup( f, V, len, qo, e, h ) && h.nf == 1u && h.nr == 0u && h.vf == x;
+            if (uq)
+            {
+                const uint64_t R = canon_revcomp( V, len );
+                e  = canon_entry( f, R, len, wide != 0u, qo );
+                uq = canon_lookup( f, R, len, qo, e, h ) && h.nf == 0u && h.nr == 1u && h.vr == x;
+            }
+        }
+        const uint64_t ub = __ballot( uq ), lo = __ballot( (sym & 1u) != 0u ), hi = __ballot( (sym & 2u) != 0u );
+        // unit U is slot U - 2 L of the lines L = U / 2, U / 2 - 1 and (U even) U / 2 - 2: slots U & 1, + 2, + 4
+        if (lane < 3u && (unit >> 1) >= lane)
+        {
+            const uint64_t L = (unit >> 1) - lane, slot = unit - 2u * L;
+            if (L < n_lines && slot < SEED_LOCUS_UNITS) { uint64_t* p = lines + L * 16u + 3u * slot; p[0] = lo; p[1] = hi; p[2] = ub; }
+        }
+    }
+}
+
+// The tile loop of fm_seed_both_kernel<.., LOCUS = true> (see there: the path, why its keys are the same, the pipeline).  seed_geom, entry_of
+// and resolve_tile are the kernel's own; a stage whose tile does not exist carries lanes without a seed, which load and write nothing.
+template <int BITS, bool COUNT, bool WIDE, typename Geom, typename Entry, typename Resolve>
+__device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const StringSetDev& q, const SeedTiles& tl, const void* __restrict__ locus,
+                                                   unsigned long long* __restrict__ sectors_out, unsigned int* __restrict__ routes, const uint32_t tile0,
+                                                   const uint32_t lane, const uint32_t lr, const uint32_t j, const bool lane_ok,
+                                                   const Geom& seed_geom, const Entry& entry_of, const Resolve& resolve_tile)
+{
+    const uint32_t n_waves = gridDim.x * 4u;
+    const uint32_t k = f.ckmer, len = q.fixed_len, n = f.length;
+    const uint32_t anchor = lane - j;                                        // the lane of this read's first seed
+    const uint4 none = make_uint4( 1u, 0u, 0u, 0u );                         // the entry of a k-mer without occurrences
+    auto qo_of = [&](const uint64_t V) -> uint32_t { return (uint32_t)(V >> (2u * (len - k) + k)) & 1u; };
+    auto add = [&](unsigned int* word, const bool on) {                      // (COUNT) one atomic per wave
+        const uint32_t c = (uint32_t)__popcll( __ballot( on ) );
+        if (lane == 0 && c) atomicAdd( word, c );
+    };
+    // per stage: seed bits V, entry e (none: not gathered), has a seed / the seed is clean (no N), its offset in the read, the read's length
+    SeedWords W = { 0, 0, 0, 0, 0 }; uint32_t w_begin = 0, w_pfw = 0, w_rlen = 0; bool w_seed = false;        // words of tile t+3, loaded
+    uint64_t aV = 0; uint4 ae = none; bool a_seed = false, a_ok = false; uint32_t a_pfw = 0, a_rlen = 0;      // tile t+2: the anchors' entries loaded
+    uint64_t lV = 0; uint4 le = none; bool l_seed = false, l_ok = false; uint32_t l_pfw = 0, l_rlen = 0;      // tile t+1: the locus units loaded
+    bool l_asked = false, l_usable = false; uint32_t l_x = 0, l_strand = 0; LocusUnits LU = { 0, 0, 0, 0, 0 };
+    uint64_t cV = 0; uint4 ce = none; bool c_seed = false, c_ok = false; uint32_t c_pfw = 0, c_rlen = 0;      // tile t: the remaining entries loaded
+    uint32_t c_settled = 0, c_x = 0;
+    for (uint32_t step = 0; ; ++step)
+    {
+        const uint64_t t4 = (uint64_t)tile0 + (uint64_t)step * n_waves;                  // the tile whose words this iteration loads
+        if (step >= 4u && t4 - 4ull * n_waves >= tl.n_tiles) break;
+        // ---- tile t+1: the lane's window against the locus ----
+        uint32_t settled = 0;
+        if (l_asked && locus_answers( LU, l_x, len, l_strand ? canon_revcomp( lV, len ) : lV )) settled = 1u + l_strand;
+        if (COUNT && routes)
+        {
+            add( routes + 1, settled != 0u );
+            add( routes + 2, l_seed && j != 0u && l_usable && !settled );
+            add( routes + 3, l_seed && j != 0u && !l_usable );
+        }
+        // ---- tile t+2: the anchor placed (its group, if its entry points to one, is gathered here), told to the lanes of its read ----
+        uint32_t a_hit = 0xFFFFFFFFu, a_strand = 0;
+        if (j == 0u && a_ok)
+        {
+            CanonHits h;
+            if (canon_lookup( f, aV, len, qo_of( aV ), ae, h ) && h.nf + h.nr == 1u) { a_strand = h.nr; a_hit = h.nr ? h.vr : h.vf; }
+        }
+        const uint32_t r_hit = (uint32_t)__shfl( (int)a_hit, (int)anchor ), r_strand = (uint32_t)__shfl( (int)a_strand, (int)anchor );
+        const bool usable = r_hit != 0xFFFFFFFFu;
+        bool ask = false; uint32_t x = 0, base = 0;                                      // the window's place on the anchor's diagonal; where the read begins
+        if (usable && j != 0u && a_ok && a_rlen <= SEED_LOCUS_MAX_READ)
+        {
+            if (r_strand == 0u) { base = r_hit; x = r_hit + a_pfw; ask = (uint64_t)r_hit + a_pfw + len <= n; }
+            else
+            {
+                const uint32_t span = a_rlen - len;                                      // (a lane with a seed: a_pfw + len <= a_rlen)
+                base = r_hit >= span ? r_hit - span : 0u; x = r_hit - a_pfw; ask = r_hit >= a_pfw;
+            }
+        }
+        if (COUNT)
+        {
+            if (routes) add( routes, j == 0u && usable );
+            // the read's locus line, once, in its anchor's lane
+            const uint64_t asked = __ballot( ask );
+            const uint64_t mine = (q.spr >= 64u ? ~0ull : ((1ull << q.spr) - 1ull)) << anchor;
+            const uint32_t c = (uint32_t)__popcll( __ballot( j == 0u && (asked & mine) != 0ull ) );
+            if (lane == 0 && c) atomicAdd( sectors_out, (unsigned long long)c );
+        }
+        // ---- tile t+3: the seed bits ----
+        uint64_t nV = 0; bool n_ok = false;
+        const bool n_seed = w_seed; const uint32_t n_pfw = w_pfw, n_rlen = w_rlen;
+        if (w_seed) n_ok = seed_bits_from_words<BITS>( W, w_begin, len, false, false, nV );
+        // ---- the loads of every stage: groups of t | remaining entries of t+1 | locus units of t+2 | anchor entries of t+3 | words of t+4 ----
+        const bool is_one   = c_ok && ce.y >= DTAB_MARK && ce.x < DTAB_MARK;
+        const bool is_group = c_ok && ce.y >= DTAB_MARK && ce.x >= DTAB_MARK;
+        const bool is_heavy = c_ok && ce.y < DTAB_MARK && ce.x <= ce.y;
+        uint4 q0 = make_uint4( 0, 0, 0, 0 ), q1 = q0, q2 = q0, q3 = q0;
+        if (is_group)
+        {
+            const uint4* g4 = (const uint4*)(f.cside + 4ull * (ce.x - DTAB_MARK));
+            q0 = g4[0]; q1 = g4[1];
+            if (ce.y - DTAB_MARK > 4u) { q2 = g4[2]; q3 = g4[3]; }
+        }
+        uint4 fe = (j == 0u) ? le : none;
+        if (l_ok && j != 0u && !settled) { uint32_t qo; fe = entry_of( lV, qo ); }
+        LocusUnits nLU = { 0, 0, 0, 0, 0 };
+        if (ask) load_locus_units( locus, base, x, nLU );
+        uint4 ne = none;
+        if (j == 0u && n_ok) { uint32_t qo; ne = entry_of( nV, qo ); }
+        {
+            const uint64_t rid4 = t4 * tl.rpt + lr;
+            w_seed = t4 < tl.n_tiles && lane_ok && rid4 < tl.reads;
+            if (w_seed) w_seed = seed_geom( (uint32_t)rid4, w_begin, w_pfw, w_rlen );
+            if (w_seed) W = load_seed_words<BITS>( q.symbols, w_begin, len );
+        }
+        // ---- tile t resolved ----
+        if (step >= 4u)
+        {
+            const uint32_t tile = (uint32_t)(t4 - 4ull * n_waves), rid = tile * tl.rpt + lr;
+            resolve_tile( tile, rid, c_seed, cV, ce, c_ok, qo_of( cV ), c_pfw, c_rlen, is_one, is_group, is_heavy, q0, q1, q2, q3, c_settled, c_x );
+        }
+        cV = lV; ce = fe; c_seed = l_seed; c_ok = l_ok; c_pfw = l_pfw; c_rlen = l_rlen; c_settled = settled; c_x = l_x;
+        lV = aV; le = ae; l_seed = a_seed; l_ok = a_ok; l_pfw = a_pfw; l_rlen = a_rlen; l_asked = ask; l_usable = usable; l_x = x; l_strand = r_strand; LU = nLU;
+        aV = nV; ae = ne; a_seed = n_seed; a_ok = n_ok; a_pfw = n_pfw; a_rlen = n_rlen;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // the seed pass of both strands: one wave per tile of whole reads, software-pipelined over the tiles a wave owns as
 // fm_seed_pipe_kernel (words of tile t+2 | table entry of tile t+1 | resolution of tile t).  A tile has 128 key slots: the keys of the
 // forward strand (at most 64), those of the reverse strand right behind them; tile_counts[tile] = both.  Seeds whose k-mer has more than
@@ -237,12 +438,29 @@ static nvbio_status build_canonical_table(FMIndexImpl* idx, const uint32_t k, co
 //   j x interval + len fits the read; q.spr is the largest seed count of a read (the stride of seed ids).
 // ---------------------------------------------------------------------------------------------
 // WIDE: 16-byte entries (NVBIO_FM_TABLE_CANONICAL_WIDE): a k-mer with TWO occurrences has both rows in its entry, groups start at three
-template <int BITS, bool COUNT, bool WIDE, bool DEFER>
+//
+// LOCUS (the handle's locus lines, bitplanes.h, built for this seed length): a read's first seed -- its anchor, lane j = 0 -- is looked up
+// as ever.  If it has exactly one hit over both strands, that hit places the whole read, and lane j's window would lie at
+// x_j = v + p_j (forward strand) or v - p_j (reverse strand; p_j: the seed's offset in the read).  The lane then reads text[x_j, x_j + len)
+// and u[x_j] from the read's ONE locus line instead of gathering a table line of its own, and is settled if the text equals its seed S_j
+// (reverse strand: rc(S_j)) and u[x_j] = 1.  Why the keys are the same: let T = text[x_j, x_j + len) with u[x_j] = 1.  By the builder's
+// test (seed_locus_kernel) the table answers T with the forward hit x_j alone and rc(T) with the reverse hit x_j alone, neither through a
+// heavy entry.  A forward lane holds S_j = T, a reverse lane S_j = rc(T): the table gather it skips would have left exactly hits[strand] = 1,
+// pos[strand][0] = x_j and nothing on the other strand, which is what the lane sets.  Every other lane -- text differs, u = 0, x_j outside
+// [0, n - len], no usable anchor, a read longer than SEED_LOCUS_MAX_READ -- gathers its entry and resolves it as without LOCUS, and the
+// emission sees the same hits and positions either way.
+// Pipeline with LOCUS: words of tile t+4 | anchor entries of t+3 | locus units of t+2 | the remaining entries of t+1 | groups and resolution
+// of t.  Each iteration first computes on what the last one loaded (locus test of t+1, anchor of t+2, seed bits of t+3), then issues the
+// loads of all five stages, then resolves tile t.  An anchor whose entry points to a group gathers it while it computes: the one
+// dependent gather outside the schedule, in the iterations where one of the wave's anchors has a k-mer with 3..8 occurrences.
+// routes (COUNT, NVBIO_FM_COUNT_LOCUS): reads with a usable anchor | windows settled on the locus | windows of such reads that gathered
+// after all | windows of reads without a usable anchor -- the last three over the windows behind the anchor (j > 0).
+template <int BITS, bool COUNT, bool WIDE, bool DEFER, bool LOCUS>
 __global__ void __launch_bounds__(256)
 fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, const uint32_t read_len, const uint32_t inline_max,
                     uint64_t* __restrict__ tile_keys, uint32_t* __restrict__ tile_counts, uint2* __restrict__ res_ranges,
                     uint32_t* __restrict__ res_ids, const uint32_t res_cap, unsigned int* __restrict__ counts, unsigned long long* __restrict__ sectors_out,
-                    uint32_t* __restrict__ tile_defer, uint32_t* __restrict__ defer_counts)
+                    uint32_t* __restrict__ tile_defer, uint32_t* __restrict__ defer_counts, const void* __restrict__ locus, unsigned int* __restrict__ routes)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_waves = gridDim.x * 4u;
@@ -276,76 +494,20 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
         return make_uint4( e.x, e.y, 0u, 0u );
     };
 
-    uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (tile >= tl.n_tiles) return;
-    // stage 1 -> 2 (the tile after the current one): packed words, where they begin, the seed's offset in its read, the read's length
-    SeedWords W = { 0, 0, 0, 0, 0 }; uint32_t w_begin = 0, w_pfw = 0, w_rlen = 0; bool w_valid = false;
-    // stage 2 -> 3 (the current tile): seed bits, table entry, orientation
-    uint64_t V = 0; uint4 e = make_uint4( 1u, 0u, 0u, 0u ); bool e_valid = false; uint32_t qo = 0, c_pfw = 0, c_rlen = 0; bool c_seed = false;
+    // ---- stage 3b: a tile resolved -- the rows of every lane's entry e (q0 .. q3: its group) into hits, the hits into keys, residual and
+    // deferred entries.  settled (LOCUS): 1 + strand of the one hit, at settled_x, of a lane answered from the locus (its e is empty)
+    auto resolve_tile = [&](const uint32_t tile, const uint32_t rid, const bool valid, const uint64_t V, const uint4 e, const bool e_valid, const uint32_t qo,
+                            const uint32_t c_pfw, const uint32_t c_rlen, const bool is_one, const bool is_group, const bool is_heavy,
+                            const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const uint32_t settled, const uint32_t settled_x)
     {
-        const uint32_t rid = tile * tl.rpt + lr;
-        if (lane_ok && rid < tl.reads)
-        {
-            uint32_t b0;
-            c_seed = seed_geom( rid, b0, c_pfw, c_rlen );
-            if (c_seed)
-            {
-                const SeedWords W0 = load_seed_words<BITS>( q.symbols, b0, len );
-                e_valid = seed_bits_from_words<BITS>( W0, b0, len, false, false, V );
-                if (e_valid) e = entry_of( V, qo );
-            }
-        }
-        const uint32_t t1 = tile + n_waves, rid1 = t1 * tl.rpt + lr;
-        if (t1 < tl.n_tiles && lane_ok && rid1 < tl.reads)
-        {
-            w_valid = seed_geom( rid1, w_begin, w_pfw, w_rlen );
-            if (w_valid) W = load_seed_words<BITS>( q.symbols, w_begin, len );
-        }
-    }
-    for (; tile < tl.n_tiles; tile += n_waves)
-    {
-        const uint32_t rid = tile * tl.rpt + lr;
-        const bool valid = lane_ok && rid < tl.reads && c_seed;
-        // ---- stage 3a: the kind of entry; the group of a k-mer with 2..8 occurrences is requested ----
-        const bool is_one   = e_valid && e.y >= DTAB_MARK && e.x < DTAB_MARK;
-        const bool is_group = e_valid && e.y >= DTAB_MARK && e.x >= DTAB_MARK;
-        const bool is_heavy = e_valid && e.y < DTAB_MARK && e.x <= e.y;
-        uint4 q0 = make_uint4( 0, 0, 0, 0 ), q1 = q0, q2 = q0, q3 = q0;
         const uint32_t m = e.y - DTAB_MARK;
-        if (is_group)
-        {
-            const uint4* g4 = (const uint4*)(f.cside + 4ull * (e.x - DTAB_MARK));
-            q0 = g4[0]; q1 = g4[1];
-            if (m > 4u) { q2 = g4[2]; q3 = g4[3]; }
-        }
-        // ---- stage 2 for the next tile ----
-        uint64_t Vn = 0; uint4 en = make_uint4( 1u, 0u, 0u, 0u ); bool en_valid = false; uint32_t qon = 0;
-        const uint32_t n_pfw = w_pfw, n_rlen = w_rlen; const bool n_seed = w_valid;
-        if (w_valid)
-        {
-            en_valid = seed_bits_from_words<BITS>( W, w_begin, len, false, false, Vn );
-            if (en_valid) en = entry_of( Vn, qon );
-        }
-        // ---- stage 1 for the tile after next ----
-        {
-            const uint32_t t2 = tile + 2u * n_waves, rid2 = t2 * tl.rpt + lr;
-            w_valid = t2 < tl.n_tiles && lane_ok && rid2 < tl.reads;
-            if (w_valid) w_valid = seed_geom( rid2, w_begin, w_pfw, w_rlen );
-            if (w_valid) W = load_seed_words<BITS>( q.symbols, w_begin, len );
-        }
-        // ---- stage 3b: resolve the current tile ----
         const uint32_t rest = (uint32_t)V & rmask;                           // the seed's first r symbols, reversed (scan order)
         const uint32_t want = qo ? (~rest & rmask) : rest;
         // per strand: the hits found among the entry's rows (the first CTAB_INLINE positions are kept)
         uint32_t hits[2] = { 0, 0 }, pos[2][CTAB_INLINE] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
         auto row = [&](const uint32_t P, const uint32_t C) {
-            const uint32_t pay = C - DTAB_MARK;
-            const uint32_t o = (pay >> 28) & 1u;
-            const uint32_t flank = qo ? (pay & 0x3FFFu) : ((pay >> 14) & 0x3FFFu);
-            if ((flank >> fshift) != want) return;
-            const bool rev = (o ^ qo) != 0u;
-            if (rev ? ((uint64_t)P + len > f.length) : (P < r)) return;
-            const uint32_t v = rev ? P : P - r;
+            bool rev; uint32_t v;
+            if (!canon_row_hit( P, C, qo, want, fshift, r, len, f.length, rev, v )) return;
             #pragma unroll
             for (int s = 0; s < 2; ++s)
                 if ((s == 1) == rev)
@@ -363,7 +525,12 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
             NVB_CROW( 4u, q2.x, q2.y ) NVB_CROW( 5u, q2.z, q2.w ) NVB_CROW( 6u, q3.x, q3.y ) NVB_CROW( 7u, q3.z, q3.w )
 #undef NVB_CROW
         }
-        uint32_t sectors = e_valid ? (is_group ? 2u : 1u) : 0u;
+        if (LOCUS && settled)
+        {
+            hits[0] = settled == 1u; hits[1] = settled == 2u;
+            pos[0][0] = pos[1][0] = settled_x;
+        }
+        uint32_t sectors = (e_valid && !(LOCUS && settled)) ? (is_group ? 2u : 1u) : 0u;
         const uint32_t i = rid * q.spr + j;
         uint32_t tile_fill = 0;                                              // keys of this tile written so far: the reverse strand's follow the forward strand's
         uint32_t defer_fill = 0;                                             // deferred searches of this tile recorded so far (DEFER)
@@ -445,6 +612,72 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
             for (int d = 32; d > 0; d >>= 1) tot += (uint32_t)__shfl_xor( (int)tot, d );
             if (lane == 0 && tot) atomicAdd( sectors_out, (unsigned long long)tot );
         }
+    };
+
+    uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= tl.n_tiles) return;
+    if constexpr (LOCUS)
+    {
+        fm_seed_locus_loop<BITS,COUNT,WIDE>( f, q, tl, locus, sectors_out, routes, tile, lane, lr, j, lane_ok, seed_geom, entry_of, resolve_tile );
+        return;
+    }
+    // stage 1 -> 2 (the tile after the current one): packed words, where they begin, the seed's offset in its read, the read's length
+    SeedWords W = { 0, 0, 0, 0, 0 }; uint32_t w_begin = 0, w_pfw = 0, w_rlen = 0; bool w_valid = false;
+    // stage 2 -> 3 (the current tile): seed bits, table entry, orientation
+    uint64_t V = 0; uint4 e = make_uint4( 1u, 0u, 0u, 0u ); bool e_valid = false; uint32_t qo = 0, c_pfw = 0, c_rlen = 0; bool c_seed = false;
+    {
+        const uint32_t rid = tile * tl.rpt + lr;
+        if (lane_ok && rid < tl.reads)
+        {
+            uint32_t b0;
+            c_seed = seed_geom( rid, b0, c_pfw, c_rlen );
+            if (c_seed)
+            {
+                const SeedWords W0 = load_seed_words<BITS>( q.symbols, b0, len );
+                e_valid = seed_bits_from_words<BITS>( W0, b0, len, false, false, V );
+                if (e_valid) e = entry_of( V, qo );
+            }
+        }
+        const uint32_t t1 = tile + n_waves, rid1 = t1 * tl.rpt + lr;
+        if (t1 < tl.n_tiles && lane_ok && rid1 < tl.reads)
+        {
+            w_valid = seed_geom( rid1, w_begin, w_pfw, w_rlen );
+            if (w_valid) W = load_seed_words<BITS>( q.symbols, w_begin, len );
+        }
+    }
+    for (; tile < tl.n_tiles; tile += n_waves)
+    {
+        const uint32_t rid = tile * tl.rpt + lr;
+        const bool valid = lane_ok && rid < tl.reads && c_seed;
+        // ---- stage 3a: the kind of entry; the group of a k-mer with 2..8 occurrences is requested ----
+        const bool is_one   = e_valid && e.y >= DTAB_MARK && e.x < DTAB_MARK;
+        const bool is_group = e_valid && e.y >= DTAB_MARK && e.x >= DTAB_MARK;
+        const bool is_heavy = e_valid && e.y < DTAB_MARK && e.x <= e.y;
+        uint4 q0 = make_uint4( 0, 0, 0, 0 ), q1 = q0, q2 = q0, q3 = q0;
+        const uint32_t m = e.y - DTAB_MARK;
+        if (is_group)
+        {
+            const uint4* g4 = (const uint4*)(f.cside + 4ull * (e.x - DTAB_MARK));
+            q0 = g4[0]; q1 = g4[1];
+            if (m > 4u) { q2 = g4[2]; q3 = g4[3]; }
+        }
+        // ---- stage 2 for the next tile ----
+        uint64_t Vn = 0; uint4 en = make_uint4( 1u, 0u, 0u, 0u ); bool en_valid = false; uint32_t qon = 0;
+        const uint32_t n_pfw = w_pfw, n_rlen = w_rlen; const bool n_seed = w_valid;
+        if (w_valid)
+        {
+            en_valid = seed_bits_from_words<BITS>( W, w_begin, len, false, false, Vn );
+            if (en_valid) en = entry_of( Vn, qon );
+        }
+        // ---- stage 1 for the tile after next ----
+        {
+            const uint32_t t2 = tile + 2u * n_waves, rid2 = t2 * tl.rpt + lr;
+            w_valid = t2 < tl.n_tiles && lane_ok && rid2 < tl.reads;
+            if (w_valid) w_valid = seed_geom( rid2, w_begin, w_pfw, w_rlen );
+            if (w_valid) W = load_seed_words<BITS>( q.symbols, w_begin, len );
+        }
+        // ---- stage 3b: resolve the current tile ----
+        resolve_tile( tile, rid, valid, V, e, e_valid, qo, c_pfw, c_rlen, is_one, is_group, is_heavy, q0, q1, q2, q3, 0u, 0u );
         V = Vn; e = en; e_valid = en_valid; qo = qon; c_pfw = n_pfw; c_rlen = n_rlen; c_seed = n_seed;
     }
 }

@@ -18,6 +18,7 @@
 #include "fm_device.h"
 #include "fm_seed_device.h"
 #include "seed_hits_device.h"
+#include "bitplanes.h"
 #include <hipcub/hipcub.hpp>
 #include <new>
 #include <stdlib.h>
@@ -47,6 +48,8 @@ struct FMIndexImpl
     uint32_t*            isa;         // owned, optional (verify mode)
     uint32_t*            text;        // owned, optional (verify mode)
     void*                planes;      // owned, optional: the text as bit planes (nvbio_text_planes_build), for the alignment batches
+    void*                locus;       // owned, optional: the seed locus lines (bitplanes.h) for seeds of locus_len symbols, for the two-strand seed pass
+    uint32_t             locus_len;
 
     DevIndex dev() const
     {
@@ -1264,6 +1267,54 @@ static nvbio_status build_kmer_table(FMIndexImpl* idx, uint32_t k, hipStream_t s
     return NVBIO_OK;
 }
 
+// ---- the seed locus lines (bitplanes.h: the layout; fm_canon_inl.h: seed_locus_kernel) ----
+constexpr uint32_t SEED_LOCUS_DEFAULT_LEN = 22u;                 // the seed length a handle builds them for on its own
+
+static nvbio_status seed_locus_served(const FMIndexImpl* idx, const uint32_t seed_len)
+{
+    if (!(idx->ctab && idx->text))
+    {
+        set_error( "the seed locus lines need the canonical table and the text: build the index with NVBIO_FM_TABLE_CANONICAL and sa_int = 1" );
+        return NVBIO_ERR_UNSUPPORTED;
+    }
+    NVB_REQUIRE( seed_len >= idx->ckmer && seed_len - idx->ckmer <= CTAB_FLANK, "seed length outside [kmer_len, kmer_len + 7]" );
+    return NVBIO_OK;
+}
+
+static nvbio_status seed_locus_fill(const FMIndexImpl* idx, const uint32_t seed_len, void* lines_dev, hipStream_t stream)
+{
+    NVB_CHECK( seed_locus_served( idx, seed_len ) );
+    NVB_REQUIRE( ((uintptr_t)lines_dev & (SEED_LOCUS_LINE_BYTES - 1u)) == 0, "lines_dev must be 128-byte aligned" );
+    const uint32_t n = idx->view.length;
+    const uint64_t n_lines = seed_locus_lines( n ), n_units = ((uint64_t)n + 63u) >> 6;
+    NVB_HIP( hipMemsetAsync( lines_dev, 0, n_lines * SEED_LOCUS_LINE_BYTES, stream ) );      // the pad words and the units past the text
+    const uint64_t blocks = (n_units + 3u) / 4u;
+    return NVB_LAUNCH( seed_locus_kernel, dim3( (unsigned)(blocks < 256u * 256u ? blocks : 256u * 256u) ), dim3(256), stream, idx->dev(), seed_len, idx->cwide,
+                       n_units, n_lines, (uint64_t*)lines_dev );
+}
+
+// build (or rebuild, for another seed length) the lines the handle owns
+static nvbio_status handle_seed_locus(FMIndexImpl* idx, const uint32_t seed_len, hipStream_t stream)
+{
+    NVB_CHECK( seed_locus_served( idx, seed_len ) );
+    const uint64_t bytes = seed_locus_lines( idx->view.length ) * SEED_LOCUS_LINE_BYTES;
+    if (!idx->locus)
+    {
+        if (hipMalloc( &idx->locus, bytes ) != hipSuccess)
+        {
+            (void)hipGetLastError(); idx->locus = nullptr;
+            set_error( "out of device memory (seed locus lines, %llu bytes)", (unsigned long long)bytes );
+            return NVBIO_ERR_NOMEM;
+        }
+        idx->owned_bytes += bytes;
+    }
+    idx->locus_len = 0;
+    NVB_CHECK( seed_locus_fill( idx, seed_len, idx->locus, stream ) );
+    if (hipStreamSynchronize( stream ) != hipSuccess) { set_error( "seed locus build failed" ); return NVBIO_ERR_HIP; }
+    idx->locus_len = seed_len;
+    return NVBIO_OK;
+}
+
 nvbio_status fm_index_adopt(const nvbio_fm_index_view* view, int device, uint32_t kmer_len, bool owns, hipStream_t stream, nvbio_fm_index_t* out,
                             uint32_t* isa, uint32_t* text, uint32_t table_flags)
 {
@@ -1277,7 +1328,7 @@ nvbio_status fm_index_adopt(const nvbio_fm_index_view* view, int device, uint32_
     idx->isa = isa; idx->text = text;
     if (isa)  idx->owned_bytes += ((uint64_t)view->length + 1u) * 4ull;
     if (text) idx->owned_bytes += (((uint64_t)view->length + 15u) / 16u) * 4ull;
-    idx->planes = nullptr;
+    idx->planes = nullptr; idx->locus = nullptr; idx->locus_len = 0;
     nvbio_status st = build_kmer_table( idx, kmer_len, stream );
     const bool tables = st == NVBIO_OK;                         // (a failed table build has released its own)
     if (st == NVBIO_OK && text && !(table_flags & NVBIO_FM_TABLE_NO_TEXT_PLANES))
@@ -1290,9 +1341,14 @@ nvbio_status fm_index_adopt(const nvbio_fm_index_view* view, int device, uint32_
         if (st == NVBIO_OK && hipStreamSynchronize( stream ) != hipSuccess) { set_error( "text planes build failed" ); st = NVBIO_ERR_HIP; }
         if (st == NVBIO_OK) idx->owned_bytes += bytes;
     }
+    // the locus lines of the two-strand seed pass, for the seed length it is run with by default
+    if (st == NVBIO_OK && idx->ctab && text && !(table_flags & NVBIO_FM_TABLE_NO_SEED_LOCUS) &&
+        idx->ckmer <= SEED_LOCUS_DEFAULT_LEN && SEED_LOCUS_DEFAULT_LEN <= idx->ckmer + CTAB_FLANK)
+        st = handle_seed_locus( idx, SEED_LOCUS_DEFAULT_LEN, stream );
     if (st != NVBIO_OK)
     {
         if (idx->planes) (void)hipFree( idx->planes );
+        if (idx->locus)  (void)hipFree( idx->locus );
         if (tables)
         {
             if (idx->ktab)  (void)hipFree( idx->ktab );
@@ -1355,6 +1411,7 @@ nvbio_status nvbio_fm_index_destroy(nvbio_fm_index_t index)
     if (idx->isa)  (void)hipFree( idx->isa );
     if (idx->text) (void)hipFree( idx->text );
     if (idx->planes) (void)hipFree( idx->planes );
+    if (idx->locus)  (void)hipFree( idx->locus );
     if (idx->owns_arrays) { (void)hipFree( (void*)idx->view.bwt_occ_dev ); (void)hipFree( (void*)idx->view.ssa_dev ); }
     delete idx;
     return NVBIO_OK;
@@ -1393,6 +1450,39 @@ nvbio_status nvbio_fm_index_text_planes(nvbio_fm_index_t index, const void** pla
     *planes_dev = idx->planes;
     *length     = idx->planes ? idx->view.length : 0u;
     return NVBIO_OK;
+}
+
+nvbio_status nvbio_seed_locus_bytes(uint32_t length, uint64_t* bytes)
+{
+    NVB_REQUIRE( bytes != nullptr, "bytes is NULL" );
+    *bytes = seed_locus_lines( length ) * SEED_LOCUS_LINE_BYTES;
+    return NVBIO_OK;
+}
+
+nvbio_status nvbio_seed_locus_build(nvbio_fm_index_t index, uint32_t seed_len, void* lines_dev, void* stream)
+{
+    NVB_REQUIRE( index && lines_dev, "index/lines_dev is NULL" );
+    const FMIndexImpl* idx = (const FMIndexImpl*)index;
+    DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return seed_locus_fill( idx, seed_len, lines_dev, (hipStream_t)stream );
+}
+
+nvbio_status nvbio_fm_index_seed_locus(nvbio_fm_index_t index, const void** lines_dev, uint32_t* seed_len)
+{
+    NVB_REQUIRE( index && lines_dev && seed_len, "index/lines_dev/seed_len is NULL" );
+    const FMIndexImpl* idx = (const FMIndexImpl*)index;
+    const bool have = idx->locus && idx->locus_len;
+    *lines_dev = have ? idx->locus : nullptr;
+    *seed_len  = have ? idx->locus_len : 0u;
+    return NVBIO_OK;
+}
+
+nvbio_status nvbio_fm_index_build_seed_locus(nvbio_fm_index_t index, uint32_t seed_len, void* stream)
+{
+    NVB_REQUIRE( index != nullptr, "index is NULL" );
+    FMIndexImpl* idx = (FMIndexImpl*)index;
+    DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
+    return handle_seed_locus( idx, seed_len, (hipStream_t)stream );
 }
 
 nvbio_status nvbio_fm_match(nvbio_fm_index_t index, const nvbio_string_set* queries, uint32_t flags,
@@ -1762,8 +1852,13 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, co
     hipStream_t s = (hipStream_t)stream;
     const bool count = (flags & NVBIO_FM_COUNT_SECTORS) != 0;
     const bool defer = (flags & NVBIO_FM_DEFER_HEAVY) != 0 && !count;
+    const bool routes = (flags & NVBIO_FM_COUNT_LOCUS) != 0;
+    NVB_REQUIRE( !routes || count, "NVBIO_FM_COUNT_LOCUS goes with NVBIO_FM_COUNT_SECTORS" );
     NVB_REQUIRE( !count || ((uintptr_t)counts_dev & 7u) == 0, "counts_dev must be 8-byte aligned with NVBIO_FM_COUNT_SECTORS" );
-    NVB_HIP( hipMemsetAsync( counts_dev, 0, (count ? 6 : 4) * sizeof(uint32_t), s ) );
+    NVB_HIP( hipMemsetAsync( counts_dev, 0, (routes ? 10 : (count ? 6 : 4)) * sizeof(uint32_t), s ) );
+    // the locus path: lines built for this seed length, reads that fit one line (ragged reads: the kernel looks at every read's length)
+    const bool use_locus = idx->locus && idx->locus_len == q.fixed_len && !(flags & NVBIO_FM_NO_SEED_LOCUS) &&
+                           (q.intervals != nullptr || read_len <= SEED_LOCUS_MAX_READ);
     if (q.n == 0) return NVBIO_OK;
     NVB_REQUIRE( keys_dev && residual_ranges_dev && residual_ids_dev, "NULL device pointer" );
     SeedScratch L; NVB_CHECK( seed_scratch_layout( seeds, true, &L ) );
@@ -1783,18 +1878,20 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, co
     inline_max = inline_max < 1u ? 1u : (inline_max > CTAB_INLINE ? CTAB_INLINE : inline_max);
     NVB_CHECK( with_value( Values<2, 4>(), seeds->symbol_bits, [&](auto BITS)
     {
-        const auto launch = [&](auto CNT, auto W, auto D)
+        const auto launch = [&](auto CNT, auto W, auto D, auto LC)
         {
-            return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D>), grid, block, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
+            return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D,LC>), grid, block, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
                                (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
-                               CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts );
+                               CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts,
+                               (const void*)(LC ? idx->locus : nullptr), routes ? (unsigned int*)counts_dev + 6 : (unsigned int*)nullptr );
         };
-        const auto wide = [&](auto W)
+        const auto kind = [&](auto W, auto LC)
         {
-            if (count) return launch( std::true_type(),  W, std::false_type() );
-            if (defer) return launch( std::false_type(), W, std::true_type() );
-            return            launch( std::false_type(), W, std::false_type() );
+            if (count) return launch( std::true_type(),  W, std::false_type(), LC );
+            if (defer) return launch( std::false_type(), W, std::true_type(),  LC );
+            return            launch( std::false_type(), W, std::false_type(), LC );
         };
+        const auto wide = [&](auto W) { return use_locus ? kind( W, std::true_type() ) : kind( W, std::false_type() ); };
         return idx->cwide ? wide( std::true_type() ) : wide( std::false_type() );
     }, bad_symbol_bits ) );                                      // (packed seeds were required above)
     size_t scan_bytes = L.scan_bytes;
