@@ -211,34 +211,29 @@ constexpr uint32_t SEED_LOCUS_UNITS      = 5u;                   // units of 64 
 constexpr uint32_t SEED_LOCUS_MAX_READ   = 193u;
 inline __host__ __device__ uint64_t seed_locus_lines(const uint32_t n) { return ((uint64_t)n >> 7) + 1u; }
 
-// the unit that holds symbol x of the read at `base` (x >= base, x + len - 1 <= base + SEED_LOCUS_MAX_READ - 1) and the planes of the next one
-struct LocusUnits { uint64_t lo0, hi0, u0, lo1, hi1; };
+// Of the read at `base`, the 32-bit word of each plane that holds symbol x (x >= base, x + len - 1 <= base + SEED_LOCUS_MAX_READ - 1) and the
+// word behind it, and the word of u that holds u[x]: a window of len <= 32 symbols spans no more.  As 32-bit words a unit is
+// (lo, lo', hi, hi', u, u'); the word behind a unit's second word is the first word of the next unit, 24 bytes on.
+struct LocusWords { uint32_t lo0, lo1, hi0, hi1, u; };
 
-__device__ __forceinline__ void load_locus_units(const void* __restrict__ lines, const uint32_t base, const uint32_t x, LocusUnits& out)
+__device__ __forceinline__ void load_locus_words(const void* __restrict__ lines, const uint32_t base, const uint32_t x, LocusWords& out)
 {
     static_assert( 127u + SEED_LOCUS_MAX_READ - 1u <= 64u * SEED_LOCUS_UNITS - 1u, "the last symbol of a read lies in the line its first symbol lies in" );
     static_assert( 24u * SEED_LOCUS_UNITS <= SEED_LOCUS_LINE_BYTES, "a line holds its units" );
-    const uint32_t line = base >> 7, unit = (x - (line << 7)) >> 6;                      // unit <= 4
-    const uint64_t* __restrict__ p = (const uint64_t*)lines + (size_t)line * 16u;
-    const uint32_t next = unit + 1u < SEED_LOCUS_UNITS ? unit + 1u : unit;               // (a window that crosses into the next unit has one)
-    out.lo0 = p[3u * unit]; out.hi0 = p[3u * unit + 1u]; out.u0 = p[3u * unit + 2u];
-    out.lo1 = p[3u * next]; out.hi1 = p[3u * next + 1u];
+    const uint32_t line = base >> 7, off = x - (line << 7), unit = off >> 6, w = (off >> 5) & 1u;   // unit <= 4
+    const uint32_t* __restrict__ p = (const uint32_t*)lines + ((size_t)line * 32u + 6u * unit);
+    // (a window that crosses into the next unit has one: in the line's last unit the second word read is one the window does not reach)
+    const uint32_t w1 = w ? (unit + 1u < SEED_LOCUS_UNITS ? 6u : 0u) : 1u;
+    out.lo0 = p[w]; out.lo1 = p[w1]; out.hi0 = p[2u + w]; out.hi1 = p[2u + w1]; out.u = p[4u + w];
 }
 
-// every 2nd bit of v (positions 0, 2, .., 62) squeezed into 32 bits
-__device__ __forceinline__ uint64_t squeeze2_64(const uint64_t v)
+// does text[x, x + len) equal the len <= 32 symbols whose bit planes are (tlo, thi) (bit t: symbol t; bits from len on are ignored), with u[x] set?
+__device__ __forceinline__ bool locus_answers(const LocusWords& lw, const uint32_t x, const uint32_t len, const uint32_t tlo, const uint32_t thi)
 {
-    return (uint64_t)squeeze2( (uint32_t)v ) | ((uint64_t)squeeze2( (uint32_t)(v >> 32) ) << 16);
-}
-
-// does text[x, x + len) equal the len <= 32 symbols T (symbol t at bits [2 t, +2)), with u[x] set?
-__device__ __forceinline__ bool locus_answers(const LocusUnits& lu, const uint32_t x, const uint32_t len, const uint64_t T)
-{
-    const uint32_t s = x & 63u;
-    const uint64_t lo = s ? (lu.lo0 >> s) | (lu.lo1 << (64u - s)) : lu.lo0;
-    const uint64_t hi = s ? (lu.hi0 >> s) | (lu.hi1 << (64u - s)) : lu.hi0;
-    const uint64_t mask = (1ull << len) - 1ull;
-    return ((((lo ^ squeeze2_64( T )) | (hi ^ squeeze2_64( T >> 1 ))) & mask) == 0ull) && ((lu.u0 >> s) & 1ull);
+    const uint32_t s = x & 31u;
+    const uint32_t lo = __builtin_amdgcn_alignbit( lw.lo1, lw.lo0, s ), hi = __builtin_amdgcn_alignbit( lw.hi1, lw.hi0, s );
+    const uint32_t mask = len >= 32u ? 0xFFFFFFFFu : (1u << len) - 1u;
+    return ((((lo ^ tlo) | (hi ^ thi)) & mask) == 0u) && ((lw.u >> s) & 1u);
 }
 
 // 224 plane bits (14 packed words), shifted so that bit 0 = window symbol 0

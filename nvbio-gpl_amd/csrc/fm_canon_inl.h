@@ -271,10 +271,14 @@ __device__ __forceinline__ bool canon_lookup(const DevIndex& f, const uint64_t V
     else
     {
         const uint32_t m = e.y - DTAB_MARK;
+        // a group is 32 bytes (up to 4 rows) or 64: its gathers are issued together and waited for once, not one latency per pair of rows
         const uint4* g4 = (const uint4*)(f.cside + 4ull * (e.x - DTAB_MARK));
+        uint4 g[CTAB_ROWS_MAX / 2u];
+        g[0] = g4[0]; g[1] = g4[1]; g[2] = g[3] = make_uint4( 0u, 0u, 0u, 0u );
+        if (m > 4u) { g[2] = g4[2]; g[3] = g4[3]; }
         #pragma unroll
         for (uint32_t t = 0; t < CTAB_ROWS_MAX; t += 2u)
-            if (t < m) { const uint4 g = g4[t >> 1]; row( g.x, g.y ); if (t + 1u < m) row( g.z, g.w ); }
+            if (t < m) { row( g[t >> 1].x, g[t >> 1].y ); if (t + 1u < m) row( g[t >> 1].z, g[t >> 1].w ); }
     }
     return true;
 }
@@ -321,8 +325,15 @@ seed_locus_kernel(const DevIndex f, const uint32_t len, const uint32_t wide, con
 
 // The tile loop of fm_seed_both_kernel<.., LOCUS = true> (see there: the path, why its keys are the same, the pipeline).  seed_geom, entry_of
 // and resolve_tile are the kernel's own; a stage whose tile does not exist carries lanes without a seed, which load and write nothing.
-template <int BITS, bool COUNT, bool WIDE, typename Geom, typename Entry, typename Resolve>
-__device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const StringSetDev& q, const SeedTiles& tl, const void* __restrict__ locus,
+// RAGGED = false (every read has read_len symbols and q.interval between its seeds): a seed's offset in its read and the read's length
+// are loop constants, and no stage carries them.
+// What a stage knows about its lane travels as bits of ONE register (LS_*): as separate bools each is a 64-bit lane mask in a scalar
+// pair, and the fourteen of them, on top of the kernel's arguments, sent the scalar file spilling into vector lanes inside the loop.
+enum : uint32_t { LS_SEED = 1u, LS_OK = 2u, LS_ASKED = 4u, LS_USABLE = 8u, LS_STRAND = 16u,   // has a seed | the seed is clean (no N) | asks the locus | its read is placed | on the reverse strand
+                  LS_SETTLED = 32u,                                                          // x 1, x 2: settled on the locus, on the forward / reverse strand
+                  LS_BEGIN = 256u };                                                         // x (begin & 15): where the seed begins in its first packed word
+template <int BITS, bool COUNT, bool WIDE, bool RAGGED, typename Geom, typename Entry, typename Resolve>
+__device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const StringSetDev& q, const SeedTiles& tl, const uint32_t read_len, const void* __restrict__ locus,
                                                    unsigned long long* __restrict__ sectors_out, unsigned int* __restrict__ routes, const uint32_t tile0,
                                                    const uint32_t lane, const uint32_t lr, const uint32_t j, const bool lane_ok,
                                                    const Geom& seed_geom, const Entry& entry_of, const Resolve& resolve_tile)
@@ -330,35 +341,45 @@ __device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const Stri
     const uint32_t n_waves = gridDim.x * 4u;
     const uint32_t k = f.ckmer, len = q.fixed_len, n = f.length;
     const uint32_t anchor = lane - j;                                        // the lane of this read's first seed
+    const bool     first = j == 0u;
+    const uint32_t u_pfw = j * q.interval;                                   // (uniform reads) the seed's offset in its read
     const uint4 none = make_uint4( 1u, 0u, 0u, 0u );                         // the entry of a k-mer without occurrences
     auto qo_of = [&](const uint64_t V) -> uint32_t { return (uint32_t)(V >> (2u * (len - k) + k)) & 1u; };
+    auto pfw_of  = [&](const uint32_t v) -> uint32_t { return RAGGED ? v : u_pfw; };
+    auto rlen_of = [&](const uint32_t v) -> uint32_t { return RAGGED ? v : read_len; };
     auto add = [&](unsigned int* word, const bool on) {                      // (COUNT) one atomic per wave
         const uint32_t c = (uint32_t)__popcll( __ballot( on ) );
         if (lane == 0 && c) atomicAdd( word, c );
     };
-    // per stage: seed bits V, entry e (none: not gathered), has a seed / the seed is clean (no N), its offset in the read, the read's length
-    SeedWords W = { 0, 0, 0, 0, 0 }; uint32_t w_begin = 0, w_pfw = 0, w_rlen = 0; bool w_seed = false;        // words of tile t+3, loaded
-    uint64_t aV = 0; uint4 ae = none; bool a_seed = false, a_ok = false; uint32_t a_pfw = 0, a_rlen = 0;      // tile t+2: the anchors' entries loaded
-    uint64_t lV = 0; uint4 le = none; bool l_seed = false, l_ok = false; uint32_t l_pfw = 0, l_rlen = 0;      // tile t+1: the locus units loaded
-    bool l_asked = false, l_usable = false; uint32_t l_x = 0, l_strand = 0; LocusUnits LU = { 0, 0, 0, 0, 0 };
-    uint64_t cV = 0; uint4 ce = none; bool c_seed = false, c_ok = false; uint32_t c_pfw = 0, c_rlen = 0;      // tile t: the remaining entries loaded
-    uint32_t c_settled = 0, c_x = 0;
+    // per stage: seed bits V, entry e (none: not gathered), the LS_* bits, (ragged reads) the seed's offset in the read, the read's length
+    SeedWords W = { 0, 0, 0, 0, 0 }; uint32_t w_pfw = 0, w_rlen = 0, w_fl = 0;                                // words of tile t+3, loaded
+    uint64_t aV = 0; uint4 ae = none; uint32_t a_fl = 0, a_pfw = 0, a_rlen = 0;                               // tile t+2: the anchors' entries loaded
+    uint64_t lV = 0; uint32_t l_fl = 0, l_pfw = 0, l_rlen = 0;                                                // tile t+1: the locus words loaded
+    uint32_t l_x = 0; LocusWords LW = { none.x, none.y, none.z, none.w, 0 };                                  // (in the lanes j = 0, which never ask: the anchor's entry)
+    uint64_t cV = 0; uint4 ce = none; uint32_t c_fl = 0, c_pfw = 0, c_rlen = 0;                               // tile t: the remaining entries loaded
     for (uint32_t step = 0; ; ++step)
     {
         const uint64_t t4 = (uint64_t)tile0 + (uint64_t)step * n_waves;                  // the tile whose words this iteration loads
         if (step >= 4u && t4 - 4ull * n_waves >= tl.n_tiles) break;
-        // ---- tile t+1: the lane's window against the locus ----
+        // ---- tile t+1: the lane's window against the locus.  The seed as bit planes; its reverse complement is the planes mirrored and inverted ----
         uint32_t settled = 0;
-        if (l_asked && locus_answers( LU, l_x, len, l_strand ? canon_revcomp( lV, len ) : lV )) settled = 1u + l_strand;
+        if (l_fl & LS_ASKED)
+        {
+            const uint32_t strand = (l_fl / LS_STRAND) & 1u;
+            const uint32_t vl = (uint32_t)lV, vh = (uint32_t)(lV >> 32);
+            uint32_t plo = squeeze2( vl ) | (squeeze2( vh ) << 16), phi = squeeze2( vl >> 1 ) | (squeeze2( vh >> 1 ) << 16);
+            if (strand) { plo = ~(__brev( plo ) >> (32u - len)); phi = ~(__brev( phi ) >> (32u - len)); }
+            if (locus_answers( LW, l_x, len, plo, phi )) settled = 1u + strand;
+        }
         if (COUNT && routes)
         {
             add( routes + 1, settled != 0u );
-            add( routes + 2, l_seed && j != 0u && l_usable && !settled );
-            add( routes + 3, l_seed && j != 0u && !l_usable );
+            add( routes + 2, (l_fl & LS_SEED) && !first && (l_fl & LS_USABLE) && !settled );
+            add( routes + 3, (l_fl & LS_SEED) && !first && !(l_fl & LS_USABLE) );
         }
         // ---- tile t+2: the anchor placed (its group, if its entry points to one, is gathered here), told to the lanes of its read ----
         uint32_t a_hit = 0xFFFFFFFFu, a_strand = 0;
-        if (j == 0u && a_ok)
+        if (first && (a_fl & LS_OK))
         {
             CanonHits h;
             if (canon_lookup( f, aV, len, qo_of( aV ), ae, h ) && h.nf + h.nr == 1u) { a_strand = h.nr; a_hit = h.nr ? h.vr : h.vf; }
@@ -366,29 +387,31 @@ __device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const Stri
         const uint32_t r_hit = (uint32_t)__shfl( (int)a_hit, (int)anchor ), r_strand = (uint32_t)__shfl( (int)a_strand, (int)anchor );
         const bool usable = r_hit != 0xFFFFFFFFu;
         bool ask = false; uint32_t x = 0, base = 0;                                      // the window's place on the anchor's diagonal; where the read begins
-        if (usable && j != 0u && a_ok && a_rlen <= SEED_LOCUS_MAX_READ)
+        if (usable && !first && (a_fl & LS_OK) && rlen_of( a_rlen ) <= SEED_LOCUS_MAX_READ)
         {
-            if (r_strand == 0u) { base = r_hit; x = r_hit + a_pfw; ask = (uint64_t)r_hit + a_pfw + len <= n; }
+            const uint32_t p = pfw_of( a_pfw );
+            if (r_strand == 0u) { base = r_hit; x = r_hit + p; ask = (uint64_t)r_hit + p + len <= n; }
             else
             {
-                const uint32_t span = a_rlen - len;                                      // (a lane with a seed: a_pfw + len <= a_rlen)
-                base = r_hit >= span ? r_hit - span : 0u; x = r_hit - a_pfw; ask = r_hit >= a_pfw;
+                const uint32_t span = rlen_of( a_rlen ) - len;                           // (a lane with a seed: p + len <= its read's length)
+                base = r_hit >= span ? r_hit - span : 0u; x = r_hit - p; ask = r_hit >= p;
             }
         }
         if (COUNT)
         {
-            if (routes) add( routes, j == 0u && usable );
+            if (routes) add( routes, first && usable );
             // the read's locus line, once, in its anchor's lane
             const uint64_t asked = __ballot( ask );
             const uint64_t mine = (q.spr >= 64u ? ~0ull : ((1ull << q.spr) - 1ull)) << anchor;
-            const uint32_t c = (uint32_t)__popcll( __ballot( j == 0u && (asked & mine) != 0ull ) );
+            const uint32_t c = (uint32_t)__popcll( __ballot( first && (asked & mine) != 0ull ) );
             if (lane == 0 && c) atomicAdd( sectors_out, (unsigned long long)c );
         }
         // ---- tile t+3: the seed bits ----
-        uint64_t nV = 0; bool n_ok = false;
-        const bool n_seed = w_seed; const uint32_t n_pfw = w_pfw, n_rlen = w_rlen;
-        if (w_seed) n_ok = seed_bits_from_words<BITS>( W, w_begin, len, false, false, nV );
-        // ---- the loads of every stage: groups of t | remaining entries of t+1 | locus units of t+2 | anchor entries of t+3 | words of t+4 ----
+        uint64_t nV = 0; uint32_t n_fl = w_fl;
+        if (w_fl & LS_SEED) n_fl |= seed_bits_from_words<BITS>( W, (w_fl / LS_BEGIN) & 15u, len, false, false, nV ) ? LS_OK : 0u;
+        const uint32_t n_pfw = w_pfw, n_rlen = w_rlen;
+        // ---- the loads of every stage: groups of t | remaining entries of t+1 | locus words of t+2 | anchor entries of t+3 | words of t+4 ----
+        const bool c_ok = (c_fl & LS_OK) != 0u;
         const bool is_one   = c_ok && ce.y >= DTAB_MARK && ce.x < DTAB_MARK;
         const bool is_group = c_ok && ce.y >= DTAB_MARK && ce.x >= DTAB_MARK;
         const bool is_heavy = c_ok && ce.y < DTAB_MARK && ce.x <= ce.y;
@@ -399,27 +422,38 @@ __device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const Stri
             q0 = g4[0]; q1 = g4[1];
             if (ce.y - DTAB_MARK > 4u) { q2 = g4[2]; q3 = g4[3]; }
         }
-        uint4 fe = (j == 0u) ? le : none;
-        if (l_ok && j != 0u && !settled) { uint32_t qo; fe = entry_of( lV, qo ); }
-        LocusUnits nLU = { 0, 0, 0, 0, 0 };
-        if (ask) load_locus_units( locus, base, x, nLU );
-        uint4 ne = none;
-        if (j == 0u && n_ok) { uint32_t qo; ne = entry_of( nV, qo ); }
+        // the anchors of t+3 sit in the lanes j = 0, the remaining windows of t+1 in the others: ONE index computation and ONE gather serve both
+        uint4 got = none;
+        if (first ? (n_fl & LS_OK) != 0u : ((l_fl & LS_OK) && !settled)) { uint32_t qo; got = entry_of( first ? nV : lV, qo ); }
+        const uint4 fe = first ? make_uint4( LW.lo0, LW.lo1, LW.hi0, LW.hi1 ) : got;     // (an anchor's entry is read in the lanes j = 0 only)
+        // the anchors' entries travel on in the registers the other lanes load their locus words into: a lane j = 0 never asks
+        LocusWords nLW = { ae.x, ae.y, ae.z, ae.w, 0 };
+        if (ask) load_locus_words( locus, base, x, nLW );
         {
             const uint64_t rid4 = t4 * tl.rpt + lr;
-            w_seed = t4 < tl.n_tiles && lane_ok && rid4 < tl.reads;
-            if (w_seed) w_seed = seed_geom( (uint32_t)rid4, w_begin, w_pfw, w_rlen );
-            if (w_seed) W = load_seed_words<BITS>( q.symbols, w_begin, len );
+            uint32_t w_begin = 0;
+            bool ws = t4 < tl.n_tiles && lane_ok && rid4 < tl.reads;
+            if (RAGGED) { if (ws) ws = seed_geom( (uint32_t)rid4, w_begin, w_pfw, w_rlen ); }
+            else if (ws) w_begin = (q.offsets ? q.offsets[rid4] : (uint32_t)rid4 * q.stride) + u_pfw;
+            if (ws) W = load_seed_words<BITS>( q.symbols, w_begin, len );
+            w_fl = ws ? LS_SEED | ((w_begin & 15u) * LS_BEGIN) : 0u;
         }
         // ---- tile t resolved ----
         if (step >= 4u)
         {
             const uint32_t tile = (uint32_t)(t4 - 4ull * n_waves), rid = tile * tl.rpt + lr;
-            resolve_tile( tile, rid, c_seed, cV, ce, c_ok, qo_of( cV ), c_pfw, c_rlen, is_one, is_group, is_heavy, q0, q1, q2, q3, c_settled, c_x );
+            resolve_tile( tile, rid, (c_fl & LS_SEED) != 0u, cV, ce, c_ok, qo_of( cV ), pfw_of( c_pfw ), rlen_of( c_rlen ), is_one, is_group, is_heavy,
+                          q0, q1, q2, q3, (c_fl / LS_SETTLED) & 3u, (uint32_t)cV );
         }
-        cV = lV; ce = fe; c_seed = l_seed; c_ok = l_ok; c_pfw = l_pfw; c_rlen = l_rlen; c_settled = settled; c_x = l_x;
-        lV = aV; le = ae; l_seed = a_seed; l_ok = a_ok; l_pfw = a_pfw; l_rlen = a_rlen; l_asked = ask; l_usable = usable; l_x = x; l_strand = r_strand; LU = nLU;
-        aV = nV; ae = ne; a_seed = n_seed; a_ok = n_ok; a_pfw = n_pfw; a_rlen = n_rlen;
+        // (a settled lane has no entry to hold its seed against: where it was settled travels in the seed's place.  resolve_tile then gets
+        // that position as V, and what it derives from V -- qo, the flank -- is garbage in such a lane.  That is harmless ONLY because a
+        // settled lane gathered nothing: its ce is `none`, so is_one / is_group / is_heavy are false and no row is held against V.  The
+        // same holds for what the lanes j > 0 carry in ae, and the lanes j = 0 in LW: stale or foreign words that nothing reads, since
+        // an anchor's entry is taken from LW in the lanes j = 0 alone and only a lane that asked reads LW as locus words.)
+        cV = settled ? (uint64_t)l_x : lV; ce = fe; c_fl = l_fl | (settled * LS_SETTLED); c_pfw = l_pfw; c_rlen = l_rlen;
+        lV = aV; l_pfw = a_pfw; l_rlen = a_rlen; l_x = x; LW = nLW;
+        l_fl = (a_fl & (LS_SEED | LS_OK)) | (ask ? LS_ASKED : 0u) | (usable ? LS_USABLE : 0u) | (r_strand ? LS_STRAND : 0u);
+        aV = nV; ae = got; a_fl = n_fl; a_pfw = n_pfw; a_rlen = n_rlen;
     }
 }
 
@@ -449,13 +483,18 @@ __device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const Stri
 // pos[strand][0] = x_j and nothing on the other strand, which is what the lane sets.  Every other lane -- text differs, u = 0, x_j outside
 // [0, n - len], no usable anchor, a read longer than SEED_LOCUS_MAX_READ -- gathers its entry and resolves it as without LOCUS, and the
 // emission sees the same hits and positions either way.
-// Pipeline with LOCUS: words of tile t+4 | anchor entries of t+3 | locus units of t+2 | the remaining entries of t+1 | groups and resolution
+// Pipeline with LOCUS: words of tile t+4 | anchor entries of t+3 | locus words of t+2 | the remaining entries of t+1 | groups and resolution
 // of t.  Each iteration first computes on what the last one loaded (locus test of t+1, anchor of t+2, seed bits of t+3), then issues the
-// loads of all five stages, then resolves tile t.  An anchor whose entry points to a group gathers it while it computes: the one
-// dependent gather outside the schedule, in the iterations where one of the wave's anchors has a k-mer with 3..8 occurrences.
+// loads of all five stages, then resolves tile t.  The anchors of t+3 and the remaining windows of t+1 sit in different lanes (j = 0, j > 0)
+// and share one index computation and one gather.  An anchor whose entry points to a group gathers it while it computes -- its two or
+// four loads issued together: the one dependent gather outside the schedule, in the iterations where one of the wave's anchors has a
+// k-mer with 3..8 occurrences.  The loop is bound by the vector instructions it issues, not by its loads: what it carries
+// from stage to stage and what it computes per lane is kept small for that reason.
 // routes (COUNT, NVBIO_FM_COUNT_LOCUS): reads with a usable anchor | windows settled on the locus | windows of such reads that gathered
 // after all | windows of reads without a usable anchor -- the last three over the windows behind the anchor (j > 0).
-template <int BITS, bool COUNT, bool WIDE, bool DEFER, bool LOCUS>
+// RAGGED (with LOCUS only; the other forms look at q.intervals): the batch has ragged reads.  A form of its own, chosen by the launcher, so
+// that uniform reads pay neither the registers nor the instructions of a geometry that is the same for every read.
+template <int BITS, bool COUNT, bool WIDE, bool DEFER, bool LOCUS, bool RAGGED = false>
 __global__ void __launch_bounds__(256)
 fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, const uint32_t read_len, const uint32_t inline_max,
                     uint64_t* __restrict__ tile_keys, uint32_t* __restrict__ tile_counts, uint2* __restrict__ res_ranges,
@@ -467,7 +506,7 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
     const uint32_t k = f.ckmer, len = q.fixed_len, r = len - k;
     const uint32_t lr = lane / q.spr, j = lane - lr * q.spr;
     const bool lane_ok = lr < tl.rpt;
-    const bool ragged = q.intervals != nullptr;
+    const bool ragged = LOCUS ? RAGGED : (q.intervals != nullptr);
     const uint32_t rmask = (1u << (2u * r)) - 1u;                            // r <= 7
     const uint32_t fshift = 2u * (CTAB_FLANK - r);
     DevIndex fplain = f; fplain.dtab = nullptr; fplain.dkmer = 0;            // the fallback searches use the plain table only
@@ -564,14 +603,18 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
             }
             // a tile's keys of one strand must fit its 64 slots: if the seeds with several keys would overflow them, those seeds go to the
             // residual list instead (a wave-uniform decision; the range of a seed resolved from its entry's rows is searched for then)
-            uint32_t total = (uint32_t)__popcll( __ballot( cnt == 1u ) );
-            #pragma unroll
-            for (uint32_t t = 0; t < CTAB_INLINE; ++t) total += (uint32_t)__popcll( __ballot( cnt >= 2u && t < cnt ) );
-            if (total > 64u && cnt >= 2u)
+            // (counted only in a wave that has such a seed: the common tile, one key per seed at most, skips the five ballots)
+            if (__ballot( cnt >= 2u ))
             {
-                if (DEFER) { deferred = true; rx = 1u; ry = 0u; }
-                else if (!searched) (void)plain_search();
-                cnt = 0u;
+                uint32_t total = (uint32_t)__popcll( __ballot( cnt == 1u ) );
+                #pragma unroll
+                for (uint32_t t = 0; t < CTAB_INLINE; ++t) total += (uint32_t)__popcll( __ballot( cnt >= 2u && t < cnt ) );
+                if (total > 64u && cnt >= 2u)
+                {
+                    if (DEFER) { deferred = true; rx = 1u; ry = 0u; }
+                    else if (!searched) (void)plain_search();
+                    cnt = 0u;
+                }
             }
             uint64_t* slots = tile_keys + (uint64_t)tile * 128u + tile_fill;
             uint32_t n_out = 0; uint64_t last = ~0ull;
@@ -618,7 +661,9 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
     if (tile >= tl.n_tiles) return;
     if constexpr (LOCUS)
     {
-        fm_seed_locus_loop<BITS,COUNT,WIDE>( f, q, tl, locus, sectors_out, routes, tile, lane, lr, j, lane_ok, seed_geom, entry_of, resolve_tile );
+        // (a wave's first tile is the same in every lane: told to the compiler, the tile and step arithmetic of the loop is scalar)
+        tile = (uint32_t)__builtin_amdgcn_readfirstlane( (int)tile );
+        fm_seed_locus_loop<BITS,COUNT,WIDE,RAGGED>( f, q, tl, read_len, locus, sectors_out, routes, tile, lane, lr, j, lane_ok, seed_geom, entry_of, resolve_tile );
         return;
     }
     // stage 1 -> 2 (the tile after the current one): packed words, where they begin, the seed's offset in its read, the read's length

@@ -1880,10 +1880,15 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, co
     {
         const auto launch = [&](auto CNT, auto W, auto D, auto LC)
         {
-            return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D,LC>), grid, block, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
-                               (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
-                               CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts,
-                               (const void*)(LC ? idx->locus : nullptr), routes ? (unsigned int*)counts_dev + 6 : (unsigned int*)nullptr );
+            const auto form = [&](auto RG)                       // (the locus path has a form of its own for ragged reads)
+            {
+                return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D,LC,RG>), grid, block, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
+                                   (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
+                                   CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts,
+                                   (const void*)(LC ? idx->locus : nullptr), routes ? (unsigned int*)counts_dev + 6 : (unsigned int*)nullptr );
+            };
+            if constexpr (LC) { if (q.intervals != nullptr) return form( std::true_type() ); }
+            return form( std::false_type() );
         };
         const auto kind = [&](auto W, auto LC)
         {
