@@ -15,6 +15,11 @@ argument meaning as the reference's C++ templates --
     SimpleGotohScheme, GotohAligner, BestSink semantics                    (nvbio/alignment/utils.h:103-123, alignment.h:437-449)
     BatchedBandedAlignmentScore, batch_banded_alignment_score              (nvbio/alignment/batched.h:104-298)
 
+The ctypes signatures are not written here: ``lib()`` reads them from the header (``abi.bind``; ``pipeline._host_lib()`` does the same with
+``include/nvbio_amd_host.h``), so a call site passes plain Python values and a new entry point needs no declaration on this side.  The
+``ctypes.Structure`` mirrors of the headers' structs are written by hand and registered in ``_MIRRORS`` at the end of this file; a CPU test
+holds each to its header struct, and names every struct without a mirror.
+
 PyTorch is used only as plumbing for device memory and streams.  There is NO CPU fallback:
 importing works anywhere (so that symbol checks can run), but every compute entry point raises
 ``NvbioError`` when the library or a gfx950 device is missing.  Nothing here imports ``oracle``.
@@ -26,9 +31,12 @@ import os
 
 import numpy as np
 
+from .abi import bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libnvbio_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nvbio_amd.h")
+HOST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nvbio_amd_host.h")      # of lib/libnvbio_amd_host.so (pipeline._host_lib)
 
 GLOBAL, LOCAL, SEMI_GLOBAL = 0, 1, 2
 SCORE_MIN = -(1 << 30)
@@ -136,8 +144,7 @@ def lib():
         # (loaded the other way round the two runtimes do not see each other's device context: NVBIO_ERR_NO_DEVICE)
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        L.nvbio_amd_last_error.restype = ctypes.c_char_p
-        L.nvbio_amd_version.restype = ctypes.c_int
+        bind(L, HEADER_PATH, _MIRRORS)
         _lib = L
     return _lib
 
@@ -151,14 +158,14 @@ def set_scratch_check(enable, fill_byte=0):
     """nvbio_amd_set_scratch_check: a test tool.  Enabled, every scratch block is a fresh exact-size allocation between two guard
     bands, its layout leaves a gap around each sub-array, and all of it (a caller's temp included) is filled with `fill_byte` before
     any work; enabling clears the report.  Switch it only between calls; query *_temp_bytes after switching."""
-    _check(lib().nvbio_amd_set_scratch_check(ctypes.c_int(1 if enable else 0), ctypes.c_uint32(fill_byte)))
+    _check(lib().nvbio_amd_set_scratch_check(1 if enable else 0, fill_byte))
 
 
 def scratch_check_report():
     """nvbio_amd_scratch_check_report, parsed: {tag: (blocks checked, blocks damaged, first bad sub-array, first bad offset)}, the
     last two None for a clean site"""
     buf = ctypes.create_string_buffer(1 << 16)
-    _check(lib().nvbio_amd_scratch_check_report(buf, ctypes.c_uint64(len(buf))))
+    _check(lib().nvbio_amd_scratch_check_report(buf, len(buf)))
     out = {}
     for line in buf.value.decode().splitlines():
         tag, checked, damaged, sub, off = line.split()
@@ -205,7 +212,7 @@ def _stream_ptr(device):
 
 def device_count():
     n = ctypes.c_int(0)
-    lib().nvbio_amd_device_count(ctypes.byref(n))
+    _check(lib().nvbio_amd_device_count(ctypes.byref(n)))
     return n.value
 
 
@@ -286,8 +293,7 @@ class FMIndex:
         v.ssa_dev, v.ssa_words = (s.data_ptr(), s.numel()) if s is not None else (None, 0)
         v.sa_int = sa_int
         h = ctypes.c_void_p()
-        _check(lib().nvbio_fm_index_create(ctypes.byref(v), cls._dev_index(device), ctypes.c_uint32(kmer_len),
-                                           _stream_ptr(device), ctypes.byref(h)))
+        _check(lib().nvbio_fm_index_create(ctypes.byref(v), cls._dev_index(device), kmer_len, _stream_ptr(device), ctypes.byref(h)))
         return cls(h, device, keep=(b, s))
 
     @classmethod
@@ -301,8 +307,7 @@ class FMIndex:
         h = ctypes.c_void_p()
         opts = _BuildOptions(kmer_len, sa_int, max_lcp, 1 if verify else 0, int(table_flags),
                              0 if bucket_symbols is None else 1 + int(bucket_symbols))
-        _check(lib().nvbio_fm_index_build(_ptr(t), ctypes.c_uint32(length), cls._dev_index(device),
-                                          ctypes.byref(opts), _stream_ptr(device), ctypes.byref(h)))
+        _check(lib().nvbio_fm_index_build(_ptr(t), length, cls._dev_index(device), ctypes.byref(opts), _stream_ptr(device), ctypes.byref(h)))
         fmi = cls(h, device, keep=(t,))
         fmi._text_src = (t.data_ptr(), int(length))
         fmi._text_planes = fmi.text_planes()
@@ -312,9 +317,8 @@ class FMIndex:
     def load(cls, bwt_path, sa_path=None, kmer_len=0, device="cuda:0"):
         """load the reference's .bwt / .sa files (io::FMIndexDataHost::load, fmindex_impl.cu:333-...)"""
         h = ctypes.c_void_p()
-        _check(lib().nvbio_fm_index_load(bwt_path.encode(), sa_path.encode() if sa_path else None,
-                                         cls._dev_index(device), ctypes.c_uint32(kmer_len), _stream_ptr(device),
-                                         ctypes.byref(h)))
+        _check(lib().nvbio_fm_index_load(bwt_path.encode(), sa_path.encode() if sa_path else None, cls._dev_index(device), kmer_len,
+                                         _stream_ptr(device), ctypes.byref(h)))
         return cls(h, device)
 
     def save(self, bwt_path, sa_path=None):
@@ -381,9 +385,9 @@ class FMIndex:
         (kmer_len .. kmer_len + 7; no seed pass of the handle may be in flight).  out: a 128-byte aligned uint8 tensor of
         seed_locus_bytes(length) bytes -- nvbio_seed_locus_build fills it instead and the handle's own lines stay as they are; returns out"""
         if out is None:
-            _check(lib().nvbio_fm_index_build_seed_locus(self._h, ctypes.c_uint32(seed_len), _stream_ptr(self.device)))
+            _check(lib().nvbio_fm_index_build_seed_locus(self._h, seed_len, _stream_ptr(self.device)))
             return None
-        _check(lib().nvbio_seed_locus_build(self._h, ctypes.c_uint32(seed_len), _ptr(out), _stream_ptr(self.device)))
+        _check(lib().nvbio_seed_locus_build(self._h, seed_len, _ptr(out), _stream_ptr(self.device)))
         return out
 
     def text_planes_of(self, text2, length):
@@ -400,8 +404,7 @@ class FMIndex:
         ranges = torch.empty((queries.n, 2), dtype=torch.int32, device=self.device)
         blocks = torch.empty(queries.n, dtype=torch.int32, device=self.device) if want_blocks else None
         qs = queries.c_struct()
-        _check(lib().nvbio_fm_match(self._h, ctypes.byref(qs), ctypes.c_uint32(flags), _ptr(ranges), _ptr(blocks),
-                                    _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_match(self._h, ctypes.byref(qs), flags, _ptr(ranges), _ptr(blocks), _stream_ptr(self.device)))
         return (ranges, blocks) if want_blocks else ranges
 
     def supports_direct(self):
@@ -416,8 +419,7 @@ class FMIndex:
         ranges = torch.empty((queries.n, 2), dtype=torch.int32, device=self.device)
         direct = torch.empty(queries.n, dtype=torch.uint8, device=self.device)
         qs = queries.c_struct()
-        _check(lib().nvbio_fm_match_direct(self._h, ctypes.byref(qs), ctypes.c_uint32(flags), _ptr(ranges), _ptr(direct),
-                                           _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_match_direct(self._h, ctypes.byref(qs), flags, _ptr(ranges), _ptr(direct), _stream_ptr(self.device)))
         return ranges, direct
 
     def hamming_backtrack(self, queries, seed_len, mismatches, quirks=False, max_ranges=0):
@@ -427,9 +429,8 @@ class FMIndex:
         nr = torch.empty(queries.n, dtype=torch.int32, device=self.device)
         rg = torch.zeros((queries.n, max_ranges, 2), dtype=torch.int32, device=self.device) if max_ranges else None
         qs = queries.c_struct()
-        _check(lib().nvbio_fm_hamming_backtrack(self._h, ctypes.byref(qs), ctypes.c_uint32(seed_len), ctypes.c_uint32(mismatches),
-                                                ctypes.c_uint32(BACKTRACK_REFERENCE_QUIRKS if quirks else 0), _ptr(counts), _ptr(nr), _ptr(rg),
-                                                ctypes.c_uint32(max_ranges), _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_hamming_backtrack(self._h, ctypes.byref(qs), seed_len, mismatches, BACKTRACK_REFERENCE_QUIRKS if quirks else 0,
+                                                _ptr(counts), _ptr(nr), _ptr(rg), max_ranges, _stream_ptr(self.device)))
         return counts, nr, rg
 
     def match_seed_diagonals(self, seeds, flags, read_len, strand, buffers=None, grid_blocks=0):
@@ -454,19 +455,15 @@ class FMIndex:
             _check(lib().nvbio_fm_match_seed_diagonals_temp_bytes(ctypes.byref(qs), ctypes.byref(nb)))
             buffers["temp"] = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
         assert grid_blocks % 64 == 0 and grid_blocks < (1 << 22)
-        _check(lib().nvbio_fm_match_seed_diagonals(self._h, ctypes.byref(qs), ctypes.c_uint32(flags | ((grid_blocks // 64) << 16)),
-                                                   ctypes.c_uint32(read_len), ctypes.c_uint32(strand), _ptr(buffers["keys"]),
-                                                   _ptr(buffers["ranges"]), _ptr(buffers["ids"]), _ptr(buffers["counts"]),
-                                                   _ptr(buffers["temp"]), ctypes.c_uint64(buffers["temp"].numel()),
-                                                   _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_match_seed_diagonals(self._h, ctypes.byref(qs), flags | ((grid_blocks // 64) << 16), read_len, strand,
+                                                   _ptr(buffers["keys"]), _ptr(buffers["ranges"]), _ptr(buffers["ids"]), _ptr(buffers["counts"]),
+                                                   _ptr(buffers["temp"]), buffers["temp"].numel(), _stream_ptr(self.device)))
         return buffers
 
     @property
     def canonical_kmer(self):
         """k of the canonical two-strand table the handle holds (built with FM_TABLE_CANONICAL; seeds of k .. k + 7 symbols), 0 if none"""
-        fn = lib().nvbio_fm_index_is_canonical
-        fn.restype = ctypes.c_int
-        return int(fn(self._h))
+        return lib().nvbio_fm_index_is_canonical(self._h)
 
     @property
     def canonical(self):
@@ -503,10 +500,9 @@ class FMIndex:
             buffers["tile_offsets"] = torch.zeros(int(nt.value) + 1, dtype=torch.int32, device=self.device)
         assert grid_blocks % 64 == 0 and grid_blocks < (1 << 22)
         _check(lib().nvbio_fm_match_seed_diagonals_both_tiled(
-            self._h, ctypes.byref(qs), ctypes.c_uint32(flags | (FM_DEFER_HEAVY if defer_heavy else 0) | ((int(inline_hits) & 15) << 8) | ((grid_blocks // 64) << 16)),
-            ctypes.c_uint32(read_len),
-            _ptr(buffers["keys"]), _ptr(buffers["ranges"]), _ptr(buffers["ids"]), ctypes.c_uint32(n), _ptr(buffers["counts"]),
-            _ptr(buffers["tile_offsets"]), _ptr(buffers["temp"]), ctypes.c_uint64(buffers["temp"].numel()), _stream_ptr(self.device)))
+            self._h, ctypes.byref(qs), flags | (FM_DEFER_HEAVY if defer_heavy else 0) | ((int(inline_hits) & 15) << 8) | ((grid_blocks // 64) << 16),
+            read_len, _ptr(buffers["keys"]), _ptr(buffers["ranges"]), _ptr(buffers["ids"]), n, _ptr(buffers["counts"]), _ptr(buffers["tile_offsets"]),
+            _ptr(buffers["temp"]), buffers["temp"].numel(), _stream_ptr(self.device)))
         return buffers
 
     def residual_diagonals(self, ranges, ids, cap, seeds_per_read, seed_interval, seed_len, read_len, read_offsets=None, seed_intervals=None):
@@ -517,9 +513,8 @@ class FMIndex:
         keys = torch.empty(max(n * int(cap), 1), dtype=torch.int64, device=self.device)
         n_keys = torch.zeros(1, dtype=torch.int32, device=self.device)
         _check(lib().nvbio_fm_residual_diagonals(
-            self._h, _ptr(ranges), _ptr(ids), ctypes.c_uint32(n), ctypes.c_uint32(int(cap)), ctypes.c_uint32(seeds_per_read),
-            ctypes.c_uint32(seed_interval), ctypes.c_uint32(seed_len), ctypes.c_uint32(read_len), _ptr(read_offsets), _ptr(seed_intervals),
-            _ptr(keys), _ptr(n_keys), _stream_ptr(self.device)))
+            self._h, _ptr(ranges), _ptr(ids), n, int(cap), seeds_per_read, seed_interval, seed_len, read_len, _ptr(read_offsets),
+            _ptr(seed_intervals), _ptr(keys), _ptr(n_keys), _stream_ptr(self.device)))
         return keys, n_keys
 
     def rank(self, rows, syms):
@@ -527,47 +522,41 @@ class FMIndex:
         rows = _dev_tensor(rows, torch.int32, self.device)
         syms = _dev_tensor(syms, torch.uint8, self.device)
         out = torch.empty(rows.numel(), dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_fm_rank(self._h, _ptr(rows), _ptr(syms), ctypes.c_uint32(rows.numel()), _ptr(out),
-                                   _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_rank(self._h, _ptr(rows), _ptr(syms), rows.numel(), _ptr(out), _stream_ptr(self.device)))
         return out
 
     def rank4(self, rows):
         torch = _torch()
         rows = _dev_tensor(rows, torch.int32, self.device)
         out = torch.empty((rows.numel(), 4), dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_fm_rank4(self._h, _ptr(rows), ctypes.c_uint32(rows.numel()), _ptr(out),
-                                    _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_rank4(self._h, _ptr(rows), rows.numel(), _ptr(out), _stream_ptr(self.device)))
         return out
 
     def basic_inv_psi(self, rows):
         torch = _torch()
         rows = _dev_tensor(rows, torch.int32, self.device)
         out = torch.empty(rows.numel(), dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_fm_basic_inv_psi(self._h, _ptr(rows), ctypes.c_uint32(rows.numel()), _ptr(out),
-                                            _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_basic_inv_psi(self._h, _ptr(rows), rows.numel(), _ptr(out), _stream_ptr(self.device)))
         return out
 
     def locate(self, rows):
         torch = _torch()
         rows = _dev_tensor(rows, torch.int32, self.device)
         pos = torch.empty(rows.numel(), dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_fm_locate(self._h, _ptr(rows), ctypes.c_uint32(rows.numel()), _ptr(pos),
-                                     _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_locate(self._h, _ptr(rows), rows.numel(), _ptr(pos), _stream_ptr(self.device)))
         return pos
 
     def locate_ssa_iterator(self, rows):
         torch = _torch()
         rows = _dev_tensor(rows, torch.int32, self.device)
         jt = torch.empty((rows.numel(), 2), dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_fm_locate_init(self._h, _ptr(rows), ctypes.c_uint32(rows.numel()), _ptr(jt),
-                                          _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_locate_init(self._h, _ptr(rows), rows.numel(), _ptr(jt), _stream_ptr(self.device)))
         return jt
 
     def lookup_ssa_iterator(self, jt):
         torch = _torch()
         pos = torch.empty(jt.shape[0], dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_fm_locate_lookup(self._h, _ptr(jt), ctypes.c_uint32(jt.shape[0]), _ptr(pos),
-                                            _stream_ptr(self.device)))
+        _check(lib().nvbio_fm_locate_lookup(self._h, _ptr(jt), jt.shape[0], _ptr(pos), _stream_ptr(self.device)))
         return pos
 
 
@@ -588,8 +577,8 @@ class FMIndexFilter:
         self._slots = torch.empty(string_set.n, dtype=torch.int64, device=index.device)
         total = ctypes.c_uint64(0)
         qs = string_set.c_struct()
-        _check(lib().nvbio_fm_filter_rank(index._h, ctypes.byref(qs), ctypes.c_uint32(flags), _ptr(self._ranges),
-                                          _ptr(self._slots), ctypes.byref(total), _stream_ptr(index.device)))
+        _check(lib().nvbio_fm_filter_rank(index._h, ctypes.byref(qs), flags, _ptr(self._ranges), _ptr(self._slots), ctypes.byref(total),
+                                          _stream_ptr(index.device)))
         self._n_hits = total.value
         return self._n_hits
 
@@ -600,8 +589,7 @@ class FMIndexFilter:
         self._index, self._n_queries, self._ranges, self._direct = index, ranges.shape[0], ranges, direct
         self._slots = torch.empty(ranges.shape[0], dtype=torch.int64, device=index.device)
         total = ctypes.c_uint64(0)
-        _check(lib().nvbio_fm_filter_scan(index._h, _ptr(ranges), ctypes.c_uint32(ranges.shape[0]), _ptr(self._slots),
-                                          ctypes.byref(total), _stream_ptr(index.device)))
+        _check(lib().nvbio_fm_filter_scan(index._h, _ptr(ranges), ranges.shape[0], _ptr(self._slots), ctypes.byref(total), _stream_ptr(index.device)))
         self._n_hits = total.value
         return self._n_hits
 
@@ -611,13 +599,11 @@ class FMIndexFilter:
         if hits is None:
             hits = torch.empty((end - begin, 2), dtype=torch.int32, device=self._index.device)
         if self._direct is not None:
-            _check(lib().nvbio_fm_filter_locate_direct(self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._direct),
-                                                       ctypes.c_uint32(self._n_queries), ctypes.c_uint64(begin),
-                                                       ctypes.c_uint64(end), _ptr(hits), _stream_ptr(self._index.device)))
+            _check(lib().nvbio_fm_filter_locate_direct(self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._direct), self._n_queries,
+                                                       begin, end, _ptr(hits), _stream_ptr(self._index.device)))
             return hits
-        _check(lib().nvbio_fm_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots),
-                                            ctypes.c_uint32(self._n_queries), ctypes.c_uint64(begin),
-                                            ctypes.c_uint64(end), _ptr(hits), _stream_ptr(self._index.device)))
+        _check(lib().nvbio_fm_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), self._n_queries, begin, end, _ptr(hits),
+                                            _stream_ptr(self._index.device)))
         return hits
 
     def locate_diagonals(self, begin, end, seeds_per_read, seed_interval, seed_len, read_len, strand, query_ids=None, read_offsets=None,
@@ -629,15 +615,12 @@ class FMIndexFilter:
         keys = torch.empty(end - begin, dtype=torch.int64, device=self._index.device)
         if read_offsets is not None:                 # ragged reads: every read's length and seed interval
             _check(lib().nvbio_fm_filter_locate_diagonals_ragged(
-                self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._direct), ctypes.c_uint32(self._n_queries),
-                ctypes.c_uint64(begin), ctypes.c_uint64(end), ctypes.c_uint32(seeds_per_read), ctypes.c_uint32(seed_len), _ptr(read_offsets),
-                _ptr(seed_intervals), ctypes.c_uint32(strand), _ptr(query_ids), _ptr(keys), _stream_ptr(self._index.device)))
+                self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._direct), self._n_queries, begin, end, seeds_per_read, seed_len,
+                _ptr(read_offsets), _ptr(seed_intervals), strand, _ptr(query_ids), _ptr(keys), _stream_ptr(self._index.device)))
             return keys
         _check(lib().nvbio_fm_filter_locate_diagonals(
-            self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._direct), ctypes.c_uint32(self._n_queries),
-            ctypes.c_uint64(begin), ctypes.c_uint64(end), ctypes.c_uint32(seeds_per_read), ctypes.c_uint32(seed_interval),
-            ctypes.c_uint32(seed_len), ctypes.c_uint32(read_len), ctypes.c_uint32(strand), _ptr(query_ids), _ptr(keys),
-            _stream_ptr(self._index.device)))
+            self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._direct), self._n_queries, begin, end, seeds_per_read, seed_interval,
+            seed_len, read_len, strand, _ptr(query_ids), _ptr(keys), _stream_ptr(self._index.device)))
         return keys
 
     def n_hits(self):
@@ -710,10 +693,9 @@ class MEMFilter:
         while True:
             nr, nm, rec = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
             self.attempts += 1
-            st = lib().nvbio_mem_filter_rank(f_index._h, r_index._h, ctypes.byref(qs), ctypes.byref(params), _ptr(self._ranges),
-                                             ctypes.c_uint32(cap), _ptr(self._first), _ptr(self._slots), _ptr(self._temp),
-                                             ctypes.c_uint64(self._temp.numel()), ctypes.byref(nr), ctypes.byref(nm), ctypes.byref(rec),
-                                             _stream_ptr(dev))
+            st = lib().nvbio_mem_filter_rank(f_index._h, r_index._h, ctypes.byref(qs), ctypes.byref(params), _ptr(self._ranges), cap,
+                                             _ptr(self._first), _ptr(self._slots), _ptr(self._temp), self._temp.numel(), ctypes.byref(nr),
+                                             ctypes.byref(nm), ctypes.byref(rec), _stream_ptr(dev))
             if st == 1 and max_ranges is None:
                 msg = lib().nvbio_amd_last_error().decode()
                 if "max_ranges" in msg and nr.value > cap:
@@ -764,8 +746,8 @@ class MEMFilter:
         if hits is None:
             hits = torch.empty((max(end - begin, 0), 4), dtype=torch.int32, device=self._index.device)
         if end > begin:
-            _check(lib().nvbio_mem_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), ctypes.c_uint32(self._n_ranges),
-                                                 ctypes.c_uint64(begin), ctypes.c_uint64(end), _ptr(hits), _stream_ptr(self._index.device)))
+            _check(lib().nvbio_mem_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), self._n_ranges, begin, end, _ptr(hits),
+                                                 _stream_ptr(self._index.device)))
         return hits
 
 
@@ -794,8 +776,7 @@ class QGramIndex:
         """QGramIndexDevice::build( q, symbol_size, length, text, qlut ); text: packed words (bits 2, 4) or bytes (8)"""
         t = _qgram_text(text, text_bits, device)
         h = ctypes.c_void_p()
-        _check(lib().nvbio_qgram_index_build(FMIndex._dev_index(device), _ptr(t), ctypes.c_uint32(text_bits), ctypes.c_uint32(length),
-                                             ctypes.c_uint32(q), ctypes.c_uint32(symbol_size), ctypes.c_uint32(qlut), ctypes.byref(h),
+        _check(lib().nvbio_qgram_index_build(FMIndex._dev_index(device), _ptr(t), text_bits, length, q, symbol_size, qlut, ctypes.byref(h),
                                              _stream_ptr(device)))
         return cls(h, device)
 
@@ -850,7 +831,7 @@ class QGramIndex:
         torch = _torch()
         g = _dev_tensor(qgrams, torch.int64, self.device)
         out = torch.empty((g.numel(), 2), dtype=torch.int32, device=self.device)
-        _check(lib().nvbio_qgram_ranges(self._h, _ptr(g), ctypes.c_uint32(g.numel()), _ptr(out), _stream_ptr(self.device)))
+        _check(lib().nvbio_qgram_ranges(self._h, _ptr(g), g.numel(), _ptr(out), _stream_ptr(self.device)))
         return out
 
 
@@ -864,8 +845,8 @@ class QGramSetIndex(QGramIndex):
         h = ctypes.c_void_p()
         ss = string_set.c_struct()
         dev = string_set.device
-        _check(lib().nvbio_qgram_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size),
-                                                 ctypes.c_uint32(seed_interval), ctypes.c_uint32(qlut), ctypes.byref(h), _stream_ptr(dev)))
+        _check(lib().nvbio_qgram_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), q, symbol_size, seed_interval, qlut, ctypes.byref(h),
+                                                 _stream_ptr(dev)))
         return cls(h, dev, keep=(string_set,))
 
 
@@ -885,8 +866,8 @@ class QGroupIndex(QGramIndex):
         """QGroupIndexDevice::build( q, symbol_size, length, text ); text: packed words (bits 2, 4) or bytes (8)"""
         t = _qgram_text(text, text_bits, device)
         h = ctypes.c_void_p()
-        _check(lib().nvbio_qgroup_index_build(FMIndex._dev_index(device), _ptr(t), ctypes.c_uint32(text_bits), ctypes.c_uint32(length),
-                                              ctypes.c_uint32(q), ctypes.c_uint32(symbol_size), ctypes.byref(h), _stream_ptr(device)))
+        _check(lib().nvbio_qgroup_index_build(FMIndex._dev_index(device), _ptr(t), text_bits, length, q, symbol_size, ctypes.byref(h),
+                                              _stream_ptr(device)))
         return cls(h, device)
 
     def view(self):
@@ -918,8 +899,8 @@ class QGroupSetIndex(QGroupIndex):
         h = ctypes.c_void_p()
         ss = string_set.c_struct()
         dev = string_set.device
-        _check(lib().nvbio_qgroup_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size),
-                                                  ctypes.c_uint32(seed_interval), ctypes.byref(h), _stream_ptr(dev)))
+        _check(lib().nvbio_qgroup_set_index_build(FMIndex._dev_index(dev), ctypes.byref(ss), q, symbol_size, seed_interval, ctypes.byref(h),
+                                                  _stream_ptr(dev)))
         return cls(h, dev, keep=(string_set,))
 
 
@@ -942,7 +923,7 @@ def set_suffix_count(string_set, flags=0):
     n = ctypes.c_uint32(0)
     ss = string_set.c_struct()
     dev = string_set.device
-    _check(lib().nvbio_set_suffix_count(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), ctypes.byref(n), _stream_ptr(dev)))
+    _check(lib().nvbio_set_suffix_count(FMIndex._dev_index(dev), ctypes.byref(ss), flags, ctypes.byref(n), _stream_ptr(dev)))
     return n.value
 
 
@@ -957,8 +938,8 @@ def set_suffix_sort(string_set, flags=0, want_global=True, capacity=None):
     glb = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if want_global else None
     n, st = ctypes.c_uint32(0), _SufsortStats()
     ss = string_set.c_struct()
-    _check(lib().nvbio_set_suffix_sort(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), _ptr(suf), _ptr(glb),
-                                       ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(st), _stream_ptr(dev)))
+    _check(lib().nvbio_set_suffix_sort(FMIndex._dev_index(dev), ctypes.byref(ss), flags, _ptr(suf), _ptr(glb), cap, ctypes.byref(n), ctypes.byref(st),
+                                       _stream_ptr(dev)))
     return suf[:n.value], (glb[:n.value] if want_global else None), st.as_dict()
 
 
@@ -973,8 +954,8 @@ def set_suffix_sort_flat(string_set, flags=0):
     cum = torch.empty(max(string_set.n, 1), dtype=torch.int32, device=dev)
     n, st = ctypes.c_uint32(0), _SufsortStats()
     ss = string_set.c_struct()
-    _check(lib().nvbio_set_suffix_sort_flat(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), _ptr(sa), _ptr(ids), _ptr(cum),
-                                            ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(st), _stream_ptr(dev)))
+    _check(lib().nvbio_set_suffix_sort_flat(FMIndex._dev_index(dev), ctypes.byref(ss), flags, _ptr(sa), _ptr(ids), _ptr(cum), cap, ctypes.byref(n),
+                                            ctypes.byref(st), _stream_ptr(dev)))
     return sa[:n.value], ids[:n.value], cum[:string_set.n], st.as_dict()
 
 
@@ -988,8 +969,8 @@ def set_bwt(string_set, flags=0, want_suffixes=True, capacity=None):
     suf = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev) if want_suffixes else None
     n, st = ctypes.c_uint32(0), _SufsortStats()
     ss = string_set.c_struct()
-    _check(lib().nvbio_set_bwt(FMIndex._dev_index(dev), ctypes.byref(ss), ctypes.c_uint32(flags), _ptr(bwt), _ptr(suf),
-                               ctypes.c_uint64(cap), ctypes.byref(n), ctypes.byref(st), _stream_ptr(dev)))
+    _check(lib().nvbio_set_bwt(FMIndex._dev_index(dev), ctypes.byref(ss), flags, _ptr(bwt), _ptr(suf), cap, ctypes.byref(n), ctypes.byref(st),
+                               _stream_ptr(dev)))
     return bwt[:n.value], (suf[:n.value] if want_suffixes else None), st.as_dict()
 
 
@@ -999,7 +980,7 @@ def suffix_sort(text2, length, device="cuda:0"):
     torch = _torch()
     t = _dev_tensor(text2, torch.int32, device)
     sa = torch.empty(int(length) + 1, dtype=torch.int32, device=device)
-    _check(lib().nvbio_suffix_sort(_ptr(t), ctypes.c_uint32(length), FMIndex._dev_index(device), _ptr(sa), _stream_ptr(device)))
+    _check(lib().nvbio_suffix_sort(_ptr(t), length, FMIndex._dev_index(device), _ptr(sa), _stream_ptr(device)))
     return sa
 
 
@@ -1010,8 +991,7 @@ def bwt(text2, length, device="cuda:0"):
     t = _dev_tensor(text2, torch.int32, device)
     words = torch.empty((int(length) + 15) // 16, dtype=torch.int32, device=device)
     primary = ctypes.c_uint32(0)
-    _check(lib().nvbio_bwt(_ptr(t), ctypes.c_uint32(length), FMIndex._dev_index(device), _ptr(words), ctypes.byref(primary),
-                           _stream_ptr(device)))
+    _check(lib().nvbio_bwt(_ptr(t), length, FMIndex._dev_index(device), _ptr(words), ctypes.byref(primary), _stream_ptr(device)))
     return words, primary.value
 
 
@@ -1026,16 +1006,14 @@ def generate_qgrams(q, symbol_size, text, text_bits, text_len, first_pos, n, sor
     qg = torch.empty(n, dtype=torch.int64, device=device)
     ix = torch.empty(n, dtype=torch.int32, device=device)
     tb = ctypes.c_uint64(0)
-    _check(lib().nvbio_generate_qgrams_temp_bytes(ctypes.c_uint32(n), ctypes.c_int(1 if sort else 0), ctypes.byref(tb)))
+    _check(lib().nvbio_generate_qgrams_temp_bytes(n, 1 if sort else 0, ctypes.byref(tb)))
     key = str(device)
     temp = _GENERATE_TEMP.get(key)
     if tb.value and (temp is None or temp.numel() < tb.value):
         _GENERATE_TEMP[key] = None
         temp = _GENERATE_TEMP[key] = torch.empty(int(tb.value), dtype=torch.uint8, device=device)
-    _check(lib().nvbio_generate_qgrams(FMIndex._dev_index(device), ctypes.c_uint32(q), ctypes.c_uint32(symbol_size), _ptr(t),
-                                       ctypes.c_uint32(text_bits), ctypes.c_uint32(text_len), ctypes.c_uint32(first_pos), ctypes.c_uint32(n),
-                                       _ptr(qg), _ptr(ix), ctypes.c_int(1 if sort else 0), _ptr(temp) if tb.value else None,
-                                       ctypes.c_uint64(temp.numel() if tb.value else 0), _stream_ptr(device)))
+    _check(lib().nvbio_generate_qgrams(FMIndex._dev_index(device), q, symbol_size, _ptr(t), text_bits, text_len, first_pos, n, _ptr(qg), _ptr(ix),
+                                       1 if sort else 0, _ptr(temp) if tb.value else None, temp.numel() if tb.value else 0, _stream_ptr(device)))
     return qg, ix
 
 
@@ -1068,11 +1046,11 @@ class QGramFilter:
             self._ranges = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
             self._slots = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         tb = ctypes.c_uint64(0)
-        _check(lib().nvbio_qgram_filter_temp_bytes(ctypes.c_uint32(n), ctypes.byref(tb)))
+        _check(lib().nvbio_qgram_filter_temp_bytes(n, ctypes.byref(tb)))
         self._grow_temp(tb.value, dev)
         nh = ctypes.c_uint64(0)
-        _check(lib().nvbio_qgram_filter_rank(index._h, _ptr(g), ctypes.c_uint32(n), _ptr(self._ranges), _ptr(self._slots), _ptr(self._temp),
-                                             ctypes.c_uint64(self._temp.numel()), ctypes.byref(nh), _stream_ptr(dev)))
+        _check(lib().nvbio_qgram_filter_rank(index._h, _ptr(g), n, _ptr(self._ranges), _ptr(self._slots), _ptr(self._temp), self._temp.numel(),
+                                             ctypes.byref(nh), _stream_ptr(dev)))
         self._n_hits = nh.value
         return self._n_hits
 
@@ -1095,9 +1073,8 @@ class QGramFilter:
         if hits is None:
             hits = torch.empty((max(end - begin, 0), cols), dtype=torch.int32, device=self._index.device)
         if end > begin:
-            _check(lib().nvbio_qgram_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._indices),
-                                                   ctypes.c_uint32(self._n_queries), ctypes.c_uint64(begin), ctypes.c_uint64(end), _ptr(hits),
-                                                   _stream_ptr(self._index.device)))
+            _check(lib().nvbio_qgram_filter_locate(self._index._h, _ptr(self._ranges), _ptr(self._slots), _ptr(self._indices), self._n_queries, begin,
+                                                   end, _ptr(hits), _stream_ptr(self._index.device)))
         return hits
 
     def merge(self, interval, hits, is_set=None):
@@ -1109,16 +1086,15 @@ class QGramFilter:
         dev = hits.device
         n = hits.shape[0]
         tb = ctypes.c_uint64(0)
-        _check(lib().nvbio_qgram_filter_merge_temp_bytes(ctypes.c_int(1 if is_set else 0), ctypes.c_uint32(n), ctypes.byref(tb)))
+        _check(lib().nvbio_qgram_filter_merge_temp_bytes(1 if is_set else 0, n, ctypes.byref(tb)))
         self._grow_temp(tb.value, dev)
         if self._merged is None or self._merged.shape[0] < max(n, 1) or self._merged.device != dev:
             self._merged = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
             self._counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         nm = ctypes.c_uint32(0)
         hits = hits.contiguous()
-        _check(lib().nvbio_qgram_filter_merge(FMIndex._dev_index(dev), ctypes.c_int(1 if is_set else 0), ctypes.c_uint32(interval), _ptr(hits),
-                                              ctypes.c_uint32(n), _ptr(self._merged), _ptr(self._counts), ctypes.byref(nm), _ptr(self._temp),
-                                              ctypes.c_uint64(self._temp.numel()), _stream_ptr(dev)))
+        _check(lib().nvbio_qgram_filter_merge(FMIndex._dev_index(dev), 1 if is_set else 0, interval, _ptr(hits), n, _ptr(self._merged),
+                                              _ptr(self._counts), ctypes.byref(nm), _ptr(self._temp), self._temp.numel(), _stream_ptr(dev)))
         m = nm.value
         merged = self._merged.view(-1)[:2 * m].view(m, 2) if is_set else self._merged.view(-1)[:m]
         return merged.clone(), self._counts[:m].clone()
@@ -1223,13 +1199,13 @@ class AlignmentBatch:
 def seed_locus_bytes(length):
     """nvbio_seed_locus_bytes: the size of the seed locus lines of a text (FMIndex.build_seed_locus(out=))"""
     b = ctypes.c_uint64()
-    _check(lib().nvbio_seed_locus_bytes(ctypes.c_uint32(length), ctypes.byref(b)))
+    _check(lib().nvbio_seed_locus_bytes(length, ctypes.byref(b)))
     return b.value
 
 
 def text_planes_bytes(length):
     b = ctypes.c_uint64()
-    _check(lib().nvbio_text_planes_bytes(ctypes.c_uint32(length), ctypes.byref(b)))
+    _check(lib().nvbio_text_planes_bytes(length, ctypes.byref(b)))
     return b.value
 
 
@@ -1240,7 +1216,7 @@ def build_text_planes(text2, length, device="cuda:0", out=None):
     t = _dev_tensor(text2, torch.int32, device)
     if out is None:
         out = torch.empty(text_planes_bytes(length), dtype=torch.uint8, device=device)
-    _check(lib().nvbio_text_planes_build(FMIndex._dev_index(device), _ptr(t), ctypes.c_uint32(length), _ptr(out), _stream_ptr(device)))
+    _check(lib().nvbio_text_planes_build(FMIndex._dev_index(device), _ptr(t), length, _ptr(out), _stream_ptr(device)))
     return out
 
 
@@ -1281,14 +1257,12 @@ class BatchedBandedAlignmentScore:
             if per_job and (min_scores.dtype != torch.int32 or min_scores.numel() != batch.n):
                 raise NvbioError(1, "min_scores: int32 per job")
             _check(lib().nvbio_banded_gotoh_score_staged(
-                FMIndex._dev_index(batch.device), ctypes.c_uint32(self.band_len), ctypes.c_int(self.aligner.type),
-                ctypes.byref(self.aligner.scheme.c), ctypes.byref(bs), _ptr(min_scores) if per_job else None,
-                ctypes.c_int32(SCORE_MIN if min_scores is None else (0 if per_job else int(min_scores))),
-                _ptr(scores), _ptr(sinks), _stream_ptr(batch.device)))
+                FMIndex._dev_index(batch.device), self.band_len, self.aligner.type, ctypes.byref(self.aligner.scheme.c), ctypes.byref(bs),
+                _ptr(min_scores) if per_job else None, SCORE_MIN if min_scores is None else (0 if per_job else int(min_scores)), _ptr(scores),
+                _ptr(sinks), _stream_ptr(batch.device)))
             return scores, sinks
         fn = lib().nvbio_banded_sw_score if sw is not None else lib().nvbio_banded_gotoh_score
-        _check(fn(FMIndex._dev_index(batch.device), ctypes.c_uint32(self.band_len), ctypes.c_int(self.aligner.type),
-                  ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c),
+        _check(fn(FMIndex._dev_index(batch.device), self.band_len, self.aligner.type, ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c),
                   ctypes.byref(bs), _ptr(scores), _ptr(sinks), _stream_ptr(batch.device)))
         return scores, sinks
 
@@ -1306,9 +1280,8 @@ def banded_gotoh_score_routes(band_len, aligner, batch):
     sinks = torch.empty((batch.n, 2), dtype=torch.int32, device=batch.device)
     routes = torch.empty(batch.n, dtype=torch.uint8, device=batch.device)
     bs = batch.c_struct()
-    _check(lib().nvbio_banded_gotoh_score_routes(FMIndex._dev_index(batch.device), ctypes.c_uint32(int(band_len)), ctypes.c_int(aligner.type),
-                                                 ctypes.byref(aligner.scheme.c), ctypes.byref(bs), _ptr(scores), _ptr(sinks), _ptr(routes),
-                                                 _stream_ptr(batch.device)))
+    _check(lib().nvbio_banded_gotoh_score_routes(FMIndex._dev_index(batch.device), int(band_len), aligner.type, ctypes.byref(aligner.scheme.c),
+                                                 ctypes.byref(bs), _ptr(scores), _ptr(sinks), _ptr(routes), _stream_ptr(batch.device)))
     return scores, sinks, routes
 
 
@@ -1332,10 +1305,9 @@ def banded_gotoh_traceback_routes(band_len, aligner, batch, cigar_stride=64, tem
     band_off = torch.empty(n, dtype=torch.uint8, device=dev)
     bs = batch.c_struct()
     _check(lib().nvbio_banded_gotoh_traceback_routes(
-        FMIndex._dev_index(dev), ctypes.c_uint32(int(band_len)), ctypes.c_int(aligner.type), ctypes.byref(aligner.scheme.c), ctypes.byref(bs),
-        _ptr(scores), _ptr(sources), _ptr(sinks), _ptr(cigars), ctypes.c_uint32(cigar_stride), _ptr(lens),
-        ctypes.c_uint32(TRACEBACK_SINKS_GIVEN if given else 0), _ptr(temp),
-        ctypes.c_uint64(0 if temp is None else temp.numel() * temp.element_size()), _ptr(routes), _ptr(band_off), _stream_ptr(dev)))
+        FMIndex._dev_index(dev), int(band_len), aligner.type, ctypes.byref(aligner.scheme.c), ctypes.byref(bs), _ptr(scores), _ptr(sources),
+        _ptr(sinks), _ptr(cigars), cigar_stride, _ptr(lens), TRACEBACK_SINKS_GIVEN if given else 0, _ptr(temp),
+        0 if temp is None else temp.numel() * temp.element_size(), _ptr(routes), _ptr(band_off), _stream_ptr(dev)))
     return scores, sources, sinks, cigars, lens, routes, band_off
 
 
@@ -1364,7 +1336,7 @@ class BatchedBandedAlignmentTraceback:
     def min_temp_storage(self, batch):
         out = ctypes.c_uint64(0)
         bs = batch.c_struct()
-        _check(lib().nvbio_banded_gotoh_traceback_temp_bytes(ctypes.byref(bs), ctypes.c_uint32(self.band_len), ctypes.byref(out)))
+        _check(lib().nvbio_banded_gotoh_traceback_temp_bytes(ctypes.byref(bs), self.band_len, ctypes.byref(out)))
         return int(out.value)
 
     def enact(self, batch, cigar_stride=64, temp=None, scores=None, sinks=None):
@@ -1383,10 +1355,9 @@ class BatchedBandedAlignmentTraceback:
         sw = getattr(self.aligner, "sw", None)                      # the linear-gap Smith-Waterman / edit-distance aligners
         fn = lib().nvbio_banded_sw_traceback if sw is not None else lib().nvbio_banded_gotoh_traceback
         _check(fn(
-            FMIndex._dev_index(dev), ctypes.c_uint32(self.band_len), ctypes.c_int(self.aligner.type),
-            ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c), ctypes.byref(bs), _ptr(scores), _ptr(sources), _ptr(sinks), _ptr(cigars),
-            ctypes.c_uint32(cigar_stride), _ptr(lens), ctypes.c_uint32(TRACEBACK_SINKS_GIVEN if given else 0), _ptr(temp),
-            ctypes.c_uint64(0 if temp is None else temp.numel() * temp.element_size()), _stream_ptr(dev)))
+            FMIndex._dev_index(dev), self.band_len, self.aligner.type, ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c),
+            ctypes.byref(bs), _ptr(scores), _ptr(sources), _ptr(sinks), _ptr(cigars), cigar_stride, _ptr(lens), TRACEBACK_SINKS_GIVEN if given else 0,
+            _ptr(temp), 0 if temp is None else temp.numel() * temp.element_size(), _stream_ptr(dev)))
         return scores, sources, sinks, cigars, lens
 
 
@@ -1400,8 +1371,7 @@ class BatchedAlignmentTraceback:
     def min_temp_storage(self, batch, max_pattern_len, max_text_len):
         out = ctypes.c_uint64(0)
         bs = batch.c_struct()
-        _check(lib().nvbio_full_gotoh_traceback_temp_bytes(ctypes.byref(bs), ctypes.c_uint32(max_pattern_len),
-                                                           ctypes.c_uint32(max_text_len), ctypes.byref(out)))
+        _check(lib().nvbio_full_gotoh_traceback_temp_bytes(ctypes.byref(bs), max_pattern_len, max_text_len, ctypes.byref(out)))
         return int(out.value)
 
     def enact(self, batch, max_pattern_len, max_text_len, min_scores=None, cigar_stride=64, temp=None, scores=None, sinks=None):
@@ -1421,10 +1391,9 @@ class BatchedAlignmentTraceback:
         sw = getattr(self.aligner, "sw", None)                      # the linear-gap Smith-Waterman / edit-distance aligners
         fn = lib().nvbio_full_sw_traceback if sw is not None else lib().nvbio_full_gotoh_traceback
         _check(fn(
-            FMIndex._dev_index(dev), ctypes.c_int(self.aligner.type), ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c), ctypes.byref(bs),
-            ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len), _ptr(ms), _ptr(scores), _ptr(sources), _ptr(sinks),
-            _ptr(cigars), ctypes.c_uint32(cigar_stride), _ptr(lens), ctypes.c_uint32(TRACEBACK_SINKS_GIVEN if given else 0),
-            _ptr(temp), ctypes.c_uint64(0 if temp is None else temp.numel() * temp.element_size()), _stream_ptr(dev)))
+            FMIndex._dev_index(dev), self.aligner.type, ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c), ctypes.byref(bs),
+            max_pattern_len, max_text_len, _ptr(ms), _ptr(scores), _ptr(sources), _ptr(sinks), _ptr(cigars), cigar_stride, _ptr(lens),
+            TRACEBACK_SINKS_GIVEN if given else 0, _ptr(temp), 0 if temp is None else temp.numel() * temp.element_size(), _stream_ptr(dev)))
         return scores, sources, sinks, cigars, lens
 
 
@@ -1437,8 +1406,8 @@ def finish_alignment(batch, sources, cigars, cigar_lens, mds_stride=0):
     mds = torch.zeros((n, mds_stride), dtype=torch.uint8, device=dev) if mds_stride else None
     ml = torch.empty(n, dtype=torch.int32, device=dev) if mds_stride else None
     bs = batch.c_struct()
-    _check(lib().nvbio_finish_alignment(FMIndex._dev_index(dev), ctypes.byref(bs), _ptr(sources), _ptr(cigars), ctypes.c_uint32(cigars.shape[1]),
-                                        _ptr(cigar_lens), _ptr(ed), _ptr(mds), ctypes.c_uint32(mds_stride), _ptr(ml), _stream_ptr(dev)))
+    _check(lib().nvbio_finish_alignment(FMIndex._dev_index(dev), ctypes.byref(bs), _ptr(sources), _ptr(cigars), cigars.shape[1], _ptr(cigar_lens),
+                                        _ptr(ed), _ptr(mds), mds_stride, _ptr(ml), _stream_ptr(dev)))
     return ed, mds, ml
 
 
@@ -1468,11 +1437,9 @@ class BatchedAlignmentScore:
         fn = lib().nvbio_full_sw_score if sw is not None else lib().nvbio_full_gotoh_score
         rows = max_pattern_len if self.text_blocking else max_text_len
         temp = _scratch(batch.device, batch.n * max(rows, 1) * 4)
-        _check(fn(FMIndex._dev_index(batch.device), ctypes.c_int(self.aligner.type),
-                  ctypes.c_int(1 if self.text_blocking else 0),
-                  ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c), ctypes.byref(bs),
-                  ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len), _ptr(ms),
-                  _ptr(scores), _ptr(sinks), _ptr(temp), ctypes.c_uint64(temp.numel()), _stream_ptr(batch.device)))
+        _check(fn(FMIndex._dev_index(batch.device), self.aligner.type, 1 if self.text_blocking else 0,
+                  ctypes.byref(sw.c if sw is not None else self.aligner.scheme.c), ctypes.byref(bs), max_pattern_len, max_text_len, _ptr(ms),
+                  _ptr(scores), _ptr(sinks), _ptr(temp), temp.numel(), _stream_ptr(batch.device)))
         return scores, sinks
 
 
@@ -1483,9 +1450,9 @@ def batch_banded_alignment_score_best2(band_len, aligner, batch, distinct_dist=0
     sc = [torch.empty(batch.n, dtype=torch.int32, device=batch.device) for _ in range(2)]
     sk = [torch.empty((batch.n, 2), dtype=torch.int32, device=batch.device) for _ in range(2)]
     bs = batch.c_struct()
-    _check(lib().nvbio_banded_gotoh_score_best2(FMIndex._dev_index(batch.device), ctypes.c_uint32(band_len), ctypes.c_int(aligner.type),
-                                                ctypes.byref(aligner.scheme.c), ctypes.byref(bs), ctypes.c_uint32(distinct_dist),
-                                                _ptr(sc[0]), _ptr(sk[0]), _ptr(sc[1]), _ptr(sk[1]), _stream_ptr(batch.device)))
+    _check(lib().nvbio_banded_gotoh_score_best2(FMIndex._dev_index(batch.device), band_len, aligner.type, ctypes.byref(aligner.scheme.c),
+                                                ctypes.byref(bs), distinct_dist, _ptr(sc[0]), _ptr(sk[0]), _ptr(sc[1]), _ptr(sk[1]),
+                                                _stream_ptr(batch.device)))
     return sc[0], sk[0], sc[1], sk[1]
 
 
@@ -1496,10 +1463,9 @@ def batch_alignment_score_best2(aligner, batch, max_pattern_len, max_text_len, d
     sk = [torch.empty((batch.n, 2), dtype=torch.int32, device=batch.device) for _ in range(2)]
     ms = _dev_tensor(min_scores, torch.int32, batch.device)
     bs = batch.c_struct()
-    _check(lib().nvbio_full_gotoh_score_best2(FMIndex._dev_index(batch.device), ctypes.c_int(aligner.type), ctypes.c_int(1 if text_blocking else 0),
-                                              ctypes.byref(aligner.scheme.c), ctypes.byref(bs), ctypes.c_uint32(max_pattern_len),
-                                              ctypes.c_uint32(max_text_len), _ptr(ms), ctypes.c_uint32(distinct_dist),
-                                              _ptr(sc[0]), _ptr(sk[0]), _ptr(sc[1]), _ptr(sk[1]), _stream_ptr(batch.device)))
+    _check(lib().nvbio_full_gotoh_score_best2(FMIndex._dev_index(batch.device), aligner.type, 1 if text_blocking else 0,
+                                              ctypes.byref(aligner.scheme.c), ctypes.byref(bs), max_pattern_len, max_text_len, _ptr(ms),
+                                              distinct_dist, _ptr(sc[0]), _ptr(sk[0]), _ptr(sc[1]), _ptr(sk[1]), _stream_ptr(batch.device)))
     return sc[0], sk[0], sc[1], sk[1]
 
 
@@ -1507,18 +1473,16 @@ def hits_to_diagonals(hits, seeds_per_read, seed_interval, seed_len, read_len, s
     """hit_to_diagonal (examples/fmmap/fmmap.cu:92-117): int64 keys read<<34 | strand<<33 | diagonal+1024"""
     torch = _torch()
     keys = torch.empty(hits.shape[0], dtype=torch.int64, device=hits.device)
-    _check(lib().nvbio_hits_to_diagonals(FMIndex._dev_index(hits.device), _ptr(hits), ctypes.c_uint64(hits.shape[0]),
-                                         ctypes.c_uint32(seeds_per_read), ctypes.c_uint32(seed_interval),
-                                         ctypes.c_uint32(seed_len), ctypes.c_uint32(read_len), ctypes.c_uint32(strand),
-                                         _ptr(keys), _stream_ptr(hits.device)))
+    _check(lib().nvbio_hits_to_diagonals(FMIndex._dev_index(hits.device), _ptr(hits), hits.shape[0], seeds_per_read, seed_interval, seed_len,
+                                         read_len, strand, _ptr(keys), _stream_ptr(hits.device)))
     return keys
 
 
 def best_candidate_reduce(keys, scores, sinks, win_begin, best):
     """best[read] = max(best[read], selection key of each candidate) by 64-bit atomic max (nvbio_best_candidate_reduce);
     best: int64 tensor, zero-initialised by the caller, one entry per read"""
-    _check(lib().nvbio_best_candidate_reduce(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(win_begin),
-                                             ctypes.c_uint64(keys.shape[0]), _ptr(best), _stream_ptr(keys.device)))
+    _check(lib().nvbio_best_candidate_reduce(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(win_begin), keys.shape[0],
+                                             _ptr(best), _stream_ptr(keys.device)))
     return best
 
 
@@ -1528,8 +1492,7 @@ def best_candidate_unpack(best):
     n, dev = best.shape[0], best.device
     score = torch.empty(n, dtype=torch.int32, device=dev); pos = torch.empty(n, dtype=torch.int64, device=dev)
     rc = torch.empty(n, dtype=torch.uint8, device=dev)
-    _check(lib().nvbio_best_candidate_unpack(FMIndex._dev_index(dev), _ptr(best), ctypes.c_uint32(n), _ptr(score), _ptr(pos), _ptr(rc),
-                                             _stream_ptr(dev)))
+    _check(lib().nvbio_best_candidate_unpack(FMIndex._dev_index(dev), _ptr(best), n, _ptr(score), _ptr(pos), _ptr(rc), _stream_ptr(dev)))
     return score, pos, rc
 
 
@@ -1538,9 +1501,8 @@ def best_candidate_windows(keys, scores, sinks, win_begin, best, best_wb, best_l
     the final keys of best_candidate_reduce) into best_wb / best_locus (int64 per read, initialised to -1 by the caller)"""
     if keys.numel() == 0:
         return
-    _check(lib().nvbio_best_candidate_windows(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(win_begin),
-                                              ctypes.c_uint64(keys.numel()), _ptr(best), _ptr(best_wb), _ptr(best_locus),
-                                              _stream_ptr(keys.device)))
+    _check(lib().nvbio_best_candidate_windows(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(win_begin), keys.numel(),
+                                              _ptr(best), _ptr(best_wb), _ptr(best_locus), _stream_ptr(keys.device)))
 
 
 def traceback_best_batch(best, best_wb, read_len, band, genome_len, min_score, read_offsets=None, min_scores=None):
@@ -1552,12 +1514,11 @@ def traceback_best_batch(best, best_wb, read_len, band, genome_len, min_score, r
     wb = torch.empty(n, dtype=torch.int32, device=dev); we = torch.empty(n, dtype=torch.int32, device=dev)
     scores = torch.empty(n, dtype=torch.int32, device=dev); sinks = torch.empty((n, 2), dtype=torch.int32, device=dev)
     if read_offsets is not None:                     # ragged reads (read_len / min_score are ignored)
-        _check(lib().nvbio_traceback_best_batch_ragged(FMIndex._dev_index(dev), _ptr(best), _ptr(best_wb), ctypes.c_uint32(n), _ptr(read_offsets),
-                                                       ctypes.c_uint32(band), ctypes.c_uint32(genome_len), _ptr(min_scores), _ptr(flags),
-                                                       _ptr(wb), _ptr(we), _ptr(scores), _ptr(sinks), _stream_ptr(dev)))
+        _check(lib().nvbio_traceback_best_batch_ragged(FMIndex._dev_index(dev), _ptr(best), _ptr(best_wb), n, _ptr(read_offsets), band, genome_len,
+                                                       _ptr(min_scores), _ptr(flags), _ptr(wb), _ptr(we), _ptr(scores), _ptr(sinks),
+                                                       _stream_ptr(dev)))
         return flags, wb, we, scores, sinks
-    _check(lib().nvbio_traceback_best_batch(FMIndex._dev_index(dev), _ptr(best), _ptr(best_wb), ctypes.c_uint32(n), ctypes.c_uint32(read_len),
-                                            ctypes.c_uint32(band), ctypes.c_uint32(genome_len), ctypes.c_int32(min_score), _ptr(flags),
+    _check(lib().nvbio_traceback_best_batch(FMIndex._dev_index(dev), _ptr(best), _ptr(best_wb), n, read_len, band, genome_len, min_score, _ptr(flags),
                                             _ptr(wb), _ptr(we), _ptr(scores), _ptr(sinks), _stream_ptr(dev)))
     return flags, wb, we, scores, sinks
 
@@ -1590,12 +1551,11 @@ def second_candidate_reduce(keys, scores, sinks, wb, best, distinct_dist, worst_
     best must already hold the final per-read maxima over ALL candidates; second is zero-initialised by the caller"""
     if read_offsets is not None:                     # ragged reads: distinct_dist = read_len / 2 and worst_score = min_score - 1 per read
         _check(lib().nvbio_second_candidate_reduce_ragged(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(wb),
-                                                          ctypes.c_uint64(keys.shape[0]), _ptr(best), _ptr(read_offsets), _ptr(min_scores),
-                                                          _ptr(second), _stream_ptr(keys.device)))
+                                                          keys.shape[0], _ptr(best), _ptr(read_offsets), _ptr(min_scores), _ptr(second),
+                                                          _stream_ptr(keys.device)))
         return second
-    _check(lib().nvbio_second_candidate_reduce(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(wb),
-                                               ctypes.c_uint64(keys.shape[0]), _ptr(best), ctypes.c_uint32(distinct_dist),
-                                               ctypes.c_int32(worst_score), _ptr(second), _stream_ptr(keys.device)))
+    _check(lib().nvbio_second_candidate_reduce(FMIndex._dev_index(keys.device), _ptr(keys), _ptr(scores), _ptr(sinks), _ptr(wb), keys.shape[0],
+                                               _ptr(best), distinct_dist, worst_score, _ptr(second), _stream_ptr(keys.device)))
     return second
 
 
@@ -1607,13 +1567,12 @@ def mapq(best, second, perfect_score, min_score, monotone, version=2, read_offse
     q = torch.empty(R, dtype=torch.uint8, device=best.device)
     ss = torch.empty(R, dtype=torch.int32, device=best.device)
     if read_offsets is not None:                     # ragged reads: perfect score = match x length, min score per read
-        _check(lib().nvbio_mapq_ragged(FMIndex._dev_index(best.device), _ptr(best), _ptr(second) if second is not None else None,
-                                       ctypes.c_uint32(R), ctypes.c_int32(int(version)), ctypes.c_int32(int(match)), _ptr(read_offsets),
-                                       _ptr(min_scores), _ptr(ss), _ptr(q), _stream_ptr(best.device)))
+        _check(lib().nvbio_mapq_ragged(FMIndex._dev_index(best.device), _ptr(best), _ptr(second) if second is not None else None, R, int(version),
+                                       int(match), _ptr(read_offsets), _ptr(min_scores), _ptr(ss), _ptr(q), _stream_ptr(best.device)))
         return q, ss
     prm = _MapqParams(int(version), 1 if monotone else 0, int(perfect_score), int(min_score))
-    _check(lib().nvbio_mapq(FMIndex._dev_index(best.device), _ptr(best), _ptr(second) if second is not None else None,
-                            ctypes.c_uint32(R), ctypes.byref(prm), _ptr(ss), _ptr(q), _stream_ptr(best.device)))
+    _check(lib().nvbio_mapq(FMIndex._dev_index(best.device), _ptr(best), _ptr(second) if second is not None else None, R, ctypes.byref(prm), _ptr(ss),
+                            _ptr(q), _stream_ptr(best.device)))
     return q, ss
 
 
@@ -1680,12 +1639,11 @@ def finish_reads(keys, scores, sinks, wb, tile_offsets, reads_per_tile, n_reads,
     prm = _MapqParams(int(version), 1 if monotone else 0, int(perfect_score), int(min_score))
     n = int(keys.numel())
     _check(lib().nvbio_finish_reads(
-        FMIndex._dev_index(dev), _ptr(keys) if n else None, _ptr(scores) if n else None, _ptr(sinks) if n else None, _ptr(wb) if n else None,
-        ctypes.c_uint64(n), _ptr(tile_offsets), ctypes.c_uint32(n_tiles), ctypes.c_uint32(int(reads_per_tile)), ctypes.c_uint32(R),
-        ctypes.c_uint32(int(distinct_dist)), ctypes.c_int32(int(worst_score)), ctypes.byref(prm), ctypes.c_int32(int(match)),
-        _ptr(read_offsets) if read_offsets is not None else None, _ptr(min_scores) if min_scores is not None else None,
-        _ptr(out["best"]), _ptr(out["second"]), _ptr(out["best_score"]), _ptr(out["best_pos"]), _ptr(out["best_rc"]), _ptr(out["mapq"]),
-        _ptr(out["second_score"]), _ptr(st.word), _stream_ptr(dev)))
+        FMIndex._dev_index(dev), _ptr(keys) if n else None, _ptr(scores) if n else None, _ptr(sinks) if n else None, _ptr(wb) if n else None, n,
+        _ptr(tile_offsets), n_tiles, int(reads_per_tile), R, int(distinct_dist), int(worst_score), ctypes.byref(prm), int(match),
+        _ptr(read_offsets) if read_offsets is not None else None, _ptr(min_scores) if min_scores is not None else None, _ptr(out["best"]),
+        _ptr(out["second"]), _ptr(out["best_score"]), _ptr(out["best_pos"]), _ptr(out["best_rc"]), _ptr(out["mapq"]), _ptr(out["second_score"]),
+        _ptr(st.word), _stream_ptr(dev)))
     st.record()
     if check:
         st.check(wait=True)
@@ -1700,10 +1658,8 @@ def opposite_mate_windows(g_pos, anchor_rc, anchor_len, opposite_gapped_len, anc
     wb = torch.empty(n, dtype=torch.int32, device=dev); we = torch.empty(n, dtype=torch.int32, device=dev)
     flags = torch.empty(n, dtype=torch.uint8, device=dev); valid = torch.empty(n, dtype=torch.uint8, device=dev)
     _check(lib().nvbio_opposite_mate_windows(
-        FMIndex._dev_index(dev), _ptr(g_pos), _ptr(anchor_rc), ctypes.c_uint32(n), ctypes.c_uint32(anchor_len),
-        ctypes.c_uint32(opposite_gapped_len), ctypes.c_uint32(anchor), ctypes.c_uint32(policy), ctypes.c_uint32(min_frag_len),
-        ctypes.c_uint32(max_frag_len), ctypes.c_uint32(1 if overlap else 0), ctypes.c_uint32(genome_len), _ptr(wb), _ptr(we),
-        _ptr(flags), _ptr(valid), _stream_ptr(dev)))
+        FMIndex._dev_index(dev), _ptr(g_pos), _ptr(anchor_rc), n, anchor_len, opposite_gapped_len, anchor, policy, min_frag_len, max_frag_len,
+        1 if overlap else 0, genome_len, _ptr(wb), _ptr(we), _ptr(flags), _ptr(valid), _stream_ptr(dev)))
     return wb, we, flags, valid
 
 
@@ -1716,13 +1672,11 @@ def diagonals_to_windows(keys, band, read_len, genome_len, read_offsets=None):
     wb = torch.empty(n, dtype=torch.int32, device=dev)
     we = torch.empty(n, dtype=torch.int32, device=dev)
     if read_offsets is not None:                     # ragged reads: window end = begin + band + the read's own length
-        _check(lib().nvbio_diagonals_to_windows_ragged(FMIndex._dev_index(dev), _ptr(keys), ctypes.c_uint64(n), ctypes.c_uint32(band),
-                                                       _ptr(read_offsets), ctypes.c_uint32(genome_len), _ptr(rid), _ptr(fl),
-                                                       _ptr(wb), _ptr(we), _stream_ptr(dev)))
+        _check(lib().nvbio_diagonals_to_windows_ragged(FMIndex._dev_index(dev), _ptr(keys), n, band, _ptr(read_offsets), genome_len, _ptr(rid),
+                                                       _ptr(fl), _ptr(wb), _ptr(we), _stream_ptr(dev)))
         return rid, fl, wb, we
-    _check(lib().nvbio_diagonals_to_windows(FMIndex._dev_index(dev), _ptr(keys), ctypes.c_uint64(n), ctypes.c_uint32(band),
-                                            ctypes.c_uint32(read_len), ctypes.c_uint32(genome_len), _ptr(rid), _ptr(fl),
-                                            _ptr(wb), _ptr(we), _stream_ptr(dev)))
+    _check(lib().nvbio_diagonals_to_windows(FMIndex._dev_index(dev), _ptr(keys), n, band, read_len, genome_len, _ptr(rid), _ptr(fl), _ptr(wb),
+                                            _ptr(we), _stream_ptr(dev)))
     return rid, fl, wb, we
 
 
@@ -1762,17 +1716,16 @@ def score_stream_flatten(hits, read_index, band_len, genome_len, reads_reversed=
     wb = torch.empty(hits.n, dtype=torch.int32, device=dev)
     we = torch.empty(hits.n, dtype=torch.int32, device=dev)
     hq = hits.c_struct()
-    _check(lib().nvbio_score_stream_flatten(FMIndex._dev_index(dev), ctypes.byref(hq), _ptr(ri), ctypes.c_uint32(band_len),
-                                            ctypes.c_uint32(genome_len), ctypes.c_uint32(1 if reads_reversed else 0), _ptr(rid), _ptr(flags),
-                                            _ptr(wb), _ptr(we), _stream_ptr(dev)))
+    _check(lib().nvbio_score_stream_flatten(FMIndex._dev_index(dev), ctypes.byref(hq), _ptr(ri), band_len, genome_len, 1 if reads_reversed else 0,
+                                            _ptr(rid), _ptr(flags), _ptr(wb), _ptr(we), _stream_ptr(dev)))
     return rid, flags, wb, we
 
 
 def score_stream_output(hits, scores, sinks, win_begin, worst_score=-65536):
     """BestScoreStream::output for the whole stream (nvbio_score_stream_output): fills hits.score / hits.sink"""
     hq = hits.c_struct()
-    _check(lib().nvbio_score_stream_output(FMIndex._dev_index(hits.device), ctypes.byref(hq), _ptr(scores), _ptr(sinks), _ptr(win_begin),
-                                           ctypes.c_int32(worst_score), _stream_ptr(hits.device)))
+    _check(lib().nvbio_score_stream_output(FMIndex._dev_index(hits.device), ctypes.byref(hq), _ptr(scores), _ptr(sinks), _ptr(win_begin), worst_score,
+                                           _stream_ptr(hits.device)))
 
 
 # ---- nvBowtie's seed-hit deques, selection and effort-limited reduction (include/nvbio_amd.h: nvbio_seed_hits_*) -----------------
@@ -1793,8 +1746,8 @@ def seed_hits_map(fw_ranges, rc_ranges, params, n_reads, deques, sizes, reseed=N
     """the exact seed mapper's deque bookkeeping (nvbio_seed_hits_map): fills deques [R, capacity, 2], sizes [R], reseed [R] for the
     n_reads reads of read_queue (None: reads 0..n_reads-1)"""
     dev = deques.device
-    _check(lib().nvbio_seed_hits_map(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), _ptr(read_queue), ctypes.c_uint32(n_reads),
-                                     ctypes.byref(params.c), _ptr(deques), _ptr(sizes), _ptr(reseed), _stream_ptr(dev)))
+    _check(lib().nvbio_seed_hits_map(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), _ptr(read_queue), n_reads, ctypes.byref(params.c),
+                                     _ptr(deques), _ptr(sizes), _ptr(reseed), _stream_ptr(dev)))
 
 
 def seed_hits_approx_capacity(params):
@@ -1807,8 +1760,8 @@ def seed_hits_map_approx(fmi, rfmi, reads, read_bits, params, n_reads, deques, s
     """nvBowtie's approximate seed mapper (nvbio_seed_hits_map_approx): fmi = the forward index, rfmi = the index of the reversed text;
     reads = the stored (reversed) reads of params.read_len symbols back to back; deques [R, seed_hits_approx_capacity, 2]"""
     dev = deques.device
-    _check(lib().nvbio_seed_hits_map_approx(fmi._h, rfmi._h, _ptr(reads), ctypes.c_uint32(read_bits), _ptr(read_queue), ctypes.c_uint32(n_reads),
-                                            ctypes.byref(params.c), _ptr(deques), _ptr(sizes), _ptr(reseed), _stream_ptr(dev)))
+    _check(lib().nvbio_seed_hits_map_approx(fmi._h, rfmi._h, _ptr(reads), read_bits, _ptr(read_queue), n_reads, ctypes.byref(params.c), _ptr(deques),
+                                            _ptr(sizes), _ptr(reseed), _stream_ptr(dev)))
 
 
 def seed_hits_select(active, trys, params, deques, sizes, hits, active_out, count):
@@ -1816,9 +1769,8 @@ def seed_hits_select(active, trys, params, deques, sizes, hits, active_out, coun
     count int32 [1] on the device receives the number of slots written"""
     dev = deques.device
     hq = hits.c_struct()
-    _check(lib().nvbio_seed_hits_select(FMIndex._dev_index(dev), _ptr(active), ctypes.c_uint32(active.numel()), _ptr(trys),
-                                        ctypes.c_uint32(params.capacity()), _ptr(deques), _ptr(sizes), _ptr(active_out), ctypes.byref(hq),
-                                        _ptr(count), _stream_ptr(dev)))
+    _check(lib().nvbio_seed_hits_select(FMIndex._dev_index(dev), _ptr(active), active.numel(), _ptr(trys), params.capacity(), _ptr(deques),
+                                        _ptr(sizes), _ptr(active_out), ctypes.byref(hq), _ptr(count), _stream_ptr(dev)))
 
 
 def seed_hits_loc(positions, hits):
@@ -1830,9 +1782,8 @@ def score_reduce_effort(active, hits, read_len, n_ext, params, best, best_rc, tr
     """score_reduce_kernel with the best-approx effort rules (nvbio_score_reduce_effort): best int32 [R, 4] = (a1 score, a1 locus,
     a2 score, a2 locus), best_rc uint8 [R], trys int32 [R], sizes int32 [R] (erased deques get 0)"""
     hq = hits.c_struct()
-    _check(lib().nvbio_score_reduce_effort(FMIndex._dev_index(hits.device), _ptr(active), ctypes.byref(hq), ctypes.c_uint32(read_len),
-                                           ctypes.c_uint32(n_ext), ctypes.byref(params.c), _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes),
-                                           _stream_ptr(hits.device)))
+    _check(lib().nvbio_score_reduce_effort(FMIndex._dev_index(hits.device), _ptr(active), ctypes.byref(hq), read_len, n_ext, ctypes.byref(params.c),
+                                           _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
 
 
 # ---- the same calls over reads of different lengths (include/nvbio_amd.h: nvbio_ragged_seed_layout and the *_ragged calls) -------------
@@ -1848,39 +1799,36 @@ class RaggedSeedLayout:
 def read_queue_begin_ragged(queue, n, layout, n_symbols, top_seed, max_effort_init, seed_offsets=None, active=None, trys=None):
     """nvbio_read_queue_begin_ragged: seed_offsets int32 [n * seeds_per_read] (one explicit offset per seed slot), active int32 [n], trys int32 [R]"""
     dev = layout.read_offsets.device
-    _check(lib().nvbio_read_queue_begin_ragged(FMIndex._dev_index(dev), _ptr(queue), ctypes.c_uint32(n), ctypes.byref(layout.c), ctypes.c_uint32(n_symbols),
-                                               ctypes.c_uint32(top_seed), ctypes.c_uint32(max_effort_init), _ptr(seed_offsets), _ptr(active), _ptr(trys),
-                                               _stream_ptr(dev)))
+    _check(lib().nvbio_read_queue_begin_ragged(FMIndex._dev_index(dev), _ptr(queue), n, ctypes.byref(layout.c), n_symbols, top_seed, max_effort_init,
+                                               _ptr(seed_offsets), _ptr(active), _ptr(trys), _stream_ptr(dev)))
 
 
 def seed_hits_map_ragged(fw_ranges, rc_ranges, layout, n_reads, max_hits, rep_seeds, deques, sizes, reseed=None, read_queue=None):
     """nvbio_seed_hits_map_ragged: the exact mapper's deques for the n_reads reads of read_queue (None: reads 0..n_reads-1) of a ragged batch"""
     dev = deques.device
-    _check(lib().nvbio_seed_hits_map_ragged(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), _ptr(read_queue), ctypes.c_uint32(n_reads),
-                                            ctypes.byref(layout.c), ctypes.c_uint32(max_hits), ctypes.c_uint32(rep_seeds), _ptr(deques), _ptr(sizes),
-                                            _ptr(reseed), _stream_ptr(dev)))
+    _check(lib().nvbio_seed_hits_map_ragged(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), _ptr(read_queue), n_reads,
+                                            ctypes.byref(layout.c), max_hits, rep_seeds, _ptr(deques), _ptr(sizes), _ptr(reseed), _stream_ptr(dev)))
 
 
 def best_approx_init_ragged(min_scores, best, best_rc):
     """nvbio_best_approx_init_ragged: best int32 [R, 4] = (min_scores[r], -1, min_scores[r], -1), best_rc uint8 [R] = 0"""
     dev = best.device
-    _check(lib().nvbio_best_approx_init_ragged(FMIndex._dev_index(dev), ctypes.c_uint32(best.shape[0]), _ptr(min_scores), _ptr(best), _ptr(best_rc),
-                                               _stream_ptr(dev)))
+    _check(lib().nvbio_best_approx_init_ragged(FMIndex._dev_index(dev), best.shape[0], _ptr(min_scores), _ptr(best), _ptr(best_rc), _stream_ptr(dev)))
 
 
 def score_reduce_effort_ragged(active, hits, read_offsets, n_ext, params, best, best_rc, trys, sizes):
     """nvbio_score_reduce_effort_ragged: score_reduce_effort with every read's own length (read_offsets int32 [R + 1]) in `distinct`"""
     hq = hits.c_struct()
-    _check(lib().nvbio_score_reduce_effort_ragged(FMIndex._dev_index(hits.device), _ptr(active), ctypes.byref(hq), _ptr(read_offsets), ctypes.c_uint32(n_ext),
+    _check(lib().nvbio_score_reduce_effort_ragged(FMIndex._dev_index(hits.device), _ptr(active), ctypes.byref(hq), _ptr(read_offsets), n_ext,
                                                   ctypes.byref(params.c), _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
 
 
 def score_reduce_effort_multi_ragged(active, n_active, hits_first, hits_count, hits, read_offsets, n_ext, params, best, best_rc, trys, sizes):
     """nvbio_score_reduce_effort_multi_ragged: the several-hits-per-read reduction over a ragged batch"""
     hq = hits.c_struct()
-    _check(lib().nvbio_score_reduce_effort_multi_ragged(FMIndex._dev_index(hits.device), _ptr(active), ctypes.c_uint32(n_active), _ptr(hits_first),
-                                                        _ptr(hits_count), ctypes.byref(hq), _ptr(read_offsets), ctypes.c_uint32(n_ext), ctypes.byref(params.c),
-                                                        _ptr(best), _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
+    _check(lib().nvbio_score_reduce_effort_multi_ragged(FMIndex._dev_index(hits.device), _ptr(active), n_active, _ptr(hits_first), _ptr(hits_count),
+                                                        ctypes.byref(hq), _ptr(read_offsets), n_ext, ctypes.byref(params.c), _ptr(best),
+                                                        _ptr(best_rc), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
 
 
 # ---- the paired loop's steps over mates of different lengths (include/nvbio_amd.h: nvbio_pe_ragged and the nvbio_pe_*_ragged calls) ----
@@ -1916,8 +1864,7 @@ class PeRagged:
 def pe_init_ragged(ragged, best_a, best_o):
     """nvbio_pe_init_ragged: best_a / best_o int32 [R, 2, 4] = unaligned at min_scores_mate1[r] / min_scores_mate2[r]"""
     dev = best_a.device
-    _check(lib().nvbio_pe_init_ragged(FMIndex._dev_index(dev), ctypes.c_uint32(best_a.shape[0]), ctypes.byref(ragged.c), _ptr(best_a), _ptr(best_o),
-                                      _stream_ptr(dev)))
+    _check(lib().nvbio_pe_init_ragged(FMIndex._dev_index(dev), best_a.shape[0], ctypes.byref(ragged.c), _ptr(best_a), _ptr(best_o), _stream_ptr(dev)))
 
 
 def pe_anchor_flatten_ragged(params, ragged, hits, best_a, best_o, read_id, flags, win_begin, win_end, min_scores):
@@ -1931,7 +1878,7 @@ def pe_anchor_flatten_ragged(params, ragged, hits, best_a, best_o, read_id, flag
 def pe_opposite_flatten_ragged(params, ragged, queue, n, hits, best_a, best_o, read_id, flags, win_begin, win_end, min_scores):
     """nvbio_pe_opposite_flatten_ragged: the same for the opposite mate of the n hits of queue (those whose anchor passed)"""
     hq = hits.c_struct()
-    _check(lib().nvbio_pe_opposite_flatten_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(queue), ctypes.c_uint32(n),
+    _check(lib().nvbio_pe_opposite_flatten_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(queue), n,
                                                   ctypes.byref(hq), _ptr(best_a), _ptr(best_o), _ptr(read_id), _ptr(flags), _ptr(win_begin), _ptr(win_end),
                                                   _ptr(min_scores), _stream_ptr(hits.device)))
 
@@ -1939,9 +1886,9 @@ def pe_opposite_flatten_ragged(params, ragged, queue, n, hits, best_a, best_o, r
 def pe_score_reduce_ragged(params, ragged, active, n_active, hits_first, hits_count, hits, hit_oscore, hit_oloc, hit_osink, n_ext, best_a, best_o, trys, sizes):
     """nvbio_pe_score_reduce_ragged: score_reduce_paired with the anchor read's own length in `distinct`"""
     hq = hits.c_struct()
-    _check(lib().nvbio_pe_score_reduce_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(active), ctypes.c_uint32(n_active),
+    _check(lib().nvbio_pe_score_reduce_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(active), n_active,
                                               _ptr(hits_first), _ptr(hits_count), ctypes.byref(hq), _ptr(hit_oscore), _ptr(hit_oloc), _ptr(hit_osink),
-                                              ctypes.c_uint32(n_ext), _ptr(best_a), _ptr(best_o), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
+                                              n_ext, _ptr(best_a), _ptr(best_o), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
 
 
 # ---- nvBowtie's all-mapping mode (include/nvbio_amd.h: nvbio_all_*; host/nvbio_amd/all_mapping.hpp) ---------------------------------
@@ -1977,9 +1924,9 @@ def all_hits_scan(fw_ranges, rc_ranges, n_reads, params):
     dev = fw_ranges.device
     slots = torch.zeros(2 * n_reads * params.c.seeds_per_read, dtype=torch.int64, device=dev)
     n_hits = torch.zeros(1, dtype=torch.int64, device=dev)
-    tmp, nb = _temp_for(lib().nvbio_all_hits_scan_temp_bytes, ctypes.c_uint32(n_reads), ctypes.c_uint32(params.c.seeds_per_read), device=dev)
-    _check(lib().nvbio_all_hits_scan(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), ctypes.c_uint32(n_reads), ctypes.byref(params.c),
-                                     _ptr(slots), _ptr(n_hits), _ptr(tmp), ctypes.c_uint64(nb), _stream_ptr(dev)))
+    tmp, nb = _temp_for(lib().nvbio_all_hits_scan_temp_bytes, n_reads, params.c.seeds_per_read, device=dev)
+    _check(lib().nvbio_all_hits_scan(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), n_reads, ctypes.byref(params.c), _ptr(slots),
+                                     _ptr(n_hits), _ptr(tmp), nb, _stream_ptr(dev)))
     return slots, n_hits
 
 
@@ -1987,8 +1934,8 @@ def all_hits_select(fw_ranges, rc_ranges, n_reads, params, slots, begin, end, hi
     """select_all_kernel (nvbio_all_hits_select): fills hits.read_id / loc (the SA row) / seed for the hits [begin, end) of the scan"""
     dev = hits.device
     hq = hits.c_struct()
-    _check(lib().nvbio_all_hits_select(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), ctypes.c_uint32(n_reads), ctypes.byref(params.c),
-                                       _ptr(slots), ctypes.c_uint64(begin), ctypes.c_uint64(end), ctypes.byref(hq), _stream_ptr(dev)))
+    _check(lib().nvbio_all_hits_select(FMIndex._dev_index(dev), _ptr(fw_ranges), _ptr(rc_ranges), n_reads, ctypes.byref(params.c), _ptr(slots), begin,
+                                       end, ctypes.byref(hq), _stream_ptr(dev)))
 
 
 def all_hits_unique(hits):
@@ -1997,10 +1944,9 @@ def all_hits_unique(hits):
     torch = _torch()
     dev = hits.device
     n_out = torch.zeros(1, dtype=torch.int32, device=dev)
-    tmp, nb = _temp_for(lib().nvbio_all_hits_unique_temp_bytes, ctypes.c_uint32(hits.n), device=dev)
+    tmp, nb = _temp_for(lib().nvbio_all_hits_unique_temp_bytes, hits.n, device=dev)
     hq = hits.c_struct()
-    _check(lib().nvbio_all_hits_unique(FMIndex._dev_index(dev), ctypes.byref(hq), ctypes.byref(hq), _ptr(n_out), _ptr(tmp), ctypes.c_uint64(nb),
-                                       _stream_ptr(dev)))
+    _check(lib().nvbio_all_hits_unique(FMIndex._dev_index(dev), ctypes.byref(hq), ctypes.byref(hq), _ptr(n_out), _ptr(tmp), nb, _stream_ptr(dev)))
     hits.n = int(n_out.item())
     return hits.n
 
@@ -2009,11 +1955,10 @@ def all_score_output(hits, scores, min_score, out, out_offset, count):
     """AllScoreStream::output (nvbio_all_score_output): appends (read_id, rc, loc, score) of the hits with score >= min_score to
     out = (read_id int32, rc uint8, loc int32, score int32) from slot out_offset on, in hit order; count int64 [1] += the number accepted"""
     dev = hits.device
-    tmp, nb = _temp_for(lib().nvbio_all_score_output_temp_bytes, ctypes.c_uint32(hits.n), device=dev)
+    tmp, nb = _temp_for(lib().nvbio_all_score_output_temp_bytes, hits.n, device=dev)
     hq = hits.c_struct()
-    _check(lib().nvbio_all_score_output(FMIndex._dev_index(dev), ctypes.byref(hq), _ptr(scores), ctypes.c_int32(min_score), _ptr(out[0]), _ptr(out[1]),
-                                        _ptr(out[2]), _ptr(out[3]), ctypes.c_uint64(out_offset), ctypes.c_uint64(out[0].numel()), _ptr(count), _ptr(tmp),
-                                        ctypes.c_uint64(nb), _stream_ptr(dev)))
+    _check(lib().nvbio_all_score_output(FMIndex._dev_index(dev), ctypes.byref(hq), _ptr(scores), min_score, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                        _ptr(out[3]), out_offset, out[0].numel(), _ptr(count), _ptr(tmp), nb, _stream_ptr(dev)))
 
 
 def all_traceback_flatten(rec_read_id, rec_rc, rec_loc, read_index, band_len, genome_len, reads_reversed=True):
@@ -2026,9 +1971,8 @@ def all_traceback_flatten(rec_read_id, rec_rc, rec_loc, read_index, band_len, ge
     flags = torch.empty(n, dtype=torch.uint8, device=dev)
     wb = torch.empty(n, dtype=torch.int32, device=dev)
     we = torch.empty(n, dtype=torch.int32, device=dev)
-    _check(lib().nvbio_all_traceback_flatten(FMIndex._dev_index(dev), _ptr(rec_read_id), _ptr(rec_rc), _ptr(rec_loc), ctypes.c_uint32(n), _ptr(ri),
-                                             ctypes.c_uint32(band_len), ctypes.c_uint32(genome_len), ctypes.c_uint32(1 if reads_reversed else 0),
-                                             _ptr(rid), _ptr(flags), _ptr(wb), _ptr(we), _stream_ptr(dev)))
+    _check(lib().nvbio_all_traceback_flatten(FMIndex._dev_index(dev), _ptr(rec_read_id), _ptr(rec_rc), _ptr(rec_loc), n, _ptr(ri), band_len,
+                                             genome_len, 1 if reads_reversed else 0, _ptr(rid), _ptr(flags), _ptr(wb), _ptr(we), _stream_ptr(dev)))
     return rid, flags, wb, we
 
 
@@ -2082,9 +2026,8 @@ def all_mapping(fmi, genome2, genome_len, stored_reads4, n_reads, read_len, para
     sw = _SWScheme(*params.scheme)
     st = _AllMappingStats()
     reads = _dev_tensor(stored_reads4, torch.int32, dev)
-    rc = _host_lib().nvbio_host_all_mapping(ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(reads),
-                                            ctypes.c_uint32(n_reads), ctypes.c_uint32(read_len), ctypes.byref(sw), ctypes.c_int32(params.min_score),
-                                            ctypes.byref(p), ctypes.byref(o), _stream_ptr(dev), ctypes.byref(st))
+    rc = _host_lib().nvbio_host_all_mapping(FMIndex._dev_index(dev), fmi._h, _ptr(genome2), genome_len, _ptr(reads), n_reads, read_len,
+                                            ctypes.byref(sw), params.min_score, ctypes.byref(p), ctypes.byref(o), _stream_ptr(dev), ctypes.byref(st))
     if rc != 0:
         raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
     k = min(int(st.n_alignments), cap)
@@ -2120,15 +2063,15 @@ class RankDictionary:
         torch = _torch()
         out = torch.empty_like(idx)
         d = self._c(self.occ)
-        _check(lib().nvbio_rank_dictionary_rank(FMIndex._dev_index(self.device), ctypes.byref(d), _ptr(idx), _ptr(syms), ctypes.c_uint32(idx.numel()),
-                                                _ptr(out), _stream_ptr(self.device)))
+        _check(lib().nvbio_rank_dictionary_rank(FMIndex._dev_index(self.device), ctypes.byref(d), _ptr(idx), _ptr(syms), idx.numel(), _ptr(out),
+                                                _stream_ptr(self.device)))
         return out
 
     def rank4(self, idx):
         torch = _torch()
         out = torch.empty((idx.numel(), 4), dtype=idx.dtype, device=idx.device)
         d = self._c(self.occ)
-        _check(lib().nvbio_rank_dictionary_rank4(FMIndex._dev_index(self.device), ctypes.byref(d), _ptr(idx), ctypes.c_uint32(idx.numel()), _ptr(out),
+        _check(lib().nvbio_rank_dictionary_rank4(FMIndex._dev_index(self.device), ctypes.byref(d), _ptr(idx), idx.numel(), _ptr(out),
                                                  _stream_ptr(self.device)))
         return out
 
@@ -2140,6 +2083,19 @@ def batch_banded_myers_score(band, aln_type, batch, min_score=SCORE_MIN):
     scores = torch.empty(batch.n, dtype=torch.int32, device=batch.device)
     sinks = torch.empty((batch.n, 2), dtype=torch.int32, device=batch.device)
     bs = batch.c_struct()
-    _check(lib().nvbio_banded_myers_score(FMIndex._dev_index(batch.device), ctypes.c_uint32(band), ctypes.c_int(aln_type), ctypes.byref(bs),
-                                          ctypes.c_int32(min_score), _ptr(scores), _ptr(sinks), _stream_ptr(batch.device)))
+    _check(lib().nvbio_banded_myers_score(FMIndex._dev_index(batch.device), band, aln_type, ctypes.byref(bs), min_score, _ptr(scores), _ptr(sinks),
+                                          _stream_ptr(batch.device)))
     return scores, sinks
+
+
+# ---- the mirrors of the headers' structs: C name -> class (abi.bind types a pointer to one as POINTER(mirror); pipeline.py adds its own) -------
+_MIRRORS = {
+    "nvbio_fm_index_view": _View, "nvbio_fm_build_options": _BuildOptions, "nvbio_string_set": _StringSet, "nvbio_rank_dictionary": _RankDict,
+    "nvbio_mem_params": _MemParams, "nvbio_qgram_index_view": _QGramView, "nvbio_qgroup_index_view": _QGroupView,
+    "nvbio_sufsort_stats": _SufsortStats, "nvbio_hit_queues": _HitQueues, "nvbio_seed_hits_params": _SeedHitsParams,
+    "nvbio_ragged_seed_layout": _RaggedSeedLayout, "nvbio_all_hits_params": _AllHitsParams, "nvbio_pe_params": _PeParams,
+    "nvbio_pe_ragged": _PeRagged, "nvbio_gotoh_scheme": _Scheme, "nvbio_sw_scheme": _SWScheme, "nvbio_alignment_batch": _Batch,
+    "nvbio_mapq_params": _MapqParams,
+    "nvbio_host_all_mapping_params": _AllMappingParams, "nvbio_host_all_mapping_output": _AllMappingOutput,
+    "nvbio_host_all_mapping_stats": _AllMappingStats,
+}

@@ -1,26 +1,10 @@
 // all_mapping_capi.cpp -- the C++ host loop of host/nvbio_amd/all_mapping.hpp behind one extern "C" entry point (libnvbio_amd_host.so), so that
 // Python callers and the parity tests can drive it through ctypes.  Plain g++: no device code; everything on the GPU goes through libnvbio_amd.so.
 #include <nvbio_amd/all_mapping.hpp>
+#include <nvbio_amd_host.h>
 
 extern "C" {
 
-void nvbio_host_set_error(const char* msg);          // best_approx_capi.cpp: the message nvbio_host_last_error returns
-
-struct nvbio_host_all_mapping_params
-{
-    uint32_t seed_len, seed_freq, max_reseed, max_dist, band, aln_type, hits_per_batch, unique, per_seed_passes, want_cigars;
-};
-// device arrays of `capacity` records; the ones from win_begin on are read with want_cigars only (mds / mds_lens may be NULL)
-struct nvbio_host_all_mapping_output
-{
-    uint64_t     capacity;
-    uint32_t*    read_id; uint8_t* rc; uint32_t* loc; int32_t* score;
-    uint32_t*    win_begin; nvbio_uint2* source; nvbio_uint2* sink; uint32_t* ed; uint16_t* cigars; uint32_t* cigar_lens; uint8_t* mds; uint32_t* mds_lens;
-    uint32_t     cigar_stride, mds_stride;
-};
-struct nvbio_host_all_mapping_stats { uint64_t n_hits, n_scored, n_alignments; uint32_t chunks, pad; };
-
-// returns 0 on success; stats->n_alignments may exceed out->capacity (the records past it are dropped)
 int nvbio_host_all_mapping(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads4_dev,
                            uint32_t n_reads, uint32_t read_len, const nvbio_sw_scheme* scheme, int32_t min_score, const nvbio_host_all_mapping_params* p,
                            const nvbio_host_all_mapping_output* out, void* stream, nvbio_host_all_mapping_stats* stats)

@@ -1,17 +1,12 @@
 // best_approx_capi.cpp -- the C++ host loop of host/nvbio_amd/best_approx.hpp behind one extern "C" entry point (libnvbio_amd_host.so), so that
 // the parity tests and bench.py can drive it through ctypes.  Plain g++: no device code; everything on the GPU goes through libnvbio_amd.so.
 #include <nvbio_amd/best_approx.hpp>
+#include <nvbio_amd_host.h>
 #include <cstring>
 
 static thread_local char g_err[512] = "";
 
 extern "C" {
-
-struct nvbio_host_best_approx_params
-{
-    uint32_t seed_len, seed_freq, max_hits, rep_seeds, max_effort, max_effort_init, min_ext, max_ext, max_reseed, band, top_seed, batch_size, multi_hit;
-};
-struct nvbio_host_best_approx_stats { uint64_t n_extensions; uint32_t passes, multi_passes, seeding_passes, pad; };
 
 const char* nvbio_host_last_error(void) { return g_err; }
 void nvbio_host_set_error(const char* msg) { strncpy( g_err, msg, sizeof(g_err) - 1 ); g_err[sizeof(g_err) - 1] = 0; }     // for the library's other entry points
@@ -39,7 +34,7 @@ template <typename F> static int guarded(F body)
 
 extern "C" {
 
-// returns 0 on success; best_dev [4 n_reads] int32 (16-byte aligned), best_rc_dev [n_reads]; n_reads * read_len must stay below 2^32 (returns 1)
+// the entry points: what each takes and refuses is said at its declaration in include/nvbio_amd_host.h
 int nvbio_host_best_approx(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads4_dev,
                            const uint8_t* quals_dev, uint32_t n_reads, uint32_t read_len, int aln_type, const nvbio_gotoh_scheme* scheme, int32_t worst_score,
                            const nvbio_host_best_approx_params* p, int32_t* best_dev, uint8_t* best_rc_dev, void* stream, nvbio_host_best_approx_stats* stats)
@@ -49,8 +44,6 @@ int nvbio_host_best_approx(int device, nvbio_fm_index_t fmi, const uint32_t* gen
                                                worst_score, params_of( p ), best_dev, best_rc_dev, (hipStream_t)stream ), stats ); } );
 }
 
-// the ragged form (best_approx_ragged): read_offsets [n_reads + 1] and min_scores [n_reads] are HOST arrays; a batch holding a read of 1024 symbols or
-// more is refused (returns 1) before anything is launched or written
 int nvbio_host_best_approx_ragged(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads4_dev,
                                   const uint8_t* quals_dev, uint32_t n_reads, const uint32_t* read_offsets, int aln_type, const nvbio_gotoh_scheme* scheme,
                                   const int32_t* min_scores, uint32_t min_read_len, const nvbio_host_best_approx_params* p, int32_t* best_dev, uint8_t* best_rc_dev,
@@ -61,11 +54,6 @@ int nvbio_host_best_approx_ragged(int device, nvbio_fm_index_t fmi, const uint32
                                                       *scheme, min_scores, params_of( p ), best_dev, best_rc_dev, (hipStream_t)stream, min_read_len ), stats ); } );
 }
 
-struct nvbio_host_paired_params { uint32_t policy, min_frag_len, max_frag_len, overlap, unpaired; };
-struct nvbio_host_paired_stats { uint64_t n_extensions, n_opposite; uint32_t passes, multi_passes; };
-
-// the paired-end form: reads1 / reads2 stored reversed, uniform lengths read_len1 / read_len2 (n_reads times either below 2^32); best_a_dev / best_o_dev
-// [n_reads][2][4] int32
 int nvbio_host_best_approx_paired(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads1_dev,
                                   const uint32_t* stored_reads2_dev, const uint8_t* quals1_dev, const uint8_t* quals2_dev, uint32_t n_reads, uint32_t read_len1,
                                   uint32_t read_len2, int aln_type, const nvbio_gotoh_scheme* scheme, int32_t worst_score1, int32_t worst_score2,
@@ -81,9 +69,6 @@ int nvbio_host_best_approx_paired(int device, nvbio_fm_index_t fmi, const uint32
         if (stats) { stats->n_extensions = s.n_extensions; stats->n_opposite = s.n_opposite; stats->passes = s.passes; stats->multi_passes = s.multi_passes; } } );
 }
 
-// the paired-end form over mates of different lengths (best_approx_paired_ragged): read_offsets1 / read_offsets2 [n_reads + 1] and min_scores1 / min_scores2
-// [n_reads] are HOST arrays; a missing table, decreasing offsets, an empty mate or a mate of 1024 symbols or more in either batch is refused (returns 1)
-// before anything is launched or written
 int nvbio_host_best_approx_paired_ragged(int device, nvbio_fm_index_t fmi, const uint32_t* genome2_dev, uint32_t genome_len, const uint32_t* stored_reads1_dev,
                                          const uint32_t* stored_reads2_dev, const uint8_t* quals1_dev, const uint8_t* quals2_dev, uint32_t n_reads,
                                          const uint32_t* read_offsets1, const uint32_t* read_offsets2, int aln_type, const nvbio_gotoh_scheme* scheme,

@@ -11,11 +11,14 @@ expand + locate, banded Gotoh); torch is used for the index arithmetic between t
 (hit -> diagonal, sort/unique of candidate loci, per-read arg-max), on the same stream.
 This module never imports the oracle.
 """
+import ctypes
 import math
+import os
 
 import numpy as np
 
-from . import (ALN_RAGGED_READS, FM_COMPLEMENT, FM_NO_SEED_LOCUS, FM_SCAN_FORWARD, LOCAL, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
+from .abi import bind
+from . import (_MIRRORS, HOST_HEADER_PATH, ALN_RAGGED_READS, FM_COMPLEMENT, FM_NO_SEED_LOCUS, FM_SCAN_FORWARD, LOCAL, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
                BatchedBandedAlignmentScore, FMIndexFilter, GotohAligner, GotohScheme, HitQueues, PackedStringSet, RaggedSeedLayout, SeedHitsParams,
                best_approx_init_ragged, read_queue_begin_ragged, score_reduce_effort, score_reduce_effort_ragged, score_stream_flatten, score_stream_output,
                seed_hits_loc, seed_hits_map, seed_hits_map_ragged, seed_hits_select, SEED_NO_LOCUS)
@@ -871,8 +874,6 @@ _HOST_LIB = None
 
 
 def _host_lib():
-    import ctypes
-    import os
     global _HOST_LIB
     if _HOST_LIB is None:
         from . import lib as _core
@@ -881,25 +882,32 @@ def _host_lib():
         if not os.path.exists(path):
             raise RuntimeError("%s is missing: build it with __graft_entry__.build()" % path)
         L = ctypes.CDLL(path)
-        L.nvbio_host_last_error.restype = ctypes.c_char_p
+        bind(L, HOST_HEADER_PATH, _HOST_MIRRORS)
         _HOST_LIB = L
     return _HOST_LIB
 
 
-def _host_structs():
-    import ctypes
-
-    class _P(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_uint32) for k in ("seed_len", "seed_freq", "max_hits", "rep_seeds", "max_effort", "max_effort_init", "min_ext", "max_ext",
-                                                  "max_reseed", "band", "top_seed", "batch_size", "multi_hit")]
-
-    class _S(ctypes.Structure):
-        _fields_ = [("n_extensions", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("multi_passes", ctypes.c_uint32), ("seeding_passes", ctypes.c_uint32),
-                    ("pad", ctypes.c_uint32)]
-    return _P, _S
+class _HostParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("seed_len", "seed_freq", "max_hits", "rep_seeds", "max_effort", "max_effort_init", "min_ext", "max_ext",
+                                              "max_reseed", "band", "top_seed", "batch_size", "multi_hit")]
 
 
-_HostParams, _HostStats = _host_structs()
+class _HostStats(ctypes.Structure):
+    _fields_ = [("n_extensions", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("multi_passes", ctypes.c_uint32), ("seeding_passes", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
+class _HostPairedParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("policy", "min_frag_len", "max_frag_len", "overlap", "unpaired")]
+
+
+class _HostPairedStats(ctypes.Structure):
+    _fields_ = [("n_extensions", ctypes.c_uint64), ("n_opposite", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("multi_passes", ctypes.c_uint32)]
+
+
+# every mirror of either header: what the package registers (the all-mapping ones among them) and the four above
+_HOST_MIRRORS = dict(_MIRRORS, nvbio_host_best_approx_params=_HostParams, nvbio_host_best_approx_stats=_HostStats,
+                     nvbio_host_paired_params=_HostPairedParams, nvbio_host_paired_stats=_HostPairedStats)
 
 
 def _host_params(nvb, seed_freq, batch_size, multi_hit):
@@ -913,18 +921,16 @@ def host_best_approx_into(fmi, genome2, genome_len, stored_reads, params, nvb, b
     worst score; the loop evaluates seed_freq( M_r ) itself (S(1, 1.15) unless nvb.seed_freq or params.seed_interval fixes one).  Raises RuntimeError,
     having launched and written nothing, for a ragged read of 1024 symbols or more or a uniform batch of 2^32 symbols or more.  Returns the
     loop's counters."""
-    import ctypes
     from . import FMIndex, _ptr, _stream_ptr
     dev = fmi.device
     R, M = stored_reads.n, stored_reads.read_len
     st = _HostStats()
-    head = (ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_reads.reads4), _ptr(stored_reads.quals),
-            ctypes.c_uint32(R))
+    head = (FMIndex._dev_index(dev), fmi._h, _ptr(genome2), genome_len, _ptr(stored_reads.reads4), _ptr(stored_reads.quals), R)
     tail = (_ptr(best), _ptr(best_rc), _stream_ptr(dev), ctypes.byref(st))
-    kind = (ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c))
+    kind = (int(params.aln_type), ctypes.byref(params.scheme.c))
     if stored_reads.offsets is None:
         p = _host_params(nvb, nvb.seed_freq or params.interval_for(M), batch_size, multi_hit)
-        rc = _host_lib().nvbio_host_best_approx(*head, ctypes.c_uint32(M), *kind, ctypes.c_int32(params.min_score_for(M)), ctypes.byref(p), *tail)
+        rc = _host_lib().nvbio_host_best_approx(*head, M, *kind, params.min_score_for(M), ctypes.byref(p), *tail)
     else:
         off = np.ascontiguousarray(stored_reads.offsets.detach().cpu().numpy().astype(np.uint32))
         lens = np.diff(off.astype(np.int64))
@@ -934,7 +940,7 @@ def host_best_approx_into(fmi, genome2, genome_len, stored_reads, params, nvb, b
         worst = np.ascontiguousarray(params.min_score_table(Mmax)[np.clip(lens, 0, Mmax)].astype(np.int32))
         p = _host_params(nvb, nvb.seed_freq or params.seed_interval or 0, batch_size, multi_hit)
         rc = _host_lib().nvbio_host_best_approx_ragged(*head, off.ctypes.data_as(ctypes.c_void_p), *kind, worst.ctypes.data_as(ctypes.c_void_p),
-                                                       ctypes.c_uint32(nvb.min_read_len), ctypes.byref(p), *tail)
+                                                       nvb.min_read_len, ctypes.byref(p), *tail)
     if rc != 0:
         raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
     return st
@@ -983,7 +989,6 @@ def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, st
     max( nvb.min_read_len, seed_len ) is not seeded but still aligned as its partner's opposite mate.  Raises RuntimeError, having launched and written
     nothing, for a mate of 1024 symbols or more, an empty mate or decreasing offsets.  out: the caller's (best_a, best_o) to write into, or None.
     -> dict( best_a, best_o [R, 2, 4] int32 = { score, position, sink offset, rc | mate << 1 | paired << 2 } x { best, second }, counters )."""
-    import ctypes
     import torch
     from . import FMIndex, _ptr, _stream_ptr
     nvb = nvb or NvBowtieParams()
@@ -993,29 +998,22 @@ def nvbowtie_best_approx_paired_host(fmi, genome2, genome_len, stored_mates1, st
     if stored_mates2.n != R:
         raise ValueError("the two mate batches must hold the same number of reads")
 
-    class _PE(ctypes.Structure):
-        _fields_ = [(k, ctypes.c_uint32) for k in ("policy", "min_frag_len", "max_frag_len", "overlap", "unpaired")]
-
-    class _S(ctypes.Structure):
-        _fields_ = [("n_extensions", ctypes.c_uint64), ("n_opposite", ctypes.c_uint64), ("passes", ctypes.c_uint32), ("multi_passes", ctypes.c_uint32)]
-
     p = _host_params(nvb, nvb.seed_freq or 0, batch_size, multi_hit)
-    q = _PE(int(pe.policy), int(pe.min_frag_len), int(pe.max_frag_len), 1 if pe.overlap else 0, 1 if unpaired else 0)
-    st = _S()
+    q = _HostPairedParams(int(pe.policy), int(pe.min_frag_len), int(pe.max_frag_len), 1 if pe.overlap else 0, 1 if unpaired else 0)
+    st = _HostPairedStats()
     best_a, best_o = out or (torch.empty((R, 2, 4), dtype=torch.int32, device=dev), torch.empty((R, 2, 4), dtype=torch.int32, device=dev))
-    head = (ctypes.c_int(FMIndex._dev_index(dev)), fmi._h, _ptr(genome2), ctypes.c_uint32(genome_len), _ptr(stored_mates1.reads4), _ptr(stored_mates2.reads4),
-            _ptr(stored_mates1.quals), _ptr(stored_mates2.quals), ctypes.c_uint32(R))
-    kind = (ctypes.c_int(int(params.aln_type)), ctypes.byref(params.scheme.c))
+    head = (FMIndex._dev_index(dev), fmi._h, _ptr(genome2), genome_len, _ptr(stored_mates1.reads4), _ptr(stored_mates2.reads4),
+            _ptr(stored_mates1.quals), _ptr(stored_mates2.quals), R)
+    kind = (int(params.aln_type), ctypes.byref(params.scheme.c))
     tail = (ctypes.byref(p), ctypes.byref(q), _ptr(best_a), _ptr(best_o), _stream_ptr(dev), ctypes.byref(st))
     if stored_mates1.offsets is None and stored_mates2.offsets is None:
-        rc = _host_lib().nvbio_host_best_approx_paired(*head, ctypes.c_uint32(M1), ctypes.c_uint32(M2), *kind, ctypes.c_int32(params.min_score_for(M1)),
-                                                       ctypes.c_int32(params.min_score_for(M2)), *tail)
+        rc = _host_lib().nvbio_host_best_approx_paired(*head, M1, M2, *kind, params.min_score_for(M1), params.min_score_for(M2), *tail)
     else:
         # mates of different lengths (nvbio_host_best_approx_paired_ragged): both mates' offsets and per-read worst scores go on the HOST
         off, worst = zip(*[_mate_tables(m, params) for m in (stored_mates1, stored_mates2)])
         host_ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         rc = _host_lib().nvbio_host_best_approx_paired_ragged(*head, host_ptr(off[0]), host_ptr(off[1]), *kind, host_ptr(worst[0]), host_ptr(worst[1]),
-                                                              ctypes.c_uint32(nvb.min_read_len), *tail)
+                                                              nvb.min_read_len, *tail)
     if rc != 0:
         raise RuntimeError(_host_lib().nvbio_host_last_error().decode())
     return dict(best_a=best_a, best_o=best_o, n_extensions=int(st.n_extensions), n_opposite=int(st.n_opposite), passes=int(st.passes),

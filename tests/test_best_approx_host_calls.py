@@ -83,23 +83,23 @@ def test_best_approx_paired_refuses_either_mate_of_2_to_the_32_symbols(long_mate
     amd, pipeline, host = _host()
     scheme = amd.GotohScheme(2, 2, 6, -5, -3, -5, -3)
     p = pipeline._host_params(pipeline.NvBowtieParams(), 0, 0, True)
-    pe = (ctypes.c_uint32 * 5)(0, 0, 500, 1, 1)                           # nvbio_host_paired_params: policy, min / max fragment, overlap, unpaired
-    st = (ctypes.c_uint64 * 3)()
+    pe = pipeline._HostPairedParams(0, 0, 500, 1, 1)                      # nvbio_host_paired_params: policy, min / max fragment, overlap, unpaired
+    st = pipeline._HostPairedStats()
     u32, i32 = ctypes.c_uint32, ctypes.c_int32
     lens = (BIG_M, 100) if long_mate == 1 else (100, BIG_M)
     rc = host.nvbio_host_best_approx_paired(0, None, None, u32(1000), None, None, None, None, u32(BIG_R), u32(lens[0]), u32(lens[1]), 1, ctypes.byref(scheme.c), i32(0),
-                                            i32(0), ctypes.byref(p), pe, None, None, None, st)
+                                            i32(0), ctypes.byref(p), ctypes.byref(pe), None, None, None, ctypes.byref(st))
     _refused(host, rc)
 
 
 def test_all_mapping_refuses_a_batch_of_2_to_the_32_symbols():
     amd, pipeline, host = _host()
-    scheme = (ctypes.c_int32 * 4)(0, -1, -1, -1)                          # nvbio_sw_scheme: edit distance
+    scheme = amd._SWScheme(0, -1, -1, -1)                                 # nvbio_sw_scheme: edit distance
     p = amd._AllMappingParams(22, 0, 2, 15, 0, 2, 0, 0, 0, 0)
     out = amd._AllMappingOutput()
     st = amd._AllMappingStats()
     u32 = ctypes.c_uint32
-    rc = host.nvbio_host_all_mapping(0, None, None, u32(1000), None, u32(BIG_R), u32(BIG_M), scheme, ctypes.c_int32(-15), ctypes.byref(p), ctypes.byref(out), None,
+    rc = host.nvbio_host_all_mapping(0, None, None, u32(1000), None, u32(BIG_R), u32(BIG_M), ctypes.byref(scheme), ctypes.c_int32(-15), ctypes.byref(p), ctypes.byref(out), None,
                                      ctypes.byref(st))
     _refused(host, rc)
 

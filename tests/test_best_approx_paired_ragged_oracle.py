@@ -3,7 +3,6 @@ against is pinned before any GPU is involved -- on a uniform batch it is the ora
 is that oracle called once per pair at the pair's own two lengths -- and the shared ragged pairs exercise what they should; the route's symbols are
 declared and exported, and the host entry refuses what the contract refuses before it touches the device."""
 import ctypes
-import re
 from importlib import import_module
 
 import numpy as np
@@ -131,12 +130,12 @@ NEW_SYMBOLS = ("nvbio_pe_init_ragged", "nvbio_pe_anchor_flatten_ragged", "nvbio_
 
 def test_symbols_are_declared_and_exported():
     amd = ge.load_package()
-    txt = re.sub(r"/\*.*?\*/", "", open(amd.HEADER_PATH).read(), flags=re.S)
-    declared = set(re.findall(r"\b(nvbio_[a-z0-9_]+)\s*\(", txt))
+    header = amd.abi.Header(amd.HEADER_PATH)
+    declared = header.prototypes
     L = amd.lib()
     for s in NEW_SYMBOLS:
         assert s in declared and hasattr(L, s), s
-    assert "nvbio_pe_ragged;" in txt
+    assert "nvbio_pe_ragged" in header.structs
     pipeline = import_module("nvbio_gpl_amd.pipeline")
     assert hasattr(pipeline._host_lib(), "nvbio_host_best_approx_paired_ragged")
     for f in ("pe_init_ragged", "pe_anchor_flatten_ragged", "pe_opposite_flatten_ragged", "pe_score_reduce_ragged"):
@@ -160,17 +159,17 @@ def _refuse(offsets1, offsets2, min1=True, min2=True):
     amd = ge.load_package()
     pipeline = import_module("nvbio_gpl_amd.pipeline")
     host = pipeline._host_lib()
-    host.nvbio_host_last_error.restype = ctypes.c_char_p
     scheme = amd.GotohScheme(0, 6, 6, -8, -3, -8, -3)
     p = pipeline._host_params(pipeline.NvBowtieParams(), 0, 0, True)
-    pe = (ctypes.c_uint32 * 5)(1, 0, 500, 1, 1)
-    st = (ctypes.c_uint64 * 3)()
+    pe = pipeline._HostPairedParams(1, 0, 500, 1, 1)
+    st = pipeline._HostPairedStats()
     off = [None if o is None else np.ascontiguousarray(np.array(o, dtype=np.uint32)) for o in (offsets1, offsets2)]
     R = len(offsets2) - 1
     worst = [np.full(R, -30, dtype=np.int32) if m else None for m in (min1, min2)]
     hp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
     rc = host.nvbio_host_best_approx_paired_ragged(0, None, None, ctypes.c_uint32(1000), None, None, None, None, ctypes.c_uint32(R), hp(off[0]), hp(off[1]), 1,
-                                                   ctypes.byref(scheme.c), hp(worst[0]), hp(worst[1]), ctypes.c_uint32(12), ctypes.byref(p), pe, None, None, None, st)
+                                                   ctypes.byref(scheme.c), hp(worst[0]), hp(worst[1]), ctypes.c_uint32(12), ctypes.byref(p), ctypes.byref(pe), None, None, None,
+                                                   ctypes.byref(st))
     assert rc == 1
     return host.nvbio_host_last_error().decode()
 
