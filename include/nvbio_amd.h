@@ -1463,6 +1463,21 @@ nvbio_status nvbio_full_gotoh_traceback(int device, nvbio_alignment_type type, c
                                         uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
                                         uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream);
 
+/* nvbio_full_gotoh_traceback plus a report of the route each job took, in the manner of nvbio_banded_gotoh_traceback_routes.  routes_dev, one
+ * byte per job: 0 = no DP (nothing to trace, the job was skipped as beyond max_pattern_len / max_text_len, or the diagonal through the sink
+ * settled it); 1 = the full matrix over all text rows; 2 = the full matrix over the rows within G diagonals of the sink's; 3 = the band-15
+ * kernel over a window of pattern_len + 14 symbols around that diagonal (routes 2 and 3: SEMI_GLOBAL, match bonus 0, the sink in the last
+ * pattern row, G = the gap bound drawn from the score at most 250 / 7).  gap_bound_dev, one byte per job: the G the job ran with on routes 2
+ * and 3, 0 otherwise.  With NVBIO_ALN_NO_UNGAPPED_TRACEBACK every job reaches the DP over all rows and reports (1, 0).  Neither pointer may
+ * be NULL.  The other outputs never depend on the report; it exists so that a test can tell which kernel body produced a CIGAR. */
+nvbio_status nvbio_full_gotoh_traceback_routes(int device, nvbio_alignment_type type, const nvbio_gotoh_scheme* scheme,
+                                               const nvbio_alignment_batch* batch, uint32_t max_pattern_len, uint32_t max_text_len,
+                                               const int32_t* min_scores_dev,
+                                               int32_t* scores_dev, nvbio_uint2* sources_dev, nvbio_uint2* sinks_dev,
+                                               uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
+                                               uint32_t flags, void* temp_dev, uint64_t temp_bytes,
+                                               uint8_t* routes_dev, uint8_t* gap_bound_dev, void* stream);
+
 /* The same for the linear-gap SmithWatermanAligner (and the EditDistanceAligner's scheme (0, -1, -1, -1)), deletion and insertion costs
  * unequal or not: aln::alignment_traceback<MAX_PATTERN_LEN, MAX_TEXT_LEN, CHECKPOINTS>( SmithWatermanAligner<type>, ... )
  * (nvbio/alignment/alignment_inl.h:355-517 over sw/sw_inl.h:306-392 -- the direction of a cell, SINK where a LOCAL score is 0 --,

@@ -1311,6 +1311,36 @@ def banded_gotoh_traceback_routes(band_len, aligner, batch, cigar_stride=64, tem
     return scores, sources, sinks, cigars, lens, routes, band_off
 
 
+FULL_TB_ROUTE_SETTLED, FULL_TB_ROUTE_ALL_ROWS, FULL_TB_ROUTE_RESTRICTED, FULL_TB_ROUTE_BAND15 = 0, 1, 2, 3
+
+
+def full_gotoh_traceback_routes(aligner, batch, max_pattern_len, max_text_len, min_scores=None, cigar_stride=64, temp=None, scores=None, sinks=None):
+    """nvbio_full_gotoh_traceback_routes: (scores, sources, sinks, cigars, lens) as BatchedAlignmentTraceback.enact plus two uint8 per
+    job: the route it took (FULL_TB_ROUTE_SETTLED -- the diagonal through the sink, a skipped job, or nothing traced --,
+    FULL_TB_ROUTE_ALL_ROWS, FULL_TB_ROUTE_RESTRICTED or FULL_TB_ROUTE_BAND15) and, for the last two, the gap bound G it ran with (0 otherwise)"""
+    torch = _torch()
+    n, dev = batch.n, batch.device
+    given = scores is not None and sinks is not None
+    if not given:
+        scores = torch.empty(n, dtype=torch.int32, device=dev)
+        sinks = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    sources = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    cigars = torch.zeros((n, cigar_stride), dtype=torch.int16, device=dev)
+    lens = torch.empty(n, dtype=torch.int32, device=dev)
+    routes = torch.empty(n, dtype=torch.uint8, device=dev)
+    gap_bound = torch.empty(n, dtype=torch.uint8, device=dev)
+    ms = _dev_tensor(min_scores, torch.int32, dev)
+    bs = batch.c_struct()
+    if temp is None and n:
+        temp = _scratch(dev, BatchedAlignmentTraceback(aligner).min_temp_storage(batch, max_pattern_len, max_text_len))
+    _check(lib().nvbio_full_gotoh_traceback_routes(
+        FMIndex._dev_index(dev), aligner.type, ctypes.byref(aligner.scheme.c), ctypes.byref(bs),
+        max_pattern_len, max_text_len, _ptr(ms), _ptr(scores), _ptr(sources), _ptr(sinks), _ptr(cigars), cigar_stride, _ptr(lens),
+        TRACEBACK_SINKS_GIVEN if given else 0, _ptr(temp), 0 if temp is None else temp.numel() * temp.element_size(),
+        _ptr(routes), _ptr(gap_bound), _stream_ptr(dev)))
+    return scores, sources, sinks, cigars, lens, routes, gap_bound
+
+
 GAP_PAIR_MAX_SHIFT = 5
 NO_PARTNER = 0xFFFFFFFF
 

@@ -424,6 +424,21 @@ tb_band_fixup_kernel(const BatchDev b, const uint32_t* __restrict__ wb2, const u
     if (sinks[job].x   != 0xFFFFFFFFu) sinks[job].x   += off;
 }
 
+// the route report (nvbio_full_gotoh_traceback_routes) from the two job lists' flags as the launches saw them: band_route (NULL: no band
+// route) and need_dp, which tb_band_route_kernel cleared for the jobs it took -- so gap_bound comes in holding need_dp as the shortcut
+// left it (2 + G for a restricted job) and leaves holding G
+__global__ void __launch_bounds__(256)
+tb_route_report_kernel(const uint32_t n, const uint8_t* __restrict__ need_dp, const uint8_t* __restrict__ band_route,
+                       uint8_t* __restrict__ routes, uint8_t* __restrict__ gap_bound)
+{
+    const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
+    if (job >= n) return;
+    const uint32_t code = need_dp[job];
+    const uint32_t route = (band_route && band_route[job]) ? 3u : (code >= 2u ? 2u : code);
+    routes[job]    = (uint8_t)route;
+    gap_bound[job] = route >= 2u ? (uint8_t)(gap_bound[job] - 2u) : (uint8_t)0;
+}
+
 } // anonymous namespace
 } // namespace nvbio_amd
 
@@ -468,7 +483,8 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
                                         const int32_t* min_scores_dev,
                                         int32_t* scores_dev, nvbio_uint2* sources_dev, nvbio_uint2* sinks_dev,
                                         uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
-                                        uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream)
+                                        uint32_t flags, void* temp_dev, uint64_t temp_bytes, void* stream,
+                                        uint8_t* routes_dev = nullptr, uint8_t* gap_bound_dev = nullptr)
 {
     NVB_REQUIRE( gotoh != nullptr || sw != nullptr, "scheme is NULL" );
     BatchDev b; NVB_CHECK( make_batch( batch, &b ) );
@@ -528,6 +544,8 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
                                (const int32_t*)scores_dev, (const uint2*)sinks_dev, (uint2*)sources_dev, cigars_dev, cigar_stride, cigar_lens_dev, need_dp,
                                go_min, narrow ? ge_min : 0 );
         }, [&] { return invalid_bits( rb, tbits ); } ); }, [&] { return invalid_type( type ); } ) );      // (the type and the pair were checked)
+        // (the route report: need_dp before the band route clears the jobs it takes)
+        if (routes_dev) NVB_HIP( hipMemcpyAsync( gap_bound_dev, need_dp, b.n, hipMemcpyDeviceToDevice, s ) );
         hipError_t e = hipSuccess;
         if (band_ok)
         {
@@ -568,7 +586,7 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
                              (const uint32_t*)band_count, (uint2*)sources_dev, (uint2*)sinks_dev );
     }
     if (st != NVBIO_OK) return st;
-    return for_each_chunk( b.n, cap_jobs, [&](const uint32_t begin, const uint32_t jobs)
+    st = for_each_chunk( b.n, cap_jobs, [&](const uint32_t begin, const uint32_t jobs)
     {
         uint32_t* column = (uint32_t*)scratch;
         const uint64_t jobs64 = ((uint64_t)jobs + 63u) & ~63ull;                  // whole waves own scratch
@@ -581,6 +599,19 @@ static nvbio_status full_traceback_impl(int device, nvbio_alignment_type type, c
                                (uint2*)sinks_dev, cigars_dev, cigar_stride, cigar_lens_dev, (const uint8_t*)(narrow ? need_dp : nullptr), sw ? 1u : 0u );
         }, [&] { return invalid_bits( rb, tbits ); } ); }, [&] { return invalid_type( type ); } );          // (the type and the pair were checked)
     } );
+    // ---- 5. the route report (nvbio_full_gotoh_traceback_routes) ----
+    if (st == NVBIO_OK && routes_dev)
+    {
+        if (shortcut)
+            st = NVB_LAUNCH( tb_route_report_kernel, dim3( (b.n + 255u) / 256u ), dim3( 256 ), s, b.n, (const uint8_t*)need_dp,
+                             (const uint8_t*)(band_ok ? band_route : nullptr), routes_dev, gap_bound_dev );
+        else
+        {
+            NVB_HIP( hipMemsetAsync( routes_dev, 1, b.n, s ) );
+            NVB_HIP( hipMemsetAsync( gap_bound_dev, 0, b.n, s ) );
+        }
+    }
+    return st;
 }
 
 extern "C" nvbio_status nvbio_full_gotoh_traceback(int device, nvbio_alignment_type type, const nvbio_gotoh_scheme* scheme,
@@ -593,6 +624,20 @@ extern "C" nvbio_status nvbio_full_gotoh_traceback(int device, nvbio_alignment_t
     NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
     return full_traceback_impl( device, type, scheme, nullptr, batch, max_pattern_len, max_text_len, min_scores_dev, scores_dev, sources_dev, sinks_dev,
                                 cigars_dev, cigar_stride, cigar_lens_dev, flags, temp_dev, temp_bytes, stream );
+}
+
+extern "C" nvbio_status nvbio_full_gotoh_traceback_routes(int device, nvbio_alignment_type type, const nvbio_gotoh_scheme* scheme,
+                                                          const nvbio_alignment_batch* batch, uint32_t max_pattern_len, uint32_t max_text_len,
+                                                          const int32_t* min_scores_dev,
+                                                          int32_t* scores_dev, nvbio_uint2* sources_dev, nvbio_uint2* sinks_dev,
+                                                          uint16_t* cigars_dev, uint32_t cigar_stride, uint32_t* cigar_lens_dev,
+                                                          uint32_t flags, void* temp_dev, uint64_t temp_bytes,
+                                                          uint8_t* routes_dev, uint8_t* gap_bound_dev, void* stream)
+{
+    NVB_REQUIRE( scheme != nullptr, "scheme is NULL" );
+    NVB_REQUIRE( routes_dev != nullptr && gap_bound_dev != nullptr, "routes_dev / gap_bound_dev is NULL" );
+    return full_traceback_impl( device, type, scheme, nullptr, batch, max_pattern_len, max_text_len, min_scores_dev, scores_dev, sources_dev, sinks_dev,
+                                cigars_dev, cigar_stride, cigar_lens_dev, flags, temp_dev, temp_bytes, stream, routes_dev, gap_bound_dev );
 }
 
 extern "C" nvbio_status nvbio_full_sw_traceback(int device, nvbio_alignment_type type, const nvbio_sw_scheme* scheme,

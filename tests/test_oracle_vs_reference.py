@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 import oracle
-from util import FULL_KINDS, LIMIT_SCHEMES, RANGE_KINDS, flat_scheme, full_jobs, full_shapes, limit_jobs, limit_thin, range_jobs
+from util import (FULL_KINDS, FULL_LIMIT_CUT_SCHEME, LIMIT_SCHEMES, RANGE_KINDS, flat_scheme, full_jobs, full_limit_jobs, full_shapes, limit_jobs,
+                  limit_thin, range_jobs)
 
 SCHEMES = [oracle.Scheme.simple(2, -1, -1, -1), oracle.Scheme.simple(0, -5, -8, -3),
            oracle.Scheme.simple(2, -1, -2, -1), oracle.Scheme(2, 2, 6, -8, -3, -8, -3),
@@ -122,6 +123,35 @@ def test_traceback_limit_fuzz(orc, ref):
                 assert np.array_equal(cig, oracle.cigar_from_ops(rops, *rclips) if r == 2 else np.zeros(0, dtype=np.uint16)), (name, j, typ)
                 traced_past_end += int(ok and snk[0] > len(txt))
     assert traced_past_end >= 5                                                 # LOCAL sinks on the sentinel, read as 3
+
+
+def test_full_traceback_limit_fuzz(orc, _live_ref):
+    """the full-matrix traceback on a thinned round of the generator of tests/test_gpu_full_traceback_routes.py: one job of every kind, read
+    length, window length and gap column, every short-text job and the reads of 249..252 symbols at the G <= 250 cut, end to end under every
+    scheme of util.LIMIT_SCHEMES (the last under their own as well); the short texts, where the implicit first row and column supply the
+    alignment's ends, under LOCAL and GLOBAL too.  Live only: it pins the oracle that the GPU tests compare with"""
+    if _live_ref is None:
+        pytest.skip("needs the reference's own host code (oracle/_ref)")
+    J = full_limit_jobs(20262)
+    short, cut = np.char.startswith(J["kind"], "short"), J["kind"] == "cut"
+    idx = sorted(set(limit_thin(J).tolist()) | set(np.nonzero(short | cut)[0].tolist()))
+    assert set(J["kind"][idx]) == set(J["kind"]) and len(idx) >= 250 and max(len(J["pats"][j]) for j in idx) <= 256
+    assert {(int(m), int(w)) for m, w in zip(J["M"][idx], J["W"][idx])} >= {(64, 13), (64, 14), (64, 15), (64, 22), (64, 40), (1, 15), (7, 15), (8, 22),
+                                                                           (9, 15), (65, 22), (64, -1), (64, -9), (20, -10), (64, -63), (250, 20), (251, 20)}
+    checked = sink_above = 0
+    for name, sv, with_q in LIMIT_SCHEMES + (FULL_LIMIT_CUT_SCHEME,):
+        sc = oracle.Scheme(*sv)
+        for j in (idx if name != "cut" else np.nonzero(cut)[0]):
+            pat, txt, quals = J["pats"][j], J["txts"][j], J["quals"][j] if with_q else None
+            for typ in ((oracle.SEMI_GLOBAL, oracle.LOCAL, oracle.GLOBAL) if short[j] else (oracle.SEMI_GLOBAL,)):
+                r, rs, rsrc, rsnk, rops, rclips = _live_ref.full_gotoh_traceback(typ, sc, pat, txt, quals)
+                ok, s, src, snk, cig = orc.full_gotoh_traceback(typ, sc, pat, txt, quals)
+                assert (ok, s, src, snk) == (1 if r == 2 else 0, rs, rsrc, rsnk), (name, j, typ)
+                assert np.array_equal(cig, oracle.cigar_from_ops(rops, *rclips) if r == 2 else np.zeros(0, dtype=np.uint16)), (name, j, typ)
+                ops = np.concatenate([np.full(int(c) >> 2, int(c) & 3, dtype=np.uint8) for c in cig if int(c) & 3 != 3] + [np.zeros(0, dtype=np.uint8)])
+                assert np.array_equal(ops, rops), (name, j, typ)
+                checked += 1; sink_above += int(ok and snk[0] < snk[1])
+    assert checked >= 1500 and sink_above >= 300                                # (sinks with x < y: the short texts)
 
 
 def test_full_gotoh_range_fuzz(orc, _live_ref):

@@ -615,15 +615,18 @@ LIMIT_FILLS = (3, 0, 4)                                              # what an o
 LIMIT_SUB_QUALS = (0, 63, 10)                                        # the substituted symbol's quality: a ramp (2..6) charges 2, 6, 3
 
 
-def _limit_path(rng, txt, M, d0, steps):
+def _limit_path(rng, txt, M, d0, steps, front=None):
     """the read that follows `txt` from diagonal d0 on through `steps` = [("D", a) | ("I", b), ...] (D: the read lacks a text symbols, the
-    diagonal moves up; I: b symbols more in the read, it moves down), 6 to 8 clean symbols in front of each and 7 or more behind the last
+    diagonal moves up; I: b symbols more in the read, it moves down), 6 to 8 clean symbols in front of each (`front` of them in front of the
+    first, when given: the read column the first gap starts at) and 7 or more behind the last
     -> (read, last diagonal, read positions free for a substitution)"""
     read, t, free = [], d0, []
     room = M - sum(n for k, n in steps if k == "I")
     flank = max(6, min(8, (room - 7) // len(steps))) if steps else 0
-    for k, n in steps:
+    for i, (k, n) in enumerate(steps):
         f = int(rng.integers(6, flank + 1)) if flank > 6 else 6
+        if i == 0 and front is not None:
+            f = front
         free += list(range(len(read) + 2, len(read) + f - 2))
         read += list(txt[t:t + f]); t += f
         if k == "D":
@@ -725,9 +728,223 @@ def limit_select(J, idx):
 
 
 def limit_thin(J):
-    """one job of every (kind, read length, window length, overhang fill and diagonal) of limit_jobs()' result, from the middle of each group"""
+    """one job of every (kind, read length, window length, overhang fill and diagonal) of limit_jobs()' result -- of every (kind, read length,
+    window length, fill, gap column) of full_limit_jobs()' --, from the middle of each group"""
     groups = {}
+    win = J["win"] if "win" in J else J["W"]
     for j in range(len(J["kind"])):
         over = J["kind"][j] == "overhang"
-        groups.setdefault((J["kind"][j], int(J["M"][j]), int(J["win"][j]) if not over else int(J["e"][j]), int(J["fill"][j])), []).append(j)
+        key = (J["kind"][j], int(J["M"][j]), int(win[j]) if not over else int(J["e"][j]), int(J["fill"][j]))
+        groups.setdefault(key + ((int(J["col"][j]),) if "col" in J else ()), []).append(j)
     return np.array(sorted(g[len(g) // 2] for g in groups.values()))
+
+
+# ---------------------------------------------------------------------------------------------
+# inputs for the full-matrix traceback at the limits of its routes (tests/test_full_traceback_limit_jobs.py,
+# tests/test_gpu_full_traceback_routes.py, tests/test_oracle_vs_reference.py::test_full_traceback_limit_fuzz)
+# ---------------------------------------------------------------------------------------------
+FULL_LIMIT_WINDOWS = (13, 14, 15, 22, 40)                            # window = M + this: M + 14 is the first the band route takes
+FULL_LIMIT_COLS = (7, 8, 9, 15, 16, 17, 30)                          # the read column a gap starts at: on, before and behind a stripe boundary
+FULL_LIMIT_READ_LENS = (1, 7, 8, 9, 16, 17, 33, 64, 65)
+FULL_LIMIT_SHORT_K = (1, 7, 8, 9)                                    # short texts: N = M - k
+FULL_LIMIT_CUT_SCHEME = ("cut", (0, 3, 3, -1, -1, -1, -1), False)    # go_min = ge_min = 1: G = -best, the cut G <= 250 | 251 at M = 250 | 251
+FULL_LIMIT_CUT_LENS = (249, 250, 251, 252)
+FULL_LIMIT_MARGIN = 64                                               # text in front of the first window and behind the last
+ALN_NO_UNGAPPED_TRACEBACK, ALN_NO_NARROW_TRACEBACK, ALN_NO_BAND_ROUTE = 16, 64, 1024    # NVBIO_ALN_* of include/nvbio_amd.h
+
+
+def full_limit_jobs(seed):
+    """jobs built so that the intended alignment of each ends on a chosen sink diagonal `delta` = sink.x - sink.y of a window of M + W
+    symbols, deterministic from the seed -> dict of per-job lists / arrays as limit_jobs(): pats (as aligned), txts (the window), quals, kind,
+    delta, L (gap symbols; substitutions of an ungapped job; the k of a short text), M, W (= N - M), fill (4: the read holds an N, else -1),
+    col (the read column the first gap starts at, else -1).
+
+      del, ins            one gap of L = 1..12 symbols ending on delta, wherever the path stays on diagonals 0..W; M = LIMIT_M; W in
+                          FULL_LIMIT_WINDOWS with every delta (W = 40: 0..9, 19, 20, 31..40); col cycles through FULL_LIMIT_COLS per kind
+      del+sub, ins+sub    the same with one substitution (its quality cycles through LIMIT_SUB_QUALS)
+      split               the gap as two of opposite kind, L = a + b, in both orders
+      lens                reads of FULL_LIMIT_READ_LENS: ungapped or with one substitution; from 16 symbols on with one gap of 1, 2, 3 or 8 as
+                          well, from 7 to 9 with a deletion of one symbol (for the restricted rows and the band: a lone substitution is settled)
+      ungapped            0..3 substitutions at every delta of W = 15 and W = 40; every seventh read holds an N
+      short               N = M - k for k in FULL_LIMIT_SHORT_K, and N = 1: the read is the text and k more symbols behind it ("short") or
+                          in front ("short_lead"); sink.x < sink.y, delta = -k
+      cut                 reads of FULL_LIMIT_CUT_LENS symbols 0 in windows of M + 20 that hold no 0: three letters, and two letters"""
+    rng = np.random.default_rng(seed)
+    keys = ("pats", "txts", "quals", "kind", "delta", "L", "M", "W", "fill", "col")
+    J = {k: [] for k in keys}
+    nsub, ncol = [0], {}
+
+    def add(kind, pat, txt, delta, L, M, W, fill=-1, col=-1, subs=()):
+        q = rng.integers(0, 64, M, dtype=np.uint8)
+        for p in subs:
+            q[p] = LIMIT_SUB_QUALS[nsub[0] % 3]; nsub[0] += 1
+        for key, v in zip(keys, (pat, txt, q, kind, delta, L, M, W, fill, col)):
+            J[key].append(v)
+
+    def gap_jobs(M, W, deltas, lens, cols, tag=None):
+        for delta in deltas:
+            for L in lens:
+                plans = [("del", [("D", L)], delta - L), ("ins", [("I", L)], delta + L)]
+                if L > 1:
+                    a = delta % (L - 1) + 1; b = L - a
+                    plans += [("split", [("D", a), ("I", b)], delta + b - a), ("split", [("I", a), ("D", b)], delta - b + a)]
+                for kind, steps, d0 in plans:
+                    d, inside = d0, 0 <= d0 <= W
+                    for k, n in steps:
+                        d += n if k == "D" else -n
+                        inside = inside and 0 <= d <= W
+                    if not inside:                                   # (the path leaves the window)
+                        continue
+                    for sub in ((0, 1) if kind != "split" else (0,)):
+                        name = kind + ("+sub" if sub else "")
+                        ins = sum(n for k, n in steps if k == "I")
+                        fit = [c for c in cols if c + ins + 8 * (len(steps) - 1) + 7 <= M]
+                        if not fit:
+                            continue
+                        col = fit[ncol.get((name, M), 0) % len(fit)]; ncol[(name, M)] = ncol.get((name, M), 0) + 1
+                        txt = rng.integers(0, 4, M + W, dtype=np.uint8)
+                        pat, end, free = _limit_path(rng, txt, M, d0, steps, front=col)
+                        assert end == delta
+                        subs = ()
+                        if sub:
+                            p = int(free[int(rng.integers(0, len(free)))])
+                            pat[p] = (pat[p] + 1 + rng.integers(0, 3)) % 4; subs = (p,)
+                        add(tag or name, pat, txt, delta, L, M, W, col=col, subs=subs)
+
+    for W in FULL_LIMIT_WINDOWS:
+        deltas = range(W + 1) if W != 40 else list(range(10)) + [19, 20] + list(range(31, 41))
+        gap_jobs(LIMIT_M, W, deltas, range(1, 13), FULL_LIMIT_COLS)
+    for M in FULL_LIMIT_READ_LENS:
+        for W in (15, 22):
+            for delta in (0, 6, 7, 8, W - 7, W - 6, W):
+                for s in (0, 1):
+                    txt = rng.integers(0, 4, M + W, dtype=np.uint8)
+                    pat = txt[delta:delta + M].copy()
+                    subs = tuple(int(p) for p in rng.choice(M, s, replace=False))
+                    for p in subs:
+                        pat[p] = (pat[p] + 1 + rng.integers(0, 3)) % 4
+                    add("lens", pat, txt, delta, s, M, W, subs=subs)
+        if 7 <= M < 16:                                              # (too short for _limit_path's flanks: one text symbol skipped mid-read)
+            for W in (15, 22):
+                for d0 in (0, 5, 6, 7, W - 8, W - 7, W - 1):
+                    txt = rng.integers(0, 4, M + W, dtype=np.uint8)
+                    c = M // 2
+                    add("lens", np.concatenate([txt[d0:d0 + c], txt[d0 + c + 1:d0 + M + 1]]), txt, d0 + 1, 1, M, W, col=c)
+        if M >= 16:
+            gap_jobs(M, 22, (0, 3, 7, 8, 11, 15, 19, 22), (1, 2, 3, 8), FULL_LIMIT_COLS, tag="lens")
+    for W in (15, 40):
+        for delta in range(W + 1):
+            for s in range(4):
+                txt = rng.integers(0, 4, LIMIT_M + W, dtype=np.uint8)
+                pat = txt[delta:delta + LIMIT_M].copy()
+                subs = tuple(int(p) for p in rng.choice(LIMIT_M, s, replace=False))
+                for p in subs:
+                    pat[p] = (pat[p] + 1 + rng.integers(0, 3)) % 4
+                fill = -1
+                if len(J["pats"]) % 7 == 0:
+                    pat[int(rng.integers(0, LIMIT_M))] = 4; fill = 4
+                add("ungapped", pat, txt, delta, s, LIMIT_M, W, fill=fill, subs=subs)
+    for M, N in [(LIMIT_M, LIMIT_M - k) for k in FULL_LIMIT_SHORT_K] + [(20, 10), (LIMIT_M, 1), (9, 1), (33, 24)]:
+        for rep in range(4):
+            txt = rng.integers(0, 4, N, dtype=np.uint8)
+            more = rng.integers(0, 4, M - N, dtype=np.uint8)       # (its ends differ from the text's: the insertions cannot slide inwards)
+            more[-1] = (txt[-1] + 1 + rng.integers(0, 3)) % 4 if more[-1] == txt[-1] else more[-1]
+            more[0] = (txt[0] + 1 + rng.integers(0, 3)) % 4 if more[0] == txt[0] else more[0]
+            add("short", np.concatenate([txt, more]), txt, N - M, M - N, M, N - M)
+            add("short_lead", np.concatenate([more, txt]), txt, N - M, M - N, M, N - M)
+    for M in FULL_LIMIT_CUT_LENS:
+        for letters in ((1, 2, 3), (1, 2, 3), (1, 2, 3), (1, 3)):
+            txt = rng.choice(np.array(letters, dtype=np.uint8), M + 20)
+            add("cut", np.zeros(M, dtype=np.uint8), txt, 20, M, M, 20)
+    for key in keys[3:]:
+        J[key] = np.array(J[key])
+    return J
+
+
+def full_limit_layout(J, with_q, flags=None):
+    """full_layout() of full_limit_jobs()' jobs (or a limit_select() of them), the windows inside one text with FULL_LIMIT_MARGIN symbols in
+    front of the first and behind the last: a window rule that is off by one reads text, never memory outside the buffer"""
+    L = full_layout(J["pats"], J["txts"], J["quals"] if with_q else None, flags)
+    m = (np.arange(FULL_LIMIT_MARGIN) % 4).astype(np.uint8)
+    L["text"] = np.concatenate([m, L["text"], m[::-1]])
+    for key in ("wb", "we", "toffs"):
+        L[key] = (L[key] + FULL_LIMIT_MARGIN).astype(np.uint32)
+    return L
+
+
+def full_limit_oracle(orc, typ, sv, J, with_q, stride, min_scores=None):
+    """orc.full_gotoh_traceback job by job -> (scores, sources, sinks, cigars[n, stride], lens) as the GPU entry point lays them out: the
+    CIGAR's elements beyond `stride` dropped, its length not"""
+    import oracle
+    n = len(J["pats"])
+    sc = oracle.Scheme(*sv)
+    scores = np.zeros(n, dtype=np.int32); lens = np.zeros(n, dtype=np.uint32)
+    sources = np.zeros((n, 2), dtype=np.uint32); sinks = np.zeros((n, 2), dtype=np.uint32)
+    cigars = np.zeros((n, stride), dtype=np.uint16)
+    for j in range(n):
+        ms = oracle.SCORE_MIN if min_scores is None else int(min_scores[j])
+        ok, s, src, snk, cig = orc.full_gotoh_traceback(typ, sc, J["pats"][j], J["txts"][j], J["quals"][j] if with_q else None, ms)
+        scores[j], sources[j], sinks[j], lens[j] = s, src, snk, len(cig)
+        cigars[j, :min(len(cig), stride)] = cig[:stride]
+    return scores, sources, sinks, cigars, lens
+
+
+def full_gap_mins(sv):
+    """the cheapest gap opening / extension penalty of a scheme (narrow_e2e's go_min, ge_min)"""
+    return -max(sv[3], sv[5]), -max(sv[4], sv[6])
+
+
+def full_gap_bound(a, sv):
+    """e2e_gap_bound of the cost a = -best"""
+    go, ge = full_gap_mins(sv)
+    return 0 if a < go else (a - go) // ge + 1
+
+
+def full_narrow_scheme(typ, sv):
+    """narrow_e2e without the algo flag"""
+    go, ge = full_gap_mins(sv)
+    return typ == _SEMI_GLOBAL and sv[0] == 0 and sv[1] >= 0 and sv[2] >= 0 and ge > 0 and go >= ge
+
+
+def _full_diagonal_settles(pat, q, txt, typ, sv, best, sink):
+    """ungapped_full_traceback_kernel's walk: do the k diagonal steps that end in `sink` score `best` -- SEMI_GLOBAL: k = sink.y, which needs
+    sink.x >= sink.y; LOCAL: some k <= min(sink.x, sink.y), or best == 0; GLOBAL: never"""
+    x, y = int(sink[0]), int(sink[1])
+    if typ == _GLOBAL or (typ == _SEMI_GLOBAL and x < y):
+        return False
+    k = min(x, y)
+    p = pat[y - k:y].astype(np.int64)
+    g = txt[x - k:x].astype(np.int64)
+    qq = np.minimum(q[y - k:y].astype(np.int64), 40) if q is not None else np.zeros(k, dtype=np.int64)
+    mm = sv[1] + (qq.astype(np.float32) / np.float32(40) * np.float32(sv[2] - sv[1])).astype(np.int64)
+    step = np.where(g == p, sv[0], -mm)
+    if typ == _LOCAL:
+        return best == 0 or bool((np.cumsum(step[::-1]) == best).any())
+    return k == y and int(step.sum()) == best
+
+
+def full_route_rule(J, with_q, typ, sv, want, algo=0):
+    """(routes, gap_bound) of every job of nvbio_full_gotoh_traceback_routes, restated from the conditions of csrc/gotoh_full_traceback.hip
+    on the oracle's score and sink (`want` as full_limit_oracle() returns it): 0 where nothing is traced or the sink's diagonal settles the job;
+    else 1, or under a scheme narrow_e2e admits, with the sink in the last pattern row, best <= 0 and G = e2e_gap_bound(best) <= 250: 2 with
+    gap_bound G -- 3 where also G <= 7, sink.x >= sink.y, N >= M + 14 and 7 <= delta <= N - M - 7"""
+    n = len(J["pats"])
+    routes, bound = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    if algo & ALN_NO_UNGAPPED_TRACEBACK:
+        return routes + 1, bound
+    narrow = full_narrow_scheme(typ, sv) and not algo & ALN_NO_NARROW_TRACEBACK
+    band = narrow and not algo & ALN_NO_BAND_ROUTE
+    sc, sk = want[0], want[2].astype(np.int64)
+    for j in range(n):
+        M, N = len(J["pats"][j]), len(J["txts"][j])
+        if want[4][j] == 0 or _full_diagonal_settles(J["pats"][j], J["quals"][j] if with_q else None, J["txts"][j], typ, sv, int(sc[j]), sk[j]):
+            continue
+        routes[j] = 1
+        if narrow and sk[j, 1] == M and sc[j] <= 0:
+            G = full_gap_bound(-int(sc[j]), sv)
+            if G <= 250:
+                routes[j], bound[j] = 2, G
+                delta = int(sk[j, 0] - sk[j, 1])
+                if band and G <= 7 and sk[j, 0] >= sk[j, 1] and N >= M + 14 and delta >= 7 and delta + 7 <= N - M:
+                    routes[j] = 3
+    return routes, bound
