@@ -1930,6 +1930,9 @@ static bool ungapped_ok(const SchemeDev& sc, const BatchDev& b, int32_t* P, bool
 {
     if (sc.match != 0) return false;
     if (sc.mm_min < 0 || sc.mm_max < 0) return false;
+    // a mismatch that costs nothing (mm_min = 0; a batch without qualities is charged mm_min whatever mm_max is): every diagonal scores 0, and
+    // BestSink's last maximum is the last reportable column, not the diagonal with the fewest mismatches the first pass would report
+    if (sc.mm_min == 0) return false;
     // the penalty depends on the row (nvBowtie's default: 2..6 by base quality): the first pass sums the candidates' rows exactly
     // (QUAL); it needs a ramp that does not decrease with the quality and a smallest penalty > 0
     *by_quality = b.quals != nullptr && sc.mm_min != sc.mm_max;

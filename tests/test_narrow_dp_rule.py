@@ -17,26 +17,11 @@ hold it at row 24.  The monitor is the guard the proof needs for everything the 
 (the qualification's share left out of the numpy run) on exact reads, where what flows outward is known in closed form."""
 import numpy as np
 
-BAND, FULL_ROWS, HALF_A, HALF_B = 31, 24, 6, 8
+from util import BAND31, NARROW_HALF_A, NARROW_HALF_B, classes, reach
+
+BAND, FULL_ROWS, HALF_A, HALF_B = BAND31, 24, NARROW_HALF_A, NARROW_HALF_B
 NEG = -16384
 SCHEMES = ((6, -8, -3), (2, -5, -1), (4, -6, -6), (3, -4, -2), (6, -5, -3))        # (mismatch penalty, gap open, gap extension)
-
-
-def reach(L, go, ge):
-    """r(L): the largest delta with go + (delta - 1) ge >= L (0: not even one column)"""
-    d = 0
-    while d < 64 and go + d * ge >= L:
-        d += 1
-    return d
-
-
-def classes(cnt, P, go, ge):
-    """per job (U*, best_d, class) from the 31 diagonals' mismatch counts: 0 none, 1 = B, 2 = A"""
-    best = cnt.min(axis=1)
-    best_d = (BAND - 1) - np.argmin(cnt[:, ::-1], axis=1)           # ties: the larger column, as BestSink
-    U = -P * best
-    w = np.array([reach(int(u), go, ge) for u in U]) + np.abs(best_d - 15)
-    return U, best_d, np.where(w <= HALF_A, 2, np.where(w <= HALF_B, 1, 0))
 
 
 def mismatches(reads, wins):

@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 
 import oracle
-from util import (FULL_KINDS, FULL_LIMIT_CUT_SCHEME, LIMIT_SCHEMES, RANGE_KINDS, flat_scheme, full_jobs, full_limit_jobs, full_shapes, limit_jobs,
-                  limit_thin, range_jobs)
+from util import (E2E31_CORNERS, E2E31_SWEEP, FULL_KINDS, FULL_LIMIT_CUT_SCHEME, LIMIT_SCHEMES, RANGE_KINDS, e2e31_sweep_jobs, flat_scheme, full_jobs,
+                  full_limit_jobs, full_shapes, limit_jobs, limit_thin, range_jobs)
 
 SCHEMES = [oracle.Scheme.simple(2, -1, -1, -1), oracle.Scheme.simple(0, -5, -8, -3),
            oracle.Scheme.simple(2, -1, -2, -1), oracle.Scheme(2, 2, 6, -8, -3, -8, -3),
@@ -123,6 +123,23 @@ def test_traceback_limit_fuzz(orc, ref):
                 assert np.array_equal(cig, oracle.cigar_from_ops(rops, *rclips) if r == 2 else np.zeros(0, dtype=np.uint16)), (name, j, typ)
                 traced_past_end += int(ok and snk[0] > len(txt))
     assert traced_past_end >= 5                                                 # LOCAL sinks on the sentinel, read as 3
+
+
+def test_e2e31_scheme_sweep(orc, ref):
+    """band 31, SEMI_GLOBAL, under every scheme of the sweep of tests/test_gpu_band31_scheme_sweep.py -- the 138 of util.E2E31_SWEEP and the
+    corners of util.E2E31_CORNERS, the ramps with the pool's qualities -- on every 40th job of its pool: a mismatch that costs nothing, a gap
+    extension that costs nothing, an opening cheaper than an extension, P = 30 against gaps of 2 and 1.  ok, score and sink are equal"""
+    J = e2e31_sweep_jobs(1)
+    idx = range(0, len(J["pats"]), 40)
+    assert len(idx) >= 100 and len(set(J["kind"][list(idx)])) >= 12
+    cases = 0
+    for sv, with_q in [(sv, False) for sv in E2E31_SWEEP] + [(c[1], c[2]) for c in E2E31_CORNERS]:
+        sc = oracle.Scheme(*sv)
+        for j in idx:
+            pat, txt, quals = J["pats"][j], J["txts"][j], J["quals"][j] if with_q else None
+            assert ref.banded_gotoh(31, oracle.SEMI_GLOBAL, sc, pat, txt, quals) == orc.banded_gotoh(31, oracle.SEMI_GLOBAL, sc, pat, txt, quals), (sv, j)
+            cases += 1
+    assert cases >= 138 * 100
 
 
 def test_full_traceback_limit_fuzz(orc, _live_ref):

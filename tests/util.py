@@ -948,3 +948,332 @@ def full_route_rule(J, with_q, typ, sv, want, algo=0):
                 if band and G <= 7 and sk[j, 0] >= sk[j, 1] and N >= M + 14 and delta >= 7 and delta + 7 <= N - M:
                     routes[j] = 3
     return routes, bound
+
+
+# ---------------------------------------------------------------------------------------------
+# the band-31 end-to-end shortcuts over the scheme space (tests/test_e2e31_sweep_jobs.py, tests/test_gpu_band31_scheme_sweep.py,
+# tests/test_oracle_vs_reference.py::test_e2e31_scheme_sweep)
+# ---------------------------------------------------------------------------------------------
+BAND31, NARROW_HALF_A, NARROW_HALF_B = 31, 6, 8                      # the narrow classes' half-widths (csrc/gotoh_banded.hip)
+ALN_NO_UNGAPPED_SCORE, ALN_NO_THIRD_CHANCE, ALN_PK_THREE_WAVES, ALN_NO_SECOND_CHANCE = 1, 2, 32, 128    # NVBIO_ALN_* of include/nvbio_amd.h
+ALN_NO_QUALITY_SHORTCUT, ALN_RAGGED_READS, ALN_NO_F16_DP, ALN_NO_GAP_CHANCE = 2048, 4096, 16384, 65536
+ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE, ALN_NO_NARROW_DP = 131072, 262144, 524288
+
+
+def reach(L, go, ge):
+    """r(L): the largest delta with go + (delta - 1) ge >= L (0: not even one column)"""
+    d = 0
+    while d < 64 and go + d * ge >= L:
+        d += 1
+    return d
+
+
+def classes(cnt, P, go, ge):
+    """per job (U*, best_d, class) from the 31 diagonals' mismatch counts: 0 none, 1 = B, 2 = A"""
+    best = cnt.min(axis=1)
+    best_d = (BAND31 - 1) - np.argmin(cnt[:, ::-1], axis=1)         # ties: the larger column, as BestSink
+    U = -P * best
+    w = np.array([reach(int(u), go, ge) for u in U]) + np.abs(best_d - 15)
+    return U, best_d, np.where(w <= NARROW_HALF_A, 2, np.where(w <= NARROW_HALF_B, 1, 0))
+
+
+def _sweep_grid():
+    out = []
+    for P in (0, 1, 2, 3, 6, 30):
+        for go in (1, 2, 5, 8, 40):
+            for ge in sorted({0, 1, 3, go, go + 2}):
+                out.append((0, P, P, -go, -ge, -go, -ge))
+    return tuple(out)
+
+
+# every (P, |go|, |ge|) of P in {0, 1, 2, 3, 6, 30} x |go| in {1, 2, 5, 8, 40} x |ge| in {0, 1, 3, |go|, |go| + 2}: 138 symmetric schemes
+E2E31_SWEEP = _sweep_grid()
+
+# (name, scheme, base qualities?): one or more per regime of the three numbers the shortcuts' arguments rest on
+E2E31_CORNERS = (
+    ("p0", (0, 0, 0, -5, -3, -5, -3), False),                        # a mismatch costs nothing: every diagonal scores 0
+    ("p0_linear", (0, 0, 0, -2, -2, -2, -2), False),
+    ("ge0", (0, 6, 6, -8, 0, -8, 0), False),                         # a gap costs its opening whatever its length
+    ("ge0_p1", (0, 1, 1, -5, 0, -5, 0), False),
+    ("open_below_ext", (0, 6, 6, -2, -5, -2, -5), False),            # |go| < |ge|: the first gap symbol is the cheapest
+    ("open_below_ext_p3", (0, 3, 3, -1, -3, -1, -3), False),
+    ("open_below_ext_p1", (0, 1, 1, -2, -5, -2, -5), False),         # ... with a U* the second chance takes: two mismatches
+    ("two_gaps_tie", (0, 2, 2, -1, -3, -1, -3), False),              # P = 2 |G|: two gaps of one symbol tie a diagonal with one mismatch
+    ("edit_distance", (0, 1, 1, -1, -1, -1, -1), False),             # go == ge == -P
+    ("linear_p_below", (0, 1, 1, -3, -3, -3, -3), False),
+    ("linear_p_above", (0, 5, 5, -2, -2, -2, -2), False),
+    ("p30_cheap_gaps", (0, 30, 30, -2, -1, -2, -1), False),          # five gaps cost less than one mismatch
+    ("p1_dear_gaps", (0, 1, 1, -40, -3, -40, -3), False),            # cap = 120
+    ("pinned_6_8_3", (0, 6, 6, -8, -3, -8, -3), False),              # the six the route tests held before this sweep
+    ("pinned_2_5_1", (0, 2, 2, -5, -1, -5, -1), False),
+    ("pinned_4_6_6", (0, 4, 4, -6, -6, -6, -6), False),
+    ("pinned_3_4_2", (0, 3, 3, -4, -2, -4, -2), False),
+    ("pinned_6_5_3", (0, 6, 6, -5, -3, -5, -3), False),
+    ("pinned_3_3_3_txt_9_1", (0, 3, 3, -3, -3, -9, -1), False),
+    ("cheap_txt", (0, 6, 6, -11, -4, -6, -2), False),                # asymmetric: G comes from the text gap, the recurrences' terms from the pattern gap
+    ("cheap_pat", (0, 6, 6, -6, -2, -11, -4), False),
+    ("ramp_2_6", (0, 2, 6, -8, -3, -8, -3), True),
+    ("ramp_1_7", (0, 1, 7, -8, -3, -8, -3), True),
+    ("ramp_3_10", (0, 3, 10, -8, -3, -8, -3), True),
+    ("ramp_0_6_no_quals", (0, 0, 6, -8, -3, -8, -3), False),         # without qualities every mismatch costs mm_min = 0
+)
+E2E31_SWEEP_M = (64, 161)                                            # the read lengths of what e2e31_sweep_jobs() adds to limit_jobs()
+E2E31_SWEEP_DIAGONALS = (0, 7, 15, 23, 30)
+
+
+def e2e31_sweep_jobs(seed):
+    """limit_jobs(seed) and, at M = 64 and M = 161 in windows of M + 31, what that pool lacks -> the same dict (e: the diagonal the intended
+    alignment ends on, L: gap symbols, or substitutions / N's of an ungapped job):
+
+      subs            4..12 substitutions on diagonals 0, 7, 15, 23 and 30: spread over the read, clustered at its front, at its end
+      gap+subs        one gap of 1..3 symbols and 2 or 3 substitutions
+      gaps2, gaps3    two and three gaps of one symbol, every order of kinds
+      longgap         one gap of 5, 6 or 9 symbols (the gap chance evaluates up to 5), alone and with one substitution
+      periodic        reads on text of period 1, 2 and 3 with 0, 1, 2 and 4 substitutions: co-optimal alignments on every diagonal
+      periodic_gap    a one-symbol gap inside a run of period 1, 2 or 3 in random text: the gap's placements tie
+      n               reads with one N and with three N's, 0..2 substitutions beside them
+      near_centre     4 and 5 substitutions on diagonals 13..17: the narrow classes' jobs at 0 / -6 / -8 / -3
+      many_subs       M = 161 with 38..43 substitutions: second and third chance where a mismatch costs 1 and a gap 40
+      allmm           a read of one letter in a window of the other three: beyond every cap"""
+    J = limit_jobs(seed)
+    J = {k: (list(v) if not isinstance(v, list) else v) for k, v in J.items()}
+    rng = np.random.default_rng(seed + 7919)
+    nsub = [0]
+
+    def add(kind, pat, txt, e, L, M, subs=()):
+        q = rng.integers(0, 64, M, dtype=np.uint8)
+        for p in subs:
+            q[p] = LIMIT_SUB_QUALS[nsub[0] % 3]; nsub[0] += 1
+        for key, v in zip(("pats", "txts", "quals", "kind", "e", "L", "M", "win", "fill"), (np.asarray(pat, dtype=np.uint8), txt, q, kind, e, L, M, 31, -1)):
+            J[key].append(v)
+
+    def substitute(pat, pos):
+        pos = np.asarray(pos, dtype=np.int64)
+        pat[pos] = (pat[pos] + 1 + rng.integers(0, 3, len(pos))) % 4
+        return tuple(int(p) for p in pos)
+
+    for M in E2E31_SWEEP_M:
+        for e in E2E31_SWEEP_DIAGONALS:
+            for k in range(4, 13):
+                for where in range(3):
+                    txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                    pat = txt[e:e + M].copy()
+                    pos = (rng.choice(M, k, replace=False), rng.choice(16, k, replace=False), M - 16 + rng.choice(16, k, replace=False))[where]
+                    add("subs", pat, txt, e, k, M, substitute(pat, pos))
+        for e in (4, 15, 26):
+            for L in (1, 2, 3):
+                for kind, d0 in (("D", e - L), ("I", e + L)):
+                    for k in (2, 3):
+                        txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                        pat, end, free = _limit_path(rng, txt, M, d0, [(kind, L)])
+                        assert end == e
+                        add("gap+subs", pat, txt, e, L, M, substitute(pat, rng.choice(free, k, replace=False)))
+            for plan in ("DD", "DI", "ID", "II", "DDD", "DID", "IDI", "III"):
+                d0 = e - plan.count("D") + plan.count("I")
+                txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                pat, end, free = _limit_path(rng, txt, M, d0, [(k, 1) for k in plan])
+                assert end == e
+                add("gaps%d" % len(plan), pat, txt, e, len(plan), M)
+        for e in (10, 15, 20):
+            for L in (5, 6, 9):
+                for kind, d0 in (("D", e - L), ("I", e + L)):
+                    for k in (0, 1):
+                        txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                        pat, end, free = _limit_path(rng, txt, M, d0, [(kind, L)])
+                        assert end == e
+                        add("longgap", pat, txt, e, L, M, substitute(pat, rng.choice(free, k, replace=False)))
+        for e in E2E31_SWEEP_DIAGONALS:
+            for period in (1, 2, 3):
+                for k in (0, 1, 2, 4):
+                    unit = rng.permutation(4)[:period].astype(np.uint8)
+                    txt = np.resize(unit, M + 31)
+                    pat = txt[e:e + M].copy()
+                    add("periodic", pat, txt, e, k, M, substitute(pat, rng.choice(M, k, replace=False)))
+        for e in (5, 15, 25):
+            for period in (1, 2, 3):
+                for kind in ("D", "I"):
+                    txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                    d0 = e - 1 if kind == "D" else e + 1
+                    at, run = M // 2, 24                             # the run covers rows at - 12 .. at + 12 of both diagonals
+                    txt[min(d0, e) + at - 12:max(d0, e) + at + 12] = np.resize(rng.permutation(4)[:period].astype(np.uint8), run + 1)
+                    pat = np.concatenate([txt[d0:d0 + at], txt[d0 + at + 1:d0 + M + 1]]) if kind == "D" else \
+                        np.concatenate([txt[d0:d0 + at], txt[d0 + at - 1:d0 + at], txt[d0 + at:d0 + M - 1]])
+                    assert len(pat) == M
+                    add("periodic_gap", pat, txt, e, 1, M)
+        for e in E2E31_SWEEP_DIAGONALS:
+            for n_count in (1, 3):
+                for k in (0, 1, 2):
+                    txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                    pat = txt[e:e + M].copy()
+                    pos = rng.choice(M, n_count + k, replace=False)
+                    subs = substitute(pat, pos[n_count:])
+                    pat[pos[:n_count]] = 4
+                    add("n", pat, txt, e, n_count, M, subs)
+        for e in (13, 14, 15, 16, 17):
+            for k in (4, 5):
+                for rep in range(6):
+                    txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                    pat = txt[e:e + M].copy()
+                    add("near_centre", pat, txt, e, k, M, substitute(pat, rng.choice(M, k, replace=False)))
+        if M == 161:
+            for e in E2E31_SWEEP_DIAGONALS:
+                for k in range(38, 44):
+                    for rep in range(2):
+                        txt = rng.integers(0, 4, M + 31, dtype=np.uint8)
+                        pat = txt[e:e + M].copy()
+                        add("many_subs", pat, txt, e, k, M, substitute(pat, rng.choice(M, k, replace=False)))
+        for a in range(4):
+            for rep in range(2):
+                txt = ((a + 1 + rng.integers(0, 3, M + 31)) % 4).astype(np.uint8)
+                add("allmm", np.full(M, a, dtype=np.uint8), txt, 30, M, M)
+    for key in ("kind", "e", "L", "M", "win", "fill"):
+        J[key] = np.array(J[key])
+    assert len(J["pats"]) < 6000
+    return J
+
+
+def e2e31_counts(J, with_q_scheme=None):
+    """per job the 31 diagonals' mismatch counts, diagonal d = the read against the window from its symbol d on; -1 where the diagonal does not
+    lie inside the window (it holds no reportable column).  An N differs from every symbol.  with_q_scheme = a scheme: the diagonals'
+    penalty sums under its quality ramp instead (mismatch_score() of csrc/gotoh_common.h: mm_min + int( min(q, 40) / 40 * (mm_max - mm_min) )
+    in binary32)"""
+    n = len(J["pats"])
+    out = np.full((n, BAND31), -1, dtype=np.int64)
+    for j in range(n):
+        pat, txt = J["pats"][j], J["txts"][j]
+        M, N = len(pat), len(txt)
+        w = np.ones(M, dtype=np.int64)
+        if with_q_scheme is not None:
+            lo, hi = with_q_scheme[1], with_q_scheme[2]
+            q = np.minimum(J["quals"][j].astype(np.int64), 40)
+            w = lo + (q.astype(np.float32) / np.float32(40) * np.float32(hi - lo)).astype(np.int64)
+        for d in range(min(BAND31, N - M + 1)):
+            out[j, d] = int(w[pat != txt[d:d + M]].sum())
+    return out
+
+
+def e2e31_admitted(sv, has_quals, max_read_len, algo=0):
+    """does nvbio_banded_gotoh_score send a SEMI_GLOBAL band-31 batch of 4- or 2-bit reads on a 2-bit text through the shortcuts at all --
+    packed_ok() and ungapped_ok() of csrc/gotoh_banded.hip as the code has them"""
+    match, mm_min, mm_max, pat_go, pat_ge, txt_go, txt_ge = (int(v) for v in sv)
+    if algo & ALN_NO_UNGAPPED_SCORE or not _band31_int16_ok(sv, int(max_read_len)):
+        return False
+    if match != 0 or mm_min < 0 or mm_max < 0:
+        return False
+    if has_quals and mm_min != mm_max and (mm_min <= 0 or mm_max < mm_min or algo & ALN_NO_QUALITY_SHORTCUT):
+        return False
+    return pat_go < 0 and txt_go < 0 and pat_ge <= 0 and txt_ge <= 0 and mm_min > 0
+
+
+def e2e31_classes_on(sv, has_quals, max_read_len, algo=0):
+    """are the DP's narrow classes formed: narrow_rule() and its caller's condition (the binary16 DP follows, no qualities, not ragged)"""
+    P, go, ge = int(sv[1]), int(sv[3]), int(sv[4])
+    f16 = (not algo & (ALN_PK_THREE_WAVES | ALN_NO_F16_DP) and sv[0] == 0 and (int(max_read_len) + 32) * scheme_step(sv) <= 2040 and sv[2] <= 400)
+    on = not has_quals and not algo & (ALN_NO_NARROW_DP | ALN_RAGGED_READS) and f16
+    return bool(on and ge < 0 and P > 0 and go + NARROW_HALF_B * ge + 1 >= -2000)
+
+
+def e2e31_first_pass(sv, has_quals, M, N, counts, weights=None, max_read_len=None, algo=0):
+    """The first pass's rule AS THE CODE HAS IT (ungapped_e2e31_job, MODE 0, of csrc/gotoh_banded.hip), restated in numpy: this is a copy of
+    the conditions, not a derivation of what they should be -- the tests hold the library's results to the oracle and its routes to this.
+    From each job's read length M, window length N and 31 diagonal mismatch counts (e2e31_counts(): -1 off the window; under a quality ramp
+    also `weights`, the diagonals' penalty sums) -> (flag, class) per job:
+
+      flag 0  settled (U* > G, or nothing to report: N < M)       flag 3  second chance       flag 2  third chance       flag 4  gap chance
+      flag 1  the DP, with its narrow class (0 none, 1 = B, 2 = A, as classes(); max_read_len decides whether classes are formed at all)
+
+    With P = mm_min, go / ge the pattern gap's terms and G = max(pat_go, txt_go):
+      floor_u = 3 min(G, go) - P, cap = the largest count with -P cnt > floor_u; cap_x = the largest count whose U* is still in class B, where
+      that is larger, the classes are formed and the window is whole (N >= M + 30); best_cnt / best_d the fewest mismatches of a diagonal
+      inside the window and the LAST diagonal that has them
+      best_cnt > cap: class job if best_cnt <= cap_x and it has a class; else flag 4 if no ramp, P > 0, N >= M + 30, ge < 0, go <= ge; else DP
+      U* = -P best_cnt (ramp: DP if U* <= 3 G - P, else U* = the largest penalty sum's negative among the diagonals with P cnt <= pmax best_cnt)
+      U* > G: settled
+      second_applies = G - P < U* and 2 G < U* and N >= M + 30, with gmax = the gap lengths 1..5 that reach U*, 1 <= gmax <= 4
+      third_applies = N >= M + 30, not `beyond` (gmax0 > 4, gmax1 > 4, go - 2P, 2go + ge, 2go - P or 3go >= U*, ge < go), gmax0 >= 1 and
+      (gmax1 >= 1 or 2 go >= U*)"""
+    match, mm_min, mm_max, pat_go, pat_ge, txt_go, txt_ge = (int(v) for v in sv)
+    P, go, ge, G = mm_min, pat_go, pat_ge, max(pat_go, txt_go)
+    qual = bool(has_quals) and mm_min != mm_max
+    M, N, counts = np.asarray(M, dtype=np.int64), np.asarray(N, dtype=np.int64), np.asarray(counts, dtype=np.int64)
+    n = len(M)
+    flag, cls = np.ones(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    floor_u = 3 * min(G, go) - P
+    cap = (-floor_u - 1) // P if P > 0 else 0xFFFFFFFE
+    classes_on = max_read_len is not None and e2e31_classes_on(sv, has_quals, max_read_len, algo)
+    cnt_max = (-(go + NARROW_HALF_B * ge + 1)) // P if classes_on else 0
+    pmax = mm_min + int(np.float32(40) / np.float32(40) * np.float32(mm_max - mm_min))
+
+    def span(base, U):                                               # how many of the gap lengths 1..5 reach U
+        g = 0
+        while g < 5 and base + g * ge >= U:
+            g += 1
+        return g
+
+    def narrow(U, best_d):
+        if not classes_on:
+            return 0
+        w = reach(int(U), go, ge) + abs(int(best_d) - 15)
+        return 2 if w <= NARROW_HALF_A else 1 if w <= NARROW_HALF_B else 0
+
+    for j in range(n):
+        m, nn = int(M[j]), int(N[j])
+        if nn < m:
+            flag[j] = 0
+            continue
+        if m == 0 or m > 161:
+            continue
+        whole = nn >= m + 30
+        on = counts[j] >= 0
+        cap_x = cnt_max if (not qual and cnt_max > cap and whole) else cap
+        c = np.where(on, counts[j], 1 << 40)
+        best_cnt = int(c.min())
+        best_d = (BAND31 - 1) - int(np.argmin(c[::-1]))
+        if best_cnt > cap:
+            if not qual and best_cnt <= cap_x and narrow(-P * best_cnt, best_d):
+                cls[j] = narrow(-P * best_cnt, best_d)
+                continue
+            if not qual and P > 0 and whole and ge < 0 and go <= ge and not algo & ALN_NO_GAP_CHANCE:
+                flag[j] = 4
+            continue
+        U = -P * best_cnt
+        if qual:
+            if U <= 3 * G - P:
+                continue
+            cand = on & (P * counts[j] <= pmax * best_cnt)
+            wsum = np.where(cand, weights[j], 1 << 40)
+            U = -int(wsum.min())
+            best_d = (BAND31 - 1) - int(np.argmin(wsum[::-1]))
+        if U > G:
+            flag[j] = 0
+            continue
+        if G - P < U and 2 * G < U and whole and not algo & ALN_NO_SECOND_CHANCE and 1 <= span(go, U) <= 4:
+            flag[j] = 3
+            continue
+        gmax0, gmax1 = span(go, U), span(go - P, U)
+        beyond = gmax0 > 4 or gmax1 > 4 or go - 2 * P >= U or 2 * go + ge >= U or 2 * go - P >= U or 3 * go >= U or ge < go
+        if whole and not beyond and gmax0 >= 1 and (gmax1 >= 1 or 2 * go >= U):
+            flag[j] = 2
+            continue
+        if not qual and whole:
+            cls[j] = narrow(U, best_d)
+    return flag, cls
+
+
+def e2e31_possible_flags(sv, has_quals, M, max_read_len=None):
+    """the flag values (and, as 10 + class, the classes) the rule can produce under a scheme at all for reads of M symbols: e2e31_first_pass() on
+    whole windows whose centre diagonal holds 0..M mismatches and every other diagonal M (under a ramp each at the smallest penalty)"""
+    cnt = np.full((M + 1, BAND31), M, dtype=np.int64)
+    cnt[:, 15] = np.arange(M + 1)
+    flag, cls = e2e31_first_pass(sv, has_quals, np.full(M + 1, M), np.full(M + 1, M + 31), cnt, weights=cnt * sv[1], max_read_len=max_read_len)
+    return {int(f) for f in flag} | {10 + int(c) for c in cls if c}
+
+
+def e2e31_layout(orc, J, idx=None, with_q=False, read_bits=4):
+    """the jobs (all, or `idx`) of e2e31_sweep_jobs() as one packed batch: dict(reads, reads4 -- what the oracle's batch call takes --, bits, roffs,
+    quals, text, wb, we, n, max_len, idx)"""
+    idx = np.arange(len(J["pats"])) if idx is None else np.asarray(idx)
+    S = limit_select(J, idx)
+    L = range_layout(S["pats"], S["txts"], S["quals"] if with_q else None)
+    return dict(reads=orc.pack4(L["reads"]) if read_bits == 4 else orc.pack2(L["reads"]), reads4=orc.pack4(L["reads"]), bits=read_bits, roffs=L["roffs"],
+                quals=L["quals"], text=orc.pack2(L["text"]), wb=L["wb"], we=L["we"], n=len(idx), max_len=int(S["M"].max()), idx=idx)
