@@ -1562,6 +1562,93 @@ nvbio_status nvbio_full_sw_score(int device, nvbio_alignment_type type, int text
                                  const int32_t* min_scores_dev, int32_t* scores_dev, nvbio_uint2* sinks_dev,
                                  void* temp_dev, uint64_t temp_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * SAM output: nvBowtie's alignment records as text, formatted on the device (io::SamOutput, nvbio/io/output/output_sam.cpp:76-544, which
+ * formats on the host, one fwrite per field and one read after another).  A record is a pure function of arrays the other calls leave
+ * in HBM; the text is the reference's byte for byte, with one divergence: generate_md_string sums a run of merged match tokens in a
+ * uint8 (a run of 300 prints 44), here the sum has 32 bits.  The header lines (@HD, @PG, @SQ; :155-178) are built on the host
+ * (nvbio_amd/sam.hpp sam_header, pipeline.sam_header).
+ *   1. nvbio_sam_record_offsets   the byte length of every record and their exclusive uint64 scan (a batch can exceed 4 GiB)
+ *   2. the caller reads offsets_dev[n], the total, and allocates the text
+ *   3. nvbio_sam_format           writes record i to text_dev[offsets[i], offsets[i + 1])
+ * One wave composes one record in LDS and copies it out with 16-byte stores (bytes only at the unaligned head and tail), so a record's
+ * text is bounded by the LDS of a wave.  The bound is taken from the declared maxima:
+ *   max_name_len + 2 * refs->max_name_len + 2 * max_read_len + 6 * cigar_stride + (2 * mds_stride + 16) + 192   bytes of text,
+ *   plus 16 and mds_stride rounded up to 16, must not exceed 16384: else NVBIO_ERR_UNSUPPORTED, before any launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct
+{
+    uint32_t        n_seqs;
+    uint32_t        max_name_len;         /* the longest sequence name, in bytes                                                          */
+    const uint32_t* sequence_index_dev;   /* n_seqs + 1: where each sequence starts in the concatenated genome, [0] = 0
+                                             (io::ConstSequenceDataView / bnt.sequence_index, output_sam.cpp:353-356)                     */
+    const uint8_t*  names_dev;            /* the sequence names' bytes (bnt.names)                                                        */
+    const uint32_t* names_index_dev;      /* n_seqs + 1 offsets into names_dev: name s = [names_index[s], names_index[s + 1]), no NULs     */
+} nvbio_sam_refs;
+
+typedef struct
+{
+    uint32_t        n;                    /* records                                                                                      */
+    uint32_t        max_name_len;         /* the longest QNAME, in bytes                                                                  */
+    uint32_t        max_read_len;         /* the longest read (< 1024)                                                                    */
+    uint32_t        reads_reversed;       /* the reads are stored reversed, as in nvbio_score_stream_flatten (nvBowtie: 1)                */
+    const uint8_t*  names_dev;            /* QNAME bytes ...                                                                              */
+    const uint32_t* name_index_dev;       /* ... n + 1 offsets into them                                                                  */
+    const void*     reads4_dev;           /* the STORED reads, 4-bit big-endian packed words (AlignmentData::read_data, :365-378)         */
+    const uint32_t* read_index_dev;       /* n + 1 symbol offsets                                                                         */
+    const uint8_t*  quals_dev;            /* one byte per stored symbol, printed + 33 (:382-395); NULL prints `*` (an extension: the
+                                             reference always has qualities)                                                               */
+    const uint8_t*  state_dev;            /* n: bit 0 aligned, bit 1 rc, bit 2 read 2 (Alignment::mate()), bit 3 paired (is_paired)        */
+    const uint32_t* pos_dev;              /* n: cigar_pos, where the alignment starts in the concatenated genome                           */
+    const int32_t*  score_dev;            /* n: AS                                                                                        */
+    const int32_t*  second_score_dev;     /* n, or NULL: XS; NVBIO_SCORE_MIN = no second alignment, no XS tag (:530-536)                   */
+    const uint32_t* ed_dev;               /* n: NM                                                                                        */
+    const uint8_t*  mapq_dev;             /* n: MAPQ                                                                                      */
+    const uint16_t* cigars_dev;           /* n x cigar_stride, as the traceback calls write them: backtracking order (:188-199)            */
+    const uint32_t* cigar_lens_dev;       /* n; a length beyond cigar_stride (0xFFFFFFFF included) is a truncated CIGAR                    */
+    const uint8_t*  mds_dev;              /* n x mds_stride, as nvbio_finish_alignment writes them (:216-289), or NULL (MD:Z:*)            */
+    const uint32_t* mds_lens_dev;         /* n: the stream's bytes, its two length bytes included; bytes beyond mds_stride are not read   */
+    const uint32_t* mate_of_dev;          /* n: the record index of the mate (:437-457,482-519), or NULL: single-end                      */
+    uint32_t        cigar_stride;
+    uint32_t        mds_stride;
+} nvbio_sam_records;
+
+#define NVBIO_SAM_LENGTHS_ONLY 1u       /* nvbio_sam_record_offsets: stop before the scan; offsets_dev[i] = the bytes of record i, [n] = 0      */
+
+/* *status_dev bits of nvbio_sam_format */
+#define NVBIO_SAM_STATUS_CAPACITY 1u   /* a record would end past text_capacity: it was not written                                        */
+#define NVBIO_SAM_STATUS_OFFSETS  2u   /* offsets_dev is not what nvbio_sam_record_offsets gives for these records: the record was not written */
+#define NVBIO_SAM_STATUS_TOO_LONG 4u   /* a record is longer than the declared maxima allow: it was not written                            */
+
+/* the bytes of temp_dev nvbio_sam_record_offsets needs for n records (the scan's; rocPRIM) */
+nvbio_status nvbio_sam_format_temp_bytes(uint32_t n, uint64_t* bytes);
+
+/* generate_cigar_string, generate_md_string, process_one_alignment and output_alignment (output_sam.cpp:182-212,216-289,344-544,292-342)
+ * as far as they decide a record's LENGTH: offsets_dev[n + 1] = the exclusive uint64 scan of the records' bytes, offsets_dev[n] the total.
+ * A record the reference does not write -- an aligned read whose CIGAR was truncated or whose non-D lengths do not sum to the read's
+ * length (:474-480) -- takes no bytes.  flags: 0 or NVBIO_SAM_LENGTHS_ONLY (the lengths, not scanned: measurements, or a caller with a scan
+ * of its own).  No host synchronisation; n = 0 writes offsets_dev[0] = 0. */
+nvbio_status nvbio_sam_record_offsets(int device, const nvbio_sam_refs* refs, const nvbio_sam_records* records, uint32_t flags, uint64_t* offsets_dev,
+                                      void* temp_dev, uint64_t temp_bytes, void* stream);
+
+/* The same functions for the TEXT (output_sam.cpp:182-544; itoa :76-115; dna_to_char nvbio/basic/dna.h:27-34): record i goes to
+ * text_dev[offsets_dev[i], offsets_dev[i + 1]); text_dev must be 16-byte aligned.
+ *   not aligned (:419-427,:300-310)  QNAME 4 * 0 0 * * 0 0 SEQ QUAL; the reference's mapq_filter test is inverted and reduces, at its
+ *                                    default of -1, to "not aligned": no filter is offered
+ *   aligned                          FLAG = 64 | 128 (bit 2), 16 (rc); with a mate 1, 2 (the MATE is paired), 8 (the mate is not aligned), 32 (the mate
+ *                                    is rc); RNAME / POS from upper_bound( sequence_index, pos ) - 1; an alignment that ends past its sequence
+ *                                    gets 4 ORed in (:459-466) and is then written in the short form above with those flags (:300)
+ *   CIGAR                            elements from last to first; RNEXT PNEXT TLEN as :482-524 (a mate whose CIGAR was truncated counts as
+ *                                    spanning no reference symbols); tags NM AS [XS] XM XO XG MD in that order (:328-339)
+ *   MD, XM, XO, XG                   generate_md_string: merged match runs, a mismatch's symbol, ^ symbols 0 for a deletion, nothing for an
+ *                                    insertion; a stream of at most 2 bytes gives MD:Z:* and zero counts
+ * *n_skipped_dev (device) = the records that took no bytes.  Checked on the device, in the manner of nvbio_finish_reads: a record that
+ * would end past text_capacity, whose offsets are not its own, or that outgrows the declared maxima is not written at all and its
+ * NVBIO_SAM_STATUS_* bit is ORed into *status_dev (a device word the caller zeroed; never cleared here).  Nothing is written past
+ * min( text_capacity, offsets_dev[n] ). */
+nvbio_status nvbio_sam_format(int device, const nvbio_sam_refs* refs, const nvbio_sam_records* records, uint32_t flags, const uint64_t* offsets_dev,
+                              uint8_t* text_dev, uint64_t text_capacity, uint32_t* n_skipped_dev, uint32_t* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2118,8 +2118,124 @@ def batch_banded_myers_score(band, aln_type, batch, min_score=SCORE_MIN):
     return scores, sinks
 
 
+# ---- SAM output ------------------------------------------------------------------------------------------------------------------
+SAM_STATUS_CAPACITY, SAM_STATUS_OFFSETS, SAM_STATUS_TOO_LONG = 1, 2, 4
+SAM_LENGTHS_ONLY = 1                                                     # sam_record_offsets: the lengths, not scanned
+SAM_ALIGNED, SAM_RC, SAM_READ_2, SAM_PAIRED = 1, 2, 4, 8                # the bits of SamRecords.state
+
+
+class _SamRefs(ctypes.Structure):
+    _fields_ = [("n_seqs", ctypes.c_uint32), ("max_name_len", ctypes.c_uint32), ("sequence_index_dev", ctypes.c_void_p), ("names_dev", ctypes.c_void_p),
+                ("names_index_dev", ctypes.c_void_p)]
+
+
+class _SamRecords(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("n", "max_name_len", "max_read_len", "reads_reversed")] + \
+               [(n, ctypes.c_void_p) for n in ("names_dev", "name_index_dev", "reads4_dev", "read_index_dev", "quals_dev", "state_dev", "pos_dev",
+                                               "score_dev", "second_score_dev", "ed_dev", "mapq_dev", "cigars_dev", "cigar_lens_dev", "mds_dev",
+                                               "mds_lens_dev", "mate_of_dev")] + \
+               [("cigar_stride", ctypes.c_uint32), ("mds_stride", ctypes.c_uint32)]
+
+
+def _name_table(names, device):
+    """[bytes or str] -> (uint8 tensor of the names' bytes, int32 tensor of n + 1 offsets, the longest name's length)"""
+    torch = _torch()
+    names = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    index = np.zeros(len(names) + 1, dtype=np.int64)
+    index[1:] = np.cumsum([len(n) for n in names]) if names else 0
+    data = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8).copy()
+    return torch.from_numpy(data).to(device), torch.from_numpy(index.astype(np.int32)).to(device), max([len(n) for n in names] or [0])
+
+
+class SamRefs:
+    """nvbio_sam_refs: the reference sequences of the genome (io::ConstSequenceDataView / bnt): names ([bytes or str]) and sequence_index
+    (n_seqs + 1 starts in the concatenated genome, [0] = 0)"""
+
+    def __init__(self, names, sequence_index, device="cuda:0"):
+        self.device = device
+        self.names = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        self.sequence_index_host = np.asarray(sequence_index, dtype=np.int64)
+        assert len(self.sequence_index_host) == len(self.names) + 1
+        self.sequence_index = _dev_tensor(self.sequence_index_host.astype(np.uint32), _torch().int32, device)
+        self.names_data, self.names_index, self.max_name_len = _name_table(self.names, device)
+
+    def c_struct(self):
+        return _SamRefs(len(self.names), self.max_name_len, self.sequence_index.data_ptr(), self.names_data.data_ptr(), self.names_index.data_ptr())
+
+
+class SamRecords:
+    """nvbio_sam_records over device tensors (numpy arrays are uploaded): what a SAM record is printed from.
+    names: [bytes or str] * n, or a (bytes tensor, offsets tensor, longest) triple already on the device; reads4 / read_index / quals: the STORED
+    reads; state: uint8 (SAM_ALIGNED | SAM_RC | SAM_READ_2 | SAM_PAIRED); pos: where the alignment starts in the concatenated genome;
+    cigars [n, cigar_stride] / cigar_lens as a traceback writes them; mds [n, mds_stride] / mds_lens as finish_alignment writes them;
+    mate_of: the record index of each record's mate, or None (single-end)."""
+
+    def __init__(self, names, reads4, read_index, max_read_len, state, pos, score, ed, mapq, cigars, cigar_lens, quals=None, second_score=None,
+                 mds=None, mds_lens=None, mate_of=None, reads_reversed=True, device="cuda:0"):
+        torch = _torch()
+        self.device = device
+        self.names_data, self.name_index, self.max_name_len = names if isinstance(names, tuple) else _name_table(names, device)
+        self.n = int(self.name_index.numel()) - 1
+        self.max_read_len, self.reads_reversed = int(max_read_len), bool(reads_reversed)
+        t = lambda a, dtype: _dev_tensor(a, dtype, device)
+        self.reads4, self.read_index, self.quals = t(reads4, torch.int32), t(read_index, torch.int32), t(quals, torch.uint8)
+        self.state, self.pos, self.score, self.second_score = t(state, torch.uint8), t(pos, torch.int32), t(score, torch.int32), t(second_score, torch.int32)
+        self.ed, self.mapq = t(ed, torch.int32), t(mapq, torch.uint8)
+        self.cigars, self.cigar_lens = cigars.to(device).contiguous() if isinstance(cigars, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(cigars).view(np.int16)).to(device), t(cigar_lens, torch.int32)
+        assert self.cigars.dim() == 2 and self.cigars.element_size() == 2 and self.cigars.shape[0] == self.n
+        self.mds, self.mds_lens = t(mds, torch.uint8), t(mds_lens, torch.int32)
+        assert self.mds is None or (self.mds.dim() == 2 and self.mds.shape[0] == self.n and self.mds_lens is not None)
+        self.mate_of = t(mate_of, torch.int32)
+
+    def c_struct(self):
+        p = lambda x: None if x is None else x.data_ptr()
+        return _SamRecords(self.n, self.max_name_len, self.max_read_len, 1 if self.reads_reversed else 0, p(self.names_data), p(self.name_index),
+                           p(self.reads4), p(self.read_index), p(self.quals), p(self.state), p(self.pos), p(self.score), p(self.second_score), p(self.ed),
+                           p(self.mapq), p(self.cigars), p(self.cigar_lens), p(self.mds), p(self.mds_lens), p(self.mate_of), self.cigars.shape[1],
+                           0 if self.mds is None else self.mds.shape[1])
+
+
+def sam_record_offsets(refs, records, flags=0):
+    """nvbio_sam_record_offsets -> offsets int64 [n + 1] on the device: the exclusive scan of the records' bytes, [n] the total"""
+    torch = _torch()
+    dev = records.device
+    offsets = torch.empty(records.n + 1, dtype=torch.int64, device=dev)
+    tmp, nb = _temp_for(lib().nvbio_sam_format_temp_bytes, records.n, device=dev)
+    rs, cs = refs.c_struct(), records.c_struct()
+    _check(lib().nvbio_sam_record_offsets(FMIndex._dev_index(dev), ctypes.byref(rs), ctypes.byref(cs), flags, _ptr(offsets), _ptr(tmp), nb, _stream_ptr(dev)))
+    return offsets
+
+
+def sam_format(refs, records, offsets, text, flags=0):
+    """nvbio_sam_format into `text` (a uint8 device tensor) -> (n_skipped, status): one host synchronisation"""
+    torch = _torch()
+    dev = records.device
+    words = torch.zeros(2, dtype=torch.int32, device=dev)                  # n_skipped | status
+    rs, cs = refs.c_struct(), records.c_struct()
+    _check(lib().nvbio_sam_format(FMIndex._dev_index(dev), ctypes.byref(rs), ctypes.byref(cs), flags, _ptr(offsets), _ptr(text), text.numel(),
+                                  ctypes.c_void_p(words.data_ptr()), ctypes.c_void_p(words.data_ptr() + 4), _stream_ptr(dev)))
+    n_skipped, status = (int(v) for v in words.cpu().numpy())
+    return n_skipped, status
+
+
+def sam_records(refs, records, flags=0):
+    """The SAM text of a batch of records (io::SamOutput, output_sam.cpp:182-544), formatted on the device: offsets, one read of the
+    total, the text -> (text uint8 tensor [offsets[n]], offsets int64 tensor [n + 1], n_skipped); record i is text[offsets[i] :
+    offsets[i + 1]], empty for a record that is skipped (a truncated or inconsistent CIGAR)"""
+    torch = _torch()
+    offsets = sam_record_offsets(refs, records, flags)
+    total = int(offsets[-1].item())
+    text = torch.empty(total, dtype=torch.uint8, device=records.device)
+    n_skipped, status = sam_format(refs, records, offsets, text, flags)
+    if status:
+        raise NvbioError(1, "nvbio_sam_format: status %d (NVBIO_SAM_STATUS_*)" % status)
+    return text, offsets, n_skipped
+
+
 # ---- the mirrors of the headers' structs: C name -> class (abi.bind types a pointer to one as POINTER(mirror); pipeline.py adds its own) -------
 _MIRRORS = {
+    "nvbio_sam_refs": _SamRefs, "nvbio_sam_records": _SamRecords,
     "nvbio_fm_index_view": _View, "nvbio_fm_build_options": _BuildOptions, "nvbio_string_set": _StringSet, "nvbio_rank_dictionary": _RankDict,
     "nvbio_mem_params": _MemParams, "nvbio_qgram_index_view": _QGramView, "nvbio_qgroup_index_view": _QGroupView,
     "nvbio_sufsort_stats": _SufsortStats, "nvbio_hit_queues": _HitQueues, "nvbio_seed_hits_params": _SeedHitsParams,

@@ -439,13 +439,14 @@ def seed_and_extend(fmi, genome2, genome_len, reads, params, timers=None, return
     return best_score, best_pos, best_rc, int(n_cand)
 
 
-def traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, cigar_stride=32, timers=None, text_planes=None):
+def traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, cigar_stride=32, timers=None, text_planes=None, return_batch=False):
     """nvBowtie's banded_traceback_best (traceback_inl.h:191-247) over ALL reads of the batch, job r = read r, the batch built on the
     device from the per-read best keys (extras["best_keys"] of seed_and_extend) and best_wb: no compaction, no host round trip.
     The scoring pass's score and sink are handed over (end-to-end; a LOCAL alignment is re-scored by the traceback).  Returns
     (scores [R], align_pos [R] int64 = text position where the alignment starts, sources, sinks, cigars [R, cigar_stride], cigar_lens
     [R]); a read that did not align has cigar_len 0 and sink (-1, -1).  text_planes: genome2's bit planes (AlignmentBatch; what
-    fmi.text_planes_of(genome2, genome_len) gives, as seed_and_extend takes them), or None."""
+    fmi.text_planes_of(genome2, genome_len) gives, as seed_and_extend takes them), or None.  return_batch: the AlignmentBatch that was
+    traced comes back as a seventh value (what finish_alignment takes)."""
     import torch
     from . import BatchedBandedAlignmentTraceback, traceback_best_batch
     dev = best_keys.device
@@ -476,7 +477,63 @@ def traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, c
     pos = (wb.to(torch.int64) & 0xFFFFFFFF) + (src[:, 0].to(torch.int64) & 0xFFFFFFFF)
     if ev is not None:
         ev.record()
+    if return_batch:
+        return sc, pos, src, snk, cig, ln, batch
     return sc, pos, src, snk, cig, ln
+
+
+def sam_header(refs, lengths=None, pg_id="nvBowtie", pg_name="nvBowtie", pg_version="0.5.1"):
+    """SamOutput::output_header (nvbio/io/output/output_sam.cpp:155-178) -> bytes: @HD VN:1.3, @PG with the reference's nvBowtie /
+    nvBowtie / 0.5.1 unless told otherwise, one @SQ SN LN per sequence.  refs: a SamRefs, or the sequence names with `lengths`."""
+    if lengths is None:
+        names, lengths = refs.names, np.diff(refs.sequence_index_host)
+    else:
+        names = refs
+    text = lambda n: n.decode("latin-1") if isinstance(n, bytes) else str(n)
+    lines = ["@HD\tVN:1.3", "@PG\tID:%s\tPN:%s\tVN:%s" % (pg_id, pg_name, pg_version)]
+    lines += ["@SQ\tSN:%s\tLN:%d" % (text(n), int(l)) for n, l in zip(names, lengths)]
+    return ("\n".join(lines) + "\n").encode("latin-1")
+
+
+def write_sam(file, header, text):
+    """header (bytes, sam_header) and the records' text (the uint8 tensor of sam_records / align_to_sam, or bytes) to `file`: a path or
+    a binary file object.  The text crosses to the host in one copy and is written in one piece."""
+    body = text if isinstance(text, (bytes, bytearray)) else text.cpu().numpy().tobytes()
+    if hasattr(file, "write"):
+        file.write(header)
+        file.write(body)
+        return
+    with open(file, "wb") as f:
+        f.write(header)
+        f.write(body)
+
+
+def align_to_sam(fmi, genome2, genome_len, reads, params, names, refs, cigar_stride=32, mds_stride=64):
+    """Reads in, SAM records out, single-end: seed_and_extend -> traceback_best_all -> finish_alignment -> sam_records, every array
+    handed from step to step on the device; MAPQ and the second score (XS) are seed_and_extend's own (params.mapq is switched on for
+    the call).  names: the reads' QNAMEs; refs: the SamRefs of the genome.  reads are stored forward, as seed_and_extend takes them.
+    Returns (text uint8 tensor, offsets int64 tensor [R + 1], n_skipped, records): records is the SamRecords the text was printed from."""
+    import copy
+    import torch
+    from . import SAM_ALIGNED, SAM_RC, SamRecords, finish_alignment, sam_records
+    if not params.mapq:
+        params = copy.copy(params)
+        params.mapq = True
+    dev = fmi.device
+    R = reads.n
+    ex = {}
+    _, _, best_rc, _, best_wb, _ = seed_and_extend(fmi, genome2, genome_len, reads, params, return_windows=True, extras=ex)
+    best_keys = ex.get("best_keys")
+    if best_keys is None:
+        best_keys = torch.zeros((R,), dtype=torch.int64, device=dev)
+    sc, pos, src, _, cig, ln, batch = traceback_best_all(genome2, genome_len, reads, params, best_keys, best_wb, cigar_stride=cigar_stride, return_batch=True)
+    ed, mds, mds_lens = finish_alignment(batch, src, cig, ln, mds_stride)
+    aligned = ln != 0
+    state = aligned.to(torch.uint8) * SAM_ALIGNED | (aligned & (best_rc != 0)).to(torch.uint8) * SAM_RC
+    records = SamRecords(names, reads.reads4, batch.read_offsets, reads.read_len, state, pos.to(torch.int32), sc, ed, ex["mapq"], cig, ln, quals=reads.quals,
+                         second_score=ex["second_score"], mds=mds, mds_lens=mds_lens, reads_reversed=False, device=dev)
+    text, offsets, n_skipped = sam_records(refs, records)
+    return text, offsets, n_skipped, records
 
 
 def traceback_best(genome2, genome_len, reads, params, best_score, best_rc, best_wb, cigar_stride=32, timers=None,
