@@ -1,5 +1,5 @@
-// bitplanes.h -- bit planes of packed reads and text windows for the ungapped shortcuts (gotoh_banded.hip, gotoh_full.hip,
-// gotoh_traceback.hip): bit i of (lo, hi, n) = low bit, high bit, "is N" of pattern row i; bit k of (tlo, thi) = the two
+// bitplanes.h -- bit planes of packed reads and text windows for the ungapped shortcuts (band31_ungapped_inl.h, band31_chances.hip,
+// gotoh_full.hip, gotoh_traceback.hip): bit i of (lo, hi, n) = low bit, high bit, "is N" of pattern row i; bit k of (tlo, thi) = the two
 // bits of window symbol k.  Built a packed word at a time: bit-reverse the big-endian word so that symbol 0 sits lowest,
 // squeeze every BITS-th bit together (3-4 shift/mask steps), drop the 8 / 16 plane bits at their storage offset, then
 // shift the planes so that bit 0 is row 0 (reversed reads: mirror first).  Every word is loaded unconditionally (index
@@ -26,24 +26,14 @@ __device__ __forceinline__ void load_read_words(const void* reads, const uint32_
     for (int j = 0; j < ReadWords<RBITS>::N; ++j) { const uint32_t widx = rw0 + (uint32_t)j; out.w[j] = rwords[widx < rw_last ? widx : rw_last]; }
 }
 
-// T = number of window symbols that will be looked at (<= 192 + 15 - offset)
-template <typename W>
-__device__ __forceinline__ void load_text_words13(const void* text, const uint32_t tb, const uint32_t T, W& out)
+// T = number of window symbols that will be looked at (<= 16 WORDS - 15: 13 words hold 192 + 15 - offset, 14 words 209)
+template <int WORDS, typename W>
+__device__ __forceinline__ void load_text_words(const void* text, const uint32_t tb, const uint32_t T, W& out)
 {
     const uint32_t* __restrict__ twords = (const uint32_t*)text;
     const uint32_t tw0 = (tb & ~15u) >> 4, tw_last = (tb + T - 1u) >> 4;
     #pragma unroll
-    for (int j = 0; j < 13; ++j) { const uint32_t widx = tw0 + (uint32_t)j; out.w[j] = twords[widx < tw_last ? widx : tw_last]; }
-}
-
-// T <= 224 - 15 window symbols
-template <typename W>
-__device__ __forceinline__ void load_text_words14(const void* text, const uint32_t tb, const uint32_t T, W& out)
-{
-    const uint32_t* __restrict__ twords = (const uint32_t*)text;
-    const uint32_t tw0 = (tb & ~15u) >> 4, tw_last = (tb + T - 1u) >> 4;
-    #pragma unroll
-    for (int j = 0; j < 14; ++j) { const uint32_t widx = tw0 + (uint32_t)j; out.w[j] = twords[widx < tw_last ? widx : tw_last]; }
+    for (int j = 0; j < WORDS; ++j) { const uint32_t widx = tw0 + (uint32_t)j; out.w[j] = twords[widx < tw_last ? widx : tw_last]; }
 }
 
 __device__ __forceinline__ void shr192(uint64_t (&v)[3], const uint32_t sh)
@@ -121,14 +111,29 @@ __device__ __forceinline__ void read_planes192(const ReadWords<RBITS>& rw, const
     }
 }
 
-// 208 plane bits (13 packed words), shifted so that bit 0 = window symbol 0; the top word holds the remainder
-template <typename W>
-__device__ __forceinline__ void text_planes208(const W& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
+// rows 64 k .. 64 k + 63 of a read's planes (read_planes192; M rows in all) as 32-bit words 2 k, 2 k + 1: bit j of word w of (pl, ph, pn, pm)
+// = row 32 w + j (its symbol's low / high bit, N, a row of the read at all; pn holds no bit past the read's end).  (One k per call: PlaneWords::set
+// fills its text words between them, and with all three k in front of those the gap chance's kernels compile to other code.)
+__device__ __forceinline__ void pattern_plane_words(const int k, const uint64_t (&rlo)[3], const uint64_t (&rhi)[3], const uint64_t (&rn)[3], const uint32_t M,
+                                                    uint32_t (&pl)[6], uint32_t (&ph)[6], uint32_t (&pn)[6], uint32_t (&pm)[6])
 {
+    const int32_t left = (int32_t)M - 64 * k;
+    const uint64_t mask = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
+    pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
+    ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
+    pm[2*k] = (uint32_t)mask;   pm[2*k+1] = (uint32_t)(mask >> 32);
+    pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
+}
+
+// 16 WORDS plane bits (13 packed words: 208, 14: 224), shifted so that bit 0 = window symbol 0; the top word holds the remainder
+template <int WORDS, typename W>
+__device__ __forceinline__ void text_planes_words(const W& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
+{
+    static_assert( WORDS <= 16, "four 64-bit plane words" );
     #pragma unroll
     for (int k = 0; k < 4; ++k) { tlo[k] = 0; thi[k] = 0; }
     #pragma unroll
-    for (int j = 0; j < 13; ++j)
+    for (int j = 0; j < WORDS; ++j)
     {
         const uint32_t w = __brev( tw.w[j] );
         const uint32_t lo = squeeze2( w >> 1 ), hi = squeeze2( w );
@@ -156,7 +161,7 @@ __device__ __forceinline__ void text_planes208(const W& tw, const uint32_t tb, u
 constexpr uint32_t TEXT_PLANE_LINE_BYTES = 128u;
 inline __host__ __device__ uint64_t text_plane_lines(const uint32_t n) { return (((uint64_t)n + 255u) >> 8) + 1u; }
 
-// The planes of the UNITS * 64 - 63 or more symbols from tb on, in the form text_planes208 / text_planes224 return: UNITS aligned 16-byte
+// The planes of the UNITS * 64 - 63 or more symbols from tb on, in the form text_planes_words returns: UNITS aligned 16-byte
 // loads from ONE line (load_text_units: issued with the read's loads), then a funnel shift by tb & 63 on 32-bit halves (text_planes_units).  Bits past the text's end are zero, bits past the window's end are
 // the text's next symbols (the caller masks them, as with the packed words).
 // Extent: the window begins in line tb >> 8 at unit u0 = (tb & 255) >> 6 <= 3 with shift s = tb & 63 <= 63, so E symbols end in unit
@@ -234,34 +239,6 @@ __device__ __forceinline__ bool locus_answers(const LocusWords& lw, const uint32
     const uint32_t lo = __builtin_amdgcn_alignbit( lw.lo1, lw.lo0, s ), hi = __builtin_amdgcn_alignbit( lw.hi1, lw.hi0, s );
     const uint32_t mask = len >= 32u ? 0xFFFFFFFFu : (1u << len) - 1u;
     return ((((lo ^ tlo) | (hi ^ thi)) & mask) == 0u) && ((lw.u >> s) & 1u);
-}
-
-// 224 plane bits (14 packed words), shifted so that bit 0 = window symbol 0
-template <typename W>
-__device__ __forceinline__ void text_planes224(const W& tw, const uint32_t tb, uint64_t (&tlo)[4], uint64_t (&thi)[4])
-{
-    #pragma unroll
-    for (int k = 0; k < 4; ++k) { tlo[k] = 0; thi[k] = 0; }
-    #pragma unroll
-    for (int j = 0; j < 14; ++j)
-    {
-        const uint32_t w = __brev( tw.w[j] );
-        const uint32_t lo = squeeze2( w >> 1 ), hi = squeeze2( w );
-        const int bitpos = j * 16;
-        tlo[bitpos >> 6] |= (uint64_t)lo << (bitpos & 63);
-        thi[bitpos >> 6] |= (uint64_t)hi << (bitpos & 63);
-    }
-    const uint32_t toff = tb & 15u;
-    if (toff)
-    {
-        #pragma unroll
-        for (int k = 0; k < 3; ++k)
-        {
-            tlo[k] = (tlo[k] >> toff) | (tlo[k + 1] << (64u - toff));
-            thi[k] = (thi[k] >> toff) | (thi[k + 1] << (64u - toff));
-        }
-        tlo[3] >>= toff; thi[3] >>= toff;
-    }
 }
 
 } // namespace nvbio_amd

@@ -655,7 +655,7 @@ extern "C" nvbio_status nvbio_fm_index_build(const uint32_t* text2_dev, uint32_t
 }
 
 // ---- the text as bit planes (bitplanes.h: the layout, load_text_units) ------------------------------------------------------------
-// one thread per 16-byte unit (64 symbols, 4 packed words): squeezed as text_planes208 does it per job, stored into the one or two lines
+// one thread per 16-byte unit (64 symbols, 4 packed words): squeezed as text_planes_words does it per job, stored into the one or two lines
 // that hold the unit -- line u / 4 at slot u % 4, and line u / 4 - 1 at slot u % 4 + 4.  Units past the text (the last lines' padding) and
 // bits at or beyond n are zero.
 __global__ void __launch_bounds__(256)

@@ -90,7 +90,7 @@ nvbio_status banded15_full_ties_traceback(const BatchDev& b, const SchemeDev& sc
                                           const uint32_t* job_list, const uint32_t* job_count, uint32_t* dirs, const uint64_t dirs_bytes,
                                           int32_t* scores, uint2* sources, uint2* sinks, uint16_t* cigars, const uint32_t stride, uint32_t* lens,
                                           hipStream_t s);                   // gotoh_traceback.hip
-bool banded31_packed_ok(const SchemeDev& sc, const uint32_t max_read_len);  // gotoh_banded.hip
+bool banded31_packed_ok(const SchemeDev& sc, const uint32_t max_read_len);  // band31_packed.hip
 nvbio_status banded31_packed_launch(const BatchDev& b, const SchemeDev& sc, const uint32_t read_bits, const uint32_t max_jobs, int32_t* scores, uint2* sinks,
                                     const uint32_t* job_list, const uint32_t* job_count, hipStream_t s);
 

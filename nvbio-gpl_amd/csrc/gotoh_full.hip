@@ -17,6 +17,7 @@
 #include "gotoh_common.h"
 #include <type_traits>
 #include "bitplanes.h"
+#include "pk_lanes.h"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>
 
@@ -354,7 +355,7 @@ full_gotoh_coop_kernel(const BatchDev b, const SchemeDev sc, const bool text_blo
 
 // ---------------------------------------------------------------------------------------------
 // Ungapped shortcut for end-to-end (SEMI_GLOBAL, match = 0) full-matrix scoring: the same argument as
-// ungapped_e2e31_kernel (gotoh_banded.hip) over ALL diagonals of the window.  An alignment with a gap scores
+// ungapped_e2e31_kernel (band31_first_pass.hip) over ALL diagonals of the window.  An alignment with a gap scores
 // at most G = max(gap opens) < 0; the ungapped alignments of the whole pattern are the diagonals d = 0..N-M,
 // U_d = -P * #{i : read[i] != text[i+d]}, ending in text column M+d.  If U* = max_d U_d > G, the optimum is
 // U*, reached in exactly the columns with U_d = U*, and both blockings report end columns in ascending order
@@ -384,15 +385,7 @@ __device__ __forceinline__ void full_planes(const BatchDev& b, const uint32_t fi
         read_planes192<RBITS>( rw, first, M, rev, comp, rlo, rhi, rn );
     }
     #pragma unroll
-    for (int k = 0; k < 3; ++k)
-    {
-        const int32_t left = (int32_t)M - 64 * k;
-        const uint64_t mask = left >= 64 ? ~0ull : (left > 0 ? ((1ull << left) - 1ull) : 0ull);
-        pl[2*k] = (uint32_t)rlo[k]; pl[2*k+1] = (uint32_t)(rlo[k] >> 32);
-        ph[2*k] = (uint32_t)rhi[k]; ph[2*k+1] = (uint32_t)(rhi[k] >> 32);
-        pm[2*k] = (uint32_t)mask;   pm[2*k+1] = (uint32_t)(mask >> 32);
-        pn[2*k] = (uint32_t)rn[k] & pm[2*k]; pn[2*k+1] = (uint32_t)(rn[k] >> 32) & pm[2*k+1];
-    }
+    for (int k = 0; k < 3; ++k) pattern_plane_words( k, rlo, rhi, rn, M, pl, ph, pn, pm );
 
     // ---- text planes: 544 bits, bit k = window symbol k (34 packed words cover 528 symbols at any offset) ----
     {
@@ -405,6 +398,8 @@ __device__ __forceinline__ void full_planes(const BatchDev& b, const uint32_t fi
         {
             const uint32_t widx = tw0 + (uint32_t)j;
             const uint32_t w = __brev( twords[widx < tw_last ? widx : tw_last] );
+            // (squeeze2( w >> 1 ), squeeze2( w ) of bitplanes.h with their steps written out side by side: called one after the other they compile
+            // to other code for the kernels of this file that take their planes from here)
             uint32_t lo = (w >> 1) & 0x55555555u, hi = w & 0x55555555u;
             lo = (lo | (lo >> 1)) & 0x33333333u; lo = (lo | (lo >> 2)) & 0x0F0F0F0Fu; lo = (lo | (lo >> 4)) & 0x00FF00FFu; lo = (lo | (lo >> 8)) & 0xFFFFu;
             hi = (hi | (hi >> 1)) & 0x33333333u; hi = (hi | (hi >> 2)) & 0x0F0F0F0Fu; hi = (hi | (hi >> 4)) & 0x00FF00FFu; hi = (hi | (hi >> 8)) & 0xFFFFu;
@@ -607,7 +602,7 @@ ungapped_full_e2e_kernel(const BatchDev b, const int32_t P, const int32_t G, con
 // The narrow route of end-to-end full-matrix scoring (pattern blocking, match = 0, one mismatch penalty P, gap of g symbols =
 // open + (g-1) ext < 0): most jobs the shortcut cannot settle hold ONE good alignment next to the best diagonal d* (an indel, or a few
 // mismatches more than the shortcut takes), and the matrix has 350 diagonals of which the DP would fill every cell.  Instead:
-//   1. the band-31 kernel (two jobs per lane, gotoh_banded.hip) scores the 31 diagonals around d*: S_b, a lower bound of the optimum S*
+//   1. the band-31 kernel (two jobs per lane, band31_packed.hip) scores the 31 diagonals around d*: S_b, a lower bound of the optimum S*
 //      (every path inside the band is a path of the matrix, with the same score and the same end);
 //   2. an alignment that scores >= S_b holds at most n = |S_b| / min(P, |open|) events (mismatches, gaps) and at most
 //      g = (|S_b| - |open|) / |ext| + 1 gap symbols: its rows that are neither split it into at most n + 1 runs of exact matches on one
@@ -755,12 +750,6 @@ narrow_check_kernel(const BatchDev b, const int32_t P, const int32_t gap_open, c
 // text symbol with the stripe's 8 pattern symbols comes from one XOR on 2-bit packed symbols per job.
 // Jobs of any other shape go through full_gotoh_kernel (a second job list).
 // ---------------------------------------------------------------------------------------------
-typedef short v2s __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2s pk(const int a, const int b) { v2s r; r.x = (short)a; r.y = (short)b; return r; }
-__device__ __forceinline__ v2s pk_max(const v2s a, const v2s b) { return __builtin_elementwise_max( a, b ); }
-__device__ __forceinline__ v2s pk_bits(const uint32_t u) { return __builtin_bit_cast( v2s, u ); }
-__device__ __forceinline__ uint32_t bits_pk(const v2s v) { return __builtin_bit_cast( uint32_t, v ); }
-
 template <int TYPE, int RBITS>
 __global__ void __launch_bounds__(128)
 full_gotoh_pb_pk_kernel(const BatchDev b, const SchemeDev sc, const uint32_t M, const uint32_t N, const uint32_t pair_begin, const uint32_t pairs,

@@ -313,14 +313,14 @@ ungapped_traceback_kernel(const BatchDev b, const SchemeDev sc, const int32_t* _
             ReadWords<RB> rw; TextUnits<4> tu;
             load_read_words<RB>( b.reads, first, M, rw );
             if (b.text_planes) load_text_units<4,0,3>( b.text_planes, tb, tu );              // (wave-uniform)
-            else               load_text_words13( b.text, tb, N < 192u ? N : 192u, tu );
+            else               load_text_words<13>( b.text, tb, N < 192u ? N : 192u, tu );
             read_planes192<RB>( rw, first, M, J.rev, J.comp, rlo, rhi, rn );
             if (b.text_planes)
             {
                 load_text_units<4,3,4>( b.text_planes, tb, tu );                             // (as the first scoring pass: 7 waves per SIMD)
                 text_planes_units<4>( tu, tb, tlo, thi );
             }
-            else text_planes208( tu, tb, tlo, thi );
+            else text_planes_words<13>( tu, tb, tlo, thi );
             uint32_t cnt = 0;
             #pragma unroll
             for (int w = 0; w < 3; ++w)

@@ -1,6 +1,6 @@
 """GPU parity at the numeric limits of band-31 scoring, and on reads far longer than the 161 rows the first pass holds.
 
-nvbio_banded_gotoh_score picks the arithmetic of band 31 on the host (packed_ok() and launch_pk_kernel(), csrc/gotoh_banded.hip), for 4- or
+nvbio_banded_gotoh_score picks the arithmetic of band 31 on the host (packed_ok() and launch_pk_kernel(), csrc/band31_packed.hip), for 4- or
 2-bit reads in a 2-bit text, from the batch's max_read_len = M and the scheme; step = the scheme's largest single penalty:
 
   binary16 lanes   SEMI_GLOBAL, match == 0, two-wave build, (M + 32) * step <= 2040 (and mm_max <= 400)

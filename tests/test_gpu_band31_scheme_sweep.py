@@ -1,5 +1,5 @@
 """GPU: the band-31 end-to-end shortcuts -- the ungapped first pass, the second, third and gap chance, the DP's narrow classes and their redo list
-(csrc/gotoh_banded.hip) -- over the space of the three scheme numbers their arguments rest on: P, the smallest mismatch penalty, and the gap's
+(csrc/band31_*.hip) -- over the space of the three scheme numbers their arguments rest on: P, the smallest mismatch penalty, and the gap's
 opening and extension terms go and ge.
 
 Every check is integer equality: scores and sinks against the oracle (the reference algorithm, band 31, SEMI_GLOBAL: orc.banded_gotoh_packed_batch,

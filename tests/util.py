@@ -366,7 +366,7 @@ RANGE_EDGES = (
 
 def band31_route(typ, sv, max_read_len):
     """which arithmetic nvbio_banded_gotoh_score runs band 31 in for 4- or 2-bit reads on a 2-bit text under default flags: 'f16', 'i16'
-    or 'i32' -- the host's rules (packed_ok() and the binary16 condition of launch_pk_kernel(), csrc/gotoh_banded.hip) restated"""
+    or 'i32' -- the host's rules (packed_ok() and the binary16 condition of launch_pk_kernel(), csrc/band31_packed.hip) restated"""
     match, mm_min, mm_max, pat_go, pat_ge, txt_go, txt_ge = sv
     M, lim, step = int(max_read_len), 4096, scheme_step(sv)
     packed = M > 0 and match >= 0 and 0 <= mm_min <= lim and 0 <= mm_max <= lim and -lim <= pat_go <= 0 and -lim <= pat_ge <= 0
@@ -506,7 +506,7 @@ def full_shapes(seed, M, N, n, dominant=2, of=3, min_text=0):
 
 
 def _band31_int16_ok(sv, M):
-    """packed_ok( SEMI_GLOBAL, ... ) of csrc/gotoh_banded.hip: what the narrow route asks of the band-31 kernel it borrows"""
+    """packed_ok( SEMI_GLOBAL, ... ) of csrc/band31_packed.hip: what the narrow route asks of the band-31 kernel it borrows"""
     match, lim = sv[0], 4096
     pen = (sv[1], sv[2], -sv[3], -sv[4], -sv[5], -sv[6])
     return M > 0 and match >= 0 and all(0 <= v <= lim for v in pen) and (M + 32) * max(max(pen), match) <= 8000
@@ -954,7 +954,7 @@ def full_route_rule(J, with_q, typ, sv, want, algo=0):
 # the band-31 end-to-end shortcuts over the scheme space (tests/test_e2e31_sweep_jobs.py, tests/test_gpu_band31_scheme_sweep.py,
 # tests/test_oracle_vs_reference.py::test_e2e31_scheme_sweep)
 # ---------------------------------------------------------------------------------------------
-BAND31, NARROW_HALF_A, NARROW_HALF_B = 31, 6, 8                      # the narrow classes' half-widths (csrc/gotoh_banded.hip)
+BAND31, NARROW_HALF_A, NARROW_HALF_B = 31, 6, 8                      # the narrow classes' half-widths (csrc/band31_jobs.h)
 ALN_NO_UNGAPPED_SCORE, ALN_NO_THIRD_CHANCE, ALN_PK_THREE_WAVES, ALN_NO_SECOND_CHANCE = 1, 2, 32, 128    # NVBIO_ALN_* of include/nvbio_amd.h
 ALN_NO_QUALITY_SHORTCUT, ALN_RAGGED_READS, ALN_NO_F16_DP, ALN_NO_GAP_CHANCE = 2048, 4096, 16384, 65536
 ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE, ALN_NO_NARROW_DP = 131072, 262144, 524288
@@ -1154,7 +1154,7 @@ def e2e31_counts(J, with_q_scheme=None):
 
 def e2e31_admitted(sv, has_quals, max_read_len, algo=0):
     """does nvbio_banded_gotoh_score send a SEMI_GLOBAL band-31 batch of 4- or 2-bit reads on a 2-bit text through the shortcuts at all --
-    packed_ok() and ungapped_ok() of csrc/gotoh_banded.hip as the code has them"""
+    packed_ok() of csrc/band31_packed.hip and ungapped_ok() of csrc/band31_stage.hip as the code has them"""
     match, mm_min, mm_max, pat_go, pat_ge, txt_go, txt_ge = (int(v) for v in sv)
     if algo & ALN_NO_UNGAPPED_SCORE or not _band31_int16_ok(sv, int(max_read_len)):
         return False
@@ -1174,7 +1174,7 @@ def e2e31_classes_on(sv, has_quals, max_read_len, algo=0):
 
 
 def e2e31_first_pass(sv, has_quals, M, N, counts, weights=None, max_read_len=None, algo=0):
-    """The first pass's rule AS THE CODE HAS IT (ungapped_e2e31_job, MODE 0, of csrc/gotoh_banded.hip), restated in numpy: this is a copy of
+    """The first pass's rule AS THE CODE HAS IT (ungapped_e2e31_job, MODE 0, of csrc/band31_ungapped_inl.h), restated in numpy: this is a copy of
     the conditions, not a derivation of what they should be -- the tests hold the library's results to the oracle and its routes to this.
     From each job's read length M, window length N and 31 diagonal mismatch counts (e2e31_counts(): -1 off the window; under a quality ramp
     also `weights`, the diagonals' penalty sums) -> (flag, class) per job:
