@@ -1649,6 +1649,103 @@ nvbio_status nvbio_sam_record_offsets(int device, const nvbio_sam_refs* refs, co
 nvbio_status nvbio_sam_format(int device, const nvbio_sam_refs* refs, const nvbio_sam_records* records, uint32_t flags, const uint64_t* offsets_dev,
                               uint8_t* text_dev, uint64_t text_capacity, uint32_t* n_skipped_dev, uint32_t* status_dev, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * FASTQ input: the bytes of a FASTQ file parsed on the device into an io::SequenceData<DNA_N>-shaped batch -- 4-bit big-endian words, a
+ * sequence index, one quality byte per symbol, names with a name index: the arrays nvbio_sam_records and the read batches take.  The
+ * reference parses on the host one byte at a time (SequenceDataFile_FASTQ_parser::nextChunk, nvbio/io/sequence/sequence_fastq.cpp:39-203)
+ * and encodes one read at a time (SequenceDataEncoder::push_back, sequence_encoder.cpp:304-368).
+ *
+ * The grammar is the reference's: ONE sequential machine over bytes.
+ *   state  | '\n'   ' '    '@'    '+'    NUL    0x21..0x7E  other | what the bytes that stay are
+ *   GAP    | GAP    GAP    NAME   error  error  error       error | between records; error = the MARKER error, the machine stops (:70-75)
+ *   NAME   | SEQ    .      .      .      SEQ    .           .     | the name, '@' '+' ' ' '\r' included (:79-88)
+ *   SEQ    | .      .      .      PLUS   PLUS   .           .     | 0x21..0x7E are symbols ('@' too), the rest is dropped: many lines (:103-117)
+ *   PLUS   | QUAL   .      .      .      QUAL   .           .     | skipped (:129)
+ *   QUAL   | GAP    .      .      .      GAP    .           .     | qualities, '\r' and ' ' included; exactly one line; the record ends (:144-145)
+ * The read's length is the QUALITY line's (:143), then min( length, truncate_len ) (sequence_encoder.cpp:315).  Symbols: A a 0, C c 1,
+ * G g 2, T t 3, '-' 5, all else 4 (nst_nt4, :30-47); complement bp < 4 ? 3 - bp : 4.  Qualities in uint8 arithmetic: PHRED q, PHRED33
+ * q - 33, PHRED64 q - 64, SOLEXA the table (:57-85: 0 1 1 1 1 1 1 2 2 3 3 4 4 5 5 6 7 8 9 10 for q < 20, q - 10 from there).  The
+ * strand operator applies to the read after truncation.  End of text in a state other than GAP is the reference's "incomplete read".
+ * Departures:
+ *   1. qualities are reversed exactly when the symbols are (sequence_string::quality tests the wrong constant, :139: under REVERSE_OP
+ *      the reference reverses symbols only, under COMPLEMENT_OP qualities only; every consumer assumes one order)
+ *   2. a quality line longer than the kept sequence: the symbols beyond it are 4 (the reference reads stale bytes of the record before)
+ *      and NVBIO_FASTQ_STATUS_LENGTH is raised; a shorter one cuts the sequence, as in the reference, and raises the same bit
+ *   3. a record with an empty quality line is delivered with length 0 and NVBIO_FASTQ_STATUS_EMPTY (the reference asserts)
+ *   4. names are stored without a terminating NUL, with n + 1 offsets, as nvbio_sam_records takes them
+ *   5. one strand operator per call (the reference can interleave 2 to 4 copies of each read)
+ * Not offered: gzip, FASTA / TXT / SAM / BAM, a CRLF mode (a CRLF file parses as in the reference: into LENGTH errors), max_bps.
+ *
+ * The machine parallelises as a scan: a byte is a function over the six states (the five and the absorbing error), functions compose
+ * associatively.  nvbio_fastq_scan composes 16 bytes per lane, lanes across the wave, waves through LDS, 4096-byte tiles through an
+ * array that one workgroup scans -- separate launches, no workgroup waits on another -- then numbers the records' '@' by the record
+ * ends before them, and one wave per record finds its fields with ballots.  nvbio_fastq_encode writes the arrays, one wave per record.
+ * ------------------------------------------------------------------------------------------- */
+#define NVBIO_FASTQ_PHRED   0u
+#define NVBIO_FASTQ_PHRED33 1u
+#define NVBIO_FASTQ_PHRED64 2u
+#define NVBIO_FASTQ_SOLEXA  3u
+
+#define NVBIO_FASTQ_NO_OP                 0u
+#define NVBIO_FASTQ_REVERSE_OP            1u
+#define NVBIO_FASTQ_COMPLEMENT_OP         2u
+#define NVBIO_FASTQ_REVERSE_COMPLEMENT_OP 3u
+
+/* nvbio_fastq_summary.status / *status_dev */
+#define NVBIO_FASTQ_STATUS_MARKER     1u   /* a byte other than '\n' ' ' '@' between records: error_offset, error_char; nothing from there on is read */
+#define NVBIO_FASTQ_STATUS_INCOMPLETE 2u   /* the text ends inside a record: consumed_bytes = the offset of its '@'                        */
+#define NVBIO_FASTQ_STATUS_LENGTH     4u   /* a delivered record's quality line and kept sequence differ in length (departure 2)           */
+#define NVBIO_FASTQ_STATUS_EMPTY      8u   /* a delivered record's quality line is empty (departure 3)                                     */
+#define NVBIO_FASTQ_STATUS_CAPACITY  16u   /* nvbio_fastq_encode: a record did not fit reads4 / quals / names and was not written          */
+
+typedef struct
+{
+    uint32_t quality_encoding;   /* NVBIO_FASTQ_PHRED .. NVBIO_FASTQ_SOLEXA (nvBowtie: PHRED33)                                            */
+    uint32_t strand_op;          /* NVBIO_FASTQ_NO_OP .. NVBIO_FASTQ_REVERSE_COMPLEMENT_OP (nvBowtie: REVERSE_OP)                          */
+    uint32_t truncate_len;       /* reads are cut to this many symbols; 0xFFFFFFFF: never                                                  */
+    uint32_t max_records;        /* the machine stops after this many records; 0xFFFFFFFF: never                                           */
+} nvbio_fastq_params;
+
+/* what the caller copies back once.  consumed_bytes: text_bytes when the text ends between records; the offset of the unfinished
+ * record's '@' (INCOMPLETE); the offset behind the '\n' or NUL that ended record max_records - 1 when max_records stopped the machine
+ * (0 for max_records = 0; nothing behind that point is looked at, an error there is not reported); error_offset (MARKER).  A caller
+ * that reads a file in chunks puts text[consumed_bytes, text_bytes) in front of the next chunk. */
+typedef struct
+{
+    uint32_t n_records;
+    uint32_t consumed_bytes;
+    uint32_t n_symbols;          /* read_index[n_records]                                                                                  */
+    uint32_t n_name_bytes;       /* name_index[n_records]                                                                                  */
+    uint32_t max_read_len;       /* after truncation                                                                                       */
+    uint32_t max_name_len;
+    uint32_t status;             /* NVBIO_FASTQ_STATUS_*                                                                                   */
+    uint32_t error_offset;       /* MARKER: the offending byte's offset and value; else 0xFFFFFFFF and 0                                   */
+    uint32_t error_char;
+    uint32_t first_bad_record;   /* the first record that raised LENGTH or EMPTY; else 0xFFFFFFFF                                          */
+} nvbio_fastq_summary;
+
+/* the bytes of temp_dev both calls need for a text of text_bytes and this max_records: 20 bytes for each of min( max_records,
+ * text_bytes / 5 ) records (a record takes 5 bytes at least), 8 for each 4096-byte tile, the record scan's (rocPRIM) */
+nvbio_status nvbio_fastq_temp_bytes(uint64_t text_bytes, uint32_t max_records, uint64_t* bytes);
+
+/* The machine over text_dev[0, text_bytes) (16-byte aligned; text_bytes >= 2^32 is NVBIO_ERR_UNSUPPORTED: feed chunks), the records'
+ * offsets and lengths, and *summary_dev.  Everything else stays in temp_dev for nvbio_fastq_encode.  No host synchronisation. */
+nvbio_status nvbio_fastq_scan(int device, const uint8_t* text_dev, uint64_t text_bytes, const nvbio_fastq_params* params, nvbio_fastq_summary* summary_dev,
+                              void* temp_dev, uint64_t temp_bytes, void* stream);
+
+/* The arrays of the records nvbio_fastq_scan found, from what it left in temp_dev (same text, text_bytes, params, temp_dev):
+ *   reads4_dev      ceil( n_symbols / 8 ) words, symbol i in bits 28 - 4 * (i % 8) of word i / 8; the unused bits of the last word are 0
+ *   quals_dev       n_symbols bytes, converted, in the symbols' order; its capacity is that of reads4_dev: 8 * reads4_capacity_words
+ *   names_dev       n_name_bytes bytes
+ *   read_index_dev, name_index_dev    n_records + 1 offsets each; sized for min( max_records, text_bytes / 5 ) + 1 if the summary was not read
+ * A record that would end past a capacity is not written (its index entries are) and NVBIO_FASTQ_STATUS_CAPACITY is ORed into
+ * *status_dev (a device word, &summary_dev->status for instance; never cleared here).  Nothing is written past a capacity; upper bounds
+ * that fit every record whose lines agree: text_bytes / 2 symbols, text_bytes name bytes (a LENGTH record's quality line may be longer:
+ * text_bytes symbols fit always).  No host synchronisation. */
+nvbio_status nvbio_fastq_encode(int device, const uint8_t* text_dev, uint64_t text_bytes, const nvbio_fastq_params* params, const void* temp_dev,
+                                uint64_t temp_bytes, uint32_t* reads4_dev, uint64_t reads4_capacity_words, uint32_t* read_index_dev, uint8_t* quals_dev,
+                                uint8_t* names_dev, uint64_t names_capacity, uint32_t* name_index_dev, uint32_t* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

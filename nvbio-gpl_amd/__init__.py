@@ -2233,9 +2233,147 @@ def sam_records(refs, records, flags=0):
     return text, offsets, n_skipped
 
 
+# ---- FASTQ input -----------------------------------------------------------------------------------------------------------------
+FASTQ_PHRED, FASTQ_PHRED33, FASTQ_PHRED64, FASTQ_SOLEXA = 0, 1, 2, 3
+FASTQ_NO_OP, FASTQ_REVERSE_OP, FASTQ_COMPLEMENT_OP, FASTQ_REVERSE_COMPLEMENT_OP = 0, 1, 2, 3
+FASTQ_STATUS_MARKER, FASTQ_STATUS_INCOMPLETE, FASTQ_STATUS_LENGTH, FASTQ_STATUS_EMPTY, FASTQ_STATUS_CAPACITY = 1, 2, 4, 8, 16
+FASTQ_UNLIMITED = 0xFFFFFFFF
+FASTQ_SUMMARY_FIELDS = ("n_records", "consumed_bytes", "n_symbols", "n_name_bytes", "max_read_len", "max_name_len", "status", "error_offset",
+                        "error_char", "first_bad_record")
+
+
+class _FastqParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("quality_encoding", "strand_op", "truncate_len", "max_records")]
+
+
+class _FastqSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in FASTQ_SUMMARY_FIELDS]
+
+
+def _fastq_text(text, device):
+    """bytes, numpy array or uint8 tensor -> a uint8 device tensor whose first byte is 16-byte aligned"""
+    torch = _torch()
+    if isinstance(text, torch.Tensor):
+        t = text.to(device).contiguous().view(torch.uint8).reshape(-1)
+        return t.clone() if t.numel() and t.data_ptr() & 15 else t
+    a = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text).view(np.uint8).reshape(-1)
+    return torch.from_numpy(a.copy()).to(device)
+
+
+def fastq_scan(text, params, temp=None, text_bytes=None):
+    """nvbio_fastq_scan over a uint8 device tensor -> (summary: int32 tensor [10] on the device, FASTQ_SUMMARY_FIELDS; temp: what
+    fastq_encode reads).  params: a _FastqParams.  text_bytes: the length to declare, when it is not the tensor's.  No synchronisation."""
+    torch = _torch()
+    dev = text.device
+    nb = text.numel() if text_bytes is None else int(text_bytes)
+    if temp is None:
+        temp, _ = _temp_for(lib().nvbio_fastq_temp_bytes, nb, params.max_records, device=dev)
+    summary = torch.empty(len(FASTQ_SUMMARY_FIELDS), dtype=torch.int32, device=dev)
+    _check(lib().nvbio_fastq_scan(FMIndex._dev_index(dev), _ptr(text) if text.numel() else None, nb, ctypes.byref(params),
+                                  ctypes.cast(summary.data_ptr(), ctypes.POINTER(_FastqSummary)), _ptr(temp), temp.numel(), _stream_ptr(dev)))
+    return summary, temp
+
+
+def fastq_encode(text, params, temp, reads4, read_index, quals, names, name_index, status, reads4_capacity_words=None, names_capacity=None,
+                 text_bytes=None):
+    """nvbio_fastq_encode into caller tensors (reads4 int32 words, quals / names uint8, the indices int32, status: an int32 device word);
+    the capacities default to the tensors' sizes.  No synchronisation."""
+    dev = text.device
+    nb = text.numel() if text_bytes is None else int(text_bytes)
+    words = reads4.numel() if reads4_capacity_words is None else int(reads4_capacity_words)
+    name_cap = names.numel() if names_capacity is None else int(names_capacity)
+    p = lambda t: _ptr(t) if t is not None and t.numel() else None
+    _check(lib().nvbio_fastq_encode(FMIndex._dev_index(dev), p(text), nb, ctypes.byref(params), _ptr(temp), temp.numel(), p(reads4), words,
+                                    _ptr(read_index), p(quals), p(names), name_cap, _ptr(name_index), _ptr(status), _stream_ptr(dev)))
+
+
+def fastq_summary(summary):
+    """the summary tensor of fastq_scan -> dict (one copy to the host)"""
+    return dict(zip(FASTQ_SUMMARY_FIELDS, (int(v) for v in summary.cpu().numpy().view(np.uint32))))
+
+
+class FastqBatch:
+    """The reads of one parsed FASTQ text in HBM, io::SequenceData<DNA_N>-shaped: reads4 (int32 words, 4-bit big-endian), read_index
+    (int32 [n + 1], the sequence index), quals (uint8, one per symbol, converted to Phred), names_data (uint8) with name_index (int32
+    [n + 1]); summary: the nvbio_fastq_summary as a dict, its fields also attributes (n_records, consumed_bytes, status, ...)."""
+
+    def __init__(self, reads4, read_index, quals, names_data, name_index, summary, device):
+        self.reads4, self.read_index, self.quals, self.names_data, self.name_index = reads4, read_index, quals, names_data, name_index
+        self.summary, self.device = summary, device
+        self.n = summary["n_records"]
+
+    def __getattr__(self, key):
+        if key != "summary" and key in self.summary:
+            return self.summary[key]
+        raise AttributeError(key)
+
+    @property
+    def names(self):
+        """the (names_data, name_index, max_name_len) triple SamRecords takes as `names`"""
+        return self.names_data, self.name_index, self.summary["max_name_len"]
+
+    def read_batch(self):
+        """a pipeline.ReadBatch over these arrays: offsets=None when every read has the same length, the int32 read_index otherwise
+        (one host synchronisation)"""
+        from .pipeline import ReadBatch
+        lens = self.read_index[1:] - self.read_index[:-1]
+        uniform = self.n == 0 or bool((lens == lens[0]).all().item())
+        return ReadBatch(self.reads4, self.n, self.summary["max_read_len"], quals=self.quals, offsets=None if uniform else self.read_index)
+
+
+def parse_fastq(text, quality_encoding=FASTQ_PHRED33, strand_op=FASTQ_NO_OP, truncate_len=FASTQ_UNLIMITED, max_records=FASTQ_UNLIMITED,
+                device="cuda:0"):
+    """The bytes of a FASTQ file (bytes, a numpy array or a uint8 device tensor, below 4 GiB) -> FastqBatch: SequenceDataFile_FASTQ_parser
+    ::nextChunk and SequenceDataEncoder::push_back (nvbio/io/sequence/sequence_fastq.cpp:39-203, sequence_encoder.cpp:304-368) on the
+    device -- the grammar and its departures are in include/nvbio_amd.h ("FASTQ input").  The summary is read once, the arrays are then
+    allocated to size.  The scan's temp takes 20 bytes per POSSIBLE record: min(max_records, len(text) / 5); a caller that knows how many
+    records a chunk can hold passes max_records.  Errors are reported, not raised: batch.status (FASTQ_STATUS_*), batch.consumed_bytes."""
+    torch = _torch()
+    t = _fastq_text(text, device)
+    params = _FastqParams(int(quality_encoding), int(strand_op), int(truncate_len), int(max_records))
+    summary_dev, temp = fastq_scan(t, params)
+    s = fastq_summary(summary_dev)
+    n = s["n_records"]
+    reads4 = torch.empty((s["n_symbols"] + 7) // 8, dtype=torch.int32, device=t.device)
+    quals = torch.empty(s["n_symbols"], dtype=torch.uint8, device=t.device)
+    names = torch.empty(s["n_name_bytes"], dtype=torch.uint8, device=t.device)
+    read_index = torch.empty(n + 1, dtype=torch.int32, device=t.device)
+    name_index = torch.empty(n + 1, dtype=torch.int32, device=t.device)
+    fastq_encode(t, params, temp, reads4, read_index, quals, names, name_index, summary_dev[6:7])
+    s["status"] = int(summary_dev[6].item()) & 0xFFFFFFFF
+    if s["status"] & FASTQ_STATUS_CAPACITY:
+        raise NvbioError(1, "nvbio_fastq_encode: a record did not fit arrays allocated from the summary")
+    return FastqBatch(reads4, read_index, quals, names, name_index, s, t.device)
+
+
+def read_fastq(path, chunk_bytes=64 << 20, **kw):
+    """A generator of FastqBatch over the file at `path`, read in chunks of chunk_bytes: the bytes a chunk's parse did not consume
+    (consumed_bytes: the record the chunk cuts) go in front of the next.  A chunk that holds no whole record grows until it does.  At the
+    end of the file an unfinished record is the reference's "incomplete read": NvbioError, as is a marker error anywhere.  kw: parse_fastq's."""
+    tail, eof, capped = b"", False, False
+    with open(path, "rb") as f:
+        while True:
+            data = b"" if eof or capped else f.read(chunk_bytes)                  # capped: whole records may be left in the tail; parse them first
+            eof = eof or (not capped and len(data) < chunk_bytes)
+            text = tail + data
+            if not text:
+                return
+            batch = parse_fastq(text, **kw)
+            if batch.status & FASTQ_STATUS_MARKER:
+                raise NvbioError(1, "%s: FASTQ parse error: byte %d where a record must begin with '@'" % (path, batch.error_char))
+            tail = text[batch.consumed_bytes:]
+            capped = batch.n > 0 and batch.n == kw.get("max_records", FASTQ_UNLIMITED) and len(tail) > 0
+            if batch.n:
+                yield batch
+            elif eof:
+                if batch.status & FASTQ_STATUS_INCOMPLETE:
+                    raise NvbioError(1, "%s: incomplete read at the end of the file" % path)
+                return
+
+
 # ---- the mirrors of the headers' structs: C name -> class (abi.bind types a pointer to one as POINTER(mirror); pipeline.py adds its own) -------
 _MIRRORS = {
-    "nvbio_sam_refs": _SamRefs, "nvbio_sam_records": _SamRecords,
+    "nvbio_sam_refs": _SamRefs, "nvbio_sam_records": _SamRecords, "nvbio_fastq_params": _FastqParams, "nvbio_fastq_summary": _FastqSummary,
     "nvbio_fm_index_view": _View, "nvbio_fm_build_options": _BuildOptions, "nvbio_string_set": _StringSet, "nvbio_rank_dictionary": _RankDict,
     "nvbio_mem_params": _MemParams, "nvbio_qgram_index_view": _QGramView, "nvbio_qgroup_index_view": _QGroupView,
     "nvbio_sufsort_stats": _SufsortStats, "nvbio_hit_queues": _HitQueues, "nvbio_seed_hits_params": _SeedHitsParams,

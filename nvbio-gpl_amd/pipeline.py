@@ -536,6 +536,18 @@ def align_to_sam(fmi, genome2, genome_len, reads, params, names, refs, cigar_str
     return text, offsets, n_skipped, records
 
 
+def fastq_to_sam(fmi, genome2, genome_len, fastq_text, params, refs, cigar_stride=32, mds_stride=64, **kw):
+    """FASTQ text in, SAM text out, with nothing but text crossing the bus: parse_fastq (the reads stored forward, NO_OP, as align_to_sam
+    takes them; kw: quality_encoding, truncate_len, max_records) then align_to_sam over the batch's own arrays and names -- a ragged
+    batch when the reads differ in length.  Returns align_to_sam's (text, offsets, n_skipped, records) and the FastqBatch, whose status
+    and consumed_bytes say how far the text was read."""
+    from . import FASTQ_NO_OP, NvbioError, parse_fastq
+    if kw.pop("strand_op", FASTQ_NO_OP) != FASTQ_NO_OP:
+        raise NvbioError(1, "fastq_to_sam stores the reads forward: strand_op must be FASTQ_NO_OP")
+    batch = parse_fastq(fastq_text, strand_op=FASTQ_NO_OP, device=fmi.device, **kw)
+    return align_to_sam(fmi, genome2, genome_len, batch.read_batch(), params, batch.names, refs, cigar_stride=cigar_stride, mds_stride=mds_stride) + (batch,)
+
+
 def traceback_best(genome2, genome_len, reads, params, best_score, best_rc, best_wb, cigar_stride=32, timers=None,
                    best_pos=None):
     """nvBowtie's banded_traceback_best (traceback_inl.h:191-247) for the pipeline's best alignment per read:
