@@ -718,7 +718,14 @@ nvbio_status nvbio_bwt(const uint32_t* text2_dev, uint32_t length, int device, u
 /* hit_to_diagonal (examples/fmmap/fmmap.cu:92-117) for uniformly enumerated seeds: for hit
  * (text_pos, seed_id), read = seed_id / seeds_per_read, seed offset p = (seed_id % seeds_per_read) *
  * seed_interval (on the reverse-complement strand p -> read_len - p - seed_len), diagonal = text_pos - p.
- * keys_dev[h] = read << 34 | strand << 33 | (diagonal + 1024): sortable, one per hit.               */
+ * keys_dev[h] = read << 34 | strand << 33 | (diagonal + 1024): sortable, one per hit.
+ * The field of the diagonal holds 33 bits and a bias of 1024, so a seed may lie at most NVBIO_MAX_SEED_OFFSET = 1024 symbols into its read:
+ * a hit of a later seed within (offset - 1024) symbols of the genome start would leave the field below zero and spill over the strand
+ * bit and the read id.  Every call that forms diagonal keys -- this one, nvbio_fm_filter_locate_diagonals, nvbio_fm_residual_diagonals,
+ * nvbio_fm_match_seed_diagonals[_both[_tiled]] -- therefore refuses read_len - seed_len > NVBIO_MAX_SEED_OFFSET with NVBIO_ERR_INVALID.
+ * Their ragged forms (read_offsets_dev on the device) cannot look at the lengths: there the limit is the CALLER's to keep, for the longest
+ * read of the batch (pipeline.seed_and_extend checks it on the host).                                                              */
+#define NVBIO_MAX_SEED_OFFSET 1024u
 nvbio_status nvbio_hits_to_diagonals(int device, const nvbio_uint2* hits_dev, uint64_t n_hits, uint32_t seeds_per_read,
                                      uint32_t seed_interval, uint32_t seed_len, uint32_t read_len, uint32_t strand,
                                      uint64_t* keys_dev, void* stream);
@@ -1252,7 +1259,12 @@ enum { NVBIO_READ_REVERSE = 1, NVBIO_READ_COMPLEMENT = 2 };
 nvbio_status nvbio_best_candidate_reduce(int device, const uint64_t* keys_dev, const int32_t* scores_dev, const nvbio_uint2* sinks_dev,
                                          const uint32_t* win_begin_dev, uint64_t n, uint64_t* best_dev, void* stream);
 
-/* ... and back: scores_dev[r] (NVBIO_SCORE_MIN without a candidate), end_pos_dev[r] (-1 without), rc_dev[r] from best_dev[r] */
+/* ... and back: scores_dev[r] (NVBIO_SCORE_MIN without a candidate), end_pos_dev[r] (-1 without), rc_dev[r] from best_dev[r].
+ * The score field of a selection key is clamped at 0, so every score <= -2^20 unpacks as NVBIO_SCORE_MIN.  That includes the jobs the
+ * scorer rejected (score NVBIO_SCORE_MIN, sink 0xFFFFFFFF): a read whose ONLY candidates were rejected has a key that is not 0 and
+ * unpacks to score NVBIO_SCORE_MIN, end_pos = win_begin + 0xFFFFFFFF of the candidate with the largest key (no alignment's end: test the
+ * score, not end_pos >= 0) and that candidate's strand; nvbio_mapq gives it 0 and nvbio_traceback_best_batch the empty job, as long as
+ * min_score > -2^20. */
 nvbio_status nvbio_best_candidate_unpack(int device, const uint64_t* best_dev, uint32_t n_reads, int32_t* scores_dev,
                                          int64_t* end_pos_dev, uint8_t* rc_dev, void* stream);
 

@@ -46,6 +46,7 @@ FM_TABLE_NO_TEXT_PLANES = 32
 FM_TABLE_NO_SEED_LOCUS = 64
 FM_NO_SEED_LOCUS, FM_COUNT_LOCUS = 128, 4096           # nvbio_fm_match_seed_diagonals_both: the pass without the locus path / its route counts
 READ_REVERSE, READ_COMPLEMENT = 1, 2
+MAX_SEED_OFFSET = 1024            # NVBIO_MAX_SEED_OFFSET: read_len - seed_len at most, for every call that forms diagonal keys
 TRACEBACK_SINKS_GIVEN = 1
 # nvbio_alignment_batch::algo_flags (which exact shortcuts / kernel variants a call may use; results do not depend on them)
 ALN_NO_UNGAPPED_SCORE, ALN_NO_THIRD_CHANCE, ALN_NO_PACKED_DP, ALN_FORCE_PACKED_DP, ALN_NO_UNGAPPED_TRACEBACK, ALN_PK_THREE_WAVES = 1, 2, 4, 8, 16, 32
@@ -1708,6 +1709,22 @@ def diagonals_to_windows(keys, band, read_len, genome_len, read_offsets=None):
     _check(lib().nvbio_diagonals_to_windows(FMIndex._dev_index(dev), _ptr(keys), n, band, read_len, genome_len, _ptr(rid), _ptr(fl), _ptr(wb),
                                             _ptr(we), _stream_ptr(dev)))
     return rid, fl, wb, we
+
+
+def text_2bit_le_to_be(words):
+    """nvbio_text_2bit_le_to_be: 2-bit text words from sw-benchmark's little-endian packing to the library's big-endian one (int32 tensor)"""
+    torch = _torch()
+    out = torch.empty_like(words)
+    _check(lib().nvbio_text_2bit_le_to_be(FMIndex._dev_index(words.device), _ptr(words), words.numel(), _ptr(out), _stream_ptr(words.device)))
+    return out
+
+
+def scores_to_int16(scores):
+    """nvbio_scores_to_int16: int32 scores stored into int16, as sw-benchmark's output() stores them (the low 16 bits)"""
+    torch = _torch()
+    out = torch.empty(scores.numel(), dtype=torch.int16, device=scores.device)
+    _check(lib().nvbio_scores_to_int16(FMIndex._dev_index(scores.device), _ptr(scores), scores.numel(), _ptr(out), _stream_ptr(scores.device)))
+    return out
 
 
 def u32(t):

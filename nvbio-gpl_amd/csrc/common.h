@@ -32,6 +32,9 @@ const char* get_error();
 #define NVB_REQUIRE(cond, msg)                                                                     \
     do { if (!(cond)) { nvbio_amd::set_error("invalid argument: %s", msg); return NVBIO_ERR_INVALID; } } while (0)
 
+// the calls that form diagonal keys (read << 34 | strand << 33 | diagonal + 1024): see NVBIO_MAX_SEED_OFFSET in nvbio_amd.h
+#define NVB_SEED_OFFSET_MSG "read_len - seed_len exceeds 1024 (NVBIO_MAX_SEED_OFFSET): a diagonal could leave the key's 33-bit field"
+
 // Scratch with stream-ordered semantics WITHOUT the runtime's stream-ordered pool: a block taken by a ScratchBlock may be used by work enqueued on
 // `s` after the call; the ScratchBlock's destruction gives it back at once, for the next call on the SAME stream (whose work runs behind everything
 // that used the block).  Blocks are plain hipMalloc allocations cached per (device, stream).  Why not hipMallocAsync / hipFreeAsync: on ROCm 7.2 a

@@ -1745,6 +1745,7 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
     NVB_REQUIRE( q.spr > 0, "the string set must enumerate seeds (seeds_per_string > 0)" );
     NVB_REQUIRE( q.intervals == nullptr, "ragged seed sets (seed_intervals_dev) go through nvbio_fm_match_seed_diagonals_both" );
     NVB_REQUIRE( (uint64_t)(q.spr - 1u) * q.interval + q.fixed_len <= read_len, "seeds do not fit the read" );
+    NVB_REQUIRE( read_len - q.fixed_len <= NVBIO_MAX_SEED_OFFSET, NVB_SEED_OFFSET_MSG );
     NVB_REQUIRE( q.fixed_len > 0, "empty seeds" );
     if (!(idx->text && idx->view.ssa_dev && idx->view.sa_int == 1))
     {
@@ -1846,6 +1847,7 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, co
     NVB_REQUIRE( seeds->symbol_bits == 2 || seeds->symbol_bits == 4, "packed seeds (2 or 4 bits per symbol)" );
     NVB_REQUIRE( q.fixed_len >= idx->ckmer && q.fixed_len - idx->ckmer <= CTAB_FLANK, "seed length outside [kmer_len, kmer_len + 7]" );
     NVB_REQUIRE( q.intervals != nullptr || (uint64_t)(q.spr - 1u) * q.interval + q.fixed_len <= read_len, "seeds do not fit the read" );
+    NVB_REQUIRE( q.intervals != nullptr || read_len - q.fixed_len <= NVBIO_MAX_SEED_OFFSET, NVB_SEED_OFFSET_MSG );      // (ragged: the caller's to keep)
     NVB_REQUIRE( residual_capacity >= q.n, "residual_capacity must be at least the number of seeds" );
     NVB_REQUIRE( q.n < (1u << 31), "at most 2^31 - 1 seeds per call (bit 31 of a seed id carries the strand)" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
@@ -1954,6 +1956,7 @@ static nvbio_status filter_locate_diagonals(nvbio_fm_index_t index, const nvbio_
     NVB_REQUIRE( seeds_per_read > 0, "seeds_per_read must be positive" );
     NVB_REQUIRE( (read_offsets_dev == nullptr) == (seed_intervals_dev == nullptr), "ragged reads need both read_offsets_dev and seed_intervals_dev" );
     NVB_REQUIRE( read_offsets_dev != nullptr || (uint64_t)(seeds_per_read - 1u) * seed_interval + seed_len <= read_len, "seeds do not fit the read" );
+    NVB_REQUIRE( read_offsets_dev != nullptr || read_len - seed_len <= NVBIO_MAX_SEED_OFFSET, NVB_SEED_OFFSET_MSG );      // (ragged: the caller's to keep)
     FMIndexImpl* idx = (FMIndexImpl*)index;
     NVB_REQUIRE( idx->view.ssa_dev, "index has no sampled suffix array" );
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
@@ -2000,6 +2003,8 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
     NVB_REQUIRE( (uint64_t)n * cap < (1ull << 31), "n * cap must stay below 2^31" );
     NVB_REQUIRE( seeds_per_read > 0, "seeds_per_read must be positive" );
     NVB_REQUIRE( (read_offsets_dev == nullptr) == (seed_intervals_dev == nullptr), "ragged reads need both read_offsets_dev and seed_intervals_dev" );
+    NVB_REQUIRE( read_offsets_dev != nullptr || (uint64_t)(seeds_per_read - 1u) * seed_interval + seed_len <= read_len, "seeds do not fit the read" );
+    NVB_REQUIRE( read_offsets_dev != nullptr || read_len - seed_len <= NVBIO_MAX_SEED_OFFSET, NVB_SEED_OFFSET_MSG );      // (ragged: the caller's to keep)
     if (!(idx->view.ssa_dev && idx->view.sa_int == 1))
     {
         set_error( "nvbio_fm_residual_diagonals needs the full suffix array: build the index with sa_int = 1" );

@@ -635,6 +635,7 @@ extern "C" nvbio_status nvbio_hits_to_diagonals(int device, const nvbio_uint2* h
     NVB_REQUIRE( hits_dev && keys_dev, "NULL device pointer" );
     NVB_REQUIRE( seeds_per_read > 0, "seeds_per_read must be positive" );
     NVB_REQUIRE( (uint64_t)(seeds_per_read - 1u) * seed_interval + seed_len <= read_len, "seeds do not fit the read" );
+    NVB_REQUIRE( read_len - seed_len <= NVBIO_MAX_SEED_OFFSET, NVB_SEED_OFFSET_MSG );
     DeviceGuard g( device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     return NVB_LAUNCH( hits_to_diagonals_kernel, dim3( grid_for( n_hits ) ), dim3(256), (hipStream_t)stream,
                        (const uint2*)hits_dev, n_hits, seeds_per_read, seed_interval, seed_len, read_len, strand, keys_dev );

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from .abi import bind
-from . import (_MIRRORS, HOST_HEADER_PATH, ALN_RAGGED_READS, FM_COMPLEMENT, FM_NO_SEED_LOCUS, FM_SCAN_FORWARD, LOCAL, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
+from . import (_MIRRORS, HOST_HEADER_PATH, ALN_RAGGED_READS, FM_COMPLEMENT, FM_NO_SEED_LOCUS, FM_SCAN_FORWARD, LOCAL, MAX_SEED_OFFSET, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
                BatchedBandedAlignmentScore, FMIndexFilter, GotohAligner, GotohScheme, HitQueues, PackedStringSet, RaggedSeedLayout, SeedHitsParams,
                best_approx_init_ragged, read_queue_begin_ragged, score_reduce_effort, score_reduce_effort_ragged, score_stream_flatten, score_stream_output,
                seed_hits_loc, seed_hits_map, seed_hits_map_ragged, seed_hits_select, SEED_NO_LOCUS)
@@ -102,6 +102,8 @@ def _batch_geometry(torch, fmi, reads, params):
     as the reference evaluates them, per length, and gathered per read on the device"""
     dev = fmi.device
     R, M, L = reads.n, reads.read_len, params.seed_len
+    if M - L > MAX_SEED_OFFSET:             # (M: the longest read of a ragged batch, whose lengths the library cannot look at)
+        raise ValueError("read_len - seed_len = %d exceeds %d (NVBIO_MAX_SEED_OFFSET): a diagonal could leave its key's field" % (M - L, MAX_SEED_OFFSET))
     S_int = params.interval_for(M)
     spr = (M - L) // S_int + 1                                   # seeds per read and strand
     ragged = reads.offsets is not None
