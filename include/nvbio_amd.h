@@ -406,6 +406,20 @@ nvbio_status nvbio_fm_match_seed_diagonals(nvbio_fm_index_t index, const nvbio_s
  * behind a read's first; all zero where the path is off).  The sectors of NVBIO_FM_COUNT_SECTORS count a read's locus line once. */
 #define NVBIO_FM_NO_SEED_LOCUS 128u
 #define NVBIO_FM_COUNT_LOCUS 4096u
+/* How a tile of reads is resolved.  A tile in which no seed has a k-mer with more than 8 occurrences and every seed ends on at most one
+ * hit over both strands -- nearly every tile of a unique-ish genome -- is resolved by counting hits and emits the keys of both strands in
+ * one pass; every other tile takes the general code (several hits on a strand, residual and deferred entries, in-line searches).  Same
+ * keys, in the same order, either way.
+ * The common way exists where it was measured to pay and costs no occupancy: 4-bit reads, 16-byte entries (NVBIO_FM_TABLE_CANONICAL_WIDE)
+ * and NVBIO_FM_DEFER_HEAVY, with the locus path or without.  Every other launch -- 2-bit reads, 8-byte entries, no NVBIO_FM_DEFER_HEAVY (the
+ * C++ host's) -- resolves every tile by the general code, as before.
+ * NVBIO_FM_NO_FAST_RESOLVE: every tile takes the general code (A/B measurements, tests).  (Bits 8..11 belong to NVBIO_FM_INLINE_HITS.)
+ * NVBIO_FM_COUNT_RESOLVE (with NVBIO_FM_COUNT_LOCUS only): counts_dev has 12 words; word 10 = tiles resolved on the common path, word
+ * 11 = tiles resolved by the general code.  A flag of its own, so that a caller of NVBIO_FM_COUNT_LOCUS keeps its 10 words.  The accounting
+ * launch reports what the launch of the same flags does: pass NVBIO_FM_DEFER_HEAVY with it to account for a launch with that flag (the
+ * accounting launch itself defers nothing); without it word 10 is 0, as the launch it stands for has no common way. */
+#define NVBIO_FM_NO_FAST_RESOLVE 8192u
+#define NVBIO_FM_COUNT_RESOLVE 16384u
 nvbio_status nvbio_fm_match_seed_diagonals_both_temp_bytes(const nvbio_string_set* seeds, uint64_t* bytes);
 nvbio_status nvbio_fm_match_seed_diagonals_both_keys_capacity(const nvbio_string_set* seeds, uint64_t* n_keys);
 nvbio_status nvbio_fm_match_seed_diagonals_both(nvbio_fm_index_t index, const nvbio_string_set* seeds, uint32_t flags, uint32_t read_len,

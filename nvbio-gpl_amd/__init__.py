@@ -45,6 +45,7 @@ FM_TABLE_NO_DIRECT, FM_TABLE_NO_CONTEXT, FM_TABLE_NO_GROUPS, FM_TABLE_CANONICAL,
 FM_TABLE_NO_TEXT_PLANES = 32
 FM_TABLE_NO_SEED_LOCUS = 64
 FM_NO_SEED_LOCUS, FM_COUNT_LOCUS = 128, 4096           # nvbio_fm_match_seed_diagonals_both: the pass without the locus path / its route counts
+FM_NO_FAST_RESOLVE, FM_COUNT_RESOLVE = 8192, 16384     # the same pass: every tile resolved by the general code / tiles per path in counts[10:12]
 READ_REVERSE, READ_COMPLEMENT = 1, 2
 MAX_SEED_OFFSET = 1024            # NVBIO_MAX_SEED_OFFSET: read_len - seed_len at most, for every call that forms diagonal keys
 TRACEBACK_SINKS_GIVEN = 1
@@ -56,6 +57,7 @@ ALN_SPLIT_CHANCES, ALN_NO_PAIRED_GAP_CHANCE = 131072, 262144
 ALN_NO_NARROW_DP = 524288
 ALN_NO_TEXT_PLANES = 1048576
 SEED_NO_LOCUS = 2097152           # not an alignment flag: in SeedExtendParams.algo_flags it makes pipeline.seed_pass_begin pass FM_NO_SEED_LOCUS (A/B)
+SEED_NO_FAST_RESOLVE = 4194304    # likewise: pipeline.seed_pass_begin passes FM_NO_FAST_RESOLVE (A/B of the common tile's resolution)
 ROUTE_SETTLED, ROUTE_FULL_BAND, ROUTE_CLASS_A, ROUTE_CLASS_B, ROUTE_REDONE = 0, 1, 2, 3, 8
 DEFAULT_ALGO_FLAGS = 0          # what an AlignmentBatch is created with unless told otherwise (tests set it for a whole run)
 BACKTRACK_REFERENCE_QUIRKS = 1
@@ -473,9 +475,11 @@ class FMIndex:
     def match_seed_diagonals_both(self, seeds, read_len, buffers=None, flags=0, grid_blocks=0, inline_hits=0, defer_heavy=False):
         """the seed pass of BOTH strands in one launch over the canonical table (nvbio_fm_match_seed_diagonals_both) -> the buffers dict:
         "keys" int64 (the first counts[0]: both strands, tile by tile), "ranges" int32 [2 n, 2] / "ids" int32 [2 n]: residual seeds on
-        several rows, forward strand in [0, counts[1]), reverse strand in [n, n + counts[2]); "counts" int32 [10] on the device
-        ([4:6]: FM_COUNT_SECTORS' uint64, [6:10]: FM_COUNT_LOCUS' route counts).
-        flags: FM_NO_SEED_LOCUS runs the pass without the locus path (seed_locus(): same results either way).
+        several rows, forward strand in [0, counts[1]), reverse strand in [n, n + counts[2]); "counts" int32 [12] on the device
+        ([4:6]: FM_COUNT_SECTORS' uint64, [6:10]: FM_COUNT_LOCUS' route counts, [10:12]: FM_COUNT_RESOLVE's tiles per path).
+        flags: FM_NO_SEED_LOCUS runs the pass without the locus path (seed_locus(): same results either way); FM_NO_FAST_RESOLVE
+        resolves every tile by the general code (same results either way; the common way exists with 4-bit reads, 16-byte entries and
+        defer_heavy only, and FM_COUNT_RESOLVE accounts for the launch of the same flags: pass defer_heavy with it).
         inline_hits (2..4): a search that ends on up to that many rows leaves all their keys in "keys" instead of a residual entry.
         "tile_offsets" int32 [n_tiles + 1]: tile t (the reads [t * reads_per_tile, (t + 1) * reads_per_tile)) owns keys[tile_offsets[t] :
         tile_offsets[t + 1]]; counts[3] = tile_offsets[n_tiles], the keys in tile order (deferred searches append theirs behind them)."""
@@ -491,7 +495,7 @@ class FMIndex:
             buffers["keys"] = torch.empty(max(int(cap.value), 1), dtype=torch.int64, device=self.device)
             buffers["ranges"] = torch.empty((2 * n, 2), dtype=torch.int32, device=self.device)
             buffers["ids"] = torch.empty(2 * n, dtype=torch.int32, device=self.device)
-            buffers["counts"] = torch.zeros(10, dtype=torch.int32, device=self.device)    # [4:6]: FM_COUNT_SECTORS' uint64, [6:10]: FM_COUNT_LOCUS
+            buffers["counts"] = torch.zeros(12, dtype=torch.int32, device=self.device)    # [4:6]: FM_COUNT_SECTORS' uint64, [6:10]: FM_COUNT_LOCUS, [10:12]: FM_COUNT_RESOLVE
             nb = ctypes.c_uint64(0)
             _check(lib().nvbio_fm_match_seed_diagonals_both_temp_bytes(ctypes.byref(qs), ctypes.byref(nb)))
             buffers["temp"] = torch.empty(nb.value, dtype=torch.uint8, device=self.device)

@@ -490,18 +490,36 @@ __device__ __forceinline__ void fm_seed_locus_loop(const DevIndex& f, const Stri
 // four loads issued together: the one dependent gather outside the schedule, in the iterations where one of the wave's anchors has a
 // k-mer with 3..8 occurrences.  The loop is bound by the vector instructions it issues, not by its loads: what it carries
 // from stage to stage and what it computes per lane is kept small for that reason.
+// Resolution and emission (resolve_tile), two ways.  The COMMON tile -- no lane heavy, every lane with at most one hit over both strands:
+// 98.4 % of the headline batch's tiles -- has its rows evaluated by counts (hits, strand and position of the last one; group rows only in
+// a wave that holds a group) and its keys of both strands emitted in ONE pass: forward keys to the slots [0, n0), reverse keys behind them,
+// a key dropped iff the nearest lower lane with a key on its strand lies in the same read on the same diagonal (which is key equality: see
+// there).  Every other tile runs the general code: hits slot by slot, one emission per strand through emit_seed_results, residual and
+// deferred entries, the in-line searches.  Same keys in the same order either way; NVBIO_FM_NO_FAST_RESOLVE (resolve_opts) sends every tile
+// through the general code, and only the forms named at FAST_FORM hold the common path at all.  paths (COUNT, NVBIO_FM_COUNT_RESOLVE): tiles resolved as common | by the general code.
 // routes (COUNT, NVBIO_FM_COUNT_LOCUS): reads with a usable anchor | windows settled on the locus | windows of such reads that gathered
 // after all | windows of reads without a usable anchor -- the last three over the windows behind the anchor (j > 0).
 // RAGGED (with LOCUS only; the other forms look at q.intervals): the batch has ragged reads.  A form of its own, chosen by the launcher, so
 // that uniform reads pay neither the registers nor the instructions of a geometry that is the same for every read.
+constexpr uint32_t SEED_RESOLVE_GENERAL = 16u;   // in resolve_opts: every tile takes the general path (NVBIO_FM_NO_FAST_RESOLVE)
 template <int BITS, bool COUNT, bool WIDE, bool DEFER, bool LOCUS, bool RAGGED = false>
 __global__ void __launch_bounds__(256)
-fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, const uint32_t read_len, const uint32_t inline_max,
+fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, const uint32_t read_len, const uint32_t resolve_opts,
                     uint64_t* __restrict__ tile_keys, uint32_t* __restrict__ tile_counts, uint2* __restrict__ res_ranges,
                     uint32_t* __restrict__ res_ids, const uint32_t res_cap, unsigned int* __restrict__ counts, unsigned long long* __restrict__ sectors_out,
-                    uint32_t* __restrict__ tile_defer, uint32_t* __restrict__ defer_counts, const void* __restrict__ locus, unsigned int* __restrict__ routes)
+                    uint32_t* __restrict__ tile_defer, uint32_t* __restrict__ defer_counts, const void* __restrict__ locus, unsigned int* __restrict__ routes,
+                    unsigned int* __restrict__ paths)
 {
     const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t inline_max = resolve_opts & 15u;                          // resolve_opts: inline_max | SEED_RESOLVE_GENERAL
+    // Which forms hold both ways of resolving a tile.  The second way costs 6 to 9 VGPRs, and that costs some forms a wave per SIMD: the
+    // locus loop without DEFER (the C++ host's: 95 -> 103 VGPRs, 5 -> 4 waves, measured no faster), the forms over 8-byte entries and the
+    // forms for 2-bit reads (6 -> 5, 7 -> 6; not measured).  Only the forms that keep their waves and were measured have it: 4-bit reads,
+    // 16-byte entries, DEFER -- the locus loop (uniform and ragged) and the old loop of the step.  Every other form is compiled with the
+    // general code alone, as before.  An accounting form (COUNT, compiled without DEFER) accounts for the launch of the same flags: the
+    // launcher sets SEED_RESOLVE_GENERAL for it where that launch asked for no DEFER.
+    constexpr bool FAST_FORM = BITS == 4 && WIDE && (COUNT || DEFER);
+    const bool fast_ok = FAST_FORM && !(resolve_opts & SEED_RESOLVE_GENERAL) && inline_max >= 1u && f.length >= q.fixed_len;
     const uint32_t n_waves = gridDim.x * 4u;
     const uint32_t k = f.ckmer, len = q.fixed_len, r = len - k;
     const uint32_t lr = lane / q.spr, j = lane - lr * q.spr;
@@ -542,6 +560,76 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
         const uint32_t m = e.y - DTAB_MARK;
         const uint32_t rest = (uint32_t)V & rmask;                           // the seed's first r symbols, reversed (scan order)
         const uint32_t want = qo ? (~rest & rmask) : rest;
+        const uint32_t i = rid * q.spr + j;
+        uint32_t sectors = (e_valid && !(LOCUS && settled)) ? (is_group ? 2u : 1u) : 0u;
+        // ---- the common tile.  The rows of every lane BY COUNTS, as canon_lookup keeps them but leaner still: the number of hits over both
+        // strands, and the strand and row position of the last one -- selects between registers, no slots, no branch (canon_row_hit's
+        // tests restated without its early returns: the field of the flank that this lane compares, and the orientation bit, read
+        // straight from the row's second word, whose mark sits above both).  The group rows run only in a wave that holds a group, rows
+        // 4..7 only where one of its groups has them.  Then ONE wave-uniform decision, behind the group rows: the tile is common iff no
+        // lane with a clean seed is heavy or has more than one hit over both strands (and one hit may stay in line: inline_max >= 1).
+        // Such a tile has no residual entry, no deferred search, no in-line search and at most 64 keys, and every lane holds at most one
+        // (strand, position): both strands are emitted in one pass.  Every other tile runs the general code below, which reads none of
+        // these registers.
+        bool common = false;
+        if (fast_ok)
+        {
+            const uint32_t fsel = (qo ? 0u : 14u) + fshift;                      // where the compared flank begins in a row's second word
+            const uint32_t plim = f.length - len + 1u;                           // a reverse-strand hit at P needs P + len <= length (fast_ok: length >= len)
+            uint32_t cnt = 0, hit_rev = 0, hit_p = 0;
+            auto crow = [&](const bool on, const uint32_t P, const uint32_t C) {
+                const uint32_t rev = ((C >> 28) ^ qo) & 1u;
+                const bool fits = rev ? P < plim : P >= r;
+                const bool hit = on & (__builtin_amdgcn_ubfe( C, fsel, 2u * r ) == want) & fits;
+                cnt += hit ? 1u : 0u; hit_rev = hit ? rev : hit_rev; hit_p = hit ? P : hit_p;
+            };
+            crow( is_one, e.x, e.y );
+            if (WIDE) crow( is_one & (e.w >= DTAB_MARK), e.z, e.w );
+            if (__ballot( is_group ))
+            {
+                const uint32_t gm = is_group ? m : 0u;
+                crow( 0u < gm, q0.x, q0.y ); crow( 1u < gm, q0.z, q0.w ); crow( 2u < gm, q1.x, q1.y ); crow( 3u < gm, q1.z, q1.w );
+                if (__ballot( gm > 4u ))
+                {
+                    crow( 4u < gm, q2.x, q2.y ); crow( 5u < gm, q2.z, q2.w ); crow( 6u < gm, q3.x, q3.y ); crow( 7u < gm, q3.z, q3.w );
+                }
+            }
+            uint32_t v = hit_rev ? hit_p : hit_p - r;                            // where the window (its reverse complement) begins in the text
+            if (LOCUS && settled) { cnt = 1u; hit_rev = settled - 1u; v = settled_x; }
+            const bool live = valid && e_valid;
+            common = __ballot( live && (is_heavy || cnt > 1u) ) == 0ull;
+            if (common)
+            {
+                // a lane's one key: (uint64) v + 1024 - p, as emit_seed_results forms it
+                const bool     has = live && cnt == 1u;
+                const uint32_t s = hit_rev;
+                const uint32_t p = s ? c_rlen - c_pfw - len : c_pfw;
+                const uint64_t diag = (uint64_t)v + 1024u - p;
+                const uint64_t key = ((uint64_t)rid << 34) | ((uint64_t)s << 33) | diag;
+                // A key is dropped iff it equals that of the nearest lower lane with a key on the same strand.  Two such keys have the same
+                // strand bit, so they are equal iff their reads and their diagonals are.  The read: a tile's reads sit in runs of q.spr
+                // lanes, so the predecessor lies in this lane's read iff its lane is not below this read's first (lane - j); the read id
+                // occupies bits 34 and up, which the diagonal never reaches: v + 1024 < 2^32 (a text has at most 2^32 - 8193 symbols) and
+                // p <= 1024 (NVBIO_MAX_SEED_OFFSET), so 0 <= diag < 2^32.  The diagonal: for the same reason its low word IS the diagonal,
+                // and one ds_bpermute of that word replaces the two of the whole key.
+                const uint64_t below = (1ull << lane) - 1ull;
+                const uint64_t m0 = __ballot( has && s == 0u ), m1 = __ballot( has && s != 0u );
+                const uint64_t prev_mask = (s ? m1 : m0) & below;
+                const int      prev_lane = prev_mask ? 63 - __clzll( (long long)prev_mask ) : 0;
+                const uint32_t prev_diag = (uint32_t)__shfl( (int)(uint32_t)diag, prev_lane );
+                const bool     dup = prev_mask != 0ull && (uint32_t)prev_lane >= lane - j && prev_diag == (uint32_t)diag;
+                const bool     keep = has && !dup;
+                // forward keys to the slots [0, n0) in lane order, reverse keys to [n0, n0 + n1)
+                const uint64_t k0 = __ballot( keep && s == 0u ), k1 = __ballot( keep && s != 0u );
+                const uint32_t n0 = (uint32_t)__popcll( k0 ), n1 = (uint32_t)__popcll( k1 );
+                if (keep) tile_keys[(uint64_t)tile * 128u + (s ? n0 + (uint32_t)__popcll( k1 & below ) : (uint32_t)__popcll( k0 & below ))] = key;
+                if (lane == 0) { tile_counts[tile] = n0 + n1; if (DEFER) defer_counts[tile] = 0u; }
+            }
+        }
+        if (COUNT && paths && lane == 0) atomicAdd( paths + (common ? 0 : 1), 1u );
+        if (!common)
+        {
+        // ---- every other tile, in general: hits and positions slot by slot, strand by strand
         // per strand: the hits found among the entry's rows (the first CTAB_INLINE positions are kept)
         uint32_t hits[2] = { 0, 0 }, pos[2][CTAB_INLINE] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
         auto row = [&](const uint32_t P, const uint32_t C) {
@@ -569,8 +657,6 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
             hits[0] = settled == 1u; hits[1] = settled == 2u;
             pos[0][0] = pos[1][0] = settled_x;
         }
-        uint32_t sectors = (e_valid && !(LOCUS && settled)) ? (is_group ? 2u : 1u) : 0u;
-        const uint32_t i = rid * q.spr + j;
         uint32_t tile_fill = 0;                                              // keys of this tile written so far: the reverse strand's follow the forward strand's
         uint32_t defer_fill = 0;                                             // deferred searches of this tile recorded so far (DEFER)
         #pragma unroll
@@ -648,6 +734,7 @@ fm_seed_both_kernel(const DevIndex f, const StringSetDev q, const SeedTiles tl, 
             }
         }
         if (lane == 0) { tile_counts[tile] = tile_fill; if (DEFER) defer_counts[tile] = defer_fill; }
+        }
         if (COUNT)
         {
             uint32_t tot = valid ? sectors : 0u;

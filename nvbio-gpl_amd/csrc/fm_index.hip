@@ -1856,8 +1856,10 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, co
     const bool defer = (flags & NVBIO_FM_DEFER_HEAVY) != 0 && !count;
     const bool routes = (flags & NVBIO_FM_COUNT_LOCUS) != 0;
     NVB_REQUIRE( !routes || count, "NVBIO_FM_COUNT_LOCUS goes with NVBIO_FM_COUNT_SECTORS" );
+    const bool paths = (flags & NVBIO_FM_COUNT_RESOLVE) != 0;
+    NVB_REQUIRE( !paths || routes, "NVBIO_FM_COUNT_RESOLVE goes with NVBIO_FM_COUNT_LOCUS" );
     NVB_REQUIRE( !count || ((uintptr_t)counts_dev & 7u) == 0, "counts_dev must be 8-byte aligned with NVBIO_FM_COUNT_SECTORS" );
-    NVB_HIP( hipMemsetAsync( counts_dev, 0, (routes ? 10 : (count ? 6 : 4)) * sizeof(uint32_t), s ) );
+    NVB_HIP( hipMemsetAsync( counts_dev, 0, (paths ? 12 : (routes ? 10 : (count ? 6 : 4))) * sizeof(uint32_t), s ) );
     // the locus path: lines built for this seed length, reads that fit one line (ragged reads: the kernel looks at every read's length)
     const bool use_locus = idx->locus && idx->locus_len == q.fixed_len && !(flags & NVBIO_FM_NO_SEED_LOCUS) &&
                            (q.intervals != nullptr || read_len <= SEED_LOCUS_MAX_READ);
@@ -1878,16 +1880,20 @@ nvbio_status nvbio_fm_match_seed_diagonals_both_tiled(nvbio_fm_index_t index, co
     // flags bits 8..11: a seed with up to that many hits on a strand leaves them all as keys (0/1: only one-hit seeds do)
     uint32_t inline_max = (flags >> 8) & 15u;
     inline_max = inline_max < 1u ? 1u : (inline_max > CTAB_INLINE ? CTAB_INLINE : inline_max);
+    // (the common path exists in the forms with NVBIO_FM_DEFER_HEAVY only -- FAST_FORM in fm_canon_inl.h; an accounting launch, which is
+    // compiled without DEFER, follows the launch it accounts for)
+    const uint32_t resolve_opts = inline_max | (((flags & NVBIO_FM_NO_FAST_RESOLVE) || !(flags & NVBIO_FM_DEFER_HEAVY)) ? SEED_RESOLVE_GENERAL : 0u);
     NVB_CHECK( with_value( Values<2, 4>(), seeds->symbol_bits, [&](auto BITS)
     {
         const auto launch = [&](auto CNT, auto W, auto D, auto LC)
         {
             const auto form = [&](auto RG)                       // (the locus path has a form of its own for ragged reads)
             {
-                return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D,LC,RG>), grid, block, s, f, q, L.tl, read_len, inline_max, tile_keys, tile_counts,
+                return NVB_LAUNCH( (fm_seed_both_kernel<BITS,CNT,W,D,LC,RG>), grid, block, s, f, q, L.tl, read_len, resolve_opts, tile_keys, tile_counts,
                                    (uint2*)residual_ranges_dev, residual_ids_dev, residual_capacity, (unsigned int*)counts_dev,
                                    CNT ? (unsigned long long*)(counts_dev + 4) : (unsigned long long*)nullptr, tile_defer, defer_counts,
-                                   (const void*)(LC ? idx->locus : nullptr), routes ? (unsigned int*)counts_dev + 6 : (unsigned int*)nullptr );
+                                   (const void*)(LC ? idx->locus : nullptr), routes ? (unsigned int*)counts_dev + 6 : (unsigned int*)nullptr,
+                                   paths ? (unsigned int*)counts_dev + 10 : (unsigned int*)nullptr );
             };
             if constexpr (LC) { if (q.intervals != nullptr) return form( std::true_type() ); }
             return form( std::false_type() );

@@ -18,10 +18,10 @@ import os
 import numpy as np
 
 from .abi import bind
-from . import (_MIRRORS, HOST_HEADER_PATH, ALN_RAGGED_READS, FM_COMPLEMENT, FM_NO_SEED_LOCUS, FM_SCAN_FORWARD, LOCAL, MAX_SEED_OFFSET, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
+from . import (_MIRRORS, HOST_HEADER_PATH, ALN_RAGGED_READS, FM_COMPLEMENT, FM_NO_FAST_RESOLVE, FM_NO_SEED_LOCUS, FM_SCAN_FORWARD, LOCAL, MAX_SEED_OFFSET, READ_COMPLEMENT, READ_REVERSE, SCORE_MIN, SEMI_GLOBAL, AlignmentBatch,
                BatchedBandedAlignmentScore, FMIndexFilter, GotohAligner, GotohScheme, HitQueues, PackedStringSet, RaggedSeedLayout, SeedHitsParams,
                best_approx_init_ragged, read_queue_begin_ragged, score_reduce_effort, score_reduce_effort_ragged, score_stream_flatten, score_stream_output,
-               seed_hits_loc, seed_hits_map, seed_hits_map_ragged, seed_hits_select, SEED_NO_LOCUS)
+               seed_hits_loc, seed_hits_map, seed_hits_map_ragged, seed_hits_select, SEED_NO_FAST_RESOLVE, SEED_NO_LOCUS)
 
 
 class SeedExtendParams:
@@ -157,10 +157,12 @@ def seed_pass_begin(fmi, reads, params, slot=0, timers=None, stream=None, after=
         a.record()
     # seeds that end on 2..4 rows (short repeats) leave all their keys at once: on unique-ish genomes the residual lists stay
     # empty and the scan + locate path with its host round trips is not entered at all
-    # (algo_flags bit SEED_NO_LOCUS is the seed pass's own: the A/B switch of its locus path; the alignment side does not know it)
+    # (algo_flags bits SEED_NO_LOCUS and SEED_NO_FAST_RESOLVE are the seed pass's own: the A/B switches of its locus path and of the common
+    # tile's resolution; the alignment side does not know them)
+    af = params.algo_flags or 0
     fmi.match_seed_diagonals_both(geo["qs"], reads.read_len, b, inline_hits=min(4, params.max_seed_hits or 4), defer_heavy=params.defer_heavy,
                                   grid_blocks=int(getattr(params, "seed_grid_blocks", 0) or 0),
-                                  flags=FM_NO_SEED_LOCUS if (params.algo_flags or 0) & SEED_NO_LOCUS else 0)
+                                  flags=(FM_NO_SEED_LOCUS if af & SEED_NO_LOCUS else 0) | (FM_NO_FAST_RESOLVE if af & SEED_NO_FAST_RESOLVE else 0))
     if ev_t is not None:
         ev_t.record()
     if "host" not in b:
