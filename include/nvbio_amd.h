@@ -1772,6 +1772,134 @@ nvbio_status nvbio_fastq_encode(int device, const uint8_t* text_dev, uint64_t te
                                 uint64_t temp_bytes, uint32_t* reads4_dev, uint64_t reads4_capacity_words, uint32_t* read_index_dev, uint8_t* quals_dev,
                                 uint8_t* names_dev, uint64_t names_capacity, uint32_t* name_index_dev, uint32_t* status_dev, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * FASTA input: the bytes of a reference FASTA file, or of a chunk of one cut anywhere, turned on the device into what the index
+ * builder and the SAM writer take -- the 2-bit big-endian packed text nvbio_fm_index_build reads, the sequences' starts and names
+ * (nvbio_sam_refs), the holes (runs of ambiguous symbols) and the symbol frequencies.  It is nvBWT's front half, which runs on the host
+ * one byte at a time: FASTA_inc_reader::read (nvbio/fasta/fasta_inl.h:64-122) feeding nvBWT's Writer (nvBWT/nvBWT.cu:102-195), whose
+ * tables save_bns and save_bpac write as .ann, .amb and .pac (nvbio/basic/bnt.cpp:28-73, nvBWT.cu:243-287).
+ *
+ * The grammar is the reference's: ONE sequential machine over bytes.
+ *   state | '>'    ' '    '\n'   0xFF   other | what the bytes that stay are
+ *   PRE   | ID     .      .      END    .     | before the first '>': everything is dropped
+ *   ID    | .      REST   BODY   .      .     | the name: every byte up to the first ' ' or '\n', '>' and 0xFF included
+ *   REST  | .      .      BODY   .      .     | the rest of the header line, dropped
+ *   BODY  | ID     .      .      END    .     | every byte but '\n', ' ', '>' and 0xFF is a symbol: '\r', tab and NUL too.  '>' starts the next
+ *         |                                   | sequence anywhere, in mid-line too
+ *   END   | .      .      .      .      .     | absorbing: 0xFF is the reader's end-of-file value, tested in PRE and BODY only
+ * Symbols: A a 0, C c 1, G g 2, T t 3; every other byte is ambiguous, '-' too (nst_nt4_table gives it 5, the Writer tests c >= 4).  The
+ * k-th ambiguous symbol of the whole input, k from 0, is stored as X[k + 1] >> 46 with X[0] = (seed << 16) | 0x330E and
+ * X[i + 1] = (0x5DEECE66D * X[i] + 0xB) mod 2^48: uint8( drand48() * 4 ) & 3 after srand48( seed ), seed 11 in nvBWT.
+ * A hole (BNTAmb) is a maximal run, within one sequence, of the SAME ambiguous byte among consecutive symbols; line breaks and spaces
+ * do not cut it, another byte does ('N' then 'n' are two holes, and so are two 'N' around an 'A').  A sequence (BNTAnnData) has an
+ * offset, a length, a name and n_ambs, the holes that start in it.
+ * Departures:
+ *   a. names are stored without a terminating NUL, with n + 1 offsets, as nvbio_sam_refs takes them
+ *   b. input that ends inside a header line raises NVBIO_FASTA_STATUS_INCOMPLETE (the reference's header loops never test for the
+ *      end of the file: it does not return)
+ *   c. the 1025th, 2049th, ... sequence is kept (nvBWT reads 1024 at a time, and read() has consumed the next record's '>' when it returns)
+ *   d. an ambiguous first symbol of a sequence always starts a hole (the Writer compares it with m_lasts = 0: a NUL that comes first
+ *      would lengthen the hole before it, or index an empty vector)
+ *   e. there is no max_length cut
+ *   f. symbol coordinates are 32-bit: an input whose symbols or name bytes would reach 2^32 raises NVBIO_FASTA_STATUS_OVERFLOW_32 and
+ *      the chunk that would cross is not encoded
+ *   g. a text with no '>' has no sequence (the reference delivers one, nameless and empty)
+ * Not offered: gzip, the reversed text (.rpac), .wpac, listing a directory of files: feed them one after another through one state.
+ *
+ * The machine parallelises as fastq's does: a byte is a function over the five states, functions compose; 16 bytes per lane, lanes
+ * across the wave, waves through LDS, 4096-byte tiles through an array that one workgroup scans, in separate launches.  With each
+ * tile's entry state known a second pass counts, per tile, symbols, ambiguous symbols, sequence starts, hole starts and name bytes,
+ * and takes the tile's first and last symbol byte ("rightmost defined, reset at '>'"); one workgroup scans these.  The body is a
+ * stream compaction: nvbio_fasta_encode stages a tile's symbols in LDS in output order, decides hole starts from the staged
+ * neighbour (the carried byte for the tile's first symbol), draws an ambiguous symbol by jumping the generator to its global rank
+ * (33 affine maps, one per bit of the rank), packs 16 symbols a word and stores whole words, 16 bytes at a time where four words lie
+ * inside the tile's range.  The word at either end of a tile's range is shared with its neighbours (or with the chunk before) and is
+ * merged with atomicOr into a word that was zeroed.
+ * ------------------------------------------------------------------------------------------- */
+#define NVBIO_FASTA_PRE  0u
+#define NVBIO_FASTA_ID   1u
+#define NVBIO_FASTA_REST 2u
+#define NVBIO_FASTA_BODY 3u
+#define NVBIO_FASTA_END  4u
+
+#define NVBIO_FASTA_NO_SYMBOL 0x100u         /* nvbio_fasta_state.last_symbol: the current sequence has no symbol yet                          */
+
+/* nvbio_fasta_summary.status / *status_dev */
+#define NVBIO_FASTA_STATUS_INCOMPLETE  1u   /* the text ends inside a header line (ID or REST): an error only behind the last chunk           */
+#define NVBIO_FASTA_STATUS_END_BYTE    2u   /* byte 0xFF in PRE or BODY ended the input (or had ended it before this chunk): consumed_bytes    */
+#define NVBIO_FASTA_STATUS_OVERFLOW_32 4u   /* departure f; nvbio_fasta_encode writes nothing and leaves the state as it is                    */
+#define NVBIO_FASTA_STATUS_CAPACITY    8u   /* nvbio_fasta_encode: a word, sequence, name byte or hole did not fit and was not written         */
+
+/* The carry from chunk to chunk, 64 bytes in device memory.  nvbio_fasta_state_init sets it, nvbio_fasta_encode advances it, the
+ * caller copies it back when it wants the totals.  n_symbols is the text's length so far, freq the counts of the four stored symbols
+ * (nvBWT's m_freq: the drawn ones included). */
+typedef struct
+{
+    uint32_t machine;            /* NVBIO_FASTA_PRE .. NVBIO_FASTA_END                                                                     */
+    uint32_t n_symbols;
+    uint32_t n_seqs;
+    uint32_t n_ambs;             /* ambiguous symbols so far = draws so far                                                                */
+    uint32_t n_holes;
+    uint32_t n_name_bytes;
+    uint32_t last_symbol;        /* the last symbol byte of the current sequence, or NVBIO_FASTA_NO_SYMBOL                                 */
+    uint32_t seed;
+    uint32_t freq[4];
+    uint32_t max_name_len;       /* set by nvbio_fasta_finish                                                                              */
+    uint32_t reserved[3];
+} nvbio_fasta_state;
+
+/* what nvbio_fasta_scan found in ONE chunk, entered in the state it was given.  consumed_bytes is text_bytes, or the offset of the 0xFF
+ * that ended the input (0 when an earlier chunk had ended it). */
+typedef struct
+{
+    uint32_t n_symbols;
+    uint32_t n_seqs;             /* sequences that START in the chunk                                                                      */
+    uint32_t n_ambs;
+    uint32_t n_holes;            /* holes that START in the chunk                                                                          */
+    uint32_t n_name_bytes;
+    uint32_t consumed_bytes;
+    uint32_t machine;            /* the state behind the chunk                                                                             */
+    uint32_t status;             /* INCOMPLETE, END_BYTE, OVERFLOW_32                                                                      */
+} nvbio_fasta_summary;
+
+/* *state_dev = the state in front of the first byte of the first file: PRE, nothing counted, this seed (nvBWT: 11) */
+nvbio_status nvbio_fasta_state_init(int device, nvbio_fasta_state* state_dev, uint32_t seed, void* stream);
+
+/* the bytes of temp_dev both calls need for a chunk of text_bytes: 36 for each 4096-byte tile and a header */
+nvbio_status nvbio_fasta_temp_bytes(uint64_t text_bytes, uint64_t* bytes);
+
+/* The machine over text_dev[0, text_bytes) (16-byte aligned; text_bytes >= 2^32 is NVBIO_ERR_UNSUPPORTED: feed chunks) entered in
+ * *state_dev, which is read and not changed; the tiles' counts stay in temp_dev for nvbio_fasta_encode, *summary_dev is the chunk's
+ * totals: what a caller reads to grow its arrays.  No host synchronisation. */
+nvbio_status nvbio_fasta_scan(int device, const uint8_t* text_dev, uint64_t text_bytes, const nvbio_fasta_state* state_dev,
+                              nvbio_fasta_summary* summary_dev, void* temp_dev, uint64_t temp_bytes, void* stream);
+
+/* The chunk's items, from what nvbio_fasta_scan left in temp_dev (same text, text_bytes and temp_dev, *state_dev as the scan read it),
+ * appended at the state's counts; then the state advances by the chunk's counts, whether the items fitted or not:
+ *   text2_dev            symbol i in bits 30 - 2 * (i % 16) of word i / 16; text2_capacity_words words, 16-byte aligned.  The words from
+ *                        ceil( state.n_symbols / 16 ) on are zeroed first; the word a chunk before filled in part is merged into
+ *   seq_offset_dev       [s] = the symbols before sequence s; max_seqs + 1 entries (nvbio_fasta_finish writes entry n_seqs)
+ *   name_index_dev       [s] = the name bytes before sequence s; max_seqs + 1 entries
+ *   names_dev            names_capacity bytes
+ *   hole_offset_dev      [h] = where hole h starts in the text
+ *   hole_rank_dev        [h] = the ambiguous symbols before hole h: nvbio_fasta_finish turns the ranks into lengths
+ *   hole_amb_dev         [h] = the hole's byte; max_holes entries each
+ * An item at or past its capacity is not written and NVBIO_FASTA_STATUS_CAPACITY is ORed into *status_dev (a device word; never cleared
+ * here).  Every output pointer may be NULL, which counts as capacity 0 without the bit: with all of them NULL the call only counts
+ * (nvBWT's Counter pass) and leaves the same state.  state.freq is counted here, where the draws are made (the counts pass through
+ * temp_dev).  Calling it again for the same scan writes the same again.  No host synchronisation. */
+nvbio_status nvbio_fasta_encode(int device, const uint8_t* text_dev, uint64_t text_bytes, void* temp_dev, uint64_t temp_bytes,
+                                nvbio_fasta_state* state_dev, uint32_t* text2_dev, uint64_t text2_capacity_words, uint32_t* seq_offset_dev,
+                                uint32_t* name_index_dev, uint32_t max_seqs, uint8_t* names_dev, uint64_t names_capacity, uint32_t* hole_offset_dev,
+                                uint32_t* hole_rank_dev, uint8_t* hole_amb_dev, uint32_t max_holes, uint32_t* status_dev, void* stream);
+
+/* Closes the tables once, behind the last chunk: seq_offset[n_seqs] = n_symbols and name_index[n_seqs] = n_name_bytes (when n_seqs <=
+ * max_seqs), hole_len[h] = the ranks' differences (the last from state.n_ambs), seq_n_ambs[s] = the holes that start in sequence s,
+ * state.max_name_len.  hole_len_dev and seq_n_ambs_dev may be NULL.  Reads only entries below the capacities and the state's counts. */
+nvbio_status nvbio_fasta_finish(int device, nvbio_fasta_state* state_dev, uint32_t* seq_offset_dev, uint32_t* name_index_dev, uint32_t max_seqs,
+                                const uint32_t* hole_offset_dev, const uint32_t* hole_rank_dev, uint32_t max_holes, uint32_t* hole_len_dev,
+                                uint32_t* seq_n_ambs_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2392,9 +2392,215 @@ def read_fastq(path, chunk_bytes=64 << 20, **kw):
                 return
 
 
+# ---- FASTA input -----------------------------------------------------------------------------------------------------------------
+FASTA_PRE, FASTA_ID, FASTA_REST, FASTA_BODY, FASTA_END = 0, 1, 2, 3, 4
+FASTA_NO_SYMBOL = 0x100
+FASTA_STATUS_INCOMPLETE, FASTA_STATUS_END_BYTE, FASTA_STATUS_OVERFLOW_32, FASTA_STATUS_CAPACITY = 1, 2, 4, 8
+FASTA_STATE_FIELDS = ("machine", "n_symbols", "n_seqs", "n_ambs", "n_holes", "n_name_bytes", "last_symbol", "seed")
+FASTA_SUMMARY_FIELDS = ("n_symbols", "n_seqs", "n_ambs", "n_holes", "n_name_bytes", "consumed_bytes", "machine", "status")
+
+
+class _FastaState(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in FASTA_STATE_FIELDS] + [("freq", ctypes.c_uint32 * 4), ("max_name_len", ctypes.c_uint32),
+                                                                     ("reserved", ctypes.c_uint32 * 3)]
+
+
+class _FastaSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in FASTA_SUMMARY_FIELDS]
+
+
+def fasta_state_init(seed=11, device="cuda:0"):
+    """nvbio_fasta_state_init -> the state as an int32 device tensor [16]: the carry from chunk to chunk"""
+    state = _torch().empty(16, dtype=_torch().int32, device=device)
+    _check(lib().nvbio_fasta_state_init(FMIndex._dev_index(device), ctypes.cast(state.data_ptr(), ctypes.POINTER(_FastaState)), int(seed), _stream_ptr(device)))
+    return state
+
+
+def fasta_state(state):
+    """the state tensor -> dict (one copy to the host): FASTA_STATE_FIELDS, freq (list of 4), max_name_len"""
+    v = [int(x) for x in state.cpu().numpy().view(np.uint32)]
+    return dict(zip(FASTA_STATE_FIELDS, v[:8]), freq=v[8:12], max_name_len=v[12])
+
+
+def fasta_scan(text, state, temp=None, text_bytes=None):
+    """nvbio_fasta_scan over a uint8 device tensor entered in `state` (not changed) -> (summary: int32 tensor [8] on the device,
+    FASTA_SUMMARY_FIELDS; temp: what fasta_encode reads).  No synchronisation."""
+    torch = _torch()
+    dev = text.device
+    nb = text.numel() if text_bytes is None else int(text_bytes)
+    if temp is None:
+        temp, _ = _temp_for(lib().nvbio_fasta_temp_bytes, nb, device=dev)
+    summary = torch.empty(len(FASTA_SUMMARY_FIELDS), dtype=torch.int32, device=dev)
+    _check(lib().nvbio_fasta_scan(FMIndex._dev_index(dev), _ptr(text) if text.numel() else None, nb, ctypes.cast(state.data_ptr(), ctypes.POINTER(_FastaState)),
+                                  ctypes.cast(summary.data_ptr(), ctypes.POINTER(_FastaSummary)), _ptr(temp), temp.numel(), _stream_ptr(dev)))
+    return summary, temp
+
+
+def fasta_summary(summary):
+    """the summary tensor of fasta_scan -> dict (one copy to the host)"""
+    return dict(zip(FASTA_SUMMARY_FIELDS, (int(v) for v in summary.cpu().numpy().view(np.uint32))))
+
+
+def fasta_encode(text, temp, state, status, text2=None, seq_offset=None, name_index=None, names=None, hole_offset=None, hole_rank=None, hole_amb=None,
+                 text2_capacity_words=None, max_seqs=None, names_capacity=None, max_holes=None, text_bytes=None):
+    """nvbio_fasta_encode into caller tensors (text2 int32 words; seq_offset / name_index int32 with one entry more than max_seqs; names
+    and hole_amb uint8; hole_offset / hole_rank int32; status: an int32 device word); a tensor left None is not written; the capacities
+    default to the tensors' sizes.  Advances `state`.  No synchronisation."""
+    dev = text.device
+    nb = text.numel() if text_bytes is None else int(text_bytes)
+    size = lambda t, less=0: 0 if t is None else max(t.numel() - less, 0)
+    words = size(text2) if text2_capacity_words is None else int(text2_capacity_words)
+    seqs = min(size(seq_offset, 1) if seq_offset is not None else 1 << 32, size(name_index, 1) if name_index is not None else 1 << 32) if max_seqs is None else int(max_seqs)
+    holes = min([size(t) for t in (hole_offset, hole_rank, hole_amb) if t is not None] or [0]) if max_holes is None else int(max_holes)
+    p = lambda t: _ptr(t) if t is not None and t.numel() else None
+    _check(lib().nvbio_fasta_encode(FMIndex._dev_index(dev), p(text), nb, _ptr(temp), temp.numel(), ctypes.cast(state.data_ptr(), ctypes.POINTER(_FastaState)),
+                                    p(text2), words, p(seq_offset), p(name_index), seqs if seqs < (1 << 32) else 0, p(names),
+                                    size(names) if names_capacity is None else int(names_capacity), p(hole_offset), p(hole_rank), p(hole_amb), holes,
+                                    _ptr(status), _stream_ptr(dev)))
+
+
+def fasta_finish(state, seq_offset=None, name_index=None, hole_offset=None, hole_rank=None, hole_len=None, seq_n_ambs=None, max_seqs=None, max_holes=None):
+    """nvbio_fasta_finish: closes the tables behind the last chunk (entry n_seqs of both indices, the holes' lengths, n_ambs per sequence,
+    state.max_name_len).  No synchronisation."""
+    dev = state.device
+    seqs = (min(t.numel() for t in (seq_offset, name_index) if t is not None) - 1 if (seq_offset is not None or name_index is not None) else 0) \
+        if max_seqs is None else int(max_seqs)
+    holes = (min(t.numel() for t in (hole_offset, hole_rank) if t is not None) if (hole_offset is not None or hole_rank is not None) else 0) \
+        if max_holes is None else int(max_holes)
+    p = lambda t: _ptr(t) if t is not None and t.numel() else None
+    _check(lib().nvbio_fasta_finish(FMIndex._dev_index(dev), ctypes.cast(state.data_ptr(), ctypes.POINTER(_FastaState)), p(seq_offset), p(name_index), max(seqs, 0),
+                                    p(hole_offset), p(hole_rank), holes, p(hole_len), p(seq_n_ambs), _stream_ptr(dev)))
+
+
+class FastaReference:
+    """A parsed reference in HBM: text2 (int32 words, 2-bit big-endian: what FMIndex.build and the aligners take as the genome) and length;
+    sequence_index (int32 [n + 1]: where each sequence starts), names_data (uint8) with name_index (int32 [n + 1]); the holes -- runs of
+    one ambiguous byte, stored as draws -- as hole_offset, hole_len (int32) and hole_amb (uint8); seq_n_ambs (int32 [n]: holes that start
+    in each sequence); freq (the counts of the four stored symbols); state: the final nvbio_fasta_state as a dict; status (FASTA_STATUS_*
+    of the last chunk: INCOMPLETE means the input ended inside a header line)."""
+
+    def __init__(self, text2, sequence_index, names_data, name_index, hole_offset, hole_len, hole_amb, seq_n_ambs, state, status, device):
+        self.text2, self.sequence_index, self.names_data, self.name_index = text2, sequence_index, names_data, name_index
+        self.hole_offset, self.hole_len, self.hole_amb, self.seq_n_ambs = hole_offset, hole_len, hole_amb, seq_n_ambs
+        self.state, self.status, self.device = state, status, device
+        self.length, self.n_seqs, self.n_holes, self.freq, self.seed = state["n_symbols"], state["n_seqs"], state["n_holes"], state["freq"], state["seed"]
+        self._names = None
+
+    @property
+    def names(self):
+        """the sequence names as a list of bytes (one copy to the host, kept)"""
+        if self._names is None:
+            b, idx = self.names_data.cpu().numpy().tobytes(), u32(self.name_index)
+            self._names = [b[idx[i]:idx[i + 1]] for i in range(self.n_seqs)]
+        return self._names
+
+    @property
+    def holes(self):
+        """(offset, len, amb) as three numpy arrays: the BNTAmb table"""
+        return u32(self.hole_offset), u32(self.hole_len), self.hole_amb.cpu().numpy()
+
+    def sam_refs(self):
+        return SamRefs(self.names, u32(self.sequence_index).astype(np.int64), device=self.device)
+
+    def build_index(self, **build_opts):
+        """FMIndex.build over the text (kw: kmer_len, sa_int, table_flags, ...)"""
+        return FMIndex.build(self.text2, self.length, device=self.device, **build_opts)
+
+    def save(self, prefix):
+        """prefix.pac, prefix.ann and prefix.amb, byte for byte as nvBWT writes them (save_bpac, nvBWT/nvBWT.cu:243-287: 4 symbols a byte,
+        a 0 byte when length % 4 == 0, then the byte length % 4; save_bns, nvbio/basic/bnt.cpp:28-73: gi 0, anno "null", a name printed up
+        to its first NUL)"""
+        n = self.length
+        words = u32(self.text2)[:(n + 15) // 16]
+        pac = words.astype(">u4").tobytes()[:(n + 3) // 4] + (b"\0" if n % 4 == 0 else b"") + bytes([n % 4])
+        off, n_ambs = u32(self.sequence_index), u32(self.seq_n_ambs)
+        ann = [b"%d %d %d\n" % (n, self.n_seqs, self.seed)]
+        for i, name in enumerate(self.names):
+            ann.append(b"0 " + name.split(b"\0")[0] + b" null\n%d %d %d\n" % (off[i], off[i + 1] - off[i], n_ambs[i]))
+        amb = [b"%d %d %d\n" % (n, self.n_seqs, self.n_holes)]
+        amb += [b"%d %d " % (o, l) + bytes([a]) + b"\n" for o, l, a in zip(*self.holes)]
+        for ext, data in (("pac", pac), ("ann", b"".join(ann)), ("amb", b"".join(amb))):
+            with open(prefix + "." + ext, "wb") as f:
+                f.write(data)
+
+
+def _fasta_chunks(chunks, total_bytes, seed, device):
+    """an iterable of byte chunks through one state -> FastaReference.  text2 is sized from total_bytes (symbols <= bytes); the sequence,
+    name and hole arrays grow when a chunk's summary says so: one read of the summary per chunk."""
+    torch = _torch()
+    dev = torch.device(device)
+    state = fasta_state_init(seed, dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
+    text2 = i32((total_bytes + 15) // 16 + 4)
+    arr = dict(seq_offset=i32(65), name_index=i32(65), names=u8(1024), hole_offset=i32(64), hole_rank=i32(64), hole_amb=u8(64))
+    n_seqs = n_holes = n_names = 0
+    last = 0
+
+    def grow(keys, used, need):
+        size = arr[keys[0]].numel()
+        if need <= size:
+            return
+        for k in keys:
+            t = torch.empty(max(need, 2 * size), dtype=arr[k].dtype, device=dev)
+            t[:used] = arr[k][:used]
+            arr[k] = t
+
+    for chunk in chunks:
+        t = _fastq_text(chunk, dev)
+        summary_dev, temp = fasta_scan(t, state)
+        s = fasta_summary(summary_dev)
+        if s["status"] & FASTA_STATUS_OVERFLOW_32:
+            raise NvbioError(4, "FASTA input: the symbols or name bytes reach 2^32: coordinates are 32-bit")
+        grow(("seq_offset", "name_index"), n_seqs, n_seqs + s["n_seqs"] + 1)
+        grow(("names",), n_names, n_names + s["n_name_bytes"])
+        grow(("hole_offset", "hole_rank", "hole_amb"), n_holes, n_holes + s["n_holes"])
+        fasta_encode(t, temp, state, status, text2=text2, **arr)
+        n_seqs, n_holes, n_names, last = n_seqs + s["n_seqs"], n_holes + s["n_holes"], n_names + s["n_name_bytes"], s["status"]
+        if s["status"] & FASTA_STATUS_END_BYTE:
+            break
+    hole_len, seq_n_ambs = i32(max(n_holes, 1)), i32(max(n_seqs, 1))
+    fasta_finish(state, arr["seq_offset"], arr["name_index"], arr["hole_offset"], arr["hole_rank"], hole_len, seq_n_ambs)
+    st = fasta_state(state)
+    if int(status.item()) & FASTA_STATUS_CAPACITY:
+        raise NvbioError(1, "nvbio_fasta_encode: an item did not fit arrays sized from the summaries")
+    return FastaReference(text2[:(st["n_symbols"] + 15) // 16], arr["seq_offset"][:n_seqs + 1], arr["names"][:n_names], arr["name_index"][:n_seqs + 1],
+                          arr["hole_offset"][:n_holes], hole_len[:n_holes], arr["hole_amb"][:n_holes], seq_n_ambs[:n_seqs], st, last, dev)
+
+
+def parse_fasta(text, seed=11, device="cuda:0"):
+    """The bytes of a reference FASTA file (bytes, a numpy array or a uint8 device tensor, below 4 GiB) -> FastaReference:
+    FASTA_inc_reader::read and nvBWT's Writer (nvbio/fasta/fasta_inl.h:64-122, nvBWT/nvBWT.cu:102-195) on the device -- the grammar and its
+    departures are in include/nvbio_amd.h ("FASTA input")."""
+    n = text.numel() if hasattr(text, "numel") else len(text)
+    return _fasta_chunks([text], n, seed, device)
+
+
+def read_fasta(paths, chunk_bytes=64 << 20, seed=11, device="cuda:0"):
+    """One path or a list of paths, read in order in chunks of chunk_bytes through ONE state (a chunk may end anywhere: in a name, a hole,
+    a word) -> FastaReference.  Input that ends inside a header line is an NvbioError."""
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+
+    def chunks():
+        for path in paths:
+            with open(path, "rb") as f:
+                while True:
+                    data = f.read(chunk_bytes)
+                    if not data:
+                        break
+                    yield data
+
+    ref = _fasta_chunks(chunks(), sum(os.path.getsize(p) for p in paths), seed, device)
+    if ref.status & FASTA_STATUS_INCOMPLETE:
+        raise NvbioError(1, "%s: the input ends inside a header line" % paths[-1])
+    return ref
+
+
 # ---- the mirrors of the headers' structs: C name -> class (abi.bind types a pointer to one as POINTER(mirror); pipeline.py adds its own) -------
 _MIRRORS = {
     "nvbio_sam_refs": _SamRefs, "nvbio_sam_records": _SamRecords, "nvbio_fastq_params": _FastqParams, "nvbio_fastq_summary": _FastqSummary,
+    "nvbio_fasta_state": _FastaState, "nvbio_fasta_summary": _FastaSummary,
     "nvbio_fm_index_view": _View, "nvbio_fm_build_options": _BuildOptions, "nvbio_string_set": _StringSet, "nvbio_rank_dictionary": _RankDict,
     "nvbio_mem_params": _MemParams, "nvbio_qgram_index_view": _QGramView, "nvbio_qgroup_index_view": _QGroupView,
     "nvbio_sufsort_stats": _SufsortStats, "nvbio_hit_queues": _HitQueues, "nvbio_seed_hits_params": _SeedHitsParams,

@@ -26,13 +26,13 @@
 //                                  assembles whole words: a word inside the window's symbol range is a plain store, the word at either
 //                                  end, which a neighbouring read (or the next window of a long read) may share, an atomicOr
 // No workgroup waits on another inside a launch.  Offsets into the text are 32-bit: a text of 2^32 bytes or more is refused.
-#include "common.h"
+#include "byte_scan.h"
 #include <hipcub/hipcub.hpp>
 
 namespace nvbio_amd {
 
 enum : uint32_t { FQ_GAP = 0u, FQ_NAME = 1u, FQ_SEQ = 2u, FQ_PLUS = 3u, FQ_QUAL = 4u, FQ_ERR = 5u };
-static constexpr uint32_t FQ_TILE = 4096u;                     // bytes per workgroup: 256 lanes x 16
+static constexpr uint32_t FQ_TILE = BS_TILE;
 static constexpr uint32_t FQ_WIN  = 1024u;                     // symbols of a read staged in a wave's LDS at a time
 static constexpr uint32_t FQ_MIN_RECORD = 5u;                  // '@' and the four bytes that end its fields
 
@@ -64,14 +64,6 @@ __device__ __forceinline__ uint32_t fq_byte_fn(const uint32_t c)
     return c == '\n' ? FQ_NL : c == ' ' ? FQ_ID : c == '@' ? FQ_AT : c == '+' ? FQ_PL : c == 0u ? FQ_NUL : FQ_OTH;
 }
 __device__ __forceinline__ uint32_t fq_next(const uint32_t s, const uint32_t c) { return (fq_byte_fn( c ) >> (3u * s)) & 7u; }
-// f, then g
-__device__ __forceinline__ uint32_t fq_compose(const uint32_t f, const uint32_t g)
-{
-    uint32_t r = 0u;
-#pragma unroll
-    for (uint32_t s = 0u; s < 18u; s += 3u) r |= ((g >> (3u * ((f >> s) & 7u))) & 7u) << s;
-    return r;
-}
 __device__ __forceinline__ bool fq_is_graph(const uint32_t c) { return c >= 0x21u && c <= 0x7Eu; }
 __device__ __forceinline__ bool fq_ends_line(const uint32_t c) { return c == '\n' || c == 0u; }
 
@@ -83,37 +75,13 @@ __device__ __forceinline__ void fq_wave_sync()
 }
 
 // the 16 bytes of this lane: text[at, at + 16), spaces (the identity) behind the text
-__device__ __forceinline__ void fq_load16(const uint8_t* __restrict__ text, const uint32_t n, const uint64_t at, uint32_t w[4])
-{
-    if (at + 16u <= n) { const uint4 v = *(const uint4*)(text + at); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; return; }
-    w[0] = w[1] = w[2] = w[3] = 0x20202020u;
-    for (uint32_t k = 0u; k < 16u; ++k)
-        if (at + k < n) w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8u * (k & 3u)))) | ((uint32_t)text[at + k] << (8u * (k & 3u)));
-}
-__device__ __forceinline__ uint32_t fq_byte(const uint32_t w[4], const uint32_t k) { return (w[k >> 2] >> (8u * (k & 3u))) & 0xFFu; }
+__device__ __forceinline__ void fq_load16(const uint8_t* __restrict__ text, const uint32_t n, const uint64_t at, uint32_t w[4]) { bs_load16( text, n, at, 0x20202020u, w ); }
 __device__ __forceinline__ uint32_t fq_fn16(const uint32_t w[4])
 {
     uint32_t f = FQ_ID;
 #pragma unroll
-    for (uint32_t k = 0u; k < 16u; ++k) f = fq_compose( f, fq_byte_fn( fq_byte( w, k ) ) );
+    for (uint32_t k = 0u; k < 16u; ++k) f = bs_compose( f, fq_byte_fn( bs_byte( w, k ) ) );
     return f;
-}
-
-// a 256-lane workgroup's scan of the lanes' functions: returns the function of the lanes before this one, *total that of all of them
-__device__ __forceinline__ uint32_t fq_block_prefix(const uint32_t f, uint32_t* lds4, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = f;
-    for (uint32_t o = 1u; o < 64u; o <<= 1) { const uint32_t t = __shfl_up( inc, o, 64 ); if (lane >= o) inc = fq_compose( t, inc ); }
-    if (lane == 63u) lds4[wave] = inc;
-    __syncthreads();
-    uint32_t ex = __shfl_up( inc, 1, 64 );
-    if (lane == 0u) ex = FQ_ID;
-    uint32_t pre = FQ_ID, tot = FQ_ID;
-    for (uint32_t w = 0u; w < 4u; ++w) { const uint32_t t = lds4[w]; if (w < wave) pre = fq_compose( pre, t ); tot = fq_compose( tot, t ); }
-    *total = tot;
-    __syncthreads();
-    return fq_compose( pre, ex );
 }
 
 // ---- the function of every tile ----
@@ -123,7 +91,7 @@ fastq_tile_fn_kernel(const uint8_t* __restrict__ text, const uint32_t n, uint32_
     __shared__ uint32_t lds4[4];
     uint32_t w[4], total;
     fq_load16( text, n, (uint64_t)blockIdx.x * FQ_TILE + threadIdx.x * 16u, w );
-    (void)fq_block_prefix( fq_fn16( w ), lds4, &total );
+    (void)bs_block_prefix( fq_fn16( w ), lds4, &total );
     if (threadIdx.x == 0u) tile_fn[blockIdx.x] = total;
 }
 
@@ -133,25 +101,9 @@ __global__ void __launch_bounds__(1024)
 fastq_tile_scan_kernel(uint32_t* __restrict__ vals, const uint32_t n, uint32_t* __restrict__ total)
 {
     __shared__ uint32_t part[16];
-    auto op = [](const uint32_t a, const uint32_t b) -> uint32_t { return COMPOSE ? fq_compose( a, b ) : a + b; };
-    const uint32_t id = COMPOSE ? FQ_ID : 0u;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t chunk = (n + 1023u) / 1024u;
-    const uint64_t b64 = (uint64_t)tid * chunk;
-    const uint32_t b = b64 < n ? (uint32_t)b64 : n, e = n - b < chunk ? n : b + chunk;
-    uint32_t acc = id;
-    for (uint32_t i = b; i < e; ++i) acc = op( acc, vals[i] );
-    uint32_t inc = acc;
-    for (uint32_t o = 1u; o < 64u; o <<= 1) { const uint32_t t = __shfl_up( inc, o, 64 ); if (lane >= o) inc = op( t, inc ); }
-    if (lane == 63u) part[wave] = inc;
-    __syncthreads();
-    uint32_t ex = __shfl_up( inc, 1, 64 );
-    if (lane == 0u) ex = id;
-    uint32_t pre = id, tot = id;
-    for (uint32_t w = 0u; w < 16u; ++w) { const uint32_t t = part[w]; if (w < wave) pre = op( pre, t ); tot = op( tot, t ); }
-    uint32_t run = op( pre, ex );
-    for (uint32_t i = b; i < e; ++i) { const uint32_t x = vals[i]; vals[i] = run; run = op( run, x ); }
-    if (tid == 0u) *total = COMPOSE ? (tot & 7u) : tot;
+    const uint32_t tot = bs_scan_in_place( vals, n, COMPOSE ? BS_IDENTITY : 0u,
+                                           [](const uint32_t a, const uint32_t b) -> uint32_t { return COMPOSE ? bs_compose( a, b ) : a + b; }, part );
+    if (threadIdx.x == 0u) *total = COMPOSE ? (tot & 7u) : tot;
 }
 
 // ---- the walk over every byte with its state known.  EMIT = 0: tile_ends[tile] = the record ends in the tile.  EMIT = 1 (tile_ends
@@ -166,14 +118,14 @@ fastq_apply_kernel(const uint8_t* __restrict__ text, const uint32_t n, const uin
     const uint64_t at = (uint64_t)blockIdx.x * FQ_TILE + threadIdx.x * 16u;
     uint32_t w[4], total;
     fq_load16( text, n, at, w );
-    const uint32_t ex = fq_block_prefix( fq_fn16( w ), lds4, &total );
+    const uint32_t ex = bs_block_prefix( fq_fn16( w ), lds4, &total );
     const uint32_t s0 = (ex >> (3u * (tile_fn[blockIdx.x] & 7u))) & 7u;       // GAP through everything before the tile, then through the lanes before
 
     uint32_t s = s0, ends = 0u;
 #pragma unroll
     for (uint32_t k = 0u; k < 16u; ++k)
     {
-        const uint32_t c = fq_byte( w, k );
+        const uint32_t c = bs_byte( w, k );
         ends += (s == FQ_QUAL && fq_ends_line( c ) && at + k < n) ? 1u : 0u;
         s = fq_next( s, c );
     }
@@ -191,7 +143,7 @@ fastq_apply_kernel(const uint8_t* __restrict__ text, const uint32_t n, const uin
 #pragma unroll
     for (uint32_t k = 0u; k < 16u; ++k)
     {
-        const uint32_t c = fq_byte( w, k );
+        const uint32_t c = bs_byte( w, k );
         if (at + k < n)
         {
             const uint32_t p = (uint32_t)(at + k);

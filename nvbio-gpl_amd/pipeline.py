@@ -552,6 +552,14 @@ def fastq_to_sam(fmi, genome2, genome_len, fastq_text, params, refs, cigar_strid
     return align_to_sam(fmi, genome2, genome_len, batch.read_batch(), params, batch.names, refs, cigar_stride=cigar_stride, mds_stride=mds_stride) + (batch,)
 
 
+def reference_from_fasta(path, chunk_bytes=64 << 20, seed=11, device="cuda:0", **build_opts):
+    """A reference FASTA file (one path or a list) -> (fmi, genome2, genome_len, refs): what align_to_sam and fastq_to_sam take, made on
+    the device with no outside tool: read_fasta, then FMIndex.build over its text (build_opts: kmer_len, sa_int, table_flags, ...)"""
+    from . import read_fasta
+    ref = read_fasta(path, chunk_bytes=chunk_bytes, seed=seed, device=device)
+    return ref.build_index(**build_opts), ref.text2, ref.length, ref.sam_refs()
+
+
 def traceback_best(genome2, genome_len, reads, params, best_score, best_rc, best_wb, cigar_stride=32, timers=None,
                    best_pos=None):
     """nvBowtie's banded_traceback_best (traceback_inl.h:191-247) for the pipeline's best alignment per read:
