@@ -1065,6 +1065,18 @@ nvbio_status nvbio_all_traceback_flatten(int device, const uint32_t* rec_read_id
  * alignments of each mate while no pair has been found (reduce_inl.h:157-290).
  * An alignment is 4 int32: { score, position (-1 = none), sink offset, rc | mate << 1 | paired << 2 } (io::Alignment, alignments.h:71-117);
  * best_a_dev / best_o_dev hold two per read pair each (pipeline.best_alignments / best_alignments_o).  Reads of both mates are stored reversed.
+ * The sums and differences of score_inl.h:238-239 and :403-413 are uint32, as the reference's.  Where the calls depart from the reference:
+ *   - BestAnchorScoreStream::init_context tests `context->min_score > a_optimal_score` before it assigns min_score (score_inl.h:246 vs :249):
+ *     the uninitialised term is taken as false;
+ *   - an anchor hit that is skipped (its locus is held by one of the four alignments, with the same mate and strand) gets the window (0, 0)
+ *     and min_score = INT32_MAX; an anchor hit whose window begins at or past genome_len, or ends before it begins (a locus that wrapped below
+ *     zero), gets the window (0, 0) and keeps its min_score;
+ *   - an opposite job that cannot run -- min_score above the perfect score, a window that begins at or past genome_len, a locus already held,
+ *     begin == end, or end < begin after the uint32 arithmetic -- gets the window (0, 0) with its orientation and min_score as computed;
+ *     nvbio_pe_opposite_output takes win_end <= win_begin as "did not run" and reports worst_score, whatever the job's score slot holds,
+ *     and loc = win_begin, sink = win_begin + sink.x (a sink.x of 0xFFFFFFFF counts as 0): loc = sink = 0 for a job that
+ *     nvbio_pe_opposite_flatten emptied and the scorer left without a sink;
+ *   - nvbio_pe_init, like init_alignments, hands `mate` to the constructor argument that is `rc`: best_o starts with rc = 1, mate = 0.
  * ------------------------------------------------------------------------------------------- */
 typedef struct
 {

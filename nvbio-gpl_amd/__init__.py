@@ -1899,9 +1899,19 @@ class PeRaggedParams:
     """nvbio_pe_params as the ragged calls read it (the uniform lengths and scores stay 0: they are ignored) with nvBowtie's defaults"""
 
     def __init__(self, anchor, scheme, genome_len, band=31, policy=1, min_frag_len=0, max_frag_len=500, overlap=True, unpaired=True, max_effort=15,
-                 min_ext=30, max_ext=400):
-        self.c = _PeParams(anchor, 0, 0, 0, 0, 0, 0, -(1 << 30), -65536, scheme.c.match, scheme.c.txt_gap_open, scheme.c.txt_gap_ext, band, genome_len, policy,
+                 min_ext=30, max_ext=400, score_limit=-(1 << 30)):
+        self.c = _PeParams(anchor, 0, 0, 0, 0, 0, 0, score_limit, -65536, scheme.c.match, scheme.c.txt_gap_open, scheme.c.txt_gap_ext, band, genome_len, policy,
                            min_frag_len, max_frag_len, 1 if overlap else 0, 1 if unpaired else 0, max_effort, min_ext, max_ext)
+
+
+class PeParams(PeRaggedParams):
+    """nvbio_pe_params as the uniform calls read it: one length per mate, perfect_score( len ) = match * len and the two min scores"""
+
+    def __init__(self, anchor, scheme, genome_len, anchor_len, opposite_len, anchor_min_score, opposite_min_score, **kw):
+        super().__init__(anchor, scheme, genome_len, **kw)
+        self.c.anchor_len, self.c.opposite_len = anchor_len, opposite_len
+        self.c.anchor_perfect_score, self.c.opposite_perfect_score = scheme.c.match * anchor_len, scheme.c.match * opposite_len
+        self.c.anchor_min_score, self.c.opposite_min_score = anchor_min_score, opposite_min_score
 
 
 class PeRagged:
@@ -1940,6 +1950,48 @@ def pe_score_reduce_ragged(params, ragged, active, n_active, hits_first, hits_co
     _check(lib().nvbio_pe_score_reduce_ragged(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(ragged.c), _ptr(active), n_active,
                                               _ptr(hits_first), _ptr(hits_count), ctypes.byref(hq), _ptr(hit_oscore), _ptr(hit_oloc), _ptr(hit_osink),
                                               n_ext, _ptr(best_a), _ptr(best_o), _ptr(trys), _ptr(sizes), _stream_ptr(hits.device)))
+
+
+def pe_init(worst_score_mate1, worst_score_mate2, best_a, best_o):
+    """nvbio_pe_init: best_a / best_o int32 [R, 2, 4] = unaligned at the two mates' min scores"""
+    dev = best_a.device
+    _check(lib().nvbio_pe_init(FMIndex._dev_index(dev), best_a.shape[0], worst_score_mate1, worst_score_mate2, _ptr(best_a), _ptr(best_o), _stream_ptr(dev)))
+
+
+def pe_anchor_flatten(params, hits, best_a, best_o, read_id, flags, win_begin, win_end, min_scores):
+    """nvbio_pe_anchor_flatten: the per-job arrays of the anchor's banded DP (int32 [hits.n], flags uint8) and the hits' min scores"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_anchor_flatten(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(hq), _ptr(best_a), _ptr(best_o), _ptr(read_id),
+                                         _ptr(flags), _ptr(win_begin), _ptr(win_end), _ptr(min_scores), _stream_ptr(hits.device)))
+
+
+def pe_anchor_output(params, hits, scores, sinks, win_begin, min_scores, hit_oscore, valid):
+    """nvbio_pe_anchor_output (serves both forms): fills hits.score / hits.sink, hit_oscore int32 [hits.n] = worst_score, valid uint8 [hits.n]"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_anchor_output(FMIndex._dev_index(hits.device), ctypes.byref(params.c), ctypes.byref(hq), _ptr(scores), _ptr(sinks), _ptr(win_begin),
+                                        _ptr(min_scores), _ptr(hit_oscore), _ptr(valid), _stream_ptr(hits.device)))
+
+
+def pe_opposite_flatten(params, queue, n, hits, best_a, best_o, read_id, flags, win_begin, win_end, min_scores):
+    """nvbio_pe_opposite_flatten: the same for the opposite mate of the n hits of queue (those whose anchor passed)"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_opposite_flatten(FMIndex._dev_index(hits.device), ctypes.byref(params.c), _ptr(queue), n, ctypes.byref(hq), _ptr(best_a), _ptr(best_o),
+                                           _ptr(read_id), _ptr(flags), _ptr(win_begin), _ptr(win_end), _ptr(min_scores), _stream_ptr(hits.device)))
+
+
+def pe_opposite_output(params, queue, n, scores, sinks, win_begin, win_end, min_scores, hit_oscore, hit_oloc, hit_osink):
+    """nvbio_pe_opposite_output (serves both forms): the opposite score, window begin and sink of the hits queue names"""
+    dev = scores.device
+    _check(lib().nvbio_pe_opposite_output(FMIndex._dev_index(dev), ctypes.byref(params.c), _ptr(queue), n, _ptr(scores), _ptr(sinks), _ptr(win_begin),
+                                          _ptr(win_end), _ptr(min_scores), _ptr(hit_oscore), _ptr(hit_oloc), _ptr(hit_osink), _stream_ptr(dev)))
+
+
+def pe_score_reduce(params, active, n_active, hits_first, hits_count, hits, hit_oscore, hit_oloc, hit_osink, n_ext, best_a, best_o, trys, sizes):
+    """nvbio_pe_score_reduce: score_reduce_paired over every active read's hits"""
+    hq = hits.c_struct()
+    _check(lib().nvbio_pe_score_reduce(FMIndex._dev_index(hits.device), ctypes.byref(params.c), _ptr(active), n_active, _ptr(hits_first), _ptr(hits_count),
+                                       ctypes.byref(hq), _ptr(hit_oscore), _ptr(hit_oloc), _ptr(hit_osink), n_ext, _ptr(best_a), _ptr(best_o), _ptr(trys),
+                                       _ptr(sizes), _stream_ptr(hits.device)))
 
 
 # ---- nvBowtie's all-mapping mode (include/nvbio_amd.h: nvbio_all_*; host/nvbio_amd/all_mapping.hpp) ---------------------------------

@@ -14,7 +14,8 @@ Also here: the ragged pairs the CPU and GPU tests share, and the references over
 import numpy as np
 
 from best_approx_ragged_cpu import min_score_e2e, seed_tables, stored_stream  # noqa: F401  (stored_stream: for the GPU tests)
-from oracle.cpu_pipeline import SCORE_MIN, max_text_gaps
+import pe_steps_cpu as pe
+from oracle.cpu_pipeline import SCORE_MIN
 from util import mutate_reads
 
 FIXED_PAIRS = ((11, 100), (100, 21), (21, 11), (22, 150), (150, 22), (23, 23), (30, 250), (250, 30), (1023, 100), (100, 1023))
@@ -40,55 +41,19 @@ def best_approx_paired_ragged_cpu(O, hidx, text, genome_len, mates1, mates2, sch
                                   max_effort=15, max_effort_init=15, min_ext=30, max_ext=400, max_reseed=2, band=31, top_seed=0, batch_size=None, multi_hit=True,
                                   policy=1, min_frag=0, max_frag=500, overlap=True, unpaired=True):
     """mates1 / mates2: lists of uint8 arrays in their ORIGINAL orientation; tables[m] = (S [R], first [max_reseed + 1, R], filtered [R]) and
-    min_scores[m] [R] of mate m: seed_tables and the worst scores of its lengths.  Alignment = [score, pos, sink, rc, mate, paired]."""
+    min_scores[m] [R] of mate m: seed_tables and the worst scores of its lengths.  Alignment = (score, pos, sink, rc, mate, paired).
+    Every step of a pass -- thresholds, windows, outputs, the reduction -- is pe_steps_cpu's; this function is the loop around them."""
     R, L = len(mates1), seed_len
     reads = (mates1, mates2)
     lens = ([len(r) for r in mates1], [len(r) for r in mates2])
     BATCH = batch_size or R
     max_effort_init = max(max_effort_init, max_effort); max_ext = max(max_ext, max_effort)
-    NONE = 0xFFFFFFFF
-    best_a = [[[int(min_scores[0][r]), NONE, 255, 0, 0, 0], [int(min_scores[0][r]), NONE, 255, 0, 0, 0]] for r in range(R)]
-    best_o = [[[int(min_scores[1][r]), NONE, 255, 1, 0, 0], [int(min_scores[1][r]), NONE, 255, 1, 0, 0]] for r in range(R)]
+    init = [pe.init(int(min_scores[0][r]), int(min_scores[1][r])) for r in range(R)]
+    best_a, best_o = [i[0] for i in init], [i[1] for i in init]
     empty = np.zeros((0, 2), dtype=np.uint32)
-
-    def paired(a): return a[5] == 1 and a[1] != NONE
-    def best_score(b): return b[0][0] + (b[2][0] if paired(b[0]) else 0)
-    def second_score(b): return b[1][0] + (b[3][0] if paired(b[1]) else 0)
-
-    def target_score(b, aw, ow):
-        if not paired(b[1]):
-            return aw + ow
-        delta = best_score(b) - second_score(b)
-        return second_score(b) + int(delta * 3 / 4) if delta * 3 >= 0 else second_score(b) - ((-delta * 3) // 4)      # C division truncates toward zero
-
-    def visited(b, mate, rc, g):
-        return any(mate == x[4] and rc == x[3] and g == x[1] for x in b)
-
-    def frame(anchor, anchor_fw):
-        a1 = anchor == 0
-        if policy == 0: return (a1 != anchor_fw), anchor_fw
-        if policy == 3: return (a1 == anchor_fw), anchor_fw
-        if policy == 1: return (not anchor_fw), (not anchor_fw)
-        return anchor_fw, (not anchor_fw)
 
     def oriented(read, rc):
         return (np.where(read[::-1] < 4, 3 - read[::-1], read[::-1]) if rc else read).astype(np.uint8)
-
-    def pair_mate(a, o, m): return a if m == a[4] else o
-
-    def pairs_distinct(a1, o1, a2, o2, dist=None):
-        p10, p11, p20, p21 = pair_mate(a1, o1, 0), pair_mate(a1, o1, 1), pair_mate(a2, o2, 0), pair_mate(a2, o2, 1)
-        u = lambda v: v & 0xFFFFFFFF
-        ap1, op1, ap2, op2 = u(p10[1] + p10[2]), u(p11[1] + p11[2]), u(p20[1] + p20[2]), u(p21[1] + p21[2])
-        if dist is None:
-            return p10[3] != p20[3] or p11[3] != p21[3] or ap1 != ap2 or op1 != op2
-        if p10[3] != p20[3] or p11[3] != p21[3]:
-            return True
-        near = lambda x, y: x >= y - min(y, dist) and x <= y + dist
-        return not (near(ap1, ap2) and near(op1, op2))
-
-    def distinct(pos1, rc1, pos2, rc2, dist):
-        return True if rc1 != rc2 else not (pos1 >= pos2 - min(pos2, dist) and pos1 <= pos2 + dist)
 
     n_extensions = n_opposite = passes = multi_passes = 0
     for anchor in (0, 1):
@@ -96,6 +61,8 @@ def best_approx_paired_ragged_cpu(O, hidx, text, genome_len, mates1, mates2, sch
         a_lens, o_lens = lens[anchor], lens[1 - anchor]
         a_min, o_min = min_scores[anchor], min_scores[1 - anchor]
         S, first, filtered = tables[anchor]
+        prm = pe.Params(anchor, SCORE_MIN, pe.WORST_SCORE, scheme.match, scheme.txt_gap_open, scheme.txt_gap_ext, band, genome_len, policy, min_frag, max_frag,
+                        1 if overlap else 0, 1 if unpaired else 0, max_effort, min_ext, max_ext)
         queue = list(range(R))
         for seeding_pass in range(max_reseed + 1):
             if not queue:
@@ -155,109 +122,25 @@ def best_approx_paired_ragged_cpu(O, hidx, text, genome_len, mates1, mates2, sch
                         pos = int(O.locate_batch(hidx, np.array([row], dtype=np.uint32))[0])
                         g = (pos - (seed & 0xFFF)) & 0xFFFFFFFF
                         rc = (seed >> 13) & 1
-                        tp = target_score(bb, a_worst, o_worst)
-                        tm = max(tp - o_opt, a_worst)
-                        skip = visited(bb, anchor, rc, g)
-                        begin = g - band // 2 if g > band // 2 else 0
-                        end = min((begin + band + M) & 0xFFFFFFFF, genome_len)
-                        ms = max(tm + 1, SCORE_MIN)
+                        _, begin, end, ms = pe.anchor_flatten(prm, bb, rc, g, M, a_worst, o_worst, o_opt)
                         s1, sink1 = SCORE_MIN, 0xFFFFFFFF
-                        if not skip and begin < genome_len and end > begin:
+                        if end > begin:
                             _, s1, k1 = O.banded_gotoh(band, aln_type, scheme, oriented(a_reads[r], rc), text[begin:end])
                             sink1 = k1[0]
-                        passed = (not skip) and s1 >= ms
-                        hit_score = s1 if passed else -65536
-                        hit_sink = (begin + sink1) & 0xFFFFFFFF if not (skip or begin >= genome_len or end < begin) else 0xFFFFFFFF
-                        o_score, o_loc, o_sink = -65536, 0, 0
-                        if passed and hit_score != -65536:
+                        hit_score, hit_sink, o_score, valid = pe.anchor_output(int(s1), int(sink1), begin, ms, pe.WORST_SCORE)
+                        o_loc = o_sink = 0
+                        if valid:
                             n_opposite += 1
-                            tm2 = max(tp - hit_score, o_worst)
-                            ms2 = max(tm2 + 1, SCORE_MIN)
-                            run = not (ms2 > o_opt)
-                            o_left, o_fw = frame(anchor, rc == 0)
-                            gaps = max_text_gaps(scheme, ms2, Mo)
-                            gaps = gaps - (1 << 32) if gaps >= (1 << 31) else gaps
-                            og = (Mo + gaps) & 0xFFFFFFFF
-                            if o_left:
-                                max_end = g + M + og - min_frag if g + M + og > min_frag else 0
-                                obeg = g + M - max_frag if g + M > max_frag else 0
-                                oend = g + M if overlap else g
-                                oend = min(oend, max_end)
-                            else:
-                                min_begin = g + min_frag - og if g + min_frag > og else 0
-                                oend = g + max_frag
-                                obeg = g if overlap else g + M
-                                obeg = max(obeg, min_begin)
-                            oend = min(oend, genome_len)
-                            if obeg >= genome_len:
-                                run = False
-                            o_rc = 0 if o_fw else 1
-                            if visited(bb, 1 - anchor, o_rc, g) or obeg == oend or oend < obeg:
-                                run = False
-                            o_loc = obeg if run else 0
-                            o_sink = o_loc
-                            if run:
-                                _, s2, k2 = O.full_gotoh(aln_type, 0, scheme, oriented(o_reads[r], o_rc), text[obeg:oend], None, ms2)
-                                if s2 >= ms2:
-                                    o_score = s2
-                                o_sink = (obeg + (k2[0] if k2[0] != 0xFFFFFFFF else 0)) & 0xFFFFFFFF
+                            o_flags, obeg, oend, ms2, why = pe.opposite_flatten(prm, bb, rc, g, hit_score, M, Mo, a_worst, o_worst, o_opt)
+                            s2, k2 = SCORE_MIN, (0xFFFFFFFF, 0xFFFFFFFF)
+                            if why is None:
+                                _, s2, k2 = O.full_gotoh(aln_type, 0, scheme, oriented(o_reads[r], 1 if o_flags == pe.READ_COMPLEMENT else 0), text[obeg:oend], None, ms2)
+                            o_score, o_loc, o_sink = pe.opposite_output(int(s2), int(k2[0]), obeg, oend, ms2, pe.WORST_SCORE)
                         rows.append((g, hit_sink, hit_score, o_score, o_loc, o_sink, rc, (seed >> 14) & 1))
                     scored.append(rows)
                 # score_reduce_paired
                 for (r, top, hits), rows in zip(out, scored):
-                    dist = a_lens[r] // 2
-                    a1, a2, o1, o2 = [list(x) for x in (best_a[r][0], best_a[r][1], best_o[r][0], best_o[r][1])]
-                    m = [list(a1), list(a2), list(o1), list(o2)]              # what has been written to memory
-                    tr = trys[r]; erase = False
-
-                    def failure(idx, top_flag):
-                        nonlocal tr
-                        if tr > 0:
-                            if n_ext + idx >= min_ext and top_flag == 0:
-                                tr -= 1
-                                if tr == 0:
-                                    return True
-                            if n_ext + idx >= max_ext:
-                                return True
-                        return False
-
-                    for idx, (gx, gy, s1, s2, ox, oy, rc, top_flag) in enumerate(rows):
-                        score = s1 + s2
-                        o_left, o_fw = frame(anchor, rc == 0)
-                        o_rc = 0 if o_fw else 1
-                        pa = [s1, gx, (gy - gx) & 0xFFFFFFFF, rc, anchor, 1]
-                        po = [s2, ox, (oy - ox) & 0xFFFFFFFF, o_rc, 1 - anchor, 1]
-                        bl = [a1, a2, o1, o2]
-                        if (not pairs_distinct(a1, o1, pa, po)) or (not pairs_distinct(a2, o2, pa, po)):
-                            continue
-                        if score > best_score(bl):
-                            tr = max_effort
-                            a2, o2 = a1, o1; a1, o1 = pa, po
-                            m = [list(a1), list(a2), list(o1), list(o2)]
-                        elif score > second_score(bl) and pairs_distinct(a1, o1, pa, po, dist):
-                            tr = max_effort
-                            a2, o2 = pa, po
-                            m = [list(a1), list(a2), list(o1), list(o2)]
-                        elif unpaired and not paired(a1):
-                            m1 = a1 if anchor == a1[4] else o1
-                            m2 = a2 if anchor == a2[4] else o2
-                            m1, m2 = list(m1), list(m2)
-                            wrote = False
-                            if s1 > m1[0]:
-                                m2 = m1; m1 = [s1, gx, (gy - gx) & 0xFFFFFFFF, rc, anchor, 0]; wrote = True
-                            elif s1 > m2[0] and distinct(m1[1], m1[3], gx, rc, dist):
-                                m2 = [s1, gx, (gy - gx) & 0xFFFFFFFF, rc, anchor, 0]; wrote = True
-                            elif failure(idx, top_flag):
-                                erase = True
-                            if wrote:
-                                if anchor:
-                                    m[2], m[3] = list(m1), list(m2)
-                                else:
-                                    m[0], m[1] = list(m1), list(m2)
-                        elif failure(idx, top_flag):
-                            erase = True
-                    best_a[r] = [m[0], m[1]]; best_o[r] = [m[2], m[3]]
-                    trys[r] = tr
+                    best_a[r], best_o[r], trys[r], erase, _ = pe.reduce_read(prm, [best_a[r][0], best_a[r][1], best_o[r][0], best_o[r][1]], trys[r], rows, a_lens[r], n_ext)
                     if erase:
                         deques[r] = deques[r][:0]
                     n_extensions += len(rows)
@@ -359,13 +242,26 @@ def tables_of(m1, m2):
     return [seed_tables(l) for l in lens], [np.array([min_score_e2e(M) for M in l], dtype=np.int32) for l in lens]
 
 
-def restatement(O, mode, batch_size, multi_hit, which="shared", max_frag=500):
-    """best_approx_paired_ragged_cpu over the shared (or the long) input in one mode and setting, computed once per process"""
+def min_score_local(M):
+    """nvBowtie's local threshold int( 10 ln M ) in float32 (MinScoreFunc, scoring.h:117-129), as pipeline.SeedExtendParams.min_score_for"""
+    import math
+    return int(np.float32(0.0) + np.float32(10.0) * np.float32(math.log(np.float32(M))))
+
+
+def restatement(O, mode, batch_size, multi_hit, which="shared", max_frag=500, local=False, pairs=None):
+    """best_approx_paired_ragged_cpu over the shared (or the long) input in one mode and setting, computed once per process.  local: nvBowtie's local
+    scheme (match 2), LOCAL alignment and the thresholds int( 10 ln M ) instead of the end-to-end ones; pairs: a slice of the input"""
     import oracle
-    key = ("want", mode, batch_size, multi_hit, which, max_frag)
+    key = ("want", mode, batch_size, multi_hit, which, max_frag, local, None if pairs is None else (pairs.start, pairs.stop))
     if key not in _SHARED:
         text, hidx, m1, m2 = shared_input(O, mode == "no_unpaired_ff") if which == "shared" else long_input(O)
+        if pairs is not None:
+            m1, m2 = m1[pairs], m2[pairs]
         tables, min_scores = tables_of(m1, m2)
-        _SHARED[key] = best_approx_paired_ragged_cpu(O, hidx, text, len(text), m1, m2, oracle.Scheme(0, 6, 6, -8, -3, -8, -3), oracle.SEMI_GLOBAL, tables, min_scores,
+        scheme, aln_type = oracle.Scheme(0, 6, 6, -8, -3, -8, -3), oracle.SEMI_GLOBAL
+        if local:
+            scheme, aln_type = oracle.Scheme(2, 2, 6, -8, -3, -8, -3), oracle.LOCAL
+            min_scores = [np.array([min_score_local(len(r)) for r in m], dtype=np.int32) for m in (m1, m2)]
+        _SHARED[key] = best_approx_paired_ragged_cpu(O, hidx, text, len(text), m1, m2, scheme, aln_type, tables, min_scores,
                                                      batch_size=batch_size or None, multi_hit=multi_hit, **pe_kw(mode, max_frag), **KW[mode])
     return _SHARED[key]

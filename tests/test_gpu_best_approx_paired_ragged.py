@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
-from best_approx_paired_ragged_cpu import KW, MODES, SETTINGS, genome_and_index, long_input, make_pairs, pe_kw, restatement, shared_input, stored_stream
+from best_approx_paired_ragged_cpu import KW, MODES, PLAIN, SETTINGS, genome_and_index, long_input, make_pairs, pe_kw, restatement, shared_input, stored_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -102,6 +102,23 @@ def test_ragged_pairs_equal_the_restatement(amd, orc, device_genome, mode):
         assert int(tbh["begin%d" % k][r]) == ob + src_[0] and int(tbh["rc%d" % k][r]) == o_rc, (mode, r, "opposite begin")
         n = int(tbh["cigar_lens%d" % k][r])
         assert n == len(cig_) and np.array_equal(tbh["cigars%d" % k][r, :n].view(np.uint16), cig_), (mode, r, "opposite cigar")
+
+
+def test_ragged_pairs_in_local_mode_equal_the_restatement(amd, orc, device_genome):
+    """nvBowtie's local mode -- match 2, LOCAL alignment, thresholds int( 10 ln M ) -- over 60 ragged pairs: the perfect-score terms (match * o_len in
+    both targets, `min_score > o_opt`, max_text_gaps' start) are live; the same arrays and counters as the end-to-end test"""
+    pipeline, fmi, g_dev, G = device_genome
+    pairs = slice(PLAIN.start, PLAIN.start + 60)
+    _, _, m1, m2 = shared_input(orc, False)
+    rb = [ragged_batch(pipeline, orc, m[pairs]) for m in (m1, m2)]
+    params = pipeline.SeedExtendParams()
+    assert params.scheme.c.match == 2 and params.aln_type == amd.LOCAL and params.min_score_for(100) == 46
+    pe, unpaired = pe_params(amd, pipeline, "default")
+    got = pipeline.nvbowtie_best_approx_paired_host(fmi, g_dev, G, rb[0], rb[1], params, pipeline.NvBowtieParams(**KW["default"]), pe, unpaired=unpaired)
+    want = restatement(orc, "default", 0, True, local=True, pairs=pairs)
+    same(got, want, ("local",))
+    a = want["best_a"]
+    assert ((a[:, 0, 5] == 1) & (a[:, 0, 1] != 0xFFFFFFFF)).sum() > 40 and (a[:, 0, 0] > 0).all()
 
 
 def test_long_mates_pair_under_a_longer_fragment_limit(amd, orc, device_genome):
