@@ -1688,6 +1688,96 @@ nvbio_status nvbio_sam_format(int device, const nvbio_sam_refs* refs, const nvbi
                               uint8_t* text_dev, uint64_t text_capacity, uint32_t* n_skipped_dev, uint32_t* status_dev, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * BAM output: the same alignment records in BAM's binary form, and the BGZF container around them, both made on the device
+ * (io::BamOutput, nvbio/io/output/output_bam.cpp:65-93,140-225,227-544; BGZF framing nvbio/io/output/output_gzip.cpp:29-42,118-134).
+ * The records are a pure function of the nvbio_sam_refs / nvbio_sam_records arrays the SAM calls read, in the same three steps:
+ *   1. nvbio_bam_record_offsets   the byte length of every record (its block_size word included) and their exclusive uint64 scan
+ *   2. the caller reads offsets_dev[n], the total, and allocates the data (16-byte aligned)
+ *   3. nvbio_bam_format           writes record i to data_dev[offsets[i], offsets[i + 1])
+ *   4. nvbio_bgzf_frame           wraps any byte string into BGZF blocks: a gzip header, a DEFLATE stream of ONE STORED block
+ *                                 (BTYPE 00: uncompressed BAM, what `samtools view -u` writes), CRC-32 and length
+ * A file is bam_header (host: nvbio_amd/bam.hpp, pipeline.bam_header) framed on its own, the framed records, and the 28-byte EOF block
+ * (:657-659); the caller writes the EOF block.  Compression on the device is not offered: the framing call takes the payload as it is.
+ * A group of 16 lanes composes one record in LDS (four records to a wave) and copies it out with 16-byte stores (bytes only at the
+ * unaligned head and tail), so a record is bounded by the LDS of a group.  The bound is taken from the declared maxima:
+ *   max_name_len + 4 * cigar_stride + max_read_len + (max_read_len + 1) / 2 + (2 * mds_stride + 16) + 72   bytes of record
+ *   (36 block_size and fixed fields, the name's NUL, 30 of NM AS XS XM XO XG, 4 of the MD tag's name, type and NUL; an MDS byte prints
+ *   at most 1.5 characters; the term in brackets is 0 without mds_dev), plus 16 and mds_stride rounded up to 16, must not exceed
+ *   16384: else NVBIO_ERR_UNSUPPORTED, before any launch.  So are max_name_len > 254 (l_read_name is one byte and counts the NUL) and
+ *   cigar_stride > 65535 (n_cigar_op has 16 bits).
+ * Divergences from the reference:
+ *   1. generate_md_string sums a run of merged match tokens in a uint8; here the sum has 32 bits (as in the SAM calls)
+ *   2. next_refID is the mate's sequence index; the reference writes the difference o_seq_index - seq_index (:419), which puts every
+ *      mate of a pair on one sequence at refID 0 and is not BAM
+ *   3. NVBIO_BAM_REG2BIN is an extension, off by default: the reference leaves bin at 0 (:393-394)
+ * ------------------------------------------------------------------------------------------- */
+#define NVBIO_BAM_LENGTHS_ONLY 1u       /* nvbio_bam_record_offsets only: stop before the scan; offsets_dev[i] = the bytes of record i, [n] = 0    */
+#define NVBIO_BAM_REG2BIN      2u       /* both calls: bin = the SAM specification's reg2bin( pos, pos + reference span ) instead of the reference's 0;
+                                           4680 for a record written as unmapped                                                            */
+
+/* *status_dev bits of nvbio_bam_format */
+#define NVBIO_BAM_STATUS_CAPACITY 1u   /* a record would end past data_capacity: it was not written                                        */
+#define NVBIO_BAM_STATUS_OFFSETS  2u   /* offsets_dev is not what nvbio_bam_record_offsets gives for these records and flags: not written  */
+#define NVBIO_BAM_STATUS_TOO_LONG 4u   /* a record is longer than the declared maxima allow: it was not written                            */
+
+/* the bytes of temp_dev nvbio_bam_record_offsets needs for n records (the scan's; rocPRIM) */
+nvbio_status nvbio_bam_format_temp_bytes(uint32_t n, uint64_t* bytes);
+
+/* process_one_alignment and output_alignment (output_bam.cpp:227-544) as far as they decide a record's LENGTH: offsets_dev[n + 1] = the
+ * exclusive uint64 scan of the records' bytes, offsets_dev[n] the total.  A record the reference does not write -- an aligned read whose
+ * CIGAR was truncated or whose non-D lengths do not sum to the read's length (:399-405) -- takes no bytes: exactly the records
+ * nvbio_sam_format skips.  flags: NVBIO_BAM_LENGTHS_ONLY, NVBIO_BAM_REG2BIN (which changes no length).  No host synchronisation; n = 0
+ * writes offsets_dev[0] = 0. */
+nvbio_status nvbio_bam_record_offsets(int device, const nvbio_sam_refs* refs, const nvbio_sam_records* records, uint32_t flags, uint64_t* offsets_dev,
+                                      void* temp_dev, uint64_t temp_bytes, void* stream);
+
+/* The same functions for the BYTES, little-endian (output_bam.cpp:227-544; generate_cigar :65-93; generate_md_string :140-213; encode_bp
+ * :216-225): record i goes to data_dev[offsets_dev[i], offsets_dev[i + 1]); data_dev must be 16-byte aligned.  flags: 0 or NVBIO_BAM_REG2BIN.
+ *   framing (:495-544)        block_size (int32: the bytes after it), refID, pos, bin_mq_nl, flag_nc, l_seq, next_refID, next_pos, tlen,
+ *                             QNAME + NUL, CIGAR, SEQ, QUAL, tags
+ *   not aligned (:330-343)    refID = pos = next_refID = next_pos = -1, tlen = 0, bin_mq_nl = l_read_name alone, flag_nc = 4 << 16 exactly
+ *                             (in paired mode too), no CIGAR, no tags
+ *   aligned (:346-394)        flags as nvbio_sam_format: 64 | 128 (bit 2), 16 (rc); with a mate 1, 2 (the MATE is paired), 8, 32; refID / pos
+ *                             from upper_bound( sequence_index, pos ) - 1, 0-based; bin_mq_nl = l_read_name | mapq << 8, bin 0
+ *   ends past its sequence    (:370-385) 4 ORed into the flags, the others kept; the four reference fields -1, tlen 0, n_cigar_op 0, no MAPQ
+ *                             (the reference ORs it in later), no tags
+ *   CIGAR (:65-93)            elements from last to first, len << 4 | op with M I D S -> 0 1 2 4
+ *   SEQ (:254-291)            the orientation nvbio_sam_format prints (both values of reads_reversed); stored symbol s -> 1 << s, any s > 3
+ *                             -> 15, complemented first when rc (s < 4 -> 3 - s); high nibble first, the low nibble of an odd tail 0
+ *   QUAL (:294-306)           the raw bytes (no + 33), same orientation; quals_dev == NULL writes 0xFF bytes (the BAM specification's
+ *                             "absent"; an extension: the reference always has qualities)
+ *   mate fields (:407-451)    mate aligned: next_refID its sequence (divergence 2), next_pos 0-based within it, tlen as in SAM (0 across
+ *                             sequences, negated when the mate starts first; a mate whose CIGAR was truncated spans no reference symbols);
+ *                             mate not aligned: next_refID = refID, next_pos = pos, tlen = 0; single-end: -1, -1, 0
+ *   tags (:520-534)           NM c (the low 8 bits of ed), AS i, XS i only with a second score, XM XO XG c (the low 8 bits), MD Z + NUL only
+ *                             when the MD string is not empty; string and counts as in nvbio_sam_format (a stream of at most 2 bytes, or
+ *                             mds_dev == NULL: empty, zero counts).  The one-byte tag types are the reference's
+ * *n_skipped_dev (device) = the records that took no bytes.  Checked on the device: a record that would end past data_capacity, whose
+ * offsets are not its own, or that outgrows the declared maxima is not written at all and its NVBIO_BAM_STATUS_* bit is ORed into
+ * *status_dev (a device word the caller zeroed; never cleared here).  Nothing is written past min( data_capacity, offsets_dev[n] ).
+ * No host synchronisation. */
+nvbio_status nvbio_bam_format(int device, const nvbio_sam_refs* refs, const nvbio_sam_records* records, uint32_t flags, const uint64_t* offsets_dev,
+                              uint8_t* data_dev, uint64_t data_capacity, uint32_t* n_skipped_dev, uint32_t* status_dev, void* stream);
+
+#define NVBIO_BGZF_BLOCK_BYTES 65280u   /* the payload of a full block (htslib's 0xff00)                                                    */
+#define NVBIO_BGZF_OVERHEAD    31u      /* 18 of gzip header + 5 of stored-block header + 8 of trailer                                     */
+
+/* host arithmetic only: *framed_bytes = n_bytes + 31 * ceil( n_bytes / 65280 ) */
+nvbio_status nvbio_bgzf_framed_bytes(uint64_t n_bytes, uint64_t* framed_bytes);
+
+/* BGZF framing on the device: block b covers data_dev[65280 b, min( 65280 (b + 1), n_bytes )) and lands at out_dev + 65311 b:
+ *   1f 8b 08 04 | mtime 0 (4 bytes) | xfl 00 | os ff | xlen 06 00 | 'B' 'C' 02 00 BSIZE (uint16: the block's bytes - 1)     18 bytes, the gzip
+ *                                                                       fields as GzipCompressor sets them (output_gzip.cpp:29-42,118-134)
+ *   01 LEN NLEN (uint16 each)                                         one final stored DEFLATE block
+ *   the payload
+ *   CRC32 (zlib's: polynomial 0xEDB88320, of the payload) ISIZE (uint32 each)
+ * One workgroup per block copies the payload with 16-byte loads and stores and computes its CRC-32 in the same pass, with no atomics.
+ * data_dev and out_dev must be 16-byte aligned and must not overlap; out_capacity below nvbio_bgzf_framed_bytes( n_bytes ) is refused
+ * on the host (NVBIO_ERR_INVALID); nothing is written past the framed bytes.  n_bytes = 0 writes nothing: the EOF block is the caller's.
+ * No host synchronisation. */
+nvbio_status nvbio_bgzf_frame(int device, const uint8_t* data_dev, uint64_t n_bytes, uint8_t* out_dev, uint64_t out_capacity, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * FASTQ input: the bytes of a FASTQ file parsed on the device into an io::SequenceData<DNA_N>-shaped batch -- 4-bit big-endian words, a
  * sequence index, one quality byte per symbol, names with a name index: the arrays nvbio_sam_records and the read batches take.  The
  * reference parses on the host one byte at a time (SequenceDataFile_FASTQ_parser::nextChunk, nvbio/io/sequence/sequence_fastq.cpp:39-203)

@@ -2306,6 +2306,72 @@ def sam_records(refs, records, flags=0):
     return text, offsets, n_skipped
 
 
+# ---- BAM output ------------------------------------------------------------------------------------------------------------------
+BAM_STATUS_CAPACITY, BAM_STATUS_OFFSETS, BAM_STATUS_TOO_LONG = 1, 2, 4
+BAM_LENGTHS_ONLY = 1                                                     # bam_record_offsets: the lengths, not scanned
+BAM_REG2BIN = 2                                                          # bin = reg2bin(pos, pos + reference span) instead of the reference's 0
+BGZF_BLOCK_BYTES, BGZF_OVERHEAD = 65280, 31
+BGZF_EOF = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0])   # output_bam.cpp:657-659
+
+
+def bam_record_offsets(refs, records, flags=0):
+    """nvbio_bam_record_offsets -> offsets int64 [n + 1] on the device: the exclusive scan of the records' bytes, [n] the total"""
+    torch = _torch()
+    dev = records.device
+    offsets = torch.empty(records.n + 1, dtype=torch.int64, device=dev)
+    tmp, nb = _temp_for(lib().nvbio_bam_format_temp_bytes, records.n, device=dev)
+    rs, cs = refs.c_struct(), records.c_struct()
+    _check(lib().nvbio_bam_record_offsets(FMIndex._dev_index(dev), ctypes.byref(rs), ctypes.byref(cs), flags, _ptr(offsets), _ptr(tmp), nb, _stream_ptr(dev)))
+    return offsets
+
+
+def bam_format(refs, records, offsets, data, flags=0):
+    """nvbio_bam_format into `data` (a uint8 device tensor) -> (n_skipped, status): one host synchronisation"""
+    torch = _torch()
+    dev = records.device
+    words = torch.zeros(2, dtype=torch.int32, device=dev)                  # n_skipped | status
+    rs, cs = refs.c_struct(), records.c_struct()
+    _check(lib().nvbio_bam_format(FMIndex._dev_index(dev), ctypes.byref(rs), ctypes.byref(cs), flags, _ptr(offsets), _ptr(data), data.numel(),
+                                  ctypes.c_void_p(words.data_ptr()), ctypes.c_void_p(words.data_ptr() + 4), _stream_ptr(dev)))
+    n_skipped, status = (int(v) for v in words.cpu().numpy())
+    return n_skipped, status
+
+
+def bam_records(refs, records, flags=0):
+    """The BAM records of a batch (io::BamOutput, output_bam.cpp:227-544), made on the device: offsets, one read of the total, the bytes
+    -> (data uint8 tensor [offsets[n]], offsets int64 tensor [n + 1], n_skipped); record i is data[offsets[i] : offsets[i + 1]], its
+    block_size word first, empty for a record that is skipped (a truncated or inconsistent CIGAR).  flags: 0 or BAM_REG2BIN."""
+    torch = _torch()
+    offsets = bam_record_offsets(refs, records, flags)
+    total = int(offsets[-1].item())
+    data = torch.empty(total, dtype=torch.uint8, device=records.device)
+    n_skipped, status = bam_format(refs, records, offsets, data, flags)
+    if status:
+        raise NvbioError(1, "nvbio_bam_format: status %d (NVBIO_BAM_STATUS_*)" % status)
+    return data, offsets, n_skipped
+
+
+def bgzf_framed_bytes(n):
+    """nvbio_bgzf_framed_bytes: n + 31 for every block of at most 65280 bytes"""
+    b = ctypes.c_uint64(0)
+    _check(lib().nvbio_bgzf_framed_bytes(int(n), ctypes.byref(b)))
+    return int(b.value)
+
+
+def bgzf_frame(data):
+    """nvbio_bgzf_frame: a uint8 device tensor (16-byte aligned; numpy arrays and bytes are uploaded to cuda:0) as BGZF blocks of stored
+    DEFLATE blocks, each with its CRC-32 -> uint8 tensor [bgzf_framed_bytes(n)] on the same device; the EOF block (BGZF_EOF) is the caller's"""
+    torch = _torch()
+    if not isinstance(data, torch.Tensor):
+        data = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to("cuda:0")
+    data = data.contiguous()
+    if data.data_ptr() & 15:
+        data = data.clone()
+    out = torch.empty(bgzf_framed_bytes(data.numel()), dtype=torch.uint8, device=data.device)
+    _check(lib().nvbio_bgzf_frame(FMIndex._dev_index(data.device), _ptr(data), data.numel(), _ptr(out), out.numel(), _stream_ptr(data.device)))
+    return out
+
+
 # ---- FASTQ input -----------------------------------------------------------------------------------------------------------------
 FASTQ_PHRED, FASTQ_PHRED33, FASTQ_PHRED64, FASTQ_SOLEXA = 0, 1, 2, 3
 FASTQ_NO_OP, FASTQ_REVERSE_OP, FASTQ_COMPLEMENT_OP, FASTQ_REVERSE_COMPLEMENT_OP = 0, 1, 2, 3

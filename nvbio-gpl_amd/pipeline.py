@@ -512,14 +512,12 @@ def write_sam(file, header, text):
         f.write(body)
 
 
-def align_to_sam(fmi, genome2, genome_len, reads, params, names, refs, cigar_stride=32, mds_stride=64):
-    """Reads in, SAM records out, single-end: seed_and_extend -> traceback_best_all -> finish_alignment -> sam_records, every array
-    handed from step to step on the device; MAPQ and the second score (XS) are seed_and_extend's own (params.mapq is switched on for
-    the call).  names: the reads' QNAMEs; refs: the SamRefs of the genome.  reads are stored forward, as seed_and_extend takes them.
-    Returns (text uint8 tensor, offsets int64 tensor [R + 1], n_skipped, records): records is the SamRecords the text was printed from."""
+def _align_to_records(fmi, genome2, genome_len, reads, params, names, cigar_stride, mds_stride):
+    """the alignment part of align_to_sam and align_to_bam: seed_and_extend -> traceback_best_all -> finish_alignment -> the SamRecords
+    either format is made from, every array handed from step to step on the device"""
     import copy
     import torch
-    from . import SAM_ALIGNED, SAM_RC, SamRecords, finish_alignment, sam_records
+    from . import SAM_ALIGNED, SAM_RC, SamRecords, finish_alignment
     if not params.mapq:
         params = copy.copy(params)
         params.mapq = True
@@ -534,8 +532,25 @@ def align_to_sam(fmi, genome2, genome_len, reads, params, names, refs, cigar_str
     ed, mds, mds_lens = finish_alignment(batch, src, cig, ln, mds_stride)
     aligned = ln != 0
     state = aligned.to(torch.uint8) * SAM_ALIGNED | (aligned & (best_rc != 0)).to(torch.uint8) * SAM_RC
-    records = SamRecords(names, reads.reads4, batch.read_offsets, reads.read_len, state, pos.to(torch.int32), sc, ed, ex["mapq"], cig, ln, quals=reads.quals,
-                         second_score=ex["second_score"], mds=mds, mds_lens=mds_lens, reads_reversed=False, device=dev)
+    return SamRecords(names, reads.reads4, batch.read_offsets, reads.read_len, state, pos.to(torch.int32), sc, ed, ex["mapq"], cig, ln, quals=reads.quals,
+                      second_score=ex["second_score"], mds=mds, mds_lens=mds_lens, reads_reversed=False, device=dev)
+
+
+def _parse_forward(fmi, fastq_text, kw, who):
+    """parse_fastq with the reads stored forward (NO_OP), as the align_to_* functions take them"""
+    from . import FASTQ_NO_OP, NvbioError, parse_fastq
+    if kw.pop("strand_op", FASTQ_NO_OP) != FASTQ_NO_OP:
+        raise NvbioError(1, "%s stores the reads forward: strand_op must be FASTQ_NO_OP" % who)
+    return parse_fastq(fastq_text, strand_op=FASTQ_NO_OP, device=fmi.device, **kw)
+
+
+def align_to_sam(fmi, genome2, genome_len, reads, params, names, refs, cigar_stride=32, mds_stride=64):
+    """Reads in, SAM records out, single-end: seed_and_extend -> traceback_best_all -> finish_alignment -> sam_records, every array
+    handed from step to step on the device; MAPQ and the second score (XS) are seed_and_extend's own (params.mapq is switched on for
+    the call).  names: the reads' QNAMEs; refs: the SamRefs of the genome.  reads are stored forward, as seed_and_extend takes them.
+    Returns (text uint8 tensor, offsets int64 tensor [R + 1], n_skipped, records): records is the SamRecords the text was printed from."""
+    from . import sam_records
+    records = _align_to_records(fmi, genome2, genome_len, reads, params, names, cigar_stride, mds_stride)
     text, offsets, n_skipped = sam_records(refs, records)
     return text, offsets, n_skipped, records
 
@@ -545,11 +560,73 @@ def fastq_to_sam(fmi, genome2, genome_len, fastq_text, params, refs, cigar_strid
     takes them; kw: quality_encoding, truncate_len, max_records) then align_to_sam over the batch's own arrays and names -- a ragged
     batch when the reads differ in length.  Returns align_to_sam's (text, offsets, n_skipped, records) and the FastqBatch, whose status
     and consumed_bytes say how far the text was read."""
-    from . import FASTQ_NO_OP, NvbioError, parse_fastq
-    if kw.pop("strand_op", FASTQ_NO_OP) != FASTQ_NO_OP:
-        raise NvbioError(1, "fastq_to_sam stores the reads forward: strand_op must be FASTQ_NO_OP")
-    batch = parse_fastq(fastq_text, strand_op=FASTQ_NO_OP, device=fmi.device, **kw)
+    batch = _parse_forward(fmi, fastq_text, kw, "fastq_to_sam")
     return align_to_sam(fmi, genome2, genome_len, batch.read_batch(), params, batch.names, refs, cigar_stride=cigar_stride, mds_stride=mds_stride) + (batch,)
+
+
+def bam_header(refs, lengths=None, text=None):
+    """BamOutput::output_header (nvbio/io/output/output_bam.cpp:601-650) -> bytes: BAM\\1, l_text, text, n_ref, then l_name, name + NUL,
+    l_ref per sequence.  text: the SAM header text, by default the reference's @HD and @PG lines with no NUL behind them; pass
+    sam_header(...) for @SQ lines too.  refs: a SamRefs, or the sequence names with `lengths`."""
+    import struct
+    if lengths is None:
+        names, lengths = refs.names, np.diff(refs.sequence_index_host)
+    else:
+        names = refs
+    if text is None:
+        text = sam_header([], [])
+    text = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    names = [n if isinstance(n, bytes) else str(n).encode("latin-1") for n in names]
+    out = [b"BAM\1", struct.pack("<I", len(text)), text, struct.pack("<I", len(names))]
+    for n, l in zip(names, lengths):
+        out += [struct.pack("<I", len(n) + 1), n, b"\0", struct.pack("<I", int(l))]
+    return b"".join(out)
+
+
+def _bgzf_frame_host(data):
+    """nvbio_bgzf_frame's blocks for bytes that are on the host already (the header): stored DEFLATE blocks of at most 65280 bytes"""
+    import struct
+    import zlib
+    out = []
+    for at in range(0, len(data), 65280):
+        block = data[at:at + 65280]
+        out += [b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", struct.pack("<HBHH", len(block) + 30, 1, len(block), ~len(block) & 0xFFFF), block,
+                struct.pack("<II", zlib.crc32(block), len(block))]
+    return b"".join(out)
+
+
+def write_bam(file, header, data):
+    """A complete BAM file to `file` (a path or a binary file object): `header` (bytes, bam_header) as a BGZF block sequence of its own,
+    as the reference writes it (output_bam.cpp:647-649), the records as the next, and the EOF block.  data: the uint8 device tensor of
+    bam_records / align_to_bam, which is framed on the device (bgzf_frame) and crosses to the host in one copy, or bytes, which are on
+    the host already and are framed there, like the header."""
+    from . import BGZF_EOF, bgzf_frame
+    body = _bgzf_frame_host(bytes(data)) if isinstance(data, (bytes, bytearray)) else bgzf_frame(data).cpu().numpy().tobytes()
+    parts = [_bgzf_frame_host(bytes(header)), body, BGZF_EOF]
+    if hasattr(file, "write"):
+        for part in parts:
+            file.write(part)
+        return
+    with open(file, "wb") as f:
+        for part in parts:
+            f.write(part)
+
+
+def align_to_bam(fmi, genome2, genome_len, reads, params, names, refs, cigar_stride=32, mds_stride=64, flags=0):
+    """align_to_sam's counterpart: the same alignment steps, then bam_records.  flags: 0 or BAM_REG2BIN.
+    Returns (data uint8 tensor, offsets int64 tensor [R + 1], n_skipped, records): records is the SamRecords the bytes were made from."""
+    from . import bam_records
+    records = _align_to_records(fmi, genome2, genome_len, reads, params, names, cigar_stride, mds_stride)
+    data, offsets, n_skipped = bam_records(refs, records, flags)
+    return data, offsets, n_skipped, records
+
+
+def fastq_to_bam(fmi, genome2, genome_len, fastq_text, params, refs, cigar_stride=32, mds_stride=64, flags=0, **kw):
+    """fastq_to_sam's counterpart: parse_fastq (kw as there) then align_to_bam over the batch's own arrays and names.  Returns
+    align_to_bam's (data, offsets, n_skipped, records) and the FastqBatch."""
+    batch = _parse_forward(fmi, fastq_text, kw, "fastq_to_bam")
+    return align_to_bam(fmi, genome2, genome_len, batch.read_batch(), params, batch.names, refs, cigar_stride=cigar_stride, mds_stride=mds_stride,
+                        flags=flags) + (batch,)
 
 
 def reference_from_fasta(path, chunk_bytes=64 << 20, seed=11, device="cuda:0", **build_opts):
