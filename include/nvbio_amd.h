@@ -1613,6 +1613,9 @@ nvbio_status nvbio_full_sw_score(int device, nvbio_alignment_type type, int text
  * text is bounded by the LDS of a wave.  The bound is taken from the declared maxima:
  *   max_name_len + 2 * refs->max_name_len + 2 * max_read_len + 6 * cigar_stride + (2 * mds_stride + 16) + 192   bytes of text,
  *   plus 16 and mds_stride rounded up to 16, must not exceed 16384: else NVBIO_ERR_UNSUPPORTED, before any launch.
+ *   The term in brackets bounds the MD text of a well-formed MDS stream (at most 1.5 characters a byte).  A stream that mds_stride cuts,
+ *   or that ends, inside a deletion token can print more -- the missing bytes read as 0: up to 255 A's -- and a record that then does not
+ *   fit its LDS is refused with NVBIO_SAM_STATUS_TOO_LONG; one that fits is written whole.  The same holds for the BAM calls.
  * ------------------------------------------------------------------------------------------- */
 typedef struct
 {
@@ -1701,8 +1704,9 @@ nvbio_status nvbio_sam_format(int device, const nvbio_sam_refs* refs, const nvbi
  * A group of 16 lanes composes one record in LDS (four records to a wave) and copies it out with 16-byte stores (bytes only at the
  * unaligned head and tail), so a record is bounded by the LDS of a group.  The bound is taken from the declared maxima:
  *   max_name_len + 4 * cigar_stride + max_read_len + (max_read_len + 1) / 2 + (2 * mds_stride + 16) + 72   bytes of record
- *   (36 block_size and fixed fields, the name's NUL, 30 of NM AS XS XM XO XG, 4 of the MD tag's name, type and NUL; an MDS byte prints
- *   at most 1.5 characters; the term in brackets is 0 without mds_dev), plus 16 and mds_stride rounded up to 16, must not exceed
+ *   (36 block_size and fixed fields, the name's NUL, 30 of NM AS XS XM XO XG, 4 of the MD tag's name, type and NUL; an MDS byte of a
+ *   well-formed stream prints at most 1.5 characters -- a cut one can print more and ends in NVBIO_BAM_STATUS_TOO_LONG at worst, see the
+ *   SAM calls; the term in brackets is 0 without mds_dev), plus 16 and mds_stride rounded up to 16, must not exceed
  *   16384: else NVBIO_ERR_UNSUPPORTED, before any launch.  So are max_name_len > 254 (l_read_name is one byte and counts the NUL) and
  *   cigar_stride > 65535 (n_cigar_op has 16 bits).
  * Divergences from the reference:

@@ -14,10 +14,12 @@
 // The length kernel runs the same code with the stores compiled out (ByteOut<EMIT, 16>), so the two cannot disagree; the write kernel
 // still compares its own length with the caller's offsets and refuses a record that differs.
 //
-// Limit: a group's LDS holds BAM_LDS[k] bytes (at most 16384; a workgroup declares at most 64 KiB, so groups of 8192 / 16384 bytes come
-// 8 / 4 to a workgroup), of which 16 go to the residue and mds_stride (rounded up to 16) to the staged MDS stream.  The bound on a record:
+// Limit: a group's LDS holds BAM_LDS[k] bytes (at most 16384; a workgroup is kept to 64 KiB of static LDS -- a choice, the limit of the
+// CDNA parts before gfx950, which accepts more -- so groups of 8192 / 16384 bytes come 8 / 4 to a workgroup), of which 16 go to the residue and mds_stride (rounded up to 16) to the staged MDS stream.  The bound on a record:
 //   max_name_len + 4 * cigar_stride + max_read_len + (max_read_len + 1) / 2 + (2 * mds_stride + 16) + 72
-// A bound that does not fit is NVBIO_ERR_UNSUPPORTED before any launch.
+// A bound that does not fit is NVBIO_ERR_UNSUPPORTED before any launch.  The MD term (1.5 characters an MDS byte) holds for well-formed
+// streams; a stream cut inside a deletion token can print more (sam.hip says how), and then the record is whole where the class has
+// the room and NVBIO_BAM_STATUS_TOO_LONG where it has not: the stores are bounded either way.
 //
 // The BGZF kernel: one workgroup per block of 65280 payload bytes.  A lane loads 16-byte words of the (aligned) payload, a row of 256
 // words at a time; the payload lands at byte 23 of its block, so the destination's 16-byte words are cut from two source words each

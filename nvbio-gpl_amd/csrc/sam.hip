@@ -16,8 +16,14 @@
 // Limit: a wave's LDS holds SAM_LDS[k] bytes (at most 16384: four waves share the 64 KiB a workgroup may declare), of which 16 go to the
 // residue and mds_stride (rounded up to 16) to the staged MDS stream.  The bound on a record's text is derived on the host:
 //   max_name_len + 2 * refs->max_name_len + 2 * max_read_len + 6 * cigar_stride + (2 * mds_stride + 16) + 192
-// (a CIGAR element prints at most 5 digits and its op; an MDS byte prints at most 1.5 characters; 192 covers the tabs, the integer
-// fields at their widest and the tag names).  A bound that does not fit is NVBIO_ERR_UNSUPPORTED before any launch.
+// (a CIGAR element prints at most 5 digits and its op; an MDS byte of a well-formed stream prints at most 1.5 characters; 192 covers the
+// tabs, the integer fields at their widest and the tag names).  A bound that does not fit is NVBIO_ERR_UNSUPPORTED before any launch.
+// The MD term holds for well-formed streams only: md_walk reads a byte past the stream as 0, so a stream that mds_stride cuts (or that
+// ends) inside a deletion token [3, l, ...] still prints ^, l bases (A for the missing ones) and 0 -- up to 257 characters from two
+// bytes, which behind the densest well-formed prefix (1.2 characters a byte) passes 2 * mds_stride + 16 for strides below about 295.
+// Nothing unsafe follows: every LDS store is bounded by the class, the length kernel runs the same walk, and such a record is written
+// whole where the class has the room and is NVBIO_SAM_STATUS_TOO_LONG where it has not (tests/test_gpu_record_edges.py runs both).  The
+// formula stays as it is: widening it would move every caller up a class.
 #include "common.h"
 #include "record_common.h"
 #include <hipcub/hipcub.hpp>
