@@ -218,8 +218,9 @@ def test_seed_enumeration_and_diagonal_helpers(amd, orc, big):
 
 def test_hamming_backtrack(amd, orc, fm_golden, bt_golden):
     """nvbio_fm_hamming_backtrack: reference-quirks mode against the reference's own outputs (bt_golden.npz: counts, numbers
-    of ranges, ranges in delegate order), default mode against the oracle (itself checked against a brute-force Hamming scan),
-    2-bit, 4-bit and byte queries; then 20,000 queries on a larger index against the oracle"""
+    of ranges, ranges in delegate order), default mode against the oracle (itself checked against a brute-force Hamming scan):
+    counts, numbers of ranges and the first 48 ranges in delegate order; 2-bit, 4-bit and byte queries; then 20,000 queries on a
+    larger index against the oracle"""
     g, b = fm_golden, bt_golden
     fmi = _golden_dev_index(amd, g, 4)
     stream, offs = b["stream"], b["offs"].astype(np.uint32)
@@ -234,10 +235,13 @@ def test_hamming_backtrack(amd, orc, fm_golden, bt_golden):
             for i in range(Q):
                 k = min(int(b["n_ranges"][mi, i]), 48)
                 assert np.array_equal(got[i, :k], b["ranges"][mi, i, :k]), (bits, mi, i)
-            cnt, nr, _ = fmi.hamming_backtrack(qs, int(seed), int(mm))
-            want = [orc.hamming_backtrack(hidx, stream, int(offs[i]), int(offs[i + 1] - offs[i]), int(seed), int(mm))[:2] for i in range(Q)]
+            cnt, nr, rg = fmi.hamming_backtrack(qs, int(seed), int(mm), max_ranges=48)
+            want = [orc.hamming_backtrack(hidx, stream, int(offs[i]), int(offs[i + 1] - offs[i]), int(seed), int(mm), cap=48) for i in range(Q)]
             assert np.array_equal(amd.u32(cnt), np.array([w[0] for w in want], dtype=np.uint32))
             assert np.array_equal(amd.u32(nr), np.array([w[1] for w in want], dtype=np.uint32))
+            got = amd.u32(rg)
+            for i in range(Q):                                      # the ranges too, in delegate order
+                assert np.array_equal(got[i, :min(want[i][1], 48)], want[i][2]), (bits, mi, i, "default")
     fmi.close()
     rng = np.random.default_rng(8)
     G = 400000
@@ -254,10 +258,11 @@ def test_hamming_backtrack(amd, orc, fm_golden, bt_golden):
     qs = amd.PackedStringSet(orc.pack2(flat), 2, Q, offsets=offs, ranges=True)
     for seed, mm in ((16, 1), (14, 2)):
         for quirks in (False, True):
-            cnt, nr, _ = fmi.hamming_backtrack(qs, seed, mm, quirks=quirks)
-            cnt, nr = amd.u32(cnt), amd.u32(nr)
+            cnt, nr, rg = fmi.hamming_backtrack(qs, seed, mm, quirks=quirks, max_ranges=48)
+            cnt, nr, rg = amd.u32(cnt), amd.u32(nr), amd.u32(rg)
             for i in range(0, Q, 9):
-                c, n, _ = orc.hamming_backtrack(hidx, flat, int(offs[i]), L, seed, mm, quirks=quirks)
+                c, n, want_rg = orc.hamming_backtrack(hidx, flat, int(offs[i]), L, seed, mm, quirks=quirks, cap=48)
                 assert (int(cnt[i]), int(nr[i])) == (c, n), (seed, mm, quirks, i)
+                assert np.array_equal(rg[i, :min(n, 48)], want_rg), (seed, mm, quirks, i, "ranges")
         assert (cnt > 0).mean() > 0.5
     fmi.close()
