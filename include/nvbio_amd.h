@@ -793,7 +793,9 @@ nvbio_status nvbio_mapq_ragged(int device, const uint64_t* best_dev, const uint6
  *   ids_dev[e]        seed id of entry e, bit 31 = reverse strand (the convention of nvbio_fm_filter_locate_diagonals' query_ids_dev)
  *   keys_dev          room for n * cap keys; *n_keys_dev (device) = keys written
  *   read_offsets_dev / seed_intervals_dev   ragged reads (both or neither; then seed_interval and read_len are ignored)
- * Needs the full suffix array (sa_int = 1).  1 <= cap <= 64, n * cap < 2^31. */
+ * Needs the full suffix array (sa_int = 1).  1 <= cap <= 64, n * cap < 2^31.  A call refused for its arguments writes nothing, *n_keys_dev included.
+ * The ranges of real searches hold rows >= 1; row 0 (the empty suffix) is outside the contract: for it this call reports the position `length`,
+ * the two-call form ssa[0] + t. */
 nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uint2* ranges_dev, const uint32_t* ids_dev, uint32_t n, uint32_t cap,
                                          uint32_t seeds_per_read, uint32_t seed_interval, uint32_t seed_len, uint32_t read_len,
                                          const uint32_t* read_offsets_dev, const uint32_t* seed_intervals_dev,

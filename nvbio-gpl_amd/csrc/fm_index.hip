@@ -2002,8 +2002,7 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
     FMIndexImpl* idx = (FMIndexImpl*)index;
     DeviceGuard g( idx->device ); if (!g.ok) return NVBIO_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    NVB_HIP( hipMemsetAsync( n_keys_dev, 0, sizeof(uint32_t), s ) );
-    if (n == 0) return NVBIO_OK;
+    if (n == 0) { NVB_HIP( hipMemsetAsync( n_keys_dev, 0, sizeof(uint32_t), s ) ); return NVBIO_OK; }
     NVB_REQUIRE( ranges_dev && ids_dev && keys_dev, "NULL device pointer" );
     NVB_REQUIRE( cap >= 1u && cap <= 64u, "cap must be in 1..64" );
     NVB_REQUIRE( (uint64_t)n * cap < (1ull << 31), "n * cap must stay below 2^31" );
@@ -2016,6 +2015,7 @@ nvbio_status nvbio_fm_residual_diagonals(nvbio_fm_index_t index, const nvbio_uin
         set_error( "nvbio_fm_residual_diagonals needs the full suffix array: build the index with sa_int = 1" );
         return NVBIO_ERR_UNSUPPORTED;
     }
+    NVB_HIP( hipMemsetAsync( n_keys_dev, 0, sizeof(uint32_t), s ) );                          // (a refused call has written nothing, *n_keys_dev included)
     size_t sort_bytes = 0;
     NVB_HIP( hipcub::DeviceRadixSort::SortPairs( nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n, 0, 32, s ) );
     // scratch: sorted ids | sorted ranges | sort temp
